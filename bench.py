@@ -1,26 +1,40 @@
 #!/usr/bin/env python3
 """bench.py -- throughput of the successor-expansion hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload C4]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload C4] [--dump-outputs DIR] [--full]
 
 A "step" is one pass of the hot path (one mplx_expand_lists_device launch) over
 one synthetic frontier batch that is already resident in HBM.  The default
 workload is BASELINE.json configs[3], the one the metric is quoted on:
     C4 = 3D VoxelMapUtil 512^3, Control::ACC, |U| = 729, 64k-node frontier.
 
+A plain run does only what the headline needs: it sets up the workload, spins
+the clocks up, runs the W warm-up steps, times the K steps and prints the line
+(`value`, `ms_per_step` = wall milliseconds of one timed step, ...).  Everything
+else listed below -- roofline counts, the store-only model, the parity sample,
+the CPU baseline, the weak / all-gather legs of N > 1 and the extras of N = 1 --
+runs only with --full (which writes the long form to bench_detail.json).
+
+--dump-outputs DIR writes what the last timed step computed (rank 0's lists) as
+DIR/<name>.npy in float64, every value finite: count of every node, and for a
+fixed, seeded sample of nodes their successors' action, cost and blocked flag (a
+blocked successor's +inf cost is written as blocked = 1, cost = 0), hash (two
+exact 32-bit halves) and state.
+The workload is seeded, so the same arguments give the same inputs in every run.
+
 N > 1 (launched by torch.distributed.run, one rank per GPU): THE frontier of the
 workload is block-partitioned by node over the ranks (shard.partition; rank r
 expands nodes [r*N/G, (r+1)*N/G) against its own replica of the map) -- no
 data-path collective, so `value` = the workload's pairs / the
 slowest rank's time per step and scaling is "strong" (BASELINE configs[3]:
-"64k-node frontier, 1 -> 8 x MI355X shard").  The same run also reports
+"64k-node frontier, 1 -> 8 x MI355X shard").  With --full the same run also reports
   weak       every rank a full-size frontier of its own (per-GPU work fixed)
   allgather  the optional exchange for a consumer that needs the whole successor
              set on every GPU: lists packed on the device, all-gathered by RCCL
              over the engine's own buffers (shard.all_gather_packed)
 MPLX_BENCH_FORCE_DIST=1 runs that code path with a world of one.
 
-Rank 0 prints ONE JSON line (see the task contract) including
+Rank 0 prints ONE JSON line (see the task contract); with --full it includes
   roofline     : algorithmic bytes per launch / HIP-event kernel time vs 8 TB/s
   cpu_baseline : the reference's own headers compiled into oracle/_ref ("reference";
                  the CPU oracle, "port", when that build is absent) timed on this
@@ -142,6 +156,45 @@ def count_work(env, frontier, n_nodes):
     st = v["status"]
     return (int(np.count_nonzero((st == 1) | (st == 2))), int(np.count_nonzero(st == 1)),
             int(v["iters"].sum(dtype=np.int64)))
+
+
+DUMP_SEED, DUMP_NODES, DUMP_MAX_BYTES = 20240611, 256, 64 * 1024 * 1024
+
+
+def dump_outputs(lists, n_nodes, out_dir, node_offset=0):
+    """What the last launch wrote into `lists`, as float64 .npy files under out_dir (--dump-outputs): `count` of every
+    node, and for DUMP_NODES nodes drawn with a fixed seed (`sample_nodes`, frontier indices) their successors one after
+    another -- `action`, `cost`, `blocked`, `hash_hi` / `hash_lo` (the 64-bit lattice hash in two exact halves) and
+    `state` (entries x 4D+2).  Entries past a node's count are never read: only what a caller of the lists receives.
+    Every value written is finite: the lists mark a blocked successor with cost +inf, which is written as blocked = 1
+    and cost = 0 (finite successors: blocked = 0 and their cost)."""
+    os.makedirs(out_dir, exist_ok=True)
+    count = lists.count.download(np.int32, (n_nodes,))
+    per_node = lists.stride * (lists.n_fields + 4) * 8
+    k = int(min(n_nodes, DUMP_NODES, max(1, (DUMP_MAX_BYTES - 16 * n_nodes) // per_node)))
+    pick = np.sort(np.random.default_rng(DUMP_SEED).choice(n_nodes, size=k, replace=False))
+    rows = {"action": [], "cost": [], "hash": [], "state": []}
+    for i in pick:
+        got = lists.download_nodes(i, i + 1)
+        c = int(count[i])
+        rows["action"].append(got["action"][:c])
+        rows["cost"].append(got["cost"][:c])
+        rows["hash"].append(got["hash"][:c] if "hash" in got else np.zeros(c, np.uint64))
+        rows["state"].append(got["state"][:, :c].T if "state" in got else np.zeros((c, 0)))
+    h = np.concatenate(rows["hash"]).astype(np.uint64)
+    cost = np.concatenate(rows["cost"])
+    blocked = ~np.isfinite(cost)
+    arrays = {"count": count, "sample_nodes": pick + node_offset, "action": np.concatenate(rows["action"]),
+              "cost": np.where(blocked, 0.0, cost), "blocked": blocked, "hash_hi": h >> np.uint64(32),
+              "hash_lo": h & np.uint64(0xFFFFFFFF), "state": np.concatenate(rows["state"])}
+    arrays = {name: np.ascontiguousarray(a, dtype=np.float64) for name, a in arrays.items()}
+    for name, a in arrays.items():
+        if not np.all(np.isfinite(a)):
+            raise RuntimeError("--dump-outputs: %d non-finite values in %s" % (int(np.count_nonzero(~np.isfinite(a))), name))
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {"dir": out_dir, "files": sorted(n + ".npy" for n in arrays), "sample_nodes": k,
+            "entries": int(arrays["cost"].size)}
 
 
 def time_lists(env, frontier, lists, steps, warmup):
@@ -811,7 +864,8 @@ def _r(x, sig=5):
 
 def compact_line(out, detail_path):
     """The ONE JSON line of the contract, from the long form: the contract's keys, `roofline`, `cpu_baseline`, and of every
-    extra leg its numbers only -- no prose, no per-call lists.  Everything else is in the detail file."""
+    extra leg its numbers only -- no prose, no per-call lists.  Everything else is in the detail file (detail_path None:
+    a plain run, which writes none)."""
     keep = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
             "dtype", "data")
     line = {k: (_r(out[k], 7) if k in ("value", "ms_per_step") else out[k]) for k in keep if k in out}
@@ -819,16 +873,19 @@ def compact_line(out, detail_path):
     line["config"] = {k: cfg[k] for k in ("workload", "frontier", "frontier_nodes", "frontier_nodes_per_gpu", "controls", "dim",
                                           "pairs_per_step", "map_cells", "device", "compute_units") if k in cfg}
     line["config"]["kernel"] = str(cfg.get("kernel", "")).split(" ")[0]
-    rf = out.get("roofline", {})
-    line["roofline"] = {k: _r(rf.get(k), 6) for k in ("bound", "achieved", "peak", "unit", "frac", "traffic", "kernel_ms",
-                                                      "algorithmic_bytes_per_launch", "issue_frac", "store_only_ms",
-                                                      "kernel_over_store_only", "emitted", "map_samples")}
+    if "roofline" in out:  # (--full)
+        rf = out["roofline"]
+        line["roofline"] = {k: _r(rf.get(k), 6) for k in ("bound", "achieved", "peak", "unit", "frac", "traffic", "kernel_ms",
+                                                          "algorithmic_bytes_per_launch", "issue_frac", "store_only_ms",
+                                                          "kernel_over_store_only", "emitted", "map_samples")}
     for k in ("ms_per_step_events", "value_events", "parity_sample_ok", "speedup_vs_cpu_all_cores",
               "speedup_vs_cpu_all_cores_e2e_host_pointers", "speedup_vs_cpu_all_cores_e2e_edges_only", "map_broadcast_ms"):
         if k in out:
             line[k] = _r(out[k])
     if "rank_kernel_ms" in out and out.get("n_gpus", 1) > 1:
         line["rank_kernel_ms"] = out["rank_kernel_ms"]
+    if isinstance(out.get("dumped_outputs"), dict):
+        line["dumped_outputs"] = {k: out["dumped_outputs"][k] for k in ("dir", "sample_nodes", "entries")}
 
     def cpu(cb):
         if not isinstance(cb, dict) or "value" not in cb:
@@ -919,7 +976,8 @@ def compact_line(out, detail_path):
                     e[k] = _r(v, 4)
             pl[name] = e
         line["plan"] = pl
-    line["detail"] = detail_path
+    if detail_path is not None:
+        line["detail"] = detail_path
     # a hard ceiling, whatever a leg grows into: optional subtrees go (they stay in the detail file) until the line fits
     for path in (("wavefront", "post"), ("wavefront", "post_fused"), ("allgather",), ("plan", "replan_3D"), ("edges_only",)):
         if len(json.dumps(line, separators=(",", ":"))) <= 7800:
@@ -957,8 +1015,15 @@ def main():
                          "allocation that is timed: a fresh process's first allocation and one that reuses freed memory "
                          "land in different placement modes about half the time (profiles/README.md) -- "
                          "profiles/run_round6_modes.sh uses it to get a trace of BOTH modes from the same binary")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip e2e / wavefront / other_configs / plan (N = 1 only)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: roofline (work counts, store-only model), parity sample of the "
+                         "timed lists against the oracle, CPU baseline, the weak / all-gather legs (N > 1), the extras "
+                         "(N = 1) and the long form in bench_detail.json.  Off: set up, warm up, time, print the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float64; see "
+                         "dump_outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip e2e / wavefront / other_configs / plan (N = 1 only)")
     ap.add_argument("--frontier", default="random", choices=["random", "wavefront"],
                     help="random: SURVEY 8(d)'s uniformly scattered frontier (the headline); wavefront: the open list of "
                          "an eps = 0 search from the map centre (realistic locality; also reported as an extra)")
@@ -976,10 +1041,11 @@ def main():
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # Plain `python bench.py --gpus N`: become the launcher -- one rank per GPU under torch.distributed.run on
-        # this node, rendezvous on 127.0.0.1 (the container hostname may not resolve), same arguments.  exec, so the
-        # exit status and rank 0's one JSON line are the launcher's.  (Under an external launcher WORLD_SIZE is set
-        # and this is skipped.)
+        # this node, rendezvous on 127.0.0.1 (the container hostname may not resolve), same arguments.  A child
+        # process whose exit status this one returns, and rank 0's one JSON line goes to the shared stdout.  (Under an
+        # external launcher WORLD_SIZE is set and this is skipped.)
         import socket
+        import subprocess
         s_ = socket.socket()
         s_.bind(("127.0.0.1", 0))
         port = s_.getsockname()[1]
@@ -994,7 +1060,7 @@ def main():
                 sys.exit("bench.py: --gpus %d needs %d GPUs, %d visible (self-launch prepared: %s)"
                          % (args.gpus, args.gpus, torch.cuda.device_count(), " ".join(cmd[1:8])))
         sys.stdout.flush()
-        os.execv(sys.executable, cmd)
+        sys.exit(subprocess.call(cmd))
     if world != args.gpus:
         args.gpus = world
 
@@ -1117,9 +1183,10 @@ def main():
     launch = lambda: env.expand_lists_resident(frontier, slots)
     dev_name, cus = env.device_info()
 
-    # ---- one untimed verification launch: counts for the algorithmic bytes of THIS rank's launch
-    n_emit, n_finite, n_samples = count_work(env, frontier, n_loc)
-    b_alg = algorithmic_bytes(wl, n_loc, n_emit, n_samples)
+    # ---- (--full) one untimed verification launch: counts for the algorithmic bytes of THIS rank's launch
+    if args.full:
+        n_emit, n_finite, n_samples = count_work(env, frontier, n_loc)
+        b_alg = algorithmic_bytes(wl, n_loc, n_emit, n_samples)
 
     def barrier():
         if distributed:
@@ -1206,13 +1273,17 @@ def main():
     rank_kernel_ms = list(timed.per_rank_ms)
     note("timed region done: %.3f ms per step" % (elapsed / args.steps * 1e3))
     route = env.last_lists_route()
+    dumped = None
+    if args.dump_outputs and rank == 0:  # (before anything below overwrites the lists)
+        dumped = dump_outputs(slots, n_loc, args.dump_outputs, node_offset=lo)
+        note("outputs written: %s" % (dumped,))
 
     # ---- parity of the TIMED output: the lists the timed launches wrote, against the oracle
-    timed_head = slots.download_nodes(0, min(n_loc, 512)) if rank == 0 else None
+    timed_head = slots.download_nodes(0, min(n_loc, 512)) if rank == 0 and args.full else None
     # ---- the list stores of that launch on their own, into the SAME allocation (mplx_debug_store_model overwrites the
     # entries: the head has just been taken): what the launch costs when its arithmetic is free
     store_only_ms = None
-    if rank == 0 and not distributed:  # (at N > 1 the gather leg still reads these lists)
+    if rank == 0 and not distributed and args.full:  # (at N > 1 the gather leg still reads these lists)
         try:
             for _ in range(5):
                 env.debug_store_model(slots, n_loc)
@@ -1225,7 +1296,7 @@ def main():
             note("store model not timed: %s" % e)
 
     weak = gather = None
-    if distributed:
+    if distributed and args.full:
         # ---- weak scaling: every rank a full-size frontier of its own
         def weak_frontier(r):
             return wl.nodes if r == 0 else m.workloads.random_frontier(
@@ -1316,7 +1387,7 @@ def main():
         tot = torch.tensor([n_emit, n_samples], dtype=torch.float64, device="cuda")
         dist.all_reduce(tot, op=dist.ReduceOp.SUM)
         n_emit_all, n_samples_all = int(tot[0].item()), int(tot[1].item())
-    else:
+    elif args.full:
         n_emit_all, n_samples_all = n_emit, n_samples
 
     if rank == 0:
@@ -1327,7 +1398,6 @@ def main():
         # N = 1 definition or with earlier rounds); the slowest rank's HIP-event time is reported beside it.
         ms_per_step = ms_wall
         out_kernel = kernel_name(env, route)
-        achieved = b_alg / (kernel_ms * 1e-3) / 1e9
         out = {
             "metric": "node-expansions/s (frontier x |U| pair evaluations per second)",
             "value": float(N) * nU / (ms_per_step * 1e-3),
@@ -1362,7 +1432,13 @@ def main():
                 "kernel": "expand_lex_kernel (per-axis factorised tables in LDS, lexicographic control table)" if out_kernel == "expand_lex_kernel" else {"grid": "expand_grid_kernel (per-axis factorised tables in LDS)", "tile": "expand_tile_kernel",
                            "dense": "expand_kernel + compact_lists_kernel", "none": "expand_kernel"}[route],
             },
-            "roofline": {
+        }
+        out.update({k: v for k, v in stats.items()})
+        if dumped is not None:
+            out["dumped_outputs"] = dumped
+        if args.full:  # (a plain run stops at the headline)
+            achieved = b_alg / (kernel_ms * 1e-3) / 1e9
+            out["roofline"] = {
                 "bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                 "frac": achieved / HBM_PEAK_GBS,
                 "traffic": measured_traffic(args.workload, out_kernel) if world == 1 and args.frontier == "random" else None,
@@ -1392,55 +1468,53 @@ def main():
                 "launch": "rank 0's launch: %d nodes" % n_loc,
                 "emitted": n_emit, "finite": n_finite, "map_samples": n_samples,
                 "emitted_all_ranks": n_emit_all, "map_samples_all_ranks": n_samples_all,
-            },
-        }
-        out.update({k: v for k, v in stats.items()})
-        if weak is not None:
-            out["weak"] = weak
-        if gather is not None:
-            out["allgather"] = gather
-        if not args.no_cpu_baseline and world == 1:
-            cb, oenv, n_chk = cpu_baseline(wl)
-            out["cpu_baseline"] = cb
-            out["speedup_vs_cpu_all_cores"] = out["value"] / cb["value"]
-        # the lists the TIMED launches wrote (first <= 512 nodes of rank 0) against the oracle: same successors, same
-        # order, bit-identical hash and state, cost exact (1e-6 for yaw controls: trig in the per-sample cost)
-        try:
-            from oracle import compare as OC
-            from oracle import oracle as O
-            oenv = O.Env(wl.dim, wl.control, wl.U, wl.grid, wl.map_dim, wl.origin, wl.res,
-                         potential=wl.potential, region=wl.region, **wl.params)
-            n_chk = min(n_loc, 512)
-            use_ref = os.path.exists(O.REF_SO)
-            ref = O.expand(oenv, my_nodes[:, :n_chk], threads=os.cpu_count() or 1, ref=use_ref)
-            problems = OC.lists_mismatches(timed_head, ref, n_chk, nU, cost_rtol=1e-6 if wl.control & 0x10 else 0.0)
-            out["parity_sample_ok"] = not problems
-            out["parity_sample"] = {"what": "lists written by the timed %s launches, first %d nodes, vs %s" % (
-                out_kernel, n_chk, "oracle/_ref (reference headers)" if use_ref else "the oracle"), "problems": problems}
-        except Exception as e:  # noqa: BLE001
-            out["parity_sample_ok"] = False
-            out["parity_sample"] = {"error": "%s: %s" % (type(e).__name__, e)}
-        if world == 1 and not distributed and not args.no_extras and args.scale == 1.0 and args.nodes is None:
-            slots.free()
-            frontier.free()
-            env.close()
-            env = None
-            extras(m, args, wl, out)
-            if "cpu_baseline" in out and isinstance(out.get("e2e"), dict) and "e2e_pairs_per_s" in out["e2e"]:
-                # BASELINE's ">= 100 x the CPU" holds for lists that stay in HBM (`value`) and for an on-device consumer;
-                # through host pointers the PCIe link is the bound and the ratio is this one
-                out["speedup_vs_cpu_all_cores_e2e_host_pointers"] = out["e2e"]["e2e_pairs_per_s"] / out["cpu_baseline"]["value"]
-                if isinstance(out.get("edges_only"), dict) and "e2e_pairs_per_s" in out["edges_only"]:
-                    out["speedup_vs_cpu_all_cores_e2e_edges_only"] = out["edges_only"]["e2e_pairs_per_s"] / out["cpu_baseline"]["value"]
-                if isinstance(out.get("wavefront"), dict) and "ratio_to_random" in out["wavefront"]:
-                    out["wavefront_ratio_to_random"] = out["wavefront"]["ratio_to_random"]
-                    pst = out["wavefront"].get("post") or {}
-                    if isinstance(pst.get("random"), dict) and isinstance(pst.get("wavefront"), dict):
-                        out["post_identity_ms"] = {"random": pst["random"]["identity_ms"], "wavefront": pst["wavefront"]["identity_ms"],
-                                                   "form": pst["random"]["identity_form"]}
-                out["speedup_note"] = ("speedup_vs_cpu_all_cores: HBM-resident lists (the metric's configuration); "
-                                       "..._e2e_host_pointers: the same batch through mplx_expand_lists on pageable host "
-                                       "arrays, bound by the PCIe link (2.8 GB of list entries per step)")
+            }
+            if weak is not None:
+                out["weak"] = weak
+            if gather is not None:
+                out["allgather"] = gather
+            if not args.no_cpu_baseline and world == 1:
+                cb, oenv, n_chk = cpu_baseline(wl)
+                out["cpu_baseline"] = cb
+                out["speedup_vs_cpu_all_cores"] = out["value"] / cb["value"]
+            # the lists the TIMED launches wrote (first <= 512 nodes of rank 0) against the oracle: same successors, same
+            # order, bit-identical hash and state, cost exact (1e-6 for yaw controls: trig in the per-sample cost)
+            try:
+                from oracle import compare as OC
+                from oracle import oracle as O
+                oenv = O.Env(wl.dim, wl.control, wl.U, wl.grid, wl.map_dim, wl.origin, wl.res,
+                             potential=wl.potential, region=wl.region, **wl.params)
+                n_chk = min(n_loc, 512)
+                use_ref = os.path.exists(O.REF_SO)
+                ref = O.expand(oenv, my_nodes[:, :n_chk], threads=os.cpu_count() or 1, ref=use_ref)
+                problems = OC.lists_mismatches(timed_head, ref, n_chk, nU, cost_rtol=1e-6 if wl.control & 0x10 else 0.0)
+                out["parity_sample_ok"] = not problems
+                out["parity_sample"] = {"what": "lists written by the timed %s launches, first %d nodes, vs %s" % (
+                    out_kernel, n_chk, "oracle/_ref (reference headers)" if use_ref else "the oracle"), "problems": problems}
+            except Exception as e:  # noqa: BLE001
+                out["parity_sample_ok"] = False
+                out["parity_sample"] = {"error": "%s: %s" % (type(e).__name__, e)}
+            if world == 1 and not distributed and not args.no_extras and args.scale == 1.0 and args.nodes is None:
+                slots.free()
+                frontier.free()
+                env.close()
+                env = None
+                extras(m, args, wl, out)
+                if "cpu_baseline" in out and isinstance(out.get("e2e"), dict) and "e2e_pairs_per_s" in out["e2e"]:
+                    # BASELINE's ">= 100 x the CPU" holds for lists that stay in HBM (`value`) and for an on-device consumer;
+                    # through host pointers the PCIe link is the bound and the ratio is this one
+                    out["speedup_vs_cpu_all_cores_e2e_host_pointers"] = out["e2e"]["e2e_pairs_per_s"] / out["cpu_baseline"]["value"]
+                    if isinstance(out.get("edges_only"), dict) and "e2e_pairs_per_s" in out["edges_only"]:
+                        out["speedup_vs_cpu_all_cores_e2e_edges_only"] = out["edges_only"]["e2e_pairs_per_s"] / out["cpu_baseline"]["value"]
+                    if isinstance(out.get("wavefront"), dict) and "ratio_to_random" in out["wavefront"]:
+                        out["wavefront_ratio_to_random"] = out["wavefront"]["ratio_to_random"]
+                        pst = out["wavefront"].get("post") or {}
+                        if isinstance(pst.get("random"), dict) and isinstance(pst.get("wavefront"), dict):
+                            out["post_identity_ms"] = {"random": pst["random"]["identity_ms"], "wavefront": pst["wavefront"]["identity_ms"],
+                                                       "form": pst["random"]["identity_form"]}
+                    out["speedup_note"] = ("speedup_vs_cpu_all_cores: HBM-resident lists (the metric's configuration); "
+                                           "..._e2e_host_pointers: the same batch through mplx_expand_lists on pageable host "
+                                           "arrays, bound by the PCIe link (2.8 GB of list entries per step)")
 
     if env is not None:
         slots.free()
@@ -1458,10 +1532,12 @@ def main():
     if rank == 0:
         # The long form (every leg with its prose, per-call times, the plans' timing splits) goes to a file; the ONE line
         # on stdout is numbers only and stays under 8 KB, so that a record which keeps the tail of stdout keeps all of it.
-        detail_path = os.environ.get("MPLX_BENCH_DETAIL", os.path.join(ROOT, "bench_detail.json"))
+        # (A plain run's line is all there is: no detail file.)
+        detail_path = os.environ.get("MPLX_BENCH_DETAIL", os.path.join(ROOT, "bench_detail.json")) if args.full else None
         try:
-            with open(detail_path, "w") as f:
-                json.dump(out, f, indent=1)
+            if detail_path:
+                with open(detail_path, "w") as f:
+                    json.dump(out, f, indent=1)
         except OSError as e:
             detail_path = "not written: %s" % e
         line = compact_line(out, detail_path)

@@ -4,7 +4,7 @@
 # against the in-tree library and profiles/micro/ab_old/libmplx.so, at several resident-wave caps.
 run() {  # lib workload cap
   local lib=$1 w=$2 cap=$3
-  MPLX_LIB=$lib MPLX_GRID_WAVES_PER_CU=$cap MPLX_GRID_VERBOSE=1 python bench.py --workload $w --no-extras --no-cpu-baseline --steps 50 --warmup 5 2>/tmp/occ_err.txt | tail -1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('$(basename $lib) $w cap=$cap kernel_ms=%.4f parity=%s' % (d['roofline']['kernel_ms'], d['parity_sample_ok']), end=' | ')"
+  MPLX_LIB=$lib MPLX_GRID_WAVES_PER_CU=$cap MPLX_GRID_VERBOSE=1 python bench.py --full --workload $w --no-extras --no-cpu-baseline --steps 50 --warmup 5 2>/tmp/occ_err.txt | tail -1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('$(basename $lib) $w cap=$cap kernel_ms=%.4f parity=%s' % (d['roofline']['kernel_ms'], d['parity_sample_ok']), end=' | ')"
   grep "mplx: grid" /tmp/occ_err.txt | head -1
 }
 NEW=motion_primitive_library_amd/csrc/libmplx.so

@@ -2,7 +2,7 @@
 # Occupancy / LDS sweep of the factorised kernel on the small configurations (run through gpurun):
 #   profiles/micro/occupancy_sweep.sh > gpurun_out/occ_sweep.txt
 # kernel_ms of `bench.py --workload W` for caps on resident waves per CU and rows per pass.
-B="python bench.py --no-extras --no-cpu-baseline --steps 30 --warmup 5"
+B="python bench.py --full --no-extras --no-cpu-baseline --steps 30 --warmup 5"
 for W in C5 C3 C2; do
   for WPC in 0 16 20 24 28 32; do
     for RMAX in 0 2 1; do

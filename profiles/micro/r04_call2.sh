@@ -3,9 +3,9 @@
 # (does the wavefront leg reproduce 0.9 ms?); the wavefront frontier as the headline frontier
 O=gpurun_out/r04_call2; mkdir -p $O
 timeout 300 python profiles/micro/c4_ablation.py $O/ablation_first_alloc.json > $O/ablation.log 2>&1
-timeout 600 python bench.py > $O/bench_head.json 2> $O/bench_head.err
-timeout 300 python bench.py --frontier wavefront --no-extras --no-cpu-baseline > $O/bench_wavefront.json 2> $O/bench_wavefront.err
-timeout 300 python bench.py --frontier wavefront --no-extras --no-cpu-baseline --placement-trials 1 > $O/bench_wavefront_p1.json 2> $O/bench_wavefront_p1.err
+timeout 600 python bench.py --full > $O/bench_head.json 2> $O/bench_head.err
+timeout 300 python bench.py --full --frontier wavefront --no-extras --no-cpu-baseline > $O/bench_wavefront.json 2> $O/bench_wavefront.err
+timeout 300 python bench.py --full --frontier wavefront --no-extras --no-cpu-baseline --placement-trials 1 > $O/bench_wavefront_p1.json 2> $O/bench_wavefront_p1.err
 for i in 1 2; do timeout 200 python profiles/micro/placement_table.py 8 >> $O/placement.txt 2>> $O/placement.err; done
 tail -c 600 $O/ablation.log; python - <<'PY'
 import json

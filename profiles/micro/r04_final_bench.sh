@@ -3,9 +3,9 @@
 # C4 (headline) and C3 (changed last: four samples per step)
 export TMPDIR=/tmp
 OUT=$PWD/gpurun_out/r04_close; mkdir -p $OUT
-python bench.py > $OUT/bench.json 2> $OUT/bench.err
+python bench.py --full > $OUT/bench.json 2> $OUT/bench.err
 for W in C4 C3; do
-  rocprofv3 --kernel-trace --stats -f csv -d $OUT/kt_$W -o kt -- python bench.py --no-extras --no-cpu-baseline --workload $W --steps 20 --warmup 5 > $OUT/kt_$W.log 2>&1
+  rocprofv3 --kernel-trace --stats -f csv -d $OUT/kt_$W -o kt -- python bench.py --full --no-extras --no-cpu-baseline --workload $W --steps 20 --warmup 5 > $OUT/kt_$W.log 2>&1
   cp $(find $OUT/kt_$W -name "*kernel_stats.csv" | head -1) $OUT/${W}_kernel_stats.csv
   rm -rf $OUT/kt_$W
 done

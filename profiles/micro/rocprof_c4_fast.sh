@@ -4,7 +4,7 @@
 export TMPDIR=/tmp
 for i in 1 2 3; do
   OUT=$PWD/gpurun_out/kt_fast_$i; rm -rf $OUT; mkdir -p $OUT
-  timeout -s KILL 150 rocprofv3 --kernel-trace --stats -f csv -d $OUT -o kt -- python bench.py --gpus 1 --steps 20 --warmup 5 --no-extras --no-cpu-baseline > $OUT/run.log 2>&1
+  timeout -s KILL 150 rocprofv3 --kernel-trace --stats -f csv -d $OUT -o kt -- python bench.py --full --gpus 1 --steps 20 --warmup 5 --no-extras --no-cpu-baseline > $OUT/run.log 2>&1
   grep '^{"metric"' $OUT/run.log > $OUT/bench.json
   python - <<PY
 import csv, glob, json

@@ -3,7 +3,7 @@
 export TMPDIR=/tmp
 OUT=$PWD/gpurun_out/${1:-small_traffic}; mkdir -p $OUT
 for W in C2 C3 C5; do for c in FETCH_SIZE WRITE_SIZE; do
-  timeout -s KILL 200 rocprofv3 --pmc $c -f csv -d $OUT/${W}_$c -o p -- python bench.py --no-extras --no-cpu-baseline --workload $W --steps 3 --warmup 1 --placement-trials 1 --spinup-ms 0 > $OUT/${W}_$c.json 2> $OUT/${W}_$c.err
+  timeout -s KILL 200 rocprofv3 --pmc $c -f csv -d $OUT/${W}_$c -o p -- python bench.py --full --no-extras --no-cpu-baseline --workload $W --steps 3 --warmup 1 --placement-trials 1 --spinup-ms 0 > $OUT/${W}_$c.json 2> $OUT/${W}_$c.err
 done; done
 python - $OUT <<'PY'
 import csv, glob, json, sys

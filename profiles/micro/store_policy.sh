@@ -21,7 +21,7 @@ else
   for rep in 1 2; do
     for name in builtin_nt asm_nt asm_plain asm_sc1 asm_sc0sc1 asm_sc0sc1nt asm_sc1nt; do
       cp profiles/micro/st_variants/$name/libmplx.so $CS/libmplx.so
-      python bench.py --no-cpu-baseline --steps 50 --warmup 5 2>/dev/null | tail -1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('$name', d['roofline']['kernel_ms'])"
+      python bench.py --full --no-cpu-baseline --steps 50 --warmup 5 2>/dev/null | tail -1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('$name', d['roofline']['kernel_ms'])"
     done
   done
   cp /tmp/keep.so $CS/libmplx.so

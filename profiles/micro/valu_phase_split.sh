@@ -4,7 +4,7 @@
 # -> sample loops = d0 - d32, rows + pass set-up + staging = d32 - d1, list stores = d1 - d7, the rest = d7
 OUT=$PWD/gpurun_out/valu_phase; mkdir -p $OUT; export TMPDIR=/tmp
 for W in ${@:-C3 C2 C5 C4}; do for DBG in 0 32 1 7; do
-  MPLX_TILE_DBG=$DBG timeout -s KILL 200 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM -f csv -d $OUT/${W}_$DBG -o p -- python bench.py --no-extras --no-cpu-baseline --workload $W --steps 3 --warmup 1 --placement-trials 1 --spinup-ms 0 > $OUT/${W}_$DBG.log 2>&1
+  MPLX_TILE_DBG=$DBG timeout -s KILL 200 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM -f csv -d $OUT/${W}_$DBG -o p -- python bench.py --full --no-extras --no-cpu-baseline --workload $W --steps 3 --warmup 1 --placement-trials 1 --spinup-ms 0 > $OUT/${W}_$DBG.log 2>&1
   python - $OUT/${W}_$DBG $W $DBG <<'PY'
 import csv, collections, glob, sys
 agg = collections.defaultdict(list)

@@ -5,7 +5,7 @@
 #  profiles/ by hand.
 set -u
 TAG=${1:-r2prof}; OUT=$PWD/gpurun_out/$TAG; mkdir -p "$OUT"; export TMPDIR=/tmp
-B="python bench.py --no-extras --no-cpu-baseline"
+B="python bench.py --full --no-extras --no-cpu-baseline"
 for W in C4 C2 C3 C5; do
   rocprofv3 --kernel-trace --stats -f csv -d "$OUT/kt_$W" -o kt -- $B --workload $W --steps 20 --warmup 5 > "$OUT/kt_$W.log" 2>&1
   rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM SQ_INSTS_SMEM SQ_WAVE_CYCLES SQ_BUSY_CYCLES -f csv -d "$OUT/p1_$W" -o p1 -- $B --workload $W --steps 3 --warmup 1 > "$OUT/p1_$W.log" 2>&1

@@ -6,7 +6,7 @@
 # Writes gpurun_out/<tag>/r05_counters.json (copied to profiles/ by hand) + the CSVs.
 set -u
 TAG=${1:-r05ctr}; OUT=$PWD/gpurun_out/$TAG; mkdir -p "$OUT/csv"; export TMPDIR=/tmp
-B="python bench.py --no-extras --no-cpu-baseline"
+B="python bench.py --full --no-extras --no-cpu-baseline"
 for W in ${WL:-C4 C2 C3 C5}; do
   rocprofv3 --kernel-trace --stats -f csv -d "$OUT/kt_$W" -o kt -- $B --workload $W --steps 20 --warmup 5 > "$OUT/bench_${W}_under_rocprof.json" 2> "$OUT/kt_$W.err"
   rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM SQ_WAVES -f csv -d "$OUT/sq_$W" -o sq -- $B --workload $W --steps 3 --warmup 1 > "$OUT/sq_$W.log" 2>&1

@@ -9,7 +9,7 @@ fast=0; slow=0
 for cyc in 0 1 2 3 4 5 0 2; do
   D="$OUT/try_${cyc}_$RANDOM"; mkdir -p "$D"
   MPLX_BENCH_DETAIL="$D/bench_detail.json" rocprofv3 --kernel-trace --stats -f csv -d "$D/kt" -o kt -- \
-      python bench.py --no-extras --no-cpu-baseline --prealloc-cycles $cyc > "$D/bench_line.json" 2> "$D/err.txt"
+      python bench.py --full --no-extras --no-cpu-baseline --prealloc-cycles $cyc > "$D/bench_line.json" 2> "$D/err.txt"
   ms=$(python -c "import json,sys; print(json.loads([l for l in open('$D/bench_line.json') if l.startswith('{')][-1])['roofline']['kernel_ms'])" 2>/dev/null || echo 0)
   for f in $(find "$D/kt" -name '*kernel_stats.csv'); do cp "$f" "$D/kernel_stats.csv"; done
   mode=$(python -c "ms=float('$ms'); print('fast' if 0 < ms < 0.505 else ('slow' if ms > 0.525 else 'between'))")

@@ -146,7 +146,7 @@ def test_bench_two_ranks_share_the_gpu_over_gloo(tmp_path, launcher):
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     tail = [os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-            "--workload", "C4", "--scale", "0.25", "--nodes", "6001"]
+            "--workload", "C4", "--scale", "0.25", "--nodes", "6001", "--full"]
     launchers = {"external": [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                               "--master-addr", "127.0.0.1", "--master-port", str(port)],
                  "self": [sys.executable]}  # plain `python bench.py --gpus 2`: bench.py becomes the launcher itself
