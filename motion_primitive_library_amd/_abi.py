@@ -31,6 +31,11 @@ SYMBOLS = [
     "mplx_selftest_math", "mplx_selftest_forward_state", "mplx_set_lists_route", "mplx_last_lists_route", "mplx_last_grid_kernel", "mplx_last_identity_form", "mplx_debug_store_model", "mplx_yaw_pin_stats", "mplx_service", "mplx_device_info",
 ]
 
+# the symbols include/mplx_map_util.h declares (MapUtil's dilate / freeUnknown / freeAll / clouds on the device map),
+# exported by the same library; kept apart from SYMBOLS, which is exactly mplx.h + mplx_debug.h
+MAP_UTIL_SYMBOLS = ["mplx_map_dilate", "mplx_map_free", "mplx_map_cloud"]
+CELL_OCCUPIED, CELL_FREE, CELL_UNKNOWN = 0, 1, 2
+
 ROUTE_AUTO, ROUTE_DENSE, ROUTE_TILE, ROUTE_GRID = 0, 1, 2, 3
 
 
@@ -212,8 +217,11 @@ def lib():
         "mplx_yaw_pin_stats": (C.c_int, [vp, C.POINTER(i64), C.POINTER(i64)]),
         "mplx_service": (C.c_int, [vp, C.c_int, C.POINTER(i64)]),
         "mplx_device_info": (C.c_int, [vp, C.c_char_p, C.c_size_t, C.POINTER(i32)]),
+        "mplx_map_dilate": (C.c_int, [vp, vp, i32, vp]),
+        "mplx_map_free": (C.c_int, [vp, C.c_int, vp]),
+        "mplx_map_cloud": (C.c_int, [vp, C.c_int, vp, i64, C.POINTER(i64)]),
     }
-    for name in SYMBOLS:
+    for name in SYMBOLS + MAP_UTIL_SYMBOLS:
         fn = getattr(L, name)  # AttributeError if the library does not export it
         fn.restype, fn.argtypes = sig[name]
     _lib = L

@@ -266,6 +266,18 @@ hipError_t launch_expand_lex(int dim, int control, const GridArgs &args, hipStre
 hipError_t launch_gather_cells(const int8_t *cells, const int64_t *idx, int64_t n, int8_t *out, hipStream_t s);
 hipError_t launch_edit_map(const int64_t *idx, const int8_t *val, int64_t n, int64_t n_cells, int8_t *map, uint32_t *blk,
                            const uint32_t *region, hipStream_t s);
+// MapUtil::dilate / freeUnknown / clouds on the device map (map_util_kernel.hip, map_util_api.cpp).
+// Dilation: `runs` = n_runs records {dy, dz, b, len} (int32 each; dx in [b - len + 1, b], 1 <= len <= 33, |offset| <
+// map size per axis), `bits` = scratch of dilate_words_per_row(d[0]) * d[1] * d[2] words.
+int64_t dilate_words_per_row(int32_t d0);
+hipError_t launch_dilate(int8_t *map, const int32_t *d, const void *runs, int n_runs, uint32_t *bits, hipStream_t s);
+hipError_t launch_free_unknown(int8_t *map, int64_t n_cells, hipStream_t s);
+// Clouds: count[d0 * (3D: d1, 2D: 1)] cells of class `kind` per column, offs[n + 1] their exclusive scan in the
+// reference's loop order; the fill writes points [lo, hi) of the cloud to xyz ([hi - lo][dim] doubles).
+hipError_t launch_cloud_count(const int8_t *map, int dim, const int32_t *d, int kind, int32_t *count, int64_t *offs,
+                              hipStream_t s);
+hipError_t launch_cloud_fill(const int8_t *map, int dim, const int32_t *d, int kind, const int64_t *offs, int64_t lo,
+                             int64_t hi, double res, const double *origin, double *xyz, hipStream_t s);
 hipError_t launch_build_sat(int dim, const uint32_t *blk, const int32_t *mdim, uint32_t *sat, hipStream_t stream);
 hipError_t launch_build_blocked_bits(const int8_t *map, const uint32_t *region, int64_t n_cells, int potential,
                                      uint32_t *out, hipStream_t stream);

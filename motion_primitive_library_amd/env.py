@@ -483,6 +483,52 @@ class EnvMap:
                                                                       int(bool(dense)), sr, out.ctypes.data))
         return out
 
+    # ---- MapUtil's own map operations on the device map (map_util.h:136-296, include/mplx_map_util.h); the potential
+    #      map, if one is installed, is a separate copy and stays as it is
+    def _map_out(self, read_back):
+        return np.empty(self._ncell, dtype=np.int8) if read_back else None
+
+    def dilate(self, neighbors, read_back=True):
+        """MapUtil::dilate: every cell an offset of `neighbors` ([n][D] ints) reaches from a cell occupied before the
+        call becomes 100.  Returns the new int8 map (read_back=True) or None."""
+        D = len(self.map_dim)
+        off = np.ascontiguousarray(np.asarray(neighbors, dtype=np.int64).reshape(-1, D), dtype=np.int32)
+        out = self._map_out(read_back)
+        _abi.check(self._ctx, _abi.lib().mplx_map_dilate(self._ctx, off.ctypes.data, off.shape[0],
+                                                         None if out is None else out.ctypes.data))
+        return out
+
+    def freeUnknown(self, read_back=True):
+        """MapUtil::freeUnknown: unknown cells (-1) become free (0)."""
+        out = self._map_out(read_back)
+        _abi.check(self._ctx, _abi.lib().mplx_map_free(self._ctx, 1, None if out is None else out.ctypes.data))
+        return out
+
+    def freeAll(self, read_back=True):
+        """MapUtil::freeAll: every cell becomes free (0)."""
+        out = self._map_out(read_back)
+        _abi.check(self._ctx, _abi.lib().mplx_map_free(self._ctx, 0, None if out is None else out.ctypes.data))
+        return out
+
+    def _cloud(self, kind):
+        L = _abi.lib()
+        n = C.c_int64(0)
+        _abi.check(self._ctx, L.mplx_map_cloud(self._ctx, kind, None, 0, C.byref(n)))
+        pts = np.empty((n.value, len(self.map_dim)), dtype=np.float64)
+        if n.value:
+            _abi.check(self._ctx, L.mplx_map_cloud(self._ctx, kind, pts.ctypes.data, n.value, C.byref(n)))
+        return pts
+
+    def getCloud(self):
+        """MapUtil::getCloud: centres of the occupied cells, (n, D) float64, x outermost as the reference loops."""
+        return self._cloud(_abi.CELL_OCCUPIED)
+
+    def getFreeCloud(self):
+        return self._cloud(_abi.CELL_FREE)
+
+    def getUnknownCloud(self):
+        return self._cloud(_abi.CELL_UNKNOWN)
+
     def _flush(self):
         if self._dirty:
             _abi.check(self._ctx, _abi.lib().mplx_set_params(self._ctx, C.byref(self._p)))

@@ -11,6 +11,7 @@ plug another provider through set_provider() -- that is how the CPU oracle is
 run under the very same search to pin config C1.
 """
 import ctypes as C
+import weakref
 
 import numpy as np
 
@@ -19,11 +20,24 @@ from .env import EnvMap, Waypoint
 
 
 class MapUtil:
-    """MapUtil<Dim> as far as the planner needs it (map_util.h:84-90)."""
+    """MapUtil<Dim> (map_util.h): the map a planner reads, and the operations a user runs on it before planning --
+    dilate, freeUnknown, freeAll and the voxel clouds -- on the device.
 
-    def __init__(self, dim):
+    The reference's planners share the MapUtil by pointer, so an operation after setMapUtil reaches the next plan() of
+    every planner holding it.  Here the operation runs on the engine context of the planner the MapUtil was installed
+    in last (its device map is changed in place, nothing is uploaded); every holder's host grid gets the result
+    through mplx_planner_set_map, and the device map of any OTHER holder's context the new cells.  A MapUtil no
+    planner holds runs on a context of its own on `device`, created on first use; its cells are uploaded once per
+    setMap.  There is no CPU implementation: without a GPU the operations raise the engine's no-device error."""
+
+    def __init__(self, dim, device=0):
         self.dim = dim
+        self.device = device
         self.origin = self.map_dim = self.cells = self.res = None
+        self._holders = []     # weak references to the MapPlanners this MapUtil is installed in, oldest first
+        self._version = 0      # bumped by every change of the cells
+        self._own = None       # the context of its own (EnvMap), for a MapUtil no planner holds
+        self._own_version = -1
 
     def setMap(self, origin, dim, cells, res):
         self.origin = [float(x) for x in origin]
@@ -31,7 +45,76 @@ class MapUtil:
         self.cells = np.ascontiguousarray(cells, dtype=np.int8).ravel()
         self.res = float(res)
         assert self.cells.size == int(np.prod(self.map_dim))
+        self._version += 1
 
+    # ---- the reference's operations (map_util.h:136-296)
+    def dilate(self, dilate_neighbor):
+        """Inflates the obstacles: every cell an offset of `dilate_neighbor` ([n][D] ints) reaches from an occupied cell
+        becomes occupied (MapUtil::dilate, map_util.h:220-256)."""
+        return self._change(lambda env: env.dilate(dilate_neighbor))
+
+    def freeUnknown(self):
+        """Unknown cells (-1) become free (0) (map_util.h:258-276)."""
+        return self._change(lambda env: env.freeUnknown())
+
+    def freeAll(self):
+        """Every cell becomes free (0) (map_util.h:278-296)."""
+        return self._change(lambda env: env.freeAll())
+
+    def getCloud(self):
+        """Centres of the occupied cells, (n, D) float64, in the reference's order (x outermost)."""
+        return self._env().getCloud()
+
+    def getFreeCloud(self):
+        return self._env().getFreeCloud()
+
+    def getUnknownCloud(self):
+        return self._env().getUnknownCloud()
+
+    # ---- where the operations run
+    def _attach(self, planner):
+        self._detach(planner)
+        self._holders.append(weakref.ref(planner))
+
+    def _detach(self, planner):
+        self._holders = [r for r in self._holders if r() is not None and r() is not planner]
+
+    def _planners(self):
+        return [p for p in (r() for r in self._holders) if p is not None and p._p]
+
+    def _env(self):
+        """The engine context whose device map holds this MapUtil's cells (uploaded first where it does not)."""
+        if self.cells is None:
+            raise ValueError("MapUtil: setMap first")
+        engines = [p for p in self._planners() if p.env is not None]
+        if engines:
+            p = engines[-1]
+            if p._map_version != self._version:
+                p.env.setMap(self.origin, self.map_dim, self.cells, self.res)
+                p._map_version = self._version
+            return p.env
+        if self._own is None:
+            from .env import EnvMap
+            self._own = EnvMap(len(self.map_dim), self.device)
+        if self._own_version != self._version:
+            self._own.setMap(self.origin, self.map_dim, self.cells, self.res)
+            self._own_version = self._version
+        return self._own
+
+    def _change(self, op):
+        env = self._env()
+        new = op(env)  # a NEW array: setMap may have kept a view of the caller's
+        self.cells = new
+        self._version += 1
+        if env is self._own:
+            self._own_version = self._version
+        for p in self._planners():
+            p._map_util_changed(self, device_done=p.env is env)
+
+    def close(self):
+        if self._own is not None:
+            self._own.close()
+            self._own = None
 
 class Trajectory:
     """What the reference's tests read off Trajectory<Dim> (trajectory.h)."""
@@ -74,6 +157,7 @@ class MapPlanner:
         self.env = None
         self._keep = provider
         self._map_util = None
+        self._map_version = -1  # the MapUtil version this planner's device map holds
         self._search_radius = None
         self._potential_radius, self._potential_range, self._pow = None, None, 1.0
         self._traj = None
@@ -106,12 +190,26 @@ class MapPlanner:
 
     # ---- MapPlanner / PlannerBase setters (same names as the reference)
     def setMapUtil(self, map_util):
+        if self._map_util is not None and self._map_util is not map_util:
+            self._map_util._detach(self)
         self._map_util = map_util
+        map_util._attach(self)  # its dilate / freeUnknown / freeAll run on this planner's context from now on
         d = (C.c_int32 * 3)(*(map_util.map_dim + [1] * (3 - len(map_util.map_dim))))
         o = (C.c_double * 3)(*(map_util.origin + [0.0] * (3 - len(map_util.origin))))
         self._check(self._L.mplx_planner_set_map(self._p, map_util.cells.ctypes.data, d, o, map_util.res))
         if self.env is not None:
             self.env.setMap(map_util.origin, map_util.map_dim, map_util.cells, map_util.res)
+        self._map_version = map_util._version
+
+    def _map_util_changed(self, mu, device_done):
+        """An operation of the MapUtil this planner holds changed its cells: the host grid (start / goal tests) gets
+        them; the device map too, unless the operation ran on this planner's own context."""
+        d = (C.c_int32 * 3)(*(mu.map_dim + [1] * (3 - len(mu.map_dim))))
+        o = (C.c_double * 3)(*(mu.origin + [0.0] * (3 - len(mu.origin))))
+        self._check(self._L.mplx_planner_set_map(self._p, mu.cells.ctypes.data, d, o, mu.res))
+        if self.env is not None and not device_done:
+            self.env.setMap(mu.origin, mu.map_dim, mu.cells, mu.res)
+        self._map_version = mu._version
 
     def setU(self, U):
         U = np.ascontiguousarray(U, dtype=np.float64)
@@ -164,6 +262,8 @@ class MapPlanner:
         new_map = self.env.updatePotentialMap(pos, self._potential_radius, self._potential_range, self._pow)
         mu = self._map_util
         mu.cells = new_map
+        mu._version += 1
+        self._map_version = mu._version
         d = (C.c_int32 * 3)(*(mu.map_dim + [1] * (3 - len(mu.map_dim))))
         o = (C.c_double * 3)(*(mu.origin + [0.0] * (3 - len(mu.origin))))
         self._check(self._L.mplx_planner_set_map(self._p, mu.cells.ctypes.data, d, o, mu.res))

@@ -24,6 +24,7 @@ def load(name, lib):
     import ctypes
     probe = ctypes.CDLL(os.path.abspath(lib))
     mod._abi.SYMBOLS = [n for n in mod._abi.SYMBOLS if hasattr(probe, n)]  # an older build lacks the newer entry points
+    mod._abi.MAP_UTIL_SYMBOLS = [n for n in mod._abi.MAP_UTIL_SYMBOLS if hasattr(probe, n)]
     mod._abi.lib()
     return mod
 

@@ -1,0 +1,180 @@
+"""Generates tests/golden/map_util_golden.npz from the REFERENCE's own MapUtil<Dim>::dilate / freeUnknown / freeAll /
+getCloud / getFreeCloud / getUnknownCloud (include/mpl_collision/map_util.h).  The small C++ driver below is compiled
+into a temporary directory against the reference's headers, where they lie, and the stand-in Eigen of
+oracle/stub_include (flags of oracle/Makefile); nothing but the .npz is kept.  Run in the build container:
+
+    python tests/golden/make_map_util_golden.py            # writes the fixture
+    python tests/golden/make_map_util_golden.py --time     # one-thread time of the reference's dilate on C4's map (JSON)
+
+REF (environment) names the reference tree, as in oracle/Makefile.
+
+Clouds are stored as the map indices of their cells in the reference's order (first index, then differences) plus a
+SHA-256 of the reference's float64 points (intToFloat, map_util.h:110-114): order and position bits are pinned at a
+fraction of the size.
+"""
+import hashlib
+import json
+import os
+import subprocess
+import sys
+import tempfile
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+REF = os.environ.get("REF", "/root/reference")
+
+DRIVER = r"""
+// argv: dim d0 d1 d2 o0 o1 o2 res op map_in out [offsets_in n_offsets [reps]]
+#include <mpl_collision/map_util.h>
+
+#include <algorithm>
+#include <chrono>
+#include <cstdio>
+#include <cstdlib>
+#include <string>
+#include <vector>
+
+template <int D>
+int run(char **argv, int argc) {
+  Veci<D> dim;
+  Vecf<D> ori;
+  size_t n = 1;
+  for (int i = 0; i < D; i++) {
+    dim(i) = std::atoi(argv[2 + i]);
+    ori(i) = std::strtod(argv[5 + i], nullptr);
+    n *= (size_t)dim(i);
+  }
+  const double res = std::strtod(argv[8], nullptr);
+  const std::string op = argv[9];
+  MPL::Tmap map(n);
+  FILE *f = std::fopen(argv[10], "rb");
+  if (!f || std::fread(map.data(), 1, n, f) != n) return 2;
+  std::fclose(f);
+  vec_Veci<D> nb;
+  if (argc > 13) {
+    const int k = std::atoi(argv[13]);
+    std::vector<int> raw((size_t)k * D);
+    f = std::fopen(argv[12], "rb");
+    if (!f || std::fread(raw.data(), sizeof(int), raw.size(), f) != raw.size()) return 3;
+    std::fclose(f);
+    for (int i = 0; i < k; i++) {
+      Veci<D> o;
+      for (int j = 0; j < D; j++) o(j) = raw[(size_t)i * D + j];
+      nb.push_back(o);
+    }
+  }
+  MPL::MapUtil<D> mu;
+  mu.setMap(ori, dim, map, res);
+  FILE *out = std::fopen(argv[11], "wb");
+  if (!out) return 4;
+  if (op == "dilate" || op == "free_unknown" || op == "free_all") {
+    if (op == "dilate") mu.dilate(nb);
+    else if (op == "free_unknown") mu.freeUnknown();
+    else mu.freeAll();
+    const MPL::Tmap m = mu.getMap();
+    std::fwrite(m.data(), 1, m.size(), out);
+  } else if (op == "cloud0" || op == "cloud1" || op == "cloud2") {
+    const vec_Vecf<D> c = op == "cloud0" ? mu.getCloud() : op == "cloud1" ? mu.getFreeCloud() : mu.getUnknownCloud();
+    for (const auto &p : c)
+      for (int j = 0; j < D; j++) {
+        const double v = p(j);
+        std::fwrite(&v, sizeof v, 1, out);
+      }
+  } else if (op == "time_dilate") {
+    const int reps = argc > 14 ? std::atoi(argv[14]) : 3;
+    for (int r = 0; r < reps; r++) {
+      mu.setMap(ori, dim, map, res);
+      const auto t0 = std::chrono::steady_clock::now();
+      mu.dilate(nb);
+      const double s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+      std::fwrite(&s, sizeof s, 1, out);
+    }
+  } else {
+    return 5;
+  }
+  std::fclose(out);
+  return 0;
+}
+
+int main(int argc, char **argv) {
+  if (argc < 12) return 1;
+  return std::atoi(argv[1]) == 2 ? run<2>(argv, argc) : run<3>(argv, argc);
+}
+"""
+
+
+def build_driver(tmp):
+    src = os.path.join(tmp, "map_util_driver.cpp")
+    exe = os.path.join(tmp, "map_util_driver")
+    with open(src, "w") as f:
+        f.write(DRIVER)
+    subprocess.run(["g++", "-O2", "-std=c++14", "-ffp-contract=off", "-fno-fast-math", "-Wno-unused", "-Wno-sign-compare",
+                    "-I", os.path.join(ROOT, "oracle", "stub_include"), "-I", os.path.join(REF, "include"), "-o", exe, src],
+                   check=True)
+    return exe
+
+
+def run_driver(exe, tmp, grid, md, org, res, op, offsets=None, reps=None):
+    dim = len(md)
+    mpath, opath = os.path.join(tmp, "map.bin"), os.path.join(tmp, "out.bin")
+    np.ascontiguousarray(grid, dtype=np.int8).ravel().tofile(mpath)
+    d3 = list(md) + [1] * (3 - dim)
+    o3 = [float(x) for x in org] + [0.0] * (3 - dim)
+    args = [exe, str(dim)] + [str(int(x)) for x in d3] + [x.hex() for x in o3] + [float(res).hex(), op, mpath, opath]
+    if offsets is not None:
+        off = np.ascontiguousarray(np.asarray(offsets, dtype=np.int32).reshape(-1, dim))
+        fpath = os.path.join(tmp, "offsets.bin")
+        off.tofile(fpath)
+        args += [fpath, str(off.shape[0])]
+        if reps is not None:
+            args.append(str(reps))
+    subprocess.run(args, check=True)
+    if op.startswith("cloud"):
+        return np.fromfile(opath, dtype=np.float64).reshape(-1, dim)
+    if op == "time_dilate":
+        return np.fromfile(opath, dtype=np.float64)
+    return np.fromfile(opath, dtype=np.int8)
+
+
+def cloud_digest(points):
+    return np.frombuffer(hashlib.sha256(np.ascontiguousarray(points, dtype="<f8").tobytes()).digest(), dtype=np.uint8)
+
+
+def main():
+    from test_map_util import CASES, index_steps, offset_sets
+
+    out = {}
+    with tempfile.TemporaryDirectory() as tmp:
+        exe = build_driver(tmp)
+        if "--time" in sys.argv:
+            import motion_primitive_library_amd.workloads as W
+            from test_map_util import ball
+            grid = W.box_map([512] * 3, 0.1, 0.15, 1004)  # C4's map (workloads.make("C4"))
+            box = [o for o in np.ndindex(3, 3, 3) if o != (1, 1, 1)]
+            sets = {"box26": np.array(box) - 1, "ball_r3": ball(3, 3)}
+            rep = {}
+            for k, offs in sets.items():
+                t = run_driver(exe, tmp, grid, [512] * 3, [0.0] * 3, 0.1, "time_dilate", offs, reps=3)
+                rep[k] = {"offsets": int(len(offs)), "seconds": [float(x) for x in t], "median_s": float(np.median(t))}
+            print(json.dumps({"reference_cpu_dilate_512": rep, "threads": 1}, indent=1))
+            return
+        for name, dim, grid, md, org, res in CASES:
+            for k, (label, offs) in enumerate(offset_sets(md)):
+                out["%s/dilate%d" % (name, k)] = run_driver(exe, tmp, grid, md, org, res, "dilate", offs)
+            out["%s/free_unknown" % name] = run_driver(exe, tmp, grid, md, org, res, "free_unknown")
+            out["%s/free_all" % name] = run_driver(exe, tmp, grid, md, org, res, "free_all")
+            for kind in range(3):
+                pts = run_driver(exe, tmp, grid, md, org, res, "cloud%d" % kind)
+                cells = np.round((pts - np.array(org)) / res - 0.5).astype(np.int64)  # MapUtil::floatToInt
+                out["%s/cloud%d_steps" % (name, kind)] = index_steps(cells, md)
+                out["%s/cloud%d_sha256" % (name, kind)] = cloud_digest(pts)
+    path = os.path.join(ROOT, "tests", "golden", "map_util_golden.npz")
+    np.savez_compressed(path, **out)
+    print("wrote %d arrays, %d bytes" % (len(out), os.path.getsize(path)))
+
+
+if __name__ == "__main__":
+    main()

@@ -1,0 +1,512 @@
+"""MapUtil<Dim>'s own map operations on the device (include/mplx_map_util.h, csrc/map_util_kernel.hip):
+dilate, freeUnknown, freeAll, getCloud / getFreeCloud / getUnknownCloud (reference map_util.h:136-296).
+
+CPU: a numpy restatement against the committed fixture made by the reference's own MapUtil
+(tests/golden/make_map_util_golden.py); the new header and the library's exports; no CPU fallback.
+GPU: the device calls bit for bit against fixture and restatement, the expansion and the planner after them, the
+potential map left alone, no map upload, full-size maps, argument errors."""
+import ctypes as C
+import hashlib
+import os
+import re
+
+import numpy as np
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+GOLDEN = os.path.join(ROOT, "tests", "golden", "map_util_golden.npz")
+
+
+def _cases():
+    """(name, dim, flat int8 grid, map_dim, origin, res): box maps with unknown cells, potential values 1..99 and
+    values outside every class (101, 127, -5)."""
+    import motion_primitive_library_amd.workloads as W
+    out = []
+    for dim, md, seed in ((2, [96, 89], 11), (3, [40, 33, 37], 12)):
+        rng = np.random.default_rng(seed)
+        grid = W.box_map(md, 0.1, 0.12, seed, side_m=(0.3, 1.0)).ravel().copy()
+        grid[rng.integers(0, grid.size, grid.size // 20)] = -1
+        grid[rng.integers(0, grid.size, 60)] = rng.integers(1, 100, 60).astype(np.int8)
+        for v in (101, 127, -5):
+            grid[rng.integers(0, grid.size, 12)] = v
+        org = [0.05, -0.4, 0.2][:dim]
+        out.append(("d%d" % dim, dim, grid, md, org, 0.1))
+    return out
+
+
+CASES = _cases()
+
+
+def ball(r, dim):
+    """Offsets of the ball of radius r (|o|^2 <= r^2, the zero offset included), x fastest."""
+    rng = range(-r, r + 1)
+    pts = np.array(np.meshgrid(*[rng] * dim, indexing="ij")).reshape(dim, -1).T[:, ::-1]
+    return np.ascontiguousarray(pts[(pts ** 2).sum(axis=1) <= r * r], dtype=np.int32)
+
+
+def box(dim):
+    """The 8- (2D) / 26- (3D) neighbour box without the zero offset."""
+    pts = ball(dim, dim)
+    pts = pts[(np.abs(pts) <= 1).all(axis=1) & (np.abs(pts).sum(axis=1) > 0)]
+    return np.ascontiguousarray(pts, dtype=np.int32)
+
+
+def offset_sets(md):
+    dim = len(md)
+    axes = np.concatenate([np.eye(dim, dtype=np.int32), -np.eye(dim, dtype=np.int32)])
+    asym = np.array([[1, 0, 0], [2, 0, 0], [2, 0, 0], [0, -3, 1], [-1, 2, 0], [1, 0, 0], [5, 1, -2], [0, 0, 0],
+                     [3, -1, 1], [4, -1, 1]], dtype=np.int32)[:, :dim]
+    d = list(md) + [1] * (3 - dim)
+    beyond = np.array([[d[0], 0, 0], [-(d[0] + 5), 1, 0], [0, d[1], 0], [0, 0, d[2]], [d[0] - 1, 0, 0],
+                       [-(d[0] - 1), 0, 0], [0, -(d[1] - 1), 0], [2, 1, -(d[2] - 1)]], dtype=np.int32)[:, :dim]
+    wide = np.array([[x, 1, 0] for x in range(-45, 46)] + [[x, -2, 0] for x in range(3, 70, 2)], dtype=np.int32)[:, :dim]
+    return [("empty", np.zeros((0, dim), np.int32)), ("zero", np.zeros((1, dim), np.int32)), ("axes", axes),
+            ("box", box(dim)), ("ball2", ball(2, dim)), ("asymmetric", asym), ("beyond", beyond), ("wide", wide)]
+
+
+# ---- numpy restatement of map_util.h:136-296
+def np_dilate(grid, md, offsets):
+    """out[m] = 100 where some offset o has m - o inside the map and occupied in `grid`, grid[m] elsewhere."""
+    dim = len(md)
+    g = np.asarray(grid, dtype=np.int8).reshape(tuple(reversed(md)))
+    occ = g == 100
+    hit = np.zeros_like(occ)
+    for o in {tuple(int(v) for v in row) for row in np.asarray(offsets).reshape(-1, dim)}:
+        if any(abs(o[i]) >= md[i] for i in range(dim)):
+            continue
+        dst, src = [], []
+        for a in range(dim):  # array axis a is map axis dim - 1 - a
+            i, s = dim - 1 - a, o[dim - 1 - a]
+            dst.append(slice(s, md[i]) if s >= 0 else slice(0, md[i] + s))
+            src.append(slice(0, md[i] - s) if s >= 0 else slice(-s, md[i]))
+        hit[tuple(dst)] |= occ[tuple(src)]
+    out = g.copy()
+    out[hit] = 100
+    return out.ravel()
+
+
+def np_free_unknown(grid):
+    out = np.array(grid, dtype=np.int8).ravel()
+    out[out == -1] = 0
+    return out
+
+
+def np_cloud(grid, md, org, res, kind):
+    """(points, cells) of class kind (0 occupied, 1 free, 2 unknown) in the reference's order: x outermost."""
+    g = np.asarray(grid, dtype=np.int8).reshape(tuple(reversed(md)))
+    mask = (g == 100) if kind == 0 else ((g >= 0) & (g < 100)) if kind == 1 else (g == -1)
+    cells = np.stack(np.nonzero(mask.transpose()), axis=1)
+    return (cells.astype(np.float64) + 0.5) * res + np.asarray(org, dtype=np.float64), cells
+
+
+def index_steps(cells, md):
+    """Map indices (x + d0 y + d0 d1 z) of a cloud's cells in its order, as first index + differences."""
+    idx = cells[:, 0].astype(np.int64)
+    mul = 1
+    for i in range(1, len(md)):
+        mul *= md[i - 1]
+        idx = idx + mul * cells[:, i]
+    return np.diff(idx, prepend=0).astype(np.int32)
+
+
+def sha256(points):
+    return np.frombuffer(hashlib.sha256(np.ascontiguousarray(points, dtype="<f8").tobytes()).digest(), dtype=np.uint8)
+
+
+# ---------------------------------------------------------------------------------------------------------------- CPU
+def test_restatement_matches_the_golden_fixture():
+    """tests/golden/map_util_golden.npz holds what the reference's MapUtil returned for these maps."""
+    z = np.load(GOLDEN)
+    n = 0
+    for name, dim, grid, md, org, res in CASES:
+        for k, (label, offs) in enumerate(offset_sets(md)):
+            assert np.array_equal(np_dilate(grid, md, offs), z["%s/dilate%d" % (name, k)]), (name, label)
+            n += 1
+        assert np.array_equal(np_free_unknown(grid), z["%s/free_unknown" % name])
+        assert np.array_equal(np.zeros(grid.size, np.int8), z["%s/free_all" % name])
+        for kind in range(3):
+            pts, cells = np_cloud(grid, md, org, res, kind)
+            assert np.array_equal(index_steps(cells, md), z["%s/cloud%d_steps" % (name, kind)]), (name, kind)
+            assert np.array_equal(sha256(pts), z["%s/cloud%d_sha256" % (name, kind)]), (name, kind)
+            assert len(pts) > 50
+            n += 1
+    assert n == 2 * (8 + 3)
+
+
+def test_offset_sets_cover_what_the_kernel_must_handle():
+    for name, dim, grid, md, org, res in CASES:
+        sets = dict(offset_sets(md))
+        assert len(sets["box"]) == 3 ** dim - 1 and len(sets["axes"]) == 2 * dim
+        assert len(sets["ball2"]) == (13 if dim == 2 else 33)
+        assert len(ball(3, 3)) == 123
+        assert len(np.unique(sets["asymmetric"], axis=0)) < len(sets["asymmetric"])  # duplicates
+        assert (np.abs(sets["beyond"]) >= np.array(md)).any(axis=1).sum() >= 3       # offsets past the map
+        changed = [not np.array_equal(np_dilate(grid, md, o), grid) for o in sets.values()]
+        assert changed == [False, False, True, True, True, True, True, True]
+
+
+def _declared(header):
+    text = open(os.path.join(ROOT, "include", header)).read()
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    return sorted(set(re.findall(r"\b(mplx_[a-z0-9_]+)\s*\(", text)))
+
+
+def test_map_util_header_declares_the_three_calls_and_the_library_exports_them(engine):
+    assert _declared("mplx_map_util.h") == sorted(["mplx_map_dilate", "mplx_map_free", "mplx_map_cloud"])
+    assert sorted(engine._abi.MAP_UTIL_SYMBOLS) == _declared("mplx_map_util.h")
+    assert not set(_declared("mplx_map_util.h")) & set(engine._abi.SYMBOLS)  # mplx.h stays at ABI v9
+    lib = C.CDLL(engine._abi.LIB_PATH)
+    for s in engine._abi.MAP_UTIL_SYMBOLS:
+        assert hasattr(lib, s), "libmplx.so does not export %s" % s
+    L = engine._abi.lib()
+    assert all(hasattr(L, s) for s in engine._abi.MAP_UTIL_SYMBOLS)
+    text = open(os.path.join(ROOT, "include", "mplx_map_util.h")).read()
+    assert "MPLX_CELL_OCCUPIED = 0" in text and "MPLX_CELL_FREE = 1" in text and "MPLX_CELL_UNKNOWN = 2" in text
+
+
+def test_map_util_has_no_cpu_fallback(engine):
+    """MapUtil's operations run on the device; without one they fail with the engine's no-device error."""
+    import torch
+    name, dim, grid, md, org, res = CASES[0]
+    mu = engine.MapUtil(dim)
+    mu.setMap(org, md, grid, res)
+    if torch.cuda.is_available():  # (the same call on a machine with a GPU: the device result)
+        mu.dilate(box(dim))
+        assert np.array_equal(mu.cells, np_dilate(grid, md, box(dim)))
+        mu.close()
+        return
+    with pytest.raises(engine._abi.MplxError) as e:
+        mu.dilate(box(dim))
+    assert e.value.code == engine._abi.ERR_NO_DEVICE and "no CPU fallback" in str(e.value)
+    assert mu.cells is not None and np.array_equal(mu.cells, grid)
+
+
+# ---------------------------------------------------------------------------------------------------------------- GPU
+@pytest.mark.gpu
+@pytest.mark.parametrize("case", CASES, ids=[c[0] for c in CASES])
+def test_device_map_util_is_bit_identical(engine, case):
+    """dilate / freeUnknown / freeAll / the three clouds on the device against the reference's fixture and the
+    restatement: cells, point order and position bits."""
+    name, dim, grid, md, org, res = case
+    z = np.load(GOLDEN)
+    env = engine.EnvMap(dim)
+    for k, (label, offs) in enumerate(offset_sets(md)):
+        env.setMap(org, md, grid, res)
+        got = env.dilate(offs)
+        want = z["%s/dilate%d" % (name, k)]
+        bad = np.nonzero(got != want)[0]
+        assert bad.size == 0, "%s %s: %d cells differ, first %s got %s want %s" % (name, label, bad.size, bad[:5], got[bad[:5]], want[bad[:5]])
+        assert np.array_equal(got, np_dilate(grid, md, offs))
+    env.setMap(org, md, grid, res)
+    assert np.array_equal(env.freeUnknown(), z["%s/free_unknown" % name])
+    env.setMap(org, md, grid, res)
+    for kind, fn in enumerate((env.getCloud, env.getFreeCloud, env.getUnknownCloud)):
+        pts = fn()
+        want, cells = np_cloud(grid, md, org, res, kind)
+        assert pts.shape == want.shape and pts.dtype == np.float64, (kind, pts.shape, want.shape)
+        assert np.array_equal(pts.view(np.uint64), want.view(np.uint64)), (name, kind)
+        assert np.array_equal(sha256(pts), z["%s/cloud%d_sha256" % (name, kind)])
+        assert np.array_equal(index_steps(cells, md), z["%s/cloud%d_steps" % (name, kind)])
+    # clouds of a changed map, and the calls without read-back
+    assert env.dilate(offset_sets(md)[4][1], read_back=False) is None
+    dil = np_dilate(grid, md, offset_sets(md)[4][1])
+    for kind, fn in enumerate((env.getCloud, env.getFreeCloud, env.getUnknownCloud)):
+        assert np.array_equal(fn().view(np.uint64), np_cloud(dil, md, org, res, kind)[0].view(np.uint64)), kind
+    assert env.freeUnknown(read_back=False) is None
+    assert np.array_equal(env.getFreeCloud().view(np.uint64), np_cloud(np_free_unknown(dil), md, org, res, 1)[0].view(np.uint64))
+    assert np.array_equal(env.freeAll(), z["%s/free_all" % name])
+    assert env.getCloud().shape == (0, dim) and env.getUnknownCloud().shape == (0, dim)
+    assert env.getFreeCloud().shape == (grid.size, dim)
+    env.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("dim,with_region", [(2, False), (3, False), (3, True)])
+def test_expansion_after_a_device_dilate_equals_a_full_upload(engine, oracle_lib, dim, with_region):
+    """A device dilate (blocked bits and free-box table rebuilt from the new cells) against mplx_set_map of the
+    numpy-dilated array and against the oracle on that map: every list route, a batch large enough to rebuild the
+    free-box table, and mplx_edit_map after the dilate."""
+    from helpers import assert_lists_equal, engine_env, oracle_env
+    from test_gpu_parity import _small_world
+    wl = _small_world(engine, dim, 0x03, seed=9100 + dim, n_nodes=200, region=with_region)
+    md = wl.map_dim
+    flat = np.ascontiguousarray(wl.grid).ravel().copy()
+    env = engine_env(engine, wl)
+    before = env.expand_lists(wl.nodes)  # (blocked bits and free-box table of the ORIGINAL map)
+    up0 = env.map_upload_bytes()
+    got_map = env.dilate(box(dim))
+    assert env.map_upload_bytes() == up0
+    dil = np_dilate(flat, md, box(dim))
+    assert np.array_equal(got_map, dil)
+    wl2 = _small_world(engine, dim, 0x03, seed=9100 + dim, n_nodes=200, region=with_region)
+    wl2.grid = dil.reshape(np.asarray(wl.grid).shape)
+    ref = oracle_lib.expand(oracle_env(wl2), wl.nodes, threads=8)
+    env2 = engine_env(engine, wl2)
+    changed = False
+    for route in ("grid", "tile", "dense"):
+        env.set_lists_route(route)
+        env2.set_lists_route(route)
+        got = env.expand_lists(wl.nodes)
+        assert_lists_equal(got, ref, wl.n_nodes, wl.U.shape[0], what="dilated map, route %s" % route)
+        whole = env2.expand_lists(wl.nodes)
+        for k in ("count", "action", "hash", "cost"):
+            assert np.array_equal(got[k], whole[k]), (route, k)
+        changed = changed or not np.array_equal(got["count"], before["count"]) or not np.array_equal(got["cost"], before["cost"])
+    assert changed, "the dilation did not touch a single successor"
+    env.set_lists_route("grid")
+    env2.set_lists_route("grid")
+    big = np.ascontiguousarray(np.tile(wl.nodes, (1, 25)))  # 5 000 nodes
+    got_big = env.expand_lists(big)
+    assert_lists_equal(got_big, oracle_lib.expand(oracle_env(wl2), big, threads=8), big.shape[1], wl.U.shape[0],
+                       what="dilated map, 5 000 nodes")
+    whole = env2.expand_lists(big)
+    for k in ("count", "action", "hash", "cost"):
+        assert np.array_equal(got_big[k], whole[k]), k
+    # mplx_edit_map after the dilate: free some of the new obstacle cells again
+    rng = np.random.default_rng(5)
+    grown = np.nonzero((dil == 100) & (flat != 100))[0]
+    idx = rng.choice(grown, min(300, grown.size), replace=False)
+    env.editMap(idx, np.zeros(idx.size, np.int8))
+    dil2 = dil.copy()
+    dil2[idx] = 0
+    wl2.grid = dil2.reshape(np.asarray(wl.grid).shape)
+    ref2 = oracle_lib.expand(oracle_env(wl2), wl.nodes, threads=8)
+    for route in ("grid", "tile", "dense"):
+        env.set_lists_route(route)
+        assert_lists_equal(env.expand_lists(wl.nodes), ref2, wl.n_nodes, wl.U.shape[0], what="dilate + edit, route %s" % route)
+    env.close()
+    env2.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("dim", [2, 3])
+def test_dilate_leaves_the_potential_map_and_the_expansion_alone(engine, dim):
+    """With a potential map installed (updatePotentialMap) the expansion reads only that copy (env_map.h:113-120); a
+    dilation of the MapUtil's map changes no expansion result, and the potential cells stay as they were."""
+    from helpers import engine_env
+    from test_gpu_parity import _small_world
+    wl = _small_world(engine, dim, 0x03, seed=9200 + dim, n_nodes=200)
+    env = engine_env(engine, wl)
+    env.set_potential_weight(0.5)
+    env.set_gradient_weight(0.25)
+    pot = env.updatePotentialMap([0.0] * dim, [0.4] * dim)
+    res = {}
+    for route in ("grid", "dense"):
+        env.set_lists_route(route)
+        res[route] = env.expand_lists(wl.nodes)
+    dense_before = env.expand(wl.nodes)
+    idx = np.arange(pot.size, dtype=np.int64)
+    new_map = env.dilate(ball(2, dim))
+    assert not np.array_equal(new_map, pot) and np.array_equal(new_map, np_dilate(pot, wl.map_dim, ball(2, dim)))
+    assert np.array_equal(env.read_cells(idx, potential=True), pot)
+    assert np.array_equal(env.read_cells(idx), new_map)
+    for route in ("grid", "dense"):
+        env.set_lists_route(route)
+        got = env.expand_lists(wl.nodes)
+        for k in ("count", "action", "hash", "cost", "state"):
+            assert np.array_equal(got[k], res[route][k]), (route, k)
+    dense_after = env.expand(wl.nodes)
+    for k in ("status", "cost", "hash", "state"):
+        assert np.array_equal(dense_after[k], dense_before[k]), k
+    assert (res["grid"]["count"] > 0).any()
+    env.close()
+
+
+@pytest.mark.gpu
+def test_map_util_calls_upload_no_map(engine):
+    name, dim, grid, md, org, res = CASES[1]
+    env = engine.EnvMap(dim)
+    env.setMap(org, md, grid, res)
+    up = env.map_upload_bytes()
+    assert up == grid.size
+    env.dilate(box(dim))
+    env.getCloud()
+    env.freeUnknown()
+    env.getUnknownCloud()
+    env.freeAll()
+    env.getFreeCloud()
+    assert env.map_upload_bytes() == up
+    env.close()
+
+
+def _plan(m, dim, mu, U, vmax, amax, batch=16):
+    pl = m.MapPlanner(dim, device=0)
+    pl.setMapUtil(mu)
+    pl.setVmax(vmax)
+    pl.setAmax(amax)
+    pl.setDt(1.0)
+    pl.setU(U)
+    pl.setBatch(batch)
+    return pl
+
+
+def _run(m, pl, dim, start, goal, ctrl):
+    ok = pl.plan(m.Waypoint(dim, ctrl, pos=start), m.Waypoint(dim, ctrl, pos=goal))
+    s = pl.summary()
+    out = {"ok": ok, "closed": pl.getCloseSet()}
+    out.update({k: s[k] for k in ("cost", "expansions", "closed", "nodes", "segments", "total_time")})
+    if ok:
+        tr = pl.getTraj()
+        out["traj_nodes"], out["traj_actions"] = tr.nodes, tr.actions
+    return out
+
+
+def _same(a, b, what):
+    assert a["ok"] == b["ok"], what
+    for k in ("cost", "expansions", "nodes", "segments", "total_time"):
+        assert a[k] == b[k], (what, k, a[k], b[k])
+    assert np.array_equal(a["closed"], b["closed"]), what
+    if a["ok"]:
+        assert np.array_equal(a["traj_nodes"], b["traj_nodes"]) and np.array_equal(a["traj_actions"], b["traj_actions"]), what
+
+
+def _problems(m):
+    from test_plan_known_answer import corridor
+    W = m.workloads
+    c = corridor()
+    yield ("corridor", 2, c["cells"], c["dim"], c["origin"], c["res"], W.grid_controls([-0.5, 0.0, 0.5], 2),
+           np.asarray(c["start"], float), np.asarray(c["goal"], float), 1.0, 1.0, box(2))
+    edge = 56
+    grid = W.box_map([edge] * 3, 0.1, 0.07, 80, side_m=(0.4, 1.2)).ravel()
+    dil = np_dilate(grid, [edge] * 3, box(3))
+    free = np.argwhere(dil.reshape([edge] * 3) == 0)  # [z, y, x]; start and goal free after the dilation
+    a, b = free[3][::-1], free[-3][::-1]
+    yield ("acc3d", 3, grid, [edge] * 3, [0.0] * 3, 0.1, W.grid_controls(np.linspace(-2.0, 2.0, 9), 3),
+           (a + 0.5) * 0.1, (b + 0.5) * 0.1, 2.0, 2.0, box(3))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("which", ["corridor", "acc3d"])
+def test_planner_sees_a_map_util_dilate(engine, which):
+    """MapPlanner + MapUtil: plan, dilate, plan again -- the same search (cost, expansions, closed set, trajectory) as a
+    fresh planner given the numpy-dilated map; two planners sharing the MapUtil both see the new map; the caller's
+    array is untouched; a start cell the dilation blocks makes plan() fail, as in the reference."""
+    m = engine
+    name, dim, cells, md, org, res, U, start, goal, vmax, amax, nb = [p for p in _problems(m) if p[0] == which][0]
+    ctrl = m.ACC
+    keep = cells.copy()
+    dil = np_dilate(cells, md, nb)
+    assert not np.array_equal(dil, cells)
+    mu = m.MapUtil(dim)
+    mu.setMap(org, md, cells, res)
+    pl1 = _plan(m, dim, mu, U, vmax, amax)
+    pl2 = _plan(m, dim, mu, U, vmax, amax)
+    r0 = _run(m, pl1, dim, start, goal, ctrl)
+    assert r0["ok"] and r0["expansions"] > 50
+    _run(m, pl2, dim, start, goal, ctrl)
+    up = [pl1.env.map_upload_bytes(), pl2.env.map_upload_bytes()]
+    mu.dilate(nb)
+    assert np.array_equal(cells, keep), "the caller's array was written"
+    assert mu.cells is not cells and np.array_equal(mu.cells, dil)
+    assert pl2.env.map_upload_bytes() == up[1]  # the context it ran on: no upload
+    r1, r2 = _run(m, pl1, dim, start, goal, ctrl), _run(m, pl2, dim, start, goal, ctrl)
+    mu_f = m.MapUtil(dim)
+    mu_f.setMap(org, md, dil, res)
+    fresh = _plan(m, dim, mu_f, U, vmax, amax)
+    rf = _run(m, fresh, dim, start, goal, ctrl)
+    assert rf["ok"]
+    _same(r1, rf, "%s planner 1 after the dilate" % name)
+    _same(r2, rf, "%s planner 2 after the dilate" % name)
+    assert (r1["cost"], r1["expansions"]) != (r0["cost"], r0["expansions"]) or not np.array_equal(r1["closed"], r0["closed"])
+    # a start cell the dilation blocks
+    g = dil.reshape(tuple(reversed(md)))
+    s_cell = np.floor((start - np.array(org)) / res).astype(int)
+    occ = np.argwhere(g == 100)[:, ::-1]  # [x, y(, z)]
+    near = occ[np.argmin(((occ - s_cell) ** 2).sum(axis=1))]
+    mu.dilate((s_cell - near)[None, :])
+    assert mu.cells.reshape(tuple(reversed(md)))[tuple(s_cell[::-1])] == 100
+    assert not _run(m, pl1, dim, start, goal, ctrl)["ok"]
+    assert not _run(m, pl2, dim, start, goal, ctrl)["ok"]
+    assert np.array_equal(cells, keep)
+    for p in (pl1, pl2, fresh):
+        p.close()
+
+
+@pytest.mark.gpu
+def test_map_util_without_a_planner_uses_its_own_context(engine):
+    name, dim, grid, md, org, res = CASES[1]
+    mu = engine.MapUtil(dim)
+    mu.setMap(org, md, grid, res)
+    keep = grid.copy()
+    mu.dilate(box(dim))
+    mu.freeUnknown()
+    want = np_free_unknown(np_dilate(grid, md, box(dim)))
+    assert np.array_equal(mu.cells, want) and np.array_equal(grid, keep)
+    assert mu._own.map_upload_bytes() == grid.size  # uploaded once for the setMap
+    assert np.array_equal(mu.getCloud().view(np.uint64), np_cloud(want, md, org, res, 0)[0].view(np.uint64))
+    mu.setMap(org, md, grid, res)  # a new map: uploaded once more
+    assert np.array_equal(mu.getUnknownCloud().view(np.uint64), np_cloud(grid, md, org, res, 2)[0].view(np.uint64))
+    assert mu._own.map_upload_bytes() == 2 * grid.size
+    mu.freeAll()
+    assert not mu.cells.any()
+    mu.close()
+
+
+def _full_size(edge, seed):
+    import motion_primitive_library_amd.workloads as W
+    return W.box_map([edge] * 3, 0.1, 0.15, seed).ravel()  # C3's / C4's map (workloads.make)
+
+
+@pytest.mark.gpu
+def test_full_size_c4_map_dilate_and_cloud(engine):
+    grid = _full_size(512, 1004)
+    md = [512] * 3
+    env = engine.EnvMap(3)
+    env.setMap([0.0] * 3, md, grid, 0.1)
+    pts = env.getCloud()
+    want, _ = np_cloud(grid, md, [0.0] * 3, 0.1, 0)
+    assert pts.shape == want.shape and np.array_equal(pts.view(np.uint64), want.view(np.uint64))
+    del pts, want
+    got = env.dilate(box(3))
+    want = np_dilate(grid, md, box(3))
+    assert np.array_equal(got, want), "512^3, 26-box: %d cells differ" % int((got != want).sum())
+    env.close()
+
+
+@pytest.mark.gpu
+def test_full_size_c3_map_ball_dilate_and_free_cloud(engine):
+    grid = _full_size(256, 1003)
+    md = [256] * 3
+    env = engine.EnvMap(3)
+    env.setMap([0.0] * 3, md, grid, 0.1)
+    b = ball(3, 3)
+    assert len(b) == 123
+    got = env.dilate(b)
+    want = np_dilate(grid, md, b)
+    assert np.array_equal(got, want), "256^3, ball r=3: %d cells differ" % int((got != want).sum())
+    env.setMap([0.0] * 3, md, grid, 0.1)
+    pts = env.getFreeCloud()
+    wp, _ = np_cloud(grid, md, [0.0] * 3, 0.1, 1)
+    assert pts.shape == wp.shape and np.array_equal(pts.view(np.uint64), wp.view(np.uint64))
+    env.close()
+
+
+@pytest.mark.gpu
+def test_bad_arguments_and_short_buffers(engine):
+    E = engine._abi
+    L = E.lib()
+    name, dim, grid, md, org, res = CASES[0]
+    env = engine.EnvMap(dim)
+    n = C.c_int64(-7)
+    assert L.mplx_map_dilate(env._ctx, None, 0, None) == E.ERR_STATE  # no map yet
+    assert L.mplx_map_free(env._ctx, 1, None) == E.ERR_STATE
+    assert L.mplx_map_cloud(env._ctx, 0, None, 0, C.byref(n)) == E.ERR_STATE
+    env.setMap(org, md, grid, res)
+    off = box(dim)
+    assert L.mplx_map_dilate(env._ctx, off.ctypes.data, -1, None) == E.ERR_ARG
+    assert L.mplx_map_dilate(env._ctx, None, 3, None) == E.ERR_ARG
+    assert L.mplx_map_dilate(env._ctx, None, 0, None) == E.OK  # an empty list: nothing changes
+    assert L.mplx_map_free(env._ctx, 2, None) == E.ERR_ARG
+    assert L.mplx_map_cloud(env._ctx, 3, None, 0, C.byref(n)) == E.ERR_ARG
+    assert L.mplx_map_cloud(env._ctx, -1, None, 0, C.byref(n)) == E.ERR_ARG
+    assert L.mplx_map_cloud(env._ctx, 0, None, -1, C.byref(n)) == E.ERR_ARG
+    assert L.mplx_map_cloud(env._ctx, 0, None, 0, None) == E.ERR_ARG
+    want, _ = np_cloud(grid, md, org, res, 1)
+    cap = len(want) // 3
+    buf = np.full((len(want), dim), -2.5)
+    assert L.mplx_map_cloud(env._ctx, 1, buf.ctypes.data, cap, C.byref(n)) == E.OK
+    assert n.value == len(want)
+    assert np.array_equal(buf[:cap].view(np.uint64), want[:cap].view(np.uint64)) and (buf[cap:] == -2.5).all()
+    assert L.mplx_map_cloud(env._ctx, 1, None, 10, C.byref(n)) == E.OK and n.value == len(want)
+    assert np.array_equal(env.read_cells(np.arange(grid.size)), grid)  # nothing above changed the map
+    env.close()
