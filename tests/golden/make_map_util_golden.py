@@ -8,6 +8,9 @@ oracle/stub_include (flags of oracle/Makefile); nothing but the .npz is kept.  R
 
 REF (environment) names the reference tree, as in oracle/Makefile.
 
+Maps: the two of tests/test_map_util.py::CASES with its eight offset sets, and the small maps of the x lengths 16, 48, 80
+and 1 (X_GOLDEN_CASES, 2D and 3D) with the six sets of x_offset_sets: the lengths at which the device kernels change path.
+
 Clouds are stored as the map indices of their cells in the reference's order (first index, then differences) plus a
 SHA-256 of the reference's float64 points (intToFloat, map_util.h:110-114): order and position bits are pinned at a
 fraction of the size.
@@ -144,7 +147,7 @@ def cloud_digest(points):
 
 
 def main():
-    from test_map_util import CASES, index_steps, offset_sets
+    from test_map_util import CASES, X_GOLDEN_CASES, index_steps, offset_sets, x_offset_sets
 
     out = {}
     with tempfile.TemporaryDirectory() as tmp:
@@ -161,11 +164,15 @@ def main():
                 rep[k] = {"offsets": int(len(offs)), "seconds": [float(x) for x in t], "median_s": float(np.median(t))}
             print(json.dumps({"reference_cpu_dilate_512": rep, "threads": 1}, indent=1))
             return
-        for name, dim, grid, md, org, res in CASES:
-            for k, (label, offs) in enumerate(offset_sets(md)):
-                out["%s/dilate%d" % (name, k)] = run_driver(exe, tmp, grid, md, org, res, "dilate", offs)
+        for name, dim, grid, md, org, res in CASES + X_GOLDEN_CASES:  # (the x-length classes 16, 48, 80 and 1 after the two maps)
+            if name.startswith("x"):
+                for label, offs in x_offset_sets(md):
+                    out["%s/dilate_%s" % (name, label)] = run_driver(exe, tmp, grid, md, org, res, "dilate", offs)
+            else:
+                for k, (label, offs) in enumerate(offset_sets(md)):
+                    out["%s/dilate%d" % (name, k)] = run_driver(exe, tmp, grid, md, org, res, "dilate", offs)
+                out["%s/free_all" % name] = run_driver(exe, tmp, grid, md, org, res, "free_all")
             out["%s/free_unknown" % name] = run_driver(exe, tmp, grid, md, org, res, "free_unknown")
-            out["%s/free_all" % name] = run_driver(exe, tmp, grid, md, org, res, "free_all")
             for kind in range(3):
                 pts = run_driver(exe, tmp, grid, md, org, res, "cloud%d" % kind)
                 cells = np.round((pts - np.array(org)) / res - 0.5).astype(np.int64)  # MapUtil::floatToInt

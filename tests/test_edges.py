@@ -13,9 +13,9 @@ from oracle import oracle as O
 REF_SO = os.path.join(O.HERE, "_ref", "libmpl_ref.so")
 
 
-def _edges(m, dim, control, seed, region=False, n=400):
+def _edges(m, dim, control, seed, region=False, n=400, dims=None):
     from test_gpu_parity import _small_world
-    wl = _small_world(m, dim, control, seed=seed, n_nodes=n, region=region)
+    wl = _small_world(m, dim, control, seed=seed, n_nodes=n, region=region, dims=dims)
     rng = np.random.default_rng(seed + 1)
     actions = rng.integers(0, wl.U.shape[0], size=n).astype(np.int32)
     wl.nodes[dim:4 * dim, :8] = 0.0  # a few parents at rest: with u = 0 the primitive does not move (n == 0)

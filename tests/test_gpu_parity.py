@@ -27,17 +27,24 @@ def _run_both(m, O, wl, threads=8, want_iters=True):
 
 
 def _small_world(m, dim, control, seed, n_nodes=96, edge=48, potential=False, region=False, limits=True,
-                 res=0.1):
-    """A small random environment exercising one control flag."""
+                 res=0.1, dims=None):
+    """A small random environment exercising one control flag.  dims: the map's axis lengths (x first) where they are
+    to differ; None is the cube [edge] * dim, with the inputs this builder has always made."""
     W = m.workloads
     rng = np.random.default_rng(seed)
-    grid = W.box_map([edge] * dim, res, 0.15, seed, side_m=(0.3, 1.2))
+    md = [edge] * dim if dims is None else [int(d) for d in dims]
+    assert len(md) == dim
+    grid = W.box_map(md, res, 0.15, seed, side_m=(0.3, 1.2))
     base = control & 0x0F
     vals = [-1.0, 0.0, 1.0] if dim == 3 else [-1.0, -0.5, 0.0, 0.5, 1.0]
     U = W.grid_controls(vals, dim, yaw_rates=[-0.5, 0.0, 0.5] if control & 0x10 else None)
     nodes = W.random_frontier(grid, [0.0] * dim, res, n_nodes, seed + 1, control, 1.5, 0.5, 1.0, 0.5, 1.0, 0.5)
     # push a few nodes to the map border / outside and add signed zeros
-    nodes[0, :4] = [0.0, -0.03, edge * res - 0.01, edge * res + 0.2][: 4]
+    nodes[0, :4] = [0.0, -0.03, md[0] * res - 0.01, md[0] * res + 0.2][: 4]
+    if dims is not None:  # ... on every axis, each with its own length: nodes 4 i .. 4 i + 3 sit on axis i's two borders
+        assert n_nodes >= 4 * dim
+        for i in range(1, dim):
+            nodes[i, 4 * i:4 * i + 4] = [0.0, -0.03, md[i] * res - 0.01, md[i] * res + 0.2]
     if base >= 0x03:
         nodes[dim, 4:8] = -0.0
     params = {}
@@ -52,8 +59,8 @@ def _small_world(m, dim, control, seed, n_nodes=96, edge=48, potential=False, re
         params.update({"potential_weight": 0.5, "gradient_weight": 0.25})
     if region:
         lo = [0.5] * dim
-        hi = [edge * res - 0.5] * dim
-        reg = W.tunnel_region([edge] * dim, [0.0] * dim, res, lo, hi, 1.0)
+        hi = [md[i] * res - 0.5 for i in range(dim)]
+        reg = W.tunnel_region(md, [0.0] * dim, res, lo, hi, 1.0)
     return W.Workload("small", dim, control, pot if potential else grid, [0.0] * dim, res, U, nodes, params,
                       potential=pot, region=reg)
 

@@ -4,7 +4,8 @@ dilate, freeUnknown, freeAll, getCloud / getFreeCloud / getUnknownCloud (referen
 CPU: a numpy restatement against the committed fixture made by the reference's own MapUtil
 (tests/golden/make_map_util_golden.py); the new header and the library's exports; no CPU fallback.
 GPU: the device calls bit for bit against fixture and restatement, the expansion and the planner after them, the
-potential map left alone, no map upload, full-size maps, argument errors."""
+potential map left alone, no map upload, full-size maps, argument errors; every x-length class the kernels branch on
+(d0 % 16, rows ending on a half word, one cell per row) and the column counts at the slice edges of the clouds' scan."""
 import ctypes as C
 import hashlib
 import os
@@ -35,6 +36,56 @@ def _cases():
 
 
 CASES = _cases()
+
+# x lengths by the classes the kernels branch on (csrc/map_util_kernel.hip): d0 % 16 (16-byte loads and read-modify-writes
+# against byte loops), fewer than 32 cells left in a row (one half word, or n < 32 bytes), the funnel shift r = (32 w - b)
+# % 32, and for freeUnknown the tail of fewer than 16 cells (n_cells % 16 != 0 in 14 of the 26 maps)
+X_LENGTHS = [1, 15, 16, 17, 31, 32, 33, 48, 63, 64, 65, 80, 112]
+X_GOLDEN = [16, 48, 80, 1]  # the classes whose restatement is pinned to the reference's MapUtil in the fixture
+
+
+def x_case(d0, dim):
+    """(name, dim, flat int8 grid, map_dim, origin, res): x length d0, the other axes small and unequal; occupied and
+    unknown cells at random (row ends included), potential values and values outside every class."""
+    md = [d0, 11] if dim == 2 else [d0, 7, 5]
+    rng = np.random.default_rng(1000 * dim + d0)
+    n = int(np.prod(md))
+    grid = rng.choice(np.array([0, 100, -1, 37, 101, -5], dtype=np.int8), size=n, p=[0.68, 0.1, 0.12, 0.06, 0.02, 0.02])
+    grid[rng.integers(0, n)] = 100  # (never without an occupied cell, however small the map)
+    if d0 > 1:  # a row that starts occupied and ends free, and the next one the other way round: dx = +-(d0 - 1) joins them
+        grid[[0, 2 * d0 - 1]] = 100
+        grid[[d0 - 1, d0]] = 0
+    org = [0.05, -0.4, 0.2][:dim]
+    return ("x%dd%d" % (d0, dim), dim, np.ascontiguousarray(grid, dtype=np.int8), md, org, 0.1)
+
+
+X_CASES = [x_case(d0, dim) for d0 in X_LENGTHS for dim in (2, 3)]
+X_GOLDEN_CASES = [c for c in X_CASES if c[3][0] in X_GOLDEN]
+
+
+def x_offset_sets(md):
+    """Offset sets for the x-length classes: the box, the ball of radius 3, the wide set above, runs of exactly 33 and
+    of 34 consecutive dx (one 64-bit window holds 33; the 34th starts a second run) and dx = +-(d0 - 1), the farthest
+    an offset can reach along a row."""
+    dim = len(md)
+    z = [0] * (dim - 1)
+    run33 = np.array([[x] + z for x in range(-16, 17)], dtype=np.int32)
+    run34 = np.array([[x, -1, 0][:dim] for x in range(-20, 14)], dtype=np.int32)
+    ends = np.array([[md[0] - 1] + z, [-(md[0] - 1)] + z], dtype=np.int32)
+    return [("box", box(dim)), ("ball3", ball(3, dim)), ("wide", dict(offset_sets(md))["wide"]), ("run33", run33),
+            ("run34", run34), ("ends", ends)]
+
+
+def cloud_edge_case(n_col, dim):
+    """A map with n_col columns for the clouds' scan (d0 in 2D, d0 * d1 in 3D): scan_counts_kernel cuts the columns into
+    1 024 slices, so 1 / 1 023 / 1 024 / 1 025 columns are one slice in use, one short of all, all of one column each, and
+    the first length at which a slice holds two."""
+    md = {(1, 2): [1, 9], (1023, 2): [1023, 3], (1024, 2): [1024, 3], (1025, 2): [1025, 3],
+          (1, 3): [1, 1, 9], (1023, 3): [33, 31, 4], (1024, 3): [32, 32, 3], (1025, 3): [41, 25, 3]}[(n_col, dim)]
+    assert md[0] * (md[1] if dim == 3 else 1) == n_col
+    rng = np.random.default_rng(n_col + dim)
+    grid = rng.choice(np.array([0, 100, -1, 55], dtype=np.int8), size=int(np.prod(md)), p=[0.4, 0.25, 0.25, 0.1])
+    return ("cols%dd%d" % (n_col, dim), dim, np.ascontiguousarray(grid, dtype=np.int8), md, [0.05, -0.4, 0.2][:dim], 0.1)
 
 
 def ball(r, dim):
@@ -145,6 +196,42 @@ def test_offset_sets_cover_what_the_kernel_must_handle():
         assert changed == [False, False, True, True, True, True, True, True]
 
 
+def test_x_length_classes_cover_the_kernel_branches():
+    assert len(X_CASES) == 26 and {c[1] for c in X_CASES} == {2, 3}
+    assert sum(c[2].size % 16 != 0 for c in X_CASES) >= 13          # freeUnknown's tail of fewer than 16 cells
+    assert {c[3][0] % 16 == 0 for c in X_CASES} == {True, False}    # both the 16-byte and the byte paths
+    assert {16, 48, 80, 112} <= {c[3][0] for c in X_CASES if c[3][0] % 32 == 16}  # rows that end on a half word
+    for name, dim, grid, md, org, res in X_CASES:
+        assert len(set(md)) == len(md)
+        sets = dict(x_offset_sets(md))
+        dx = lambda k: sorted(int(v) for v in sets[k][:, 0])
+        assert dx("run33") == list(range(-16, 17)) and dx("run34") == list(range(-20, 14))
+        assert len(sets["ball3"]) == (29 if dim == 2 else 123)
+        assert np.abs(sets["ends"][:, 0]).tolist() == [md[0] - 1] * 2 and not sets["ends"][:, 1:].any()
+        for kind in range(3):
+            assert len(np_cloud(grid, md, org, res, kind)[0]) > 0, (name, kind)
+        if md[0] > 1:  # (one cell per row: no offset along x joins two cells, and "ends" is the zero offset)
+            changed = [label for label, o in sets.items() if not np.array_equal(np_dilate(grid, md, o), grid)]
+            assert changed == list(sets), (name, changed)
+
+
+def test_restatement_matches_the_golden_fixture_on_the_x_length_classes():
+    """The fixture also holds the reference MapUtil's results for the x lengths 16, 48, 80 and 1 (2D and 3D)."""
+    z = np.load(GOLDEN)
+    n = 0
+    for name, dim, grid, md, org, res in X_GOLDEN_CASES:
+        for label, offs in x_offset_sets(md):
+            assert np.array_equal(np_dilate(grid, md, offs), z["%s/dilate_%s" % (name, label)]), (name, label)
+            n += 1
+        assert np.array_equal(np_free_unknown(grid), z["%s/free_unknown" % name])
+        for kind in range(3):
+            pts, cells = np_cloud(grid, md, org, res, kind)
+            assert np.array_equal(index_steps(cells, md), z["%s/cloud%d_steps" % (name, kind)]), (name, kind)
+            assert np.array_equal(sha256(pts), z["%s/cloud%d_sha256" % (name, kind)]), (name, kind)
+            n += 1
+    assert n == 8 * (6 + 3)
+
+
 def _declared(header):
     text = open(os.path.join(ROOT, "include", header)).read()
     text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
@@ -217,6 +304,52 @@ def test_device_map_util_is_bit_identical(engine, case):
     assert np.array_equal(env.freeAll(), z["%s/free_all" % name])
     assert env.getCloud().shape == (0, dim) and env.getUnknownCloud().shape == (0, dim)
     assert env.getFreeCloud().shape == (grid.size, dim)
+    env.close()
+
+
+def _assert_clouds(env, grid, md, org, res, what):
+    for kind, fn in enumerate((env.getCloud, env.getFreeCloud, env.getUnknownCloud)):
+        pts = fn()
+        want, _ = np_cloud(grid, md, org, res, kind)
+        assert pts.shape == want.shape and pts.dtype == np.float64, (what, kind, pts.shape, want.shape)
+        assert np.array_equal(pts.view(np.uint64), want.view(np.uint64)), (what, kind)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("case", X_CASES, ids=[c[0] for c in X_CASES])
+def test_device_map_util_on_every_x_length_class(engine, case):
+    """dilate with six offset sets, freeUnknown and the three clouds on maps of every x-length class, against the numpy
+    restatement (itself pinned to the reference's MapUtil for the classes 16, 48, 80 and 1): cells and position bits."""
+    name, dim, grid, md, org, res = case
+    z = np.load(GOLDEN)
+    env = engine.EnvMap(dim)
+    for label, offs in x_offset_sets(md):
+        env.setMap(org, md, grid, res)
+        got = env.dilate(offs)
+        want = np_dilate(grid, md, offs)
+        bad = np.nonzero(got != want)[0]
+        assert bad.size == 0, "%s %s: %d cells differ, first %s got %s want %s" % (name, label, bad.size, bad[:5], got[bad[:5]], want[bad[:5]])
+        if md[0] in X_GOLDEN:
+            assert np.array_equal(got, z["%s/dilate_%s" % (name, label)]), (name, label)
+        _assert_clouds(env, want, md, org, res, "%s after %s" % (name, label))
+    env.setMap(org, md, grid, res)
+    _assert_clouds(env, grid, md, org, res, name)
+    got = env.freeUnknown()
+    assert np.array_equal(got, np_free_unknown(grid)) and (got != grid).any()
+    _assert_clouds(env, np_free_unknown(grid), md, org, res, name + " after freeUnknown")
+    assert env.getUnknownCloud().shape == (0, dim)
+    env.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("dim", [2, 3])
+@pytest.mark.parametrize("n_col", [1, 1023, 1024, 1025])
+def test_clouds_at_the_slice_edges_of_the_column_scan(engine, n_col, dim):
+    name, dim, grid, md, org, res = cloud_edge_case(n_col, dim)
+    env = engine.EnvMap(dim)
+    env.setMap(org, md, grid, res)
+    _assert_clouds(env, grid, md, org, res, name)
+    assert sum(len(np_cloud(grid, md, org, res, kind)[0]) for kind in range(3)) == grid.size
     env.close()
 
 
