@@ -254,7 +254,13 @@ int mplx_set_map(mplx_ctx *c, const int8_t *cells, const int32_t *dim, const dou
 int mplx_set_potential(mplx_ctx *c, const int8_t *cells) {
   if (!c) return MPLX_ERR_ARG;
   if (int rc = resolve_pending(c)) return rc;
-  if (!cells) { c->blk_ok = c->blk_ok && !c->has_pot; c->has_pot = false; return MPLX_OK; }
+  if (!cells) {
+    c->svc.streak = 0;
+    if (int rc = mplx_detail::svc_stop(c)) return rc;  // (no resident kernel serves a potential map today: kept in step with mplx_set_region)
+    c->blk_ok = c->blk_ok && !c->has_pot;
+    c->has_pot = false;
+    return MPLX_OK;
+  }
   if (!c->has_map) return fail(c, MPLX_ERR_STATE, "mplx_set_potential: set the map first");
   if (int rc = bind_device(c)) return rc;
   if (int rc = ensure(c, c->pot, (size_t)c->n_cells)) return rc;
@@ -269,7 +275,13 @@ int mplx_set_potential(mplx_ctx *c, const int8_t *cells) {
 int mplx_set_region(mplx_ctx *c, const uint8_t *cells) {
   if (!c) return MPLX_ERR_ARG;
   if (int rc = resolve_pending(c)) return rc;
-  if (!cells) { c->blk_ok = c->blk_ok && !c->has_region; c->has_region = false; return MPLX_OK; }
+  if (!cells) {
+    c->svc.streak = 0;
+    if (int rc = mplx_detail::svc_stop(c)) return rc;  // a resident kernel carries the region in its arguments
+    c->blk_ok = c->blk_ok && !c->has_region;
+    c->has_region = false;
+    return MPLX_OK;
+  }
   if (!c->has_map) return fail(c, MPLX_ERR_STATE, "mplx_set_region: set the map first");
   if (int rc = bind_device(c)) return rc;
   const size_t words = (size_t)((c->n_cells + 31) >> 5);
@@ -582,7 +594,9 @@ GridPlan plan_grid(const mplx_ctx *c) {
   if (c->tune.grid_rmax > 0) rmax = c->tune.grid_rmax;
   if (c->tune.grid_boxcap > 0) boxcap = c->tune.grid_boxcap;
   if (rmax < 1) rmax = 1;
-  const int ulex = (c->u_lex && !c->tune.no_lex) ? 1 : 0;  // = GridArgs::ulex
+  // (a table with a yaw-rate column under a flag without yaw is nested-loop order over FOUR factors, and the kernels
+  // enumerate three then: such a table goes through its per-control indices)
+  const int ulex = (c->u_lex && !c->tune.no_lex && (yaw || c->udim == c->dim)) ? 1 : 0;  // = GridArgs::ulex
   // the lexicographic kernel: same plan, its own LDS carve-up and occupancy
   g.lex = ulex && !yaw && !c->has_pot && !g.gather && c->tune.grid_lex && mplx::lex_covers(c->dim, p.control);
   if (lex_only && !g.lex) return GridPlan();
@@ -959,7 +973,7 @@ int lists_device(mplx_ctx *c, const double *d_nodes, int64_t n_nodes, int64_t no
     a.uidx = (const uint32_t *)c->uidx.p;
     a.nd0 = c->u_nd[0]; a.nd1 = c->u_nd[1]; a.nd2 = c->u_nd[2];
     a.ndp = gp.ndp;
-    a.ulex = (c->u_lex && !c->tune.no_lex) ? 1 : 0;
+    a.ulex = (c->u_lex && !c->tune.no_lex && (yaw || c->udim == c->dim)) ? 1 : 0;  // (as plan_grid)
     a.nU = c->nU;
     a.nodes = d_nodes; a.n_nodes = n_nodes; a.node_stride = node_stride;
     a.n_max = gp.n_max; a.rmax = gp.rmax; a.boxcap = gp.boxcap; a.grid_limit = gp.grid;

@@ -351,6 +351,7 @@ class EnvMap:
         self._dirty = True
         self.nU = 0
         self.map_dim = None
+        self._geometry = None  # (dim, origin, res) of the map the context holds
 
     # ---- lifetime
     def close(self):
@@ -382,7 +383,11 @@ class EnvMap:
         n = int(np.prod([int(x) for x in dim]))
         if cells.size != n:
             raise ValueError("map has %d cells, dim says %d" % (cells.size, n))
+        geometry = ([int(x) for x in dim], [float(x) for x in origin], float(res))
         _abi.check(self._ctx, _abi.lib().mplx_set_map(self._ctx, cells.ctypes.data, d, o, float(res)))
+        if geometry != self._geometry:
+            self.has_potential = False  # mplx_set_map drops the potential map (and the region) of another geometry
+        self._geometry = geometry
         self.map_dim = [int(x) for x in dim]
         self._ncell = n
 
