@@ -212,6 +212,34 @@ int mplx_expand_lists_device(mplx_ctx *ctx, const double *d_nodes, int64_t n_nod
 int mplx_expand_lists(mplx_ctx *ctx, const double *h_nodes, int64_t n_nodes, int64_t node_stride,
                       const mplx_succ_lists *h_out);
 
+/* ---- state rows that hold nothing but +0.0 (additive to ABI v9).
+ * A control of order K fills the derivative rows of order above K with the literal +0.0, and a control without the
+ * yaw bit the yaw row (primitive.h:322): for ACC in 3D that is 4 of the 14 state rows, 32 of the 132 bytes a
+ * store-bound launch writes per successor.  A launch need not store to such a row if EVERY entry of it, used or
+ * not, holds +0.0 already -- the buffer then has the same bytes either way.  The library keeps no record of
+ * buffers: the promise is a mask the caller carries beside its mplx_succ_lists, bit f = "every entry of state row f
+ * of this buffer is +0.0" (row f of the 4D+2, f < 4D+2).
+ *   Who may set a bit: whoever zero-filled the row (mplx_lists_zero_fill, or its own memset ordered before the launch)
+ *   and has let nothing but mplx_expand_lists_device_z launches, mplx_pack_lists_device and the library's deferred
+ *   heading-limit re-check write to or read from the state rows since, handing the mask returned by each _z launch
+ *   to the next.  Anything else that writes into the state rows -- mplx_expand_lists_device, mplx_memcpy_h2d,
+ *   mplx_memset with a non-zero value, mplx_debug_store_model, a kernel or copy of the caller's own, another buffer
+ *   under the same pointer -- voids it: pass 0 from then on, or zero-fill again.  A bit set wrongly is a stale row
+ *   nothing detects; a bit cleared wrongly only costs the stores.
+ *
+ * mplx_lists_zero_fill: asynchronous on the context stream; sets all 4D+2 state rows of d_lists (state_stride
+ * doubles each) to +0.0 and returns *zero_rows = (1 << (4D+2)) - 1; state == NULL: *zero_rows = 0.                 */
+int mplx_lists_zero_fill(mplx_ctx *ctx, const mplx_succ_lists *d_lists, uint32_t *zero_rows);
+/* mplx_expand_lists_device with the mask in and out.  const_rows = the rows this launch can only fill with +0.0,
+ * from the control flags alone.  The launch does not store to the rows *zero_rows & const_rows (nor to their
+ * line-padding entries) where its kernel supports that -- the three kernels of the GRID route; the rows it did
+ * skip: mplx_last_lists_zero_rows -- and on return *zero_rows holds the rows still known to be all +0.0: a subset
+ * of *zero_rows & const_rows (exactly that on the GRID route; 0 on the TILE and DENSE routes, which store every
+ * row).  The lists are the same bytes as mplx_expand_lists_device writes into a buffer whose rows were zero.
+ * zero_rows == NULL or *zero_rows == 0: exactly mplx_expand_lists_device.                                            */
+int mplx_expand_lists_device_z(mplx_ctx *ctx, const double *d_nodes, int64_t n_nodes, int64_t node_stride,
+                               const mplx_succ_lists *d_out, uint32_t *zero_rows);
+
 /* ---- successor post-processing on the device: what
  *      GraphSearch::Astar does with every successor right after get_succ
  *      (graph_search.h:84-88, :146), for a whole batch of lists in HBM ------ */
@@ -568,6 +596,9 @@ enum { MPLX_ROUTE_AUTO = 0, MPLX_ROUTE_DENSE = 1, MPLX_ROUTE_TILE = 2, MPLX_ROUT
 int mplx_set_lists_route(mplx_ctx *ctx, int route);
 /* Route taken by the last mplx_expand_lists* call (MPLX_ROUTE_*).            */
 int mplx_last_lists_route(const mplx_ctx *ctx);
+/* State rows the last mplx_expand_lists* call of the context did not store to (mplx_expand_lists_device_z); 0 for
+ * every other entry point and for the routes that store every row.                                                  */
+int mplx_last_lists_zero_rows(const mplx_ctx *ctx);
 /* ABI v6.  The GRID route has two kernels with identical results: the general factorised one, and one for the
  * control tables the reference's programs build -- the nested-loop (lexicographic) enumeration of per-axis values,
  * no yaw, occupancy map (expand_lex_kernel.hip; MPLX_GRID_LEX=0 sends those to the general kernel too).  Which one

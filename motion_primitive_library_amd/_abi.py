@@ -18,7 +18,7 @@ SYMBOLS = [
     "mplx_create", "mplx_destroy", "mplx_last_error", "mplx_abi_version",
     "mplx_set_map", "mplx_edit_map", "mplx_map_upload_bytes", "mplx_read_cells", "mplx_set_potential", "mplx_set_region", "mplx_set_params", "mplx_set_controls",
     "mplx_update_potential_map", "mplx_set_search_region_path",
-    "mplx_expand_device", "mplx_expand", "mplx_expand_lists_device", "mplx_expand_lists", "mplx_get_succ",
+    "mplx_expand_device", "mplx_expand", "mplx_expand_lists_device", "mplx_expand_lists", "mplx_lists_zero_fill", "mplx_expand_lists_device_z", "mplx_get_succ",
     "mplx_set_goal", "mplx_post_lists_device", "mplx_post_packed_device",
     "mplx_pack_lists_device", "mplx_comm_unique_id", "mplx_comm_init", "mplx_comm_destroy", "mplx_comm_broadcast_map",
     "mplx_comm_allgather_lists", "mplx_comm_schedule",
@@ -28,7 +28,7 @@ SYMBOLS = [
     "mplx_planner_create", "mplx_planner_destroy", "mplx_planner_attach_ctx", "mplx_planner_set_provider",
     "mplx_planner_set_map", "mplx_planner_edit_map", "mplx_planner_set_controls", "mplx_planner_configure", "mplx_planner_plan",
     "mplx_planner_trajectory", "mplx_planner_trajectory_end", "mplx_planner_closed_set", "mplx_planner_open_set", "mplx_planner_last_error", "mplx_planner_timing", "mplx_planner_set_prior_trajectory", "mplx_planner_set_prior_trajectory_potential", "mplx_planner_use_device_heuristic", "mplx_planner_set_lpastar", "mplx_planner_reset", "mplx_planner_linked_nodes", "mplx_planner_update_blocked_nodes", "mplx_planner_update_cleared_nodes", "mplx_planner_sub_state_space", "mplx_planner_set_edge_provider",
-    "mplx_selftest_math", "mplx_selftest_forward_state", "mplx_set_lists_route", "mplx_last_lists_route", "mplx_last_grid_kernel", "mplx_last_identity_form", "mplx_debug_store_model", "mplx_yaw_pin_stats", "mplx_service", "mplx_device_info",
+    "mplx_selftest_math", "mplx_selftest_forward_state", "mplx_set_lists_route", "mplx_last_lists_route", "mplx_last_lists_zero_rows", "mplx_last_grid_kernel", "mplx_last_identity_form", "mplx_debug_store_model", "mplx_yaw_pin_stats", "mplx_service", "mplx_device_info",
 ]
 
 # the symbols include/mplx_map_util.h declares (MapUtil's dilate / freeUnknown / freeAll / clouds on the device map),
@@ -163,6 +163,8 @@ def lib():
         "mplx_expand": (C.c_int, [vp, vp, i64, i64, C.POINTER(Succ)]),
         "mplx_expand_lists_device": (C.c_int, [vp, vp, i64, i64, C.POINTER(SuccLists)]),
         "mplx_expand_lists": (C.c_int, [vp, vp, i64, i64, C.POINTER(SuccLists)]),
+        "mplx_lists_zero_fill": (C.c_int, [vp, C.POINTER(SuccLists), C.POINTER(C.c_uint32)]),
+        "mplx_expand_lists_device_z": (C.c_int, [vp, vp, i64, i64, C.POINTER(SuccLists), C.POINTER(C.c_uint32)]),
         "mplx_get_succ": (C.c_int, [vp, vp, vp, vp, vp, C.POINTER(i32)]),
         "mplx_post_lists_device": (C.c_int, [vp, C.POINTER(SuccLists), i64, C.POINTER(GoalSpec), C.POINTER(Post)]),
         "mplx_check_edges": (C.c_int, [vp, vp, vp, i64, i64, C.POINTER(EdgesOut)]),
@@ -211,6 +213,7 @@ def lib():
         "mplx_selftest_forward_state": (C.c_int, [i32, i32, vp, vp, C.c_double, vp]),
         "mplx_set_lists_route": (C.c_int, [vp, C.c_int]),
         "mplx_last_lists_route": (C.c_int, [vp]),
+        "mplx_last_lists_zero_rows": (C.c_int, [vp]),
         "mplx_last_grid_kernel": (C.c_int, [vp]),
         "mplx_last_identity_form": (C.c_int, [vp]),
         "mplx_debug_store_model": (C.c_int, [vp, C.POINTER(SuccLists), i64]),

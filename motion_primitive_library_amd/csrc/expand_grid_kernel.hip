@@ -818,6 +818,9 @@ void expand_grid_kernel(const GridArgs A_kernarg) {
           if (A.l_state && (mine || pad16)) {
             double *o = A.l_state + idx;
             const int64_t ss = A.l_stride;
+            // rows that only ever receive the literal +0.0 are not stored to when the caller vouches they hold it
+            // already (GridArgs::l_zrows: a scalar bit test per row, padding lanes included)
+            const unsigned int zr = A.l_zrows;
 #pragma unroll
             for (int i = 0; i < D; i++) {
               const double *st = s_est + en[i] * (K - 1);
@@ -826,11 +829,13 @@ void expand_grid_kernel(const GridArgs A_kernarg) {
               const double top = (0.0 + u * T) + s_node[(K - 1) * D + i];    // field of order K - 1
               st_stream((double)((K >= 2) ? st[0] : top), &o[(0 * D + i) * ss]);
               st_stream((double)((K >= 3) ? st[1] : (K == 2 ? top : uK)), &o[(1 * D + i) * ss]);
-              st_stream((double)((K >= 4) ? st[2] : (K == 3 ? top : (K == 2 ? uK : 0.0))), &o[(2 * D + i) * ss]);
-              st_stream((double)((K == 4) ? top : (K == 3 ? uK : 0.0)), &o[(3 * D + i) * ss]);
+              if (K >= 2 || !((zr >> (2 * D + i)) & 1u))
+                st_stream((double)((K >= 4) ? st[2] : (K == 3 ? top : (K == 2 ? uK : 0.0))), &o[(2 * D + i) * ss]);
+              if (K >= 3 || !((zr >> (3 * D + i)) & 1u))
+                st_stream((double)((K == 4) ? top : (K == 3 ? uK : 0.0)), &o[(3 * D + i) * ss]);
             }
             // Waypoint::yaw: 0 for a control without yaw (primitive.h:322)
-            st_stream(YAW ? s_yawT[jy] : 0.0, &o[(4 * D) * ss]);
+            if (YAW || !((zr >> (4 * D)) & 1u)) st_stream(YAW ? s_yawT[jy] : 0.0, &o[(4 * D) * ss]);
             st_stream(node_t + A.dt, &o[(4 * D + 1) * ss]);  // env_map.h:161
           }
           // what the search computes for the successor next (graph_search.h:84-88), while it is in registers

@@ -643,6 +643,9 @@ void expand_pair_kernel(const GridArgs A_kernarg) {
           if (A.l_state && (mine || pad16)) {
             double *o = A.l_state + idx;
             const int64_t ss = A.l_stride;
+            // rows that only ever receive the literal +0.0 are not stored to when the caller vouches they hold it
+            // already (GridArgs::l_zrows: a scalar bit test per row, padding lanes included)
+            const unsigned int zr = A.l_zrows;
 #pragma unroll
             for (int i = 0; i < D; i++) {
               const double *st = s_est + en[i] * (K - 1);
@@ -652,7 +655,7 @@ void expand_pair_kernel(const GridArgs A_kernarg) {
               st_stream((double)st[0], &o[(0 * D + i) * ss]);
               st_stream((double)((K >= 3) ? st[1] : top), &o[(1 * D + i) * ss]);
               st_stream((double)((K == 3) ? top : uK), &o[(2 * D + i) * ss]);
-              st_stream((double)((K == 3) ? uK : 0.0), &o[(3 * D + i) * ss]);
+              if (K == 3 || !((zr >> (3 * D + i)) & 1u)) st_stream((double)((K == 3) ? uK : 0.0), &o[(3 * D + i) * ss]);
             }
             st_stream(s_yawT[jy], &o[(4 * D) * ss]);
             st_stream(node_t + A.dt, &o[(4 * D + 1) * ss]);  // env_map.h:161

@@ -928,10 +928,36 @@ mplx::TileArgs tile_args(mplx_ctx *c, const TilePlan &tp, const double *d_nodes,
   return a;
 }
 
+// State rows a launch with this control can only fill with the literal +0.0 (bit f = row f of the 4D+2): the derivative
+// rows of order above the control's, and the yaw row when the control carries no yaw (primitive.h:322).  From the
+// control flags alone, hence the same for every launch of a search.
+uint32_t const_zero_rows(int dim, int control) {
+  const int ctl = control & 0x0f;
+  const int order = ctl == MPLX_VEL ? 1 : ctl == MPLX_ACC ? 2 : ctl == MPLX_JRK ? 3 : 4;
+  uint32_t m = 0;
+  for (int b = order + 1; b <= 3; b++)
+    for (int i = 0; i < dim; i++) m |= 1u << (b * dim + i);
+  if (!(control & 0x10)) m |= 1u << (4 * dim);
+  return m;
+}
+
+// zero_rows (may be null = 0): in, the state rows of `o` the caller vouches hold +0.0 in every entry; out, the rows that
+// still do after this launch (mplx_expand_lists_device_z, include/mplx.h).  Rows in both the caller's mask and
+// const_zero_rows are not stored to by the kernels of the GRID route.  The yaw fix pass (resolve_pending) re-runs the
+// same kernel with the same GridArgs -- it skips the same rows and only replaces entries of the others -- and
+// mplx_pack_lists_device only reads: all-zero rows are invariant under both, so neither needs to know the mask.
 int lists_device(mplx_ctx *c, const double *d_nodes, int64_t n_nodes, int64_t node_stride,
-                 const mplx_succ_lists *o) {
+                 const mplx_succ_lists *o, uint32_t *zero_rows = nullptr) {
   const int F = 4 * c->dim + 2;
   const int route = c->lists_route;
+  const uint32_t const_rows = const_zero_rows(c->dim, c->prm.control);
+  const uint32_t in_rows = zero_rows ? (*zero_rows & ((1u << F) - 1u)) : 0u;
+  const uint32_t skip = o->state ? (in_rows & const_rows) : 0u;
+  c->last_zero_rows = 0;
+  // Until a route has launched with the skip, nothing is promised: a failure on the way, and the TILE and DENSE routes
+  // (which store every row, the tile kernel from computed values), leave the caller with "no row is known to be zero".
+  // Lists without state rows: no launch writes into them, the mask only narrows to the constant rows.
+  if (zero_rows) *zero_rows = o->state ? 0u : (in_rows & const_rows);
   if ((o->heur || o->flags) && !c->has_goal)
     return fail(c, MPLX_ERR_STATE, "the heur / flags rows of the lists need a goal: call mplx_set_goal first");
   GridPlan gp = (route == MPLX_ROUTE_AUTO || route == MPLX_ROUTE_GRID) ? plan_grid(c) : GridPlan();
@@ -989,6 +1015,7 @@ int lists_device(mplx_ctx *c, const double *d_nodes, int64_t n_nodes, int64_t no
     // 17^3).  With short lists it only adds bytes: C5 (81 controls, 24 successors per live node) writes 23.1 MB padded and
     // 18.8 MB unpadded in the same 46.5 us, C3 and C2 likewise (profiles/r06_line_pad_small_lists.txt).
     a.l_pad = (a.l_nstride % 32 == 0 && !c->tune.no_line_pad && c->nU >= mplx::kLinePadMinControls) ? 1 : 0;
+    a.l_zrows = skip;
     a.post = post_of(c, o);
     if (int rc = yaw_slot(c, &a.yaw)) return rc;
     // Yaw controls with a heading limit on a frontier of several nodes per wave: validate_yaw(t = 0) of every node
@@ -1077,6 +1104,9 @@ int lists_device(mplx_ctx *c, const double *d_nodes, int64_t n_nodes, int64_t no
       c->yaw_pending.push_back(p);
     }
     c->last_route = MPLX_ROUTE_GRID;
+    // every kernel of this route writes the literal +0.0 into the constant rows it does store to, and skipped `skip`
+    c->last_zero_rows = skip;
+    if (zero_rows && o->state) *zero_rows = skip;
     return MPLX_OK;
   }
   const TilePlan tp = (route == MPLX_ROUTE_AUTO || route == MPLX_ROUTE_TILE) ? plan_tile(c) : TilePlan();
@@ -1500,6 +1530,36 @@ int mplx_expand_lists_device(mplx_ctx *c, const double *d_nodes, int64_t n_nodes
   return lists_device(c, d_nodes, n_nodes, node_stride, d_out);
 }
 
+int mplx_expand_lists_device_z(mplx_ctx *c, const double *d_nodes, int64_t n_nodes, int64_t node_stride,
+                               const mplx_succ_lists *d_out, uint32_t *zero_rows) {
+  if (!zero_rows || *zero_rows == 0) return mplx_expand_lists_device(c, d_nodes, n_nodes, node_stride, d_out);
+  if (!c) return MPLX_ERR_ARG;
+  if (!d_out || !d_out->count || n_nodes < 0 || node_stride < n_nodes || (!d_nodes && n_nodes > 0))
+    return fail(c, MPLX_ERR_ARG, "mplx_expand_lists_device_z: bad arguments");
+  if (int rc = ready(c)) return rc;
+  if (n_nodes == 0) return MPLX_OK;  // nothing is written: the mask stands as it is
+  if (d_out->node_stride != 0 && d_out->node_stride < c->nU)
+    return fail(c, MPLX_ERR_ARG, "mplx_expand_lists_device_z: node_stride %lld < nU %d", (long long)d_out->node_stride, c->nU);
+  if (d_out->state && d_out->state_stride < n_nodes * (d_out->node_stride ? d_out->node_stride : c->nU))
+    return fail(c, MPLX_ERR_ARG, "mplx_expand_lists_device_z: state_stride < n_nodes*node_stride");
+  if (int rc = bind_device(c)) return rc;
+  return lists_device(c, d_nodes, n_nodes, node_stride, d_out, zero_rows);
+}
+
+int mplx_lists_zero_fill(mplx_ctx *c, const mplx_succ_lists *d_lists, uint32_t *zero_rows) {
+  if (!c) return MPLX_ERR_ARG;
+  if (!d_lists || !zero_rows) return fail(c, MPLX_ERR_ARG, "mplx_lists_zero_fill: NULL argument");
+  *zero_rows = 0;
+  if (!d_lists->state) return MPLX_OK;
+  if (d_lists->state_stride <= 0) return fail(c, MPLX_ERR_ARG, "mplx_lists_zero_fill: state_stride <= 0");
+  if (int rc = bind_device(c)) return rc;
+  if (int rc = mplx_detail::resolve_pending(c)) return rc;  // (a pending yaw fix pass would write after the fill)
+  const int F = 4 * c->dim + 2;
+  HIP_TRY(c, hipMemsetAsync(d_lists->state, 0, (size_t)F * (size_t)d_lists->state_stride * 8, c->stream));
+  *zero_rows = (1u << F) - 1u;
+  return MPLX_OK;
+}
+
 int mplx_expand_lists(mplx_ctx *c, const double *h_nodes, int64_t n_nodes, int64_t node_stride,
                       const mplx_succ_lists *h_out) {
   if (!c) return MPLX_ERR_ARG;
@@ -1722,6 +1782,7 @@ int mplx_set_lists_route(mplx_ctx *c, int route) {
 }
 
 int mplx_last_lists_route(const mplx_ctx *c) { return c ? c->last_route : MPLX_ERR_ARG; }
+int mplx_last_lists_zero_rows(const mplx_ctx *c) { return c ? (int)c->last_zero_rows : MPLX_ERR_ARG; }
 int mplx_last_grid_kernel(const mplx_ctx *c) {
   if (!c) return MPLX_ERR_ARG;
   if (c->last_route != MPLX_ROUTE_GRID) return MPLX_KERNEL_NONE;

@@ -84,6 +84,7 @@ struct mplx_ctx {
   } tune;
   int lists_route = MPLX_ROUTE_AUTO;
   int last_route = MPLX_ROUTE_AUTO;
+  uint32_t last_zero_rows = 0;  // state rows the last lists launch did not store to (mplx_last_lists_zero_rows)
   bool last_grid_pair = false;  // ... or to expand_pair_kernel.hip
   bool last_grid_lex = false;  // the last factorised launch went to expand_lex_kernel.hip (mplx_debug_last_kernel)
   int n_cus = 256;

@@ -205,8 +205,12 @@ struct GridArgs {
   int32_t *l_iters;
   int64_t l_nstride;  // entries reserved per node (>= nU)
   int32_t l_pad;      // 1: complete the last 128-byte line of every list row (node stride is a multiple of 32)
+  // State rows this launch does not store to (bit f = row f of l_state): rows the caller vouches hold +0.0 in every
+  // entry AND that this control can only fill with the literal +0.0 (mplx_expand_lists_device_z, include/mplx.h).
+  // Padding lanes of such a row are skipped as well.  0: every row is written.
+  uint32_t l_zrows;
   PostFuse post;      // heuristic / goal flags per successor, same indexing as the lists
-  YawPin yaw;         // heading-limit decisions pinned to the host libm (see YawPin); tab row: [c0, s0, cT[16], sT[16]]
+  YawPin yaw;        // heading-limit decisions pinned to the host libm (see YawPin); tab row: [c0, s0, cT[16], sT[16]]
   // Pre-screen of yaw controls (grid_prescreen_kernel): the nodes whose own heading passes validate_yaw at t = 0, in
   // frontier order, and their number (device memory, written by the pre-screen launch that precedes this one on the
   // stream).  Null: the kernel walks [0, n_nodes) and tests every node itself.
@@ -282,9 +286,11 @@ hipError_t launch_build_sat(int dim, const uint32_t *blk, const int32_t *mdim, u
 hipError_t launch_build_blocked_bits(const int8_t *map, const uint32_t *region, int64_t n_cells, int potential,
                                      uint32_t *out, hipStream_t stream);
 
-// store_model_kernel.hip (diagnostic): the list stores of a launch alone, into the lists themselves
+// store_model_kernel.hip (diagnostic): the list stores of a launch alone, into the lists themselves; bit f of skip_rows:
+// state row f is left alone (GridArgs::l_zrows of the launch that is modelled)
 hipError_t launch_store_model(const int32_t *count, int64_t n_nodes, int64_t S, int32_t *action, double *cost, uint64_t *hash,
-                              double *state, int64_t state_stride, int n_fields, int pad, int blocks, int mode, hipStream_t s);
+                              double *state, int64_t state_stride, int n_fields, int pad, int blocks, int mode,
+                              uint32_t skip_rows, hipStream_t s);
 
 // Batched edge re-validation (edge_kernel.hip).
 struct EdgeArgs {

@@ -72,7 +72,9 @@ extern "C" int mplx_debug_store_model(mplx_ctx *c, const mplx_succ_lists *L, int
   // (experiments: MPLX_STORE_MODEL_MODE / _WGS vary the order inside a node, the nodes per chunk and the workgroups per CU)
   const char *em = getenv("MPLX_STORE_MODEL_MODE"), *ew = getenv("MPLX_STORE_MODEL_WGS");
   const int mode = em ? atoi(em) : 0, wgs = ew && atoi(ew) > 0 ? atoi(ew) : 5;
+  // "the stores of the launch": the state rows the context's last lists launch did not store to are not stored to here
+  // either (mplx_last_lists_zero_rows); every other row receives unspecified values
   HIP_TRY(c, mplx::launch_store_model(L->count, n_nodes, S, L->action, L->cost, L->hash, L->state, L->state_stride,
-                                      4 * c->dim + 2, pad, c->n_cus * wgs, mode, c->stream));
+                                      4 * c->dim + 2, pad, c->n_cus * wgs, mode, c->last_zero_rows, c->stream));
   return MPLX_OK;
 }

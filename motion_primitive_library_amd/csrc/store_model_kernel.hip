@@ -3,7 +3,7 @@
 // entries) is exactly as long as writing them takes, and that this time is a property of the memory behind the allocation
 // (5.9 against 5.15 TB/s for the same pattern, profiles/r04_store_layouts_vs_kernel.txt).  This kernel writes, for every
 // node k, the first count[k] entries of every row present in the lists -- rounded up to whole 128-byte lines like the
-// expansion kernels do -- with unspecified values, in the same order (a wave per node, chunks of nodes dealt over the
+// expansion kernels do, and leaving alone the state rows that launch did not store to (skip_rows) -- with unspecified values, in the same order (a wave per node, chunks of nodes dealt over the
 // waves, `sc1 nt` stores): bench.py reports its time next to the kernel's (`roofline.store_only_ms`).
 // It OVERWRITES the successor entries (count[] stays): call it when the results have been consumed.
 #include "mplx_internal.h"
@@ -21,7 +21,7 @@ __device__ __forceinline__ void sm_st(T v, T *p) {
 // (a row's whole segment, then the next row) instead of step-major (64 entries of every row, then the next 64)
 __global__ __launch_bounds__(256) void store_model_kernel(const int32_t *count, int64_t n_nodes, int64_t S, int32_t *action,
                                                           double *cost, uint64_t *hash, double *state, int64_t state_stride,
-                                                          int n_fields, int pad, int mode) {
+                                                          int n_fields, int pad, int mode, uint32_t skip_rows) {
   const int lane = threadIdx.x & 63;
   const int64_t wave = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   const int64_t W = (int64_t)gridDim.x * 4;
@@ -40,8 +40,10 @@ __global__ __launch_bounds__(256) void store_model_kernel(const int32_t *count, 
         if (action) for (int e = lane; e < e32; e += 64) sm_st((int32_t)e, &action[base + e]);
         if (hash) for (int e = lane; e < e16; e += 64) sm_st((uint64_t)node, &hash[base + e]);
         if (state)
-          for (int f = 0; f < n_fields; f++)
+          for (int f = 0; f < n_fields; f++) {
+            if ((skip_rows >> f) & 1u) continue;
             for (int e = lane; e < e16; e += 64) sm_st((double)f, &state[(int64_t)f * state_stride + base + e]);
+          }
         if (cost) for (int e = lane; e < e16; e += 64) sm_st(1.0, &cost[base + e]);
         continue;
       }
@@ -51,23 +53,27 @@ __global__ __launch_bounds__(256) void store_model_kernel(const int32_t *count, 
         if (e < e16) {
           if (hash) sm_st((uint64_t)node, &hash[base + e]);
           if (state && !hybrid)
-            for (int f = 0; f < n_fields; f++) sm_st((double)f, &state[(int64_t)f * state_stride + base + e]);
+            for (int f = 0; f < n_fields; f++)
+              if (!((skip_rows >> f) & 1u)) sm_st((double)f, &state[(int64_t)f * state_stride + base + e]);
           if (cost) sm_st(1.0, &cost[base + e]);
         }
       }
       if (state && hybrid)
-        for (int f = 0; f < n_fields; f++)
+        for (int f = 0; f < n_fields; f++) {
+          if ((skip_rows >> f) & 1u) continue;
           for (int e = lane; e < e16; e += 64) sm_st((double)f, &state[(int64_t)f * state_stride + base + e]);
+        }
     }
 }
 
 }  // namespace
 
 hipError_t launch_store_model(const int32_t *count, int64_t n_nodes, int64_t S, int32_t *action, double *cost, uint64_t *hash,
-                              double *state, int64_t state_stride, int n_fields, int pad, int blocks, int mode, hipStream_t s) {
+                              double *state, int64_t state_stride, int n_fields, int pad, int blocks, int mode,
+                              uint32_t skip_rows, hipStream_t s) {
   if (n_nodes == 0) return hipSuccess;
   hipLaunchKernelGGL(store_model_kernel, dim3((unsigned)blocks), dim3(256), 0, s, count, n_nodes, S, action, cost, hash, state,
-                     state_stride, n_fields, pad, mode);
+                     state_stride, n_fields, pad, mode, skip_rows);
   return hipGetLastError();
 }
 

@@ -177,11 +177,32 @@ class Lists:
         self.hash = _alloc(env, n * 8, alloc) if want_hash else None
         # entries between consecutive state rows (mplx_succ_lists::state_stride): n_slots + state_pad
         self.state_stride = n + (STATE_ROW_PAD if state_pad is None else int(state_pad))
-        self.state = _alloc(env, self.state_stride * 8 * self.n_fields, alloc) if want_state else None
+        self._state = _alloc(env, self.state_stride * 8 * self.n_fields, alloc) if want_state else None
         self.iters = _alloc(env, n * 4, alloc) if want_iters else None
         # rows the expansion launch fills for the search (mplx_set_goal): default heuristic, goal flags
         self.heur = _alloc(env, n * 8, alloc) if want_heur else None
         self.flags = _alloc(env, n, alloc) if want_flags else None
+        # State rows known to hold +0.0 in every entry (include/mplx.h, mplx_expand_lists_device_z): the rows are
+        # zero-filled once here, and EnvMap.expand_lists_resident hands the mask from launch to launch, so that a launch
+        # does not store the rows its control can only fill with +0.0.  Whatever else writes into the state rows
+        # sets it to 0.  (Synchronised: the buffer may be handed to another context, i.e. another stream, next.)
+        self.zero_rows = 0
+        if self._state:
+            m = C.c_uint32(0)
+            s = self.c_struct()
+            _abi.check(env._ctx, _abi.lib().mplx_lists_zero_fill(env._ctx, C.byref(s), C.byref(m)))
+            _abi.check(env._ctx, _abi.lib().mplx_synchronize(env._ctx))
+            self.zero_rows = int(m.value)
+
+    @property
+    def state(self):
+        return self._state
+
+    @state.setter
+    def state(self, buf):
+        # another buffer under the same name: nothing is known about its contents (a fresh allocation is not zero)
+        self._state = buf
+        self.zero_rows = 0
 
     def c_struct(self):
         s = _abi.SuccLists()
@@ -676,10 +697,18 @@ class EnvMap:
         return no, eo
 
     def expand_lists_resident(self, frontier, lists, n_nodes=None):
-        """Asynchronous launch on HBM-resident buffers (mplx_expand_lists_device)."""
+        """Asynchronous launch on HBM-resident buffers: mplx_expand_lists_device_z for lists that carry the mask of
+        their all-zero state rows (`zero_rows`, env.Lists), mplx_expand_lists_device for any other object."""
         self._flush()
         n = frontier.n_nodes if n_nodes is None else int(n_nodes)
         s = lists.c_struct()
+        if hasattr(lists, "zero_rows"):
+            m = C.c_uint32(int(lists.zero_rows))
+            lists.zero_rows = 0  # (a call that fails on the way promises nothing)
+            _abi.check(self._ctx, _abi.lib().mplx_expand_lists_device_z(self._ctx, frontier.ptr, n, frontier.n_nodes,
+                                                                        C.byref(s), C.byref(m)))
+            lists.zero_rows = int(m.value)
+            return
         _abi.check(self._ctx, _abi.lib().mplx_expand_lists_device(self._ctx, frontier.ptr, n, frontier.n_nodes,
                                                                   C.byref(s)))
 
@@ -814,6 +843,13 @@ class EnvMap:
         self._flush()
         s = lists.c_struct()
         _abi.check(self._ctx, _abi.lib().mplx_debug_store_model(self._ctx, C.byref(s), lists.n_nodes if n_nodes is None else int(n_nodes)))
+        if hasattr(lists, "zero_rows"):  # it leaves alone the rows the last launch skipped and writes junk into all others
+            lists.zero_rows &= self.last_lists_zero_rows()
+
+    def last_lists_zero_rows(self):
+        """Bit mask of the state rows the last expand_lists* call of this context did not store to
+        (mplx_last_lists_zero_rows): 0 unless the lists carried a mask and the GRID route ran."""
+        return int(_abi.lib().mplx_last_lists_zero_rows(self._ctx))
 
     def last_grid_kernel(self):
         """Which kernel of the GRID route the last expand_lists* call ran: "lex" (expand_lex_kernel.hip: lexicographic
