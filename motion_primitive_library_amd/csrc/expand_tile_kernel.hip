@@ -38,7 +38,7 @@
 // as in expand_kernel.hip (-ffp-contract=off, explicit fma only inside the
 // division tail).
 //
-// SERVICE MODE (template flag SVC; mplx_api.cpp, "service").  A search asks for a few nodes at a time and waits for
+// SERVICE MODE (template flag SVC; lists_host.cpp, "service").  A search asks for a few nodes at a time and waits for
 // the answer: one launch + hipStreamSynchronize is 11 - 12 us before the kernel has done anything
 // (profiles/micro/mailbox_latency.hip), as much as the work itself.  In service mode the same kernel stays RESIDENT:
 // its workgroups wait for requests on a doorbell word in pinned host memory, run the tile loop on the nodes the host

@@ -75,7 +75,7 @@ void release_copy_buffers(mplx_ctx *c) {
 
 int copy_lists_to_host(mplx_ctx *c, const mplx_succ_lists &d, const mplx_succ_lists *h, int64_t n_nodes) {
   const int F = 4 * c->dim + 2;
-  const int64_t S = d.node_stride ? d.node_stride : c->nU;
+  const int64_t S = list_stride(c, &d);
   // counts first: they size everything else
   HIP_TRY(c, hipMemcpyAsync(h->count, d.count, (size_t)n_nodes * 4, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -237,7 +237,7 @@ int expand_lists_packed(mplx_ctx *c, const double *h_nodes, int64_t n_nodes, int
   const int64_t S = (c->nU + 31) & ~31;  // line-aligned node stride (see expand_grid_kernel.hip)
   const int64_t n_slots = n_nodes * S;
   {
-    // the batches of a search, from the second in a row: the resident kernel (mplx_api.cpp, "service"); the view
+    // the batches of a search, from the second in a row: the resident kernel (lists_host.cpp, "service"); the view
     // describes the lists in its landing block
     mplx_succ_lists want{}, v{};
     int32_t dummy_i = 0;
@@ -299,7 +299,7 @@ int expand_lists_packed(mplx_ctx *c, const double *h_nodes, int64_t n_nodes, int
     if (want_heur) d.heur = (double *)(hb + o_heur);
     d.node_stride = S;
     c->want_done = true;  // the kernel tells the host itself when the lists are in the block (DoneSignal)
-    const int rc_launch = lists_on_device(c, (const double *)hb, n_nodes, n_nodes, &d);
+    const int rc_launch = lists_device(c, (const double *)hb, n_nodes, n_nodes, &d);
     c->want_done = false;
     if (rc_launch) return rc_launch;
     if (int rc = wait_small_launch(c)) return rc;
@@ -349,7 +349,7 @@ int expand_lists_packed(mplx_ctx *c, const double *h_nodes, int64_t n_nodes, int
   d.hash = (uint64_t *)c->s_hash.p;
   if (want_state) { d.state = (double *)c->s_state.p; d.state_stride = n_slots; }
   d.node_stride = S;
-  if (int rc = lists_on_device(c, (const double *)c->s_nodes.p, n_nodes, n_nodes, &d)) return rc;
+  if (int rc = lists_device(c, (const double *)c->s_nodes.p, n_nodes, n_nodes, &d)) return rc;
   if (int rc = resolve_pending(c)) return rc;  // yaw pinning: lists final before they are packed
   int32_t *cnt = (int32_t *)(hb + o_cnt);
   int64_t *offs = (int64_t *)(hb + o_off);

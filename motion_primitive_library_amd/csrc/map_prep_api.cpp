@@ -71,7 +71,7 @@ int mplx_edit_map(mplx_ctx *c, const int64_t *cell_index, const int8_t *values, 
   HIP_TRY(c, hipStreamSynchronize(c->stream));  // the caller may free its arrays on return
   if (blk && c->sat_ok) {
     // the summed-area table (free-box shortcut of the factorised kernels) changes in every entry behind an edited cell:
-    // it is switched off and rebuilt by the first launch large enough to be worth it (mplx_api.cpp, lists_device)
+    // it is switched off and rebuilt by the first launch large enough to be worth it (lists_route.cpp, lists_grid)
     c->sat_ok = false;
     c->sat_stale = true;
   }

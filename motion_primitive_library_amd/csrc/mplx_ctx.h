@@ -109,7 +109,7 @@ struct mplx_ctx {
   bool want_done = false;            // set by a caller that will wait for the launch on the spot (around lists_device)
   bool done_armed = false;           // ... and the launch that went in carries the signal
   int64_t done_waits = 0, done_timeouts = 0;
-  // Resident form of the tiled kernel for the small synchronous batches of a search ("service", mplx_api.cpp and
+  // Resident form of the tiled kernel for the small synchronous batches of a search ("service", lists_host.cpp and
   // expand_tile_kernel.hip): requests go through a mailbox in pinned memory instead of launch + synchronise.
   struct Service {
     bool running = false;   // a resident kernel has been launched and has not been seen to leave
@@ -197,9 +197,7 @@ inline int fail(mplx_ctx *c, int code, const char *fmt, ...) {
   catch (const std::exception &e) { return mplx_detail::fail((c), MPLX_ERR_NOMEM, "unexpected exception: %s", e.what()); } \
   catch (...) { return mplx_detail::fail((c), MPLX_ERR_NOMEM, "unexpected exception"); }
 
-int svc_stop(mplx_ctx *c);  // mplx_api.cpp
-int svc_request(mplx_ctx *c, const double *h_nodes, int64_t n_nodes, int64_t node_stride, const mplx_succ_lists *h_out,
-                bool *handled, mplx_succ_lists *view);
+int svc_stop(mplx_ctx *c);  // lists_host.cpp (the other declarations of that unit: below)
 
 // Every entry point that touches the device comes through here first.  A resident service kernel reads the
 // context's tables through the arguments it was launched with and writes into the context's landing block: it is
@@ -245,15 +243,55 @@ struct PackedLists {
 };
 int expand_lists_packed(mplx_ctx *c, const double *h_nodes, int64_t n_nodes, int64_t node_stride, bool want_state,
                         PackedLists *out, bool want_heur = false);  // want_state = false: out->state == nullptr, the kernel skips the states
-// mplx_api.cpp: readiness check and the route dispatch behind mplx_expand_lists*
-int ctx_ready(mplx_ctx *c);
-int lists_on_device(mplx_ctx *c, const double *d_nodes, int64_t n_nodes, int64_t node_stride, const mplx_succ_lists *d);
+// ---- what crosses the boundaries of the API translation units (every such function is declared here and only here)
 
-// mplx_api.cpp: synchronises the stream and, where a launch flagged heading-limit decisions within rounding noise of
-// their threshold, re-expands those nodes with the host libm's trig values (YawPin, mplx_internal.h).  Every
-// synchronising entry point and every call that changes what a pending launch read goes through it.
+constexpr size_t kLdsBudget = 160 * 1024;   // LDS of a CU: what the workgroups resident on it share
+constexpr size_t kTcntOffset = 64 * 64 * 8; // mplx_ctx::tables: ttab [64][64] doubles, then tcnt [64] bytes, then 3 reciprocals
+
+// entries reserved per node in the rows of `o` (mplx_succ_lists::node_stride, 0 = one per control)
+inline int64_t list_stride(const mplx_ctx *c, const mplx_succ_lists *o) { return o->node_stride ? o->node_stride : c->nU; }
+
+// Line padding (expand_grid_kernel.hip) pays where a launch is bound by its stores -- the large control tables (C4: 729,
+// 17^3).  With short lists it only adds bytes: C5 (81 controls, 24 successors per live node) writes 23.1 MB padded and
+// 18.8 MB unpadded in the same 46.5 us, C3 and C2 likewise (profiles/r06_line_pad_small_lists.txt).
+inline int line_pad(const mplx_ctx *c, int64_t stride) {
+  return (stride % 32 == 0 && !c->tune.no_line_pad && c->nU >= mplx::kLinePadMinControls) ? 1 : 0;
+}
+
+// derivative order of the control input: 1 VEL .. 4 SNP (the yaw bit is ignored)
+inline int control_order(int control) {
+  const int ctl = control & 0x0f;
+  return ctl == MPLX_VEL ? 1 : ctl == MPLX_ACC ? 2 : ctl == MPLX_JRK ? 3 : 4;
+}
+
+// mplx_api.cpp: map, parameters and controls are set and fit each other
+int ctx_ready(mplx_ctx *c);
+
+// lists_route.cpp: the route dispatch behind mplx_expand_lists* (GRID / TILE / DENSE), its plans and argument blocks.
+struct TilePlan {
+  bool ok = false;
+  int npb = 1, tile_pairs = 0, wl_cap = 0, n_max = 0, u_offset = 0, grid = 0;
+};
+TilePlan plan_tile(const mplx_ctx *c);
+int ensure_tables(mplx_ctx *c);
+mplx::ExpandArgs expand_args(mplx_ctx *c, const double *d_nodes, int64_t n_nodes, int64_t node_stride, const mplx_succ *o);
+mplx::TileArgs tile_args(mplx_ctx *c, const TilePlan &tp, const double *d_nodes, int64_t n_nodes, int64_t node_stride,
+                         const mplx_succ_lists *o);
+int launch_grid(mplx_ctx *c, mplx::GridArgs *a);
+int lists_device(mplx_ctx *c, const double *d_nodes, int64_t n_nodes, int64_t node_stride, const mplx_succ_lists *o,
+                 uint32_t *zero_rows = nullptr);
+
+// yaw_pin.cpp: heading-limit decisions pinned to the host libm (YawPin, mplx_internal.h).  yaw_slot: the detection block
+// of the next launch.  resolve_pending: synchronises the stream and, where a launch flagged decisions within rounding
+// noise of their threshold, re-expands those nodes with the host libm's trig values.  Every synchronising entry point
+// and every call that changes what a pending launch read goes through it.
+int yaw_slot(mplx_ctx *c, mplx::YawPin *y);
 int resolve_pending(mplx_ctx *c, bool stream_is_idle = false);
-// after a small-batch launch through lists_on_device with want_done set: waits for it (kernel-written word, or the
+
+// lists_host.cpp: the host-pointer lists calls and the resident service kernel behind their small batches.
+int svc_request(mplx_ctx *c, const double *h_nodes, int64_t n_nodes, int64_t node_stride, const mplx_succ_lists *h_out,
+                bool *handled, mplx_succ_lists *view);
+// after a small-batch launch through lists_device with want_done set: waits for it (kernel-written word, or the
 // stream); *idle = everything enqueued on the context's stream so far is complete
 int wait_small_launch(mplx_ctx *c);
 

@@ -78,7 +78,7 @@ __device__ __forceinline__ unsigned int wave_reduce_or(unsigned int v) {
 // Lattice searches hit that tie all the time (yaw_max and the yaw steps are the same multiples of 0.5), so it must
 // not count as ambiguous; it is decided identically by the device and by the host -- PROVIDED the host's cosine of
 // the pair sincos(+-yaw_max) (what GCC makes of primitive.h:519-520) is bit-equal to its stand-alone cos(yaw_max)
-// (primitive.h:521).  The host checks exactly that once per launch set-up (yaw_slot, mplx_api.cpp) and passes
+// (primitive.h:521).  The host checks exactly that once per launch set-up (yaw_slot, yaw_pin.cpp) and passes
 // tie_yaw = yaw_max when it holds, NaN when it does not: then nothing compares equal and the tie goes through the
 // host-pinned pass like every other decision inside the band.
 __device__ __forceinline__ bool near_limit(double d, double cos_lim, double margin, double vy, double yaw,

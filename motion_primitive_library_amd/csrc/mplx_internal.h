@@ -1,4 +1,4 @@
-// Internal declarations shared by the C-ABI layer (mplx_api.cpp) and the HIP
+// Internal declarations shared by the C-ABI layer (mplx_api.cpp and the units beside it) and the HIP
 // kernels (expand_kernel.hip).  Not installed; the public surface is
 // include/mplx.h.
 #ifndef MPLX_INTERNAL_H
@@ -228,7 +228,7 @@ bool pair_covers(int dim, int control);
 hipError_t launch_expand_pair(int dim, int control, const GridArgs &a, hipStream_t s);
 int pair_resident_blocks(int dim, int control, int ndy, size_t lds);
 constexpr int kWorkCounters = 64;
-// list rows are completed to whole 128-byte lines only for control tables of at least this many entries (mplx_api.cpp)
+// list rows are completed to whole 128-byte lines only for control tables of at least this many entries (line_pad, mplx_ctx.h)
 constexpr int kLinePadMinControls = 256;
 // lane-per-node validate_yaw(t = 0) over a whole frontier (expand_grid_kernel.hip); fills live / live_n of `a`'s launch
 // (live_n is zero when the launch begins; the launch zeroes live_zero, the counter of the NEXT pre-screen of the stream)

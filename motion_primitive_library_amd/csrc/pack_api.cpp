@@ -21,7 +21,7 @@ extern "C" int mplx_pack_lists_device(mplx_ctx *c, const mplx_succ_lists *L, int
   if (int rc = bind_device(c)) return rc;
   if (int rc = resolve_pending(c)) return rc;  // yaw pinning: the lists must be final
   const int F = 4 * c->dim + 2;
-  const int64_t S = L->node_stride ? L->node_stride : c->nU;
+  const int64_t S = list_stride(c, L);
   HIP_TRY(c, mplx::launch_scan_counts(L->count, n_nodes, o->offs, c->stream));
   if (o->count && n_nodes > 0)
     HIP_TRY(c, hipMemcpyAsync(o->count, L->count, (size_t)n_nodes * 4, hipMemcpyDeviceToDevice, c->stream));
@@ -67,8 +67,8 @@ extern "C" int mplx_debug_store_model(mplx_ctx *c, const mplx_succ_lists *L, int
   if (!c->has_U) return fail(c, MPLX_ERR_STATE, "mplx_debug_store_model: controls not set");
   if (int rc = bind_device(c)) return rc;
   if (int rc = resolve_pending(c)) return rc;
-  const int64_t S = L->node_stride ? L->node_stride : c->nU;
-  const int pad = (S % 32 == 0 && !c->tune.no_line_pad && c->nU >= mplx::kLinePadMinControls) ? 1 : 0;  // (the expansion's own rule)
+  const int64_t S = list_stride(c, L);
+  const int pad = line_pad(c, S);  // (the expansion's own rule)
   // (experiments: MPLX_STORE_MODEL_MODE / _WGS vary the order inside a node, the nodes per chunk and the workgroups per CU)
   const char *em = getenv("MPLX_STORE_MODEL_MODE"), *ew = getenv("MPLX_STORE_MODEL_WGS");
   const int mode = em ? atoi(em) : 0, wgs = ew && atoi(ew) > 0 ? atoi(ew) : 5;

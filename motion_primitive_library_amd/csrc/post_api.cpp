@@ -27,7 +27,7 @@ static int post_lists_impl(mplx_ctx *c, const mplx_succ_lists *d_lists, int64_t 
   if (int rc = bind_device(c)) return rc;
   if (int rc = resolve_pending(c)) return rc;  // yaw pinning: the lists must be final
   const int D = c->dim, F = 4 * D + 2;
-  const int64_t S = d_lists->node_stride ? d_lists->node_stride : c->nU;
+  const int64_t S = list_stride(c, d_lists);
   const int64_t n = n_nodes * S;
   if (n >= 0x7f7f7f7fLL) return fail(c, MPLX_ERR_ARG, "mplx_post_lists_device: %lld list entries exceed the int32 index", (long long)n);
   mplx::PostArgs a{};

@@ -78,7 +78,7 @@ class Model:
                      potential=None if without_potential else self.potential, region=self.region, **self.params)
 
     def service_eligible(self):
-        """plan_tile (mplx_api.cpp) restated for the tables of this module: the configurations the resident kernel serves."""
+        """plan_tile (lists_route.cpp) restated for the tables of this module: the configurations the resident kernel serves."""
         p = self.params
         if self.control & 0x10 or self.potential is not None or self.nU > 1024:
             return False

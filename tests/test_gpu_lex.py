@@ -124,7 +124,7 @@ def test_lex_kernel_is_not_taken_outside_its_scope(engine, monkeypatch):
 
 @pytest.mark.parametrize("case", ["n_max_62", "unbounded_velocity", "9261_controls", "8000_controls_in_scope"])
 def test_lex_scope_exits_still_give_the_reference_lists(engine, oracle_lib, case):
-    """The edges of the lexicographic kernel's scope (expand_lex_kernel.hip header; plan_grid in mplx_api.cpp): more than 61
+    """The edges of the lexicographic kernel's scope (expand_lex_kernel.hip header; plan_grid in lists_route.cpp): more than 61
     samples per primitive (v_max * dt / res > 60), no velocity bound (v_max <= 0: the sample count has no bound either)
     and more than 8 192 controls leave the factorised route altogether -- AUTO must pick a kernel that covers them and the
     lists must still be the reference's; 8 000 controls (20^3) are the largest cubic table still inside."""
