@@ -35,6 +35,9 @@ SYMBOLS = [
 # exported by the same library; kept apart from SYMBOLS, which is exactly mplx.h + mplx_debug.h
 MAP_UTIL_SYMBOLS = ["mplx_map_dilate", "mplx_map_free", "mplx_map_cloud"]
 CELL_OCCUPIED, CELL_FREE, CELL_UNKNOWN = 0, 1, 2
+# ... and the ones include/mplx_rollout.h declares (batched rollouts), kept apart in the same way
+ROLLOUT_SYMBOLS = ["mplx_rollout_device", "mplx_rollout"]
+ROLLOUT_BAD_ACTION, ROLLOUT_HEADING_BAND = 4, 0x80
 
 ROUTE_AUTO, ROUTE_DENSE, ROUTE_TILE, ROUTE_GRID = 0, 1, 2, 3
 
@@ -60,6 +63,14 @@ class SuccLists(C.Structure):
         ("count", C.c_void_p), ("action", C.c_void_p), ("cost", C.c_void_p), ("hash", C.c_void_p),
         ("state", C.c_void_p), ("state_stride", C.c_int64), ("iters", C.c_void_p), ("node_stride", C.c_int64),
         ("heur", C.c_void_p), ("flags", C.c_void_p),  # ABI v8: written by the expansion launch (mplx_set_goal)
+    ]
+
+
+class RolloutOut(C.Structure):
+    _fields_ = [
+        ("status", C.c_void_p), ("steps", C.c_void_p), ("cost", C.c_void_p), ("prefix_cost", C.c_void_p),
+        ("end_state", C.c_void_p), ("end_stride", C.c_int64),
+        ("end_hash", C.c_void_p), ("end_heur", C.c_void_p), ("end_flags", C.c_void_p),
     ]
 
 
@@ -223,8 +234,10 @@ def lib():
         "mplx_map_dilate": (C.c_int, [vp, vp, i32, vp]),
         "mplx_map_free": (C.c_int, [vp, C.c_int, vp]),
         "mplx_map_cloud": (C.c_int, [vp, C.c_int, vp, i64, C.POINTER(i64)]),
+        "mplx_rollout_device": (C.c_int, [vp, vp, i64, i64, vp, i64, i32, i64, C.POINTER(RolloutOut)]),
+        "mplx_rollout": (C.c_int, [vp, vp, i64, i64, vp, i64, i32, i64, C.POINTER(RolloutOut)]),
     }
-    for name in SYMBOLS + MAP_UTIL_SYMBOLS:
+    for name in SYMBOLS + MAP_UTIL_SYMBOLS + ROLLOUT_SYMBOLS:
         fn = getattr(L, name)  # AttributeError if the library does not export it
         fn.restype, fn.argtypes = sig[name]
     _lib = L

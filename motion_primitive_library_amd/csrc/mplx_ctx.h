@@ -98,7 +98,8 @@ struct mplx_ctx {
   mplx_detail::DevBuf d_status, d_cost, d_hash, d_state, d_iters;
   // staging for the host-pointer entry points
   mplx_detail::DevBuf s_nodes, s_status, s_cost, s_hash, s_state, s_iters, s_count, s_action;
-  // small host-pointer batches: one device arena + one pinned mirror (mplx_expand_lists)
+  // small host-pointer batches: one device arena + one pinned mirror (mplx_expand_lists); the arena is also the staging
+  // block of mplx_rollout (rollout_api.cpp)
   mplx_detail::DevBuf s_arena;
   void *h_arena = nullptr;
   size_t h_arena_cap = 0;

@@ -404,6 +404,29 @@ hipError_t launch_compact_lists(const CompactArgs &args, hipStream_t stream);
 // `stream`.  Returns hipSuccess or the launch error.
 hipError_t launch_expand(int dim, int control, const ExpandArgs &args, hipStream_t stream);
 
+// Batched rollouts (rollout_kernel.hip, include/mplx_rollout.h): one lane walks one action sequence, one pair per
+// step, with the pair arithmetic of expand_kernel.hip (mplx_pair_device.h).
+struct RolloutArgs {
+  ExpandArgs env;          // map, region, parameters and controls as expand_args() fills them; nodes / slots unused
+  const double *starts;    // field-major [4D+2][start_stride]
+  int64_t n_starts, start_stride;  // n_starts == 1: every rollout starts at column 0
+  const int32_t *actions;  // step-major: rollout k at step h = actions[h * action_stride + k]
+  int64_t n_rollouts, action_stride;
+  int32_t horizon;
+  int32_t u_lds;           // 1: the control table is staged in LDS (nU * udim doubles of dynamic LDS)
+  int32_t band;            // 1: heading-limit decisions within env.yaw.margin of their threshold set bit 0x80 of status
+  // outputs, any may be null
+  uint8_t *status;
+  int32_t *steps;
+  double *cost, *prefix_cost;
+  double *end_state;
+  int64_t end_stride;
+  uint64_t *end_hash;
+  PostFuse post;           // goal of mplx_set_goal; heur / flags = the end_heur / end_flags rows ([n_rollouts]) or null
+};
+constexpr size_t kRolloutLdsControls = 32 * 1024;  // largest control table staged in LDS (C4: 729 x 3 x 8 B = 17.5 KB)
+hipError_t launch_rollout(int dim, int control, const RolloutArgs &args, hipStream_t stream);
+
 // Element-wise math probe (see mplx_selftest_math in mplx.h).
 hipError_t launch_math_probe(int op, const double *a, const double *b, double *out, int64_t n,
                              hipStream_t stream);

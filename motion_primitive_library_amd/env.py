@@ -31,6 +31,7 @@ VEL, ACC, JRK, SNP = 0x01, 0x03, 0x07, 0x0F
 VELxYAW, ACCxYAW, JRKxYAW, SNPxYAW = 0x11, 0x13, 0x17, 0x1F
 
 SLOT_SKIP_SAME, SLOT_FINITE, SLOT_BLOCKED, SLOT_SKIP_DYN = 0, 1, 2, 3
+ROLLOUT_BAD_ACTION, ROLLOUT_HEADING_BAND = _abi.ROLLOUT_BAD_ACTION, _abi.ROLLOUT_HEADING_BAND  # include/mplx_rollout.h
 
 
 class Waypoint:
@@ -152,6 +153,60 @@ class Slots:
 
     def free(self):
         for b in (self.status, self.cost, self.hash, self.state, self.iters):
+            if b is not None:
+                b.free()
+
+
+def _device_ptr(buf):
+    """The device address of a DeviceArray (or anything with .ptr) or of a torch tensor (data_ptr())."""
+    if hasattr(buf, "ptr"):
+        return int(buf.ptr)
+    if hasattr(buf, "data_ptr"):
+        return int(buf.data_ptr())
+    raise TypeError("need a device buffer with .ptr or .data_ptr(), got %r" % type(buf))
+
+
+class Rollouts:
+    """HBM-resident output rows of n rollouts (mplx_rollout_out)."""
+
+    def __init__(self, env, n_rollouts, want_end=True, want_goal_rows=False):
+        self.n = int(n_rollouts)
+        self.n_fields = env.n_fields
+        n = max(self.n, 1)
+        self.status = DeviceArray(env, n)
+        self.steps = DeviceArray(env, n * 4)
+        self.cost = DeviceArray(env, n * 8)
+        self.prefix_cost = DeviceArray(env, n * 8)
+        self.end_state = DeviceArray(env, n * 8 * self.n_fields) if want_end else None
+        self.end_hash = DeviceArray(env, n * 8) if want_end else None
+        self.end_heur = DeviceArray(env, n * 8) if want_goal_rows else None
+        self.end_flags = DeviceArray(env, n) if want_goal_rows else None
+
+    def c_struct(self):
+        s = _abi.RolloutOut()
+        s.status, s.steps, s.cost, s.prefix_cost = self.status.ptr, self.steps.ptr, self.cost.ptr, self.prefix_cost.ptr
+        s.end_state = self.end_state.ptr if self.end_state else None
+        s.end_stride = self.n
+        s.end_hash = self.end_hash.ptr if self.end_hash else None
+        s.end_heur = self.end_heur.ptr if self.end_heur else None
+        s.end_flags = self.end_flags.ptr if self.end_flags else None
+        return s
+
+    def download(self):
+        n = self.n
+        out = {"status": self.status.download(np.uint8, (n,)), "steps": self.steps.download(np.int32, (n,)),
+               "cost": self.cost.download(np.float64, (n,)), "prefix_cost": self.prefix_cost.download(np.float64, (n,))}
+        if self.end_state:
+            out["end_state"] = self.end_state.download(np.float64, (self.n_fields, n))
+            out["end_hash"] = self.end_hash.download(np.uint64, (n,))
+        if self.end_heur:
+            out["end_heur"] = self.end_heur.download(np.float64, (n,))
+            out["end_flags"] = self.end_flags.download(np.uint8, (n,))
+        return out
+
+    def free(self):
+        for b in (self.status, self.steps, self.cost, self.prefix_cost, self.end_state, self.end_hash, self.end_heur,
+                  self.end_flags):
             if b is not None:
                 b.free()
 
@@ -814,6 +869,66 @@ class EnvMap:
         s = slots.c_struct()
         _abi.check(self._ctx, _abi.lib().mplx_expand_device(
             self._ctx, frontier.ptr + 8 * int(node_offset), n, frontier.n_nodes, C.byref(s)))
+
+    # ---- batched rollouts (include/mplx_rollout.h): cost and validity of action sequences on the device map
+    def rollout(self, starts, actions, want_end=True, want_goal_rows=False):
+        """K action sequences from their start states, one pair per step with the primitive, the limits and the cost
+        of get_succ, on the map the device holds now (mplx_rollout; synchronous).
+        starts: [4D+2][K], or one state ([4D+2] / [4D+2][1]) every rollout starts from; actions: [H][K] indices into
+        the control table, -1 ends a sequence early.  Returns numpy arrays: status (SLOT_* of the step that stopped the
+        rollout, SLOT_FINITE when it is complete, ROLLOUT_BAD_ACTION), steps, cost (+inf unless complete), prefix_cost;
+        want_end: end_state [4D+2][K], end_hash; want_goal_rows (needs set_goal): end_heur, end_flags."""
+        self._flush()
+        actions = np.ascontiguousarray(actions, dtype=np.int32)
+        if actions.ndim != 2 or actions.shape[0] < 1:
+            raise ValueError("actions must be [H][K] with H >= 1")
+        H, K = actions.shape
+        starts = np.ascontiguousarray(starts, dtype=np.float64)
+        if starts.ndim == 1:
+            starts = starts.reshape(-1, 1)
+        if starts.shape[0] != self.n_fields or starts.shape[1] not in (1, K):
+            raise ValueError("starts must be [%d][%d] or one state" % (self.n_fields, K))
+        out = {"status": np.zeros(K, np.uint8), "steps": np.zeros(K, np.int32), "cost": np.zeros(K, np.float64),
+               "prefix_cost": np.zeros(K, np.float64)}
+        o = _abi.RolloutOut()
+        o.status, o.steps, o.cost = out["status"].ctypes.data, out["steps"].ctypes.data, out["cost"].ctypes.data
+        o.prefix_cost = out["prefix_cost"].ctypes.data
+        if want_end:
+            out["end_state"] = np.zeros((self.n_fields, K), np.float64)
+            out["end_hash"] = np.zeros(K, np.uint64)
+            o.end_state, o.end_stride, o.end_hash = out["end_state"].ctypes.data, K, out["end_hash"].ctypes.data
+        if want_goal_rows:
+            out["end_heur"] = np.zeros(K, np.float64)
+            out["end_flags"] = np.zeros(K, np.uint8)
+            o.end_heur, o.end_flags = out["end_heur"].ctypes.data, out["end_flags"].ctypes.data
+        _abi.check(self._ctx, _abi.lib().mplx_rollout(self._ctx, starts.ctypes.data, starts.shape[1], starts.shape[1],
+                                                       actions.ctypes.data, K, H, K, C.byref(o)))
+        return out
+
+    def alloc_rollouts(self, n_rollouts, want_end=True, want_goal_rows=False):
+        return Rollouts(self, n_rollouts, want_end, want_goal_rows)
+
+    def rollout_resident(self, starts, actions, out, horizon, n_rollouts=None, n_starts=None, start_stride=None,
+                         action_stride=None):
+        """Asynchronous launch on HBM-resident buffers (mplx_rollout_device).  starts: float64 [4D+2][start_stride],
+        actions: int32 [horizon][action_stride], each a DeviceArray or anything with .ptr / data_ptr() -- a torch tensor
+        on the device is read in place, without a copy; out: env.Rollouts (alloc_rollouts).  n_starts: n_rollouts or 1
+        (default: start_stride); the strides default to n_rollouts.  Rollouts that met a heading-limit decision
+        inside the band of the yaw pinning carry ROLLOUT_HEADING_BAND in their status (rollout() resolves them).
+        The launch runs on the CONTEXT's stream: a caller that filled the inputs on another stream (torch's) makes
+        that stream finish first (torch.cuda.synchronize() or an event), and calls synchronize() before it reads
+        `out` or overwrites the inputs."""
+        self._flush()
+        n = out.n if n_rollouts is None else int(n_rollouts)
+        if n > out.n:
+            raise ValueError("out holds %d rollouts, %d asked for" % (out.n, n))
+        sstride = n if start_stride is None else int(start_stride)
+        if n_starts is None:
+            n_starts = n if start_stride is None else sstride
+        astride = n if action_stride is None else int(action_stride)
+        o = out.c_struct()
+        _abi.check(self._ctx, _abi.lib().mplx_rollout_device(self._ctx, _device_ptr(starts), int(n_starts), sstride,
+                                                              _device_ptr(actions), n, int(horizon), astride, C.byref(o)))
 
     def synchronize(self):
         _abi.check(self._ctx, _abi.lib().mplx_synchronize(self._ctx))

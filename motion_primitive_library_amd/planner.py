@@ -428,3 +428,17 @@ class MapPlanner:
 
     def getTrajCost(self):
         return self._summary.cost
+
+    def checkTraj(self):
+        """The last plan's trajectory -- its start state and one control index per segment -- walked again on the map
+        the device holds NOW (EnvMap.rollout): (status, steps, cost).  status SLOT_FINITE and cost == getTrajCost()
+        while the trajectory is still valid; after a map edit the slot status of the first segment that is not
+        (SLOT_BLOCKED, ...), the number of segments before it, and +inf."""
+        if self.env is None:
+            raise RuntimeError("checkTraj needs the engine's own env (provider=None)")
+        traj = self.getTraj()
+        if len(traj.actions) == 0:
+            raise RuntimeError("checkTraj: the last plan has no trajectory")
+        r = self.env.rollout(np.asarray(traj.nodes[0], dtype=np.float64), np.asarray(traj.actions, dtype=np.int32).reshape(-1, 1),
+                             want_end=False)
+        return int(r["status"][0]), int(r["steps"][0]), float(r["cost"][0])
