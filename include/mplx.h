@@ -193,7 +193,8 @@ typedef struct {
    * successor is still in registers; needs mplx_set_goal:     */
   double *heur;            /* [n_nodes*S] env_base::get_heur, default branch (env_base.h:46-64), or NULL */
   uint8_t *flags;          /* [n_nodes*S] bit 0 inside the goal tolerances (env_map.h:25-37, no ray trace),
-                              bit 1 same lattice state as the goal (env_base.h:47), or NULL              */
+                              bit 1 same lattice state as the goal (env_base.h:47), or NULL; the ray
+                              trace: mplx_goal_sight_device (mplx_ray.h) ORs bit 3 into this row        */
 } mplx_succ_lists;
 
 /* Batched get_succ producing lists; device pointers, asynchronous on the
@@ -268,7 +269,8 @@ int mplx_set_goal(mplx_ctx *ctx, const mplx_goal_spec *goal);
  *          goal's own lattice state, else w * |pos - goal.pos|_inf / v_max
  *          (w * |.|_inf when v_max <= 0)
  *   flags  bit 0: inside the goal tolerances (env_map.h:25-37; the ray trace of
- *          :38-43 is left to the caller), bit 1: same lattice state as the
+ *          :38-43 is left to the caller -- on the device: mplx_goal_sight_device,
+ *          mplx_ray.h, which ORs bit 3 in), bit 1: same lattice state as the
  *          goal, bit 2 (with canon): first successor of the batch with its hash
  *   canon  list index (node*S + j) of the first successor of the batch with the
  *          same lattice hash -- the search's node identity (waypoint.h:128-135) */

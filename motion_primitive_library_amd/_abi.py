@@ -38,6 +38,10 @@ CELL_OCCUPIED, CELL_FREE, CELL_UNKNOWN = 0, 1, 2
 # ... and the ones include/mplx_rollout.h declares (batched rollouts), kept apart in the same way
 ROLLOUT_SYMBOLS = ["mplx_rollout_device", "mplx_rollout"]
 ROLLOUT_BAD_ACTION, ROLLOUT_HEADING_BAND = 4, 0x80
+# ... and the ones include/mplx_ray.h declares (MapUtil::rayTrace, the ray trace of is_goal)
+RAY_SYMBOLS = ["mplx_ray_trace_device", "mplx_ray_trace", "mplx_goal_sight_device"]
+RAY_LEFT_MAP, RAY_HIT, RAY_BAD, RAY_TRUNCATED = 1, 2, 4, 8
+FLAG_GOAL_BLOCKED = 8
 
 ROUTE_AUTO, ROUTE_DENSE, ROUTE_TILE, ROUTE_GRID = 0, 1, 2, 3
 
@@ -72,6 +76,11 @@ class RolloutOut(C.Structure):
         ("end_state", C.c_void_p), ("end_stride", C.c_int64),
         ("end_hash", C.c_void_p), ("end_heur", C.c_void_p), ("end_flags", C.c_void_p),
     ]
+
+
+class RayOut(C.Structure):
+    _fields_ = [("status", C.c_void_p), ("n_cells", C.c_void_p), ("first_hit", C.c_void_p), ("cells", C.c_void_p),
+                ("cell_cap", C.c_int32)]
 
 
 class PackedLists(C.Structure):
@@ -236,8 +245,11 @@ def lib():
         "mplx_map_cloud": (C.c_int, [vp, C.c_int, vp, i64, C.POINTER(i64)]),
         "mplx_rollout_device": (C.c_int, [vp, vp, i64, i64, vp, i64, i32, i64, C.POINTER(RolloutOut)]),
         "mplx_rollout": (C.c_int, [vp, vp, i64, i64, vp, i64, i32, i64, C.POINTER(RolloutOut)]),
+        "mplx_ray_trace_device": (C.c_int, [vp, vp, vp, i64, i64, i64, i32, C.POINTER(RayOut)]),
+        "mplx_ray_trace": (C.c_int, [vp, vp, vp, i64, i64, i64, i32, C.POINTER(RayOut)]),
+        "mplx_goal_sight_device": (C.c_int, [vp, C.POINTER(SuccLists), i64, C.POINTER(GoalSpec), vp]),
     }
-    for name in SYMBOLS + MAP_UTIL_SYMBOLS + ROLLOUT_SYMBOLS:
+    for name in SYMBOLS + MAP_UTIL_SYMBOLS + ROLLOUT_SYMBOLS + RAY_SYMBOLS:
         fn = getattr(L, name)  # AttributeError if the library does not export it
         fn.restype, fn.argtypes = sig[name]
     _lib = L

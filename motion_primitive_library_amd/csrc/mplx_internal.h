@@ -427,6 +427,34 @@ struct RolloutArgs {
 constexpr size_t kRolloutLdsControls = 32 * 1024;  // largest control table staged in LDS (C4: 729 x 3 x 8 B = 17.5 KB)
 hipError_t launch_rollout(int dim, int control, const RolloutArgs &args, hipStream_t stream);
 
+// MapUtil::rayTrace on the device map and the ray trace of env_map::is_goal (ray_kernel.hip, ray_api.cpp;
+// include/mplx_ray.h).  The int8 occupancy map, never the potential copy or the blocked bits.
+struct RayArgs {
+  const int8_t *map;
+  int32_t dim0, dim1, dim2;
+  double org0, org1, org2;
+  double res;
+  // query: points field-major [D][stride]; p2_stride == 0: one p2 (D consecutive doubles)
+  const double *p1, *p2;
+  int64_t n, stride, p2_stride;
+  uint8_t *status;
+  int32_t *n_cells, *first_hit, *cells;
+  int32_t cell_cap;
+};
+struct GoalSightArgs {
+  RayArgs ray;             // map and geometry; the point and output fields are unused
+  const int32_t *count;    // lists: [n_nodes]
+  const double *state;     // lists: position rows 0 .. D-1 of [4D+2][sstride]
+  int64_t n_nodes, nstride, sstride;
+  double goal[3];
+  uint8_t *flags;          // [n_nodes * nstride]; bit 0 read, bit 3 ORed in
+  int32_t *work;           // [n_nodes * nstride] list indices of the candidates
+  uint32_t *work_count;    // their number; zero before the scan
+};
+// lanes in {4, 16, 64}
+hipError_t launch_ray_trace(int dim, int lanes, const RayArgs &a, hipStream_t s);
+hipError_t launch_goal_sight(int dim, int lanes, int n_cus, const GoalSightArgs &a, hipStream_t s);
+
 // Element-wise math probe (see mplx_selftest_math in mplx.h).
 hipError_t launch_math_probe(int op, const double *a, const double *b, double *out, int64_t n,
                              hipStream_t stream);

@@ -32,6 +32,8 @@ VELxYAW, ACCxYAW, JRKxYAW, SNPxYAW = 0x11, 0x13, 0x17, 0x1F
 
 SLOT_SKIP_SAME, SLOT_FINITE, SLOT_BLOCKED, SLOT_SKIP_DYN = 0, 1, 2, 3
 ROLLOUT_BAD_ACTION, ROLLOUT_HEADING_BAND = _abi.ROLLOUT_BAD_ACTION, _abi.ROLLOUT_HEADING_BAND  # include/mplx_rollout.h
+RAY_LEFT_MAP, RAY_HIT, RAY_BAD, RAY_TRUNCATED = _abi.RAY_LEFT_MAP, _abi.RAY_HIT, _abi.RAY_BAD, _abi.RAY_TRUNCATED  # include/mplx_ray.h
+FLAG_GOAL_BLOCKED = _abi.FLAG_GOAL_BLOCKED
 
 
 class Waypoint:
@@ -207,6 +209,41 @@ class Rollouts:
     def free(self):
         for b in (self.status, self.steps, self.cost, self.prefix_cost, self.end_state, self.end_hash, self.end_heur,
                   self.end_flags):
+            if b is not None:
+                b.free()
+
+
+class Rays:
+    """HBM-resident output rows of n rays (mplx_ray_out); cells only with cell_cap > 0."""
+
+    def __init__(self, env, n, cell_cap=0, want_counts=True):
+        self.n, self.cell_cap = int(n), int(cell_cap)
+        n = max(self.n, 1)
+        self.status = DeviceArray(env, n)
+        self.n_cells = DeviceArray(env, n * 4) if want_counts else None
+        self.first_hit = DeviceArray(env, n * 4) if want_counts else None
+        self.cells = DeviceArray(env, n * self.cell_cap * 4) if self.cell_cap > 0 else None
+
+    def c_struct(self):
+        s = _abi.RayOut()
+        s.status = self.status.ptr
+        s.n_cells = self.n_cells.ptr if self.n_cells else None
+        s.first_hit = self.first_hit.ptr if self.first_hit else None
+        s.cells = self.cells.ptr if self.cells else None
+        s.cell_cap = self.cell_cap
+        return s
+
+    def download(self):
+        out = {"status": self.status.download(np.uint8, (self.n,))}
+        if self.n_cells:
+            out["n_cells"] = self.n_cells.download(np.int32, (self.n,))
+            out["first_hit"] = self.first_hit.download(np.int32, (self.n,))
+        if self.cells:
+            out["cells"] = self.cells.download(np.int32, (self.n, self.cell_cap))
+        return out
+
+    def free(self):
+        for b in (self.status, self.n_cells, self.first_hit, self.cells):
             if b is not None:
                 b.free()
 
@@ -929,6 +966,80 @@ class EnvMap:
         o = out.c_struct()
         _abi.check(self._ctx, _abi.lib().mplx_rollout_device(self._ctx, _device_ptr(starts), int(n_starts), sstride,
                                                               _device_ptr(actions), n, int(horizon), astride, C.byref(o)))
+
+    # ---- MapUtil::rayTrace and the ray trace of is_goal on the device map (include/mplx_ray.h)
+    def ray_trace(self, p1, p2, cell_cap=0, lanes=0, cells=None):
+        """MapUtil::rayTrace for n point pairs on the int8 map the device holds now (mplx_ray_trace; synchronous).
+        p1: [D][n] field-major like node rows (or one point [D]); p2: [D][n], or one point [D] every ray ends at.
+        Returns numpy arrays: status (RAY_LEFT_MAP | RAY_HIT | RAY_BAD | RAY_TRUNCATED bits), n_cells (the length of
+        the reference's list), first_hit (getIndex of the first occupied cell of the list, -1 without one) and, with
+        cell_cap > 0, cells [n][cell_cap]: getIndex of the first cell_cap emitted cells in order, the entries past
+        min(n_cells, cell_cap) untouched (`cells`: the array to write into, default zeros).  lanes: 0 (automatic) or
+        4 / 16 / 64 lanes of a wavefront per ray; the results do not depend on it."""
+        D = self.dim
+        p1 = np.ascontiguousarray(p1, dtype=np.float64)
+        if p1.ndim == 1:
+            p1 = p1.reshape(D, 1)
+        if p1.ndim != 2 or p1.shape[0] != D:
+            raise ValueError("p1 must be [%d][n]" % D)
+        n = p1.shape[1]
+        p2 = np.ascontiguousarray(p2, dtype=np.float64)
+        if p2.shape == (D,):
+            p2_stride = 0
+        elif p2.shape == (D, n):
+            p2_stride = n
+        else:
+            raise ValueError("p2 must be [%d][%d] or one point" % (D, n))
+        out = {"status": np.zeros(n, np.uint8), "n_cells": np.zeros(n, np.int32), "first_hit": np.zeros(n, np.int32)}
+        o = _abi.RayOut()
+        o.status, o.n_cells, o.first_hit = out["status"].ctypes.data, out["n_cells"].ctypes.data, out["first_hit"].ctypes.data
+        if cell_cap > 0:
+            if cells is None:
+                cells = np.zeros((n, int(cell_cap)), np.int32)
+            if cells.shape != (n, int(cell_cap)) or cells.dtype != np.int32 or not cells.flags.c_contiguous:
+                raise ValueError("cells must be a contiguous int32 [%d][%d]" % (n, cell_cap))
+            out["cells"] = cells
+            o.cells, o.cell_cap = cells.ctypes.data, int(cell_cap)
+        _abi.check(self._ctx, _abi.lib().mplx_ray_trace(self._ctx, p1.ctypes.data, p2.ctypes.data, n, n, p2_stride,
+                                                         int(lanes), C.byref(o)))
+        return out
+
+    def alloc_rays(self, n, cell_cap=0, want_counts=True):
+        return Rays(self, n, cell_cap, want_counts)
+
+    def ray_trace_resident(self, p1, p2, out, n=None, stride=None, p2_stride=None, lanes=0):
+        """Asynchronous launch on HBM-resident buffers (mplx_ray_trace_device).  p1, p2: float64 [D][stride] /
+        [D][p2_stride], each a DeviceArray or anything with .ptr / data_ptr(); p2_stride=0: p2 is one point (D doubles).
+        out: env.Rays (alloc_rays).  The strides default to n.  Runs on the context's stream: synchronize() before
+        reading `out`."""
+        n = out.n if n is None else int(n)
+        if n > out.n:
+            raise ValueError("out holds %d rays, %d asked for" % (out.n, n))
+        stride = n if stride is None else int(stride)
+        p2_stride = n if p2_stride is None else int(p2_stride)
+        o = out.c_struct()
+        _abi.check(self._ctx, _abi.lib().mplx_ray_trace_device(self._ctx, _device_ptr(p1), _device_ptr(p2), n, stride,
+                                                                p2_stride, int(lanes), C.byref(o)))
+
+    def goal_sight(self, lists, flags=None, goal_row=None, tol_pos=0.5, n_nodes=None):
+        """The ray trace of env_map::is_goal (env_map.h:38-43) on HBM-resident lists (mplx_goal_sight_device;
+        asynchronous): every emitted successor whose flags byte has bit 0 (inside the goal tolerances) and whose ray
+        to the goal position meets an occupied cell gets FLAG_GOAL_BLOCKED ORed in; afterwards (flags & 9) == 1 is
+        the reference's is_goal.  flags: the device row to work on (default lists.flags, the row the expansion
+        launch wrote).  goal_row: the goal waypoint (with tol_pos) instead of the one of set_goal."""
+        self._flush()
+        n = lists.n_nodes if n_nodes is None else int(n_nodes)
+        s = lists.c_struct()
+        fl = lists.flags if flags is None else flags
+        g = None
+        if goal_row is not None:
+            goal = np.ascontiguousarray(goal_row, dtype=np.float64)
+            g = _abi.GoalSpec()
+            g.goal, g.control, g.tol_pos = goal.ctypes.data, int(self._p.control), float(tol_pos)
+            g.w, g.v_max = float(self._p.w), float(self._p.v_max)
+            g.tol_vel = g.tol_acc = g.tol_yaw = -1.0
+        _abi.check(self._ctx, _abi.lib().mplx_goal_sight_device(self._ctx, C.byref(s), n, None if g is None else C.byref(g),
+                                                                 None if fl is None else _device_ptr(fl)))
 
     def synchronize(self):
         _abi.check(self._ctx, _abi.lib().mplx_synchronize(self._ctx))

@@ -21,7 +21,7 @@ from .env import EnvMap, Waypoint
 
 class MapUtil:
     """MapUtil<Dim> (map_util.h): the map a planner reads, and the operations a user runs on it before planning --
-    dilate, freeUnknown, freeAll and the voxel clouds -- on the device.
+    dilate, freeUnknown, freeAll, the voxel clouds and rayTrace -- on the device.
 
     The reference's planners share the MapUtil by pointer, so an operation after setMapUtil reaches the next plan() of
     every planner holding it.  Here the operation runs on the engine context of the planner the MapUtil was installed
@@ -70,6 +70,23 @@ class MapUtil:
 
     def getUnknownCloud(self):
         return self._env().getUnknownCloud()
+
+    def rayTrace(self, pt1, pt2):
+        """MapUtil::rayTrace (map_util.h:117-134): the cells the ray from pt1 to pt2 passes, (n, D) int32 cell
+        coordinates in order, without the cells of the end points; stops where the ray leaves the map."""
+        env = self._env()
+        p1 = np.asarray(pt1, dtype=np.float64).reshape(-1)
+        p2 = np.asarray(pt2, dtype=np.float64).reshape(-1)
+        n = int(env.ray_trace(p1, p2)["n_cells"][0])
+        D = len(self.map_dim)
+        if n == 0:
+            return np.zeros((0, D), np.int32)
+        idx = env.ray_trace(p1, p2, cell_cap=n)["cells"][0].astype(np.int64)
+        out = np.empty((n, D), np.int32)
+        for i in range(D):
+            out[:, i] = idx % self.map_dim[i]
+            idx //= self.map_dim[i]
+        return out
 
     # ---- where the operations run
     def _attach(self, planner):
