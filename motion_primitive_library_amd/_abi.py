@@ -42,6 +42,11 @@ ROLLOUT_BAD_ACTION, ROLLOUT_HEADING_BAND = 4, 0x80
 RAY_SYMBOLS = ["mplx_ray_trace_device", "mplx_ray_trace", "mplx_goal_sight_device"]
 RAY_LEFT_MAP, RAY_HIT, RAY_BAD, RAY_TRUNCATED = 1, 2, 4, 8
 FLAG_GOAL_BLOCKED = 8
+# ... and the ones include/mplx_traj.h declares (Trajectory: info, samples, traverse_trajectory)
+TRAJ_SYMBOLS = ["mplx_traj_info_device", "mplx_traj_info", "mplx_traj_sample_device", "mplx_traj_sample",
+                "mplx_traj_traverse_device", "mplx_traj_traverse"]
+TRAJ_EMPTY, TRAJ_BAD_ACTION, TRAJ_BAD = 1, 2, 4
+TRAJ_COMMAND, TRAJ_WAYPOINT = 0, 1
 
 ROUTE_AUTO, ROUTE_DENSE, ROUTE_TILE, ROUTE_GRID = 0, 1, 2, 3
 
@@ -81,6 +86,30 @@ class RolloutOut(C.Structure):
 class RayOut(C.Structure):
     _fields_ = [("status", C.c_void_p), ("n_cells", C.c_void_p), ("first_hit", C.c_void_p), ("cells", C.c_void_p),
                 ("cell_cap", C.c_int32)]
+
+
+class TrajSet(C.Structure):
+    _fields_ = [("starts", C.c_void_p), ("n_starts", C.c_int64), ("start_stride", C.c_int64), ("actions", C.c_void_p),
+                ("n_traj", C.c_int64), ("horizon", C.c_int32), ("action_stride", C.c_int64)]
+
+
+class TrajInfoOut(C.Structure):
+    _fields_ = [("status", C.c_void_p), ("n_segs", C.c_void_p), ("total_time", C.c_void_p), ("effort", C.c_void_p),
+                ("effort_stride", C.c_int64), ("seg_state", C.c_void_p), ("seg_stride", C.c_int64)]
+
+
+class TrajTimes(C.Structure):
+    _fields_ = [("form", C.c_int32), ("n_uniform", C.c_int32), ("times", C.c_void_p), ("n_times", C.c_int64),
+                ("time_stride", C.c_int64)]
+
+
+class TrajSampleOut(C.Structure):
+    _fields_ = [("out", C.c_void_p), ("row_stride", C.c_int64), ("sample_stride", C.c_int64), ("status", C.c_void_p)]
+
+
+class TrajTraverseOut(C.Structure):
+    _fields_ = [("status", C.c_void_p), ("cost", C.c_void_p), ("n_samples", C.c_void_p), ("n_cells", C.c_void_p),
+                ("stop_sample", C.c_void_p)]
 
 
 class PackedLists(C.Structure):
@@ -248,8 +277,14 @@ def lib():
         "mplx_ray_trace_device": (C.c_int, [vp, vp, vp, i64, i64, i64, i32, C.POINTER(RayOut)]),
         "mplx_ray_trace": (C.c_int, [vp, vp, vp, i64, i64, i64, i32, C.POINTER(RayOut)]),
         "mplx_goal_sight_device": (C.c_int, [vp, C.POINTER(SuccLists), i64, C.POINTER(GoalSpec), vp]),
+        "mplx_traj_info_device": (C.c_int, [vp, C.POINTER(TrajSet), C.POINTER(TrajInfoOut)]),
+        "mplx_traj_info": (C.c_int, [vp, C.POINTER(TrajSet), C.POINTER(TrajInfoOut)]),
+        "mplx_traj_sample_device": (C.c_int, [vp, C.POINTER(TrajSet), C.POINTER(TrajTimes), C.POINTER(TrajSampleOut)]),
+        "mplx_traj_sample": (C.c_int, [vp, C.POINTER(TrajSet), C.POINTER(TrajTimes), C.POINTER(TrajSampleOut)]),
+        "mplx_traj_traverse_device": (C.c_int, [vp, C.POINTER(TrajSet), i32, C.POINTER(TrajTraverseOut)]),
+        "mplx_traj_traverse": (C.c_int, [vp, C.POINTER(TrajSet), i32, C.POINTER(TrajTraverseOut)]),
     }
-    for name in SYMBOLS + MAP_UTIL_SYMBOLS + ROLLOUT_SYMBOLS + RAY_SYMBOLS:
+    for name in SYMBOLS + MAP_UTIL_SYMBOLS + ROLLOUT_SYMBOLS + RAY_SYMBOLS + TRAJ_SYMBOLS:
         fn = getattr(L, name)  # AttributeError if the library does not export it
         fn.restype, fn.argtypes = sig[name]
     _lib = L

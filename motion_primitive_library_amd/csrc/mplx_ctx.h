@@ -53,6 +53,7 @@ struct mplx_ctx {
   mplx_detail::DevBuf post_keys;                 // node-identity table (post_api.cpp)
   mplx_detail::DevBuf post_ws;                   // workspace of the partitioned identity pass (identity_kernel.hip)
   mplx_detail::DevBuf ray_work;                  // candidate worklist of mplx_goal_sight_device (ray_api.cpp)
+  mplx_detail::DevBuf traj_tab;                  // segment table of the trajectory calls (traj_api.cpp); grow-only
   mplx_detail::DevBuf prep_lut, prep_a, prep_b;  // map preprocessing scratch (map_prep_api.cpp)
   bool blk_ok = false;   // blocked-bit map matches the current map + region
   bool u_factored = false;

@@ -455,6 +455,42 @@ struct GoalSightArgs {
 hipError_t launch_ray_trace(int dim, int lanes, const RayArgs &a, hipStream_t s);
 hipError_t launch_goal_sight(int dim, int lanes, int n_cus, const GoalSightArgs &a, hipStream_t s);
 
+// Trajectory<Dim> on the device (traj_kernel.hip, traj_api.cpp; include/mplx_traj.h).  The chain launch writes the
+// segment table of a trajectory set into scratch memory of the context; the sample and traverse launches read it.
+// Table, N = n_traj, H = horizon, NC = 5 D + 2: S[N], n[N] (samples - 1 of the traversal, -1 = BAD), status[N], T[N],
+// tau[H + 1][N], seg[H][NC][N] -- per segment and axis the coefficients c1 .. c5 of primitive.h:34-50 (c0 is always 0),
+// then the yaw primitive's c4 (yaw rate) and c5 (yaw); all zero-padded rows are never read.
+struct TrajArgs {
+  ExpandArgs env;          // map, potential, geometry, parameters and controls as expand_args() fills them
+  const double *starts;    // field-major [4D+2][start_stride]
+  int64_t n_starts, start_stride;
+  const int32_t *actions;  // step-major
+  int64_t n_traj, action_stride;
+  int32_t horizon;
+  int32_t yaw;             // the control flag has the yaw bit
+  int32_t *tab_S, *tab_n;
+  uint8_t *tab_status;
+  double *tab_T, *tab_tau, *tab_seg;
+  // info outputs (chain launch), any may be null
+  uint8_t *status;
+  int32_t *n_segs;
+  double *total_time, *effort, *seg_state;
+  int64_t effort_stride, seg_stride;
+  // sample launch
+  int32_t n_uniform;       // N, or 0: times from `times`
+  const double *times;
+  int64_t time_stride;     // 0: shared by all trajectories
+  int64_t count;           // samples per trajectory: N + 1 or Q
+  double *out;
+  int64_t row_stride, sample_stride;
+  // traverse launch, any may be null
+  double *cost;
+  int32_t *n_samples, *n_cells, *stop_sample;
+};
+hipError_t launch_traj_chain(int dim, int control, const TrajArgs &a, hipStream_t s);
+hipError_t launch_traj_sample(int dim, int form, const TrajArgs &a, hipStream_t s);
+hipError_t launch_traj_traverse(int dim, int lanes, const TrajArgs &a, hipStream_t s);  // lanes in {4, 16, 64}
+
 // Element-wise math probe (see mplx_selftest_math in mplx.h).
 hipError_t launch_math_probe(int op, const double *a, const double *b, double *out, int64_t n,
                              hipStream_t stream);

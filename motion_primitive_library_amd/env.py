@@ -34,6 +34,8 @@ SLOT_SKIP_SAME, SLOT_FINITE, SLOT_BLOCKED, SLOT_SKIP_DYN = 0, 1, 2, 3
 ROLLOUT_BAD_ACTION, ROLLOUT_HEADING_BAND = _abi.ROLLOUT_BAD_ACTION, _abi.ROLLOUT_HEADING_BAND  # include/mplx_rollout.h
 RAY_LEFT_MAP, RAY_HIT, RAY_BAD, RAY_TRUNCATED = _abi.RAY_LEFT_MAP, _abi.RAY_HIT, _abi.RAY_BAD, _abi.RAY_TRUNCATED  # include/mplx_ray.h
 FLAG_GOAL_BLOCKED = _abi.FLAG_GOAL_BLOCKED
+TRAJ_EMPTY, TRAJ_BAD_ACTION, TRAJ_BAD = _abi.TRAJ_EMPTY, _abi.TRAJ_BAD_ACTION, _abi.TRAJ_BAD  # include/mplx_traj.h
+TRAJ_COMMAND, TRAJ_WAYPOINT = _abi.TRAJ_COMMAND, _abi.TRAJ_WAYPOINT
 
 
 class Waypoint:
@@ -246,6 +248,91 @@ class Rays:
         for b in (self.status, self.n_cells, self.first_hit, self.cells):
             if b is not None:
                 b.free()
+
+
+class TrajInfo:
+    """HBM-resident rows of mplx_traj_info_out for n trajectories of up to `horizon` segments."""
+
+    def __init__(self, env, n, horizon, want_states=False):
+        self.n, self.horizon, self.n_fields = int(n), int(horizon), env.n_fields
+        n = max(self.n, 1)
+        self.status = DeviceArray(env, n)
+        self.n_segs = DeviceArray(env, n * 4)
+        self.total_time = DeviceArray(env, n * 8)
+        self.effort = DeviceArray(env, 5 * n * 8)
+        self.seg_state = DeviceArray(env, self.n_fields * (self.horizon + 1) * n * 8) if want_states else None
+
+    def c_struct(self):
+        s = _abi.TrajInfoOut()
+        s.status, s.n_segs, s.total_time, s.effort = self.status.ptr, self.n_segs.ptr, self.total_time.ptr, self.effort.ptr
+        s.effort_stride = s.seg_stride = self.n
+        s.seg_state = self.seg_state.ptr if self.seg_state else None
+        return s
+
+    def download(self):
+        n = self.n
+        out = {"status": self.status.download(np.uint8, (n,)), "n_segs": self.n_segs.download(np.int32, (n,)),
+               "total_time": self.total_time.download(np.float64, (n,)), "effort": self.effort.download(np.float64, (5, n))}
+        if self.seg_state:
+            out["seg_state"] = self.seg_state.download(np.float64, (self.n_fields, self.horizon + 1, n))
+        return out
+
+    def free(self):
+        for b in (self.status, self.n_segs, self.total_time, self.effort, self.seg_state):
+            if b is not None:
+                b.free()
+
+
+class TrajSamples:
+    """HBM-resident sample rows (mplx_traj_sample_out): [4D+3][n_stride][sample_stride] float64, and status [n]."""
+
+    def __init__(self, env, n, count, n_stride=None, sample_stride=None):
+        self.n, self.count, self.rows = int(n), int(count), 4 * env.dim + 3
+        self.n_stride = self.n if n_stride is None else int(n_stride)
+        self.sample_stride = self.count if sample_stride is None else int(sample_stride)
+        self.out = DeviceArray(env, max(self.rows * self.n_stride * self.sample_stride, 1) * 8)
+        self.status = DeviceArray(env, max(self.n, 1))
+
+    def c_struct(self):
+        s = _abi.TrajSampleOut()
+        s.out, s.status = self.out.ptr, self.status.ptr
+        s.row_stride, s.sample_stride = self.n_stride * self.sample_stride, self.sample_stride
+        return s
+
+    def download(self):
+        return {"samples": self.out.download(np.float64, (self.rows, self.n_stride, self.sample_stride)),
+                "status": self.status.download(np.uint8, (self.n,))}
+
+    def free(self):
+        self.out.free()
+        self.status.free()
+
+
+class TrajTraverse:
+    """HBM-resident rows of mplx_traj_traverse_out for n trajectories."""
+
+    def __init__(self, env, n):
+        self.n = int(n)
+        n = max(self.n, 1)
+        self.status = DeviceArray(env, n)
+        self.cost = DeviceArray(env, n * 8)
+        self.n_samples, self.n_cells, self.stop_sample = (DeviceArray(env, n * 4) for _ in range(3))
+
+    def c_struct(self):
+        s = _abi.TrajTraverseOut()
+        s.status, s.cost = self.status.ptr, self.cost.ptr
+        s.n_samples, s.n_cells, s.stop_sample = self.n_samples.ptr, self.n_cells.ptr, self.stop_sample.ptr
+        return s
+
+    def download(self):
+        n = self.n
+        return {"status": self.status.download(np.uint8, (n,)), "cost": self.cost.download(np.float64, (n,)),
+                "n_samples": self.n_samples.download(np.int32, (n,)), "n_cells": self.n_cells.download(np.int32, (n,)),
+                "stop_sample": self.stop_sample.download(np.int32, (n,))}
+
+    def free(self):
+        for b in (self.status, self.cost, self.n_samples, self.n_cells, self.stop_sample):
+            b.free()
 
 
 STATE_ROW_PAD = 0  # default padding between the state rows of Lists, in entries (see Lists.state_stride)
@@ -1040,6 +1127,152 @@ class EnvMap:
             g.tol_vel = g.tol_acc = g.tol_yaw = -1.0
         _abi.check(self._ctx, _abi.lib().mplx_goal_sight_device(self._ctx, C.byref(s), n, None if g is None else C.byref(g),
                                                                  None if fl is None else _device_ptr(fl)))
+
+    # ---- Trajectory<Dim> on the device (include/mplx_traj.h): info, samples, traverse_trajectory
+    def _traj_host_set(self, starts, actions):
+        actions = np.ascontiguousarray(actions, dtype=np.int32)
+        if actions.ndim == 1:
+            actions = actions.reshape(-1, 1)
+        if actions.ndim != 2 or actions.shape[0] < 1:
+            raise ValueError("actions must be [H][K] with H >= 1")
+        H, K = actions.shape
+        starts = np.ascontiguousarray(starts, dtype=np.float64)
+        if starts.ndim == 1:
+            starts = starts.reshape(-1, 1)
+        if starts.shape[0] != self.n_fields or starts.shape[1] not in (1, K):
+            raise ValueError("starts must be [%d][%d] or one state" % (self.n_fields, K))
+        s = _abi.TrajSet()
+        s.starts, s.n_starts, s.start_stride = starts.ctypes.data, starts.shape[1], starts.shape[1]
+        s.actions, s.n_traj, s.horizon, s.action_stride = actions.ctypes.data, K, H, K
+        return s, (starts, actions), K, H
+
+    def _traj_device_set(self, starts, actions, horizon, n_traj, n_starts, start_stride, action_stride):
+        n = int(n_traj)
+        sstride = n if start_stride is None else int(start_stride)
+        if n_starts is None:
+            n_starts = n if start_stride is None else sstride
+        s = _abi.TrajSet()
+        s.starts, s.n_starts, s.start_stride = _device_ptr(starts), int(n_starts), sstride
+        s.actions, s.n_traj, s.horizon = _device_ptr(actions), n, int(horizon)
+        s.action_stride = n if action_stride is None else int(action_stride)
+        return s
+
+    def traj_info(self, starts, actions, want_states=False):
+        """Per trajectory (start state + action sequence, as rollout() takes them; -1 ends a sequence): status (TRAJ_EMPTY
+        | TRAJ_BAD_ACTION), n_segs, total_time, effort [5][K] = J(VEL), J(ACC), J(JRK), J(SNP), Jyaw of
+        Trajectory<Dim>; want_states: seg_state [4D+2][H+1][K], the chain states (entries past n_segs: zero).
+        No validity check of any kind is made (mplx_traj_info; synchronous)."""
+        self._flush()
+        s, keep, K, H = self._traj_host_set(starts, actions)
+        out = {"status": np.zeros(K, np.uint8), "n_segs": np.zeros(K, np.int32), "total_time": np.zeros(K, np.float64),
+               "effort": np.zeros((5, K), np.float64)}
+        o = _abi.TrajInfoOut()
+        o.status, o.n_segs, o.total_time = out["status"].ctypes.data, out["n_segs"].ctypes.data, out["total_time"].ctypes.data
+        o.effort, o.effort_stride = out["effort"].ctypes.data, K
+        if want_states:
+            out["seg_state"] = np.zeros((self.n_fields, H + 1, K), np.float64)
+            o.seg_state, o.seg_stride = out["seg_state"].ctypes.data, K
+        _abi.check(self._ctx, _abi.lib().mplx_traj_info(self._ctx, C.byref(s), C.byref(o)))
+        return out
+
+    def _traj_times(self, N, times, form, K):
+        t = _abi.TrajTimes()
+        t.form = int(form)
+        if (N is None) == (times is None):
+            raise ValueError("give N (uniform samples) or times, not both")
+        if N is not None:
+            t.n_uniform = int(N)
+            return t, None, int(N) + 1
+        times = np.ascontiguousarray(times, dtype=np.float64)
+        if times.ndim == 1:
+            t.n_times, t.time_stride = times.shape[0], 0
+        elif times.ndim == 2 and times.shape[0] == K:
+            t.n_times, t.time_stride = times.shape[1], times.shape[1]
+        else:
+            raise ValueError("times must be [Q] (shared) or [K][Q] (one column per trajectory)")
+        t.times = times.ctypes.data
+        return t, times, int(t.n_times)
+
+    def traj_sample(self, starts, actions, N=None, times=None, form=TRAJ_COMMAND, out=None):
+        """Samples of K trajectories (mplx_traj_sample; synchronous).  N: Trajectory::sample(N), the N + 1 uniform times
+        i * (T / N); or times: [Q] shared or [K][Q].  form TRAJ_COMMAND: rows pos, vel, acc, jrk, yaw, yaw_dot, t of
+        Trajectory::evaluate(t, Command&); TRAJ_WAYPOINT: the first 4D+1 rows of evaluate(t) -> Waypoint, the last two
+        untouched.  Returns samples [4D+3][K][count] (`out`: a C-contiguous float64 [4D+3][>= K][>= count] to write
+        into instead of zeros; entries the call does not own keep their values) and status [K]."""
+        self._flush()
+        s, keep, K, H = self._traj_host_set(starts, actions)
+        t, tkeep, count = self._traj_times(N, times, form, K)
+        rows = 4 * self.dim + 3
+        if out is None:
+            out = np.zeros((rows, K, max(count, 0)), np.float64)
+        if out.dtype != np.float64 or not out.flags.c_contiguous or out.ndim != 3 or out.shape[0] != rows:
+            raise ValueError("out must be a C-contiguous float64 [%d][K'][count']" % rows)
+        status = np.zeros(K, np.uint8)
+        o = _abi.TrajSampleOut()
+        o.out, o.row_stride, o.sample_stride, o.status = out.ctypes.data, out.shape[1] * out.shape[2], out.shape[2], status.ctypes.data
+        if out.shape[1] < K:
+            raise ValueError("out holds %d trajectories, %d asked for" % (out.shape[1], K))
+        _abi.check(self._ctx, _abi.lib().mplx_traj_sample(self._ctx, C.byref(s), C.byref(t), C.byref(o)))
+        return {"samples": out, "status": status}
+
+    def traj_traverse(self, starts, actions, lanes=0):
+        """env_map::traverse_trajectory of K trajectories on the maps the device holds now (mplx_traj_traverse;
+        synchronous): cost (0.0, a finite sum of potential terms, or +inf), n_samples, n_cells (samples not skipped),
+        stop_sample (the sample that made the cost +inf, -1), status (TRAJ_EMPTY | TRAJ_BAD_ACTION | TRAJ_BAD).
+        lanes: 0 (automatic) or 4 / 16 / 64 lanes of a wavefront per trajectory; the results do not depend on it."""
+        self._flush()
+        s, keep, K, H = self._traj_host_set(starts, actions)
+        out = {"status": np.zeros(K, np.uint8), "cost": np.zeros(K, np.float64), "n_samples": np.zeros(K, np.int32),
+               "n_cells": np.zeros(K, np.int32), "stop_sample": np.zeros(K, np.int32)}
+        o = _abi.TrajTraverseOut()
+        for key in out:
+            setattr(o, key, out[key].ctypes.data)
+        _abi.check(self._ctx, _abi.lib().mplx_traj_traverse(self._ctx, C.byref(s), int(lanes), C.byref(o)))
+        return out
+
+    def alloc_traj_info(self, n, horizon, want_states=False):
+        return TrajInfo(self, n, horizon, want_states)
+
+    def alloc_traj_samples(self, n, count, n_stride=None, sample_stride=None):
+        return TrajSamples(self, n, count, n_stride, sample_stride)
+
+    def alloc_traj_traverse(self, n):
+        return TrajTraverse(self, n)
+
+    def traj_info_resident(self, starts, actions, out, horizon, n_traj=None, n_starts=None, start_stride=None,
+                           action_stride=None):
+        """Asynchronous on HBM-resident buffers (mplx_traj_info_device); starts / actions as rollout_resident takes
+        them (DeviceArray or anything with .ptr / data_ptr()), out: env.TrajInfo.  synchronize() before reading."""
+        self._flush()
+        s = self._traj_device_set(starts, actions, horizon, out.n if n_traj is None else n_traj, n_starts, start_stride,
+                                  action_stride)
+        o = out.c_struct()
+        _abi.check(self._ctx, _abi.lib().mplx_traj_info_device(self._ctx, C.byref(s), C.byref(o)))
+
+    def traj_sample_resident(self, starts, actions, out, horizon, N=None, times=None, n_times=None, time_stride=0,
+                             form=TRAJ_COMMAND, n_traj=None, n_starts=None, start_stride=None, action_stride=None):
+        """Asynchronous (mplx_traj_sample_device).  N, or times: a device buffer of n_times values (time_stride 0:
+        shared; >= n_times: trajectory k reads times[k * time_stride + i]).  out: env.TrajSamples."""
+        self._flush()
+        s = self._traj_device_set(starts, actions, horizon, out.n if n_traj is None else n_traj, n_starts, start_stride,
+                                  action_stride)
+        t = _abi.TrajTimes()
+        t.form = int(form)
+        if N is not None:
+            t.n_uniform = int(N)
+        else:
+            t.times, t.n_times, t.time_stride = _device_ptr(times), int(n_times), int(time_stride)
+        o = out.c_struct()
+        _abi.check(self._ctx, _abi.lib().mplx_traj_sample_device(self._ctx, C.byref(s), C.byref(t), C.byref(o)))
+
+    def traj_traverse_resident(self, starts, actions, out, horizon, lanes=0, n_traj=None, n_starts=None, start_stride=None,
+                               action_stride=None):
+        """Asynchronous (mplx_traj_traverse_device); out: env.TrajTraverse."""
+        self._flush()
+        s = self._traj_device_set(starts, actions, horizon, out.n if n_traj is None else n_traj, n_starts, start_stride,
+                                  action_stride)
+        o = out.c_struct()
+        _abi.check(self._ctx, _abi.lib().mplx_traj_traverse_device(self._ctx, C.byref(s), int(lanes), C.byref(o)))
 
     def synchronize(self):
         _abi.check(self._ctx, _abi.lib().mplx_synchronize(self._ctx))

@@ -134,10 +134,12 @@ class MapUtil:
             self._own = None
 
 class Trajectory:
-    """What the reference's tests read off Trajectory<Dim> (trajectory.h)."""
+    """What the reference's tests read off Trajectory<Dim> (trajectory.h).  With `env` (the engine's EnvMap, as getTraj()
+    passes it) sample / evaluate / Jyaw run on the device (include/mplx_traj.h); there is no host implementation."""
 
-    def __init__(self, total_time, J, nodes, actions, cost, end=None):
+    def __init__(self, total_time, J, nodes, actions, cost, end=None, env=None):
         self._T, self._J, self.nodes, self.actions, self.cost, self.end = total_time, J, nodes, actions, cost, end
+        self._env = env
 
     def getWaypoints(self):
         """Rows of 4D+2: the start state of every primitive and the state the last one reaches
@@ -152,6 +154,40 @@ class Trajectory:
     def J(self, control):
         order = {0x01: 0, 0x03: 1, 0x07: 2, 0x0F: 3}[control & 0x0F]
         return self._J[order]
+
+    def _set(self):
+        if self._env is None:
+            raise RuntimeError("this Trajectory has no engine env (getTraj() of a planner with provider=None passes one)")
+        if len(self.actions) == 0:
+            raise RuntimeError("the trajectory has no segment")
+        return np.asarray(self.nodes[0], dtype=np.float64), np.asarray(self.actions, dtype=np.int32).reshape(-1, 1)
+
+    def sample(self, N):
+        """Trajectory::sample(N): N + 1 Commands at i * (T / N), rows of 4D+3 = pos, vel, acc, jrk, yaw, yaw_dot, t."""
+        start, acts = self._set()
+        return self._env.traj_sample(start, acts, N=int(N))["samples"][:, 0, :].T.copy()
+
+    def evaluate(self, t, command=True):
+        """Trajectory::evaluate at time t: the Command (4D+3 values) or, command=False, the Waypoint's pos, vel, acc,
+        jrk, yaw (4D+1 values)."""
+        from .env import TRAJ_COMMAND, TRAJ_WAYPOINT
+        start, acts = self._set()
+        r = self._env.traj_sample(start, acts, times=[float(t)], form=TRAJ_COMMAND if command else TRAJ_WAYPOINT)
+        row = r["samples"][:, 0, 0]
+        return row.copy() if command else row[:4 * self._env.dim + 1].copy()
+
+    def Jyaw(self):
+        start, acts = self._set()
+        return float(self._env.traj_info(start, acts)["effort"][4, 0])
+
+    def getSegmentTimes(self):
+        """Trajectory::getSegmentTimes: the differences of the accumulated segment times (taus by sequential addition)."""
+        if self._env is None:
+            raise RuntimeError("this Trajectory has no engine env")
+        taus = [0.0]
+        for _ in range(len(self.actions)):
+            taus.append(float(self._env._p.dt) + taus[-1])
+        return [taus[i + 1] - taus[i] for i in range(len(taus) - 1)]
 
 
 class MapPlanner:
@@ -441,7 +477,7 @@ class MapPlanner:
             self._check(self._L.mplx_planner_trajectory_end(self._p, end.ctypes.data))
         else:
             end = None
-        return Trajectory(o.total_time, list(o.J), nodes[:o.segments], acts[:o.segments], o.cost, end)
+        return Trajectory(o.total_time, list(o.J), nodes[:o.segments], acts[:o.segments], o.cost, end, env=self.env)
 
     def getTrajCost(self):
         return self._summary.cost
@@ -459,3 +495,15 @@ class MapPlanner:
         r = self.env.rollout(np.asarray(traj.nodes[0], dtype=np.float64), np.asarray(traj.actions, dtype=np.int32).reshape(-1, 1),
                              want_end=False)
         return int(r["status"][0]), int(r["steps"][0]), float(r["cost"][0])
+
+    def traverseTraj(self):
+        """env_map::traverse_trajectory of the last plan's trajectory on the maps the device holds NOW
+        (EnvMap.traj_traverse): (cost, stop_sample) -- 0.0 or the potential sum and -1 while the trajectory is free,
+        +inf and the index of the sample that hit an occupied cell or left the map after a map edit."""
+        if self.env is None:
+            raise RuntimeError("traverseTraj needs the engine's own env (provider=None)")
+        traj = self.getTraj()
+        if len(traj.actions) == 0:
+            raise RuntimeError("traverseTraj: the last plan has no trajectory")
+        r = self.env.traj_traverse(np.asarray(traj.nodes[0], dtype=np.float64), np.asarray(traj.actions, dtype=np.int32).reshape(-1, 1))
+        return float(r["cost"][0]), int(r["stop_sample"][0])
