@@ -17,11 +17,14 @@ extern "C" int mplx_check_edges(mplx_ctx *c, const double *h_parents, const int3
       return fail(c, MPLX_ERR_ARG, "mplx_check_edges: action %d of edge %lld is outside the control table", h_actions[e], (long long)e);
   if (int rc = bind_device(c)) return rc;
   const int F = 4 * c->dim + 2;
-  if (int rc = ensure(c, c->e_parents, (size_t)F * n_edges * 8)) return rc;
-  if (int rc = ensure(c, c->e_action, (size_t)n_edges * 4)) return rc;
-  HIP_TRY(c, hipMemcpy2DAsync(c->e_parents.p, (size_t)n_edges * 8, h_parents, (size_t)stride * 8, (size_t)n_edges * 8, F,
-                              hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(c->e_action.p, h_actions, (size_t)n_edges * 4, hipMemcpyHostToDevice, c->stream));
+  const size_t n = (size_t)n_edges, cell_bytes = h_out->cells ? n * (size_t)h_out->cell_cap * 4 : 0;
+  StageLayout l;
+  const size_t o_parents = l.add((size_t)F * n * 8), o_action = l.add(n * 4), o_free = l.add(h_out->free_flag ? n : 0),
+               o_outside = l.add(h_out->outside ? n : 0), o_cost = l.add(h_out->cost ? n * 8 : 0),
+               o_count = l.add(h_out->cell_count ? n * 4 : 0), o_cells = l.add(cell_bytes);
+  if (int rc = stage_commit(c, &l)) return rc;
+  HIP_TRY(c, stage_in_rows(c, l.base + o_parents, h_parents, (size_t)stride * 8, n * 8, F));
+  HIP_TRY(c, stage_in(c, l.base + o_action, h_actions, n * 4));
   mplx::EdgeArgs a{};
   a.map = (const int8_t *)c->map.p;
   a.region = c->has_region ? (const uint32_t *)c->region_bits.p : nullptr;
@@ -31,28 +34,20 @@ extern "C" int mplx_check_edges(mplx_ctx *c, const double *h_parents, const int3
   a.dt = c->prm.dt; a.w = c->prm.w;
   a.U = (const double *)c->U.p;
   a.nU = c->nU; a.udim = c->udim;
-  a.parents = (const double *)c->e_parents.p;
-  a.action = (const int32_t *)c->e_action.p;
+  a.parents = (const double *)(l.base + o_parents);
+  a.action = (const int32_t *)(l.base + o_action);
   a.n_edges = n_edges; a.stride = n_edges;
-  if (h_out->free_flag) { if (int rc = ensure(c, c->e_free, (size_t)n_edges)) return rc; a.free_out = (uint8_t *)c->e_free.p; }
-  if (h_out->cost) { if (int rc = ensure(c, c->e_cost, (size_t)n_edges * 8)) return rc; a.cost = (double *)c->e_cost.p; }
-  if (h_out->cell_count) { if (int rc = ensure(c, c->e_count, (size_t)n_edges * 4)) return rc; a.cell_count = (int32_t *)c->e_count.p; }
-  if (h_out->cells) {
-    if (int rc = ensure(c, c->e_cells, (size_t)n_edges * h_out->cell_cap * 4)) return rc;
-    a.cells = (int32_t *)c->e_cells.p;
-    a.cell_cap = h_out->cell_cap;
-  }
-  if (h_out->outside) {  // (rides at the end of the free-flag staging buffer)
-    if (int rc = ensure(c, c->e_free, (size_t)n_edges * 2)) return rc;
-    if (h_out->free_flag) a.free_out = (uint8_t *)c->e_free.p;
-    a.outside_out = (uint8_t *)c->e_free.p + n_edges;
-  }
+  if (h_out->free_flag) a.free_out = (uint8_t *)(l.base + o_free);
+  if (h_out->outside) a.outside_out = (uint8_t *)(l.base + o_outside);
+  if (h_out->cost) a.cost = (double *)(l.base + o_cost);
+  if (h_out->cell_count) a.cell_count = (int32_t *)(l.base + o_count);
+  if (h_out->cells) { a.cells = (int32_t *)(l.base + o_cells); a.cell_cap = h_out->cell_cap; }
   HIP_TRY(c, mplx::launch_check_edges(c->dim, c->prm.control, a, c->stream));
-  if (h_out->outside) HIP_TRY(c, hipMemcpyAsync(h_out->outside, a.outside_out, (size_t)n_edges, hipMemcpyDeviceToHost, c->stream));
-  if (h_out->free_flag) HIP_TRY(c, hipMemcpyAsync(h_out->free_flag, a.free_out, (size_t)n_edges, hipMemcpyDeviceToHost, c->stream));
-  if (h_out->cost) HIP_TRY(c, hipMemcpyAsync(h_out->cost, a.cost, (size_t)n_edges * 8, hipMemcpyDeviceToHost, c->stream));
-  if (h_out->cell_count) HIP_TRY(c, hipMemcpyAsync(h_out->cell_count, a.cell_count, (size_t)n_edges * 4, hipMemcpyDeviceToHost, c->stream));
-  if (h_out->cells) HIP_TRY(c, hipMemcpyAsync(h_out->cells, a.cells, (size_t)n_edges * h_out->cell_cap * 4, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, stage_out(c, h_out->outside, a.outside_out, n));
+  HIP_TRY(c, stage_out(c, h_out->free_flag, a.free_out, n));
+  HIP_TRY(c, stage_out(c, h_out->cost, a.cost, n * 8));
+  HIP_TRY(c, stage_out(c, h_out->cell_count, a.cell_count, n * 4));
+  HIP_TRY(c, stage_out(c, h_out->cells, a.cells, cell_bytes));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   return MPLX_OK;
 }

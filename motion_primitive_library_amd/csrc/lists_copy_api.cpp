@@ -108,7 +108,7 @@ int copy_lists_to_host(mplx_ctx *c, const mplx_succ_lists &d, const mplx_succ_li
   size_t cap = kChunkBytes;
   if ((size_t)max_cnt * bpe > cap) cap = (size_t)max_cnt * bpe;
   if ((size_t)total * bpe < cap) cap = (size_t)total * bpe;
-  cap = (cap + 255) & ~(size_t)255;
+  cap = align256(cap);
   const int64_t cap_entries = (int64_t)(cap / bpe);
   if (int rc = ensure_pinned(c, cap)) return rc;
   for (int i = 0; i < 2; i++) {
@@ -271,15 +271,14 @@ int expand_lists_packed(mplx_ctx *c, const double *h_nodes, int64_t n_nodes, int
     // Batches of a search: the kernel reads the nodes from and writes the lists into one pinned host block itself
     // (only the used entries cross PCIe, while the kernel runs): the call is the kernel and one synchronisation.
     // The view then describes the strided lists as they are: offs[k] = k * S, row stride n_nodes * S.
-    auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    const size_t o_cnt = up((size_t)F * n_nodes * 8);
-    const size_t o_off = o_cnt + up((size_t)n_nodes * 4);
-    const size_t o_act = o_off + up((size_t)(n_nodes + 1) * 8);
-    const size_t o_cost = o_act + up((size_t)n_slots * 4);
-    const size_t o_hash = o_cost + up((size_t)n_slots * 8);
-    const size_t o_heur = o_hash + up((size_t)n_slots * 8);
-    const size_t o_state = o_heur + (want_heur ? up((size_t)n_slots * 8) : 0);
-    const size_t bytes = o_state + (want_state ? up((size_t)F * n_slots * 8) : 0);
+    const size_t o_cnt = align256((size_t)F * n_nodes * 8);
+    const size_t o_off = o_cnt + align256((size_t)n_nodes * 4);
+    const size_t o_act = o_off + align256((size_t)(n_nodes + 1) * 8);
+    const size_t o_cost = o_act + align256((size_t)n_slots * 4);
+    const size_t o_hash = o_cost + align256((size_t)n_slots * 8);
+    const size_t o_heur = o_hash + align256((size_t)n_slots * 8);
+    const size_t o_state = o_heur + (want_heur ? align256((size_t)n_slots * 8) : 0);
+    const size_t bytes = o_state + (want_state ? align256((size_t)F * n_slots * 8) : 0);
     if (bytes > c->pk_hb_cap) {
       if (c->pk_hb) HIP_TRY(c, hipHostFree(c->pk_hb));
       c->pk_hb = nullptr;
@@ -320,8 +319,8 @@ int expand_lists_packed(mplx_ctx *c, const double *h_nodes, int64_t n_nodes, int
   // (larger batches are packed on the device and copied: the heuristic row does not travel that way -- the search
   // evaluates it itself, host_planner.hpp, as it does for every provider without that row)
   // pinned host block: [nodes F x n][count n][offs n + 1]
-  const size_t o_cnt = ((size_t)F * n_nodes * 8 + 255) & ~(size_t)255;
-  const size_t o_off = (o_cnt + (size_t)n_nodes * 4 + 255) & ~(size_t)255;
+  const size_t o_cnt = align256((size_t)F * n_nodes * 8);
+  const size_t o_off = o_cnt + align256((size_t)n_nodes * 4);
   const size_t hb_bytes = o_off + (size_t)(n_nodes + 1) * 8;
   if (hb_bytes > c->pk_hb_cap) {
     if (c->pk_hb) HIP_TRY(c, hipHostFree(c->pk_hb));
@@ -333,23 +332,21 @@ int expand_lists_packed(mplx_ctx *c, const double *h_nodes, int64_t n_nodes, int
   char *hb = (char *)c->pk_hb;
   for (int f = 0; f < F; f++)
     std::memcpy(hb + (size_t)f * n_nodes * 8, h_nodes + (size_t)f * node_stride, (size_t)n_nodes * 8);
-  if (int rc = ensure(c, c->s_nodes, (size_t)F * n_nodes * 8)) return rc;
-  if (int rc = ensure(c, c->s_count, (size_t)n_nodes * 4)) return rc;
-  if (int rc = ensure(c, c->s_action, (size_t)n_slots * 4)) return rc;
-  if (int rc = ensure(c, c->s_cost, (size_t)n_slots * 8)) return rc;
-  if (int rc = ensure(c, c->s_hash, (size_t)n_slots * 8)) return rc;
-  if (want_state)
-    if (int rc = ensure(c, c->s_state, (size_t)F * n_slots * 8)) return rc;
+  const size_t slots = (size_t)n_slots;
+  StageLayout l;
+  const size_t o_nodes = l.add((size_t)F * n_nodes * 8), o_count = l.add((size_t)n_nodes * 4), o_action = l.add(slots * 4),
+               o_cost = l.add(slots * 8), o_hash = l.add(slots * 8), o_state = l.add(want_state ? F * slots * 8 : 0);
+  if (int rc = stage_commit(c, &l)) return rc;
   if (int rc = ensure(c, c->pk_offs, (size_t)n_nodes * 8)) return rc;
-  HIP_TRY(c, hipMemcpyAsync(c->s_nodes.p, hb, (size_t)F * n_nodes * 8, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, stage_in(c, l.base + o_nodes, hb, (size_t)F * n_nodes * 8));
   mplx_succ_lists d{};
-  d.count = (int32_t *)c->s_count.p;
-  d.action = (int32_t *)c->s_action.p;
-  d.cost = (double *)c->s_cost.p;
-  d.hash = (uint64_t *)c->s_hash.p;
-  if (want_state) { d.state = (double *)c->s_state.p; d.state_stride = n_slots; }
+  d.count = (int32_t *)(l.base + o_count);
+  d.action = (int32_t *)(l.base + o_action);
+  d.cost = (double *)(l.base + o_cost);
+  d.hash = (uint64_t *)(l.base + o_hash);
+  if (want_state) { d.state = (double *)(l.base + o_state); d.state_stride = n_slots; }
   d.node_stride = S;
-  if (int rc = lists_device(c, (const double *)c->s_nodes.p, n_nodes, n_nodes, &d)) return rc;
+  if (int rc = lists_device(c, (const double *)(l.base + o_nodes), n_nodes, n_nodes, &d)) return rc;
   if (int rc = resolve_pending(c)) return rc;  // yaw pinning: lists final before they are packed
   int32_t *cnt = (int32_t *)(hb + o_cnt);
   int64_t *offs = (int64_t *)(hb + o_off);
@@ -364,7 +361,7 @@ int expand_lists_packed(mplx_ctx *c, const double *h_nodes, int64_t n_nodes, int
   out->offs = offs;
   if (total == 0) return MPLX_OK;
   const int bpe = 8 + 8 + (want_state ? 8 * F : 0) + 4;
-  const size_t bytes = ((size_t)total * bpe + 255) & ~(size_t)255;
+  const size_t bytes = align256((size_t)total * bpe);
   if (int rc = ensure_pinned(c, bytes)) return rc;
   if (int rc = ensure(c, c->pk_dev[0], bytes)) return rc;
   HIP_TRY(c, hipMemcpyAsync(c->pk_offs.p, offs, (size_t)n_nodes * 8, hipMemcpyHostToDevice, c->stream));

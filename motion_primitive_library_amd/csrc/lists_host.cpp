@@ -28,19 +28,18 @@ unsigned rows_of(const mplx_succ_lists *o) {
 }
 
 ArenaLayout arena_layout(int F, int64_t n_alloc, int64_t S, unsigned rows) {
-  auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
   ArenaLayout L;
   L.n_alloc = n_alloc;
   L.n_slots = n_alloc * S;
-  L.o_count = up((size_t)F * n_alloc * 8);
-  L.o_action = L.o_count + up((size_t)n_alloc * 4);
-  L.o_cost = L.o_action + ((rows & kRowAction) ? up((size_t)L.n_slots * 4) : 0);
-  L.o_hash = L.o_cost + ((rows & kRowCost) ? up((size_t)L.n_slots * 8) : 0);
-  L.o_iters = L.o_hash + ((rows & kRowHash) ? up((size_t)L.n_slots * 8) : 0);
-  L.o_heur = L.o_iters + ((rows & kRowIters) ? up((size_t)L.n_slots * 4) : 0);
-  L.o_flags = L.o_heur + ((rows & kRowHeur) ? up((size_t)L.n_slots * 8) : 0);
-  L.o_state = L.o_flags + ((rows & kRowFlags) ? up((size_t)L.n_slots) : 0);
-  L.total = L.o_state + ((rows & kRowState) ? up((size_t)F * L.n_slots * 8) : 0);
+  L.o_count = align256((size_t)F * n_alloc * 8);
+  L.o_action = L.o_count + align256((size_t)n_alloc * 4);
+  L.o_cost = L.o_action + ((rows & kRowAction) ? align256((size_t)L.n_slots * 4) : 0);
+  L.o_hash = L.o_cost + ((rows & kRowCost) ? align256((size_t)L.n_slots * 8) : 0);
+  L.o_iters = L.o_hash + ((rows & kRowHash) ? align256((size_t)L.n_slots * 8) : 0);
+  L.o_heur = L.o_iters + ((rows & kRowIters) ? align256((size_t)L.n_slots * 4) : 0);
+  L.o_flags = L.o_heur + ((rows & kRowHeur) ? align256((size_t)L.n_slots * 8) : 0);
+  L.o_state = L.o_flags + ((rows & kRowFlags) ? align256((size_t)L.n_slots) : 0);
+  L.total = L.o_state + ((rows & kRowState) ? align256((size_t)F * L.n_slots * 8) : 0);
   return L;
 }
 
@@ -330,26 +329,24 @@ int mplx_expand_lists(mplx_ctx *c, const double *h_nodes, int64_t n_nodes, int64
   if (h_out->heur || h_out->flags)
     return fail(c, MPLX_ERR_ARG, "mplx_expand_lists: the heur / flags rows come back through host pointers for batches of up to "
                                  "8 MiB of lists only (a search's); larger ones: mplx_expand_lists_device and a copy of the rows");
-  if (int rc = ensure(c, c->s_nodes, (size_t)F * n_nodes * sizeof(double))) return rc;
-  HIP_TRY(c, hipMemcpy2DAsync(c->s_nodes.p, (size_t)n_nodes * sizeof(double), h_nodes,
-                              (size_t)node_stride * sizeof(double), (size_t)n_nodes * sizeof(double), F,
-                              hipMemcpyHostToDevice, c->stream));
+  const size_t slots = (size_t)n_slots;
+  StageLayout l;
+  const size_t o_nodes = l.add((size_t)F * n_nodes * 8), o_count = l.add((size_t)n_nodes * 4), o_action = l.add(h_out->action ? slots * 4 : 0),
+               o_cost = l.add(h_out->cost ? slots * 8 : 0), o_hash = l.add(h_out->hash ? slots * 8 : 0),
+               o_iters = l.add(h_out->iters ? slots * 4 : 0), o_state = l.add(h_out->state ? F * slots * 8 : 0);
+  if (int rc = stage_commit(c, &l)) return rc;
+  HIP_TRY(c, stage_in_rows(c, l.base + o_nodes, h_nodes, (size_t)node_stride * 8, (size_t)n_nodes * 8, F));
   mplx_succ_lists d{};
-  if (int rc = ensure(c, c->s_count, (size_t)n_nodes * 4)) return rc;
-  d.count = (int32_t *)c->s_count.p;
-  if (h_out->action) { if (int rc = ensure(c, c->s_action, (size_t)n_slots * 4)) return rc; d.action = (int32_t *)c->s_action.p; }
-  if (h_out->cost) { if (int rc = ensure(c, c->s_cost, (size_t)n_slots * 8)) return rc; d.cost = (double *)c->s_cost.p; }
-  if (h_out->hash) { if (int rc = ensure(c, c->s_hash, (size_t)n_slots * 8)) return rc; d.hash = (uint64_t *)c->s_hash.p; }
-  if (h_out->iters) { if (int rc = ensure(c, c->s_iters, (size_t)n_slots * 4)) return rc; d.iters = (int32_t *)c->s_iters.p; }
-  if (h_out->state) {
-    if (int rc = ensure(c, c->s_state, (size_t)F * n_slots * 8)) return rc;
-    d.state = (double *)c->s_state.p;
-    d.state_stride = n_slots;
-  }
+  d.count = (int32_t *)(l.base + o_count);
+  if (h_out->action) d.action = (int32_t *)(l.base + o_action);
+  if (h_out->cost) d.cost = (double *)(l.base + o_cost);
+  if (h_out->hash) d.hash = (uint64_t *)(l.base + o_hash);
+  if (h_out->iters) d.iters = (int32_t *)(l.base + o_iters);
+  if (h_out->state) { d.state = (double *)(l.base + o_state); d.state_stride = n_slots; }
   d.node_stride = h_out->node_stride;
-  if (int rc = lists_device(c, (const double *)c->s_nodes.p, n_nodes, n_nodes, &d)) return rc;
+  if (int rc = lists_device(c, (const double *)(l.base + o_nodes), n_nodes, n_nodes, &d)) return rc;
   // everything larger: only the used prefixes cross the link, packed on the device and pipelined through pinned
-  // buffers (lists_copy_api.cpp)
+  // buffers (lists_copy_api.cpp); that copy returns with the stream idle: nothing reads the arena after this call
   MPLX_GUARD_BEGIN
   if (int rc = resolve_pending(c)) return rc;
   return copy_lists_to_host(c, d, h_out, n_nodes);

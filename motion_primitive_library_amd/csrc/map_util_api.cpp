@@ -98,7 +98,7 @@ int mplx_map_cloud(mplx_ctx *c, int kind, double *xyz, int64_t cap, int64_t *n_o
   if (int rc = resolve_pending(c)) return rc;
   const int D = c->dim;
   const int64_t n_col = (int64_t)c->mdim[0] * (D == 3 ? c->mdim[1] : 1);
-  const size_t count_bytes = (((size_t)n_col * 4) + 255) & ~(size_t)255;
+  const size_t count_bytes = align256((size_t)n_col * 4);
   if (int rc = ensure(c, c->prep_b, count_bytes + (size_t)(n_col + 1) * 8)) return rc;
   int32_t *count = (int32_t *)c->prep_b.p;
   int64_t *offs = (int64_t *)((char *)c->prep_b.p + count_bytes);

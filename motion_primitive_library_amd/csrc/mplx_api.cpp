@@ -166,9 +166,8 @@ void mplx_destroy(mplx_ctx *c) {
   if (c->stream) (void)hipStreamSynchronize(c->stream);
   if (c->done_host) (void)hipHostFree(c->done_host);
   release(c->done_count);
-  for (DevBuf *b : {&c->map, &c->pot, &c->region_bits, &c->region_bytes, &c->U, &c->s_nodes, &c->s_status,
-                    &c->s_cost, &c->s_hash, &c->s_state, &c->s_iters, &c->s_count, &c->s_action, &c->tables,
-                    &c->d_status, &c->d_cost, &c->d_hash, &c->d_state, &c->d_iters, &c->uvals, &c->uidx, &c->blk, &c->sat, &c->prep_lut, &c->prep_a, &c->prep_b, &c->post_keys, &c->post_ws, &c->ray_work, &c->traj_tab, &c->live_list, &c->live_ctr, &c->edit_buf, &c->e_parents, &c->e_action, &c->e_free, &c->e_cost, &c->e_cells, &c->e_count})
+  for (DevBuf *b : {&c->map, &c->pot, &c->region_bits, &c->region_bytes, &c->U, &c->tables,
+                    &c->d_status, &c->d_cost, &c->d_hash, &c->d_state, &c->d_iters, &c->uvals, &c->uidx, &c->blk, &c->sat, &c->prep_lut, &c->prep_a, &c->prep_b, &c->post_keys, &c->post_ws, &c->ray_work, &c->traj_tab, &c->live_list, &c->live_ctr})
     release(*b);
   (void)mplx_comm_destroy(c);
   release(c->comm_meta);
@@ -423,22 +422,21 @@ int mplx_expand(mplx_ctx *c, const double *h_nodes, int64_t n_nodes, int64_t nod
   const int64_t n_slots = n_nodes * c->nU;
   if (h_out->state && h_out->state_stride < n_slots)
     return fail(c, MPLX_ERR_ARG, "mplx_expand: state_stride < n_slots");
-  // frontier: pack rows to stride n_nodes on the device
-  if (int rc = ensure(c, c->s_nodes, (size_t)F * n_nodes * sizeof(double))) return rc;
-  HIP_TRY(c, hipMemcpy2DAsync(c->s_nodes.p, (size_t)n_nodes * sizeof(double), h_nodes,
-                              (size_t)node_stride * sizeof(double), (size_t)n_nodes * sizeof(double), F,
-                              hipMemcpyHostToDevice, c->stream));
+  // one arena block: the frontier packed to stride n_nodes, then the rows that were asked for
+  const size_t slots = (size_t)n_slots;
+  StageLayout l;
+  const size_t o_nodes = l.add((size_t)F * n_nodes * 8), o_status = l.add(h_out->status ? slots : 0),
+               o_cost = l.add(h_out->cost ? slots * 8 : 0), o_hash = l.add(h_out->hash ? slots * 8 : 0),
+               o_iters = l.add(h_out->iters ? slots * 4 : 0), o_state = l.add(h_out->state ? F * slots * 8 : 0);
+  if (int rc = stage_commit(c, &l)) return rc;
+  HIP_TRY(c, stage_in_rows(c, l.base + o_nodes, h_nodes, (size_t)node_stride * 8, (size_t)n_nodes * 8, F));
   mplx_succ d{};
-  if (h_out->status) { if (int rc = ensure(c, c->s_status, (size_t)n_slots)) return rc; d.status = (uint8_t *)c->s_status.p; }
-  if (h_out->cost) { if (int rc = ensure(c, c->s_cost, (size_t)n_slots * 8)) return rc; d.cost = (double *)c->s_cost.p; }
-  if (h_out->hash) { if (int rc = ensure(c, c->s_hash, (size_t)n_slots * 8)) return rc; d.hash = (uint64_t *)c->s_hash.p; }
-  if (h_out->iters) { if (int rc = ensure(c, c->s_iters, (size_t)n_slots * 4)) return rc; d.iters = (int32_t *)c->s_iters.p; }
-  if (h_out->state) {
-    if (int rc = ensure(c, c->s_state, (size_t)F * n_slots * 8)) return rc;
-    d.state = (double *)c->s_state.p;
-    d.state_stride = n_slots;
-  }
-  mplx::ExpandArgs a = expand_args(c, (const double *)c->s_nodes.p, n_nodes, n_nodes, &d);
+  if (h_out->status) d.status = (uint8_t *)(l.base + o_status);
+  if (h_out->cost) d.cost = (double *)(l.base + o_cost);
+  if (h_out->hash) d.hash = (uint64_t *)(l.base + o_hash);
+  if (h_out->iters) d.iters = (int32_t *)(l.base + o_iters);
+  if (h_out->state) { d.state = (double *)(l.base + o_state); d.state_stride = n_slots; }
+  mplx::ExpandArgs a = expand_args(c, (const double *)(l.base + o_nodes), n_nodes, n_nodes, &d);
   a.stream_out = 1;
   if (int rc = yaw_slot(c, &a.yaw)) return rc;
   HIP_TRY(c, mplx::launch_expand(c->dim, c->prm.control, a, c->stream));
@@ -449,13 +447,11 @@ int mplx_expand(mplx_ctx *c, const double *h_nodes, int64_t n_nodes, int64_t nod
     c->yaw_pending.push_back(p);
     if (int rc = mplx_detail::resolve_pending(c)) return rc;
   }
-  if (h_out->status) HIP_TRY(c, hipMemcpyAsync(h_out->status, d.status, (size_t)n_slots, hipMemcpyDeviceToHost, c->stream));
-  if (h_out->cost) HIP_TRY(c, hipMemcpyAsync(h_out->cost, d.cost, (size_t)n_slots * 8, hipMemcpyDeviceToHost, c->stream));
-  if (h_out->hash) HIP_TRY(c, hipMemcpyAsync(h_out->hash, d.hash, (size_t)n_slots * 8, hipMemcpyDeviceToHost, c->stream));
-  if (h_out->iters) HIP_TRY(c, hipMemcpyAsync(h_out->iters, d.iters, (size_t)n_slots * 4, hipMemcpyDeviceToHost, c->stream));
-  if (h_out->state)
-    HIP_TRY(c, hipMemcpy2DAsync(h_out->state, (size_t)h_out->state_stride * 8, d.state, (size_t)n_slots * 8,
-                                (size_t)n_slots * 8, F, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, stage_out(c, h_out->status, d.status, slots));
+  HIP_TRY(c, stage_out(c, h_out->cost, d.cost, slots * 8));
+  HIP_TRY(c, stage_out(c, h_out->hash, d.hash, slots * 8));
+  HIP_TRY(c, stage_out(c, h_out->iters, d.iters, slots * 4));
+  HIP_TRY(c, stage_out_rows(c, h_out->state, (size_t)h_out->state_stride * 8, d.state, slots * 8, F));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   return MPLX_OK;
 }

@@ -49,7 +49,6 @@ struct mplx_ctx {
   // per-axis factorisation of the control table (expand_grid_kernel.hip)
   mplx_detail::DevBuf uvals, uidx, blk, sat;
   bool sat_ok = false;   // summed-area table of blk is current
-  mplx_detail::DevBuf e_parents, e_action, e_free, e_cost, e_cells, e_count;  // edge re-validation staging
   mplx_detail::DevBuf post_keys;                 // node-identity table (post_api.cpp)
   mplx_detail::DevBuf post_ws;                   // workspace of the partitioned identity pass (identity_kernel.hip)
   mplx_detail::DevBuf ray_work;                  // candidate worklist of mplx_goal_sight_device (ray_api.cpp)
@@ -98,10 +97,8 @@ struct mplx_ctx {
   double recips[3] = {0, 0, 0};
   // scratch for the dense -> lists route
   mplx_detail::DevBuf d_status, d_cost, d_hash, d_state, d_iters;
-  // staging for the host-pointer entry points
-  mplx_detail::DevBuf s_nodes, s_status, s_cost, s_hash, s_state, s_iters, s_count, s_action;
-  // small host-pointer batches: one device arena + one pinned mirror (mplx_expand_lists); the arena is also the staging
-  // block of mplx_rollout (rollout_api.cpp)
+  // The one device block every host-pointer entry point stages its arrays in for the length of the call (StageLayout
+  // below states the rules), and the pinned mirror of the small batches of mplx_expand_lists (lists_host.cpp).
   mplx_detail::DevBuf s_arena;
   void *h_arena = nullptr;
   size_t h_arena_cap = 0;
@@ -147,7 +144,6 @@ struct mplx_ctx {
   std::vector<YawPending> yaw_pending;
   int32_t *yaw_any_host = nullptr;  // pinned word: some launch since the last resolve flagged a node
   int32_t *id_ovf_host = nullptr;   // pinned word: a bucket of the claimed identity pass overflowed (post_api.cpp)
-  mplx_detail::DevBuf edit_buf;     // cell indices + values of mplx_edit_map
   bool sat_stale = false;           // the blocked bits were patched by mplx_edit_map: the summed-area table waits for a launch worth rebuilding it for
   int id_backoff = 0;               // calls left that skip the claimed identity form after an overflow (post_api.cpp)
   int last_identity_form = 0;       // 0 none / table in HBM, 1 claimed, 2 exact partition, 3 claimed then exact (overflow)
@@ -167,8 +163,7 @@ struct mplx_ctx {
   void *comm = nullptr;
   int comm_rank = 0, comm_world = 1;
   mplx_detail::DevBuf comm_meta;  // [world + 1][MPLX_COMM_META] int64: the meta record of every rank, then the own one
-  std::vector<uint8_t> h_status;
-  std::vector<double> h_cost, h_state;
+  std::vector<double> h_state;  // mplx_get_succ: the state rows of its one node
 };
 
 namespace mplx_detail {
@@ -229,6 +224,42 @@ inline void release(DevBuf &b) {
   if (b.p) (void)hipFree(b.p);
   b.p = nullptr;
   b.cap = 0;
+}
+
+// ---- Staging of host arrays on the device: rows carved out of mplx_ctx::s_arena for the length of one call.
+//  1. A call lays out everything it stages and commits ONCE, before it enqueues its first copy: ensure() synchronises
+//     and frees on growth, so a second growth would lose the copies already enqueued.
+//  2. When a host-pointer entry point returns, no launch or copy that reads or writes the arena is outstanding (each
+//     ends in a synchronise, in resolve_pending, or in the wait of its small-batch launch).
+//  3. A call that enters another entry point while it holds arena rows has first copied everything it still needs to
+//     the host: the inner call carves the same block.
+//  4. Device-pointer entry points never touch the arena.  It only grows: the rounded rows of the largest call so far.
+inline size_t align256(size_t bytes) { return (bytes + 255) & ~(size_t)255; }  // the only rounding of staging offsets
+
+struct StageLayout {
+  size_t total = 0;
+  char *base = nullptr;       // the arena, once committed
+  // offset of a row of `bytes` (0: a row that was not asked for; the caller leaves its pointer null)
+  size_t add(size_t bytes) { const size_t at = total; total += align256(bytes); return at; }
+};
+inline int stage_commit(mplx_ctx *c, StageLayout *l) {
+  if (int rc = ensure(c, c->s_arena, l->total)) return rc;
+  l->base = (char *)c->s_arena.p;
+  return MPLX_OK;
+}
+// The copies, on the context's stream, for HIP_TRY at the call site.  In: one row / `rows` host rows of `width` bytes,
+// `src_stride` bytes apart, to packed device rows.  Out, if the caller asked for the row (host != null): the reverse.
+inline hipError_t stage_in(mplx_ctx *c, void *dev, const void *host, size_t bytes) {
+  return hipMemcpyAsync(dev, host, bytes, hipMemcpyHostToDevice, c->stream);
+}
+inline hipError_t stage_in_rows(mplx_ctx *c, void *dev, const void *host, size_t src_stride, size_t width, size_t rows) {
+  return hipMemcpy2DAsync(dev, width, host, src_stride, width, rows, hipMemcpyHostToDevice, c->stream);
+}
+inline hipError_t stage_out(mplx_ctx *c, void *host, const void *dev, size_t bytes) {
+  return host ? hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, c->stream) : hipSuccess;
+}
+inline hipError_t stage_out_rows(mplx_ctx *c, void *host, size_t dst_stride, const void *dev, size_t width, size_t rows) {
+  return host ? hipMemcpy2DAsync(host, dst_stride, dev, width, width, rows, hipMemcpyDeviceToHost, c->stream) : hipSuccess;
 }
 
 // The per-node lists of a host frontier, left packed in the context's pinned landing buffer (node k owns entries

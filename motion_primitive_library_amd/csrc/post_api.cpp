@@ -70,12 +70,11 @@ static int post_lists_impl(mplx_ctx *c, const mplx_succ_lists *d_lists, int64_t 
     int64_t ctr1 = 0, ctr2 = 0;
     mplx::identity_sizes(n, ia.b1, ia.b2, &ia.tiles1, &ia.tiles2_cap, &ctr1, &ctr2);
     const int levels = ia.b2 ? 2 : 1;
-    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
     // workspace of the exact form: pairs of both levels, counters, block totals, segments
-    const size_t sz_h = up((size_t)n * 8), sz_g = up((size_t)n * 4);
-    const size_t sz_c1 = up((size_t)ctr1 * 4), sz_c2 = up((size_t)ctr2 * 4);
-    const size_t sz_t1 = up((size_t)(ctr1 / 4096 + 1) * 4), sz_t2 = up((size_t)(ctr2 / 4096 + 1) * 4);
-    const size_t sz_r = up(((size_t)1 << (ia.b1 + ia.b2)) * 4 + 4);
+    const size_t sz_h = align256((size_t)n * 8), sz_g = align256((size_t)n * 4);
+    const size_t sz_c1 = align256((size_t)ctr1 * 4), sz_c2 = align256((size_t)ctr2 * 4);
+    const size_t sz_t1 = align256((size_t)(ctr1 / 4096 + 1) * 4), sz_t2 = align256((size_t)(ctr2 / 4096 + 1) * 4);
+    const size_t sz_r = align256(((size_t)1 << (ia.b1 + ia.b2)) * 4 + 4);
     const size_t total = levels * (sz_h + sz_g) + sz_c1 + sz_c2 + sz_t1 + sz_t2 + sz_r + 1024;
     // ... and of the claimed form (two levels): buckets of fixed capacity, cursors, the tile table of level 2
     const char *e_cl = getenv("MPLX_POST_CLAIMED"), *e_cap = getenv("MPLX_POST_CAP");
@@ -94,9 +93,9 @@ static int post_lists_impl(mplx_ctx *c, const mplx_succ_lists *d_lists, int64_t 
         long long x = 0, y = 0;
         if (sscanf(e_cap, "%lld,%lld", &x, &y) == 2 && x >= 16 && y >= 16 && x <= subcap1 && y <= cap2) { subcap1 = x; cap2 = y; }
       }
-      cl_h0 = up((size_t)pairs1 * 8); cl_g0 = up((size_t)pairs1 * 4);
-      cl_h1 = up((size_t)pairs2 * 8); cl_g1 = up((size_t)pairs2 * 4);
-      cl_cur = up((size_t)cur_words * 4); cl_ts = up((size_t)(1 + 512 + tiles2_max) * 4);
+      cl_h0 = align256((size_t)pairs1 * 8); cl_g0 = align256((size_t)pairs1 * 4);
+      cl_h1 = align256((size_t)pairs2 * 8); cl_g1 = align256((size_t)pairs2 * 4);
+      cl_cur = align256((size_t)cur_words * 4); cl_ts = align256((size_t)(1 + 512 + tiles2_max) * 4);
       total_cl = cl_h0 + cl_g0 + cl_h1 + cl_g1 + cl_cur + cl_ts;
     }
     if (int rc = ensure(c, c->post_ws, total > total_cl ? total : total_cl)) return rc;

@@ -94,72 +94,68 @@ int mplx_rollout(mplx_ctx *c, const double *h_starts, int64_t n_starts, int64_t 
   if (n_rollouts == 0) return MPLX_OK;
   MPLX_GUARD_BEGIN
   if (int rc = bind_device(c)) return rc;
-  if (int rc = resolve_pending(c)) return rc;  // the staging buffers below are shared with the other host-pointer calls
+  if (int rc = resolve_pending(c)) return rc;  // the arena is shared with the other host-pointer calls
   const int D = c->dim, F = 4 * D + 2, nU = c->nU;
   const int64_t n = n_rollouts, H = horizon;
   const bool yaw_limit = (c->prm.control & 0x10) && c->prm.yaw_max > 0;
-  // One device block: starts [F][n_starts], actions [H][n], then the output rows.  The status, steps, prefix, end state
+  // One arena block: starts [F][n_starts], actions [H][n], then the output rows.  The status, steps, prefix, end state
   // and end hash rows are always produced: resolving a rollout inside the band needs them.
-  auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-  const size_t o_starts = 0, o_actions = up((size_t)F * n_starts * 8), o_status = o_actions + up((size_t)H * n * 4),
-               o_steps = o_status + up((size_t)n), o_cost = o_steps + up((size_t)n * 4), o_prefix = o_cost + up((size_t)n * 8),
-               o_state = o_prefix + up((size_t)n * 8), o_hash = o_state + up((size_t)F * n * 8),
-               o_heur = o_hash + up((size_t)n * 8), o_flags = o_heur + up((size_t)n * 8), total = o_flags + up((size_t)n);
-  if (int rc = ensure(c, c->s_arena, total)) return rc;
-  char *base = (char *)c->s_arena.p;
-  HIP_TRY(c, hipMemcpy2DAsync(base + o_starts, (size_t)n_starts * 8, h_starts, (size_t)start_stride * 8, (size_t)n_starts * 8, F,
-                              hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(c, hipMemcpy2DAsync(base + o_actions, (size_t)n * 4, h_actions, (size_t)action_stride * 4, (size_t)n * 4, H,
-                              hipMemcpyHostToDevice, c->stream));
+  const size_t N = (size_t)n;
+  StageLayout l;
+  const size_t o_starts = l.add((size_t)F * n_starts * 8), o_actions = l.add((size_t)H * N * 4), o_status = l.add(N),
+               o_steps = l.add(N * 4), o_cost = l.add(N * 8), o_prefix = l.add(N * 8), o_state = l.add((size_t)F * N * 8),
+               o_hash = l.add(N * 8), o_heur = l.add(h_out->end_heur ? N * 8 : 0), o_flags = l.add(h_out->end_flags ? N : 0);
+  if (int rc = stage_commit(c, &l)) return rc;
+  HIP_TRY(c, stage_in_rows(c, l.base + o_starts, h_starts, (size_t)start_stride * 8, (size_t)n_starts * 8, F));
+  HIP_TRY(c, stage_in_rows(c, l.base + o_actions, h_actions, (size_t)action_stride * 4, N * 4, H));
   mplx_rollout_out d{};
-  d.status = (uint8_t *)(base + o_status);
-  d.steps = (int32_t *)(base + o_steps);
-  d.cost = (double *)(base + o_cost);
-  d.prefix_cost = (double *)(base + o_prefix);
-  d.end_state = (double *)(base + o_state);
+  d.status = (uint8_t *)(l.base + o_status);
+  d.steps = (int32_t *)(l.base + o_steps);
+  d.cost = (double *)(l.base + o_cost);
+  d.prefix_cost = (double *)(l.base + o_prefix);
+  d.end_state = (double *)(l.base + o_state);
   d.end_stride = n;
-  d.end_hash = (uint64_t *)(base + o_hash);
-  d.end_heur = h_out->end_heur ? (double *)(base + o_heur) : nullptr;
-  d.end_flags = h_out->end_flags ? (uint8_t *)(base + o_flags) : nullptr;
-  if (int rc = launch(c, (const double *)(base + o_starts), n_starts, n_starts, (const int32_t *)(base + o_actions), n, horizon, n,
+  d.end_hash = (uint64_t *)(l.base + o_hash);
+  d.end_heur = h_out->end_heur ? (double *)(l.base + o_heur) : nullptr;
+  d.end_flags = h_out->end_flags ? (uint8_t *)(l.base + o_flags) : nullptr;
+  if (int rc = launch(c, (const double *)(l.base + o_starts), n_starts, n_starts, (const int32_t *)(l.base + o_actions), n, horizon, n,
                       &d))
     return rc;
-  std::vector<uint8_t> status((size_t)n);
-  HIP_TRY(c, hipMemcpyAsync(status.data(), d.status, (size_t)n, hipMemcpyDeviceToHost, c->stream));
+  std::vector<uint8_t> status(N);
+  HIP_TRY(c, stage_out(c, status.data(), d.status, N));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   std::vector<int64_t> band;  // rollouts that met a heading-limit decision inside the band
   if (yaw_limit)
     for (int64_t k = 0; k < n; k++)
       if (status[(size_t)k] & MPLX_ROLLOUT_HEADING_BAND) band.push_back(k);
 
-  if (band.empty()) {
-    if (h_out->status) std::copy(status.begin(), status.end(), h_out->status);
-    if (h_out->steps) HIP_TRY(c, hipMemcpyAsync(h_out->steps, d.steps, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
-    if (h_out->cost) HIP_TRY(c, hipMemcpyAsync(h_out->cost, d.cost, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
-    if (h_out->prefix_cost) HIP_TRY(c, hipMemcpyAsync(h_out->prefix_cost, d.prefix_cost, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
-    if (h_out->end_state)
-      HIP_TRY(c, hipMemcpy2DAsync(h_out->end_state, (size_t)h_out->end_stride * 8, d.end_state, (size_t)n * 8, (size_t)n * 8, F,
-                                  hipMemcpyDeviceToHost, c->stream));
-    if (h_out->end_hash) HIP_TRY(c, hipMemcpyAsync(h_out->end_hash, d.end_hash, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
-    if (h_out->end_heur) HIP_TRY(c, hipMemcpyAsync(h_out->end_heur, d.end_heur, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
-    if (h_out->end_flags) HIP_TRY(c, hipMemcpyAsync(h_out->end_flags, d.end_flags, (size_t)n, hipMemcpyDeviceToHost, c->stream));
+  // every row but the status to the host (a null row is skipped), then the stream is idle
+  auto fetch = [&](int32_t *steps, double *cost, double *prefix, double *state, int64_t stride, uint64_t *hash, double *heur, uint8_t *flags) -> int {
+    HIP_TRY(c, stage_out(c, steps, d.steps, N * 4));
+    HIP_TRY(c, stage_out(c, cost, d.cost, N * 8));
+    HIP_TRY(c, stage_out(c, prefix, d.prefix_cost, N * 8));
+    HIP_TRY(c, stage_out_rows(c, state, (size_t)stride * 8, d.end_state, N * 8, F));
+    HIP_TRY(c, stage_out(c, hash, d.end_hash, N * 8));
+    HIP_TRY(c, stage_out(c, heur, d.end_heur, N * 8));
+    HIP_TRY(c, stage_out(c, flags, d.end_flags, N));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     return MPLX_OK;
+  };
+  if (band.empty()) {
+    if (h_out->status) std::copy(status.begin(), status.end(), h_out->status);
+    return fetch(h_out->steps, h_out->cost, h_out->prefix_cost, h_out->end_state, h_out->end_stride, h_out->end_hash, h_out->end_heur,
+                 h_out->end_flags);
   }
 
-  // ---- everything to the host, then the flagged rollouts again through the pinned dense path
-  std::vector<int32_t> steps((size_t)n);
-  std::vector<double> cost((size_t)n), prefix((size_t)n), state((size_t)F * n), heur(h_out->end_heur ? (size_t)n : 0);
-  std::vector<uint64_t> hash((size_t)n);
-  std::vector<uint8_t> flags(h_out->end_flags ? (size_t)n : 0);
-  HIP_TRY(c, hipMemcpyAsync(steps.data(), d.steps, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(cost.data(), d.cost, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(prefix.data(), d.prefix_cost, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(state.data(), d.end_state, (size_t)F * n * 8, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(hash.data(), d.end_hash, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
-  if (d.end_heur) HIP_TRY(c, hipMemcpyAsync(heur.data(), d.end_heur, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
-  if (d.end_flags) HIP_TRY(c, hipMemcpyAsync(flags.data(), d.end_flags, (size_t)n, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  // ---- everything to the host, then the flagged rollouts again through the pinned dense path.  Every row comes down
+  // BEFORE the walk: mplx_expand below carves the same arena (rule 3 of the staging block, mplx_ctx.h).
+  std::vector<int32_t> steps(N);
+  std::vector<double> cost(N), prefix(N), state((size_t)F * N), heur(h_out->end_heur ? N : 0);
+  std::vector<uint64_t> hash(N);
+  std::vector<uint8_t> flags(h_out->end_flags ? N : 0);
+  if (int rc = fetch(steps.data(), cost.data(), prefix.data(), state.data(), n, hash.data(), h_out->end_heur ? heur.data() : nullptr,
+                     h_out->end_flags ? flags.data() : nullptr))
+    return rc;
 
   // The flagged rollouts walk again from their start states, all of them one step per mplx_expand call: that call runs
   // the dense kernel with the detection and override passes of the yaw pinning, and its dense slots carry the status.
@@ -232,16 +228,16 @@ int mplx_rollout(mplx_ctx *c, const double *h_starts, int64_t n_starts, int64_t 
     std::vector<int32_t> minus1((size_t)r, -1);
     for (int64_t i = 0; i < r; i++)
       for (int f = 0; f < F; f++) st0[(size_t)f * r + i] = cur[(size_t)f * m + rehash[(size_t)i]];
-    if (int rc = ensure(c, c->s_nodes, (size_t)F * r * 8)) return rc;
-    if (int rc = ensure(c, c->s_action, (size_t)r * 4)) return rc;
-    if (int rc = ensure(c, c->s_hash, (size_t)r * 8)) return rc;
-    HIP_TRY(c, hipMemcpyAsync(c->s_nodes.p, st0.data(), st0.size() * 8, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(c->s_action.p, minus1.data(), (size_t)r * 4, hipMemcpyHostToDevice, c->stream));
+    StageLayout lr;  // (the arena again: nothing of the first launch is still needed on the device)
+    const size_t o_st0 = lr.add((size_t)F * r * 8), o_minus1 = lr.add((size_t)r * 4), o_h0 = lr.add((size_t)r * 8);
+    if (int rc = stage_commit(c, &lr)) return rc;
+    HIP_TRY(c, stage_in(c, lr.base + o_st0, st0.data(), st0.size() * 8));
+    HIP_TRY(c, stage_in(c, lr.base + o_minus1, minus1.data(), (size_t)r * 4));
     mplx_rollout_out ho{};
-    ho.end_hash = (uint64_t *)c->s_hash.p;
-    if (int rc = launch(c, (const double *)c->s_nodes.p, r, r, (const int32_t *)c->s_action.p, r, 1, r, &ho)) return rc;
+    ho.end_hash = (uint64_t *)(lr.base + o_h0);
+    if (int rc = launch(c, (const double *)(lr.base + o_st0), r, r, (const int32_t *)(lr.base + o_minus1), r, 1, r, &ho)) return rc;
     std::vector<uint64_t> h0((size_t)r);
-    HIP_TRY(c, hipMemcpyAsync(h0.data(), c->s_hash.p, (size_t)r * 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, stage_out(c, h0.data(), ho.end_hash, (size_t)r * 8));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     for (int64_t i = 0; i < r; i++) hash[(size_t)band[(size_t)rehash[(size_t)i]]] = h0[(size_t)i];
   }

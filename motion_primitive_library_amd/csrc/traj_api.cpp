@@ -12,8 +12,6 @@ using namespace mplx_detail;
 
 namespace {
 
-size_t up(size_t b) { return (b + 255) & ~(size_t)255; }
-
 int check_set(mplx_ctx *c, const char *who, const mplx_traj_set *s, const void *out) {
   if (!s || !out || s->horizon < 1 || s->n_traj < 0 || (s->n_starts != 1 && s->n_starts != s->n_traj) ||
       s->start_stride < s->n_starts || s->action_stride < s->n_traj || (s->n_traj > 0 && (!s->starts || !s->actions)))
@@ -54,9 +52,9 @@ int build(mplx_ctx *c, const mplx_traj_set *s, const mplx_traj_info_out *io, mpl
   a.actions = s->actions; a.n_traj = s->n_traj; a.action_stride = s->action_stride; a.horizon = s->horizon;
   a.yaw = (c->prm.control & 0x10) ? 1 : 0;
   const size_t N = (size_t)s->n_traj, H = (size_t)s->horizon, NC = 5 * (size_t)c->dim + 2;
-  const size_t o_S = 0, o_n = up(N * 4), o_st = o_n + up(N * 4), o_T = o_st + up(N), o_tau = o_T + up(N * 8),
-               o_seg = o_tau + up((H + 1) * N * 8), total = o_seg + up(H * NC * N * 8);
-  if (int rc = ensure(c, c->traj_tab, total)) return rc;
+  StageLayout l;  // (only the carving: the table is the context's own scratch, not the arena)
+  const size_t o_S = l.add(N * 4), o_n = l.add(N * 4), o_st = l.add(N), o_T = l.add(N * 8), o_tau = l.add((H + 1) * N * 8), o_seg = l.add(H * NC * N * 8);
+  if (int rc = ensure(c, c->traj_tab, l.total)) return rc;
   char *base = (char *)c->traj_tab.p;
   a.tab_S = (int32_t *)(base + o_S);
   a.tab_n = (int32_t *)(base + o_n);
@@ -80,9 +78,11 @@ int check_info(mplx_ctx *c, const char *who, const mplx_traj_set *s, const mplx_
   return MPLX_OK;
 }
 
-int sample_launch(mplx_ctx *c, const mplx_traj_set *s, const mplx_traj_times *t, const mplx_traj_sample_out *o, int64_t count) {
+// n_segs: the segment counts as well (the host twin needs them: they decide which samples exist)
+int sample_launch(mplx_ctx *c, const mplx_traj_set *s, const mplx_traj_times *t, const mplx_traj_sample_out *o, int64_t count, int32_t *n_segs = nullptr) {
   mplx_traj_info_out io{};
   io.status = o->status;
+  io.n_segs = n_segs;
   mplx::TrajArgs a;
   if (int rc = build(c, s, &io, &a)) return rc;
   if (!o->out) return MPLX_OK;
@@ -110,20 +110,19 @@ int traverse_launch(mplx_ctx *c, const mplx_traj_set *s, int32_t lanes, const mp
   return MPLX_OK;
 }
 
-// Host set -> the arena at `base`; returns the device view.  sizes: starts [F][n_starts], actions [H][n].
-size_t set_bytes(const mplx_ctx *c, const mplx_traj_set *s) {
-  const size_t F = 4 * (size_t)c->dim + 2;
-  return up(F * (size_t)s->n_starts * 8) + up((size_t)s->horizon * (size_t)s->n_traj * 4);
+// Host set -> the arena: set_rows lays out starts [F][n_starts] and actions [H][n]; stage_set copies them: the device view.
+struct SetRows { size_t starts, actions; };
+SetRows set_rows(const mplx_ctx *c, const mplx_traj_set *s, StageLayout *l) {
+  const size_t o_starts = l->add((4 * (size_t)c->dim + 2) * (size_t)s->n_starts * 8);
+  return {o_starts, l->add((size_t)s->horizon * (size_t)s->n_traj * 4)};
 }
-int stage_set(mplx_ctx *c, const mplx_traj_set *s, char *base, mplx_traj_set *d) {
+int stage_set(mplx_ctx *c, const mplx_traj_set *s, const StageLayout &l, const SetRows &r, mplx_traj_set *d) {
   const size_t F = 4 * (size_t)c->dim + 2, n = (size_t)s->n_traj, ns = (size_t)s->n_starts;
-  char *acts = base + up(F * ns * 8);
-  HIP_TRY(c, hipMemcpy2DAsync(base, ns * 8, s->starts, (size_t)s->start_stride * 8, ns * 8, F, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(c, hipMemcpy2DAsync(acts, n * 4, s->actions, (size_t)s->action_stride * 4, n * 4, (size_t)s->horizon, hipMemcpyHostToDevice,
-                              c->stream));
+  HIP_TRY(c, stage_in_rows(c, l.base + r.starts, s->starts, (size_t)s->start_stride * 8, ns * 8, F));
+  HIP_TRY(c, stage_in_rows(c, l.base + r.actions, s->actions, (size_t)s->action_stride * 4, n * 4, (size_t)s->horizon));
   *d = *s;
-  d->starts = (const double *)base; d->start_stride = s->n_starts;
-  d->actions = (const int32_t *)acts; d->action_stride = s->n_traj;
+  d->starts = (const double *)(l.base + r.starts); d->start_stride = s->n_starts;
+  d->actions = (const int32_t *)(l.base + r.actions); d->action_stride = s->n_traj;
   return MPLX_OK;
 }
 
@@ -150,30 +149,30 @@ int mplx_traj_info(mplx_ctx *c, const mplx_traj_set *h_set, const mplx_traj_info
   if (int rc = bind_device(c)) return rc;
   if (int rc = resolve_pending(c)) return rc;  // the arena is shared with the other host-pointer calls
   const size_t n = (size_t)h_set->n_traj, F = 4 * (size_t)c->dim + 2, H1 = (size_t)h_set->horizon + 1;
-  const size_t o_in = 0, o_st = set_bytes(c, h_set), o_S = o_st + up(n), o_T = o_S + up(n * 4), o_e = o_T + up(n * 8),
-               o_seg = o_e + up(5 * n * 8), total = o_seg + (h_out->seg_state ? up(F * H1 * n * 8) : 0);
-  if (int rc = ensure(c, c->s_arena, total)) return rc;
-  char *base = (char *)c->s_arena.p;
+  StageLayout l;
+  const SetRows in = set_rows(c, h_set, &l);
+  const size_t o_st = l.add(n), o_S = l.add(n * 4), o_T = l.add(n * 8), o_e = l.add(h_out->effort ? 5 * n * 8 : 0),
+               o_seg = l.add(h_out->seg_state ? F * H1 * n * 8 : 0);
+  if (int rc = stage_commit(c, &l)) return rc;
   mplx_traj_set d;
-  if (int rc = stage_set(c, h_set, base + o_in, &d)) return rc;
+  if (int rc = stage_set(c, h_set, l, in, &d)) return rc;
   mplx_traj_info_out o{};
-  o.status = (uint8_t *)(base + o_st);
-  o.n_segs = (int32_t *)(base + o_S);
-  o.total_time = (double *)(base + o_T);
-  o.effort = h_out->effort ? (double *)(base + o_e) : nullptr;
+  o.status = (uint8_t *)(l.base + o_st);
+  o.n_segs = (int32_t *)(l.base + o_S);
+  o.total_time = (double *)(l.base + o_T);
+  o.effort = h_out->effort ? (double *)(l.base + o_e) : nullptr;
   o.effort_stride = (int64_t)n;
-  o.seg_state = h_out->seg_state ? (double *)(base + o_seg) : nullptr;
+  o.seg_state = h_out->seg_state ? (double *)(l.base + o_seg) : nullptr;
   o.seg_stride = (int64_t)n;
   mplx::TrajArgs a;
   if (int rc = build(c, &d, &o, &a)) return rc;
   std::vector<int32_t> S(n);
   std::vector<double> seg(h_out->seg_state ? F * H1 * n : 0);
-  HIP_TRY(c, hipMemcpyAsync(S.data(), o.n_segs, n * 4, hipMemcpyDeviceToHost, c->stream));
-  if (h_out->status) HIP_TRY(c, hipMemcpyAsync(h_out->status, o.status, n, hipMemcpyDeviceToHost, c->stream));
-  if (h_out->total_time) HIP_TRY(c, hipMemcpyAsync(h_out->total_time, o.total_time, n * 8, hipMemcpyDeviceToHost, c->stream));
-  if (h_out->effort)
-    HIP_TRY(c, hipMemcpy2DAsync(h_out->effort, (size_t)h_out->effort_stride * 8, o.effort, n * 8, n * 8, 5, hipMemcpyDeviceToHost, c->stream));
-  if (h_out->seg_state) HIP_TRY(c, hipMemcpyAsync(seg.data(), o.seg_state, seg.size() * 8, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, stage_out(c, S.data(), o.n_segs, n * 4));
+  HIP_TRY(c, stage_out(c, h_out->status, o.status, n));
+  HIP_TRY(c, stage_out(c, h_out->total_time, o.total_time, n * 8));
+  HIP_TRY(c, stage_out_rows(c, h_out->effort, (size_t)h_out->effort_stride * 8, o.effort, n * 8, 5));
+  HIP_TRY(c, stage_out(c, h_out->seg_state ? seg.data() : nullptr, o.seg_state, seg.size() * 8));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   if (h_out->n_segs) std::copy(S.begin(), S.end(), h_out->n_segs);
   if (h_out->seg_state)  // states past S_k keep the caller's bytes
@@ -208,40 +207,31 @@ int mplx_traj_sample(mplx_ctx *c, const mplx_traj_set *h_set, const mplx_traj_ti
   const size_t rows = h_times->form == MPLX_TRAJ_COMMAND ? 4 * D + 3 : 4 * D + 1;
   const bool own_times = h_times->n_uniform == 0;
   const size_t n_cols = own_times ? (h_times->time_stride ? n : 1) : 0;
-  const size_t o_in = 0, o_t = set_bytes(c, h_set), o_st = o_t + up(n_cols * cnt * 8), o_S = o_st + up(n),
-               o_out = o_S + up(n * 4), total = o_out + (h_out->out ? up(rows * n * cnt * 8) : 0);
-  if (int rc = ensure(c, c->s_arena, total)) return rc;
-  char *base = (char *)c->s_arena.p;
+  StageLayout l;
+  const SetRows in = set_rows(c, h_set, &l);
+  const size_t o_t = l.add(n_cols * cnt * 8), o_st = l.add(n), o_S = l.add(n * 4), o_out = l.add(h_out->out ? rows * n * cnt * 8 : 0);
+  if (int rc = stage_commit(c, &l)) return rc;
   mplx_traj_set d;
-  if (int rc = stage_set(c, h_set, base + o_in, &d)) return rc;
+  if (int rc = stage_set(c, h_set, l, in, &d)) return rc;
   mplx_traj_times t = *h_times;
   if (own_times) {
-    HIP_TRY(c, hipMemcpy2DAsync(base + o_t, cnt * 8, h_times->times, (size_t)(h_times->time_stride ? h_times->time_stride : (int64_t)cnt) * 8,
-                                cnt * 8, n_cols, hipMemcpyHostToDevice, c->stream));
-    t.times = (const double *)(base + o_t);
+    const size_t src_stride = (size_t)(h_times->time_stride ? h_times->time_stride : (int64_t)cnt) * 8;
+    HIP_TRY(c, stage_in_rows(c, l.base + o_t, h_times->times, src_stride, cnt * 8, n_cols));
+    t.times = (const double *)(l.base + o_t);
     t.time_stride = h_times->time_stride ? (int64_t)cnt : 0;
   }
   mplx_traj_sample_out o{};
-  o.out = h_out->out ? (double *)(base + o_out) : nullptr;
+  o.out = h_out->out ? (double *)(l.base + o_out) : nullptr;
   o.sample_stride = (int64_t)cnt;
   o.row_stride = (int64_t)(n * cnt);
-  o.status = (uint8_t *)(base + o_st);
+  o.status = (uint8_t *)(l.base + o_st);
   // the segment counts decide which samples exist: EMPTY trajectories keep the caller's bytes
-  mplx_traj_info_out io{};
-  io.status = o.status;
-  io.n_segs = (int32_t *)(base + o_S);
-  mplx::TrajArgs a;
-  if (int rc = build(c, &d, &io, &a)) return rc;
-  if (o.out) {
-    a.n_uniform = t.n_uniform; a.times = t.times; a.time_stride = t.n_uniform > 0 ? 0 : t.time_stride; a.count = count;
-    a.out = o.out; a.row_stride = o.row_stride; a.sample_stride = o.sample_stride;
-    HIP_TRY(c, mplx::launch_traj_sample(c->dim, t.form, a, c->stream));
-  }
+  if (int rc = sample_launch(c, &d, &t, &o, count, (int32_t *)(l.base + o_S))) return rc;
   std::vector<int32_t> S(n);
   std::vector<double> buf(h_out->out ? rows * n * cnt : 0);
-  HIP_TRY(c, hipMemcpyAsync(S.data(), io.n_segs, n * 4, hipMemcpyDeviceToHost, c->stream));
-  if (h_out->status) HIP_TRY(c, hipMemcpyAsync(h_out->status, o.status, n, hipMemcpyDeviceToHost, c->stream));
-  if (h_out->out) HIP_TRY(c, hipMemcpyAsync(buf.data(), o.out, buf.size() * 8, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, stage_out(c, S.data(), l.base + o_S, n * 4));
+  HIP_TRY(c, stage_out(c, h_out->status, o.status, n));
+  HIP_TRY(c, stage_out(c, h_out->out ? buf.data() : nullptr, o.out, buf.size() * 8));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   if (h_out->out)
     for (size_t r = 0; r < rows; r++)
@@ -271,24 +261,25 @@ int mplx_traj_traverse(mplx_ctx *c, const mplx_traj_set *h_set, int32_t lanes, c
   if (int rc = bind_device(c)) return rc;
   if (int rc = resolve_pending(c)) return rc;
   const size_t n = (size_t)h_set->n_traj;
-  const size_t o_in = 0, o_st = set_bytes(c, h_set), o_cost = o_st + up(n), o_ns = o_cost + up(n * 8), o_nc = o_ns + up(n * 4),
-               o_stop = o_nc + up(n * 4), total = o_stop + up(n * 4);
-  if (int rc = ensure(c, c->s_arena, total)) return rc;
-  char *base = (char *)c->s_arena.p;
+  StageLayout l;
+  const SetRows in = set_rows(c, h_set, &l);
+  const size_t o_st = l.add(h_out->status ? n : 0), o_cost = l.add(h_out->cost ? n * 8 : 0), o_ns = l.add(h_out->n_samples ? n * 4 : 0),
+               o_nc = l.add(h_out->n_cells ? n * 4 : 0), o_stop = l.add(h_out->stop_sample ? n * 4 : 0);
+  if (int rc = stage_commit(c, &l)) return rc;
   mplx_traj_set d;
-  if (int rc = stage_set(c, h_set, base + o_in, &d)) return rc;
+  if (int rc = stage_set(c, h_set, l, in, &d)) return rc;
   mplx_traj_traverse_out o{};
-  o.status = h_out->status ? (uint8_t *)(base + o_st) : nullptr;
-  o.cost = h_out->cost ? (double *)(base + o_cost) : nullptr;
-  o.n_samples = h_out->n_samples ? (int32_t *)(base + o_ns) : nullptr;
-  o.n_cells = h_out->n_cells ? (int32_t *)(base + o_nc) : nullptr;
-  o.stop_sample = h_out->stop_sample ? (int32_t *)(base + o_stop) : nullptr;
+  o.status = h_out->status ? (uint8_t *)(l.base + o_st) : nullptr;
+  o.cost = h_out->cost ? (double *)(l.base + o_cost) : nullptr;
+  o.n_samples = h_out->n_samples ? (int32_t *)(l.base + o_ns) : nullptr;
+  o.n_cells = h_out->n_cells ? (int32_t *)(l.base + o_nc) : nullptr;
+  o.stop_sample = h_out->stop_sample ? (int32_t *)(l.base + o_stop) : nullptr;
   if (int rc = traverse_launch(c, &d, lanes, &o)) return rc;
-  if (o.status) HIP_TRY(c, hipMemcpyAsync(h_out->status, o.status, n, hipMemcpyDeviceToHost, c->stream));
-  if (o.cost) HIP_TRY(c, hipMemcpyAsync(h_out->cost, o.cost, n * 8, hipMemcpyDeviceToHost, c->stream));
-  if (o.n_samples) HIP_TRY(c, hipMemcpyAsync(h_out->n_samples, o.n_samples, n * 4, hipMemcpyDeviceToHost, c->stream));
-  if (o.n_cells) HIP_TRY(c, hipMemcpyAsync(h_out->n_cells, o.n_cells, n * 4, hipMemcpyDeviceToHost, c->stream));
-  if (o.stop_sample) HIP_TRY(c, hipMemcpyAsync(h_out->stop_sample, o.stop_sample, n * 4, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, stage_out(c, h_out->status, o.status, n));
+  HIP_TRY(c, stage_out(c, h_out->cost, o.cost, n * 8));
+  HIP_TRY(c, stage_out(c, h_out->n_samples, o.n_samples, n * 4));
+  HIP_TRY(c, stage_out(c, h_out->n_cells, o.n_cells, n * 4));
+  HIP_TRY(c, stage_out(c, h_out->stop_sample, o.stop_sample, n * 4));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   return MPLX_OK;
 }

@@ -16,7 +16,7 @@ invalidated by exactly the right calls:
 | fused goal `goal_fuse`, `has_goal` | set_goal | stops the service when it changes |
 | counters zero between launches (`work_counter`, `live_ctr`, `done_count`) | previous launch | each kernel's epilogue |
 | pending yaw fix-ups `yaw_pending` | earlier launches | resolve_pending() at the top of every mutating call |
-| scratch shared between operations (`prep_a`, `prep_b`, `prep_lut`, `edit_buf`) | dilate, potential passes, region boxes, clouds, read / edit cells | ensure() grows only |
+| scratch shared between operations (`prep_a`, `prep_b`, `prep_lut`; the staging block `s_arena` of every host-pointer call) | dilate, potential passes, region boxes, clouds; read / edit cells and the other host-pointer calls | ensure() grows only |
 | Python mirror `EnvMap.has_potential` | Python setters | by hand -- setMap with another geometry left it True (fixed with this module) |
 
 A new setter, or new derived state, belongs in the alphabet of tests/sequence_model.py (MUTATORS + variants()): the

@@ -1,0 +1,303 @@
+"""Every host-pointer call stages its arrays in ONE device block of the context (csrc/mplx_ctx.h, StageLayout): here
+they share it, at sizes that grow and shrink.
+
+One long-lived context runs a fixed order of host-pointer calls -- the expansion calls and check_edges / read_cells /
+editMap next to the rollouts, rays and trajectories -- and after every step its output equals, byte for byte, what a
+context created for that step alone returns for the same inputs.  Every output array is filled with the same poison
+in both contexts before the call, so the bytes a call must leave alone (list entries past count[k], ray cells past
+min(n_cells, cell_cap), chain states past S_k, samples of EMPTY trajectories, the last two sample rows of the waypoint
+form) compare as well; the one exception is the `cells` row of check_edges, whose entries past cell_count[e] mplx.h
+leaves undefined (they are cleared before the comparison).  Where a call has a device-pointer twin, the twin runs on the long-lived context on uploaded
+copies of the same inputs into poisoned device rows and must return the same bytes (rollouts that carry
+MPLX_ROLLOUT_HEADING_BAND from the device call excepted, as in tests/test_gpu_rollout.py; of the lists the count row
+and the used prefixes, which is what both forms define).  No tolerance anywhere.
+
+Sizes.  n in {1, 3, 65, 257, 1000}: a 3-byte status row in front of an int32 row, and 65 x 4 = 260 bytes, are the
+smallest shapes that expose a wrong offset or a missing rounding step; 1000 after 3 grows the block between two calls
+and 3 after 1000 runs a small call in a large block.  MPLX_ARENA_KB = 1 sends every mplx_expand_lists batch through
+the large path, the one that stages in the shared block.
+
+Order.  A closed walk over every ordered pair of call kinds (each kind directly after every other kind), every step of
+it at the largest size; the first four visits of a kind are preceded by the same kind at one of the four smaller
+sizes.  The order is data (schedule()): a failure names its step, and two tests without a GPU pin that every kind runs
+at every size and directly after every other kind's largest size."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+from motion_primitive_library_amd import workloads as W
+
+POISON = 0xA5
+SIZES = (1, 3, 65, 257, 1000)
+KINDS = ("expand", "expand_lists", "edges_cap0", "edges_cap3", "read_cells", "edit_map", "rollout", "rollout_goal",
+         "ray_trace", "traj_info", "sample_uniform", "sample_times", "traj_traverse")
+TWINNED = ("expand", "expand_lists", "rollout", "rollout_goal", "ray_trace", "traj_info", "sample_uniform", "sample_times",
+           "traj_traverse")
+H = 3           # horizon of rollouts and trajectories
+N_UNIFORM = 4   # Trajectory::sample(N)
+Q = 3           # the caller's own times per trajectory
+CELL_CAP = 5    # cells kept per ray
+SEED = 20261017
+_SET = ("nodes", "actions")
+NEEDS = {"expand": ("nodes",), "expand_lists": ("nodes",), "edges_cap0": ("nodes", "edge_actions"), "edges_cap3": ("nodes", "edge_actions"),
+         "read_cells": ("cell_index",), "edit_map": ("cell_index", "cell_values"), "rollout": _SET, "rollout_goal": _SET,
+         "ray_trace": ("p1", "p2"), "traj_info": _SET, "sample_uniform": _SET, "sample_times": _SET + ("times",), "traj_traverse": _SET}
+CONFIGS = {"2d_acc_yaw": (2, W.ACCxYAW, (48, 40)), "3d_acc": (3, W.ACC, (20, 18, 16))}
+
+
+def schedule():
+    """[(kind, n, visit)]: visit counts the earlier steps of the same kind (variant() picks the form of a call by it)."""
+    k = len(KINDS)
+    rng = np.random.default_rng(SEED)
+    out = {a: [int(b) for b in rng.permutation([b for b in range(k) if b != a])] for a in range(k)}
+    stack, walk = [0], []
+    while stack:  # Hierholzer: a closed walk over every arc of the complete digraph
+        v = stack[-1]
+        if out[v]:
+            stack.append(out[v].pop())
+        else:
+            walk.append(stack.pop())
+    steps, visits = [], [0] * k
+    for v in reversed(walk):
+        if visits[v] < len(SIZES) - 1:
+            steps.append((KINDS[v], SIZES[(visits[v] + v) % (len(SIZES) - 1)], 2 * visits[v]))
+        steps.append((KINDS[v], SIZES[-1], 2 * visits[v] + 1 if visits[v] < len(SIZES) - 1 else visits[v] + len(SIZES) - 1))
+        visits[v] += 1
+    return steps
+
+
+def variant(kind, visit):
+    """(form of the samples: 0 TRAJ_COMMAND / 1 TRAJ_WAYPOINT, one column per item: the caller's times per trajectory,
+    the end point per ray -- or one shared by all)."""
+    return (visit // 2 + (kind == "sample_times")) % 2, visit % 2 == 1
+
+
+def test_the_order_runs_every_kind_at_every_size():
+    steps = schedule()
+    assert {(kind, n) for kind, n, _ in steps} == {(kind, n) for kind in KINDS for n in SIZES}
+    sizes = [n for _, n, _ in steps]
+    assert any(a == 3 and b == 1000 for a, b in zip(sizes, sizes[1:])) and any(a == 1000 and b == 3 for a, b in zip(sizes, sizes[1:]))
+    assert sizes != sorted(sizes) and sizes != sorted(sizes, reverse=True)
+    for kind in KINDS:
+        assert [visit for k, _, visit in steps if k == kind] == list(range(sum(k == kind for k, _, _ in steps))), kind
+    for kind in ("sample_uniform", "sample_times"):  # both forms; the caller's times shared and per trajectory
+        assert {variant(kind, visit) for k, _, visit in steps if k == kind} == {(f, c) for f in (0, 1) for c in (False, True)}, kind
+    assert steps == schedule(), "the order must not depend on the run"
+
+
+def test_every_kind_runs_directly_after_every_other_kinds_largest_size():
+    steps = schedule()
+    after = {(a, b) for (a, n, _), (b, _, _) in zip(steps, steps[1:]) if n == SIZES[-1] and a != b}
+    assert after == {(a, b) for a in KINDS for b in KINDS if a != b}
+
+
+# ---- the world of a configuration and the inputs of a step (numpy only; the same for both contexts and the twin)
+class World:
+    def __init__(self, name):
+        self.dim, self.control, self.map_dim = CONFIGS[name]
+        self.res, self.origin = 0.1, [0.0] * self.dim
+        self.cells = W.box_map(self.map_dim, self.res, 0.15, 1017, side_m=(0.2, 0.8))  # [z][y][x]; editMap steps change it
+        yaw = [-0.5, 0.0, 0.5] if self.control & 0x10 else None
+        self.U = W.grid_controls([-1, 0, 1], self.dim, yaw_rates=yaw)
+        self.params = {"v_max": 2.0, "yaw_max": 0.5} if yaw else {"v_max": 2.0}
+        self.F, self.nU = 4 * self.dim + 2, self.U.shape[0]
+        probe = W.random_frontier(self.cells, self.origin, self.res, 1, 7, self.control, 2.0, 0.5)
+        self.goal = probe[:, 0].copy()
+
+    def configure(self, env):
+        env.setMap(self.origin, list(self.map_dim), self.cells, self.res)
+        env.set_control(self.control)
+        env.set_u(self.U)
+        for k, v in self.params.items():
+            getattr(env, "set_" + k)(v)
+        env.set_goal(self.goal, tol_pos=1.0)
+        env._flush()
+
+    def inputs(self, i, kind, n, visit):
+        rng = np.random.default_rng(SEED + i)
+        x = {"nodes": W.random_frontier(self.cells, self.origin, self.res, n, SEED + i, self.control, 2.0, 0.5)}
+        x["edge_actions"] = rng.integers(0, self.nU, size=n).astype(np.int32)
+        acts = rng.integers(-1, self.nU, size=(H, n)).astype(np.int32)  # -1 ends a sequence (in row 0: an EMPTY trajectory)
+        x["actions"] = np.ascontiguousarray(acts)
+        x["cell_index"] = rng.integers(0, self.cells.size, size=n).astype(np.int64)
+        x["cell_values"] = rng.choice(np.array([0, 100], np.int8), size=n)
+        ext = np.array(self.map_dim, np.float64)[:, None] * self.res
+        x["p1"] = np.ascontiguousarray(rng.uniform(-0.05, 1.05, size=(self.dim, n)) * ext)
+        p2 = rng.uniform(-0.05, 1.05, size=(self.dim, n)) * ext
+        x["form"], per_item = variant(kind, visit)
+        x["p2"] = np.ascontiguousarray(p2 if per_item else p2[:, 0])
+        x["times"] = np.ascontiguousarray(rng.uniform(-0.5, H + 0.5, size=(n, Q) if per_item else (Q,)))
+        return {k: v for k, v in x.items() if k in NEEDS[kind] or k == "form"}
+
+
+def poisoned(dtype, shape):
+    a = np.empty(shape, dtype=dtype)
+    a.view(np.uint8)[...] = POISON
+    return a
+
+
+def out_spec(w, kind, n, x):
+    """name -> (dtype, shape) of the rows a step asks for."""
+    F, nU, ns = w.F, w.nU, n * w.nU
+    if kind == "expand":
+        return {"status": ("u1", (ns,)), "cost": ("<f8", (ns,)), "hash": ("<u8", (ns,)), "state": ("<f8", (F, ns)), "iters": ("<i4", (ns,))}
+    if kind == "expand_lists":
+        return {"count": ("<i4", (n,)), "action": ("<i4", (ns,)), "cost": ("<f8", (ns,)), "hash": ("<u8", (ns,)),
+                "state": ("<f8", (F, ns)), "iters": ("<i4", (ns,))}
+    if kind in ("edges_cap0", "edges_cap3"):
+        s = {"free_flag": ("u1", (n,)), "cost": ("<f8", (n,)), "outside": ("u1", (n,))}
+        if kind == "edges_cap3":
+            s.update({"cells": ("<i4", (n, 3)), "cell_count": ("<i4", (n,))})
+        return s
+    if kind in ("read_cells", "edit_map"):
+        return {"values": ("i1", (n,))}
+    if kind == "rollout":  # (the end rows are produced on the device all the same)
+        return {"status": ("u1", (n,)), "steps": ("<i4", (n,)), "cost": ("<f8", (n,))}
+    if kind == "rollout_goal":
+        return {"status": ("u1", (n,)), "steps": ("<i4", (n,)), "cost": ("<f8", (n,)), "prefix_cost": ("<f8", (n,)),
+                "end_state": ("<f8", (F, n)), "end_hash": ("<u8", (n,)), "end_heur": ("<f8", (n,)), "end_flags": ("u1", (n,))}
+    if kind == "ray_trace":
+        return {"status": ("u1", (n,)), "n_cells": ("<i4", (n,)), "first_hit": ("<i4", (n,)), "cells": ("<i4", (n, CELL_CAP))}
+    if kind == "traj_info":
+        return {"status": ("u1", (n,)), "n_segs": ("<i4", (n,)), "total_time": ("<f8", (n,)), "effort": ("<f8", (5, n)),
+                "seg_state": ("<f8", (F, H + 1, n))}
+    if kind in ("sample_uniform", "sample_times"):
+        count = N_UNIFORM + 1 if kind == "sample_uniform" else Q
+        return {"out": ("<f8", (4 * w.dim + 3, n, count)), "status": ("u1", (n,))}
+    assert kind == "traj_traverse"
+    return {"status": ("u1", (n,)), "cost": ("<f8", (n,)), "n_samples": ("<i4", (n,)), "n_cells": ("<i4", (n,)), "stop_sample": ("<i4", (n,))}
+
+
+def fill(struct, ptrs, **extra):
+    for k, p in ptrs.items():
+        setattr(struct, k, p)
+    for k, v in extra.items():
+        setattr(struct, k, v)
+    return struct
+
+
+def call(abi, env, w, kind, n, x, ptrs, inp, device):
+    """One call through the C ABI: `ptrs` name the output rows, `inp` the inputs (host addresses, or device addresses
+    for the device-pointer twin)."""
+    L, ctx, sfx = abi.lib(), env._ctx, "_device" if device else ""
+    ns = n * w.nU
+    if kind == "expand":
+        s = fill(abi.Succ(), ptrs, state_stride=ns)
+        rc = getattr(L, "mplx_expand" + sfx)(ctx, inp["nodes"], n, n, C.byref(s))
+    elif kind == "expand_lists":
+        s = fill(abi.SuccLists(), ptrs, state_stride=ns, node_stride=w.nU)
+        rc = getattr(L, "mplx_expand_lists" + sfx)(ctx, inp["nodes"], n, n, C.byref(s))
+    elif kind in ("edges_cap0", "edges_cap3"):
+        o = fill(abi.EdgesOut(), ptrs, cell_cap=3 if kind == "edges_cap3" else 0)
+        rc = L.mplx_check_edges(ctx, inp["nodes"], inp["edge_actions"], n, n, C.byref(o))
+    elif kind == "read_cells":
+        rc = L.mplx_read_cells(ctx, 0, inp["cell_index"], n, ptrs["values"])
+    elif kind == "edit_map":  # observed through the cells it names
+        abi.check(ctx, L.mplx_edit_map(ctx, inp["cell_index"], inp["cell_values"], n))
+        rc = L.mplx_read_cells(ctx, 0, inp["cell_index"], n, ptrs["values"])
+    elif kind in ("rollout", "rollout_goal"):
+        o = fill(abi.RolloutOut(), ptrs, end_stride=n)
+        rc = getattr(L, "mplx_rollout" + sfx)(ctx, inp["nodes"], n, n, inp["actions"], n, H, n, C.byref(o))
+    elif kind == "ray_trace":
+        o = fill(abi.RayOut(), ptrs, cell_cap=CELL_CAP)
+        rc = getattr(L, "mplx_ray_trace" + sfx)(ctx, inp["p1"], inp["p2"], n, n, n if x["p2"].ndim == 2 else 0, 0, C.byref(o))
+    else:
+        s = fill(abi.TrajSet(), {}, starts=inp["nodes"], n_starts=n, start_stride=n, actions=inp["actions"], n_traj=n, horizon=H,
+                 action_stride=n)
+        if kind == "traj_info":
+            o = fill(abi.TrajInfoOut(), ptrs, effort_stride=n, seg_stride=n)
+            rc = getattr(L, "mplx_traj_info" + sfx)(ctx, C.byref(s), C.byref(o))
+        elif kind == "traj_traverse":
+            o = fill(abi.TrajTraverseOut(), ptrs)
+            rc = getattr(L, "mplx_traj_traverse" + sfx)(ctx, C.byref(s), 0, C.byref(o))
+        else:
+            t = abi.TrajTimes()
+            t.form = x["form"]
+            if kind == "sample_uniform":
+                count, t.n_uniform = N_UNIFORM + 1, N_UNIFORM
+            else:
+                count, t.times, t.n_times, t.time_stride = Q, inp["times"], Q, Q if x["times"].ndim == 2 else 0
+            o = fill(abi.TrajSampleOut(), ptrs, row_stride=n * count, sample_stride=count)
+            rc = getattr(L, "mplx_traj_sample" + sfx)(ctx, C.byref(s), C.byref(t), C.byref(o))
+    abi.check(ctx, rc)
+
+
+def host_call(abi, env, w, kind, n, x):
+    out = {k: poisoned(dt, shape) for k, (dt, shape) in out_spec(w, kind, n, x).items()}
+    call(abi, env, w, kind, n, x, {k: a.ctypes.data for k, a in out.items()}, {k: a.ctypes.data for k, a in x.items() if k != "form"}, False)
+    if kind == "edges_cap3":  # mplx.h defines cell_count[e] entries of row e and nothing about the rest of it
+        out["cells"][np.arange(3)[None, :] >= out["cell_count"][:, None]] = 0
+    return out
+
+
+def device_call(engine, env, w, kind, n, x):
+    abi, L = engine._abi, engine._abi.lib()
+    spec = out_spec(w, kind, n, x)
+    rows = {k: engine.DeviceArray(env, int(np.prod(shape)) * np.dtype(dt).itemsize) for k, (dt, shape) in spec.items()}
+    inp = {}
+    for k, a in x.items():
+        if k != "form":
+            inp[k] = engine.DeviceArray(env, a.nbytes)
+            inp[k].upload(a)
+    for r in rows.values():
+        abi.check(env._ctx, L.mplx_memset(env._ctx, r.ptr, POISON, r.nbytes))
+    call(abi, env, w, kind, n, x, {k: r.ptr for k, r in rows.items()}, {k: b.ptr for k, b in inp.items()}, True)
+    env.synchronize()
+    out = {k: rows[k].download(dt, shape) for k, (dt, shape) in spec.items()}
+    for b in list(rows.values()) + list(inp.values()):
+        b.free()
+    return out
+
+
+def raw(a):
+    return np.ascontiguousarray(a).view(np.uint8)
+
+
+def assert_same_bytes(got, want, what):
+    assert sorted(got) == sorted(want), what
+    for k in got:
+        assert np.array_equal(raw(got[k]), raw(want[k])), "%s: row `%s` differs in %d bytes" % (
+            what, k, int((raw(got[k]) != raw(want[k])).sum()))
+
+
+def assert_equals_twin(w, kind, n, host, dev, what):
+    if kind == "expand_lists":  # both forms define the counts and the used prefix of every list
+        assert np.array_equal(host["count"], dev["count"]), what + ": count"
+        used = (np.arange(n * w.nU) % w.nU) < np.repeat(host["count"], w.nU)
+        for k in ("action", "cost", "hash", "iters", "state"):
+            assert np.array_equal(raw(host[k][..., used]), raw(dev[k][..., used])), "%s: row `%s`" % (what, k)
+        return
+    keep = np.ones(host["status"].shape[-1], bool)
+    if kind in ("rollout", "rollout_goal"):
+        band = np.uint8(0x80)  # MPLX_ROLLOUT_HEADING_BAND: the host call resolves these itself
+        assert not np.any(host["status"] & band), what + ": mplx_rollout left a rollout in the heading band"
+        keep = (dev["status"] & band) == 0
+    for k in host:  # the item (rollout, ray, trajectory, pair) is the last axis of every row but these two
+        axis = 0 if (kind, k) == ("ray_trace", "cells") else 1 if k == "out" else -1
+        h, d = np.moveaxis(host[k], axis, 0), np.moveaxis(dev[k], axis, 0)
+        assert np.array_equal(raw(h[keep]), raw(d[keep])), "%s: row `%s` differs from the device-pointer call" % (what, k)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("config", sorted(CONFIGS))
+def test_host_calls_share_the_staging_block_of_a_long_lived_context(engine, monkeypatch, config):
+    monkeypatch.setenv("MPLX_ARENA_KB", "1")  # read by mplx_create: every lists batch takes the large path
+    abi, w = engine._abi, World(config)
+    env = engine.EnvMap(w.dim, 0)
+    w.configure(env)
+    for i, (kind, n, visit) in enumerate(schedule()):
+        what = "%s step %d: %s n=%d visit %d" % (config, i, kind, n, visit)
+        x = w.inputs(i, kind, n, visit)
+        fresh = engine.EnvMap(w.dim, 0)
+        w.configure(fresh)
+        want = host_call(abi, fresh, w, kind, n, x)
+        fresh.close()
+        got = host_call(abi, env, w, kind, n, x)
+        assert_same_bytes(got, want, what)
+        if kind in TWINNED:
+            assert_equals_twin(w, kind, n, got, device_call(engine, env, w, kind, n, x), what)
+        if kind == "edit_map":  # the world follows (the last mention of a cell wins, as in mplx_edit_map)
+            w.cells.ravel()[x["cell_index"]] = x["cell_values"]
+            assert np.array_equal(got["values"], w.cells.ravel()[x["cell_index"]]), what
+    env.close()
