@@ -47,6 +47,10 @@ TRAJ_SYMBOLS = ["mplx_traj_info_device", "mplx_traj_info", "mplx_traj_sample_dev
                 "mplx_traj_traverse_device", "mplx_traj_traverse"]
 TRAJ_EMPTY, TRAJ_BAD_ACTION, TRAJ_BAD = 1, 2, 4
 TRAJ_COMMAND, TRAJ_WAYPOINT = 0, 1
+# ... and the ones include/mplx_table.h declares (the persistent node table: relax, frontier, path)
+TABLE_SYMBOLS = ["mplx_table_create", "mplx_table_destroy", "mplx_table_clear", "mplx_table_view_of", "mplx_table_stats",
+                 "mplx_table_seed", "mplx_table_relax_device", "mplx_table_find_device", "mplx_table_find", "mplx_table_path"]
+TABLE_NODES_FULL, TABLE_PROBE_FULL, TABLE_FRONTIER_FULL = 1, 2, 4
 
 ROUTE_AUTO, ROUTE_DENSE, ROUTE_TILE, ROUTE_GRID = 0, 1, 2, 3
 
@@ -110,6 +114,16 @@ class TrajSampleOut(C.Structure):
 class TrajTraverseOut(C.Structure):
     _fields_ = [("status", C.c_void_p), ("cost", C.c_void_p), ("n_samples", C.c_void_p), ("n_cells", C.c_void_p),
                 ("stop_sample", C.c_void_p)]
+
+
+class TableView(C.Structure):
+    _fields_ = [("hash", C.c_void_p), ("g", C.c_void_p), ("pred", C.c_void_p), ("pred_action", C.c_void_p),
+                ("state", C.c_void_p), ("state_stride", C.c_int64)]
+
+
+class TableFrontier(C.Structure):
+    _fields_ = [("id", C.c_void_p), ("g", C.c_void_p), ("state", C.c_void_p), ("state_stride", C.c_int64),
+                ("capacity", C.c_int64), ("count", C.c_void_p)]
 
 
 class PackedLists(C.Structure):
@@ -283,8 +297,19 @@ def lib():
         "mplx_traj_sample": (C.c_int, [vp, C.POINTER(TrajSet), C.POINTER(TrajTimes), C.POINTER(TrajSampleOut)]),
         "mplx_traj_traverse_device": (C.c_int, [vp, C.POINTER(TrajSet), i32, C.POINTER(TrajTraverseOut)]),
         "mplx_traj_traverse": (C.c_int, [vp, C.POINTER(TrajSet), i32, C.POINTER(TrajTraverseOut)]),
+        "mplx_table_create": (C.c_int, [vp, i64, i32, C.POINTER(vp)]),
+        "mplx_table_destroy": (None, [vp]),
+        "mplx_table_clear": (C.c_int, [vp]),
+        "mplx_table_view_of": (C.c_int, [vp, C.POINTER(TableView)]),
+        "mplx_table_stats": (C.c_int, [vp, C.POINTER(i64), C.POINTER(C.c_uint32)]),
+        "mplx_table_seed": (C.c_int, [vp, vp, i64, i64, vp, C.POINTER(TableFrontier), C.POINTER(i64)]),
+        "mplx_table_relax_device": (C.c_int, [vp, C.POINTER(SuccLists), i64, vp, vp, dbl, C.POINTER(TableFrontier), vp,
+                                              C.POINTER(i64)]),
+        "mplx_table_find_device": (C.c_int, [vp, vp, i64, vp]),
+        "mplx_table_find": (C.c_int, [vp, vp, i64, vp]),
+        "mplx_table_path": (C.c_int, [vp, i32, vp, vp, i64, C.POINTER(i64)]),
     }
-    for name in SYMBOLS + MAP_UTIL_SYMBOLS + ROLLOUT_SYMBOLS + RAY_SYMBOLS + TRAJ_SYMBOLS:
+    for name in SYMBOLS + MAP_UTIL_SYMBOLS + ROLLOUT_SYMBOLS + RAY_SYMBOLS + TRAJ_SYMBOLS + TABLE_SYMBOLS:
         fn = getattr(L, name)  # AttributeError if the library does not export it
         fn.restype, fn.argtypes = sig[name]
     _lib = L

@@ -491,6 +491,59 @@ hipError_t launch_traj_chain(int dim, int control, const TrajArgs &a, hipStream_
 hipError_t launch_traj_sample(int dim, int form, const TrajArgs &a, hipStream_t s);
 hipError_t launch_traj_traverse(int dim, int lanes, const TrajArgs &a, hipStream_t s);  // lanes in {4, 16, 64}
 
+// Persistent node table (table_kernel.hip, table_api.cpp; include/mplx_table.h).
+struct TableSlot { uint64_t key; int32_t id; uint32_t first_e; };  // all bytes 0xff: empty, no id, no claimant
+struct TableCtl {      // device memory
+  int32_t n_nodes;     // nodes in the table
+  int32_t base;        // ... before the call in flight (the ids of its new nodes start here)
+  uint32_t status;     // MPLX_TABLE_* bits, sticky
+  int32_t emit;        // the call in flight got as far as its frontier
+};
+struct TableMirror { int64_t n_nodes; uint32_t status; };  // pinned host memory: what the last finished call left in TableCtl
+struct TableArgs {
+  // the table: n_slots (a power of two) + 1 slots, the last one for the hash equal to the empty marker
+  TableSlot *slots;
+  uint64_t n_slots;
+  uint64_t *hash;
+  unsigned long long *g;     // the doubles' bit patterns: non-negative doubles order like uint64 (atomicMin)
+  int32_t *pred, *pred_action;
+  double *state;             // [n_fields][cap]
+  unsigned long long *pick;  // per node (tag << 32 | e): improved in the call `tag` belongs to, by entry e at the earliest
+  int64_t cap;
+  int32_t n_fields;
+  uint32_t tag;              // 0xffffffff - epoch of the call: later calls carry SMALLER tags, so atomicMin prefers them
+  TableCtl *ctl;
+  TableMirror *mirror;
+  // the entries: n_rows lists of S entries.  Seeds: S = 1, count / action / cost / parent_id null (cand = parent_g[k], or 0)
+  const int32_t *count, *action;
+  const double *cost;
+  const uint64_t *src_hash;
+  const double *src_state;
+  int64_t src_sstride;
+  int64_t n_rows, S;
+  const int32_t *parent_id;
+  const double *parent_g;
+  double g_max;
+  // scratch of the table: per entry its slot, then its node id; per entry a mark; per tile of 4096 entries a count
+  uint32_t *ent;
+  uint8_t *mark;
+  uint32_t *tot;
+  int64_t n_tiles;
+  // outputs
+  int32_t *f_id;
+  double *f_g, *f_state;
+  int64_t f_stride, f_cap;
+  int64_t *f_count;
+  int32_t *entry_id;  // or null
+};
+constexpr int kTableTile = 4096;
+hipError_t launch_table_relax(const TableArgs &a, hipStream_t s);
+hipError_t launch_table_clear(const TableArgs &a, hipStream_t s);  // slots, control block and mirror
+hipError_t launch_table_hash(int dim, int control, const double *states, int64_t n, int64_t stride, uint64_t *hash, hipStream_t s);
+hipError_t launch_table_find(const TableArgs &a, const uint64_t *hash, int64_t n, int32_t *id, hipStream_t s);
+// leaf first: ids[0 .. len], actions[0 .. len); *len < 0: -1 more than cap edges, -2 bad id, -3 no seed within n_nodes steps
+hipError_t launch_table_path(const TableArgs &a, int32_t id, int32_t *ids, int32_t *actions, int64_t cap, int64_t *len, hipStream_t s);
+
 // Element-wise math probe (see mplx_selftest_math in mplx.h).
 hipError_t launch_math_probe(int op, const double *a, const double *b, double *out, int64_t n,
                              hipStream_t stream);

@@ -1274,6 +1274,53 @@ class EnvMap:
         o = out.c_struct()
         _abi.check(self._ctx, _abi.lib().mplx_traj_traverse_device(self._ctx, C.byref(s), int(lanes), C.byref(o)))
 
+    # ---- the persistent node table (include/mplx_table.h; table.py): relax successor lists, emit the next frontier
+    def alloc_table(self, capacity, slots_log2=0):
+        from .table import NodeTable
+        return NodeTable(self, capacity, slots_log2)
+
+    def alloc_table_frontier(self, capacity):
+        from .table import TableFrontier
+        return TableFrontier(self, capacity)
+
+    def cost_to_come(self, starts, g=None, g_max=float("inf"), max_rounds=None, capacity=1 << 16, lists_stride=None,
+                     max_frontier=None):
+        """A label-correcting sweep from `starts` ([4D+2][n] or one state; cost-to-come g, default 0): seed, then while
+        the frontier is not empty expand it, relax its lists against the table, and go on with the nodes whose g fell.
+        Nodes with g > g_max are never created.  Everything stays on the device; the host reads one 8-byte count per
+        round.  Lists and the two frontiers are allocated once, for max_frontier nodes (default: capacity, which no
+        frontier can exceed).  Returns (table, rounds): rounds = relax calls made; at the fixed point (the last one left
+        an empty frontier) table.download()["g"] is the exact cost-to-come of every reachable lattice state within
+        g_max.  A table that ran out of nodes, probe length or frontier raises."""
+        from .table import NodeTable, TableFrontier
+        self._flush()
+        fcap = int(capacity if max_frontier is None else max_frontier)
+        tab = NodeTable(self, capacity)
+        cur, nxt = TableFrontier(self, fcap), TableFrontier(self, fcap)
+        lists = self.alloc_lists(fcap, want_state=True, stride=lists_stride)
+        try:
+            def check(where):
+                status = tab.stats()[1]  # (the stream is idle: no copy, no wait)
+                if status:
+                    raise RuntimeError("cost_to_come: table status %d %s (1 nodes full, 2 probe full, 4 frontier full): "
+                                       "raise capacity / max_frontier" % (status, where))
+            count = tab.seed(starts, g, frontier=cur)
+            check("after seeding")
+            rounds = 0
+            while count > 0 and (max_rounds is None or rounds < max_rounds):
+                self.expand_lists_resident(cur, lists, n_nodes=count)
+                count = tab.relax(lists, cur.id, cur.g, g_max, frontier=nxt, n_nodes=count)
+                rounds += 1
+                check("in round %d" % rounds)
+                cur, nxt = nxt, cur
+        except Exception:
+            tab.free()
+            raise
+        finally:
+            for b in (cur, nxt, lists):
+                b.free()
+        return tab, rounds
+
     def synchronize(self):
         _abi.check(self._ctx, _abi.lib().mplx_synchronize(self._ctx))
 
