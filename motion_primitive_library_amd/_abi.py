@@ -51,6 +51,11 @@ TRAJ_COMMAND, TRAJ_WAYPOINT = 0, 1
 TABLE_SYMBOLS = ["mplx_table_create", "mplx_table_destroy", "mplx_table_clear", "mplx_table_view_of", "mplx_table_stats",
                  "mplx_table_seed", "mplx_table_relax_device", "mplx_table_find_device", "mplx_table_find", "mplx_table_path"]
 TABLE_NODES_FULL, TABLE_PROBE_FULL, TABLE_FRONTIER_FULL = 1, 2, 4
+# ... and the ones include/mplx_open.h declares (the open set of a table: push, select)
+OPEN_SYMBOLS = ["mplx_open_create", "mplx_open_destroy", "mplx_open_clear", "mplx_open_view_of", "mplx_open_push_device",
+                "mplx_open_select_device"]
+OPEN_IS_OPEN, OPEN_IS_GOAL, OPEN_SEEN = 1, 2, 4
+OPEN_SELECTED, OPEN_FOUND, OPEN_EMPTY = 0, 1, 2
 
 ROUTE_AUTO, ROUTE_DENSE, ROUTE_TILE, ROUTE_GRID = 0, 1, 2, 3
 
@@ -124,6 +129,15 @@ class TableView(C.Structure):
 class TableFrontier(C.Structure):
     _fields_ = [("id", C.c_void_p), ("g", C.c_void_p), ("state", C.c_void_p), ("state_stride", C.c_int64),
                 ("capacity", C.c_int64), ("count", C.c_void_p)]
+
+
+class OpenView(C.Structure):
+    _fields_ = [("f", C.c_void_p), ("flags", C.c_void_p)]
+
+
+class OpenResult(C.Structure):
+    _fields_ = [("status", C.c_int32), ("goal_id", C.c_int32), ("count", C.c_int64), ("n_open", C.c_int64),
+                ("f_min", C.c_double), ("goal_f", C.c_double), ("goal_g", C.c_double)]
 
 
 class PackedLists(C.Structure):
@@ -308,8 +322,14 @@ def lib():
         "mplx_table_find_device": (C.c_int, [vp, vp, i64, vp]),
         "mplx_table_find": (C.c_int, [vp, vp, i64, vp]),
         "mplx_table_path": (C.c_int, [vp, i32, vp, vp, i64, C.POINTER(i64)]),
+        "mplx_open_create": (C.c_int, [vp, C.POINTER(vp)]),
+        "mplx_open_destroy": (None, [vp]),
+        "mplx_open_clear": (C.c_int, [vp]),
+        "mplx_open_view_of": (C.c_int, [vp, C.POINTER(OpenView)]),
+        "mplx_open_push_device": (C.c_int, [vp, C.POINTER(TableFrontier), i64, dbl, i32]),
+        "mplx_open_select_device": (C.c_int, [vp, dbl, C.POINTER(TableFrontier), vp, C.POINTER(OpenResult)]),
     }
-    for name in SYMBOLS + MAP_UTIL_SYMBOLS + ROLLOUT_SYMBOLS + RAY_SYMBOLS + TRAJ_SYMBOLS + TABLE_SYMBOLS:
+    for name in SYMBOLS + MAP_UTIL_SYMBOLS + ROLLOUT_SYMBOLS + RAY_SYMBOLS + TRAJ_SYMBOLS + TABLE_SYMBOLS + OPEN_SYMBOLS:
         fn = getattr(L, name)  # AttributeError if the library does not export it
         fn.restype, fn.argtypes = sig[name]
     _lib = L

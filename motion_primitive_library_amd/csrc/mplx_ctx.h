@@ -14,6 +14,8 @@
 #include <string>
 #include <vector>
 
+struct mplx_table;  // include/mplx_table.h
+
 namespace mplx_detail {
 
 struct DevBuf {
@@ -332,6 +334,13 @@ int wait_small_launch(mplx_ctx *c);
 // lists_copy_api.cpp: device lists -> host lists, only the used prefixes, pipelined through pinned memory
 int copy_lists_to_host(mplx_ctx *c, const mplx_succ_lists &d, const mplx_succ_lists *h_out, int64_t n_nodes);
 void release_copy_buffers(mplx_ctx *c);
+
+
+// table_api.cpp: the table as its open set (open_api.cpp) sees it.  table_open_args: the table's context, MPLX_ERR_STATE
+// (with `who` in the text) once the host has seen a status bit, else the table fields of `a`.  table_observe: after a
+// wait for the stream, what the last finished call left (status bit, node count).
+int table_open_args(mplx_table *t, const char *who, mplx_ctx **c, mplx::OpenArgs *a);
+void table_observe(mplx_table *t);
 
 }  // namespace mplx_detail
 #endif

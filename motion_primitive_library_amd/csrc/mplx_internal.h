@@ -544,6 +544,51 @@ hipError_t launch_table_find(const TableArgs &a, const uint64_t *hash, int64_t n
 // leaf first: ids[0 .. len], actions[0 .. len); *len < 0: -1 more than cap edges, -2 bad id, -3 no seed within n_nodes steps
 hipError_t launch_table_path(const TableArgs &a, int32_t id, int32_t *ids, int32_t *actions, int64_t cap, int64_t *len, hipStream_t s);
 
+// Open set of a node table (open_kernel.hip, open_api.cpp; include/mplx_open.h).
+struct OpenResult { int32_t status, goal_id; int64_t count, n_open; double f_min, goal_f, goal_g; };  // mplx_open_result
+struct OpenCtl {                   // device memory; two of them, used by alternate selects: a select's scan resets the other
+  unsigned long long fmin_bits;    // min over the open nodes of f's bit pattern (+inf: none)
+  unsigned long long goalf_bits;   // ... over the goal-region nodes
+  uint32_t n_open, n_goal;
+  int32_t goal_id;                 // smallest id among the goal-region nodes with f == goal_f (INT32_MAX: none yet)
+  int32_t emit;                    // the select in flight is SELECTED and got as far as its frontier
+};
+struct OpenArgs {
+  // the table (read only)
+  const TableCtl *t_ctl;
+  const uint64_t *t_hash;
+  const unsigned long long *t_g;
+  const double *t_state;           // [n_fields][cap]
+  int64_t cap;
+  int32_t n_fields;
+  // the open set
+  unsigned long long *f;           // the doubles' bit patterns: non-negative doubles order like uint64
+  uint8_t *flags;
+  OpenCtl *ctl, *ctl_next;
+  OpenResult *mirror;              // pinned host memory: the result of the last finished select
+  int64_t n_bound;                 // host-known upper bound of the table's n_nodes: sizes the grids
+  // push: rows [0, min(*f_count, n_max, f_cap)) of the frontier; row_flags != null: the two-pass form around the ray trace
+  int64_t n_max;
+  double eps;
+  PostFuse goal;                   // goal of mplx_set_goal (output pointers unused)
+  uint8_t *row_flags;              // [rows] bit 0 inside the tolerances, bit 3 ray blocked (goal_trace_kernel), bit 7 the row counts
+  int32_t *row_count;              // [rows] all 1: the frontier as lists of stride 1
+  // select
+  double delta;
+  uint8_t *mark;                   // [n_bound]
+  uint32_t *tot;                   // [n_tiles]
+  int64_t n_tiles;
+  OpenResult *result;              // device memory of the caller, or null
+  // the frontier: read by push, written by select
+  int32_t *f_id;
+  double *f_g, *f_state;
+  int64_t f_stride, f_cap;
+  int64_t *f_count;
+};
+hipError_t launch_open_clear(const OpenArgs &a, hipStream_t s);
+hipError_t launch_open_push(int dim, int pass, const OpenArgs &a, int64_t rows, hipStream_t s);  // pass 0: all (or up to the row flags); 1: after the ray trace
+hipError_t launch_open_select(const OpenArgs &a, hipStream_t s);
+
 // Element-wise math probe (see mplx_selftest_math in mplx.h).
 hipError_t launch_math_probe(int op, const double *a, const double *b, double *out, int64_t n,
                              hipStream_t stream);

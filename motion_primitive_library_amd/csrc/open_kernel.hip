@@ -1,0 +1,294 @@
+// open_kernel.hip -- the open set of a node table (include/mplx_open.h): what GraphSearch::Astar keeps in its priority
+// queue (reference include/mpl_planner/common/graph_search.h:53-143: the key g + eps * h, pop the smallest, re-open a
+// closed node whose g fell, stop when the goal is at the top), for whole batches on the arrays of table_kernel.hip.
+//
+// The table's discipline holds here too: a launch boundary is the only ordering between
+// passes, no workgroup waits for another, only order-free atomics (min, add) decide anything, and ranks come from prefix
+// sums in id order -- every output is a pure function of the inputs.
+//
+// A push is one lane per frontier row: the fused heuristic and tolerance test of the expansion kernels (dev::post_eval)
+// on the row's state, f = g + eps * h, one 8-byte and one 1-byte store per node.  With the ray trace it is two passes
+// around the goal passes of ray_kernel.hip, which see the frontier as lists of stride 1.
+//
+// A select is four launches:
+//   reduce   per node: wave minima of f's bit patterns over the open nodes and over the goal-region nodes (non-negative
+//            doubles order like uint64, as the table's lower pass uses), one 64-bit atomicMin per wave; both sets counted
+//   mark     per tile of 4096 ids: the status from the control block; SELECTED: open nodes with f <= f_min + delta are
+//            marked and counted per tile; goal-region nodes with f == goal_f: atomicMin(goal_id)
+//   scan     exclusive prefix sums of the tile counts (one workgroup), clamped to the frontier's capacity; the result
+//            block, the frontier count, the pinned mirror; resets the control block of the NEXT select
+//   emit     marked nodes in id order -> id, g and the state rows gathered from the table; IS_OPEN is cleared for the
+//            ranks below the capacity only
+// Every index is checked where it is formed: ids against the table's own node count, rows against the frontier's
+// capacity.  A table with a status bit makes every pass return at its first instruction.
+#include "mplx_internal.h"
+#include "mplx_device_common.h"
+
+namespace mplx {
+namespace {
+
+constexpr int kBlock = 256;
+constexpr int kItems = kTableTile / kBlock;
+constexpr unsigned long long kInfBits = 0x7ff0000000000000ull;
+constexpr uint8_t kIsOpen = 1, kIsGoal = 2, kSeen = 4;  // MPLX_OPEN_* of include/mplx_open.h
+constexpr int32_t kSelected = 0, kFound = 1, kEmpty = 2;
+constexpr uint8_t kRowTol = 1, kRowBlocked = 8, kRowCounts = 0x80;
+
+__device__ __forceinline__ int64_t node_count(const OpenArgs &A) {
+  const int64_t n = A.t_ctl->n_nodes;
+  return n < 0 ? 0 : (n < A.cap ? n : A.cap);
+}
+
+__device__ __forceinline__ unsigned long long wave_min(unsigned long long v) {
+  for (int d = 32; d > 0; d >>= 1) {
+    const unsigned long long o = ((unsigned long long)(uint32_t)__shfl_xor((int)(v >> 32), d) << 32) | (unsigned long long)(uint32_t)__shfl_xor((int)v, d);
+    v = o < v ? o : v;
+  }
+  return v;
+}
+
+// What the control block decides once the reduce pass is complete.
+struct Decision {
+  int32_t status;
+  double f_min, goal_f, T;
+  unsigned long long goalf_bits;
+  bool any_goal;
+};
+__device__ __forceinline__ Decision decide(const OpenArgs &A) {
+  Decision d;
+  const uint32_t n_open = A.ctl->n_open;
+  d.any_goal = A.ctl->n_goal != 0;
+  d.goalf_bits = A.ctl->goalf_bits;
+  d.f_min = __longlong_as_double((long long)A.ctl->fmin_bits);
+  d.goal_f = __longlong_as_double((long long)d.goalf_bits);
+  d.status = (d.any_goal && d.goal_f <= d.f_min) ? kFound : n_open == 0 ? kEmpty : kSelected;
+  d.T = d.f_min + A.delta;
+  return d;
+}
+
+template <int D>
+__global__ __launch_bounds__(kBlock) void open_push_kernel(const OpenArgs A, int64_t rows, int pass) {
+  if (A.t_ctl->status) return;
+  const int64_t r = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (r >= rows) return;  // rows <= min(n_max, f_cap): the host's bound
+  if (pass == 0 && A.row_flags) {
+    A.row_flags[r] = 0;
+    A.row_count[r] = 1;
+  }
+  int64_t n = *A.f_count;
+  n = n < A.n_max ? n : A.n_max;
+  n = n < A.f_cap ? n : A.f_cap;
+  if (r >= n) return;
+  const int64_t id = A.f_id[r];
+  if (id < 0 || id >= node_count(A)) return;
+  if (pass == 1) {
+    const uint8_t rf = A.row_flags[r];
+    if (rf & kRowCounts) A.flags[id] = (uint8_t)(kSeen | kIsOpen | (((rf & kRowTol) && !(rf & kRowBlocked)) ? kIsGoal : 0));
+    return;
+  }
+  double s[4 * D + 1];
+#pragma unroll
+  for (int i = 0; i < 3 * D; i++) s[i] = A.f_state[(int64_t)i * A.f_stride + r];
+  s[4 * D] = A.f_state[(int64_t)(4 * D) * A.f_stride + r];
+  MPLX_POST_GOAL(PG, A.goal, D)
+  double h;
+  unsigned int fl;
+  dev::post_eval<D>(PG, A.t_hash[id], s, s + D, s + 2 * D, s[4 * D], &h, &fl);
+  const double g = A.f_g[r];
+  double f = g;
+  if (A.eps != 0.0) {
+    const double eh = A.eps * h;
+    f = g + eh;
+  }
+  if (!(f >= 0.0)) return;
+  f = f + 0.0;  // -0.0 -> +0.0: the bit patterns of the keys order like the keys
+  A.f[id] = (unsigned long long)__double_as_longlong(f);
+  if (A.row_flags) A.row_flags[r] = (uint8_t)(kRowCounts | (fl & 1u));
+  else A.flags[id] = (uint8_t)(kSeen | kIsOpen | ((fl & 1u) ? kIsGoal : 0));
+}
+
+__global__ __launch_bounds__(kBlock) void open_reduce_kernel(const OpenArgs A) {
+  if (A.t_ctl->status) return;  // (uniform)
+  const int64_t id = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  unsigned long long fo = kInfBits, fg = kInfBits;
+  bool o = false, g = false;
+  if (id < node_count(A)) {
+    const uint8_t fl = A.flags[id];
+    o = (fl & kIsOpen) != 0;
+    g = (fl & kIsGoal) != 0;
+    if (o || g) {
+      const unsigned long long v = A.f[id];
+      if (o) fo = v;
+      if (g) fg = v;
+    }
+  }
+  const unsigned long long bo = __ballot(o), bg = __ballot(g);  // the wave's sets, in every lane
+  if (bo) fo = wave_min(fo);
+  if (bg) fg = wave_min(fg);
+  if ((threadIdx.x & 63) != 0) return;
+  if (bo) {
+    atomicMin(&A.ctl->fmin_bits, fo);
+    atomicAdd(&A.ctl->n_open, (uint32_t)__popcll(bo));
+  }
+  if (bg) {
+    atomicMin(&A.ctl->goalf_bits, fg);
+    atomicAdd(&A.ctl->n_goal, (uint32_t)__popcll(bg));
+  }
+}
+
+__global__ __launch_bounds__(kBlock) void open_mark_kernel(const OpenArgs A) {
+  if (A.t_ctl->status) return;  // (uniform: nothing below is skipped by part of a workgroup)
+  __shared__ uint32_t wsum[kBlock / 64];
+  const int64_t n = node_count(A), base = (int64_t)blockIdx.x * kTableTile;
+  const Decision d = decide(A);
+  uint32_t cnt = 0;
+  for (int i = 0; i < kItems; i++) {
+    const int64_t id = base + (int64_t)i * kBlock + threadIdx.x;
+    bool m = false;
+    if (id < n) {
+      const uint8_t fl = A.flags[id];
+      if (fl & (kIsOpen | kIsGoal)) {
+        const unsigned long long v = A.f[id];
+        if ((fl & kIsGoal) && v == d.goalf_bits) atomicMin(&A.ctl->goal_id, (int32_t)id);
+        m = d.status == kSelected && (fl & kIsOpen) && __longlong_as_double((long long)v) <= d.T;
+      }
+      A.mark[id] = m ? 1 : 0;
+    }
+    cnt += (uint32_t)__popcll(__ballot(m));  // the wave's count, in every lane
+  }
+  if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = cnt;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    uint32_t t = 0;
+    for (int w = 0; w < kBlock / 64; w++) t += wsum[w];
+    A.tot[blockIdx.x] = t;
+  }
+}
+
+// table_scan_kernel's scan of the tile counts, then the result of the select.
+__global__ __launch_bounds__(1024) void open_scan_kernel(const OpenArgs A) {
+  __shared__ uint32_t part[1024];
+  if (A.t_ctl->status) return;  // (uniform)
+  const int t = threadIdx.x;
+  const int64_t per = (A.n_tiles + 1023) / 1024;
+  const int64_t a = (int64_t)t * per < A.n_tiles ? (int64_t)t * per : A.n_tiles, b = a + per < A.n_tiles ? a + per : A.n_tiles;
+  uint32_t s = 0;
+  for (int64_t k = a; k < b; k++) s += A.tot[k];
+  part[t] = s;
+  __syncthreads();
+  for (int d = 1; d < 1024; d <<= 1) {
+    const uint32_t v = t >= d ? part[t - d] : 0;
+    __syncthreads();
+    part[t] += v;
+    __syncthreads();
+  }
+  uint32_t run = part[t] - s;
+  for (int64_t k = a; k < b; k++) {
+    const uint32_t c = A.tot[k];
+    A.tot[k] = run;
+    run += c;
+  }
+  if (t != 0) return;
+  const Decision d = decide(A);
+  int64_t cnt = 0;
+  if (d.status == kSelected) {
+    cnt = part[1023];
+    if (cnt > A.f_cap) cnt = A.f_cap;  // the rest stay open
+  }
+  A.ctl->emit = cnt > 0 ? 1 : 0;
+  *A.f_count = cnt;
+  OpenResult R;
+  R.status = d.status;
+  R.goal_id = d.any_goal ? A.ctl->goal_id : -1;
+  R.count = cnt;
+  R.n_open = (int64_t)A.ctl->n_open - cnt;
+  R.f_min = d.f_min;
+  R.goal_f = d.goal_f;
+  R.goal_g = (R.goal_id >= 0 && R.goal_id < node_count(A)) ? __longlong_as_double((long long)A.t_g[R.goal_id]) : __longlong_as_double((long long)kInfBits);
+  if (A.result) *A.result = R;
+  // the pinned mirror: what the host reads, without a copy, once it has waited for the stream
+  __hip_atomic_store(&A.mirror->goal_id, R.goal_id, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  __hip_atomic_store(&A.mirror->count, R.count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  __hip_atomic_store(&A.mirror->n_open, R.n_open, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  __hip_atomic_store(&A.mirror->f_min, R.f_min, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  __hip_atomic_store(&A.mirror->goal_f, R.goal_f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  __hip_atomic_store(&A.mirror->goal_g, R.goal_g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  __hip_atomic_store(&A.mirror->status, R.status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  // the next select reduces into the other control block (this one is read by the emit pass behind this launch)
+  A.ctl_next->fmin_bits = kInfBits;
+  A.ctl_next->goalf_bits = kInfBits;
+  A.ctl_next->n_open = 0;
+  A.ctl_next->n_goal = 0;
+  A.ctl_next->goal_id = 0x7fffffff;
+  A.ctl_next->emit = 0;
+}
+
+// Rank of every marked node of a tile in id order = its frontier row.
+__global__ __launch_bounds__(kBlock) void open_emit_kernel(const OpenArgs A) {
+  if (A.t_ctl->status || A.ctl->emit == 0) return;  // (uniform)
+  __shared__ uint32_t wsum[kBlock / 64];
+  const int64_t n = node_count(A), base = (int64_t)blockIdx.x * kTableTile;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  int64_t run = A.tot[blockIdx.x];
+  for (int i = 0; i < kItems; i++) {
+    const int64_t id = base + (int64_t)i * kBlock + threadIdx.x;
+    const bool m = id < n && A.mark[id] != 0;
+    const unsigned long long bal = __ballot(m);
+    if (lane == 0) wsum[wave] = (uint32_t)__popcll(bal);
+    __syncthreads();
+    uint32_t before = 0, all = 0;
+    for (int w = 0; w < kBlock / 64; w++) {
+      if (w < wave) before += wsum[w];
+      all += wsum[w];
+    }
+    __syncthreads();
+    const int64_t r = run + before + (int64_t)__popcll(bal & ((1ull << lane) - 1ull));
+    run += all;
+    if (!m || r >= A.f_cap) continue;
+    A.flags[id] = (uint8_t)(A.flags[id] & ~kIsOpen);
+    A.f_id[r] = (int32_t)id;
+    A.f_g[r] = __longlong_as_double((long long)A.t_g[id]);
+    for (int f = 0; f < A.n_fields; f++) A.f_state[(int64_t)f * A.f_stride + r] = A.t_state[(int64_t)f * A.cap + id];
+  }
+}
+
+__global__ void open_clear_kernel(const OpenArgs A) {
+  OpenCtl *both[2] = {A.ctl, A.ctl_next};
+  for (int i = 0; i < 2; i++) {
+    both[i]->fmin_bits = kInfBits;
+    both[i]->goalf_bits = kInfBits;
+    both[i]->n_open = 0;
+    both[i]->n_goal = 0;
+    both[i]->goal_id = 0x7fffffff;
+    both[i]->emit = 0;
+  }
+}
+
+}  // namespace
+
+hipError_t launch_open_clear(const OpenArgs &a, hipStream_t s) {
+  if (hipError_t e = hipMemsetAsync(a.flags, 0, (size_t)a.cap, s)) return e;
+  hipLaunchKernelGGL(open_clear_kernel, dim3(1), dim3(1), 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_open_push(int dim, int pass, const OpenArgs &a, int64_t rows, hipStream_t s) {
+  if (rows <= 0) return hipSuccess;
+  const dim3 grid((unsigned)((rows + kBlock - 1) / kBlock)), block(kBlock);
+  if (dim == 2) hipLaunchKernelGGL(open_push_kernel<2>, grid, block, 0, s, a, rows, pass);
+  else if (dim == 3) hipLaunchKernelGGL(open_push_kernel<3>, grid, block, 0, s, a, rows, pass);
+  else return hipErrorInvalidValue;
+  return hipGetLastError();
+}
+
+hipError_t launch_open_select(const OpenArgs &a, hipStream_t s) {
+  const int64_t n = a.n_bound > 0 ? a.n_bound : 1;  // (an empty table still gets its result)
+  const dim3 per_node((unsigned)((n + kBlock - 1) / kBlock)), per_tile((unsigned)a.n_tiles), block(kBlock);
+  hipLaunchKernelGGL(open_reduce_kernel, per_node, block, 0, s, a);
+  hipLaunchKernelGGL(open_mark_kernel, per_tile, block, 0, s, a);
+  hipLaunchKernelGGL(open_scan_kernel, dim3(1), dim3(1024), 0, s, a);
+  hipLaunchKernelGGL(open_emit_kernel, per_tile, block, 0, s, a);
+  return hipGetLastError();
+}
+
+}  // namespace mplx

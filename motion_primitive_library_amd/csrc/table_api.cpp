@@ -19,6 +19,7 @@ struct mplx_table {
   DevBuf scratch;                    // per-call passes (ent, mark, tile counts, seed hashes); grows on demand
   mplx::TableMirror *mirror = nullptr;  // pinned
   uint32_t epoch = 0;                // calls since the last clear
+  int64_t bound = 0;                 // upper bound of n_nodes: the mirror's value at the last wait + what the calls queued since can add
   bool poisoned = false;             // the host has seen a status bit
 };
 
@@ -59,6 +60,7 @@ int usable(mplx_table *t, const char *who) {
 // after a wait for the stream: what the last finished call left
 void observe(mplx_table *t) {
   if (*(volatile uint32_t *)&t->mirror->status) t->poisoned = true;
+  else t->bound = *(volatile int64_t *)&t->mirror->n_nodes;
 }
 
 int check_frontier(mplx_ctx *c, const char *who, const mplx_table_frontier *f) {
@@ -84,6 +86,7 @@ int run_passes(mplx_table *t, mplx::TableArgs *a, const mplx_table_frontier *f, 
   if (t->epoch >= 0xfffffff0u) return fail(c, MPLX_ERR_STATE, "mplx_table: 2^32 calls since the last mplx_table_clear");
   t->epoch++;
   a->tag = 0xffffffffu - t->epoch;
+  t->bound = std::min(t->cap, t->bound + n);  // every entry may be a new node
   return MPLX_OK;
 }
 
@@ -96,6 +99,26 @@ int read_count(mplx_table *t, const mplx_table_frontier *f, int64_t *h_count) {
 }
 
 }  // namespace
+
+// What the open set of a table (open_api.cpp) needs of it.
+namespace mplx_detail {
+
+int table_open_args(mplx_table *t, const char *who, mplx_ctx **c, mplx::OpenArgs *a) {
+  *c = t->c;
+  if (int rc = usable(t, who)) return rc;
+  a->t_ctl = (const mplx::TableCtl *)t->ctl.p;
+  a->t_hash = (const uint64_t *)t->hash.p;
+  a->t_g = (const unsigned long long *)t->g.p;
+  a->t_state = (const double *)t->state.p;
+  a->cap = t->cap;
+  a->n_fields = t->F;
+  a->n_bound = t->bound;
+  return MPLX_OK;
+}
+
+void table_observe(mplx_table *t) { observe(t); }
+
+}  // namespace mplx_detail
 
 extern "C" {
 
@@ -157,6 +180,7 @@ int mplx_table_clear(mplx_table *t) {
   HIP_TRY(c, mplx::launch_table_clear(table_args(t), c->stream));
   t->epoch = 0;
   t->poisoned = false;
+  t->bound = 0;
   return MPLX_OK;
 }
 

@@ -1321,6 +1321,28 @@ class EnvMap:
                 b.free()
         return tab, rounds
 
+    # ---- the open set of a table (include/mplx_open.h; search.py): goal-directed search on the device
+    def alloc_open(self, table):
+        from .search import OpenSet
+        return OpenSet(self, table)
+
+    def search(self, start, goal_row, eps=1.0, delta=None, g_max=float("inf"), max_rounds=None, max_expand=None,
+               capacity=1 << 16, max_frontier=None, lists_stride=None, sight=True, tol_pos=0.5, tol_vel=-1.0, tol_acc=-1.0,
+               tol_yaw=-1.0, w=None, v_max=None):
+        """A goal-directed search from `start` (one 4D+2 state) to the goal region of `goal_row` that stays on the
+        device: set_goal, seed, push; then per round one select (the round's only read-back, 48 bytes), and while it
+        selects: expand the selection, relax its lists against the table, push the nodes whose g fell.  Keys are
+        f = g + eps * h with the default heuristic; a select takes every open node with f <= f_min + delta (default
+        delta: w * dt, the time term every edge costs at least; 0 is A*'s one-key-at-a-time order, +inf the
+        label-correcting sweep) and announces the goal once no open key is below the best goal-region node's.
+        sight: a goal-region node also needs a free line of sight to the goal (env_map::is_goal's ray trace).
+        Nodes with g > g_max are never created.  Lists and the selection frontier are allocated for max_frontier nodes
+        (default: capacity); a larger selection is taken in id order, the rest stays open.  Returns a SearchResult
+        (search.py) that owns the table and the open set.  A table that ran out of nodes or probe length raises."""
+        from .search import run_search
+        return run_search(self, start, goal_row, eps, delta, g_max, max_rounds, max_expand, capacity, max_frontier,
+                          lists_stride, sight, tol_pos, tol_vel, tol_acc, tol_yaw, w, v_max)
+
     def synchronize(self):
         _abi.check(self._ctx, _abi.lib().mplx_synchronize(self._ctx))
 
