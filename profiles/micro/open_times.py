@@ -130,7 +130,11 @@ def one_problem(m, p, res):
             r.free()
         if cost is not None and math.isfinite(cost):
             t0 = time.perf_counter()
-            tab, rounds = env.cost_to_come(start, g_max=cost, **kw)
+            try:
+                tab, rounds = env.cost_to_come(start, g_max=cost, **kw)
+            except RuntimeError as e:  # the table or the frontier ran full: recorded, the other legs go on
+                out["sweep"]["error"] = str(e)
+                continue
             ms = (time.perf_counter() - t0) * 1e3
             out["sweep"].update({"g_max": cost, "rounds": rounds, "nodes": tab.stats()[0]})
             tab.free()

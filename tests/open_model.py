@@ -1,6 +1,7 @@
 """A plain sequential restatement of include/mplx_open.h over tests/table_model.py::TableModel: keys and flags per node,
 push, select, and the search loop of EnvMap.search built on them.  Test infrastructure: Python floats (IEEE doubles, no
-contraction) and dicts, nothing shared with the engine.
+contraction) and dicts, nothing shared with the engine.  OpenArrays restates push and select once more on whole numpy arrays, for
+tables the loops cannot follow (tests/large_case.py); tests/test_open.py pins it to OpenModel bit for bit.
 
 Frontiers are the dicts TableModel emits ("count", "id", "g", "state" [4D+2][count]).  `blocked(positions [n][D])` is the
 ray trace of env_map::is_goal (True: an occupied cell on the ray to the goal); ray_blocked() builds it from
@@ -114,6 +115,86 @@ class OpenModel:
         fr = {"count": len(chosen), "id": np.array(chosen, dtype=np.int32),
               "g": np.array([self.table.g[i] for i in chosen], dtype=np.float64), "state": st}
         res = {"status": status, "goal_id": goal_id, "count": len(chosen), "n_open": len(O) - len(chosen), "f_min": f_min,
+               "goal_f": goal_f, "goal_g": goal_g}
+        return res, fr
+
+
+class OpenArrays:
+    """OpenModel's push and select on whole arrays (no ray trace): the same IEEE operations in the same order, the same
+    return values.  `table`: anything with n_nodes, n_fields, hash, g [n_nodes] and state [n_fields][n_nodes] as arrays
+    (tests/table_model.py::TableArrays); it may grow between calls."""
+
+    def __init__(self, table, dim, goal_row, goal_hash, w, v_max, tol_pos=0.5, tol_vel=-1.0, tol_acc=-1.0, tol_yaw=-1.0):
+        self.table, self.dim = table, dim
+        self.goal = np.asarray(goal_row, dtype=np.float64)
+        self.goal_hash = np.uint64(goal_hash)
+        self.w, self.v_max = float(w), float(v_max)
+        self.tol = (float(tol_pos), float(tol_vel), float(tol_acc), float(tol_yaw))
+        self.f, self.flags = np.zeros(0), np.zeros(0, np.uint8)
+
+    def _grow(self):
+        more = self.table.n_nodes - self.f.size
+        if more > 0:
+            self.f, self.flags = np.concatenate([self.f, np.zeros(more)]), np.concatenate([self.flags, np.zeros(more, np.uint8)])
+
+    def heur_and_tol(self, ids, s):
+        """OpenModel.heur_and_tol for the state columns s of nodes ids."""
+        D, g = self.dim, self.goal
+        # (max() over Python floats starts at 0.0 and never takes a NaN: fmax)
+        linf = lambda a, b: np.fmax.reduce(np.abs(s[a:a + D] - g[b:b + D, None]), axis=0, initial=0.0)
+        m = linf(0, 0)
+        h = self.w * m / self.v_max if self.v_max > 0 else self.w * m
+        h = np.where(np.asarray(self.table.hash)[ids] == self.goal_hash, 0.0, h)
+        tol_pos, tol_vel, tol_acc, tol_yaw = self.tol
+        ok = m <= tol_pos
+        if tol_vel >= 0:
+            ok &= linf(D, D) <= tol_vel
+        if tol_acc >= 0:
+            ok &= linf(2 * D, 2 * D) <= tol_acc
+        if tol_yaw >= 0:
+            ok &= np.abs(s[4 * D] - g[4 * D]) <= tol_yaw
+        return h, ok
+
+    def push(self, fr, n_max, eps, capacity=None):
+        self._grow()
+        n = min(int(fr["count"]), int(n_max))
+        if capacity is not None:
+            n = min(n, int(capacity))
+        ids = np.asarray(fr["id"][:n]).astype(np.int64)
+        inside = (ids >= 0) & (ids < self.table.n_nodes)
+        ids, g, s = ids[inside], np.asarray(fr["g"][:n], dtype=np.float64)[inside], np.asarray(fr["state"])[:, :n][:, inside]
+        h, ok = self.heur_and_tol(ids, s)
+        with np.errstate(invalid="ignore"):
+            f = g if eps == 0 else g + float(eps) * h
+            keep = f >= 0.0
+        ids, f, ok = ids[keep], f[keep], ok[keep]
+        self.f[ids] = f + 0.0
+        self.flags[ids] = (SEEN | IS_OPEN) | np.where(ok, IS_GOAL, 0).astype(np.uint8)
+
+    def arrays(self):
+        self._grow()
+        return self.f, self.flags
+
+    def select(self, delta, capacity):
+        self._grow()
+        t = self.table
+        O, G = np.nonzero(self.flags & IS_OPEN)[0], np.nonzero(self.flags & IS_GOAL)[0]
+        f_min = float(self.f[O].min()) if O.size else math.inf
+        goal_f = float(self.f[G].min()) if G.size else math.inf
+        goal_id = int(G[self.f[G] == goal_f][0]) if G.size else -1
+        goal_g = float(t.g[goal_id]) if goal_id >= 0 else math.inf
+        chosen = np.zeros(0, np.int64)
+        if G.size and goal_f <= f_min:
+            status = FOUND
+        elif not O.size:
+            status = EMPTY
+        else:
+            status = SELECTED
+            T = f_min + float(delta)
+            chosen = O[self.f[O] <= T][:int(capacity)]
+            self.flags[chosen] &= np.uint8(0xff & ~IS_OPEN)
+        fr = {"count": chosen.size, "id": chosen.astype(np.int32), "g": np.asarray(t.g)[chosen], "state": np.asarray(t.state)[:, chosen]}
+        res = {"status": status, "goal_id": goal_id, "count": int(chosen.size), "n_open": int(O.size - chosen.size), "f_min": f_min,
                "goal_f": goal_f, "goal_g": goal_g}
         return res, fr
 

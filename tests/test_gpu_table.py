@@ -8,15 +8,12 @@ import numpy as np
 import pytest
 
 from helpers import engine_env, oracle_env
-from table_model import TableModel, dijkstra, oracle_provider, sweep
+from table_model import EMPTY, F2, TableModel, dijkstra, hand_case, hand_lists, oracle_provider, sweep
 from test_gpu_parity import _small_world
 from test_plan_known_answer import corridor
 from test_table import small_start
 
 pytestmark = pytest.mark.gpu
-
-EMPTY = np.uint64(0xFFFFFFFFFFFFFFFF)  # the hash the table's key field cannot hold
-F2 = 10                                # state rows in 2D
 
 
 def bits(a):
@@ -42,26 +39,6 @@ def upload(env, m, a):
     buf = m.DeviceArray(env, max(a.nbytes, 8))
     buf.upload(a)
     return buf
-
-
-def hand_lists(rng, n, S, pool, poison_base, inf_rate=0.05, nan_rate=0.05):
-    """Random lists over a pool of hashes: costs from a few dyadic values (equal candidates across parents are common),
-    +inf and NaN costs sprinkled in, entries past count poisoned with NaN cost and hashes that exist nowhere else."""
-    count = rng.integers(0, S + 1, size=n).astype(np.int32)
-    count[:3] = [0, S, 1]
-    N = n * S
-    live = (np.arange(S)[None, :] < count[:, None]).ravel()
-    hsh = pool[rng.integers(0, len(pool), size=N)].astype(np.uint64)
-    cost = rng.choice([0.25, 0.5, 1.0, 1.5, 2.0], size=N)
-    r = rng.random(N)
-    cost[r < inf_rate] = np.inf
-    cost[(r >= inf_rate) & (r < inf_rate + nan_rate)] = np.nan
-    cost[~live] = np.nan
-    hsh[~live] = (np.uint64(poison_base) + np.arange(N, dtype=np.uint64))[~live]
-    state = rng.standard_normal((F2, N))
-    state[:, ~live] = np.nan
-    return {"stride": S, "count": count, "action": rng.integers(0, 25, size=N).astype(np.int32), "cost": cost, "hash": hsh,
-            "state": state}
 
 
 def relax_both(m, env, tab, model, host, parent_id, parent_g, g_max, fcap=None, spare=0):
@@ -102,16 +79,6 @@ def assert_table_equal(tab, model, what=""):
 def bare_env(m):
     """A 2D context without map or controls: relax needs neither."""
     return m.EnvMap(2)
-
-
-def hand_case(seed=11, n=300, S=40):
-    rng = np.random.default_rng(seed)
-    pool = np.concatenate([rng.integers(1, 2 ** 63, size=1500, dtype=np.uint64), np.full(12, EMPTY, np.uint64)])
-    host = hand_lists(rng, n, S, pool, poison_base=0xDEAD00000000)
-    parent_id = np.arange(1000, 1000 + n, dtype=np.int32)
-    parent_id[7] = -1
-    parent_g = rng.choice([0.0, 0.5, 1.0, 1.5, 2.5], size=n)
-    return rng, pool, host, parent_id, parent_g
 
 
 def test_one_relax_on_hand_built_lists(engine):

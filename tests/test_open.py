@@ -10,9 +10,10 @@ import subprocess
 import numpy as np
 import pytest
 
+import large_case as LC
 import open_model as OM
 from oracle import oracle as O
-from table_model import TableModel, oracle_provider
+from table_model import TableArrays, TableModel, oracle_provider
 from test_plan_known_answer import corridor
 from test_table import _declared
 
@@ -160,6 +161,71 @@ def test_the_hand_built_scenario_covers_what_it_claims():
     assert statuses[-1] == OM.FOUND and 5 < len(statuses) < 60 and res["n_open"] > 0
     tied = [i for i, fl in opn.flags.items() if fl & OM.IS_GOAL and opn.f[i] == res["goal_f"]]
     assert len(tied) >= 2 and res["goal_id"] == min(tied) and res["goal_g"] == 0.0  # (the table's g: the seeds' 0)
+
+
+def _bits(a):
+    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
+
+
+def test_array_reference_is_the_model_on_the_hand_built_scenario():
+    """The calls of tests/test_gpu_open.py::test_hand_built_push_and_select (push 1, every select of HAND_SELECTS, push 2,
+    selects until FOUND, clear, eps = 0) through OpenModel and OpenArrays: f, the flags, every result field and every
+    frontier row bit for bit."""
+    table, model, states, goal, in_goal, ignored, push1, push2 = hand_model(O)
+    tarr = TableArrays(10)
+    tarr.seed(states, np.array(table.hash, dtype=np.uint64))
+    arr = OM.OpenArrays(tarr, 2, goal, model.goal_hash, OM.HAND_W, OM.HAND_VMAX, tol_pos=OM.HAND_TOL)
+
+    def same_open(what):
+        (f, fl), (wf, wfl) = arr.arrays(), model.arrays()
+        assert fl.dtype == wfl.dtype and np.array_equal(fl, wfl), what + ": flags"
+        assert np.array_equal(_bits(f), _bits(wf)), what + ": f"
+
+    def select_both(delta, cap, what):
+        (got, got_fr), (want, want_fr) = arr.select(delta, cap), model.select(delta, cap)
+        assert list(got) == list(want), what
+        for k in want:
+            same = type(got[k]) is type(want[k]) and _bits([got[k]])[0] == _bits([want[k]])[0]
+            assert same, "%s: %s %r != %r" % (what, k, got[k], want[k])
+        assert got_fr["count"] == want_fr["count"] and got_fr["id"].dtype == want_fr["id"].dtype, what
+        assert np.array_equal(got_fr["id"], want_fr["id"]), what + ": frontier ids / order"
+        assert np.array_equal(_bits(got_fr["g"]), _bits(want_fr["g"])), what + ": frontier g"
+        assert got_fr["state"].shape == want_fr["state"].shape, what
+        assert np.array_equal(_bits(got_fr["state"]), _bits(want_fr["state"])), what + ": frontier state rows"
+        same_open(what)
+        return want
+
+    same_open("new")
+    assert select_both(0.0, 8, "nothing pushed")["status"] == OM.EMPTY
+    host = OM.hand_frontier(states, push1, with_tail=True)
+    arr.push(host, len(push1["id"]), 1.0)
+    model.push(host, len(push1["id"]), 1.0)
+    same_open("push 1")
+    for delta, cap in OM.HAND_SELECTS:
+        assert select_both(delta, cap, "select(%r, %d)" % (delta, cap))["status"] == OM.SELECTED
+    host = OM.hand_frontier(states, push2, with_tail=True)
+    arr.push(host, 10 ** 9, 1.0, capacity=len(push2["id"]))
+    model.push(host, 10 ** 9, 1.0, capacity=len(push2["id"]))
+    same_open("push 2")
+    for k in range(200):
+        res = select_both(2.5, 5000, "select %d after push 2" % k)
+        if res["status"] != OM.SELECTED:
+            break
+    assert res["status"] == OM.FOUND and k > 5
+    arr.f[:], arr.flags[:] = 0.0, 0
+    model.f, model.flags = {}, {}
+    arr.push(host, 100, 0.0)
+    model.push(host, 100, 0.0)
+    same_open("eps = 0")
+    assert select_both(math.inf, 5000, "eps = 0")["count"] > 50
+
+
+def test_the_large_scenario_covers_what_it_claims():
+    """The open-set part of tests/large_case.py on the array references alone (tests/test_table.py has the table part):
+    what keeps the push and select tests of tests/test_gpu_table_large.py from being vacuous (they repeat it)."""
+    gh = O.lattice_hash(2, O.ACC, LC.goal_row())
+    sc, snaps = LC.reference(gh)
+    LC.assert_open_conditions(sc, snaps, gh)
 
 
 def test_every_function_of_the_header_is_declared_in_abi(engine):
