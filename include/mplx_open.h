@@ -46,7 +46,9 @@
  * with a status bit (calls queued before the host saw the bit do nothing), for a push without a goal, and for a push
  * with sight != 0 without a map.  n_max == 0, a frontier of capacity 0 and a table without nodes are successful
  * no-ops of push; a select then returns MPLX_OPEN_EMPTY.  No call writes past the capacity of any array or loops
- * without bound.                                                                                                    */
+ * without bound.
+ *
+ * The open set of a table with several queries has one goal and one result per query: include/mplx_multi.h.         */
 #ifndef MPLX_OPEN_H
 #define MPLX_OPEN_H
 

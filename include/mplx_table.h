@@ -43,7 +43,10 @@
  * Errors: MPLX_ERR_ARG for NULL required pointers, n_nodes < 0, lists without hash / cost / action / state, strides
  * smaller than counts, more than 2^31 - 2 list entries, node_capacity < 1 or >= 2^31, 2^slots_log2 <= node_capacity;
  * MPLX_ERR_STATE for a seed without params / controls and for a table with a status bit.  n_nodes == 0 is a successful
- * no-op with frontier count 0.                                                                                       */
+ * no-op with frontier count 0.
+ *
+ * A table can also hold the nodes of several queries at once, a node then being a (query, hash) pair: that form, what
+ * it changes for relax, and which of the calls below it refuses are in include/mplx_multi.h.                          */
 #ifndef MPLX_TABLE_H
 #define MPLX_TABLE_H
 

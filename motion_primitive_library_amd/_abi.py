@@ -56,6 +56,9 @@ OPEN_SYMBOLS = ["mplx_open_create", "mplx_open_destroy", "mplx_open_clear", "mpl
                 "mplx_open_select_device"]
 OPEN_IS_OPEN, OPEN_IS_GOAL, OPEN_SEEN = 1, 2, 4
 OPEN_SELECTED, OPEN_FOUND, OPEN_EMPTY = 0, 1, 2
+# ... and the ones include/mplx_multi.h declares (Q queries in one table and one open set)
+MULTI_SYMBOLS = ["mplx_table_create_multi", "mplx_table_query_of", "mplx_table_seed_multi", "mplx_table_find_multi_device",
+                 "mplx_table_find_multi", "mplx_open_set_goals", "mplx_open_select_multi_device"]
 
 ROUTE_AUTO, ROUTE_DENSE, ROUTE_TILE, ROUTE_GRID = 0, 1, 2, 3
 
@@ -328,8 +331,15 @@ def lib():
         "mplx_open_view_of": (C.c_int, [vp, C.POINTER(OpenView)]),
         "mplx_open_push_device": (C.c_int, [vp, C.POINTER(TableFrontier), i64, dbl, i32]),
         "mplx_open_select_device": (C.c_int, [vp, dbl, C.POINTER(TableFrontier), vp, C.POINTER(OpenResult)]),
+        "mplx_table_create_multi": (C.c_int, [vp, i64, i32, i32, C.POINTER(vp)]),
+        "mplx_table_query_of": (C.c_int, [vp, C.POINTER(vp), C.POINTER(i32)]),
+        "mplx_table_seed_multi": (C.c_int, [vp, vp, i64, i64, vp, vp, C.POINTER(TableFrontier), C.POINTER(i64)]),
+        "mplx_table_find_multi_device": (C.c_int, [vp, vp, vp, i64, vp]),
+        "mplx_table_find_multi": (C.c_int, [vp, vp, vp, i64, vp]),
+        "mplx_open_set_goals": (C.c_int, [vp, C.POINTER(GoalSpec), i32]),
+        "mplx_open_select_multi_device": (C.c_int, [vp, dbl, C.POINTER(TableFrontier), vp, C.POINTER(OpenResult)]),
     }
-    for name in SYMBOLS + MAP_UTIL_SYMBOLS + ROLLOUT_SYMBOLS + RAY_SYMBOLS + TRAJ_SYMBOLS + TABLE_SYMBOLS + OPEN_SYMBOLS:
+    for name in SYMBOLS + MAP_UTIL_SYMBOLS + ROLLOUT_SYMBOLS + RAY_SYMBOLS + TRAJ_SYMBOLS + TABLE_SYMBOLS + OPEN_SYMBOLS + MULTI_SYMBOLS:
         fn = getattr(L, name)  # AttributeError if the library does not export it
         fn.restype, fn.argtypes = sig[name]
     _lib = L

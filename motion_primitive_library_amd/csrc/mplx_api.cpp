@@ -53,6 +53,21 @@ bool control_ok(int32_t control) {
 
 }  // namespace
 
+int mplx_detail::goal_fuse_of(mplx_ctx *c, const char *who, const mplx_goal_spec *g, mplx::PostFuse *out) {
+  mplx::PostFuse f{};
+  if (!g->goal) return fail(c, MPLX_ERR_ARG, "%s: goal waypoint is NULL", who);
+  if (!control_ok(g->control) || (g->goal_control && !control_ok(g->goal_control)))
+    return fail(c, MPLX_ERR_ARG, "%s: unknown control flag", who);
+  const int F = 4 * c->dim + 2;
+  for (int i = 0; i < F; i++) f.goal[i] = g->goal[i];
+  // env_base.h:47 compares the goal with a state by hash, each side hashed with its own flags (waypoint.h:93-125)
+  f.goal_hash = mplx::host::lattice_hash(c->dim, g->goal_control ? g->goal_control : g->control, g->goal);
+  f.w = g->w; f.v_max = g->v_max;
+  f.tol_pos = g->tol_pos; f.tol_vel = g->tol_vel; f.tol_acc = g->tol_acc; f.tol_yaw = g->tol_yaw;
+  *out = f;
+  return MPLX_OK;
+}
+
 extern "C" {
 
 int mplx_abi_version(void) { return MPLX_ABI_VERSION; }
@@ -285,15 +300,7 @@ int mplx_set_goal(mplx_ctx *c, const mplx_goal_spec *g) {
   mplx::PostFuse f{};
   bool has = false;
   if (g) {
-    if (!g->goal) return fail(c, MPLX_ERR_ARG, "mplx_set_goal: goal waypoint is NULL");
-    if (!control_ok(g->control) || (g->goal_control && !control_ok(g->goal_control)))
-      return fail(c, MPLX_ERR_ARG, "mplx_set_goal: unknown control flag");
-    const int F = 4 * c->dim + 2;
-    for (int i = 0; i < F; i++) f.goal[i] = g->goal[i];
-    // env_base.h:47 compares the goal with a state by hash, each side hashed with its own flags (waypoint.h:93-125)
-    f.goal_hash = mplx::host::lattice_hash(c->dim, g->goal_control ? g->goal_control : g->control, g->goal);
-    f.w = g->w; f.v_max = g->v_max;
-    f.tol_pos = g->tol_pos; f.tol_vel = g->tol_vel; f.tol_acc = g->tol_acc; f.tol_yaw = g->tol_yaw;
+    if (int rc = mplx_detail::goal_fuse_of(c, "mplx_set_goal", g, &f)) return rc;
     has = true;
   }
   if (has != c->has_goal || std::memcmp(&f, &c->goal_fuse, sizeof(f)) != 0) {

@@ -342,5 +342,12 @@ void release_copy_buffers(mplx_ctx *c);
 int table_open_args(mplx_table *t, const char *who, mplx_ctx **c, mplx::OpenArgs *a);
 void table_observe(mplx_table *t);
 
+// mplx_api.cpp: a goal as the kernels take it (mplx_set_goal's checks and hash), for the goals of an open set.
+int goal_fuse_of(mplx_ctx *c, const char *who, const mplx_goal_spec *g, mplx::PostFuse *out);
+// ray_api.cpp: mplx_goal_sight_device with the goal per list entry -- entry i aims at d_goals[d_row_query[i]].goal; tol:
+// the largest tol_pos among the goals.  Read for candidates only (entries within their count whose flags have bit 0).
+int goal_sight_rows(mplx_ctx *c, const mplx_succ_lists *d_lists, int64_t n_nodes, const int32_t *d_row_query,
+                    const mplx::PostFuse *d_goals, double tol, uint8_t *d_flags);
+
 }  // namespace mplx_detail
 #endif

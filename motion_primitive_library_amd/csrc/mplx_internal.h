@@ -447,6 +447,9 @@ struct GoalSightArgs {
   const double *state;     // lists: position rows 0 .. D-1 of [4D+2][sstride]
   int64_t n_nodes, nstride, sstride;
   double goal[3];
+  // the per-row form (the open set of a table with several queries): entry i aims at goals[row_query[i]]; null: `goal`
+  const struct PostFuse *goals;
+  const int32_t *row_query;
   uint8_t *flags;          // [n_nodes * nstride]; bit 0 read, bit 3 ORed in
   int32_t *work;           // [n_nodes * nstride] list indices of the candidates
   uint32_t *work_count;    // their number; zero before the scan
@@ -501,9 +504,13 @@ struct TableCtl {      // device memory
 };
 struct TableMirror { int64_t n_nodes; uint32_t status; };  // pinned host memory: what the last finished call left in TableCtl
 struct TableArgs {
-  // the table: n_slots (a power of two) + 1 slots, the last one for the hash equal to the empty marker
+  // the table: n_queries regions of q_slots (a power of two) slots, n_slots in all, then one slot per query for the hash
+  // equal to the empty marker.  One query: a single region, n_slots + 1 slots
   TableSlot *slots;
-  uint64_t n_slots;
+  uint64_t n_slots, q_slots;
+  int32_t n_queries;
+  int32_t *query;            // per node its query; null for a table of one query (no kernel then looks a query up)
+  const int32_t *src_query;  // seeds of a table with several queries: the query per entry; a relax takes query[parent_id[k]]
   uint64_t *hash;
   unsigned long long *g;     // the doubles' bit patterns: non-negative doubles order like uint64 (atomicMin)
   int32_t *pred, *pred_action;
@@ -540,7 +547,8 @@ constexpr int kTableTile = 4096;
 hipError_t launch_table_relax(const TableArgs &a, hipStream_t s);
 hipError_t launch_table_clear(const TableArgs &a, hipStream_t s);  // slots, control block and mirror
 hipError_t launch_table_hash(int dim, int control, const double *states, int64_t n, int64_t stride, uint64_t *hash, hipStream_t s);
-hipError_t launch_table_find(const TableArgs &a, const uint64_t *hash, int64_t n, int32_t *id, hipStream_t s);
+// query: per hash its query (outside [0, n_queries): -1), or null on a table of one query
+hipError_t launch_table_find(const TableArgs &a, const uint64_t *hash, const int32_t *query, int64_t n, int32_t *id, hipStream_t s);
 // leaf first: ids[0 .. len], actions[0 .. len); *len < 0: -1 more than cap edges, -2 bad id, -3 no seed within n_nodes steps
 hipError_t launch_table_path(const TableArgs &a, int32_t id, int32_t *ids, int32_t *actions, int64_t cap, int64_t *len, hipStream_t s);
 
@@ -552,6 +560,8 @@ struct OpenCtl {                   // device memory; two of them, used by altern
   uint32_t n_open, n_goal;
   int32_t goal_id;                 // smallest id among the goal-region nodes with f == goal_f (INT32_MAX: none yet)
   int32_t emit;                    // the select in flight is SELECTED and got as far as its frontier
+  uint32_t n_sel;                  // select_multi: rows of this query below the frontier's capacity (the emit pass counts)
+  uint32_t pad;
 };
 struct OpenArgs {
   // the table (read only)
@@ -559,6 +569,8 @@ struct OpenArgs {
   const uint64_t *t_hash;
   const unsigned long long *t_g;
   const double *t_state;           // [n_fields][cap]
+  const int32_t *t_query;          // per node its query; null for a table of one query
+  int32_t n_queries;
   int64_t cap;
   int32_t n_fields;
   // the open set
@@ -571,6 +583,8 @@ struct OpenArgs {
   int64_t n_max;
   double eps;
   PostFuse goal;                   // goal of mplx_set_goal (output pointers unused)
+  const PostFuse *goals;           // mplx_open_set_goals: [n_queries] in device memory, or null: `goal`
+  int32_t *row_query;              // [rows] with goals and row_flags: the query of every row, for the per-row ray trace
   uint8_t *row_flags;              // [rows] bit 0 inside the tolerances, bit 3 ray blocked (goal_trace_kernel), bit 7 the row counts
   int32_t *row_count;              // [rows] all 1: the frontier as lists of stride 1
   // select
@@ -585,9 +599,11 @@ struct OpenArgs {
   int64_t f_stride, f_cap;
   int64_t *f_count;
 };
-hipError_t launch_open_clear(const OpenArgs &a, hipStream_t s);
+hipError_t launch_open_clear(const OpenArgs &a, hipStream_t s);  // ctl: 2 * n_queries control blocks
 hipError_t launch_open_push(int dim, int pass, const OpenArgs &a, int64_t rows, hipStream_t s);  // pass 0: all (or up to the row flags); 1: after the ray trace
 hipError_t launch_open_select(const OpenArgs &a, hipStream_t s);
+// select_multi: ctl / ctl_next / mirror / result are arrays of n_queries
+hipError_t launch_open_select_multi(const OpenArgs &a, hipStream_t s);
 
 // Element-wise math probe (see mplx_selftest_math in mplx.h).
 hipError_t launch_math_probe(int op, const double *a, const double *b, double *out, int64_t n,

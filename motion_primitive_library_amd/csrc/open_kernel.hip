@@ -21,6 +21,12 @@
 //            ranks below the capacity only
 // Every index is checked where it is formed: ids against the table's own node count, rows against the frontier's
 // capacity.  A table with a status bit makes every pass return at its first instruction.
+//
+// A table with several queries (include/mplx_multi.h) has one control block, one goal and one result per query.  Its
+// push is the same kernel with the goal looked up by the node's query; its select is the *_multi kernels at the end of
+// this file: the same four passes with every decision taken per query, and a fifth launch of one lane per query that
+// writes the results once the emit pass has counted each query's rows below the frontier's capacity.  The kernels of a
+// table with one query are untouched by that.
 #include "mplx_internal.h"
 #include "mplx_device_common.h"
 
@@ -54,19 +60,21 @@ struct Decision {
   unsigned long long goalf_bits;
   bool any_goal;
 };
-__device__ __forceinline__ Decision decide(const OpenArgs &A) {
+__device__ __forceinline__ Decision decide(const OpenCtl *c, double delta) {
   Decision d;
-  const uint32_t n_open = A.ctl->n_open;
-  d.any_goal = A.ctl->n_goal != 0;
-  d.goalf_bits = A.ctl->goalf_bits;
-  d.f_min = __longlong_as_double((long long)A.ctl->fmin_bits);
+  const uint32_t n_open = c->n_open;
+  d.any_goal = c->n_goal != 0;
+  d.goalf_bits = c->goalf_bits;
+  d.f_min = __longlong_as_double((long long)c->fmin_bits);
   d.goal_f = __longlong_as_double((long long)d.goalf_bits);
   d.status = (d.any_goal && d.goal_f <= d.f_min) ? kFound : n_open == 0 ? kEmpty : kSelected;
-  d.T = d.f_min + A.delta;
+  d.T = d.f_min + delta;
   return d;
 }
+__device__ __forceinline__ Decision decide(const OpenArgs &A) { return decide(A.ctl, A.delta); }
 
-template <int D>
+// MULTI: the goal is goals[query of the node] (mplx_open_set_goals), not the context's
+template <int D, bool MULTI>
 __global__ __launch_bounds__(kBlock) void open_push_kernel(const OpenArgs A, int64_t rows, int pass) {
   if (A.t_ctl->status) return;
   const int64_t r = (int64_t)blockIdx.x * kBlock + threadIdx.x;
@@ -90,7 +98,13 @@ __global__ __launch_bounds__(kBlock) void open_push_kernel(const OpenArgs A, int
 #pragma unroll
   for (int i = 0; i < 3 * D; i++) s[i] = A.f_state[(int64_t)i * A.f_stride + r];
   s[4 * D] = A.f_state[(int64_t)(4 * D) * A.f_stride + r];
-  MPLX_POST_GOAL(PG, A.goal, D)
+  int32_t q = 0;
+  if (MULTI && A.t_query) {
+    q = A.t_query[id];
+    if (q < 0 || q >= A.n_queries) return;  // (never: the column holds only queries)
+  }
+  const PostFuse &GF = MULTI ? A.goals[q] : A.goal;
+  MPLX_POST_GOAL(PG, GF, D)
   double h;
   unsigned int fl;
   dev::post_eval<D>(PG, A.t_hash[id], s, s + D, s + 2 * D, s[4 * D], &h, &fl);
@@ -103,8 +117,10 @@ __global__ __launch_bounds__(kBlock) void open_push_kernel(const OpenArgs A, int
   if (!(f >= 0.0)) return;
   f = f + 0.0;  // -0.0 -> +0.0: the bit patterns of the keys order like the keys
   A.f[id] = (unsigned long long)__double_as_longlong(f);
-  if (A.row_flags) A.row_flags[r] = (uint8_t)(kRowCounts | (fl & 1u));
-  else A.flags[id] = (uint8_t)(kSeen | kIsOpen | ((fl & 1u) ? kIsGoal : 0));
+  if (A.row_flags) {
+    A.row_flags[r] = (uint8_t)(kRowCounts | (fl & 1u));
+    if (MULTI) A.row_query[r] = q;
+  } else A.flags[id] = (uint8_t)(kSeen | kIsOpen | ((fl & 1u) ? kIsGoal : 0));
 }
 
 __global__ __launch_bounds__(kBlock) void open_reduce_kernel(const OpenArgs A) {
@@ -221,6 +237,7 @@ __global__ __launch_bounds__(1024) void open_scan_kernel(const OpenArgs A) {
   A.ctl_next->n_goal = 0;
   A.ctl_next->goal_id = 0x7fffffff;
   A.ctl_next->emit = 0;
+  A.ctl_next->n_sel = 0;
 }
 
 // Rank of every marked node of a tile in id order = its frontier row.
@@ -252,32 +269,231 @@ __global__ __launch_bounds__(kBlock) void open_emit_kernel(const OpenArgs A) {
   }
 }
 
-__global__ void open_clear_kernel(const OpenArgs A) {
-  OpenCtl *both[2] = {A.ctl, A.ctl_next};
-  for (int i = 0; i < 2; i++) {
-    both[i]->fmin_bits = kInfBits;
-    both[i]->goalf_bits = kInfBits;
-    both[i]->n_open = 0;
-    both[i]->n_goal = 0;
-    both[i]->goal_id = 0x7fffffff;
-    both[i]->emit = 0;
+__device__ __forceinline__ void reset_ctl(OpenCtl *c) {
+  c->fmin_bits = kInfBits;
+  c->goalf_bits = kInfBits;
+  c->n_open = 0;
+  c->n_goal = 0;
+  c->goal_id = 0x7fffffff;
+  c->emit = 0;
+  c->n_sel = 0;
+  c->pad = 0;
+}
+
+// both halves: n_queries control blocks each
+__global__ __launch_bounds__(kBlock) void open_clear_kernel(const OpenArgs A) {
+  const int64_t q = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (q >= A.n_queries) return;
+  reset_ctl(A.ctl + q);
+  reset_ctl(A.ctl_next + q);
+}
+
+// ---- select on a table with several queries ------------------------------------------------------------------------
+
+__device__ __forceinline__ int32_t query_of(const OpenArgs &A, int64_t id) {
+  if (!A.t_query) return 0;
+  const int32_t q = A.t_query[id];
+  return (q >= 0 && q < A.n_queries) ? q : 0;  // (the column holds only queries: no index leaves the control blocks)
+}
+
+__device__ __forceinline__ Decision decide_query(const OpenArgs &A, int32_t q) { return decide(A.ctl + q, A.delta); }
+
+// `on` lanes share query q (wave-uniform): the wave's minimum and count go to that query with one atomic each.  Every
+// lane of the wave calls this.
+__device__ __forceinline__ void reduce_one(const OpenArgs &A, int32_t q, bool o, bool g, unsigned long long f) {
+  const unsigned long long bo = __ballot(o), bg = __ballot(g);
+  unsigned long long fo = o ? f : kInfBits, fg = g ? f : kInfBits;
+  if (bo) fo = wave_min(fo);
+  if (bg) fg = wave_min(fg);
+  if ((threadIdx.x & 63) != 0) return;
+  OpenCtl *c = A.ctl + q;
+  if (bo) {
+    atomicMin(&c->fmin_bits, fo);
+    atomicAdd(&c->n_open, (uint32_t)__popcll(bo));
   }
+  if (bg) {
+    atomicMin(&c->goalf_bits, fg);
+    atomicAdd(&c->n_goal, (uint32_t)__popcll(bg));
+  }
+}
+
+__global__ __launch_bounds__(kBlock) void open_reduce_multi_kernel(const OpenArgs A) {
+  if (A.t_ctl->status) return;  // (uniform)
+  const int64_t id = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  unsigned long long f = kInfBits;
+  bool o = false, g = false;
+  int32_t q = 0;
+  if (id < node_count(A)) {
+    const uint8_t fl = A.flags[id];
+    o = (fl & kIsOpen) != 0;
+    g = (fl & kIsGoal) != 0;
+    if (o || g) {
+      f = A.f[id];
+      q = query_of(A, id);
+    }
+  }
+  unsigned long long left = __ballot(o || g);  // the lanes with something to say
+  if (!left) return;
+  const int32_t q0 = __shfl(q, __builtin_ctzll(left));
+  if (__ballot((o || g) && q != q0) == 0ull) {  // one query in the wave: the pass of a table with one query
+    reduce_one(A, q0, o, g, f);
+    return;
+  }
+  while (left) {  // one round per distinct query present, at most 64
+    const int32_t qq = __shfl(q, __builtin_ctzll(left));
+    const bool mine = (o || g) && q == qq;
+    reduce_one(A, qq, mine && o, mine && g, f);
+    left &= ~__ballot(mine);
+  }
+}
+
+__global__ __launch_bounds__(kBlock) void open_mark_multi_kernel(const OpenArgs A) {
+  if (A.t_ctl->status) return;  // (uniform: nothing below is skipped by part of a workgroup)
+  __shared__ uint32_t wsum[kBlock / 64];
+  const int64_t n = node_count(A), base = (int64_t)blockIdx.x * kTableTile;
+  uint32_t cnt = 0;
+  for (int i = 0; i < kItems; i++) {
+    const int64_t id = base + (int64_t)i * kBlock + threadIdx.x;
+    bool m = false;
+    if (id < n) {
+      const uint8_t fl = A.flags[id];
+      if (fl & (kIsOpen | kIsGoal)) {
+        const int32_t q = query_of(A, id);
+        const Decision d = decide_query(A, q);  // the node's own query decides
+        const unsigned long long v = A.f[id];
+        if ((fl & kIsGoal) && v == d.goalf_bits) atomicMin(&A.ctl[q].goal_id, (int32_t)id);
+        m = d.status == kSelected && (fl & kIsOpen) && __longlong_as_double((long long)v) <= d.T;
+      }
+      A.mark[id] = m ? 1 : 0;
+    }
+    cnt += (uint32_t)__popcll(__ballot(m));  // the wave's count, in every lane
+  }
+  if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = cnt;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    uint32_t t = 0;
+    for (int w = 0; w < kBlock / 64; w++) t += wsum[w];
+    A.tot[blockIdx.x] = t;
+  }
+}
+
+// The scan of the tile counts; the frontier count (the marks are those of the SELECTED queries only) clamped to the
+// capacity; the control blocks of the NEXT select.  The results wait for the emit pass's counts (open_finish_kernel).
+__global__ __launch_bounds__(1024) void open_scan_multi_kernel(const OpenArgs A) {
+  __shared__ uint32_t part[1024];
+  if (A.t_ctl->status) return;  // (uniform)
+  const int t = threadIdx.x;
+  const int64_t per = (A.n_tiles + 1023) / 1024;
+  const int64_t a = (int64_t)t * per < A.n_tiles ? (int64_t)t * per : A.n_tiles, b = a + per < A.n_tiles ? a + per : A.n_tiles;
+  uint32_t s = 0;
+  for (int64_t k = a; k < b; k++) s += A.tot[k];
+  part[t] = s;
+  __syncthreads();
+  for (int d = 1; d < 1024; d <<= 1) {
+    const uint32_t v = t >= d ? part[t - d] : 0;
+    __syncthreads();
+    part[t] += v;
+    __syncthreads();
+  }
+  uint32_t run = part[t] - s;
+  for (int64_t k = a; k < b; k++) {
+    const uint32_t c = A.tot[k];
+    A.tot[k] = run;
+    run += c;
+  }
+  for (int32_t q = t; q < A.n_queries; q += 1024) reset_ctl(A.ctl_next + q);
+  if (t != 0) return;
+  int64_t cnt = part[1023];
+  if (cnt > A.f_cap) cnt = A.f_cap;  // the rest stay open
+  A.ctl[0].emit = cnt > 0 ? 1 : 0;  // (query 0's block carries the flag of the whole select)
+  *A.f_count = cnt;
+}
+
+// open_emit_kernel, and per (wave, query) one atomicAdd of the rows emitted: integer sums, the same whatever the order.
+__global__ __launch_bounds__(kBlock) void open_emit_multi_kernel(const OpenArgs A) {
+  if (A.t_ctl->status || A.ctl[0].emit == 0) return;  // (uniform)
+  __shared__ uint32_t wsum[kBlock / 64];
+  const int64_t n = node_count(A), base = (int64_t)blockIdx.x * kTableTile;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  int64_t run = A.tot[blockIdx.x];
+  for (int i = 0; i < kItems; i++) {
+    const int64_t id = base + (int64_t)i * kBlock + threadIdx.x;
+    const bool m = id < n && A.mark[id] != 0;
+    const unsigned long long bal = __ballot(m);
+    if (lane == 0) wsum[wave] = (uint32_t)__popcll(bal);
+    __syncthreads();
+    uint32_t before = 0, all = 0;
+    for (int w = 0; w < kBlock / 64; w++) {
+      if (w < wave) before += wsum[w];
+      all += wsum[w];
+    }
+    __syncthreads();
+    const int64_t r = run + before + (int64_t)__popcll(bal & ((1ull << lane) - 1ull));
+    run += all;
+    const bool take = m && r < A.f_cap;
+    int32_t q = 0;
+    if (take) {
+      q = query_of(A, id);
+      A.flags[id] = (uint8_t)(A.flags[id] & ~kIsOpen);
+      A.f_id[r] = (int32_t)id;
+      A.f_g[r] = __longlong_as_double((long long)A.t_g[id]);
+      for (int f = 0; f < A.n_fields; f++) A.f_state[(int64_t)f * A.f_stride + r] = A.t_state[(int64_t)f * A.cap + id];
+    }
+    unsigned long long left = __ballot(take);
+    while (left) {  // one round per distinct query among the wave's rows (one, when the wave holds one query)
+      const int32_t qq = __shfl(q, __builtin_ctzll(left));
+      const unsigned long long mine = __ballot(take && q == qq);
+      if (lane == 0) atomicAdd(&A.ctl[qq].n_sel, (uint32_t)__popcll(mine));
+      left &= ~mine;
+    }
+  }
+}
+
+// One lane per query: the result, to the caller's device memory and to the pinned mirror.
+__global__ __launch_bounds__(kBlock) void open_finish_kernel(const OpenArgs A) {
+  if (A.t_ctl->status) return;
+  const int64_t q = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (q >= A.n_queries) return;
+  const Decision d = decide_query(A, (int32_t)q);
+  const OpenCtl *c = A.ctl + q;
+  OpenResult R;
+  R.status = d.status;
+  R.goal_id = d.any_goal ? c->goal_id : -1;
+  R.count = d.status == kSelected ? (int64_t)c->n_sel : 0;
+  R.n_open = (int64_t)c->n_open - R.count;
+  R.f_min = d.f_min;
+  R.goal_f = d.goal_f;
+  R.goal_g = (R.goal_id >= 0 && R.goal_id < node_count(A)) ? __longlong_as_double((long long)A.t_g[R.goal_id]) : __longlong_as_double((long long)kInfBits);
+  if (A.result) A.result[q] = R;
+  OpenResult *m = A.mirror + q;
+  __hip_atomic_store(&m->goal_id, R.goal_id, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  __hip_atomic_store(&m->count, R.count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  __hip_atomic_store(&m->n_open, R.n_open, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  __hip_atomic_store(&m->f_min, R.f_min, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  __hip_atomic_store(&m->goal_f, R.goal_f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  __hip_atomic_store(&m->goal_g, R.goal_g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  __hip_atomic_store(&m->status, R.status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
 }  // namespace
 
 hipError_t launch_open_clear(const OpenArgs &a, hipStream_t s) {
   if (hipError_t e = hipMemsetAsync(a.flags, 0, (size_t)a.cap, s)) return e;
-  hipLaunchKernelGGL(open_clear_kernel, dim3(1), dim3(1), 0, s, a);
+  hipLaunchKernelGGL(open_clear_kernel, dim3((unsigned)((a.n_queries + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, a);
   return hipGetLastError();
 }
 
 hipError_t launch_open_push(int dim, int pass, const OpenArgs &a, int64_t rows, hipStream_t s) {
   if (rows <= 0) return hipSuccess;
   const dim3 grid((unsigned)((rows + kBlock - 1) / kBlock)), block(kBlock);
-  if (dim == 2) hipLaunchKernelGGL(open_push_kernel<2>, grid, block, 0, s, a, rows, pass);
-  else if (dim == 3) hipLaunchKernelGGL(open_push_kernel<3>, grid, block, 0, s, a, rows, pass);
-  else return hipErrorInvalidValue;
+  if (dim != 2 && dim != 3) return hipErrorInvalidValue;
+  if (a.goals) {
+    if (dim == 2) hipLaunchKernelGGL((open_push_kernel<2, true>), grid, block, 0, s, a, rows, pass);
+    else hipLaunchKernelGGL((open_push_kernel<3, true>), grid, block, 0, s, a, rows, pass);
+  } else {
+    if (dim == 2) hipLaunchKernelGGL((open_push_kernel<2, false>), grid, block, 0, s, a, rows, pass);
+    else hipLaunchKernelGGL((open_push_kernel<3, false>), grid, block, 0, s, a, rows, pass);
+  }
   return hipGetLastError();
 }
 
@@ -288,6 +504,17 @@ hipError_t launch_open_select(const OpenArgs &a, hipStream_t s) {
   hipLaunchKernelGGL(open_mark_kernel, per_tile, block, 0, s, a);
   hipLaunchKernelGGL(open_scan_kernel, dim3(1), dim3(1024), 0, s, a);
   hipLaunchKernelGGL(open_emit_kernel, per_tile, block, 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_open_select_multi(const OpenArgs &a, hipStream_t s) {
+  const int64_t n = a.n_bound > 0 ? a.n_bound : 1;  // (an empty table still gets its results)
+  const dim3 per_node((unsigned)((n + kBlock - 1) / kBlock)), per_tile((unsigned)a.n_tiles), block(kBlock);
+  hipLaunchKernelGGL(open_reduce_multi_kernel, per_node, block, 0, s, a);
+  hipLaunchKernelGGL(open_mark_multi_kernel, per_tile, block, 0, s, a);
+  hipLaunchKernelGGL(open_scan_multi_kernel, dim3(1), dim3(1024), 0, s, a);
+  hipLaunchKernelGGL(open_emit_multi_kernel, per_tile, block, 0, s, a);
+  hipLaunchKernelGGL(open_finish_kernel, dim3((unsigned)((a.n_queries + kBlock - 1) / kBlock)), block, 0, s, a);
   return hipGetLastError();
 }
 

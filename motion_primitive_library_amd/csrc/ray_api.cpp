@@ -112,13 +112,13 @@ int mplx_ray_trace(mplx_ctx *c, const double *h_p1, const double *h_p2, int64_t 
   return MPLX_OK;
 }
 
-int mplx_goal_sight_device(mplx_ctx *c, const mplx_succ_lists *d_lists, int64_t n_nodes, const mplx_goal_spec *goal,
-                           uint8_t *d_flags) {
-  if (!c) return MPLX_ERR_ARG;
-  if (!d_lists || n_nodes < 0 || !d_flags || !d_lists->count || !d_lists->state || (goal && !goal->goal))
+// goal_or_null / the context's goal, or (d_goals != null) the goal per list entry
+static int goal_sight(mplx_ctx *c, const mplx_succ_lists *d_lists, int64_t n_nodes, const mplx_goal_spec *goal, const int32_t *d_row_query,
+                      const mplx::PostFuse *d_goals, double goals_tol, uint8_t *d_flags) {
+  if (!d_lists || n_nodes < 0 || !d_flags || !d_lists->count || !d_lists->state || (goal && !goal->goal) || (d_goals && !d_row_query))
     return fail(c, MPLX_ERR_ARG, "mplx_goal_sight_device: the lists need count and state, and a flags row");
   if (!c->has_map) return fail(c, MPLX_ERR_STATE, "mplx_goal_sight_device: set the map first");
-  if (!goal && !c->has_goal) return fail(c, MPLX_ERR_STATE, "mplx_goal_sight_device: no goal (mplx_set_goal or goal_or_null)");
+  if (!d_goals && !goal && !c->has_goal) return fail(c, MPLX_ERR_STATE, "mplx_goal_sight_device: no goal (mplx_set_goal or goal_or_null)");
   if (c->n_cells > 0x7fffffffLL)
     return fail(c, MPLX_ERR_STATE, "mplx_goal_sight_device: the map has more cells than getIndex (int32) can number");
   if (!d_lists->node_stride && !c->has_U) return fail(c, MPLX_ERR_STATE, "mplx_goal_sight_device: controls not set");
@@ -138,15 +138,32 @@ int mplx_goal_sight_device(mplx_ctx *c, const mplx_succ_lists *d_lists, int64_t 
   a.n_nodes = n_nodes;
   a.nstride = S;
   a.sstride = d_lists->state_stride;
-  const double *g = goal ? goal->goal : c->goal_fuse.goal;
-  for (int i = 0; i < c->dim; i++) a.goal[i] = g[i];
+  if (d_goals) {
+    a.goals = d_goals;
+    a.row_query = d_row_query;
+  } else {
+    const double *g = goal ? goal->goal : c->goal_fuse.goal;
+    for (int i = 0; i < c->dim; i++) a.goal[i] = g[i];
+  }
   a.flags = d_flags;
   a.work_count = (uint32_t *)c->ray_work.p;
   a.work = (int32_t *)((char *)c->ray_work.p + 256);
   // a candidate lies within tol_pos of the goal on every axis: at most tol_pos / res / 0.8 steps
-  const double tol = goal ? goal->tol_pos : c->goal_fuse.tol_pos;
+  const double tol = d_goals ? goals_tol : goal ? goal->tol_pos : c->goal_fuse.tol_pos;
   HIP_TRY(c, mplx::launch_goal_sight(c->dim, auto_lanes(tol / c->res / 0.8), c->n_cus, a, c->stream));
   return MPLX_OK;
 }
 
+int mplx_goal_sight_device(mplx_ctx *c, const mplx_succ_lists *d_lists, int64_t n_nodes, const mplx_goal_spec *goal,
+                           uint8_t *d_flags) {
+  if (!c) return MPLX_ERR_ARG;
+  return goal_sight(c, d_lists, n_nodes, goal, nullptr, nullptr, 0.0, d_flags);
+}
+
 }  // extern "C"
+
+int mplx_detail::goal_sight_rows(mplx_ctx *c, const mplx_succ_lists *d_lists, int64_t n_nodes, const int32_t *d_row_query,
+                                 const mplx::PostFuse *d_goals, double tol, uint8_t *d_flags) {
+  if (!d_goals) return fail(c, MPLX_ERR_ARG, "goal_sight_rows: NULL goals");
+  return goal_sight(c, d_lists, n_nodes, nullptr, d_row_query, d_goals, tol, d_flags);
+}

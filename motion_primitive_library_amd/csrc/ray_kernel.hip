@@ -176,7 +176,8 @@ __global__ __launch_bounds__(kBlock) void goal_scan_kernel(const GoalSightArgs A
   }
 }
 
-template <int D, int G>
+// ROWS: the goal per list entry, goals[row_query[i]] (the open set of a table with several queries)
+template <int D, int G, bool ROWS>
 __global__ __launch_bounds__(kBlock) void goal_trace_kernel(const GoalSightArgs A) {
   constexpr int kRays = kBlock / G;
   const int64_t m = (int64_t)*A.work_count, stride = (int64_t)gridDim.x * kRays;
@@ -185,10 +186,12 @@ __global__ __launch_bounds__(kBlock) void goal_trace_kernel(const GoalSightArgs 
     const bool have = w < m;
     const int64_t i = have ? (int64_t)A.work[w] : 0;
     double p1[D], p2[D];
+    const PostFuse *goal = nullptr;
+    if (ROWS && have) goal = A.goals + A.row_query[i];  // (a candidate: its row counted, its query is one)
 #pragma unroll
     for (int d = 0; d < D; d++) {
       p1[d] = have ? A.state[(int64_t)d * A.sstride + i] : 0.0;
-      p2[d] = A.goal[d];
+      p2[d] = ROWS ? (have ? goal->goal[d] : 0.0) : A.goal[d];
     }
     const RayResult R = trace_group<D, G, true>(A.ray, have, p1, p2, nullptr, 0);
     if (have && (threadIdx.x & (G - 1)) == 0 && R.first_hit >= 0) A.flags[i] = (uint8_t)(A.flags[i] | 8);
@@ -214,7 +217,8 @@ hipError_t launch_goal(int n_cus, const GoalSightArgs &a, hipStream_t s) {
   // at most one group per slot is ever needed; the loop bound is the device's count
   int64_t tblocks = (total + kBlock / G - 1) / (kBlock / G);
   if (tblocks > cap) tblocks = cap;
-  hipLaunchKernelGGL((goal_trace_kernel<D, G>), dim3((unsigned)tblocks), dim3(kBlock), 0, s, a);
+  if (a.goals) hipLaunchKernelGGL((goal_trace_kernel<D, G, true>), dim3((unsigned)tblocks), dim3(kBlock), 0, s, a);
+  else hipLaunchKernelGGL((goal_trace_kernel<D, G, false>), dim3((unsigned)tblocks), dim3(kBlock), 0, s, a);
   return hipGetLastError();
 }
 

@@ -2,7 +2,7 @@
 // table's arrays, its control block and its scratch are the table's own; launches go to the context's stream and the
 // host-pointer calls stage through the context's arena.
 #include "mplx_ctx.h"
-#include "../../include/mplx_table.h"
+#include "../../include/mplx_multi.h"
 
 #include <algorithm>
 #include <cmath>
@@ -13,9 +13,12 @@ using namespace mplx_detail;
 struct mplx_table {
   mplx_ctx *c = nullptr;
   int64_t cap = 0;
-  uint64_t n_slots = 0;
+  uint64_t n_slots = 0;              // all regions together (the dedicated slots of the empty marker come behind them)
+  uint64_t q_slots = 0;              // one query's region
+  int32_t Q = 1;
   int F = 0;
   DevBuf slots, hash, g, pred, pact, state, pick, ctl;
+  DevBuf query;                      // per node its query: tables with Q > 1 only
   DevBuf scratch;                    // per-call passes (ent, mark, tile counts, seed hashes); grows on demand
   mplx::TableMirror *mirror = nullptr;  // pinned
   uint32_t epoch = 0;                // calls since the last clear
@@ -31,6 +34,9 @@ mplx::TableArgs table_args(const mplx_table *t) {
   mplx::TableArgs a{};
   a.slots = (mplx::TableSlot *)t->slots.p;
   a.n_slots = t->n_slots;
+  a.q_slots = t->q_slots;
+  a.n_queries = t->Q;
+  a.query = (int32_t *)t->query.p;
   a.hash = (uint64_t *)t->hash.p;
   a.g = (unsigned long long *)t->g.p;
   a.pred = (int32_t *)t->pred.p;
@@ -45,7 +51,7 @@ mplx::TableArgs table_args(const mplx_table *t) {
 }
 
 void release_table(mplx_table *t) {
-  for (DevBuf *b : {&t->slots, &t->hash, &t->g, &t->pred, &t->pact, &t->state, &t->pick, &t->ctl, &t->scratch}) release(*b);
+  for (DevBuf *b : {&t->slots, &t->hash, &t->g, &t->pred, &t->pact, &t->state, &t->pick, &t->ctl, &t->query, &t->scratch}) release(*b);
   if (t->mirror) (void)hipHostFree(t->mirror);
   delete t;
 }
@@ -110,6 +116,8 @@ int table_open_args(mplx_table *t, const char *who, mplx_ctx **c, mplx::OpenArgs
   a->t_hash = (const uint64_t *)t->hash.p;
   a->t_g = (const unsigned long long *)t->g.p;
   a->t_state = (const double *)t->state.p;
+  a->t_query = (const int32_t *)t->query.p;
+  a->n_queries = t->Q;
   a->cap = t->cap;
   a->n_fields = t->F;
   a->n_bound = t->bound;
@@ -119,6 +127,53 @@ int table_open_args(mplx_table *t, const char *who, mplx_ctx **c, mplx::OpenArgs
 void table_observe(mplx_table *t) { observe(t); }
 
 }  // namespace mplx_detail
+
+namespace {
+
+// Q regions of q_slots slots each; the arguments are checked
+int create_table(mplx_ctx *c, const char *who, int64_t node_capacity, int32_t Q, uint64_t q_slots, mplx_table **out) {
+  *out = nullptr;
+  MPLX_GUARD_BEGIN
+  if (int rc = bind_device(c)) return rc;
+  mplx_table *t = new mplx_table;
+  t->c = c;
+  t->cap = node_capacity;
+  t->Q = Q;
+  t->q_slots = q_slots;
+  t->n_slots = q_slots * (uint64_t)Q;
+  t->F = 4 * c->dim + 2;
+  const uint64_t n_slots = t->n_slots;
+  const size_t cap = (size_t)node_capacity;
+  int rc = MPLX_OK;
+  if (!rc) rc = ensure(c, t->slots, (size_t)(n_slots + (uint64_t)Q) * sizeof(mplx::TableSlot));
+  if (!rc && Q > 1) rc = ensure(c, t->query, cap * 4);
+  if (!rc) rc = ensure(c, t->hash, cap * 8);
+  if (!rc) rc = ensure(c, t->g, cap * 8);
+  if (!rc) rc = ensure(c, t->pred, cap * 4);
+  if (!rc) rc = ensure(c, t->pact, cap * 4);
+  if (!rc) rc = ensure(c, t->state, cap * 8 * (size_t)t->F);
+  if (!rc) rc = ensure(c, t->pick, cap * 8);
+  if (!rc) rc = ensure(c, t->ctl, sizeof(mplx::TableCtl));
+  if (!rc && hipHostMalloc((void **)&t->mirror, 64, hipHostMallocCoherent) != hipSuccess)
+    rc = fail(c, MPLX_ERR_HIP, "%s: hipHostMalloc failed", who);
+  if (!rc && mplx::launch_table_clear(table_args(t), c->stream) != hipSuccess) rc = fail(c, MPLX_ERR_HIP, "%s: the clearing launch failed", who);
+  if (rc) {
+    (void)hipGetLastError();
+    release_table(t);
+    return rc;
+  }
+  *out = t;
+  return MPLX_OK;
+  MPLX_GUARD_END(c)
+}
+
+// what the plain calls answer on a table with several queries
+int single_only(mplx_table *t, const char *who) {
+  if (t->Q > 1) return fail(t->c, MPLX_ERR_STATE, "%s: the table has %d queries: use the _multi form (mplx_multi.h)", who, (int)t->Q);
+  return MPLX_OK;
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -135,35 +190,36 @@ int mplx_table_create(mplx_ctx *c, int64_t node_capacity, int32_t slots_log2, mp
   }
   if (n_slots <= (uint64_t)node_capacity)
     return fail(c, MPLX_ERR_ARG, "mplx_table_create: 2^slots_log2 = %llu slots cannot hold %lld nodes", (unsigned long long)n_slots, (long long)node_capacity);
-  *out = nullptr;
-  MPLX_GUARD_BEGIN
-  if (int rc = bind_device(c)) return rc;
-  mplx_table *t = new mplx_table;
-  t->c = c;
-  t->cap = node_capacity;
-  t->n_slots = n_slots;
-  t->F = 4 * c->dim + 2;
-  const size_t cap = (size_t)node_capacity;
-  int rc = MPLX_OK;
-  if (!rc) rc = ensure(c, t->slots, (size_t)(n_slots + 1) * sizeof(mplx::TableSlot));
-  if (!rc) rc = ensure(c, t->hash, cap * 8);
-  if (!rc) rc = ensure(c, t->g, cap * 8);
-  if (!rc) rc = ensure(c, t->pred, cap * 4);
-  if (!rc) rc = ensure(c, t->pact, cap * 4);
-  if (!rc) rc = ensure(c, t->state, cap * 8 * (size_t)t->F);
-  if (!rc) rc = ensure(c, t->pick, cap * 8);
-  if (!rc) rc = ensure(c, t->ctl, sizeof(mplx::TableCtl));
-  if (!rc && hipHostMalloc((void **)&t->mirror, 64, hipHostMallocCoherent) != hipSuccess)
-    rc = fail(c, MPLX_ERR_HIP, "mplx_table_create: hipHostMalloc failed");
-  if (!rc && mplx::launch_table_clear(table_args(t), c->stream) != hipSuccess) rc = fail(c, MPLX_ERR_HIP, "mplx_table_create: the clearing launch failed");
-  if (rc) {
-    (void)hipGetLastError();
-    release_table(t);
-    return rc;
+  return create_table(c, "mplx_table_create", node_capacity, 1, n_slots, out);
+}
+
+int mplx_table_create_multi(mplx_ctx *c, int64_t node_capacity, int32_t n_queries, int32_t query_slots_log2, mplx_table **out) {
+  if (!c) return MPLX_ERR_ARG;
+  const char *who = "mplx_table_create_multi";
+  if (n_queries == 1) return mplx_table_create(c, node_capacity, query_slots_log2, out);  // the same table
+  if (!out || node_capacity < 1 || node_capacity >= (1LL << 31) || query_slots_log2 < 0 || query_slots_log2 > 31)
+    return fail(c, MPLX_ERR_ARG, "%s: need out, 1 <= node_capacity < 2^31 and 0 <= query_slots_log2 <= 31", who);
+  if (n_queries < 1 || n_queries > 65536) return fail(c, MPLX_ERR_ARG, "%s: n_queries = %d is not in [1, 65536]", who, (int)n_queries);
+  uint64_t q_slots = 0;
+  if (query_slots_log2 == 0) {
+    const uint64_t share = ((uint64_t)node_capacity + (uint64_t)n_queries - 1) / (uint64_t)n_queries;
+    q_slots = 64;
+    while (q_slots < 2 * share) q_slots <<= 1;
+  } else {
+    q_slots = 1ull << query_slots_log2;
   }
-  *out = t;
+  // slot indices are uint32 in the per-entry scratch, 2^32 - 1 means "none", and the dedicated slots come last
+  if (q_slots * (uint64_t)n_queries + (uint64_t)n_queries >= 0xffffffffull)
+    return fail(c, MPLX_ERR_ARG, "%s: %d regions of %llu slots exceed the 32-bit slot index", who, (int)n_queries, (unsigned long long)q_slots);
+  return create_table(c, who, node_capacity, n_queries, q_slots, out);
+}
+
+int mplx_table_query_of(mplx_table *t, const int32_t **d_query, int32_t *n_queries) {
+  if (!t) return MPLX_ERR_ARG;
+  if (!d_query && !n_queries) return fail(t->c, MPLX_ERR_ARG, "mplx_table_query_of: nothing asked for");
+  if (d_query) *d_query = (const int32_t *)t->query.p;
+  if (n_queries) *n_queries = t->Q;
   return MPLX_OK;
-  MPLX_GUARD_END(c)
 }
 
 void mplx_table_destroy(mplx_table *t) {
@@ -237,11 +293,9 @@ int mplx_table_relax_device(mplx_table *t, const mplx_succ_lists *L, int64_t n_n
   return h_count ? read_count(t, d_next, h_count) : MPLX_OK;
 }
 
-int mplx_table_seed(mplx_table *t, const double *h_states, int64_t n, int64_t stride, const double *h_g, const mplx_table_frontier *d_frontier,
-                    int64_t *h_count) {
-  if (!t) return MPLX_ERR_ARG;
+static int seed_table(mplx_table *t, const char *who, const double *h_states, int64_t n, int64_t stride, const double *h_g,
+                      const int32_t *h_query, const mplx_table_frontier *d_frontier, int64_t *h_count) {
   mplx_ctx *c = t->c;
-  const char *who = "mplx_table_seed";
   if (n < 0 || n > kMaxEntries || stride < n || (n > 0 && !h_states)) return fail(c, MPLX_ERR_ARG, "%s: need states and 0 <= n <= stride", who);
   if (int rc = check_frontier(c, who, d_frontier)) return rc;
   if (!c->has_params) return fail(c, MPLX_ERR_STATE, "%s: mplx_set_params has not been called", who);
@@ -255,12 +309,15 @@ int mplx_table_seed(mplx_table *t, const double *h_states, int64_t n, int64_t st
     if (h_count) *h_count = 0;
     return MPLX_OK;
   }
+  const bool multi = t->Q > 1;  // (one query: every seed is query 0 and no kernel looks a query up)
   StageLayout l;
-  const size_t o_st = l.add((size_t)t->F * (size_t)n * 8), o_g = l.add(h_g ? (size_t)n * 8 : 0);
+  const size_t o_st = l.add((size_t)t->F * (size_t)n * 8), o_g = l.add(h_g ? (size_t)n * 8 : 0), o_q = l.add(multi ? (size_t)n * 4 : 0);
   if (int rc = stage_commit(c, &l)) return rc;
   HIP_TRY(c, stage_in_rows(c, l.base + o_st, h_states, (size_t)stride * 8, (size_t)n * 8, (size_t)t->F));
   if (h_g) HIP_TRY(c, stage_in(c, l.base + o_g, h_g, (size_t)n * 8));
+  if (multi) HIP_TRY(c, stage_in(c, l.base + o_q, h_query, (size_t)n * 4));
   mplx::TableArgs a = table_args(t);
+  a.src_query = multi ? (const int32_t *)(l.base + o_q) : nullptr;
   a.src_state = (const double *)(l.base + o_st); a.src_sstride = n;
   a.n_rows = n; a.S = 1; a.parent_g = h_g ? (const double *)(l.base + o_g) : nullptr; a.g_max = INFINITY;
   void *hashes = nullptr;
@@ -274,33 +331,80 @@ int mplx_table_seed(mplx_table *t, const double *h_states, int64_t n, int64_t st
   return MPLX_OK;
 }
 
-int mplx_table_find_device(mplx_table *t, const uint64_t *d_hash, int64_t n, int32_t *d_id) {
+int mplx_table_seed(mplx_table *t, const double *h_states, int64_t n, int64_t stride, const double *h_g, const mplx_table_frontier *d_frontier,
+                    int64_t *h_count) {
   if (!t) return MPLX_ERR_ARG;
+  if (int rc = single_only(t, "mplx_table_seed")) return rc;
+  return seed_table(t, "mplx_table_seed", h_states, n, stride, h_g, nullptr, d_frontier, h_count);
+}
+
+int mplx_table_seed_multi(mplx_table *t, const double *h_states, int64_t n, int64_t stride, const double *h_g, const int32_t *h_query,
+                          const mplx_table_frontier *d_frontier, int64_t *h_count) {
+  if (!t) return MPLX_ERR_ARG;
+  const char *who = "mplx_table_seed_multi";
+  if (n > 0 && !h_query) return fail(t->c, MPLX_ERR_ARG, "%s: NULL h_query", who);
+  for (int64_t i = 0; i < n; i++)
+    if (h_query[i] < 0 || h_query[i] >= t->Q)
+      return fail(t->c, MPLX_ERR_ARG, "%s: h_query[%lld] = %d is not in [0, %d)", who, (long long)i, (int)h_query[i], (int)t->Q);
+  return seed_table(t, who, h_states, n, stride, h_g, h_query, d_frontier, h_count);
+}
+
+// d_query / h_query null: the plain calls (a table of one query)
+static int find_device(mplx_table *t, const char *who, const uint64_t *d_hash, const int32_t *d_query, int64_t n, int32_t *d_id) {
   mplx_ctx *c = t->c;
-  if (n < 0 || (n > 0 && (!d_hash || !d_id))) return fail(c, MPLX_ERR_ARG, "mplx_table_find_device: NULL argument or n < 0");
-  if (int rc = usable(t, "mplx_table_find_device")) return rc;
+  if (n < 0 || (n > 0 && (!d_hash || !d_id))) return fail(c, MPLX_ERR_ARG, "%s: NULL argument or n < 0", who);
+  if (int rc = usable(t, who)) return rc;
   if (int rc = bind_device(c)) return rc;
-  HIP_TRY(c, mplx::launch_table_find(table_args(t), d_hash, n, d_id, c->stream));
+  HIP_TRY(c, mplx::launch_table_find(table_args(t), d_hash, d_query, n, d_id, c->stream));
   return MPLX_OK;
 }
 
-int mplx_table_find(mplx_table *t, const uint64_t *h_hash, int64_t n, int32_t *h_id) {
-  if (!t) return MPLX_ERR_ARG;
+static int find_host(mplx_table *t, const char *who, const uint64_t *h_hash, const int32_t *h_query, int64_t n, int32_t *h_id) {
   mplx_ctx *c = t->c;
-  if (n < 0 || (n > 0 && (!h_hash || !h_id))) return fail(c, MPLX_ERR_ARG, "mplx_table_find: NULL argument or n < 0");
-  if (int rc = usable(t, "mplx_table_find")) return rc;
+  if (n < 0 || (n > 0 && (!h_hash || !h_id))) return fail(c, MPLX_ERR_ARG, "%s: NULL argument or n < 0", who);
+  if (int rc = usable(t, who)) return rc;
   if (n == 0) return MPLX_OK;
   if (int rc = bind_device(c)) return rc;
   if (int rc = resolve_pending(c)) return rc;
   StageLayout l;
-  const size_t o_h = l.add((size_t)n * 8), o_id = l.add((size_t)n * 4);
+  const size_t o_h = l.add((size_t)n * 8), o_id = l.add((size_t)n * 4), o_q = l.add(h_query ? (size_t)n * 4 : 0);
   if (int rc = stage_commit(c, &l)) return rc;
   HIP_TRY(c, stage_in(c, l.base + o_h, h_hash, (size_t)n * 8));
-  HIP_TRY(c, mplx::launch_table_find(table_args(t), (const uint64_t *)(l.base + o_h), n, (int32_t *)(l.base + o_id), c->stream));
+  if (h_query) HIP_TRY(c, stage_in(c, l.base + o_q, h_query, (size_t)n * 4));
+  HIP_TRY(c, mplx::launch_table_find(table_args(t), (const uint64_t *)(l.base + o_h), h_query ? (const int32_t *)(l.base + o_q) : nullptr, n,
+                                     (int32_t *)(l.base + o_id), c->stream));
   HIP_TRY(c, stage_out(c, h_id, l.base + o_id, (size_t)n * 4));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   observe(t);
   return MPLX_OK;
+}
+
+int mplx_table_find_device(mplx_table *t, const uint64_t *d_hash, int64_t n, int32_t *d_id) {
+  if (!t) return MPLX_ERR_ARG;
+  if (int rc = single_only(t, "mplx_table_find_device")) return rc;
+  return find_device(t, "mplx_table_find_device", d_hash, nullptr, n, d_id);
+}
+
+int mplx_table_find(mplx_table *t, const uint64_t *h_hash, int64_t n, int32_t *h_id) {
+  if (!t) return MPLX_ERR_ARG;
+  if (int rc = single_only(t, "mplx_table_find")) return rc;
+  return find_host(t, "mplx_table_find", h_hash, nullptr, n, h_id);
+}
+
+int mplx_table_find_multi_device(mplx_table *t, const uint64_t *d_hash, const int32_t *d_query, int64_t n, int32_t *d_id) {
+  if (!t) return MPLX_ERR_ARG;
+  if (n > 0 && !d_query) return fail(t->c, MPLX_ERR_ARG, "mplx_table_find_multi_device: NULL d_query");
+  return find_device(t, "mplx_table_find_multi_device", d_hash, d_query, n, d_id);
+}
+
+int mplx_table_find_multi(mplx_table *t, const uint64_t *h_hash, const int32_t *h_query, int64_t n, int32_t *h_id) {
+  if (!t) return MPLX_ERR_ARG;
+  const char *who = "mplx_table_find_multi";
+  if (n > 0 && !h_query) return fail(t->c, MPLX_ERR_ARG, "%s: NULL h_query", who);
+  for (int64_t i = 0; i < n; i++)
+    if (h_query[i] < 0 || h_query[i] >= t->Q)
+      return fail(t->c, MPLX_ERR_ARG, "%s: h_query[%lld] = %d is not in [0, %d)", who, (long long)i, (int)h_query[i], (int)t->Q);
+  return find_host(t, who, h_hash, h_query, n, h_id);
 }
 
 int mplx_table_path(mplx_table *t, int32_t id, int32_t *h_ids, int32_t *h_actions, int64_t cap, int64_t *n_edges) {

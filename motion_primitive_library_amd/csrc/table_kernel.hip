@@ -6,6 +6,8 @@
 // The table is open addressing in HBM keyed by the 64-bit lattice hash, as in post_kernel.hip: linear probing from a
 // mixed hash, 64-bit CAS for the key, key and id in one 16-byte slot, a dedicated slot for the one hash equal to the
 // empty marker.  Unlike that one-call table it persists, and its probe loop is bounded by the table's length.
+// A table with several queries (include/mplx_multi.h) keeps one such region of slots, and one dedicated slot, per
+// query: claim and find add the region's base, the number pass writes the new node's query, nothing else changes.
 //
 // One relax call is nine launches; a launch boundary is the only ordering between passes (no grid-wide barrier, no
 // spinning workgroup: DESIGN.md 11.1), and inside a pass only order-free atomics decide anything:
@@ -41,10 +43,13 @@ __device__ __forceinline__ uint64_t mix(uint64_t h) {  // table position only; n
 }
 
 // Does entry e count (include/mplx_table.h), and with which candidate?  Reads nothing of an entry past count[k].
-__device__ __forceinline__ bool entry(const TableArgs &A, int64_t e, int64_t *row, double *cand_out) {
+// n_before: the nodes the table held before the call -- on a table with several queries a parent must be one of them
+// (its query is the entry's).
+__device__ __forceinline__ bool entry(const TableArgs &A, int64_t e, int64_t n_before, int64_t *row, double *cand_out) {
   const int64_t k = e / A.S;
   if (A.count && (int)(e - k * A.S) >= A.count[k]) return false;
   if (A.parent_id && A.parent_id[k] < 0) return false;
+  if (A.query && A.parent_id && A.parent_id[k] >= n_before) return false;
   double cand = A.parent_g ? A.parent_g[k] : 0.0;
   if (A.cost) {
     const double c = A.cost[e];
@@ -57,6 +62,11 @@ __device__ __forceinline__ bool entry(const TableArgs &A, int64_t e, int64_t *ro
   return true;
 }
 
+// The query of a counting entry of a table with several queries: the seed's own, or its parent's (an id below n_before).
+__device__ __forceinline__ int32_t entry_query(const TableArgs &A, int64_t e, int64_t row) {
+  return A.src_query ? A.src_query[e] : A.query[A.parent_id[row]];
+}
+
 __global__ __launch_bounds__(kBlock) void table_claim_kernel(const TableArgs A) {
   if (A.ctl->status) return;
   const int64_t e = (int64_t)blockIdx.x * kBlock + threadIdx.x;
@@ -64,23 +74,31 @@ __global__ __launch_bounds__(kBlock) void table_claim_kernel(const TableArgs A) 
   int64_t k;
   double cand;
   uint32_t s = kNone;
-  if (entry(A, e, &k, &cand)) {
+  if (entry(A, e, A.query ? A.ctl->n_nodes : 0, &k, &cand)) {
     const uint64_t h = A.src_hash[e];
+    // a query's keys live in its own region of q_slots slots: the compare stays the hash alone
+    uint64_t q = 0;
+    if (A.query) {
+      const int32_t qq = entry_query(A, e, k);
+      q = (qq >= 0 && qq < A.n_queries) ? (uint64_t)qq : 0;  // (the host checks the seeds; the column holds only queries)
+    }
     if (h == kEmpty) {
-      s = (uint32_t)A.n_slots;  // the one hash the key field cannot hold
+      s = (uint32_t)(A.n_slots + q);  // the one hash the key field cannot hold
     } else {
-      const uint64_t mask = A.n_slots - 1;
+      const uint64_t mask = A.q_slots - 1, base = q * A.q_slots;
       uint64_t p = mix(h) & mask;
-      for (uint64_t tries = 0; tries < A.n_slots; tries++) {
-        uint64_t key = A.slots[p].key;  // (a stale "empty" only costs the CAS; a key never changes once it is set)
-        if (key == kEmpty) key = atomicCAS((unsigned long long *)&A.slots[p].key, (unsigned long long)kEmpty, (unsigned long long)h);
+      for (uint64_t tries = 0; tries < A.q_slots; tries++) {
+        TableSlot *sl = &A.slots[base + p];
+        uint64_t key = sl->key;  // (a stale "empty" only costs the CAS; a key never changes once it is set)
+        if (key == kEmpty) key = atomicCAS((unsigned long long *)&sl->key, (unsigned long long)kEmpty, (unsigned long long)h);
         if (key == kEmpty || key == h) {
-          s = (uint32_t)p;
+          s = (uint32_t)(base + p);
           break;
         }
         p = (p + 1) & mask;
       }
-      // every slot holds another key: more keys than slots, hence than node_capacity (< n_slots) -- both bits
+      // every slot of the region holds another key.  One query: more keys than slots, hence than node_capacity
+      // (< n_slots); several: the query's region is full -- both bits either way
       if (s == kNone) atomicOr(&A.ctl->status, kProbeFull | kNodesFull);
     }
     // a key without an id is new in this call (ids are written by the number pass, behind a launch boundary)
@@ -220,6 +238,7 @@ __global__ __launch_bounds__(kBlock) void table_apply_kernel(const TableArgs A) 
       A.pick[id] = ~0ull;
       A.pred[id] = -1;
       A.pred_action[id] = -1;
+      if (A.query) A.query[id] = entry_query(A, e, e / A.S);  // (a counting entry: its parent is an older node)
       for (int f = 0; f < A.n_fields; f++) A.state[(int64_t)f * A.cap + id] = A.src_state[(int64_t)f * A.src_sstride + e];
     } else {
       if (r >= A.f_cap) continue;
@@ -241,7 +260,7 @@ __global__ __launch_bounds__(kBlock) void table_lower_kernel(const TableArgs A) 
     id = A.slots[s].id;
     int64_t k;
     double cand;
-    if (id >= 0 && id < A.cap && entry(A, e, &k, &cand)) {
+    if (id >= 0 && id < A.cap && entry(A, e, A.query ? A.ctl->base : 0, &k, &cand)) {
       const unsigned long long bits = (unsigned long long)__double_as_longlong(cand);
       const unsigned long long old = atomicMin(&A.g[id], bits);
       if (old > bits) atomicMin(&A.pick[id], ((unsigned long long)A.tag << 32) | 0xffffffffull);  // improved in this call
@@ -262,7 +281,7 @@ __global__ __launch_bounds__(kBlock) void table_pick_kernel(const TableArgs A) {
   if ((uint32_t)(A.pick[id] >> 32) != A.tag) return;  // not improved in this call
   int64_t k;
   double cand;
-  if (!entry(A, e, &k, &cand)) return;
+  if (!entry(A, e, A.query ? A.ctl->base : 0, &k, &cand)) return;
   if ((unsigned long long)__double_as_longlong(cand) == A.g[id]) atomicMin(&A.pick[id], ((unsigned long long)A.tag << 32) | (unsigned long long)e);
 }
 
@@ -302,24 +321,28 @@ hipError_t hash_dim(int control, const double *states, int64_t n, int64_t stride
   return hipGetLastError();
 }
 
-__global__ __launch_bounds__(kBlock) void table_find_kernel(const TableArgs A, const uint64_t *hash, int64_t n, int32_t *id) {
-  const int64_t q = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-  if (q >= n) return;
-  const uint64_t h = hash[q];
+__global__ __launch_bounds__(kBlock) void table_find_kernel(const TableArgs A, const uint64_t *hash, const int32_t *query, int64_t n,
+                                                            int32_t *id) {
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= n) return;
+  const uint64_t h = hash[i];
+  const int64_t q = query ? (int64_t)query[i] : 0;
   int32_t out = -1;
-  if (h == kEmpty) {
-    out = A.slots[A.n_slots].id;
+  if (q < 0 || q >= A.n_queries) {
+    // no such query: not in the table
+  } else if (h == kEmpty) {
+    out = A.slots[A.n_slots + (uint64_t)q].id;
   } else {
-    const uint64_t mask = A.n_slots - 1;
+    const uint64_t mask = A.q_slots - 1, base = (uint64_t)q * A.q_slots;
     uint64_t p = mix(h) & mask;
-    for (uint64_t tries = 0; tries < A.n_slots; tries++) {
-      const uint64_t key = A.slots[p].key;
-      if (key == h) out = A.slots[p].id;
+    for (uint64_t tries = 0; tries < A.q_slots; tries++) {
+      const uint64_t key = A.slots[base + p].key;
+      if (key == h) out = A.slots[base + p].id;
       if (key == h || key == kEmpty) break;
       p = (p + 1) & mask;
     }
   }
-  id[q] = out < 0 ? -1 : out;
+  id[i] = out < 0 ? -1 : out;
 }
 
 __global__ void table_path_kernel(const TableArgs A, int32_t id, int32_t *ids, int32_t *actions, int64_t cap, int64_t *len) {
@@ -372,7 +395,7 @@ hipError_t launch_table_relax(const TableArgs &a, hipStream_t s) {
 }
 
 hipError_t launch_table_clear(const TableArgs &a, hipStream_t s) {
-  if (hipError_t e = hipMemsetAsync(a.slots, 0xff, (a.n_slots + 1) * sizeof(TableSlot), s)) return e;
+  if (hipError_t e = hipMemsetAsync(a.slots, 0xff, (a.n_slots + (uint64_t)a.n_queries) * sizeof(TableSlot), s)) return e;
   hipLaunchKernelGGL(table_clear_kernel, dim3(1), dim3(1), 0, s, a);
   return hipGetLastError();
 }
@@ -384,9 +407,9 @@ hipError_t launch_table_hash(int dim, int control, const double *states, int64_t
   return hipErrorInvalidValue;
 }
 
-hipError_t launch_table_find(const TableArgs &a, const uint64_t *hash, int64_t n, int32_t *id, hipStream_t s) {
+hipError_t launch_table_find(const TableArgs &a, const uint64_t *hash, const int32_t *query, int64_t n, int32_t *id, hipStream_t s) {
   if (n <= 0) return hipSuccess;
-  hipLaunchKernelGGL(table_find_kernel, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, a, hash, n, id);
+  hipLaunchKernelGGL(table_find_kernel, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, a, hash, query, n, id);
   return hipGetLastError();
 }
 

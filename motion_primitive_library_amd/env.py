@@ -1275,9 +1275,9 @@ class EnvMap:
         _abi.check(self._ctx, _abi.lib().mplx_traj_traverse_device(self._ctx, C.byref(s), int(lanes), C.byref(o)))
 
     # ---- the persistent node table (include/mplx_table.h; table.py): relax successor lists, emit the next frontier
-    def alloc_table(self, capacity, slots_log2=0):
+    def alloc_table(self, capacity, slots_log2=0, n_queries=1):
         from .table import NodeTable
-        return NodeTable(self, capacity, slots_log2)
+        return NodeTable(self, capacity, slots_log2, n_queries)
 
     def alloc_table_frontier(self, capacity):
         from .table import TableFrontier
@@ -1342,6 +1342,19 @@ class EnvMap:
         from .search import run_search
         return run_search(self, start, goal_row, eps, delta, g_max, max_rounds, max_expand, capacity, max_frontier,
                           lists_stride, sight, tol_pos, tol_vel, tol_acc, tol_yaw, w, v_max)
+
+    def search_many(self, starts, goal_rows, eps=1.0, delta=None, g_max=float("inf"), max_rounds=None, max_expand=None,
+                    capacity=1 << 16, max_frontier=None, lists_stride=None, sight=True, tol_pos=0.5, tol_vel=-1.0,
+                    tol_acc=-1.0, tol_yaw=-1.0, w=None, v_max=None):
+        """Q searches of EnvMap.search at once, sharing every launch of a round (include/mplx_multi.h): starts
+        [4D+2][Q], goal_rows [Q][4D+2], query q from starts[:, q] to the goal region of goal_rows[q].  One table of
+        `capacity` nodes and one open set hold all of them; a round selects, expands, relaxes and pushes the union of
+        what the queries select, and reads Q results back.  The loop goes on while any query selects; max_expand counts
+        all queries together.  As long as no selection is cut at max_frontier every query does exactly what its own
+        EnvMap.search does.  Returns a MultiSearchResult (search.py) that owns the table and the open set."""
+        from .search import run_search_many
+        return run_search_many(self, starts, goal_rows, eps, delta, g_max, max_rounds, max_expand, capacity, max_frontier,
+                               lists_stride, sight, tol_pos, tol_vel, tol_acc, tol_yaw, w, v_max)
 
     def synchronize(self):
         _abi.check(self._ctx, _abi.lib().mplx_synchronize(self._ctx))

@@ -64,15 +64,22 @@ class TableFrontier:
 
 
 class NodeTable:
-    """mplx_table of an EnvMap's context.  Free it (or let it go) before the EnvMap is closed."""
+    """mplx_table of an EnvMap's context.  Free it (or let it go) before the EnvMap is closed.  n_queries > 1: a table
+    of that many queries (include/mplx_multi.h): a node is a (query, hash) pair, slots_log2 sizes one query's region of
+    the hash table, seed / find take the query of every state / hash."""
 
-    def __init__(self, env, capacity, slots_log2=0):
+    def __init__(self, env, capacity, slots_log2=0, n_queries=1):
         self._env = env
         self._tab = None
         self.capacity = int(capacity)
+        self.n_queries = int(n_queries)
         self.n_fields = env.n_fields
         t = C.c_void_p()
-        _abi.check(env._ctx, _abi.lib().mplx_table_create(env._ctx, self.capacity, int(slots_log2), C.byref(t)))
+        if self.n_queries == 1:
+            rc = _abi.lib().mplx_table_create(env._ctx, self.capacity, int(slots_log2), C.byref(t))
+        else:
+            rc = _abi.lib().mplx_table_create_multi(env._ctx, self.capacity, self.n_queries, int(slots_log2), C.byref(t))
+        _abi.check(env._ctx, rc)
         self._tab = t
 
     def _check(self, rc):
@@ -98,10 +105,11 @@ class NodeTable:
         self._check(_abi.lib().mplx_table_stats(self._tab, C.byref(n), C.byref(st)))
         return int(n.value), int(st.value)
 
-    def seed(self, states, g=None, frontier=None):
+    def seed(self, states, g=None, frontier=None, query=None):
         """Creates / improves the nodes of `states` ([4D+2][n] or one state) with cost-to-come g (default 0) and no
         predecessor; writes the first frontier.  Returns the frontier count (and the frontier it allocated, if none
-        was given: (count, frontier))."""
+        was given: (count, frontier)).  query: the query of every state ([n] or one for all; mplx_table_seed_multi);
+        None is the plain call, which a table of several queries refuses."""
         self._env._flush()
         states = np.ascontiguousarray(states, dtype=np.float64)
         if states.ndim == 1:
@@ -118,7 +126,12 @@ class NodeTable:
             frontier = TableFrontier(self._env, n)
         f = frontier.c_struct()
         cnt = C.c_int64(-1)
-        self._check(_abi.lib().mplx_table_seed(self._tab, states.ctypes.data, n, n, gp, C.byref(f), C.byref(cnt)))
+        if query is None:
+            self._check(_abi.lib().mplx_table_seed(self._tab, states.ctypes.data, n, n, gp, C.byref(f), C.byref(cnt)))
+        else:
+            q = np.ascontiguousarray(np.broadcast_to(np.asarray(query, dtype=np.int32), (n,)))
+            self._check(_abi.lib().mplx_table_seed_multi(self._tab, states.ctypes.data, n, n, gp, q.ctypes.data, C.byref(f),
+                                                         C.byref(cnt)))
         return (int(cnt.value), frontier) if own else int(cnt.value)
 
     def relax(self, lists, parent_id, parent_g, g_max=float("inf"), frontier=None, n_nodes=None, entry_id=None, want_count=True):
@@ -135,12 +148,23 @@ class NodeTable:
             _device_ptr(entry_id) if entry_id is not None else None, C.byref(cnt) if want_count else None))
         return int(cnt.value) if want_count else None
 
-    def find(self, hashes):
-        """Node id of every hash, -1 for a hash the table does not hold."""
+    def find(self, hashes, query=None):
+        """Node id of every hash (with query: of every (query, hash) pair; [n] or one for all), -1 for one the table
+        does not hold."""
         h = np.ascontiguousarray(hashes, dtype=np.uint64).ravel()
         out = np.full(h.size, -1, np.int32)
-        self._check(_abi.lib().mplx_table_find(self._tab, h.ctypes.data, h.size, out.ctypes.data))
+        if query is None:
+            self._check(_abi.lib().mplx_table_find(self._tab, h.ctypes.data, h.size, out.ctypes.data))
+        else:
+            q = np.ascontiguousarray(np.broadcast_to(np.asarray(query, dtype=np.int32), (h.size,)))
+            self._check(_abi.lib().mplx_table_find_multi(self._tab, h.ctypes.data, q.ctypes.data, h.size, out.ctypes.data))
         return out
+
+    def query_ptr(self):
+        """Device address of the per-node query column (None for a table of one query)."""
+        p, q = C.c_void_p(), C.c_int32()
+        self._check(_abi.lib().mplx_table_query_of(self._tab, C.byref(p), C.byref(q)))
+        return p.value
 
     def path(self, node_id, cap=None):
         """(ids, actions) of the chain of best predecessors from a seed to `node_id`, root first: actions[i] leads from
@@ -164,13 +188,16 @@ class NodeTable:
         return out
 
     def download(self):
-        """The used prefix of every node array: n_nodes, hash, g, pred, pred_action, state [4D+2][n_nodes]."""
+        """The used prefix of every node array: n_nodes, hash, g, pred, pred_action, query (zeros for a table of one
+        query), state [4D+2][n_nodes]."""
         n, status = self.stats()
         v = self.view()
         st = np.empty((self.n_fields, n), np.float64)
         for f in range(self.n_fields):
             st[f] = self._read(v.state + 8 * f * v.state_stride, np.float64, n)
+        qp = self.query_ptr()
         return {"n_nodes": n, "status": status, "hash": self._read(v.hash, np.uint64, n), "g": self._read(v.g, np.float64, n),
+                "query": self._read(qp, np.int32, n) if qp else np.zeros(n, np.int32),
                 "pred": self._read(v.pred, np.int32, n), "pred_action": self._read(v.pred_action, np.int32, n), "state": st}
 
     def state_of(self, node_id):
