@@ -48,7 +48,8 @@
  * no-ops of push; a select then returns MPLX_OPEN_EMPTY.  No call writes past the capacity of any array or loops
  * without bound.
  *
- * The open set of a table with several queries has one goal and one result per query: include/mplx_multi.h.         */
+ * The open set of a table with several queries has one goal and one result per query: include/mplx_multi.h.  The push
+ * that sets keys and goal bits without opening the nodes (after a rebase of the table): include/mplx_replan.h.      */
 #ifndef MPLX_OPEN_H
 #define MPLX_OPEN_H
 

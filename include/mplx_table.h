@@ -46,7 +46,9 @@
  * no-op with frontier count 0.
  *
  * A table can also hold the nodes of several queries at once, a node then being a (query, hash) pair: that form, what
- * it changes for relax, and which of the calls below it refuses are in include/mplx_multi.h.                          */
+ * it changes for relax, and which of the calls below it refuses are in include/mplx_multi.h.  Planning again on the
+ * same table after the robot has moved or the map was edited -- which nodes are kept, with their g -- is
+ * include/mplx_replan.h.                                                                                             */
 #ifndef MPLX_TABLE_H
 #define MPLX_TABLE_H
 

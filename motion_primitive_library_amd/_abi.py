@@ -59,6 +59,8 @@ OPEN_SELECTED, OPEN_FOUND, OPEN_EMPTY = 0, 1, 2
 # ... and the ones include/mplx_multi.h declares (Q queries in one table and one open set)
 MULTI_SYMBOLS = ["mplx_table_create_multi", "mplx_table_query_of", "mplx_table_seed_multi", "mplx_table_find_multi_device",
                  "mplx_table_find_multi", "mplx_open_set_goals", "mplx_open_select_multi_device"]
+# ... and the ones include/mplx_replan.h declares (re-root and repair a table after a map edit)
+REPLAN_SYMBOLS = ["mplx_table_rebase_device", "mplx_table_rebase_multi_device", "mplx_open_push_closed_device"]
 
 ROUTE_AUTO, ROUTE_DENSE, ROUTE_TILE, ROUTE_GRID = 0, 1, 2, 3
 
@@ -141,6 +143,10 @@ class OpenView(C.Structure):
 class OpenResult(C.Structure):
     _fields_ = [("status", C.c_int32), ("goal_id", C.c_int32), ("count", C.c_int64), ("n_open", C.c_int64),
                 ("f_min", C.c_double), ("goal_f", C.c_double), ("goal_g", C.c_double)]
+
+
+class RebaseResult(C.Structure):
+    _fields_ = [("n_kept", C.c_int64), ("n_bad_edges", C.c_int64), ("n_roots", C.c_int64)]
 
 
 class PackedLists(C.Structure):
@@ -338,8 +344,11 @@ def lib():
         "mplx_table_find_multi": (C.c_int, [vp, vp, vp, i64, vp]),
         "mplx_open_set_goals": (C.c_int, [vp, C.POINTER(GoalSpec), i32]),
         "mplx_open_select_multi_device": (C.c_int, [vp, dbl, C.POINTER(TableFrontier), vp, C.POINTER(OpenResult)]),
+        "mplx_table_rebase_device": (C.c_int, [vp, i32, i32, C.POINTER(TableFrontier), vp, C.POINTER(RebaseResult)]),
+        "mplx_table_rebase_multi_device": (C.c_int, [vp, vp, i32, C.POINTER(TableFrontier), vp, C.POINTER(RebaseResult)]),
+        "mplx_open_push_closed_device": (C.c_int, [vp, C.POINTER(TableFrontier), i64, dbl, i32]),
     }
-    for name in SYMBOLS + MAP_UTIL_SYMBOLS + ROLLOUT_SYMBOLS + RAY_SYMBOLS + TRAJ_SYMBOLS + TABLE_SYMBOLS + OPEN_SYMBOLS + MULTI_SYMBOLS:
+    for name in SYMBOLS + MAP_UTIL_SYMBOLS + ROLLOUT_SYMBOLS + RAY_SYMBOLS + TRAJ_SYMBOLS + TABLE_SYMBOLS + OPEN_SYMBOLS + MULTI_SYMBOLS + REPLAN_SYMBOLS:
         fn = getattr(L, name)  # AttributeError if the library does not export it
         fn.restype, fn.argtypes = sig[name]
     _lib = L

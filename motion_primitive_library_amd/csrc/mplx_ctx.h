@@ -5,6 +5,7 @@
 
 #include "../../include/mplx.h"
 #include "../../include/mplx_debug.h"
+#include "../../include/mplx_open.h"  // mplx_open, mplx_table_frontier: what open_push() below takes
 #include "mplx_internal.h"
 
 #include <cstdarg>
@@ -341,6 +342,12 @@ void release_copy_buffers(mplx_ctx *c);
 // wait for the stream, what the last finished call left (status bit, node count).
 int table_open_args(mplx_table *t, const char *who, mplx_ctx **c, mplx::OpenArgs *a);
 void table_observe(mplx_table *t);
+// ... and as a rebase (replan_api.cpp) sees it: the same check, the table's arrays, its bound of n_nodes and the scratch
+// of the rebase passes (scratch: allocated here on the first call, for the table's capacity; the device is bound.  Without
+// it only the check, n_queries and n_bound)
+int table_replan_args(mplx_table *t, const char *who, bool scratch, mplx_ctx **c, mplx::ReplanArgs *a);
+// open_api.cpp: mplx_open_push_device; closed: without IS_OPEN (mplx_open_push_closed_device, replan_api.cpp)
+int open_push(mplx_open *o, const char *who, const mplx_table_frontier *d_rows, int64_t n_max, double eps, int32_t sight, bool closed);
 
 // mplx_api.cpp: a goal as the kernels take it (mplx_set_goal's checks and hash), for the goals of an open set.
 int goal_fuse_of(mplx_ctx *c, const char *who, const mplx_goal_spec *g, mplx::PostFuse *out);

@@ -600,10 +600,50 @@ struct OpenArgs {
   int64_t *f_count;
 };
 hipError_t launch_open_clear(const OpenArgs &a, hipStream_t s);  // ctl: 2 * n_queries control blocks
-hipError_t launch_open_push(int dim, int pass, const OpenArgs &a, int64_t rows, hipStream_t s);  // pass 0: all (or up to the row flags); 1: after the ray trace
+// closed: the push of include/mplx_replan.h -- the rows get SEEN (and IS_GOAL) but not IS_OPEN
+hipError_t launch_open_push(int dim, int pass, const OpenArgs &a, int64_t rows, hipStream_t s, bool closed = false);  // pass 0: all (or up to the row flags); 1: after the ray trace
 hipError_t launch_open_select(const OpenArgs &a, hipStream_t s);
 // select_multi: ctl / ctl_next / mirror / result are arrays of n_queries
 hipError_t launch_open_select_multi(const OpenArgs &a, hipStream_t s);
+
+// Re-rooting and repair of a node table after a map edit (replan_kernel.hip, replan_api.cpp; include/mplx_replan.h).
+struct ReplanResult { int64_t n_kept, n_bad_edges, n_roots; };  // mplx_rebase_result
+struct ReplanArgs {
+  ExpandArgs env;            // map, potential, region, parameters and controls as expand_args() fills them (check_edges only)
+  int32_t band;              // 1: a heading-limit decision within env.yaw.margin of its threshold makes the edge bad
+  int32_t check_edges;
+  // the table
+  TableCtl *ctl;
+  TableMirror *mirror;
+  const uint64_t *hash;
+  unsigned long long *g;
+  int32_t *pred, *pred_action;
+  const double *state;       // [n_fields][cap]
+  const int32_t *query;      // per node its query; null for a table of one query
+  int32_t n_queries, n_fields;
+  int64_t cap;
+  int64_t n_bound;           // host-known upper bound of n_nodes: sizes the grids and the number of resolve passes
+  // the roots: root_of_query ([n_queries], device memory) or, when it is null, root_id for the one query
+  int32_t root_id;
+  const int32_t *root_of_query;
+  // scratch of the table, sized by its capacity
+  uint8_t *bad;              // [cap] the edge (pred, pred_action) of a non-root node no longer holds
+  uint8_t *dec[2];           // [cap] each: 0 unknown, 1 keep, 2 drop; a resolve pass reads one and writes the other
+  int32_t *jump[2];          // [cap] each: the ancestor an unknown node looks at next
+  uint8_t *mark;             // [cap] kept
+  uint32_t *tot;             // [n_tiles] kept nodes per tile of kTableTile ids, then their exclusive prefix sums
+  int64_t n_tiles;
+  ReplanResult *counters;    // zero before the call: the result, summed by order-free integer atomics
+  // the frontier of kept nodes
+  int32_t *f_id;
+  double *f_g, *f_state;
+  int64_t f_stride, f_cap;
+  int64_t *f_count;
+};
+hipError_t launch_replan_rebase(int dim, int control, const ReplanArgs &a, int passes, hipStream_t s);
+// table_kernel.hip: the scan of tile counts tot[n_tiles] in place, the frontier count (FRONTIER_FULL when it exceeds
+// f_cap), ctl->emit and the pinned mirror -- the second scan of a relax, for a pass that marked per tile itself
+hipError_t launch_table_scan_frontier(const TableArgs &a, hipStream_t s);
 
 // Element-wise math probe (see mplx_selftest_math in mplx.h).
 hipError_t launch_math_probe(int op, const double *a, const double *b, double *out, int64_t n,

@@ -125,8 +125,14 @@ int mplx_open_view_of(mplx_open *o, mplx_open_view *v) {
 
 int mplx_open_push_device(mplx_open *o, const mplx_table_frontier *d_rows, int64_t n_max, double eps, int32_t sight) {
   if (!o) return MPLX_ERR_ARG;
+  return open_push(o, "mplx_open_push_device", d_rows, n_max, eps, sight, false);
+}
+
+}  // extern "C"
+
+int mplx_detail::open_push(mplx_open *o, const char *who, const mplx_table_frontier *d_rows, int64_t n_max, double eps, int32_t sight,
+                           bool closed) {
   mplx_ctx *c = o->c;
-  const char *who = "mplx_open_push_device";
   if (n_max < 0 || !(eps >= 0.0) || std::isinf(eps)) return fail(c, MPLX_ERR_ARG, "%s: need n_max >= 0 and a finite eps >= 0", who);
   if (int rc = check_frontier(c, who, d_rows)) return rc;
   if (o->Q > 1 && !o->has_goals) return fail(c, MPLX_ERR_STATE, "%s: no goals (mplx_open_set_goals)", who);
@@ -143,7 +149,7 @@ int mplx_open_push_device(mplx_open *o, const mplx_table_frontier *d_rows, int64
   a.goal = c->goal_fuse;
   a.goals = o->has_goals ? (const mplx::PostFuse *)o->goals.p : nullptr;
   if (!sight) {
-    HIP_TRY(c, mplx::launch_open_push(c->dim, 0, a, rows, c->stream));
+    HIP_TRY(c, mplx::launch_open_push(c->dim, 0, a, rows, c->stream, closed));
     return MPLX_OK;
   }
   // around the goal passes of ray_kernel.hip: the frontier as `rows` lists of stride 1 with a flags byte each
@@ -153,7 +159,7 @@ int mplx_open_push_device(mplx_open *o, const mplx_table_frontier *d_rows, int64
   a.row_flags = (uint8_t *)o->rows.p;
   a.row_count = (int32_t *)((char *)o->rows.p + o_cnt);
   a.row_query = a.goals ? (int32_t *)((char *)o->rows.p + o_qry) : nullptr;
-  HIP_TRY(c, mplx::launch_open_push(c->dim, 0, a, rows, c->stream));
+  HIP_TRY(c, mplx::launch_open_push(c->dim, 0, a, rows, c->stream, closed));
   mplx_succ_lists L{};
   L.count = a.row_count;
   L.state = d_rows->state;
@@ -165,9 +171,11 @@ int mplx_open_push_device(mplx_open *o, const mplx_table_frontier *d_rows, int64
   } else if (int rc = mplx_goal_sight_device(c, &L, rows, nullptr, a.row_flags)) {
     return rc;
   }
-  HIP_TRY(c, mplx::launch_open_push(c->dim, 1, a, rows, c->stream));
+  HIP_TRY(c, mplx::launch_open_push(c->dim, 1, a, rows, c->stream, closed));
   return MPLX_OK;
 }
+
+extern "C" {
 
 int mplx_open_select_device(mplx_open *o, double delta, const mplx_table_frontier *d_out, mplx_open_result *d_result,
                             mplx_open_result *h_result) {

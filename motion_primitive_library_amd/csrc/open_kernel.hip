@@ -74,7 +74,8 @@ __device__ __forceinline__ Decision decide(const OpenCtl *c, double delta) {
 __device__ __forceinline__ Decision decide(const OpenArgs &A) { return decide(A.ctl, A.delta); }
 
 // MULTI: the goal is goals[query of the node] (mplx_open_set_goals), not the context's
-template <int D, bool MULTI>
+// CLOSED: the push of include/mplx_replan.h -- key and goal bit as ever, but the node is not opened
+template <int D, bool MULTI, bool CLOSED>
 __global__ __launch_bounds__(kBlock) void open_push_kernel(const OpenArgs A, int64_t rows, int pass) {
   if (A.t_ctl->status) return;
   const int64_t r = (int64_t)blockIdx.x * kBlock + threadIdx.x;
@@ -91,7 +92,7 @@ __global__ __launch_bounds__(kBlock) void open_push_kernel(const OpenArgs A, int
   if (id < 0 || id >= node_count(A)) return;
   if (pass == 1) {
     const uint8_t rf = A.row_flags[r];
-    if (rf & kRowCounts) A.flags[id] = (uint8_t)(kSeen | kIsOpen | (((rf & kRowTol) && !(rf & kRowBlocked)) ? kIsGoal : 0));
+    if (rf & kRowCounts) A.flags[id] = (uint8_t)(kSeen | (CLOSED ? 0 : kIsOpen) | (((rf & kRowTol) && !(rf & kRowBlocked)) ? kIsGoal : 0));
     return;
   }
   double s[4 * D + 1];
@@ -120,7 +121,7 @@ __global__ __launch_bounds__(kBlock) void open_push_kernel(const OpenArgs A, int
   if (A.row_flags) {
     A.row_flags[r] = (uint8_t)(kRowCounts | (fl & 1u));
     if (MULTI) A.row_query[r] = q;
-  } else A.flags[id] = (uint8_t)(kSeen | kIsOpen | ((fl & 1u) ? kIsGoal : 0));
+  } else A.flags[id] = (uint8_t)(kSeen | (CLOSED ? 0 : kIsOpen) | ((fl & 1u) ? kIsGoal : 0));
 }
 
 __global__ __launch_bounds__(kBlock) void open_reduce_kernel(const OpenArgs A) {
@@ -483,16 +484,22 @@ hipError_t launch_open_clear(const OpenArgs &a, hipStream_t s) {
   return hipGetLastError();
 }
 
-hipError_t launch_open_push(int dim, int pass, const OpenArgs &a, int64_t rows, hipStream_t s) {
+template <int D, bool MULTI>
+void push_closed(bool closed, dim3 grid, dim3 block, hipStream_t s, const OpenArgs &a, int64_t rows, int pass) {
+  if (closed) hipLaunchKernelGGL((open_push_kernel<D, MULTI, true>), grid, block, 0, s, a, rows, pass);
+  else hipLaunchKernelGGL((open_push_kernel<D, MULTI, false>), grid, block, 0, s, a, rows, pass);
+}
+
+hipError_t launch_open_push(int dim, int pass, const OpenArgs &a, int64_t rows, hipStream_t s, bool closed) {
   if (rows <= 0) return hipSuccess;
   const dim3 grid((unsigned)((rows + kBlock - 1) / kBlock)), block(kBlock);
   if (dim != 2 && dim != 3) return hipErrorInvalidValue;
   if (a.goals) {
-    if (dim == 2) hipLaunchKernelGGL((open_push_kernel<2, true>), grid, block, 0, s, a, rows, pass);
-    else hipLaunchKernelGGL((open_push_kernel<3, true>), grid, block, 0, s, a, rows, pass);
+    if (dim == 2) push_closed<2, true>(closed, grid, block, s, a, rows, pass);
+    else push_closed<3, true>(closed, grid, block, s, a, rows, pass);
   } else {
-    if (dim == 2) hipLaunchKernelGGL((open_push_kernel<2, false>), grid, block, 0, s, a, rows, pass);
-    else hipLaunchKernelGGL((open_push_kernel<3, false>), grid, block, 0, s, a, rows, pass);
+    if (dim == 2) push_closed<2, false>(closed, grid, block, s, a, rows, pass);
+    else push_closed<3, false>(closed, grid, block, s, a, rows, pass);
   }
   return hipGetLastError();
 }

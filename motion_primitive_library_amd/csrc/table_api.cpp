@@ -20,6 +20,7 @@ struct mplx_table {
   DevBuf slots, hash, g, pred, pact, state, pick, ctl;
   DevBuf query;                      // per node its query: tables with Q > 1 only
   DevBuf scratch;                    // per-call passes (ent, mark, tile counts, seed hashes); grows on demand
+  DevBuf replan;                     // the passes of a rebase (replan_kernel.hip), for `cap` nodes; allocated by the first rebase
   mplx::TableMirror *mirror = nullptr;  // pinned
   uint32_t epoch = 0;                // calls since the last clear
   int64_t bound = 0;                 // upper bound of n_nodes: the mirror's value at the last wait + what the calls queued since can add
@@ -51,7 +52,7 @@ mplx::TableArgs table_args(const mplx_table *t) {
 }
 
 void release_table(mplx_table *t) {
-  for (DevBuf *b : {&t->slots, &t->hash, &t->g, &t->pred, &t->pact, &t->state, &t->pick, &t->ctl, &t->query, &t->scratch}) release(*b);
+  for (DevBuf *b : {&t->slots, &t->hash, &t->g, &t->pred, &t->pact, &t->state, &t->pick, &t->ctl, &t->query, &t->scratch, &t->replan}) release(*b);
   if (t->mirror) (void)hipHostFree(t->mirror);
   delete t;
 }
@@ -125,6 +126,41 @@ int table_open_args(mplx_table *t, const char *who, mplx_ctx **c, mplx::OpenArgs
 }
 
 void table_observe(mplx_table *t) { observe(t); }
+
+int table_replan_args(mplx_table *t, const char *who, bool scratch, mplx_ctx **c, mplx::ReplanArgs *a) {
+  *c = t->c;
+  if (int rc = usable(t, who)) return rc;
+  a->n_queries = t->Q;
+  a->n_bound = t->bound;
+  if (!scratch) return MPLX_OK;
+  const size_t cap = (size_t)t->cap, tiles = (cap + mplx::kTableTile - 1) / mplx::kTableTile;
+  StageLayout l;  // (only the carving: the table's own scratch, not the arena)
+  const size_t o_bad = l.add(cap), o_d0 = l.add(cap), o_d1 = l.add(cap), o_j0 = l.add(cap * 4), o_j1 = l.add(cap * 4), o_mark = l.add(cap),
+               o_tot = l.add(tiles * 4), o_cnt = l.add(sizeof(mplx::ReplanResult));
+  if (int rc = ensure(t->c, t->replan, l.total)) return rc;
+  char *base = (char *)t->replan.p;
+  a->bad = (uint8_t *)(base + o_bad);
+  a->dec[0] = (uint8_t *)(base + o_d0);
+  a->dec[1] = (uint8_t *)(base + o_d1);
+  a->jump[0] = (int32_t *)(base + o_j0);
+  a->jump[1] = (int32_t *)(base + o_j1);
+  a->mark = (uint8_t *)(base + o_mark);
+  a->tot = (uint32_t *)(base + o_tot);
+  a->counters = (mplx::ReplanResult *)(base + o_cnt);
+  a->ctl = (mplx::TableCtl *)t->ctl.p;
+  a->mirror = t->mirror;
+  a->hash = (const uint64_t *)t->hash.p;
+  a->g = (unsigned long long *)t->g.p;
+  a->pred = (int32_t *)t->pred.p;
+  a->pred_action = (int32_t *)t->pact.p;
+  a->state = (const double *)t->state.p;
+  a->query = (const int32_t *)t->query.p;
+  a->n_queries = t->Q;
+  a->n_fields = t->F;
+  a->cap = t->cap;
+  a->n_bound = t->bound;
+  return MPLX_OK;
+}
 
 }  // namespace mplx_detail
 

@@ -394,6 +394,11 @@ hipError_t launch_table_relax(const TableArgs &a, hipStream_t s) {
   return hipGetLastError();
 }
 
+hipError_t launch_table_scan_frontier(const TableArgs &a, hipStream_t s) {
+  hipLaunchKernelGGL(table_scan_kernel<1>, dim3(1), dim3(1024), 0, s, a);
+  return hipGetLastError();
+}
+
 hipError_t launch_table_clear(const TableArgs &a, hipStream_t s) {
   if (hipError_t e = hipMemsetAsync(a.slots, 0xff, (a.n_slots + (uint64_t)a.n_queries) * sizeof(TableSlot), s)) return e;
   hipLaunchKernelGGL(table_clear_kernel, dim3(1), dim3(1), 0, s, a);

@@ -1328,7 +1328,7 @@ class EnvMap:
 
     def search(self, start, goal_row, eps=1.0, delta=None, g_max=float("inf"), max_rounds=None, max_expand=None,
                capacity=1 << 16, max_frontier=None, lists_stride=None, sight=True, tol_pos=0.5, tol_vel=-1.0, tol_acc=-1.0,
-               tol_yaw=-1.0, w=None, v_max=None):
+               tol_yaw=-1.0, w=None, v_max=None, start_g=0.0):
         """A goal-directed search from `start` (one 4D+2 state) to the goal region of `goal_row` that stays on the
         device: set_goal, seed, push; then per round one select (the round's only read-back, 48 bytes), and while it
         selects: expand the selection, relax its lists against the table, push the nodes whose g fell.  Keys are
@@ -1338,23 +1338,26 @@ class EnvMap:
         sight: a goal-region node also needs a free line of sight to the goal (env_map::is_goal's ray trace).
         Nodes with g > g_max are never created.  Lists and the selection frontier are allocated for max_frontier nodes
         (default: capacity); a larger selection is taken in id order, the rest stays open.  Returns a SearchResult
-        (search.py) that owns the table and the open set.  A table that ran out of nodes or probe length raises."""
+        (search.py) that owns the table and the open set.  A table that ran out of nodes or probe length raises.
+        start_g: the cost-to-come the start is seeded with (what a SearchResult.replan from a node with that g is
+        compared against).  result.replan(...) plans again on the same table after a move or a map edit."""
         from .search import run_search
         return run_search(self, start, goal_row, eps, delta, g_max, max_rounds, max_expand, capacity, max_frontier,
-                          lists_stride, sight, tol_pos, tol_vel, tol_acc, tol_yaw, w, v_max)
+                          lists_stride, sight, tol_pos, tol_vel, tol_acc, tol_yaw, w, v_max, start_g)
 
     def search_many(self, starts, goal_rows, eps=1.0, delta=None, g_max=float("inf"), max_rounds=None, max_expand=None,
                     capacity=1 << 16, max_frontier=None, lists_stride=None, sight=True, tol_pos=0.5, tol_vel=-1.0,
-                    tol_acc=-1.0, tol_yaw=-1.0, w=None, v_max=None):
+                    tol_acc=-1.0, tol_yaw=-1.0, w=None, v_max=None, start_g=0.0):
         """Q searches of EnvMap.search at once, sharing every launch of a round (include/mplx_multi.h): starts
         [4D+2][Q], goal_rows [Q][4D+2], query q from starts[:, q] to the goal region of goal_rows[q].  One table of
         `capacity` nodes and one open set hold all of them; a round selects, expands, relaxes and pushes the union of
         what the queries select, and reads Q results back.  The loop goes on while any query selects; max_expand counts
         all queries together.  As long as no selection is cut at max_frontier every query does exactly what its own
-        EnvMap.search does.  Returns a MultiSearchResult (search.py) that owns the table and the open set."""
+        EnvMap.search does.  Returns a MultiSearchResult (search.py) that owns the table and the open set.  start_g: one
+        cost-to-come for every start, or [Q]."""
         from .search import run_search_many
         return run_search_many(self, starts, goal_rows, eps, delta, g_max, max_rounds, max_expand, capacity, max_frontier,
-                               lists_stride, sight, tol_pos, tol_vel, tol_acc, tol_yaw, w, v_max)
+                               lists_stride, sight, tol_pos, tol_vel, tol_acc, tol_yaw, w, v_max, start_g)
 
     def synchronize(self):
         _abi.check(self._ctx, _abi.lib().mplx_synchronize(self._ctx))

@@ -60,12 +60,14 @@ class OpenSet:
     def clear(self):
         self._check(_abi.lib().mplx_open_clear(self._open))
 
-    def push(self, frontier, n_max=None, eps=1.0, sight=False):
+    def push(self, frontier, n_max=None, eps=1.0, sight=False, closed=False):
         """mplx_open_push_device: the first min(count on the device, n_max, capacity) rows of `frontier` become open
-        with f = g + eps * h.  Asynchronous."""
+        with f = g + eps * h.  closed: mplx_open_push_closed_device (include/mplx_replan.h) -- key and goal bit are
+        set, the nodes stay closed.  Asynchronous."""
         f = frontier.c_struct()
         n = frontier.capacity if n_max is None else int(n_max)
-        self._check(_abi.lib().mplx_open_push_device(self._open, C.byref(f), n, float(eps), 1 if sight else 0))
+        fn = _abi.lib().mplx_open_push_closed_device if closed else _abi.lib().mplx_open_push_device
+        self._check(fn(self._open, C.byref(f), n, float(eps), 1 if sight else 0))
 
     def select(self, delta, frontier, want_result=True, d_result=None):
         """mplx_open_select_device into `frontier`.  Returns the result as a dict (one synchronisation), or None with
@@ -131,7 +133,8 @@ class SearchResult:
     (inf unless FOUND); rounds = relax calls made; expanded = nodes expanded (a re-opened node counts again); table and
     open: the NodeTable and OpenSet, owned by the result -- free() it (or let it go) before the EnvMap is closed."""
 
-    def __init__(self, status, last, table, open_set, rounds, expanded):
+    def __init__(self, status, last, table, open_set, rounds, expanded, env=None, params=None):
+        self._env, self._params = env, params  # what replan() runs again with
         self.status = status
         self.found = status == FOUND
         self.goal_id = last["goal_id"] if self.found else -1
@@ -150,60 +153,107 @@ class SearchResult:
         ids, act = self.table.path(self.goal_id)
         return self.table.state_of(ids[0]), act
 
+    def replan(self, root=None, advance=None, goal_row=None, check_edges=True):
+        """Plans again on the table of this search after the robot has moved and / or the map was edited
+        (include/mplx_replan.h), with the parameters of the search that made this result.  root: the
+        node id the robot is at (default: the seed); advance=k: ids[k] of the chain path() follows.  Nodes that still
+        hang below the root by edges valid on the map as it is now keep their g -- costs go on being measured from the
+        original start --, all of them are expanded once in a forced round (in chunks of max_frontier rows), then the
+        loop of EnvMap.search finishes.  goal_row: a new goal; keys and goal bits of the kept nodes are recomputed
+        anyway.  Returns a new SearchResult that owns the table and the open set; this one no longer does."""
+        if self.table is None or self._params is None:
+            raise RuntimeError("replan: this result does not own a table (it was replanned or freed)")
+        if root is not None and advance is not None:
+            raise ValueError("replan: give root or advance, not both")
+        if advance is not None:
+            if not self.found:
+                raise RuntimeError("replan: advance needs a path (status %s)" % STATUS_NAMES[self.status])
+            root = int(self.table.path(self.goal_id)[0][int(advance)])
+        return run_replan(self, False, [-1 if root is None else int(root)], goal_row, check_edges)
+
     def free(self):
-        self.open.free()
-        self.table.free()
+        if self.open is not None:
+            self.open.free()
+        if self.table is not None:
+            self.table.free()
+        self.open = self.table = None
 
     def __repr__(self):
         return "SearchResult(%s, cost=%r, rounds=%d, expanded=%d)" % (STATUS_NAMES[self.status], self.cost, self.rounds, self.expanded)
 
 
-def run_search(env, start, goal_row, eps, delta, g_max, max_rounds, max_expand, capacity, max_frontier, lists_stride, sight,
-               tol_pos, tol_vel, tol_acc, tol_yaw, w, v_max):
-    env._flush()
+def _table_check(tab, who, where):
+    status = tab.stats()[1]  # (the stream is idle: no copy, no wait)
+    if status:
+        raise RuntimeError("%s: table status %d %s (1 nodes full, 2 probe full, 4 frontier full): raise capacity"
+                           % (who, status, where))
+
+
+def _search_loop(env, who, multi, tab, opn, sel, imp, lists, prm, total, rounds, expanded):
+    """The rounds of a search from its first select on: select (the round's only read-back), and while any query
+    selects: expand the selection, relax its lists against the table, push the nodes whose g fell.  rounds / expanded:
+    per query (one entry for a table of one query), counted on from what they hold.  Returns (status per query, the
+    results of the last select, relax calls made)."""
+    eps, delta, g_max, sight = prm["eps"], prm["delta"], prm["g_max"], prm["sight"]
+    max_rounds, max_expand = prm["max_rounds"], prm["max_expand"]
+    limit = None
+    while True:
+        try:
+            res = opn.select_many(delta, sel) if multi else [opn.select(delta, sel)]
+        except _abi.MplxError as e:
+            if e.code != _abi.ERR_STATE:
+                raise
+            _table_check(tab, who, "in round %d" % total)
+            raise
+        n = sum(r["count"] for r in res)
+        if not any(r["status"] == SELECTED for r in res):
+            break
+        limit = MAX_ROUNDS if (max_rounds is not None and total >= max_rounds) else \
+            MAX_EXPAND if (max_expand is not None and sum(expanded) + n > max_expand) else None
+        if limit is not None:
+            opn.push(sel, n_max=n, eps=eps, sight=sight)  # the selection is open again: same g, same keys
+            break
+        env.expand_lists_resident(sel, lists, n_nodes=n)
+        tab.relax(lists, sel.id, sel.g, g_max, frontier=imp, n_nodes=n, want_count=False)
+        opn.push(imp, n_max=n * lists.stride, eps=eps, sight=sight)
+        total += 1
+        for q, r in enumerate(res):
+            if r["status"] == SELECTED:
+                rounds[q] += 1
+                expanded[q] += r["count"]
+    status = [limit if (r["status"] == SELECTED and limit is not None) else r["status"] for r in res]
+    return status, res, total
+
+
+def _params(env, eps, delta, g_max, max_rounds, max_expand, capacity, max_frontier, lists_stride, sight, goal_kw):
     if delta is None:
         delta = float(env._p.w) * float(env._p.dt)
-    fcap = int(capacity if max_frontier is None else max_frontier)
-    env.set_goal(goal_row, w=w, v_max=v_max, tol_pos=tol_pos, tol_vel=tol_vel, tol_acc=tol_acc, tol_yaw=tol_yaw)
+    return {"eps": eps, "delta": delta, "g_max": g_max, "max_rounds": max_rounds, "max_expand": max_expand,
+            "capacity": int(capacity), "fcap": int(capacity if max_frontier is None else max_frontier),
+            "lists_stride": lists_stride, "sight": sight, "goal_kw": goal_kw}
+
+
+def run_search(env, start, goal_row, eps, delta, g_max, max_rounds, max_expand, capacity, max_frontier, lists_stride, sight,
+               tol_pos, tol_vel, tol_acc, tol_yaw, w, v_max, start_g=0.0):
+    env._flush()
+    prm = _params(env, eps, delta, g_max, max_rounds, max_expand, capacity, max_frontier, lists_stride, sight,
+                  dict(w=w, v_max=v_max, tol_pos=tol_pos, tol_vel=tol_vel, tol_acc=tol_acc, tol_yaw=tol_yaw))
+    prm["goal_row"] = np.array(goal_row, dtype=np.float64)
+    fcap = prm["fcap"]
+    env.set_goal(goal_row, **prm["goal_kw"])
     tab = NodeTable(env, capacity)
     opn = sel = imp = lists = None
     try:
         opn = OpenSet(env, tab)
         sel, imp = TableFrontier(env, fcap), TableFrontier(env, int(capacity))  # (no more nodes can improve than exist)
         lists = env.alloc_lists(fcap, want_state=True, stride=lists_stride)
-
-        def check(where):
-            status = tab.stats()[1]  # (the stream is idle: no copy, no wait)
-            if status:
-                raise RuntimeError("search: table status %d %s (1 nodes full, 2 probe full, 4 frontier full): raise capacity"
-                                   % (status, where))
-        count = tab.seed(start, frontier=imp)
-        check("after seeding")
+        # (g = None is the call without a g row: the bytes of a search before start_g existed)
+        count = tab.seed(start, None if (start_g is None or float(start_g) == 0.0) else float(start_g), frontier=imp)
+        _table_check(tab, "search", "after seeding")
         opn.push(imp, n_max=count, eps=eps, sight=sight)
-        rounds = expanded = 0
-        while True:
-            try:
-                r = opn.select(delta, sel)
-            except _abi.MplxError as e:
-                if e.code != _abi.ERR_STATE:
-                    raise
-                check("in round %d" % rounds)
-                raise
-            status, n = r["status"], r["count"]
-            if status != SELECTED:
-                break
-            limit = MAX_ROUNDS if (max_rounds is not None and rounds >= max_rounds) else \
-                MAX_EXPAND if (max_expand is not None and expanded + n > max_expand) else None
-            if limit is not None:
-                opn.push(sel, n_max=n, eps=eps, sight=sight)  # the selection is open again: same g, same keys
-                status = limit
-                break
-            env.expand_lists_resident(sel, lists, n_nodes=n)
-            tab.relax(lists, sel.id, sel.g, g_max, frontier=imp, n_nodes=n, want_count=False)
-            opn.push(imp, n_max=n * lists.stride, eps=eps, sight=sight)
-            rounds += 1
-            expanded += n
-        return SearchResult(status, r, tab, opn, rounds, expanded)
+        rounds, expanded = [0], [0]
+        status, res, total = _search_loop(env, "search", False, tab, opn, sel, imp, lists, prm, 0, rounds, expanded)
+        return SearchResult(status[0], res[0], tab, opn, total, expanded[0], env, prm)
     except Exception:
         if opn is not None:
             opn.free()
@@ -221,7 +271,8 @@ class MultiSearchResult:
     expanded[q]; total_rounds = relax calls made.  last_select: the Q results of the last select.  table and open are
     owned by the result: free() it (or let it go) before the EnvMap is closed."""
 
-    def __init__(self, status, last, table, open_set, rounds, expanded, total_rounds):
+    def __init__(self, status, last, table, open_set, rounds, expanded, total_rounds, env=None, params=None):
+        self._env, self._params = env, params  # what replan() runs again with
         self.n_queries = len(status)
         self.status = list(status)
         self.found = [st == FOUND for st in status]
@@ -241,9 +292,30 @@ class MultiSearchResult:
         ids, act = self.table.path(self.goal_id[q])
         return self.table.state_of(ids[0]), act
 
+    def replan(self, roots=None, advance=None, goal_rows=None, check_edges=True):
+        """SearchResult.replan for Q queries at once: roots [Q] (node ids; -1 or None: that query's seed), or advance
+        (one k for all or [Q]; a query without a path keeps its seed), goal_rows [Q][4D+2] or None.  Every launch of
+        the rebase, of the forced round and of the rounds after it is shared by the queries.  Returns a new
+        MultiSearchResult that owns the table and the open set; this one no longer does."""
+        if self.table is None or self._params is None:
+            raise RuntimeError("replan: this result does not own a table (it was replanned or freed)")
+        if roots is not None and advance is not None:
+            raise ValueError("replan: give roots or advance, not both")
+        Q = self.n_queries
+        r = [-1] * Q
+        if roots is not None:
+            r = [-1 if x is None else int(x) for x in np.broadcast_to(np.asarray(roots, dtype=object), (Q,))]
+        if advance is not None:
+            ks = np.broadcast_to(np.asarray(advance, dtype=np.int64), (Q,))
+            r = [int(self.table.path(self.goal_id[q])[0][int(ks[q])]) if self.found[q] else -1 for q in range(Q)]
+        return run_replan(self, True, r, goal_rows, check_edges)
+
     def free(self):
-        self.open.free()
-        self.table.free()
+        if self.open is not None:
+            self.open.free()
+        if self.table is not None:
+            self.table.free()
+        self.open = self.table = None
 
     def __repr__(self):
         return "MultiSearchResult(%s, rounds=%d, expanded=%d)" % (
@@ -251,7 +323,7 @@ class MultiSearchResult:
 
 
 def run_search_many(env, starts, goal_rows, eps, delta, g_max, max_rounds, max_expand, capacity, max_frontier, lists_stride,
-                    sight, tol_pos, tol_vel, tol_acc, tol_yaw, w, v_max):
+                    sight, tol_pos, tol_vel, tol_acc, tol_yaw, w, v_max, start_g=0.0):
     env._flush()
     starts = np.ascontiguousarray(starts, dtype=np.float64)
     goal_rows = np.ascontiguousarray(goal_rows, dtype=np.float64)
@@ -260,54 +332,25 @@ def run_search_many(env, starts, goal_rows, eps, delta, g_max, max_rounds, max_e
     Q = starts.shape[1]
     if Q < 1:
         raise ValueError("search_many: no query")
-    if delta is None:
-        delta = float(env._p.w) * float(env._p.dt)
-    fcap = int(capacity if max_frontier is None else max_frontier)
+    prm = _params(env, eps, delta, g_max, max_rounds, max_expand, capacity, max_frontier, lists_stride, sight,
+                  dict(w=w, v_max=v_max, tol_pos=tol_pos, tol_vel=tol_vel, tol_acc=tol_acc, tol_yaw=tol_yaw))
+    fcap = prm["fcap"]
+    g0 = None if start_g is None else np.broadcast_to(np.asarray(start_g, dtype=np.float64), (Q,))
+    if g0 is not None and not g0.any():
+        g0 = None  # (the call without a g row: the bytes of a search before start_g existed)
     tab = NodeTable(env, capacity, n_queries=Q)
     opn = sel = imp = lists = None
     try:
         opn = OpenSet(env, tab)
-        opn.set_goals(goal_rows, w=w, v_max=v_max, tol_pos=tol_pos, tol_vel=tol_vel, tol_acc=tol_acc, tol_yaw=tol_yaw)
+        opn.set_goals(goal_rows, **prm["goal_kw"])
         sel, imp = TableFrontier(env, fcap), TableFrontier(env, int(capacity))  # (no more nodes can improve than exist)
         lists = env.alloc_lists(fcap, want_state=True, stride=lists_stride)
-
-        def check(where):
-            status = tab.stats()[1]  # (the stream is idle: no copy, no wait)
-            if status:
-                raise RuntimeError("search_many: table status %d %s (1 nodes full, 2 probe full, 4 frontier full): raise capacity"
-                                   % (status, where))
-        count = tab.seed(starts, frontier=imp, query=np.arange(Q, dtype=np.int32))
-        check("after seeding")
+        count = tab.seed(starts, g0, frontier=imp, query=np.arange(Q, dtype=np.int32))
+        _table_check(tab, "search_many", "after seeding")
         opn.push(imp, n_max=count, eps=eps, sight=sight)
-        total = 0
         rounds, expanded = [0] * Q, [0] * Q
-        limit = None
-        while True:
-            try:
-                res = opn.select_many(delta, sel)
-            except _abi.MplxError as e:
-                if e.code != _abi.ERR_STATE:
-                    raise
-                check("in round %d" % total)
-                raise
-            n = sum(r["count"] for r in res)
-            if not any(r["status"] == SELECTED for r in res):
-                break
-            limit = MAX_ROUNDS if (max_rounds is not None and total >= max_rounds) else \
-                MAX_EXPAND if (max_expand is not None and sum(expanded) + n > max_expand) else None
-            if limit is not None:
-                opn.push(sel, n_max=n, eps=eps, sight=sight)  # the selection is open again: same g, same keys
-                break
-            env.expand_lists_resident(sel, lists, n_nodes=n)
-            tab.relax(lists, sel.id, sel.g, g_max, frontier=imp, n_nodes=n, want_count=False)
-            opn.push(imp, n_max=n * lists.stride, eps=eps, sight=sight)
-            total += 1
-            for q, r in enumerate(res):
-                if r["status"] == SELECTED:
-                    rounds[q] += 1
-                    expanded[q] += r["count"]
-        status = [limit if (r["status"] == SELECTED and limit is not None) else r["status"] for r in res]
-        return MultiSearchResult(status, res, tab, opn, rounds, expanded, total)
+        status, res, total = _search_loop(env, "search_many", True, tab, opn, sel, imp, lists, prm, 0, rounds, expanded)
+        return MultiSearchResult(status, res, tab, opn, rounds, expanded, total, env, prm)
     except Exception:
         if opn is not None:
             opn.free()
@@ -315,5 +358,67 @@ def run_search_many(env, starts, goal_rows, eps, delta, g_max, max_rounds, max_e
         raise
     finally:
         for b in (sel, imp, lists):
+            if b is not None:
+                b.free()
+
+
+def run_replan(old, multi, roots, goal_rows, check_edges):
+    """SearchResult.replan / MultiSearchResult.replan: rebase into a frontier of the table's capacity, clear the open
+    set, push the kept nodes closed, expand all of them in chunks of max_frontier rows (the forced round), then the
+    loop of the search.  The forced chunks count as rounds and expansions."""
+    env, prm, tab, opn = old._env, old._params, old.table, old.open
+    who = "replan"
+    env._flush()
+    eps, g_max, sight, fcap, capacity = prm["eps"], prm["g_max"], prm["sight"], prm["fcap"], prm["capacity"]
+    Q = tab.n_queries
+    if goal_rows is not None:
+        if multi:
+            opn.set_goals(goal_rows, **prm["goal_kw"])
+        else:
+            prm = dict(prm, goal_row=np.array(goal_rows, dtype=np.float64))
+    if not multi:
+        env.set_goal(prm["goal_row"], **prm["goal_kw"])  # (the context's goal may have been moved since the search)
+    kept = sel = imp = lists = None
+    try:
+        kept, sel, imp = TableFrontier(env, capacity), TableFrontier(env, fcap), TableFrontier(env, capacity)
+        lists = env.alloc_lists(fcap, want_state=True, stride=prm["lists_stride"])
+        info = tab.rebase(roots=roots, check_edges=check_edges, frontier=kept) if multi else \
+            tab.rebase(root=roots[0], check_edges=check_edges, frontier=kept)
+        _table_check(tab, who, "after the rebase")
+        n_kept = info["n_kept"]
+        opn.clear()
+        opn.push(kept, n_max=n_kept, eps=eps, sight=sight, closed=True)
+        rounds, expanded = [0] * Q, [0] * Q
+        query = None
+        if multi and n_kept:  # whose the kept rows are: the forced chunks are counted per query
+            query = tab._read(tab.query_ptr(), np.int32, tab.stats()[0])[kept.id.download(np.int32, (n_kept,))] if tab.query_ptr() \
+                else np.zeros(n_kept, np.int32)
+        total = 0
+        for first in range(0, n_kept, max(fcap, 1)):
+            n = min(fcap, n_kept - first)
+            rows = kept.rows(first, n)
+            env.expand_lists_resident(rows, lists, n_nodes=n)
+            tab.relax(lists, rows.id, rows.g, g_max, frontier=imp, n_nodes=n, want_count=False)
+            opn.push(imp, n_max=n * lists.stride, eps=eps, sight=sight)
+            total += 1
+            if query is None:
+                rounds[0] += 1
+                expanded[0] += n
+            else:
+                per = np.bincount(query[first:first + n], minlength=Q)
+                for q in range(Q):
+                    if per[q]:
+                        rounds[q] += 1
+                        expanded[q] += int(per[q])
+        status, res, total = _search_loop(env, who, multi, tab, opn, sel, imp, lists, prm, total, rounds, expanded)
+        if multi:
+            new = MultiSearchResult(status, res, tab, opn, rounds, expanded, total, env, prm)
+        else:
+            new = SearchResult(status[0], res[0], tab, opn, total, expanded[0], env, prm)
+        new.rebase_info = info
+        old.table = old.open = None  # the new result owns them
+        return new
+    finally:
+        for b in (kept, sel, imp, lists):
             if b is not None:
                 b.free()

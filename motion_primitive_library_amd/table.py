@@ -62,11 +62,34 @@ class TableFrontier:
         for b in (self.id, self.g, self.state, self.count):
             b.free()
 
+    def rows(self, first, n):
+        """Rows [first, first + n) as the `frontier` of EnvMap.expand_lists_resident and, through .id / .g, as the
+        parent_id / parent_g of NodeTable.relax: a view, valid while this frontier is."""
+        first, n = int(first), int(n)
+        if first < 0 or n < 0 or first + n > self.state_stride:
+            raise ValueError("rows [%d, %d) of a frontier of %d" % (first, first + n, self.state_stride))
+        return _FrontierRows(self, first)
+
+
+class _Ptr:
+    def __init__(self, ptr):
+        self.ptr = ptr
+
+
+class _FrontierRows:
+    def __init__(self, frontier, first):
+        self._frontier = frontier  # (kept alive)
+        self.id, self.g = _Ptr(frontier.id.ptr + 4 * first), _Ptr(frontier.g.ptr + 8 * first)
+        self.ptr = frontier.state.ptr + 8 * first
+        self.n_nodes = frontier.state_stride
+
 
 class NodeTable:
     """mplx_table of an EnvMap's context.  Free it (or let it go) before the EnvMap is closed.  n_queries > 1: a table
     of that many queries (include/mplx_multi.h): a node is a (query, hash) pair, slots_log2 sizes one query's region of
     the hash table, seed / find take the query of every state / hash."""
+
+    _roots = None  # device copy of the roots of a rebase, allocated by the first one that needs it
 
     def __init__(self, env, capacity, slots_log2=0, n_queries=1):
         self._env = env
@@ -86,9 +109,12 @@ class NodeTable:
         _abi.check(self._env._ctx, rc)
 
     def free(self):
-        if self._tab and self._env._ctx:
-            _abi.lib().mplx_table_destroy(self._tab)
-        self._tab = None
+        tab, roots = self._tab, self._roots
+        self._tab, self._roots = None, None  # (first: whatever happens below, nothing is destroyed twice)
+        if tab and self._env._ctx:
+            _abi.lib().mplx_table_destroy(tab)
+            if roots is not None:
+                roots.free()
 
     def __del__(self):
         try:
@@ -147,6 +173,32 @@ class NodeTable:
             self._tab, C.byref(s), n, _device_ptr(parent_id), _device_ptr(parent_g), float(g_max), C.byref(f),
             _device_ptr(entry_id) if entry_id is not None else None, C.byref(cnt) if want_count else None))
         return int(cnt.value) if want_count else None
+
+    def rebase(self, root=-1, roots=None, check_edges=True, frontier=None, want_result=True):
+        """mplx_table_rebase_device (include/mplx_replan.h): keeps the nodes that hang below `root` (a node id; -1: the
+        seeds) by edges that still hold on the map the context has now, resets every other node to "never reached" and
+        writes the kept nodes to `frontier` in id order.  roots: one root per query ([Q], -1 = that query's seeds;
+        mplx_table_rebase_multi_device) -- a table of several queries needs it.  check_edges=False keeps every edge.
+        Returns {"n_kept", "n_bad_edges", "n_roots"} (one synchronisation) or, with want_result=False, None -- the call
+        is then asynchronous."""
+        if frontier is None:
+            raise ValueError("rebase needs a frontier to write (EnvMap.alloc_table_frontier)")
+        self._env._flush()
+        f = frontier.c_struct()
+        r = _abi.RebaseResult()
+        rp = C.byref(r) if want_result else None
+        if roots is None:
+            self._check(_abi.lib().mplx_table_rebase_device(self._tab, int(root), 1 if check_edges else 0, C.byref(f), None, rp))
+        else:
+            h = np.ascontiguousarray(np.broadcast_to(np.asarray(roots, dtype=np.int32), (self.n_queries,)))
+            if self._roots is None:
+                self._roots = DeviceArray(self._env, 4 * self.n_queries)
+            self._roots.upload(h)
+            self._check(_abi.lib().mplx_table_rebase_multi_device(self._tab, self._roots.ptr, 1 if check_edges else 0, C.byref(f),
+                                                                  None, rp))
+        if not want_result:
+            return None
+        return {"n_kept": int(r.n_kept), "n_bad_edges": int(r.n_bad_edges), "n_roots": int(r.n_roots)}
 
     def find(self, hashes, query=None):
         """Node id of every hash (with query: of every (query, hash) pair; [n] or one for all), -1 for one the table
