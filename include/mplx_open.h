@@ -49,7 +49,8 @@
  * without bound.
  *
  * The open set of a table with several queries has one goal and one result per query: include/mplx_multi.h.  The push
- * that sets keys and goal bits without opening the nodes (after a rebase of the table): include/mplx_replan.h.      */
+ * that sets keys and goal bits without opening the nodes (after a rebase of the table): include/mplx_replan.h.  The
+ * heuristic that follows a prior trajectory per query: include/mplx_prior.h.                                         */
 #ifndef MPLX_OPEN_H
 #define MPLX_OPEN_H
 

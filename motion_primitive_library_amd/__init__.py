@@ -14,11 +14,11 @@ from .env import (ACC, ACCxYAW, JRK, JRKxYAW, SNP, SNPxYAW, VEL, VELxYAW, SLOT_B
                   Rollouts, Slots, Waypoint, lists_from_dense, pack_host_lists)
 
 from .table import NodeTable, TableFrontier
-from .search import MultiSearchResult, OpenSet, SearchResult
+from .search import MultiSearchResult, OpenSet, Prior, SearchResult
 from .planner import MapPlanner, MapUtil, Trajectory
 
 __all__ = ["MapPlanner", "MapUtil", "Trajectory", "EnvMap", "Waypoint", "Slots", "Lists", "lists_from_dense", "PackedLists", "pack_host_lists", "DeviceArray", "workloads", "VEL", "ACC", "JRK", "SNP", "VELxYAW",
            "ACCxYAW", "JRKxYAW", "SNPxYAW", "SLOT_SKIP_SAME", "SLOT_FINITE", "SLOT_BLOCKED", "SLOT_SKIP_DYN",
            "ROLLOUT_BAD_ACTION", "ROLLOUT_HEADING_BAND", "Rollouts", "Rays", "RAY_LEFT_MAP", "RAY_HIT", "RAY_BAD", "RAY_TRUNCATED",
            "FLAG_GOAL_BLOCKED", "TRAJ_EMPTY", "TRAJ_BAD_ACTION", "TRAJ_BAD", "TRAJ_COMMAND", "TRAJ_WAYPOINT", "TrajInfo",
-           "TrajSamples", "TrajTraverse", "NodeTable", "TableFrontier", "OpenSet", "SearchResult", "MultiSearchResult"]
+           "TrajSamples", "TrajTraverse", "NodeTable", "TableFrontier", "OpenSet", "SearchResult", "MultiSearchResult", "Prior"]

@@ -61,6 +61,8 @@ MULTI_SYMBOLS = ["mplx_table_create_multi", "mplx_table_query_of", "mplx_table_s
                  "mplx_table_find_multi", "mplx_open_set_goals", "mplx_open_select_multi_device"]
 # ... and the ones include/mplx_replan.h declares (re-root and repair a table after a map edit)
 REPLAN_SYMBOLS = ["mplx_table_rebase_device", "mplx_table_rebase_multi_device", "mplx_open_push_closed_device"]
+# ... and the ones include/mplx_prior.h declares (prior-trajectory guidance of an open set)
+PRIOR_SYMBOLS = ["mplx_open_set_priors_device", "mplx_open_clear_priors", "mplx_open_prior_view_of", "mplx_planner_prior_table"]
 
 ROUTE_AUTO, ROUTE_DENSE, ROUTE_TILE, ROUTE_GRID = 0, 1, 2, 3
 
@@ -143,6 +145,19 @@ class OpenView(C.Structure):
 class OpenResult(C.Structure):
     _fields_ = [("status", C.c_int32), ("goal_id", C.c_int32), ("count", C.c_int64), ("n_open", C.c_int64),
                 ("f_min", C.c_double), ("goal_f", C.c_double), ("goal_g", C.c_double)]
+
+
+class PriorSource(C.Structure):
+    _fields_ = [("control", C.c_int32), ("nU", C.c_int32), ("udim", C.c_int32), ("U", C.c_void_p), ("dt", C.c_double)]
+
+
+class PriorInfo(C.Structure):
+    _fields_ = [("status", C.c_void_p), ("n_steps", C.c_void_p)]
+
+
+class PriorView(C.Structure):
+    _fields_ = [("n_steps", C.c_void_p), ("pos", C.c_void_p), ("togo", C.c_void_p), ("goal_row", C.c_void_p),
+                ("goal_hash", C.c_void_p), ("step_capacity", C.c_int64)]
 
 
 class RebaseResult(C.Structure):
@@ -347,8 +362,12 @@ def lib():
         "mplx_table_rebase_device": (C.c_int, [vp, i32, i32, C.POINTER(TableFrontier), vp, C.POINTER(RebaseResult)]),
         "mplx_table_rebase_multi_device": (C.c_int, [vp, vp, i32, C.POINTER(TableFrontier), vp, C.POINTER(RebaseResult)]),
         "mplx_open_push_closed_device": (C.c_int, [vp, C.POINTER(TableFrontier), i64, dbl, i32]),
+        "mplx_open_set_priors_device": (C.c_int, [vp, C.POINTER(PriorSource), C.POINTER(TrajSet), C.POINTER(PriorInfo)]),
+        "mplx_open_clear_priors": (C.c_int, [vp]),
+        "mplx_open_prior_view_of": (C.c_int, [vp, C.POINTER(PriorView)]),
+        "mplx_planner_prior_table": (C.c_int, [vp, vp, vp, i32, C.POINTER(i32), vp, C.POINTER(i32)]),
     }
-    for name in SYMBOLS + MAP_UTIL_SYMBOLS + ROLLOUT_SYMBOLS + RAY_SYMBOLS + TRAJ_SYMBOLS + TABLE_SYMBOLS + OPEN_SYMBOLS + MULTI_SYMBOLS + REPLAN_SYMBOLS:
+    for name in SYMBOLS + MAP_UTIL_SYMBOLS + ROLLOUT_SYMBOLS + RAY_SYMBOLS + TRAJ_SYMBOLS + TABLE_SYMBOLS + OPEN_SYMBOLS + MULTI_SYMBOLS + REPLAN_SYMBOLS + PRIOR_SYMBOLS:
         fn = getattr(L, name)  # AttributeError if the library does not export it
         fn.restype, fn.argtypes = sig[name]
     _lib = L

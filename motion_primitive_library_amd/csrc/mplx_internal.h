@@ -494,6 +494,29 @@ hipError_t launch_traj_chain(int dim, int control, const TrajArgs &a, hipStream_
 hipError_t launch_traj_sample(int dim, int form, const TrajArgs &a, hipStream_t s);
 hipError_t launch_traj_traverse(int dim, int lanes, const TrajArgs &a, hipStream_t s);  // lanes in {4, 16, 64}
 
+// The prior table of an open set (traj_kernel.hip, open_api.cpp; include/mplx_prior.h), built on the segment table of a
+// chain launch with the prior's controls and the `cost` of a traverse launch.
+struct PriorArgs {
+  TrajArgs traj;           // env (the searching context's but U / nU / udim / dt: the prior's), n_traj, the segment table
+  double dt;               // the searching context's dt
+  const double *traverse;  // [n_traj] cost of launch_traj_traverse
+  // scratch: per sample of a trajectory its cell index and its term of the potential sum
+  int32_t *s_idx;          // [n_traj][s_cap]
+  double *s_term;          // [n_traj][s_cap]
+  double *costs;           // [n_traj][k_cap]
+  int64_t s_cap, k_cap;
+  // the table
+  int32_t *n_steps;        // [n_traj]
+  double *pos, *togo;      // [n_traj][k_cap][D], [n_traj][k_cap]
+  uint8_t *status;         // [n_traj] MPLX_TRAJ_* bits
+  // goals: the open set's (goals0: as mplx_open_set_goals left them), and the effective rows for the view
+  const PostFuse *goals0;
+  PostFuse *goals;
+  double *goal_row;        // [n_traj][14]
+  uint64_t *goal_hash;     // [n_traj]
+};
+hipError_t launch_prior_build(int dim, int control, const PriorArgs &a, hipStream_t s);
+
 // Persistent node table (table_kernel.hip, table_api.cpp; include/mplx_table.h).
 struct TableSlot { uint64_t key; int32_t id; uint32_t first_e; };  // all bytes 0xff: empty, no id, no claimant
 struct TableCtl {      // device memory
@@ -598,6 +621,12 @@ struct OpenArgs {
   double *f_g, *f_state;
   int64_t f_stride, f_cap;
   int64_t *f_count;
+  // push with priors (include/mplx_prior.h; appended: every field above keeps its place): null = no prior in force
+  const int32_t *prior_n;          // [n_queries] steps per query, 0 = none
+  const double *prior_pos;         // [n_queries][prior_cap][D]
+  const double *prior_togo;        // [n_queries][prior_cap]
+  int64_t prior_cap;
+  double prior_dt;                 // the searching context's dt
 };
 hipError_t launch_open_clear(const OpenArgs &a, hipStream_t s);  // ctl: 2 * n_queries control blocks
 // closed: the push of include/mplx_replan.h -- the rows get SEEN (and IS_GOAL) but not IS_OPEN

@@ -3,6 +3,7 @@
 // staging arena: push and select take device pointers only.
 #include "mplx_ctx.h"
 #include "../../include/mplx_multi.h"
+#include "../../include/mplx_prior.h"
 #include "../../include/mplx_ray.h"
 
 #include <algorithm>
@@ -25,12 +26,20 @@ struct mplx_open {
   double goals_tol = 0.0;               // the largest tol_pos among them: bounds the rays of a push
   mplx::OpenResult *mirror = nullptr;   // pinned, [Q]
   int parity = 0;                       // which control block the next select reduces into
+  // include/mplx_prior.h: goals0 = the goals as mplx_open_set_goals gave them (`goals` carries the priors' ends while
+  // priors are in force); the table, its scratch and the rows of the view
+  DevBuf goals0, pr_n, pr_pos, pr_togo, pr_status, pr_sidx, pr_sterm, pr_costs, pr_trav, pr_grow, pr_ghash;
+  bool has_priors = false;
+  int64_t pr_cap = 0;                   // steps per query the table is laid out for
+  double pr_dt = 0.0;                   // the searching context's dt when the table was built
 };
 
 namespace {
 
 void release_open(mplx_open *o) {
-  for (DevBuf *b : {&o->f, &o->flags, &o->ctl, &o->mark, &o->tot, &o->rows, &o->goals}) release(*b);
+  for (DevBuf *b : {&o->f, &o->flags, &o->ctl, &o->mark, &o->tot, &o->rows, &o->goals, &o->goals0, &o->pr_n, &o->pr_pos, &o->pr_togo,
+                    &o->pr_status, &o->pr_sidx, &o->pr_sterm, &o->pr_costs, &o->pr_trav, &o->pr_grow, &o->pr_ghash})
+    release(*b);
   if (o->mirror) (void)hipHostFree(o->mirror);
   delete o;
 }
@@ -148,6 +157,13 @@ int mplx_detail::open_push(mplx_open *o, const char *who, const mplx_table_front
   a.eps = eps;
   a.goal = c->goal_fuse;
   a.goals = o->has_goals ? (const mplx::PostFuse *)o->goals.p : nullptr;
+  if (o->has_priors && o->has_goals) {
+    a.prior_n = (const int32_t *)o->pr_n.p;
+    a.prior_pos = (const double *)o->pr_pos.p;
+    a.prior_togo = (const double *)o->pr_togo.p;
+    a.prior_cap = o->pr_cap;
+    a.prior_dt = o->pr_dt;
+  }
   if (!sight) {
     HIP_TRY(c, mplx::launch_open_push(c->dim, 0, a, rows, c->stream, closed));
     return MPLX_OK;
@@ -221,12 +237,15 @@ int mplx_open_set_goals(mplx_open *o, const mplx_goal_spec *h_goals, int32_t n) 
   if (int rc = resolve_pending(c)) return rc;  // the arena is shared with the other host-pointer calls
   const size_t bytes = (size_t)n * sizeof(mplx::PostFuse);
   if (int rc = ensure(c, o->goals, bytes)) return rc;
+  if (int rc = ensure(c, o->goals0, bytes)) return rc;
   StageLayout l;
   const size_t o_g = l.add(bytes);
   if (int rc = stage_commit(c, &l)) return rc;
   HIP_TRY(c, stage_in(c, l.base + o_g, f.data(), bytes));
   HIP_TRY(c, hipMemcpyAsync(o->goals.p, l.base + o_g, bytes, hipMemcpyDeviceToDevice, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(o->goals0.p, l.base + o_g, bytes, hipMemcpyDeviceToDevice, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));  // (f leaves scope; the arena is free again)
+  o->has_priors = false;  // a new goal: the old prior no longer leads to it (include/mplx_prior.h)
   o->has_goals = true;
   o->goals_tol = tol;
   return MPLX_OK;
@@ -259,6 +278,123 @@ int mplx_open_select_multi_device(mplx_open *o, double delta, const mplx_table_f
     h->status = m[q].status; h->goal_id = m[q].goal_id; h->count = m[q].count; h->n_open = m[q].n_open;
     h->f_min = m[q].f_min; h->goal_f = m[q].goal_f; h->goal_g = m[q].goal_g;
   }
+  return MPLX_OK;
+}
+
+// ---- include/mplx_prior.h ----------------------------------------------------------------------------------------------
+
+int mplx_open_set_priors_device(mplx_open *o, const mplx_prior_source *src, const mplx_traj_set *s, const mplx_prior_info *h_info) {
+  if (!o) return MPLX_ERR_ARG;
+  mplx_ctx *c = o->c;
+  const char *who = "mplx_open_set_priors_device";
+  if (!src || !s) return fail(c, MPLX_ERR_ARG, "%s: NULL source or set", who);
+  const int ctl = src->control & 0x0f;
+  if ((src->control & ~0x1f) || (ctl != 0x01 && ctl != 0x03 && ctl != 0x07 && ctl != 0x0f))
+    return fail(c, MPLX_ERR_ARG, "%s: unknown control flag %d of the source", who, (int)src->control);
+  if (!src->U || src->nU < 1 || src->udim < c->dim + ((src->control & 0x10) ? 1 : 0) || !(src->dt > 0.0) || std::isinf(src->dt))
+    return fail(c, MPLX_ERR_ARG, "%s: the source needs U, nU >= 1, udim as its control flag asks and a finite dt > 0", who);
+  if (s->n_traj != o->Q) return fail(c, MPLX_ERR_ARG, "%s: %lld trajectories for a table of %d queries", who, (long long)s->n_traj, (int)o->Q);
+  if (s->horizon < 1 || (s->n_starts != 1 && s->n_starts != s->n_traj) || s->start_stride < s->n_starts || s->action_stride < s->n_traj ||
+      !s->starts || !s->actions)
+    return fail(c, MPLX_ERR_ARG, "%s: bad trajectory set (horizon >= 1, starts, actions, strides >= counts)", who);
+  if (!o->has_goals) return fail(c, MPLX_ERR_STATE, "%s: no goals of the open set's own (mplx_open_set_goals)", who);
+  if (!c->has_params) return fail(c, MPLX_ERR_STATE, "%s: mplx_set_params has not been called", who);
+  if (!c->has_map) return fail(c, MPLX_ERR_STATE, "%s: set the map first", who);
+  if (c->n_cells > 0x7fffffffLL) return fail(c, MPLX_ERR_STATE, "%s: the map has more cells than getIndex (int32) can number", who);
+  if (!(c->prm.v_max > 0)) return fail(c, MPLX_ERR_STATE, "%s: v_max must be > 0 (env_map.h:231)", who);
+  if (!(c->prm.dt > 0) || !(c->res > 0)) return fail(c, MPLX_ERR_STATE, "%s: dt and the resolution must be > 0", who);
+  {
+    mplx::OpenArgs probe{};
+    if (int rc = open_args(o, who, &probe)) return rc;  // a table with a status bit
+  }
+  // the host's bounds: steps t_k < T <= horizon * source dt, samples n + 1 with n = ceil(v_max T / res)
+  const double span = (double)s->horizon * src->dt;
+  const double kb = std::ceil(span / c->prm.dt) + 2.0, sb = std::ceil(c->prm.v_max * span / c->res) + 3.0;
+  const double lim = 268435456.0 / (double)o->Q;  // 2^28 entries
+  if (!(kb <= lim) || !(sb <= lim)) return fail(c, MPLX_ERR_ARG, "%s: the prior table would exceed 2^28 entries", who);
+  const size_t Q = (size_t)o->Q, K = (size_t)kb, SC = (size_t)sb, D = (size_t)c->dim;
+  if (int rc = bind_device(c)) return rc;
+  if (int rc = ensure(c, o->pr_n, Q * 4)) return rc;
+  if (int rc = ensure(c, o->pr_status, Q)) return rc;
+  if (int rc = ensure(c, o->pr_trav, Q * 8)) return rc;
+  if (int rc = ensure(c, o->pr_grow, Q * 14 * 8)) return rc;
+  if (int rc = ensure(c, o->pr_ghash, Q * 8)) return rc;
+  if (int rc = ensure(c, o->pr_pos, Q * K * D * 8)) return rc;
+  if (int rc = ensure(c, o->pr_togo, Q * K * 8)) return rc;
+  if (int rc = ensure(c, o->pr_costs, Q * K * 8)) return rc;
+  if (int rc = ensure(c, o->pr_sidx, Q * SC * 4)) return rc;
+  if (int rc = ensure(c, o->pr_sterm, Q * SC * 8)) return rc;
+  // the chain launch on a copy of the context's arguments with the source's controls and duration (traj_api.cpp build())
+  const mplx_succ none{};
+  mplx::PriorArgs P{};
+  mplx::TrajArgs &a = P.traj;
+  a.env = expand_args(c, nullptr, 0, 0, &none);
+  a.env.U = src->U; a.env.nU = src->nU; a.env.udim = src->udim; a.env.dt = src->dt;
+  a.starts = s->starts; a.n_starts = s->n_starts; a.start_stride = s->start_stride;
+  a.actions = s->actions; a.n_traj = s->n_traj; a.action_stride = s->action_stride; a.horizon = s->horizon;
+  a.yaw = (src->control & 0x10) ? 1 : 0;
+  {
+    const size_t H = (size_t)s->horizon, NC = 5 * D + 2;
+    StageLayout l;  // (only the carving: the table is the context's own scratch, not the arena)
+    const size_t o_S = l.add(Q * 4), o_n = l.add(Q * 4), o_st = l.add(Q), o_T = l.add(Q * 8), o_tau = l.add((H + 1) * Q * 8),
+                 o_seg = l.add(H * NC * Q * 8);
+    if (int rc = ensure(c, c->traj_tab, l.total)) return rc;
+    char *base = (char *)c->traj_tab.p;
+    a.tab_S = (int32_t *)(base + o_S);
+    a.tab_n = (int32_t *)(base + o_n);
+    a.tab_status = (uint8_t *)(base + o_st);
+    a.tab_T = (double *)(base + o_T);
+    a.tab_tau = (double *)(base + o_tau);
+    a.tab_seg = (double *)(base + o_seg);
+  }
+  o->has_priors = false;  // (a failure below leaves the open set without priors ...
+  HIP_TRY(c, hipMemcpyAsync(o->goals.p, o->goals0.p, Q * sizeof(mplx::PostFuse), hipMemcpyDeviceToDevice, c->stream));  // ... and with its own goals)
+  HIP_TRY(c, mplx::launch_traj_chain(c->dim, src->control, a, c->stream));
+  a.cost = (double *)o->pr_trav.p;
+  const double B = std::ceil(c->prm.v_max * span / c->res) + 1.0;  // auto_lanes of traj_api.cpp
+  HIP_TRY(c, mplx::launch_traj_traverse(c->dim, !(B > 64.0) ? 4 : B <= 256.0 ? 16 : 64, a, c->stream));
+  a.cost = nullptr;
+  P.dt = c->prm.dt;
+  P.traverse = (const double *)o->pr_trav.p;
+  P.s_idx = (int32_t *)o->pr_sidx.p; P.s_term = (double *)o->pr_sterm.p; P.costs = (double *)o->pr_costs.p;
+  P.s_cap = (int64_t)SC; P.k_cap = (int64_t)K;
+  P.n_steps = (int32_t *)o->pr_n.p; P.pos = (double *)o->pr_pos.p; P.togo = (double *)o->pr_togo.p; P.status = (uint8_t *)o->pr_status.p;
+  P.goals0 = (const mplx::PostFuse *)o->goals0.p; P.goals = (mplx::PostFuse *)o->goals.p;
+  P.goal_row = (double *)o->pr_grow.p; P.goal_hash = (uint64_t *)o->pr_ghash.p;
+  HIP_TRY(c, mplx::launch_prior_build(c->dim, src->control, P, c->stream));
+  o->has_priors = true;
+  o->pr_cap = (int64_t)K;
+  o->pr_dt = c->prm.dt;
+  if (h_info && (h_info->status || h_info->n_steps)) {
+    if (h_info->status) HIP_TRY(c, hipMemcpyAsync(h_info->status, o->pr_status.p, Q, hipMemcpyDeviceToHost, c->stream));
+    if (h_info->n_steps) HIP_TRY(c, hipMemcpyAsync(h_info->n_steps, o->pr_n.p, Q * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+  }
+  return MPLX_OK;
+}
+
+int mplx_open_clear_priors(mplx_open *o) {
+  if (!o) return MPLX_ERR_ARG;
+  mplx_ctx *c = o->c;
+  if (!o->has_priors) return MPLX_OK;
+  if (int rc = bind_device(c)) return rc;
+  o->has_priors = false;
+  if (o->has_goals)
+    HIP_TRY(c, hipMemcpyAsync(o->goals.p, o->goals0.p, (size_t)o->Q * sizeof(mplx::PostFuse), hipMemcpyDeviceToDevice, c->stream));
+  return MPLX_OK;
+}
+
+int mplx_open_prior_view_of(mplx_open *o, mplx_prior_view *v) {
+  if (!o) return MPLX_ERR_ARG;
+  if (!v) return fail(o->c, MPLX_ERR_ARG, "mplx_open_prior_view_of: NULL view");
+  *v = mplx_prior_view{};
+  if (!o->has_priors) return MPLX_OK;
+  v->n_steps = (const int32_t *)o->pr_n.p;
+  v->pos = (const double *)o->pr_pos.p;
+  v->togo = (const double *)o->pr_togo.p;
+  v->goal_row = (const double *)o->pr_grow.p;
+  v->goal_hash = (const uint64_t *)o->pr_ghash.p;
+  v->step_capacity = o->pr_cap;
   return MPLX_OK;
 }
 

@@ -27,6 +27,9 @@
 // this file: the same four passes with every decision taken per query, and a fifth launch of one lane per query that
 // writes the results once the emit pass has counted each query's rows below the frontier's capacity.  The kernels of a
 // table with one query are untouched by that.
+//
+// With priors (include/mplx_prior.h) the push is the same kernel again with the heuristic of a guided query read from the
+// open set's prior table (built by traj_kernel.hip); the instantiations without priors are untouched by that.
 #include "mplx_internal.h"
 #include "mplx_device_common.h"
 
@@ -75,7 +78,9 @@ __device__ __forceinline__ Decision decide(const OpenArgs &A) { return decide(A.
 
 // MULTI: the goal is goals[query of the node] (mplx_open_set_goals), not the context's
 // CLOSED: the push of include/mplx_replan.h -- key and goal bit as ever, but the node is not opened
-template <int D, bool MULTI, bool CLOSED>
+// PRIOR: include/mplx_prior.h -- a query with a prior table takes its heuristic from where the prior is at the row's time
+// (env_base.h:46-53); the instantiations without it are the kernels they were
+template <int D, bool MULTI, bool CLOSED, bool PRIOR>
 __global__ __launch_bounds__(kBlock) void open_push_kernel(const OpenArgs A, int64_t rows, int pass) {
   if (A.t_ctl->status) return;
   const int64_t r = (int64_t)blockIdx.x * kBlock + threadIdx.x;
@@ -99,6 +104,7 @@ __global__ __launch_bounds__(kBlock) void open_push_kernel(const OpenArgs A, int
 #pragma unroll
   for (int i = 0; i < 3 * D; i++) s[i] = A.f_state[(int64_t)i * A.f_stride + r];
   s[4 * D] = A.f_state[(int64_t)(4 * D) * A.f_stride + r];
+  const double t_row = PRIOR ? A.f_state[(int64_t)(4 * D + 1) * A.f_stride + r] : 0.0;
   int32_t q = 0;
   if (MULTI && A.t_query) {
     q = A.t_query[id];
@@ -109,6 +115,23 @@ __global__ __launch_bounds__(kBlock) void open_push_kernel(const OpenArgs A, int
   double h;
   unsigned int fl;
   dev::post_eval<D>(PG, A.t_hash[id], s, s + D, s + 2 * D, s[4 * D], &h, &fl);
+  if (PRIOR && !(fl & 2u)) {  // (bit 1: the goal's own lattice state keeps h = 0, env_base.h:47)
+    const int32_t ns = A.prior_n[q];
+    const double x = t_row > 0 ? t_row / A.prior_dt : 0.0;  // env_base.h:48
+    if (ns > 0 && x < (double)ns) {
+      int64_t k = (int64_t)x;
+      k = k < 0 ? 0 : (k < A.prior_cap ? k : A.prior_cap - 1);  // (0 <= x < ns <= prior_cap: never moves)
+      const double *pp = A.prior_pos + ((int64_t)q * A.prior_cap + k) * D;
+      double m = 0;
+#pragma unroll
+      for (int i = 0; i < D; i++) {
+        const double d = fabs(s[i] - pp[i]);
+        m = d > m ? d : m;
+      }
+      const double lin = PG.v_max > 0 ? PG.w * m / PG.v_max : PG.w * m;
+      h = lin + A.prior_togo[(int64_t)q * A.prior_cap + k];
+    }
+  }
   const double g = A.f_g[r];
   double f = g;
   if (A.eps != 0.0) {
@@ -484,17 +507,21 @@ hipError_t launch_open_clear(const OpenArgs &a, hipStream_t s) {
   return hipGetLastError();
 }
 
-template <int D, bool MULTI>
+template <int D, bool MULTI, bool PRIOR = false>
 void push_closed(bool closed, dim3 grid, dim3 block, hipStream_t s, const OpenArgs &a, int64_t rows, int pass) {
-  if (closed) hipLaunchKernelGGL((open_push_kernel<D, MULTI, true>), grid, block, 0, s, a, rows, pass);
-  else hipLaunchKernelGGL((open_push_kernel<D, MULTI, false>), grid, block, 0, s, a, rows, pass);
+  if (closed) hipLaunchKernelGGL((open_push_kernel<D, MULTI, true, PRIOR>), grid, block, 0, s, a, rows, pass);
+  else hipLaunchKernelGGL((open_push_kernel<D, MULTI, false, PRIOR>), grid, block, 0, s, a, rows, pass);
 }
 
 hipError_t launch_open_push(int dim, int pass, const OpenArgs &a, int64_t rows, hipStream_t s, bool closed) {
   if (rows <= 0) return hipSuccess;
   const dim3 grid((unsigned)((rows + kBlock - 1) / kBlock)), block(kBlock);
   if (dim != 2 && dim != 3) return hipErrorInvalidValue;
-  if (a.goals) {
+  if (a.prior_n) {  // (priors need goals of the open set's own: open_api.cpp)
+    if (!a.goals || !a.prior_pos || !a.prior_togo || a.prior_cap < 1) return hipErrorInvalidValue;
+    if (dim == 2) push_closed<2, true, true>(closed, grid, block, s, a, rows, pass);
+    else push_closed<3, true, true>(closed, grid, block, s, a, rows, pass);
+  } else if (a.goals) {
     if (dim == 2) push_closed<2, true>(closed, grid, block, s, a, rows, pass);
     else push_closed<3, true>(closed, grid, block, s, a, rows, pass);
   } else {

@@ -2,10 +2,12 @@
 // "host search" section) on top of host_planner.hpp.
 #include "../../include/mplx.h"
 #include "../../include/mplx_debug.h"
+#include "../../include/mplx_prior.h"
 #include "host_planner.hpp"
 #include "host_lpastar.hpp"
 #include "mplx_ctx.h"
 
+#include <algorithm>
 #include <new>
 #include <string>
 
@@ -242,6 +244,19 @@ int mplx_planner_plan(mplx_planner *p, const double *start, const double *goal, 
 int mplx_planner_use_device_heuristic(mplx_planner *p, int on) {
   if (!p) return MPLX_ERR_ARG;
   p->want_device_heur = on != 0;
+  return MPLX_OK;
+}
+
+// include/mplx_prior.h: the table set_prior_trajectory() left, for comparison with the device's
+int mplx_planner_prior_table(const mplx_planner *p, double *pos, double *togo, int32_t cap, int32_t *n, double *goal_row, int32_t *control) {
+  if (!p || cap < 0) return MPLX_ERR_ARG;
+  const int D = p->pl.dim;
+  const size_t steps = p->pl.prior_togo.size(), m = std::min(steps, (size_t)cap);
+  if (n) *n = (int32_t)steps;
+  if (pos) std::copy(p->pl.prior_pos.begin(), p->pl.prior_pos.begin() + (ptrdiff_t)(m * (size_t)D), pos);
+  if (togo) std::copy(p->pl.prior_togo.begin(), p->pl.prior_togo.begin() + (ptrdiff_t)m, togo);
+  if (goal_row) std::copy(p->pl.prior_goal, p->pl.prior_goal + 4 * D + 2, goal_row);
+  if (control) *control = p->pl.prior_control;
   return MPLX_OK;
 }
 

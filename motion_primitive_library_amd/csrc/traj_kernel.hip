@@ -17,6 +17,9 @@
 // counts; the ordered sum walks the set bits of the round's `adds` ballot and broadcasts each term with __shfl: at
 // most G adds per round, none on occupancy maps.  The loop bound is the n the chain launch left on the device.
 //
+// prior_sample_kernel<D> / prior_build_kernel<D>: the prior table of an open set (include/mplx_prior.h) on the same segment
+// table, with find_segment / eval_segment as the kernels above use them; stated where they are defined, further down.
+//
 // Bit-exactness: -ffp-contract=off, true divisions, power by repeated multiply, sums in the reference's order.  The
 // coefficient c0 of a forward primitive is 0: its terms of p / v / a / j are +0.0 for the finite tau >= 0 evaluated here
 // and are stated as the leading `0.0 +`; the effort formulas keep c0 as a variable.
@@ -366,6 +369,159 @@ __global__ __launch_bounds__(kBlock) void traj_traverse_kernel(const TrajArgs R)
   if (R.stop_sample) R.stop_sample[k] = stop;
 }
 
+// ---- the prior table of an open set (include/mplx_prior.h; env_map.h:189-226 as csrc/host_planner.hpp restates it) ----
+//
+// prior_sample_kernel<D>: one lane per sample of the traversal (the samples traj_traverse_kernel walks, the same
+// expressions): its cell index and its term potential_weight * value + gradient_weight * |vel| -- the map bytes of a wave
+// are independent loads.  A sample outside the map reads 0; no range test on the value (env_map.h:205-211).
+// prior_build_kernel<D>: one lane per trajectory: the two serial chains (t_k by sequential addition; the prefix of the
+// terms in sample order, one IEEE add each), pos / togo, and the goal the query's pushes use from now on.  Every loop is
+// bounded by s_cap / k_cap, the host's bounds; a trajectory that would pass them is MPLX_TRAJ_BAD.
+template <int D>
+__global__ __launch_bounds__(kBlock) void prior_sample_kernel(const PriorArgs P) {
+  const TrajArgs &R = P.traj;
+  const ExpandArgs &A = R.env;
+  const int64_t N = R.n_traj;
+  const int64_t g = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (g >= N * P.s_cap) return;
+  const int64_t k = g / P.s_cap, i = g - k * P.s_cap;
+  const int S = R.tab_S[k], n = R.tab_n[k];
+  if (S <= 0 || n < 1 || (int64_t)n + 1 > P.s_cap || i > (int64_t)n) return;
+  const double T = R.tab_T[k];
+  const double step = T / (double)n;  // trajectory.h:233
+  const double *taus = R.tab_tau + k;
+  double tau = (double)i * step;  // >= 0 and finite
+  if (tau > T) tau = T;
+  const int id = find_segment<true>(taus, N, S, tau, A.dt);
+  tau -= taus[(int64_t)id * N];
+  Sample<D> sm;
+  eval_segment<D, true, false>(R.tab_seg + (int64_t)id * (5 * D + 2) * N + k, N, tau, sm);
+  const int32_t mdim[3] = {A.dim0, A.dim1, A.dim2};
+  const double org[3] = {A.org0, A.org1, A.org2};
+  uint32_t ui = 0, mul = 1;
+  bool inside = true;
+#pragma unroll
+  for (int d = 0; d < D; d++) {
+    // map_util.h:103-108; a value the reference could not convert saturates (NaN: the lower end)
+    double c = round((sm.pos[d] - org[d]) / A.res - 0.5);
+    c = fmin(fmax(c, -2147483648.0), 2147483647.0);
+    const int ci = (int)c;
+    inside = inside && ci >= 0 && ci < mdim[d];
+    ui += (uint32_t)ci * mul;  // map_util.h:34-41 in wrapping 32-bit arithmetic, also for cells outside
+    mul *= (uint32_t)mdim[d];
+  }
+  const int idx = (int)ui;
+  double term = 0.0;
+  if (A.pot) {
+    const int v = inside ? A.pot[idx] : 0;
+    double q = 0;
+#pragma unroll
+    for (int d = 0; d < D; d++) q += sm.vel[d] * sm.vel[d];
+    term = A.pot_w * v + A.grad_w * sqrt(q);  // env_map.h:209-210
+  }
+  P.s_idx[k * P.s_cap + i] = idx;
+  P.s_term[k * P.s_cap + i] = term;
+}
+
+// waypoint.h:93-125 with the control flag at run time (the prior's), as host::lattice_hash states it
+template <int D>
+__device__ __forceinline__ uint64_t prior_goal_hash(int control, const Sample<D> &sm) {
+  uint64_t h = 0;
+#pragma unroll
+  for (int i = 0; i < D; i++) {
+    if (control & 1) pair::fold(h, pair::quantise(sm.pos[i], 0.01));
+    if (control & 2) pair::fold(h, pair::quantise(sm.vel[i], 0.1));
+    if (control & 4) pair::fold(h, pair::quantise(sm.acc[i], 0.1));
+    if (control & 8) pair::fold(h, pair::quantise(sm.jrk[i], 0.1));
+  }
+  if (control & 16) pair::fold(h, pair::quantise(sm.yaw, 0.1));
+  return h;
+}
+
+template <int D>
+__global__ __launch_bounds__(kBlock) void prior_build_kernel(const PriorArgs P, int control) {
+  const TrajArgs &R = P.traj;
+  const ExpandArgs &A = R.env;
+  const int64_t N = R.n_traj;
+  const int64_t k = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (k >= N) return;
+  const int S = R.tab_S[k], n = R.tab_n[k];
+  const double T = R.tab_T[k];
+  const double *taus = R.tab_tau + k;
+  uint8_t status = R.tab_status[k];
+  if (n < 0 || (int64_t)n + 1 > P.s_cap) status |= 4;  // MPLX_TRAJ_BAD
+  int64_t cnt = 0;
+  if (S > 0 && !(status & 4)) {
+    const double total = P.traverse[k] + A.w * T;  // env_map.h:194
+    const double step = T / (double)n;
+    double *costs = P.costs + k * P.k_cap;
+    const int32_t *s_idx = P.s_idx + k * P.s_cap;
+    const double *s_term = P.s_term + k * P.s_cap;
+    const bool pot = A.pot != nullptr && n >= 1;
+    // env_map.h:197-216: the loop over samples of step k is a prefix of the loop of step k + 1 -- the same adds in the
+    // same order, carried on
+    double t = 0.0, pc = 0.0;
+    int64_t j = 0;
+    int prev = -1;
+    for (; cnt < P.k_cap && t < T; cnt++) {
+      if (pot) {
+        while (j <= (int64_t)n) {  // (n + 1 <= s_cap)
+          if ((double)j * step >= t) break;
+          const int idx = s_idx[j];
+          if (idx != prev) {
+            prev = idx;
+            pc = pc + s_term[j];
+          }
+          j++;
+        }
+      }
+      costs[cnt] = A.w * t + pc;
+      t = t + P.dt;
+    }
+    if (t < T) {  // (more steps than the host's bound: never with finite dt)
+      status |= 4;
+      cnt = 0;
+    }
+    t = 0.0;
+    for (int64_t kk = 0; kk < cnt; kk++) {
+      int64_t id = (int64_t)(int)(t / P.dt);  // env_map.h:219: the truncated quotient
+      id = id < 0 ? 0 : (id < cnt ? id : cnt - 1);
+      double tau = t;
+      if (tau > T) tau = T;
+      const int seg = find_segment<false>(taus, N, S, tau, A.dt);
+      tau -= taus[(int64_t)seg * N];
+      Sample<D> sm;
+      eval_segment<D, false, false>(R.tab_seg + (int64_t)seg * (5 * D + 2) * N + k, N, tau, sm);
+#pragma unroll
+      for (int d = 0; d < D; d++) P.pos[(k * P.k_cap + kk) * D + d] = sm.pos[d];
+      P.togo[k * P.k_cap + kk] = total - costs[id];
+      t = t + P.dt;
+    }
+  }
+  P.n_steps[k] = (int32_t)cnt;
+  P.status[k] = status;
+  // the goal of query k from now on: the prior's end (env_map.h:225), or what mplx_open_set_goals gave
+  PostFuse G = P.goals0[k];
+  if (cnt > 0) {
+    Sample<D> sm;
+    eval_segment<D, false, true>(R.tab_seg + (int64_t)(S - 1) * (5 * D + 2) * N + k, N, T - taus[(int64_t)(S - 1) * N], sm);
+#pragma unroll
+    for (int d = 0; d < D; d++) {
+      G.goal[d] = sm.pos[d];
+      G.goal[D + d] = sm.vel[d];
+      G.goal[2 * D + d] = sm.acc[d];
+      G.goal[3 * D + d] = sm.jrk[d];
+    }
+    G.goal[4 * D] = sm.yaw;
+    G.goal[4 * D + 1] = 0.0;  // (Trajectory::evaluate returns a fresh Waypoint: t = 0)
+    G.goal_hash = prior_goal_hash<D>(control, sm);
+  }
+  P.goals[k] = G;
+#pragma unroll
+  for (int f = 0; f < 14; f++) P.goal_row[k * 14 + f] = G.goal[f];
+  P.goal_hash[k] = G.goal_hash;
+}
+
 template <int D, int K>
 hipError_t chain_one(const TrajArgs &a, hipStream_t s) {
   const int64_t blocks = (a.n_traj + kBlock - 1) / kBlock;
@@ -415,6 +571,22 @@ hipError_t launch_traj_sample(int dim, int form, const TrajArgs &a, hipStream_t 
   if (dim == 2) return form == 0 ? sample_one<2, 0>(a, s) : sample_one<2, 1>(a, s);
   if (dim == 3) return form == 0 ? sample_one<3, 0>(a, s) : sample_one<3, 1>(a, s);
   return hipErrorInvalidValue;
+}
+
+hipError_t launch_prior_build(int dim, int control, const PriorArgs &a, hipStream_t s) {
+  const int64_t N = a.traj.n_traj;
+  if (N <= 0) return hipSuccess;
+  if (dim != 2 && dim != 3) return hipErrorInvalidValue;
+  const int64_t sb = (N * a.s_cap + kBlock - 1) / kBlock, nb = (N + kBlock - 1) / kBlock;
+  if (sb > 0x7fffffffLL) return hipErrorInvalidValue;
+  if (dim == 2) {
+    hipLaunchKernelGGL((prior_sample_kernel<2>), dim3((unsigned)sb), dim3(kBlock), 0, s, a);
+    hipLaunchKernelGGL((prior_build_kernel<2>), dim3((unsigned)nb), dim3(kBlock), 0, s, a, control);
+  } else {
+    hipLaunchKernelGGL((prior_sample_kernel<3>), dim3((unsigned)sb), dim3(kBlock), 0, s, a);
+    hipLaunchKernelGGL((prior_build_kernel<3>), dim3((unsigned)nb), dim3(kBlock), 0, s, a, control);
+  }
+  return hipGetLastError();
 }
 
 hipError_t launch_traj_traverse(int dim, int lanes, const TrajArgs &a, hipStream_t s) {

@@ -630,6 +630,7 @@ class EnvMap:
             raise ValueError("U must be [nU][udim]")
         _abi.check(self._ctx, _abi.lib().mplx_set_controls(self._ctx, U.ctypes.data, U.shape[0], U.shape[1]))
         self.nU = U.shape[0]
+        self._U_host = U.copy()  # (what SearchResult.as_prior hands to a later search as the prior's control table)
 
     def _setp(self, name, v):
         setattr(self._p, name, float(v))
@@ -1328,7 +1329,7 @@ class EnvMap:
 
     def search(self, start, goal_row, eps=1.0, delta=None, g_max=float("inf"), max_rounds=None, max_expand=None,
                capacity=1 << 16, max_frontier=None, lists_stride=None, sight=True, tol_pos=0.5, tol_vel=-1.0, tol_acc=-1.0,
-               tol_yaw=-1.0, w=None, v_max=None, start_g=0.0):
+               tol_yaw=-1.0, w=None, v_max=None, start_g=0.0, prior=None):
         """A goal-directed search from `start` (one 4D+2 state) to the goal region of `goal_row` that stays on the
         device: set_goal, seed, push; then per round one select (the round's only read-back, 48 bytes), and while it
         selects: expand the selection, relax its lists against the table, push the nodes whose g fell.  Keys are
@@ -1340,24 +1341,27 @@ class EnvMap:
         (default: capacity); a larger selection is taken in id order, the rest stays open.  Returns a SearchResult
         (search.py) that owns the table and the open set.  A table that ran out of nodes or probe length raises.
         start_g: the cost-to-come the start is seeded with (what a SearchResult.replan from a node with that g is
-        compared against).  result.replan(...) plans again on the same table after a move or a map edit."""
+        compared against).  result.replan(...) plans again on the same table after a move or a map edit.
+        prior: a search.Prior (e.g. another result's as_prior()): the heuristic follows the prior trajectory at the
+        node's own time and the goal moves to the prior's end (include/mplx_prior.h)."""
         from .search import run_search
         return run_search(self, start, goal_row, eps, delta, g_max, max_rounds, max_expand, capacity, max_frontier,
-                          lists_stride, sight, tol_pos, tol_vel, tol_acc, tol_yaw, w, v_max, start_g)
+                          lists_stride, sight, tol_pos, tol_vel, tol_acc, tol_yaw, w, v_max, start_g, prior)
 
     def search_many(self, starts, goal_rows, eps=1.0, delta=None, g_max=float("inf"), max_rounds=None, max_expand=None,
                     capacity=1 << 16, max_frontier=None, lists_stride=None, sight=True, tol_pos=0.5, tol_vel=-1.0,
-                    tol_acc=-1.0, tol_yaw=-1.0, w=None, v_max=None, start_g=0.0):
+                    tol_acc=-1.0, tol_yaw=-1.0, w=None, v_max=None, start_g=0.0, priors=None):
         """Q searches of EnvMap.search at once, sharing every launch of a round (include/mplx_multi.h): starts
         [4D+2][Q], goal_rows [Q][4D+2], query q from starts[:, q] to the goal region of goal_rows[q].  One table of
         `capacity` nodes and one open set hold all of them; a round selects, expands, relaxes and pushes the union of
         what the queries select, and reads Q results back.  The loop goes on while any query selects; max_expand counts
         all queries together.  As long as no selection is cut at max_frontier every query does exactly what its own
         EnvMap.search does.  Returns a MultiSearchResult (search.py) that owns the table and the open set.  start_g: one
-        cost-to-come for every start, or [Q]."""
+        cost-to-come for every start, or [Q].  priors: [Q] search.Prior or None (no prior for that query), e.g. another
+        result's as_priors(): one mplx_open_set_priors_device for all of them (include/mplx_prior.h)."""
         from .search import run_search_many
         return run_search_many(self, starts, goal_rows, eps, delta, g_max, max_rounds, max_expand, capacity, max_frontier,
-                               lists_stride, sight, tol_pos, tol_vel, tol_acc, tol_yaw, w, v_max, start_g)
+                               lists_stride, sight, tol_pos, tol_vel, tol_acc, tol_yaw, w, v_max, start_g, priors)
 
     def synchronize(self):
         _abi.check(self._ctx, _abi.lib().mplx_synchronize(self._ctx))

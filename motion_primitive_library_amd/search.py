@@ -13,7 +13,8 @@
         opn.push(imp, n_max=r["count"] * lists.stride, eps=1.0)
 
 is EnvMap.search.  With a table of Q queries (include/mplx_multi.h), opn.set_goals(goal_rows) and opn.select_many the
-same loop runs Q searches at once: EnvMap.search_many.
+same loop runs Q searches at once: EnvMap.search_many.  opn.set_priors(...) (include/mplx_prior.h) steers every query by
+a prior trajectory -- coarse-to-fine planning is two searches, the second with priors=first.as_priors().
 """
 import ctypes as C
 import math
@@ -28,6 +29,29 @@ SELECTED, FOUND, EMPTY = _abi.OPEN_SELECTED, _abi.OPEN_FOUND, _abi.OPEN_EMPTY
 # statuses of a SearchResult beyond those of a select: the search stopped at a limit with nodes still open
 MAX_ROUNDS, MAX_EXPAND = 3, 4
 STATUS_NAMES = {SELECTED: "SELECTED", FOUND: "FOUND", EMPTY: "EMPTY", MAX_ROUNDS: "MAX_ROUNDS", MAX_EXPAND: "MAX_EXPAND"}
+
+
+class Prior:
+    """A prior trajectory and what it was planned with: start row [4D+2], actions [S] (rows of U), the control flag,
+    the control table U [nU][udim] and the primitive duration dt of the planner that made it."""
+
+    def __init__(self, start, actions, control, U, dt):
+        self.start = np.array(start, dtype=np.float64).ravel()
+        self.actions = np.array(actions, dtype=np.int32).ravel()
+        self.control = int(control)
+        self.U = np.ascontiguousarray(U, dtype=np.float64)
+        self.dt = float(dt)
+
+    def __repr__(self):
+        return "Prior(%d segments, control=%#x, dt=%r)" % (self.actions.size, self.control, self.dt)
+
+
+def _prior_of(result, q):
+    prm = result._params
+    if prm is None or prm.get("U") is None:
+        raise RuntimeError("as_prior: the search kept no control table")
+    start, act = result.path() if q is None else result.path(q)
+    return Prior(start, act, prm["control"], prm["U"], prm["dt"])
 
 
 class OpenSet:
@@ -115,6 +139,76 @@ class OpenSet:
         return [{"status": int(r.status), "goal_id": int(r.goal_id), "count": int(r.count), "n_open": int(r.n_open),
                  "f_min": float(r.f_min), "goal_f": float(r.goal_f), "goal_g": float(r.goal_g)} for r in res]
 
+    def set_priors(self, starts, actions, control, U, dt):
+        """mplx_open_set_priors_device: starts [4D+2][Q] (or one state for all), actions [H][Q] (-1 ends; a first action
+        of -1: no prior for that query), and the source the priors were planned with (control flag, control table U
+        [nU][udim], primitive duration dt).  Replaces the priors of all queries; needs set_goals first.  Returns
+        {"status" [Q] (TRAJ_* bits), "n_steps" [Q]} (one synchronisation)."""
+        env = self._env
+        env._flush()
+        s, keep, K, H = env._traj_host_set(starts, actions)
+        starts_h, actions_h = keep
+        U = np.ascontiguousarray(U, dtype=np.float64)
+        if U.ndim != 2:
+            raise ValueError("U must be [nU][udim]")
+        from .env import DeviceArray
+        bufs = [DeviceArray(env, max(a.nbytes, 8)) for a in (starts_h, actions_h, U)]
+        try:
+            for b, a in zip(bufs, (starts_h, actions_h, U)):
+                if a.nbytes:
+                    b.upload(a)
+            s.starts, s.actions = bufs[0].ptr, bufs[1].ptr
+            src = _abi.PriorSource()
+            src.control, src.nU, src.udim, src.U, src.dt = int(control), U.shape[0], U.shape[1], bufs[2].ptr, float(dt)
+            status, n_steps = np.zeros(max(K, 1), np.uint8), np.zeros(max(K, 1), np.int32)
+            info = _abi.PriorInfo()
+            info.status, info.n_steps = status.ctypes.data, n_steps.ctypes.data
+            # (the info read-back synchronises: the uploads may be freed when the call returns)
+            self._check(_abi.lib().mplx_open_set_priors_device(self._open, C.byref(src), C.byref(s), C.byref(info)))
+        finally:
+            for b in bufs:
+                b.free()
+        return {"status": status[:K], "n_steps": n_steps[:K]}
+
+    def set_prior_list(self, priors):
+        """set_priors from [Q] Prior or None entries; the priors of one call share control flag, U and dt."""
+        env = self._env
+        some = [p for p in priors if p is not None]
+        if len(priors) != self.n_queries:
+            raise ValueError("priors: %d entries for %d queries" % (len(priors), self.n_queries))
+        if not some:
+            self.clear_priors()
+            return None
+        p0 = some[0]
+        for p in some[1:]:
+            if p.control != p0.control or p.dt != p0.dt or p.U.shape != p0.U.shape or not np.array_equal(p.U, p0.U):
+                raise ValueError("priors: the priors of one call must share control flag, control table and dt")
+        H = max(1, max(p.actions.size for p in some))
+        starts = np.zeros((env.n_fields, len(priors)))
+        actions = np.full((H, len(priors)), -1, np.int32)
+        for q, p in enumerate(priors):
+            if p is not None:
+                starts[:, q] = p.start
+                actions[:p.actions.size, q] = p.actions
+        return self.set_priors(starts, actions, p0.control, p0.U, p0.dt)
+
+    def clear_priors(self):
+        self._check(_abi.lib().mplx_open_clear_priors(self._open))
+
+    def priors(self):
+        """The prior table in force (a download): {"n_steps" [Q], "pos": [Q] arrays [n_steps][D], "togo": [Q] arrays,
+        "goal_row" [Q][4D+2], "goal_hash" [Q]}, or None while no prior is in force."""
+        v = _abi.PriorView()
+        self._check(_abi.lib().mplx_open_prior_view_of(self._open, C.byref(v)))
+        if not v.n_steps:
+            return None
+        Q, K, D, rd = self.n_queries, int(v.step_capacity), self._env.dim, self._table._read
+        n = rd(v.n_steps, np.int32, Q)
+        pos, togo = rd(v.pos, np.float64, Q * K * D).reshape(Q, K, D), rd(v.togo, np.float64, Q * K).reshape(Q, K)
+        return {"n_steps": n, "pos": [pos[q, :n[q]].copy() for q in range(Q)], "togo": [togo[q, :n[q]].copy() for q in range(Q)],
+                "goal_row": rd(v.goal_row, np.float64, Q * 14).reshape(Q, 14)[:, :self._env.n_fields].copy(),
+                "goal_hash": rd(v.goal_hash, np.uint64, Q)}
+
     def view(self):
         v = _abi.OpenView()
         self._check(_abi.lib().mplx_open_view_of(self._open, C.byref(v)))
@@ -153,14 +247,19 @@ class SearchResult:
         ids, act = self.table.path(self.goal_id)
         return self.table.state_of(ids[0]), act
 
-    def replan(self, root=None, advance=None, goal_row=None, check_edges=True):
+    def as_prior(self):
+        """This result's path as the Prior of a later search (with the control set this search ran with)."""
+        return _prior_of(self, None)
+
+    def replan(self, root=None, advance=None, goal_row=None, check_edges=True, prior=None):
         """Plans again on the table of this search after the robot has moved and / or the map was edited
         (include/mplx_replan.h), with the parameters of the search that made this result.  root: the
         node id the robot is at (default: the seed); advance=k: ids[k] of the chain path() follows.  Nodes that still
         hang below the root by edges valid on the map as it is now keep their g -- costs go on being measured from the
         original start --, all of them are expanded once in a forced round (in chunks of max_frontier rows), then the
         loop of EnvMap.search finishes.  goal_row: a new goal; keys and goal bits of the kept nodes are recomputed
-        anyway.  Returns a new SearchResult that owns the table and the open set; this one no longer does."""
+        anyway.  A search with a prior replans with it (the open set keeps it); a new goal_row drops it unless `prior`
+        gives one again.  Returns a new SearchResult that owns the table and the open set; this one no longer does."""
         if self.table is None or self._params is None:
             raise RuntimeError("replan: this result does not own a table (it was replanned or freed)")
         if root is not None and advance is not None:
@@ -169,7 +268,7 @@ class SearchResult:
             if not self.found:
                 raise RuntimeError("replan: advance needs a path (status %s)" % STATUS_NAMES[self.status])
             root = int(self.table.path(self.goal_id)[0][int(advance)])
-        return run_replan(self, False, [-1 if root is None else int(root)], goal_row, check_edges)
+        return run_replan(self, False, [-1 if root is None else int(root)], goal_row, check_edges, None if prior is None else [prior])
 
     def free(self):
         if self.open is not None:
@@ -230,21 +329,27 @@ def _params(env, eps, delta, g_max, max_rounds, max_expand, capacity, max_fronti
         delta = float(env._p.w) * float(env._p.dt)
     return {"eps": eps, "delta": delta, "g_max": g_max, "max_rounds": max_rounds, "max_expand": max_expand,
             "capacity": int(capacity), "fcap": int(capacity if max_frontier is None else max_frontier),
-            "lists_stride": lists_stride, "sight": sight, "goal_kw": goal_kw}
+            "lists_stride": lists_stride, "sight": sight, "goal_kw": goal_kw,
+            # what as_prior() hands on: the control set of this search
+            "control": int(env._p.control), "U": getattr(env, "_U_host", None), "dt": float(env._p.dt)}
 
 
 def run_search(env, start, goal_row, eps, delta, g_max, max_rounds, max_expand, capacity, max_frontier, lists_stride, sight,
-               tol_pos, tol_vel, tol_acc, tol_yaw, w, v_max, start_g=0.0):
+               tol_pos, tol_vel, tol_acc, tol_yaw, w, v_max, start_g=0.0, prior=None):
     env._flush()
     prm = _params(env, eps, delta, g_max, max_rounds, max_expand, capacity, max_frontier, lists_stride, sight,
                   dict(w=w, v_max=v_max, tol_pos=tol_pos, tol_vel=tol_vel, tol_acc=tol_acc, tol_yaw=tol_yaw))
     prm["goal_row"] = np.array(goal_row, dtype=np.float64)
+    prm["own_goals"] = prior is not None  # the open set carries its goal itself (priors need that): replan keeps it so
     fcap = prm["fcap"]
     env.set_goal(goal_row, **prm["goal_kw"])
     tab = NodeTable(env, capacity)
     opn = sel = imp = lists = None
     try:
         opn = OpenSet(env, tab)
+        if prior is not None:
+            opn.set_goals(prm["goal_row"].reshape(1, -1), **prm["goal_kw"])
+            opn.set_prior_list([prior])
         sel, imp = TableFrontier(env, fcap), TableFrontier(env, int(capacity))  # (no more nodes can improve than exist)
         lists = env.alloc_lists(fcap, want_state=True, stride=lists_stride)
         # (g = None is the call without a g row: the bytes of a search before start_g existed)
@@ -292,7 +397,11 @@ class MultiSearchResult:
         ids, act = self.table.path(self.goal_id[q])
         return self.table.state_of(ids[0]), act
 
-    def replan(self, roots=None, advance=None, goal_rows=None, check_edges=True):
+    def as_priors(self):
+        """[Q] Prior (None for a query without a path): the `priors` of a later search_many."""
+        return [_prior_of(self, q) if self.found[q] else None for q in range(self.n_queries)]
+
+    def replan(self, roots=None, advance=None, goal_rows=None, check_edges=True, priors=None):
         """SearchResult.replan for Q queries at once: roots [Q] (node ids; -1 or None: that query's seed), or advance
         (one k for all or [Q]; a query without a path keeps its seed), goal_rows [Q][4D+2] or None.  Every launch of
         the rebase, of the forced round and of the rounds after it is shared by the queries.  Returns a new
@@ -308,7 +417,7 @@ class MultiSearchResult:
         if advance is not None:
             ks = np.broadcast_to(np.asarray(advance, dtype=np.int64), (Q,))
             r = [int(self.table.path(self.goal_id[q])[0][int(ks[q])]) if self.found[q] else -1 for q in range(Q)]
-        return run_replan(self, True, r, goal_rows, check_edges)
+        return run_replan(self, True, r, goal_rows, check_edges, priors)
 
     def free(self):
         if self.open is not None:
@@ -323,7 +432,7 @@ class MultiSearchResult:
 
 
 def run_search_many(env, starts, goal_rows, eps, delta, g_max, max_rounds, max_expand, capacity, max_frontier, lists_stride,
-                    sight, tol_pos, tol_vel, tol_acc, tol_yaw, w, v_max, start_g=0.0):
+                    sight, tol_pos, tol_vel, tol_acc, tol_yaw, w, v_max, start_g=0.0, priors=None):
     env._flush()
     starts = np.ascontiguousarray(starts, dtype=np.float64)
     goal_rows = np.ascontiguousarray(goal_rows, dtype=np.float64)
@@ -343,6 +452,8 @@ def run_search_many(env, starts, goal_rows, eps, delta, g_max, max_rounds, max_e
     try:
         opn = OpenSet(env, tab)
         opn.set_goals(goal_rows, **prm["goal_kw"])
+        if priors is not None:
+            opn.set_prior_list(list(priors))
         sel, imp = TableFrontier(env, fcap), TableFrontier(env, int(capacity))  # (no more nodes can improve than exist)
         lists = env.alloc_lists(fcap, want_state=True, stride=lists_stride)
         count = tab.seed(starts, g0, frontier=imp, query=np.arange(Q, dtype=np.int32))
@@ -362,7 +473,7 @@ def run_search_many(env, starts, goal_rows, eps, delta, g_max, max_rounds, max_e
                 b.free()
 
 
-def run_replan(old, multi, roots, goal_rows, check_edges):
+def run_replan(old, multi, roots, goal_rows, check_edges, priors=None):
     """SearchResult.replan / MultiSearchResult.replan: rebase into a frontier of the table's capacity, clear the open
     set, push the kept nodes closed, expand all of them in chunks of max_frontier rows (the forced round), then the
     loop of the search.  The forced chunks count as rounds and expansions."""
@@ -373,9 +484,16 @@ def run_replan(old, multi, roots, goal_rows, check_edges):
     Q = tab.n_queries
     if goal_rows is not None:
         if multi:
-            opn.set_goals(goal_rows, **prm["goal_kw"])
+            opn.set_goals(goal_rows, **prm["goal_kw"])  # (drops the priors)
         else:
             prm = dict(prm, goal_row=np.array(goal_rows, dtype=np.float64))
+            if prm.get("own_goals"):  # a search with a prior: the open set's own goal decides, not the context's
+                opn.set_goals(prm["goal_row"].reshape(1, -1), **prm["goal_kw"])
+    if priors is not None:
+        if not multi and not prm.get("own_goals"):
+            prm = dict(prm, own_goals=True)
+            opn.set_goals(prm["goal_row"].reshape(1, -1), **prm["goal_kw"])
+        opn.set_prior_list(list(priors))
     if not multi:
         env.set_goal(prm["goal_row"], **prm["goal_kw"])  # (the context's goal may have been moved since the search)
     kept = sel = imp = lists = None
