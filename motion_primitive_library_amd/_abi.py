@@ -63,6 +63,12 @@ MULTI_SYMBOLS = ["mplx_table_create_multi", "mplx_table_query_of", "mplx_table_s
 REPLAN_SYMBOLS = ["mplx_table_rebase_device", "mplx_table_rebase_multi_device", "mplx_open_push_closed_device"]
 # ... and the ones include/mplx_prior.h declares (prior-trajectory guidance of an open set)
 PRIOR_SYMBOLS = ["mplx_open_set_priors_device", "mplx_open_clear_priors", "mplx_open_prior_view_of", "mplx_planner_prior_table"]
+# ... and the ones include/mplx_solve.h declares (the batched trajectory solver and Trajectory on what it returns)
+SOLVE_SYMBOLS = ["mplx_poly_create", "mplx_poly_destroy", "mplx_solve_device", "mplx_solve", "mplx_poly_info_device",
+                 "mplx_poly_info", "mplx_poly_sample_device", "mplx_poly_sample", "mplx_poly_traverse_device",
+                 "mplx_poly_traverse"]
+SOLVE_EMPTY, SOLVE_BAD_TIME, SOLVE_SINGULAR = 1, 2, 8
+USE_POS, USE_VEL, USE_ACC = 1, 2, 4
 
 ROUTE_AUTO, ROUTE_DENSE, ROUTE_TILE, ROUTE_GRID = 0, 1, 2, 3
 
@@ -126,6 +132,19 @@ class TrajSampleOut(C.Structure):
 class TrajTraverseOut(C.Structure):
     _fields_ = [("status", C.c_void_p), ("cost", C.c_void_p), ("n_samples", C.c_void_p), ("n_cells", C.c_void_p),
                 ("stop_sample", C.c_void_p)]
+
+
+class SolveIn(C.Structure):
+    _fields_ = [("waypoints", C.c_void_p), ("n_prob", C.c_int64), ("w_max", C.c_int32), ("wp_stride", C.c_int64),
+                ("n_wp", C.c_void_p), ("dts", C.c_void_p), ("dt_stride", C.c_int64), ("v", C.c_double),
+                ("v_arr", C.c_void_p), ("control", C.c_int32), ("yaw_control", C.c_int32), ("wp_flags", C.c_void_p),
+                ("flag_stride", C.c_int64)]
+
+
+class SolveOut(C.Structure):
+    _fields_ = [("status", C.c_void_p), ("n_segs", C.c_void_p), ("total_time", C.c_void_p), ("coeff", C.c_void_p),
+                ("coeff_stride", C.c_int64), ("dts_out", C.c_void_p), ("dts_out_stride", C.c_int64),
+                ("yaw_coeff", C.c_void_p), ("yaw_stride", C.c_int64), ("taus", C.c_void_p), ("taus_stride", C.c_int64)]
 
 
 class TableView(C.Structure):
@@ -335,6 +354,16 @@ def lib():
         "mplx_traj_sample": (C.c_int, [vp, C.POINTER(TrajSet), C.POINTER(TrajTimes), C.POINTER(TrajSampleOut)]),
         "mplx_traj_traverse_device": (C.c_int, [vp, C.POINTER(TrajSet), i32, C.POINTER(TrajTraverseOut)]),
         "mplx_traj_traverse": (C.c_int, [vp, C.POINTER(TrajSet), i32, C.POINTER(TrajTraverseOut)]),
+        "mplx_poly_create": (C.c_int, [vp, i64, i32, C.POINTER(vp)]),
+        "mplx_poly_destroy": (None, [vp]),
+        "mplx_solve_device": (C.c_int, [vp, C.POINTER(SolveIn), C.POINTER(SolveOut)]),
+        "mplx_solve": (C.c_int, [vp, C.POINTER(SolveIn), C.POINTER(SolveOut)]),
+        "mplx_poly_info_device": (C.c_int, [vp, C.POINTER(TrajInfoOut)]),
+        "mplx_poly_info": (C.c_int, [vp, C.POINTER(TrajInfoOut)]),
+        "mplx_poly_sample_device": (C.c_int, [vp, C.POINTER(TrajTimes), C.POINTER(TrajSampleOut)]),
+        "mplx_poly_sample": (C.c_int, [vp, C.POINTER(TrajTimes), C.POINTER(TrajSampleOut)]),
+        "mplx_poly_traverse_device": (C.c_int, [vp, i32, C.POINTER(TrajTraverseOut)]),
+        "mplx_poly_traverse": (C.c_int, [vp, i32, C.POINTER(TrajTraverseOut)]),
         "mplx_table_create": (C.c_int, [vp, i64, i32, C.POINTER(vp)]),
         "mplx_table_destroy": (None, [vp]),
         "mplx_table_clear": (C.c_int, [vp]),
@@ -367,7 +396,7 @@ def lib():
         "mplx_open_prior_view_of": (C.c_int, [vp, C.POINTER(PriorView)]),
         "mplx_planner_prior_table": (C.c_int, [vp, vp, vp, i32, C.POINTER(i32), vp, C.POINTER(i32)]),
     }
-    for name in SYMBOLS + MAP_UTIL_SYMBOLS + ROLLOUT_SYMBOLS + RAY_SYMBOLS + TRAJ_SYMBOLS + TABLE_SYMBOLS + OPEN_SYMBOLS + MULTI_SYMBOLS + REPLAN_SYMBOLS + PRIOR_SYMBOLS:
+    for name in SYMBOLS + MAP_UTIL_SYMBOLS + ROLLOUT_SYMBOLS + RAY_SYMBOLS + TRAJ_SYMBOLS + TABLE_SYMBOLS + OPEN_SYMBOLS + MULTI_SYMBOLS + REPLAN_SYMBOLS + PRIOR_SYMBOLS + SOLVE_SYMBOLS:
         fn = getattr(L, name)  # AttributeError if the library does not export it
         fn.restype, fn.argtypes = sig[name]
     _lib = L

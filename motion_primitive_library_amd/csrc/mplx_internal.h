@@ -489,10 +489,48 @@ struct TrajArgs {
   // traverse launch, any may be null
   double *cost;
   int32_t *n_samples, *n_cells, *stop_sample;
+  // the table of a solved set (include/mplx_solve.h; appended: every field above keeps its place).  poly == 1: a segment
+  // has 6 D + 2 rows (c0 .. c5 per axis, then the yaw primitive's c4, c5) and its own duration tab_dt[s][N]; the segment
+  // of a time is found by bisection of tab_tau; tab_n is not used (the traversal forms n from T); tab_wp: the waypoints,
+  // [4D+2][horizon + 1][N]; horizon = w_max - 1
+  int32_t poly;
+  const double *tab_dt, *tab_wp;
 };
 hipError_t launch_traj_chain(int dim, int control, const TrajArgs &a, hipStream_t s);
 hipError_t launch_traj_sample(int dim, int form, const TrajArgs &a, hipStream_t s);
 hipError_t launch_traj_traverse(int dim, int lanes, const TrajArgs &a, hipStream_t s);  // lanes in {4, 16, 64}
+
+// ... and on the table of a solved set (a.poly == 1): efforts / waypoints, samples, traversal
+hipError_t launch_poly_info(int dim, const TrajArgs &a, hipStream_t s);
+
+// The batched trajectory solver (solve_kernel.hip, solve_api.cpp; include/mplx_solve.h): one lane per problem, a block
+// tridiagonal LDL^T over the waypoints.  Everything is problem-minor: element (row, k) of an array at [row * stride + k].
+struct SolveArgs {
+  int64_t n_prob, cap;       // problems of this call; the stride of the poly's own arrays (its k_cap)
+  int32_t w_max;
+  int32_t so;                // 0 VEL, 1 ACC, 2 JRK: smoothing order of the ends' control
+  // input
+  const double *waypoints;   // [(f * w_max + w) * wp_stride + k]
+  int64_t wp_stride;
+  const int32_t *n_wp;       // [n_prob] or null: w_max each
+  const double *dts;         // [(w_max - 1)][dt_stride] or null: allocate_time
+  int64_t dt_stride;
+  double v;
+  const double *v_arr;       // [n_prob] or null: v
+  const uint8_t *wp_flags;   // [w_max][flag_stride] use_pos 1 | use_vel 2 | use_acc 4, or null: setPath mode
+  int64_t flag_stride;
+  // the poly: segment table (TrajArgs with poly == 1, stride cap) and the workspace of the elimination
+  int32_t *tab_S;
+  uint8_t *tab_status;
+  double *tab_T, *tab_tau, *tab_seg, *tab_dt, *tab_wp;
+  double *ws;                // per waypoint h * h + h * D rows of cap doubles: Z = G'^-1 C, z = G'^-1 b
+  // outputs, any may be null
+  uint8_t *status;
+  int32_t *n_segs;
+  double *total_time, *coeff, *yaw_coeff, *dts_out, *taus_out;
+  int64_t coeff_stride, yaw_stride, dts_out_stride, taus_stride;
+};
+hipError_t launch_solve(int dim, const SolveArgs &a, hipStream_t s);
 
 // The prior table of an open set (traj_kernel.hip, open_api.cpp; include/mplx_prior.h), built on the segment table of a
 // chain launch with the prior's controls and the `cost` of a traverse launch.

@@ -176,8 +176,18 @@ struct Sample {
 
 // COMMAND: the first id with tau >= taus[id] && tau <= taus[id+1]; WAYPOINT: ... && tau < taus[id+1], else the last.
 // taus grow strictly (dt > 0), so the first match is the smallest id whose upper end admits tau.
-template <bool COMMAND>
+// POLY (a solved set: every segment has its own duration): no guess, a bisection on the stored taus for the same id.
+template <bool COMMAND, bool POLY = false>
 __device__ __forceinline__ int find_segment(const double *taus, int64_t N, int S, double tau, double dt) {
+  if (POLY) {
+    int lo = 0, hi = S - 1;
+    while (lo < hi) {
+      const int mid = (lo + hi) >> 1;
+      const double up = taus[(int64_t)(mid + 1) * N];
+      if (COMMAND ? tau <= up : tau < up) hi = mid; else lo = mid + 1;
+    }
+    return lo;
+  }
   double q = tau / dt;
   q = q >= 0.0 ? q : 0.0;  // (a NaN goes to 0)
   int g = q < (double)(S - 1) ? (int)q : S - 1;
@@ -193,21 +203,32 @@ __device__ __forceinline__ int find_segment(const double *taus, int64_t N, int S
 
 // seg: the segment's rows for this trajectory (stride N); t: tau - taus[id], finite and >= 0.
 // primitive.h:128-145 with c0 = 0 (its term is +0.0: the leading `0.0 +`), power by repeated multiply.
-template <int D, bool COMMAND, bool WANT_ALL>
+// POLY: a solved segment, rows c0 .. c5 per axis: all six terms of primitive.h:128-145, operation for operation.
+template <int D, bool COMMAND, bool WANT_ALL, bool POLY = false>
 __device__ __forceinline__ void eval_segment(const double *seg, int64_t N, double t, Sample<D> &o) {
   const double t3 = (t * t) * t, t4 = t3 * t;
+  constexpr int NA = POLY ? 6 : 5;  // rows per axis
 #pragma unroll
   for (int i = 0; i < D; i++) {
-    const double c1 = seg[(5 * i + 0) * N], c2 = seg[(5 * i + 1) * N], c3 = seg[(5 * i + 2) * N], c4 = seg[(5 * i + 3) * N],
-                 c5 = seg[(5 * i + 4) * N];
-    o.pos[i] = ((((0.0 + c1 / 24 * t4) + c2 / 6 * t3) + c3 / 2 * t * t) + c4 * t) + c5;
-    const double v = (((0.0 + c1 / 6 * t3) + c2 / 2 * t * t) + c3 * t) + c4;
+    const double *sa = seg + (int64_t)(NA * i + (POLY ? 1 : 0)) * N;
+    const double c1 = sa[0 * N], c2 = sa[1 * N], c3 = sa[2 * N], c4 = sa[3 * N], c5 = sa[4 * N];
+    double v, a, j;
+    if (POLY) {
+      const double c0 = seg[(int64_t)(NA * i) * N], t5 = t4 * t;
+      o.pos[i] = ((((c0 / 120 * t5 + c1 / 24 * t4) + c2 / 6 * t3) + c3 / 2 * t * t) + c4 * t) + c5;
+      v = (((c0 / 24 * t4 + c1 / 6 * t3) + c2 / 2 * t * t) + c3 * t) + c4;
+      a = ((c0 / 6 * t3 + c1 / 2 * t * t) + c2 * t) + c3;
+      j = (c0 / 2 * t * t + c1 * t) + c2;
+    } else {
+      o.pos[i] = ((((0.0 + c1 / 24 * t4) + c2 / 6 * t3) + c3 / 2 * t * t) + c4 * t) + c5;
+      v = (((0.0 + c1 / 6 * t3) + c2 / 2 * t * t) + c3 * t) + c4;
+      a = ((0.0 + c1 / 2 * t * t) + c2 * t) + c3;
+      j = (0.0 + c1 * t) + c2;
+    }
     if (!WANT_ALL) {
       o.vel[i] = v;  // (lambda = 1: v / 1)
       continue;
     }
-    const double a = ((0.0 + c1 / 2 * t * t) + c2 * t) + c3;
-    const double j = (0.0 + c1 * t) + c2;
     if (COMMAND) {
       // trajectory.h:119-124 with lambda = 1, lambda_dot = 0, operation for operation
       const double lambda = 1.0, lambda_dot = 0.0;
@@ -222,13 +243,13 @@ __device__ __forceinline__ void eval_segment(const double *seg, int64_t N, doubl
     }
   }
   if (WANT_ALL) {
-    const double uy = seg[(5 * D) * N], y0 = seg[(5 * D + 1) * N];
+    const double uy = seg[(NA * D) * N], y0 = seg[(NA * D + 1) * N];
     o.yaw = pair::wrap_angle((0.0 + uy * t) + y0);
     o.yaw_dot = pair::wrap_angle(0.0 + uy);  // (yes: normalize_angle of the yaw rate, trajectory.h:126)
   }
 }
 
-template <int D, int FORM>
+template <int D, int FORM, bool POLY = false>
 __global__ __launch_bounds__(kBlock) void traj_sample_kernel(const TrajArgs R) {
   const int64_t g = (int64_t)blockIdx.x * kBlock + threadIdx.x;
   const int64_t N = R.n_traj;
@@ -255,10 +276,10 @@ __global__ __launch_bounds__(kBlock) void traj_sample_kernel(const TrajArgs R) {
   if (tau < 0) tau = 0;
   if (tau > T) tau = T;
   const double *taus = R.tab_tau + k;
-  const int id = find_segment<FORM == 0>(taus, N, S, tau, R.env.dt);
+  const int id = find_segment<FORM == 0, POLY>(taus, N, S, tau, R.env.dt);
   tau -= taus[(int64_t)id * N];
   Sample<D> sm;
-  eval_segment<D, FORM == 0, true>(R.tab_seg + (int64_t)id * (5 * D + 2) * N + k, N, tau, sm);
+  eval_segment<D, FORM == 0, true, POLY>(R.tab_seg + (int64_t)id * ((POLY ? 6 : 5) * D + 2) * N + k, N, tau, sm);
 #pragma unroll
   for (int d = 0; d < D; d++) {
     o[(int64_t)(0 * D + d) * R.row_stride] = sm.pos[d];
@@ -273,7 +294,7 @@ __global__ __launch_bounds__(kBlock) void traj_sample_kernel(const TrajArgs R) {
   }
 }
 
-template <int D, int G>
+template <int D, int G, bool POLY = false>
 __global__ __launch_bounds__(kBlock) void traj_traverse_kernel(const TrajArgs R) {
   const ExpandArgs &A = R.env;
   constexpr int kTraj = kBlock / G;
@@ -287,8 +308,16 @@ __global__ __launch_bounds__(kBlock) void traj_traverse_kernel(const TrajArgs R)
   const double org[3] = {A.org0, A.org1, A.org2};
 
   const int S = have ? R.tab_S[k] : 0;
-  const int n = have ? R.tab_n[k] : 0;
   const double T = have ? R.tab_T[k] : 0.0;
+  int n = 0;
+  if (POLY) {  // a solved set outlives parameter changes: n of env_map.h:231 from the v_max and res of now
+    if (S > 0) {
+      const double cn = ceil(A.v_max * T / A.res);
+      n = !(cn < 2147483648.0) ? -1 : cn > 0.0 ? (int)cn : 0;
+    }
+  } else if (have) {
+    n = R.tab_n[k];
+  }
   const bool active = have && S > 0 && n >= 0;
   const double step = T / (double)n;  // trajectory.h:233
   const double *taus = R.tab_tau + (have ? k : 0);
@@ -308,10 +337,10 @@ __global__ __launch_bounds__(kBlock) void traj_traverse_kernel(const TrajArgs R)
     if (has) {
       double tau = (double)i * step;  // >= 0 and finite
       if (tau > T) tau = T;
-      const int id = find_segment<true>(taus, N, S, tau, A.dt);
+      const int id = find_segment<true, POLY>(taus, N, S, tau, A.dt);
       tau -= taus[(int64_t)id * N];
       Sample<D> sm;
-      eval_segment<D, true, false>(R.tab_seg + (int64_t)id * (5 * D + 2) * N + k, N, tau, sm);
+      eval_segment<D, true, false, POLY>(R.tab_seg + (int64_t)id * ((POLY ? 6 : 5) * D + 2) * N + k, N, tau, sm);
       uint32_t ui = 0, mul = 1;
       inside = true;
 #pragma unroll
@@ -545,7 +574,10 @@ template <int D, int FORM>
 hipError_t sample_one(const TrajArgs &a, hipStream_t s) {
   const int64_t blocks = (a.n_traj * a.count + kBlock - 1) / kBlock;
   if (blocks > 0x7fffffffLL) return hipErrorInvalidValue;
-  hipLaunchKernelGGL((traj_sample_kernel<D, FORM>), dim3((unsigned)blocks), dim3(kBlock), 0, s, a);
+  if (a.poly)
+    hipLaunchKernelGGL((traj_sample_kernel<D, FORM, true>), dim3((unsigned)blocks), dim3(kBlock), 0, s, a);
+  else
+    hipLaunchKernelGGL((traj_sample_kernel<D, FORM>), dim3((unsigned)blocks), dim3(kBlock), 0, s, a);
   return hipGetLastError();
 }
 
@@ -553,8 +585,55 @@ template <int D, int G>
 hipError_t traverse_one(const TrajArgs &a, hipStream_t s) {
   const int64_t blocks = (a.n_traj + kBlock / G - 1) / (kBlock / G);
   if (blocks > 0x7fffffffLL) return hipErrorInvalidValue;
-  hipLaunchKernelGGL((traj_traverse_kernel<D, G>), dim3((unsigned)blocks), dim3(kBlock), 0, s, a);
+  if (a.poly)
+    hipLaunchKernelGGL((traj_traverse_kernel<D, G, true>), dim3((unsigned)blocks), dim3(kBlock), 0, s, a);
+  else
+    hipLaunchKernelGGL((traj_traverse_kernel<D, G>), dim3((unsigned)blocks), dim3(kBlock), 0, s, a);
   return hipGetLastError();
+}
+
+// Efforts and waypoints of a solved set (include/mplx_solve.h): one lane per problem over its stored segments.
+// Trajectory::J / Primitive::J as traj_chain_kernel sums them, with the segment's own duration and all of c0 .. c4.
+template <int D>
+__global__ __launch_bounds__(kBlock) void poly_info_kernel(const TrajArgs R) {
+  const int64_t k = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (k >= R.n_traj) return;
+  const int64_t N = R.n_traj;  // (the stride of the table)
+  constexpr int F = 4 * D + 2, NC = 6 * D + 2;
+  const int S = R.tab_S[k];
+  if (R.status) R.status[k] = R.tab_status[k];
+  if (S == 0) return;  // a failed problem: its status only
+  if (R.n_segs) R.n_segs[k] = S;
+  if (R.total_time) R.total_time[k] = R.tab_T[k];
+  if (R.effort) {
+    double e[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+    for (int s = 0; s < S; s++) {
+      const double *seg = R.tab_seg + (int64_t)s * NC * N + k;
+      const double T = R.tab_dt[(int64_t)s * N + k];
+#pragma unroll
+      for (int o = 1; o <= 4; o++) {
+        double j = 0.0;
+#pragma unroll
+        for (int i = 0; i < D; i++) {
+          const double c[5] = {seg[(6 * i + 0) * N], seg[(6 * i + 1) * N], seg[(6 * i + 2) * N], seg[(6 * i + 3) * N],
+                               seg[(6 * i + 4) * N]};
+          j = j + effort_1d(c, T, o);
+        }
+        e[o - 1] = e[o - 1] + j;
+      }
+      const double cy[5] = {0.0, 0.0, 0.0, 0.0, seg[(6 * D) * N]};
+      e[4] = e[4] + effort_1d(cy, T, 1);
+    }
+#pragma unroll
+    for (int o = 0; o < 5; o++) R.effort[(int64_t)o * R.effort_stride + k] = e[o];
+  }
+  if (R.seg_state) {
+    const int64_t W1 = (int64_t)R.horizon + 1;
+    for (int w = 0; w <= S; w++) {
+#pragma unroll
+      for (int f = 0; f < F; f++) R.seg_state[(f * W1 + w) * R.seg_stride + k] = R.tab_wp[(f * W1 + w) * N + k];
+    }
+  }
 }
 
 }  // namespace
@@ -571,6 +650,16 @@ hipError_t launch_traj_sample(int dim, int form, const TrajArgs &a, hipStream_t 
   if (dim == 2) return form == 0 ? sample_one<2, 0>(a, s) : sample_one<2, 1>(a, s);
   if (dim == 3) return form == 0 ? sample_one<3, 0>(a, s) : sample_one<3, 1>(a, s);
   return hipErrorInvalidValue;
+}
+
+hipError_t launch_poly_info(int dim, const TrajArgs &a, hipStream_t s) {
+  if (a.n_traj == 0) return hipSuccess;
+  const int64_t blocks = (a.n_traj + kBlock - 1) / kBlock;
+  if (blocks > 0x7fffffffLL) return hipErrorInvalidValue;
+  if (dim == 2) hipLaunchKernelGGL((poly_info_kernel<2>), dim3((unsigned)blocks), dim3(kBlock), 0, s, a);
+  else if (dim == 3) hipLaunchKernelGGL((poly_info_kernel<3>), dim3((unsigned)blocks), dim3(kBlock), 0, s, a);
+  else return hipErrorInvalidValue;
+  return hipGetLastError();
 }
 
 hipError_t launch_prior_build(int dim, int control, const PriorArgs &a, hipStream_t s) {

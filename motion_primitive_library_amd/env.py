@@ -36,6 +36,8 @@ RAY_LEFT_MAP, RAY_HIT, RAY_BAD, RAY_TRUNCATED = _abi.RAY_LEFT_MAP, _abi.RAY_HIT,
 FLAG_GOAL_BLOCKED = _abi.FLAG_GOAL_BLOCKED
 TRAJ_EMPTY, TRAJ_BAD_ACTION, TRAJ_BAD = _abi.TRAJ_EMPTY, _abi.TRAJ_BAD_ACTION, _abi.TRAJ_BAD  # include/mplx_traj.h
 TRAJ_COMMAND, TRAJ_WAYPOINT = _abi.TRAJ_COMMAND, _abi.TRAJ_WAYPOINT
+SOLVE_EMPTY, SOLVE_BAD_TIME, SOLVE_SINGULAR = _abi.SOLVE_EMPTY, _abi.SOLVE_BAD_TIME, _abi.SOLVE_SINGULAR  # include/mplx_solve.h
+USE_POS, USE_VEL, USE_ACC = _abi.USE_POS, _abi.USE_VEL, _abi.USE_ACC
 
 
 class Waypoint:
@@ -333,6 +335,196 @@ class TrajTraverse:
     def free(self):
         for b in (self.status, self.cost, self.n_samples, self.n_cells, self.stop_sample):
             b.free()
+
+
+def _solve_order(control):
+    """Smoothing order of a control flag (traj_solver.h:22-27): 0 VEL, 1 ACC, 2 JRK."""
+    try:
+        return {VEL: 0, ACC: 1, JRK: 2}[int(control) & 0x0F]
+    except KeyError:
+        raise ValueError("the trajectory solver takes VEL, ACC or JRK controls, got %#x" % int(control))
+
+
+class SolveOut:
+    """HBM-resident rows of mplx_solve_out for n problems of up to w_max waypoints with smoothing order so."""
+
+    def __init__(self, env, n, w_max, so):
+        self.n, self.w_max, self.so, self.dim = int(n), int(w_max), int(so), env.dim
+        n, S = max(self.n, 1), self.w_max - 1
+        self.rows = S * 2 * (self.so + 1) * self.dim
+        self.status = DeviceArray(env, n)
+        self.n_segs = DeviceArray(env, n * 4)
+        self.total_time = DeviceArray(env, n * 8)
+        self.coeff = DeviceArray(env, max(self.rows, 1) * n * 8)
+        self.dts = DeviceArray(env, S * n * 8)
+        self.yaw_coeff = DeviceArray(env, 2 * S * n * 8)
+        self.taus = DeviceArray(env, self.w_max * n * 8)
+
+    def c_struct(self):
+        s = _abi.SolveOut()
+        s.status, s.n_segs, s.total_time = self.status.ptr, self.n_segs.ptr, self.total_time.ptr
+        s.coeff, s.dts_out, s.yaw_coeff, s.taus = self.coeff.ptr, self.dts.ptr, self.yaw_coeff.ptr, self.taus.ptr
+        s.coeff_stride = s.dts_out_stride = s.yaw_stride = s.taus_stride = self.n
+        return s
+
+    def download(self):
+        """Rows the solve did not own (failed problems, segments past S_k) hold whatever the buffers held."""
+        n, S = self.n, self.w_max - 1
+        return {"status": self.status.download(np.uint8, (n,)), "n_segs": self.n_segs.download(np.int32, (n,)),
+                "total_time": self.total_time.download(np.float64, (n,)),
+                "coeff": self.coeff.download(np.float64, (S, 2 * (self.so + 1), self.dim, n)),
+                "dts": self.dts.download(np.float64, (S, n)), "yaw_coeff": self.yaw_coeff.download(np.float64, (S, 2, n)),
+                "taus": self.taus.download(np.float64, (self.w_max, n))}
+
+    def free(self):
+        for b in (self.status, self.n_segs, self.total_time, self.coeff, self.dts, self.yaw_coeff, self.taus):
+            b.free()
+
+
+class PolyTrajSet:
+    """K solved trajectories on the device (mplx_poly of include/mplx_solve.h): what EnvMap.solve_traj returns and what
+    EnvMap.solve_traj_resident solves into.  status [K] (SOLVE_EMPTY | SOLVE_BAD_TIME | SOLVE_SINGULAR; 0 = solved);
+    a failed problem has no samples and traverses as an empty trajectory.  free() it before the EnvMap is closed."""
+
+    def __init__(self, env, k_cap, w_max):
+        self._env, self.k_cap, self.w_max = env, int(k_cap), int(w_max)
+        self.n, self.so, self.n_wmax = 0, None, 0
+        self._host, self._out = None, None
+        h = C.c_void_p()
+        _abi.check(env._ctx, _abi.lib().mplx_poly_create(env._ctx, self.k_cap, self.w_max, C.byref(h)))
+        self._h = h
+
+    def free(self):
+        if self._h is not None and self._env._ctx:
+            _abi.lib().mplx_poly_destroy(self._h)
+        self._h = None
+        if self._out is not None:
+            self._out.free()
+            self._out = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+    def _rows(self):
+        """The rows of the last solve on the host: from the host-pointer solve, or downloaded from its SolveOut."""
+        if self._host is None:
+            if self._out is None:
+                raise RuntimeError("PolyTrajSet: the solve kept no output rows (solve_traj_resident without out)")
+            self._env.synchronize()
+            d = self._out.download()
+            ok = d["status"] == 0
+            d["n_segs"] = np.where(ok, d["n_segs"], 0)
+            d["total_time"] = np.where(ok, d["total_time"], 0.0)
+            seg = np.arange(self._out.w_max - 1)[:, None] < d["n_segs"][None, :]
+            d["coeff"] = np.where(seg[:, None, None, :], d["coeff"], 0.0)
+            d["dts"] = np.where(seg, d["dts"], 0.0)
+            d["yaw_coeff"] = np.where(seg[:, None, :], d["yaw_coeff"], 0.0)
+            d["taus"] = np.where(np.arange(self._out.w_max)[:, None] <= d["n_segs"][None, :], d["taus"], 0.0) * ok[None, :]
+            self._host = d
+        return self._host
+
+    @property
+    def status(self):
+        return self._rows()["status"]
+
+    @property
+    def n_segs(self):
+        return self._rows()["n_segs"]
+
+    @property
+    def total_time(self):
+        return self._rows()["total_time"]
+
+    def coefficients(self):
+        """PolyTraj::p() of every problem: [w_max - 1][N][D][K], coefficient r of axis i of segment s at [s][r][i][k]
+        (increasing powers of the segment's own time); zero past S_k and for a failed problem."""
+        return self._rows()["coeff"]
+
+    def yaw_coefficients(self):
+        """The yaw solve's p: [w_max - 1][2][K]."""
+        return self._rows()["yaw_coeff"]
+
+    def dts(self):
+        """[w_max - 1][K] segment durations (given, or allocate_time's); zero past S_k."""
+        return self._rows()["dts"]
+
+    def taus(self):
+        """[w_max][K]: taus[0 .. S_k] by sequential addition of dts."""
+        return self._rows()["taus"]
+
+    def _need(self):
+        if self._h is None or self.n == 0:
+            raise RuntimeError("PolyTrajSet: nothing solved (or freed)")
+        self._env._flush()
+
+    def info(self, want_states=False):
+        """status, n_segs, total_time, effort [5][K] = J(VEL), J(ACC), J(JRK), J(SNP), Jyaw of the solved primitives;
+        want_states: seg_state [4D+2][w_max][K], the waypoints (mplx_poly_info; synchronous)."""
+        self._need()
+        K, env = self.n, self._env
+        out = {"status": np.zeros(K, np.uint8), "n_segs": np.zeros(K, np.int32), "total_time": np.zeros(K, np.float64),
+               "effort": np.zeros((5, K), np.float64)}
+        o = _abi.TrajInfoOut()
+        o.status, o.n_segs, o.total_time = out["status"].ctypes.data, out["n_segs"].ctypes.data, out["total_time"].ctypes.data
+        o.effort, o.effort_stride = out["effort"].ctypes.data, K
+        if want_states:
+            out["seg_state"] = np.zeros((env.n_fields, self.n_wmax, K), np.float64)
+            o.seg_state, o.seg_stride = out["seg_state"].ctypes.data, K
+        _abi.check(env._ctx, _abi.lib().mplx_poly_info(self._h, C.byref(o)))
+        return out
+
+    def sample(self, N=None, times=None, form=TRAJ_COMMAND, out=None):
+        """As EnvMap.traj_sample on the solved set (mplx_poly_sample; synchronous): samples [4D+3][K][count], status."""
+        self._need()
+        K, env = self.n, self._env
+        t, tkeep, count = env._traj_times(N, times, form, K)
+        rows = 4 * env.dim + 3
+        if out is None:
+            out = np.zeros((rows, K, max(count, 0)), np.float64)
+        if out.dtype != np.float64 or not out.flags.c_contiguous or out.ndim != 3 or out.shape[0] != rows or out.shape[1] < K:
+            raise ValueError("out must be a C-contiguous float64 [%d][>= K][count']" % rows)
+        status = np.zeros(K, np.uint8)
+        o = _abi.TrajSampleOut()
+        o.out, o.row_stride, o.sample_stride, o.status = out.ctypes.data, out.shape[1] * out.shape[2], out.shape[2], status.ctypes.data
+        _abi.check(env._ctx, _abi.lib().mplx_poly_sample(self._h, C.byref(t), C.byref(o)))
+        return {"samples": out, "status": status}
+
+    def traverse(self, lanes=0):
+        """As EnvMap.traj_traverse on the solved set, on the maps the device holds now (mplx_poly_traverse)."""
+        self._need()
+        K, env = self.n, self._env
+        out = {"status": np.zeros(K, np.uint8), "cost": np.zeros(K, np.float64), "n_samples": np.zeros(K, np.int32),
+               "n_cells": np.zeros(K, np.int32), "stop_sample": np.zeros(K, np.int32)}
+        o = _abi.TrajTraverseOut()
+        for key in out:
+            setattr(o, key, out[key].ctypes.data)
+        _abi.check(env._ctx, _abi.lib().mplx_poly_traverse(self._h, int(lanes), C.byref(o)))
+        return out
+
+    # asynchronous forms on HBM-resident rows (env.TrajInfo / TrajSamples / TrajTraverse); synchronize() before reading
+    def info_resident(self, out):
+        self._need()
+        o = out.c_struct()
+        _abi.check(self._env._ctx, _abi.lib().mplx_poly_info_device(self._h, C.byref(o)))
+
+    def sample_resident(self, out, N=None, times=None, n_times=None, time_stride=0, form=TRAJ_COMMAND):
+        self._need()
+        t = _abi.TrajTimes()
+        t.form = int(form)
+        if N is not None:
+            t.n_uniform = int(N)
+        else:
+            t.times, t.n_times, t.time_stride = _device_ptr(times), int(n_times), int(time_stride)
+        o = out.c_struct()
+        _abi.check(self._env._ctx, _abi.lib().mplx_poly_sample_device(self._h, C.byref(t), C.byref(o)))
+
+    def traverse_resident(self, out, lanes=0):
+        self._need()
+        o = out.c_struct()
+        _abi.check(self._env._ctx, _abi.lib().mplx_poly_traverse_device(self._h, int(lanes), C.byref(o)))
 
 
 STATE_ROW_PAD = 0  # default padding between the state rows of Lists, in entries (see Lists.state_stride)
@@ -1274,6 +1466,100 @@ class EnvMap:
                                   action_stride)
         o = out.c_struct()
         _abi.check(self._ctx, _abi.lib().mplx_traj_traverse_device(self._ctx, C.byref(s), int(lanes), C.byref(o)))
+
+    # ---- the trajectory solver (include/mplx_solve.h): TrajSolver / PolySolver::solve for K problems in one launch
+    def alloc_poly(self, k_cap, w_max):
+        return PolyTrajSet(self, k_cap, w_max)
+
+    def alloc_solve_out(self, n, w_max, control=None):
+        return SolveOut(self, n, w_max, _solve_order(self._p.control if control is None else control))
+
+    def solve_traj(self, waypoints, n_wp=None, dts=None, v=1.0, control=None, wp_flags=None, yaw_control=VEL):
+        """Minimum-velocity / acceleration / jerk polynomials through K waypoint lists (mplx_solve; synchronous).
+        waypoints: state rows [4D+2][w_max][K] (the seg_state of traj_info(want_states=True)), or positions [D][w_max][K]
+        (every other field zero); n_wp [K] or None (w_max each); dts [w_max - 1][K] or None: allocate_time with v, a
+        scalar or [K]; control: of the two ends (default: the EnvMap's), VEL / ACC / JRK; wp_flags [w_max][K] USE_POS |
+        USE_VEL | USE_ACC (TrajSolver::setWaypoints), or None: interior waypoints fix their position only
+        (TrajSolver::setPath).  Returns a PolyTrajSet."""
+        self._flush()
+        control = int(self._p.control if control is None else control)
+        so = _solve_order(control)
+        wp = np.asarray(waypoints, dtype=np.float64)
+        if wp.ndim == 2:
+            wp = wp[:, :, None]
+        if wp.ndim != 3 or wp.shape[0] not in (self.dim, self.n_fields):
+            raise ValueError("waypoints must be [%d][w_max][K] or [%d][w_max][K]" % (self.n_fields, self.dim))
+        if wp.shape[0] == self.dim:
+            full = np.zeros((self.n_fields,) + wp.shape[1:])
+            full[:self.dim] = wp
+            wp = full
+        wp = np.ascontiguousarray(wp)
+        W, K = wp.shape[1], wp.shape[2]
+        poly = PolyTrajSet(self, max(K, 1), max(W, 2))
+        try:
+            i = _abi.SolveIn()
+            i.waypoints, i.n_prob, i.w_max, i.wp_stride = wp.ctypes.data, K, W, K
+            keep = [wp]
+            if n_wp is not None:
+                n_wp = np.ascontiguousarray(np.broadcast_to(np.asarray(n_wp, dtype=np.int32), (K,)))
+                i.n_wp = n_wp.ctypes.data
+            if dts is not None:
+                dts = np.ascontiguousarray(np.asarray(dts, dtype=np.float64).reshape(W - 1, K))
+                i.dts, i.dt_stride = dts.ctypes.data, K
+            if np.ndim(v) == 0:
+                i.v = float(v)
+            else:
+                v = np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=np.float64), (K,)))
+                i.v_arr = v.ctypes.data
+            if wp_flags is not None:
+                wp_flags = np.ascontiguousarray(np.asarray(wp_flags, dtype=np.uint8).reshape(W, K))
+                i.wp_flags, i.flag_stride = wp_flags.ctypes.data, K
+            i.control, i.yaw_control = control, int(yaw_control)
+            N, S = 2 * (so + 1), W - 1
+            host = {"status": np.zeros(K, np.uint8), "n_segs": np.zeros(K, np.int32), "total_time": np.zeros(K, np.float64),
+                    "coeff": np.zeros((S, N, self.dim, K)), "dts": np.zeros((S, K)), "yaw_coeff": np.zeros((S, 2, K)),
+                    "taus": np.zeros((W, K))}
+            o = _abi.SolveOut()
+            o.status, o.n_segs, o.total_time = host["status"].ctypes.data, host["n_segs"].ctypes.data, host["total_time"].ctypes.data
+            o.coeff, o.dts_out, o.yaw_coeff, o.taus = (host[k].ctypes.data for k in ("coeff", "dts", "yaw_coeff", "taus"))
+            o.coeff_stride = o.dts_out_stride = o.yaw_stride = o.taus_stride = K
+            _abi.check(self._ctx, _abi.lib().mplx_solve(poly._h, C.byref(i), C.byref(o)))
+            poly.n, poly.so, poly.n_wmax, poly._host = K, so, W, host
+            return poly
+        except Exception:
+            poly.free()
+            raise
+
+    def solve_traj_resident(self, poly, waypoints, n_prob, w_max, wp_stride=None, n_wp=None, dts=None, dt_stride=None, v=1.0,
+                            v_arr=None, control=None, wp_flags=None, flag_stride=None, out=None, yaw_control=VEL):
+        """Asynchronous on HBM-resident buffers (mplx_solve_device): waypoints / n_wp / dts / v_arr / wp_flags are
+        DeviceArrays or anything with .ptr / data_ptr() (torch tensors); strides default to n_prob.  poly: alloc_poly;
+        out: alloc_solve_out (then owned by poly: coefficients() / dts() / status download from it) or None."""
+        self._flush()
+        control = int(self._p.control if control is None else control)
+        so = _solve_order(control)
+        K = int(n_prob)
+        i = _abi.SolveIn()
+        i.waypoints, i.n_prob, i.w_max = _device_ptr(waypoints), K, int(w_max)
+        i.wp_stride = K if wp_stride is None else int(wp_stride)
+        if n_wp is not None:
+            i.n_wp = _device_ptr(n_wp)
+        if dts is not None:
+            i.dts, i.dt_stride = _device_ptr(dts), K if dt_stride is None else int(dt_stride)
+        i.v = float(v)
+        if v_arr is not None:
+            i.v_arr = _device_ptr(v_arr)
+        if wp_flags is not None:
+            i.wp_flags, i.flag_stride = _device_ptr(wp_flags), K if flag_stride is None else int(flag_stride)
+        i.control, i.yaw_control = control, int(yaw_control)
+        if out is not None and (out.n != K or out.w_max != int(w_max) or out.so != so):
+            raise ValueError("out was allocated for another problem count, w_max or control")
+        o = out.c_struct() if out is not None else _abi.SolveOut()
+        _abi.check(self._ctx, _abi.lib().mplx_solve_device(poly._h, C.byref(i), C.byref(o)))
+        if poly._out is not None and poly._out is not out:
+            poly._out.free()
+        poly.n, poly.so, poly.n_wmax, poly._host, poly._out = K, so, int(w_max), None, out
+        return poly
 
     # ---- the persistent node table (include/mplx_table.h; table.py): relax successor lists, emit the next frontier
     def alloc_table(self, capacity, slots_log2=0, n_queries=1):

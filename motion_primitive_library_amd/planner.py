@@ -507,3 +507,70 @@ class MapPlanner:
             raise RuntimeError("traverseTraj: the last plan has no trajectory")
         r = self.env.traj_traverse(np.asarray(traj.nodes[0], dtype=np.float64), np.asarray(traj.actions, dtype=np.int32).reshape(-1, 1))
         return float(r["cost"][0]), int(r["stop_sample"][0])
+
+
+class TrajSolver:
+    """TrajSolver<Dim> (reference include/mpl_traj_solver/traj_solver.h): the minimum-velocity / acceleration / jerk
+    polynomial through waypoints, solved on the device (include/mplx_solve.h; EnvMap.solve_traj is the batched form).
+    control: of the two ends, VEL / ACC / JRK; yaw_control: VEL.  env: the EnvMap to solve on (one is made otherwise)."""
+
+    def __init__(self, dim, control, yaw_control=0x01, env=None, device=0):
+        from .env import _solve_order
+        _solve_order(control)
+        self.dim, self.control, self.yaw_control = int(dim), int(control), int(yaw_control)
+        self._env, self._own_env = (env, False) if env is not None else (EnvMap(dim, device), True)
+        self._waypoints, self._flags, self._path = [], None, np.zeros((0, dim))
+        self._dts, self._v = [], 1.0
+
+    def close(self):
+        if self._own_env and self._env is not None:
+            self._env.close()
+        self._env = None
+
+    def setWaypoints(self, ws):
+        """Waypoints with their own control flags (use_pos / use_vel / use_acc = the low bits of Waypoint.control)."""
+        self._waypoints = [Waypoint(self.dim, w.control, w.pos, w.vel, w.acc, w.jrk, w.yaw, w.t) for w in ws]
+        self._path = np.array([w.pos for w in self._waypoints], dtype=np.float64).reshape(-1, self.dim)
+        self._flags = np.array([int(w.control) & 0x07 for w in self._waypoints], dtype=np.uint8)
+
+    def setV(self, v):
+        self._v = float(v)
+
+    def setDts(self, dts):
+        self._dts = [float(x) for x in dts]
+
+    def setPath(self, path):
+        """Positions only: interior waypoints are Control::VEL, the ends the solver's control; vel / acc / jrk / yaw are
+        zeroed as the reference does (traj_solver.h:55-70)."""
+        self._path = np.asarray(path, dtype=np.float64).reshape(-1, self.dim)
+        self._waypoints = [Waypoint(self.dim, 0x01, p) for p in self._path]
+        if self._waypoints:
+            self._waypoints[0].control = self._waypoints[-1].control = self.control
+        self._flags = None
+
+    def solve(self):
+        """Returns the PolyTrajSet of the one problem (status, coefficients(), sample(), info(), traverse())."""
+        W = len(self._waypoints)
+        rows = np.zeros((self._env.n_fields, max(W, 2), 1))
+        for w, wp in enumerate(self._waypoints):
+            rows[:, w, 0] = wp.to_row()
+        given = len(self._dts) + 1 == W  # traj_solver.h:74
+        dts = np.asarray(self._dts, dtype=np.float64).reshape(-1, 1) if given and W >= 2 else None
+        flags = None
+        if self._flags is not None:
+            flags = np.zeros((max(W, 2), 1), np.uint8)
+            flags[:W, 0] = self._flags
+        out = self._env.solve_traj(rows, n_wp=[W], dts=dts, v=self._v, control=self.control, wp_flags=flags,
+                                   yaw_control=self.yaw_control)
+        if not given and out.status[0] == 0:
+            self._dts = [float(x) for x in out.dts()[:W - 1, 0]]
+        return out
+
+    def getPath(self):
+        return self._path.copy()
+
+    def getWaypoints(self):
+        return list(self._waypoints)
+
+    def getDts(self):
+        return list(self._dts)

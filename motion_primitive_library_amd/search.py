@@ -221,6 +221,54 @@ class OpenSet:
         return {"n_nodes": n, "f": self._table._read(v.f, np.float64, n), "flags": self._table._read(v.flags, np.uint8, n)}
 
 
+def _smooth(env, paths, v, control):
+    """The paths [(start, actions) or None] of Q queries -> chain states on the device (mplx_traj_info_device, want_states)
+    -> one mplx_solve_device for Q x n_v problems, problem vi * Q + q = path q at speed v[vi]; the states never visit the
+    host.  A query without a path is an empty problem (SOLVE_EMPTY)."""
+    from .env import DeviceArray
+    env._flush()
+    vs = np.atleast_1d(np.asarray(v, dtype=np.float64)).ravel()
+    Q, nv = len(paths), len(vs)
+    K = Q * nv
+    H = max([len(p[1]) for p in paths if p is not None] + [1])
+    starts = np.zeros((env.n_fields, K))
+    actions = np.full((H, K), -1, np.int32)
+    n_wp = np.zeros(K, np.int32)
+    for q, p in enumerate(paths):
+        if p is None:
+            continue
+        for vi in range(nv):
+            k = vi * Q + q
+            starts[:, k] = p[0]
+            actions[:len(p[1]), k] = p[1]
+            n_wp[k] = len(p[1]) + 1
+    bufs = [DeviceArray(env, a.nbytes) for a in (starts, actions, n_wp, np.zeros(K))]
+    info = poly = None
+    try:
+        for b, a in zip(bufs, (starts, actions, n_wp, np.repeat(vs, Q))):
+            b.upload(a)
+        info = env.alloc_traj_info(K, H, want_states=True)
+        env.traj_info_resident(bufs[0], bufs[1], info, H)
+        poly = env.alloc_poly(K, H + 1)
+        out = env.alloc_solve_out(K, H + 1, control)
+        try:
+            env.solve_traj_resident(poly, info.seg_state, K, H + 1, n_wp=bufs[2], v_arr=bufs[3], control=control, out=out)
+        except Exception:
+            out.free()
+            raise
+        env.synchronize()
+        return poly
+    except Exception:
+        if poly is not None:
+            poly.free()
+        raise
+    finally:
+        for b in bufs:
+            b.free()
+        if info is not None:
+            info.free()
+
+
 class SearchResult:
     """What EnvMap.search returns.  status: FOUND, EMPTY (no open node left: the goal region is not reachable within
     g_max), MAX_ROUNDS or MAX_EXPAND (stopped early; the nodes selected last are open again); cost: g of the goal node
@@ -250,6 +298,11 @@ class SearchResult:
     def as_prior(self):
         """This result's path as the Prior of a later search (with the control set this search ran with)."""
         return _prior_of(self, None)
+
+    def smooth(self, v=1.0, control=None):
+        """The path smoothed into a polynomial through its chain states (include/mplx_solve.h): v a scalar or [n_v]
+        speeds of the time allocation -> a PolyTrajSet of n_v problems; control: of the ends (default: the EnvMap's)."""
+        return _smooth(self._env, [self.path()], v, control)
 
     def replan(self, root=None, advance=None, goal_row=None, check_edges=True, prior=None):
         """Plans again on the table of this search after the robot has moved and / or the map was edited
@@ -400,6 +453,11 @@ class MultiSearchResult:
     def as_priors(self):
         """[Q] Prior (None for a query without a path): the `priors` of a later search_many."""
         return [_prior_of(self, q) if self.found[q] else None for q in range(self.n_queries)]
+
+    def smooth(self, v=1.0, control=None):
+        """SearchResult.smooth for every query in one solve: a PolyTrajSet of Q x n_v problems, problem vi * Q + q = the
+        path of query q at speed v[vi]; a query without a path is SOLVE_EMPTY."""
+        return _smooth(self._env, [self.path(q) if self.found[q] else None for q in range(self.n_queries)], v, control)
 
     def replan(self, roots=None, advance=None, goal_rows=None, check_edges=True, priors=None):
         """SearchResult.replan for Q queries at once: roots [Q] (node ids; -1 or None: that query's seed), or advance
