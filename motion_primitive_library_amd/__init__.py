@@ -11,11 +11,12 @@ from .env import (ACC, ACCxYAW, JRK, JRKxYAW, SNP, SNPxYAW, VEL, VELxYAW, SLOT_B
                   SLOT_SKIP_DYN, SLOT_SKIP_SAME, ROLLOUT_BAD_ACTION, ROLLOUT_HEADING_BAND, RAY_LEFT_MAP, RAY_HIT, RAY_BAD,
                   RAY_TRUNCATED, FLAG_GOAL_BLOCKED, TRAJ_EMPTY, TRAJ_BAD_ACTION, TRAJ_BAD, TRAJ_COMMAND,
                   TRAJ_WAYPOINT, SOLVE_EMPTY, SOLVE_BAD_TIME, SOLVE_SINGULAR, USE_POS, USE_VEL, USE_ACC, PolyTrajSet, SolveOut,
+                  LIMITS_REFERENCE, LIMITS_ALL_ROOTS, EXCEED_VEL, EXCEED_ACC, EXCEED_JRK, PolyLimits, LoadOut, ShortcutResult, SHORTCUT_BAD_CHAIN,
                   TrajInfo, TrajSamples, TrajTraverse, Rays, DeviceArray, EnvMap, Lists, PackedLists,
                   Rollouts, Slots, Waypoint, lists_from_dense, pack_host_lists)
 
 from .table import NodeTable, TableFrontier
-from .search import MultiSearchResult, OpenSet, Prior, SearchResult
+from .search import MultiSearchResult, OpenSet, Prior, SearchResult, pick_fastest
 from .planner import MapPlanner, MapUtil, Trajectory, TrajSolver
 
 __all__ = ["MapPlanner", "MapUtil", "Trajectory", "EnvMap", "Waypoint", "Slots", "Lists", "lists_from_dense", "PackedLists", "pack_host_lists", "DeviceArray", "workloads", "VEL", "ACC", "JRK", "SNP", "VELxYAW",
@@ -23,4 +24,5 @@ __all__ = ["MapPlanner", "MapUtil", "Trajectory", "EnvMap", "Waypoint", "Slots",
            "ROLLOUT_BAD_ACTION", "ROLLOUT_HEADING_BAND", "Rollouts", "Rays", "RAY_LEFT_MAP", "RAY_HIT", "RAY_BAD", "RAY_TRUNCATED",
            "FLAG_GOAL_BLOCKED", "TRAJ_EMPTY", "TRAJ_BAD_ACTION", "TRAJ_BAD", "TRAJ_COMMAND", "TRAJ_WAYPOINT", "TrajInfo",
            "TrajSamples", "TrajTraverse", "NodeTable", "TableFrontier", "OpenSet", "SearchResult", "MultiSearchResult", "Prior",
-           "PolyTrajSet", "SolveOut", "TrajSolver", "SOLVE_EMPTY", "SOLVE_BAD_TIME", "SOLVE_SINGULAR", "USE_POS", "USE_VEL", "USE_ACC"]
+           "PolyTrajSet", "SolveOut", "TrajSolver", "SOLVE_EMPTY", "SOLVE_BAD_TIME", "SOLVE_SINGULAR", "USE_POS", "USE_VEL", "USE_ACC",
+           "LIMITS_REFERENCE", "LIMITS_ALL_ROOTS", "EXCEED_VEL", "EXCEED_ACC", "EXCEED_JRK", "PolyLimits", "LoadOut", "ShortcutResult", "SHORTCUT_BAD_CHAIN", "pick_fastest"]

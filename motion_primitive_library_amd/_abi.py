@@ -69,6 +69,12 @@ SOLVE_SYMBOLS = ["mplx_poly_create", "mplx_poly_destroy", "mplx_solve_device", "
                  "mplx_poly_traverse"]
 SOLVE_EMPTY, SOLVE_BAD_TIME, SOLVE_SINGULAR = 1, 2, 8
 USE_POS, USE_VEL, USE_ACC = 1, 2, 4
+# ... and the ones include/mplx_limits.h declares (caller-given segments in a poly, and the dynamic limits of a set)
+LIMITS_SYMBOLS = ["mplx_poly_load_device", "mplx_poly_load", "mplx_poly_limits_device", "mplx_poly_limits",
+                  "mplx_shortcut_device", "mplx_shortcut"]
+SHORTCUT_BAD_CHAIN = 16
+LIMITS_REFERENCE, LIMITS_ALL_ROOTS = 0, 1
+EXCEED_VEL, EXCEED_ACC, EXCEED_JRK = 1, 2, 4
 
 ROUTE_AUTO, ROUTE_DENSE, ROUTE_TILE, ROUTE_GRID = 0, 1, 2, 3
 
@@ -145,6 +151,36 @@ class SolveOut(C.Structure):
     _fields_ = [("status", C.c_void_p), ("n_segs", C.c_void_p), ("total_time", C.c_void_p), ("coeff", C.c_void_p),
                 ("coeff_stride", C.c_int64), ("dts_out", C.c_void_p), ("dts_out_stride", C.c_int64),
                 ("yaw_coeff", C.c_void_p), ("yaw_stride", C.c_int64), ("taus", C.c_void_p), ("taus_stride", C.c_int64)]
+
+
+class PolyLoadIn(C.Structure):
+    _fields_ = [("n_prob", C.c_int64), ("w_max", C.c_int32), ("control", C.c_int32), ("n_segs", C.c_void_p),
+                ("dts", C.c_void_p), ("dt_stride", C.c_int64), ("coeff", C.c_void_p), ("coeff_stride", C.c_int64),
+                ("src", C.c_void_p), ("src_index", C.c_void_p), ("index_stride", C.c_int64)]
+
+
+class PolyLoadOut(C.Structure):
+    _fields_ = [("status", C.c_void_p), ("n_segs", C.c_void_p), ("total_time", C.c_void_p), ("taus", C.c_void_p),
+                ("taus_stride", C.c_int64)]
+
+
+class ShortcutIn(C.Structure):
+    _fields_ = [("states", C.c_void_p), ("n_query", C.c_int64), ("w_max", C.c_int32), ("control", C.c_int32),
+                ("stride", C.c_int64), ("n_wp", C.c_void_p), ("max_hop", C.c_int32)]
+
+
+class ShortcutOut(C.Structure):
+    _fields_ = [("status", C.c_void_p), ("n_keep", C.c_void_p), ("keep", C.c_void_p), ("keep_stride", C.c_int64),
+                ("cost", C.c_void_p), ("chain_cost", C.c_void_p), ("edge_cost", C.c_void_p), ("pair_out", C.POINTER(SolveOut))]
+
+
+class LimitsIn(C.Structure):
+    _fields_ = [("mv", C.c_double), ("ma", C.c_double), ("mj", C.c_double), ("mode", C.c_int32)]
+
+
+class LimitsOut(C.Structure):
+    _fields_ = [("max_vel", C.c_void_p), ("max_acc", C.c_void_p), ("max_jrk", C.c_void_p), ("max_stride", C.c_int64),
+                ("exceed", C.c_void_p), ("valid", C.c_void_p), ("first_bad", C.c_void_p)]
 
 
 class TableView(C.Structure):
@@ -364,6 +400,12 @@ def lib():
         "mplx_poly_sample": (C.c_int, [vp, C.POINTER(TrajTimes), C.POINTER(TrajSampleOut)]),
         "mplx_poly_traverse_device": (C.c_int, [vp, i32, C.POINTER(TrajTraverseOut)]),
         "mplx_poly_traverse": (C.c_int, [vp, i32, C.POINTER(TrajTraverseOut)]),
+        "mplx_poly_load_device": (C.c_int, [vp, C.POINTER(PolyLoadIn), C.POINTER(PolyLoadOut)]),
+        "mplx_poly_load": (C.c_int, [vp, C.POINTER(PolyLoadIn), C.POINTER(PolyLoadOut)]),
+        "mplx_poly_limits_device": (C.c_int, [vp, C.POINTER(LimitsIn), C.POINTER(LimitsOut)]),
+        "mplx_poly_limits": (C.c_int, [vp, C.POINTER(LimitsIn), C.POINTER(LimitsOut)]),
+        "mplx_shortcut_device": (C.c_int, [vp, vp, C.POINTER(ShortcutIn), C.POINTER(ShortcutOut)]),
+        "mplx_shortcut": (C.c_int, [vp, vp, C.POINTER(ShortcutIn), C.POINTER(ShortcutOut)]),
         "mplx_table_create": (C.c_int, [vp, i64, i32, C.POINTER(vp)]),
         "mplx_table_destroy": (None, [vp]),
         "mplx_table_clear": (C.c_int, [vp]),
@@ -396,7 +438,7 @@ def lib():
         "mplx_open_prior_view_of": (C.c_int, [vp, C.POINTER(PriorView)]),
         "mplx_planner_prior_table": (C.c_int, [vp, vp, vp, i32, C.POINTER(i32), vp, C.POINTER(i32)]),
     }
-    for name in SYMBOLS + MAP_UTIL_SYMBOLS + ROLLOUT_SYMBOLS + RAY_SYMBOLS + TRAJ_SYMBOLS + TABLE_SYMBOLS + OPEN_SYMBOLS + MULTI_SYMBOLS + REPLAN_SYMBOLS + PRIOR_SYMBOLS + SOLVE_SYMBOLS:
+    for name in SYMBOLS + MAP_UTIL_SYMBOLS + ROLLOUT_SYMBOLS + RAY_SYMBOLS + TRAJ_SYMBOLS + TABLE_SYMBOLS + OPEN_SYMBOLS + MULTI_SYMBOLS + REPLAN_SYMBOLS + PRIOR_SYMBOLS + SOLVE_SYMBOLS + LIMITS_SYMBOLS:
         fn = getattr(L, name)  # AttributeError if the library does not export it
         fn.restype, fn.argtypes = sig[name]
     _lib = L

@@ -1,0 +1,332 @@
+// limits_api.cpp -- C ABI of include/mplx_limits.h: caller-given segments into an mplx_poly (poly_load_kernel) and the
+// dynamic limits of the set a poly holds (poly_limits_kernel), both in limits_kernel.hip.  The host-pointer twins stage
+// through the context's arena and scatter the compact device rows into the caller's strides, as solve_api.cpp does.
+#include "mplx_poly.h"
+#include "../../include/mplx_limits.h"
+
+#include <vector>
+
+using namespace mplx_detail;
+
+namespace {
+
+int check_load(mplx_poly *p, const char *who, const mplx_poly_load_in *in, const mplx_poly_load_out *out) {
+  mplx_ctx *c = p->c;
+  if (!in || !out || in->n_prob < 0 || in->w_max < 2 || in->w_max > p->w_max || in->n_prob > p->k_cap)
+    return fail(c, MPLX_ERR_ARG, "%s: NULL in / out, w_max outside [2, %d] or more than %lld problems", who, p->w_max, (long long)p->k_cap);
+  const int ctl = in->control & 0x0f;
+  if ((in->control & ~0x1f) || (ctl != MPLX_VEL && ctl != MPLX_ACC && ctl != MPLX_JRK && ctl != MPLX_SNP))
+    return fail(c, MPLX_ERR_ARG, "%s: control must be VEL, ACC, JRK or SNP (with or without the yaw bit)", who);
+  const int64_t K = in->n_prob;
+  if (in->src || in->src_index) {  // the gather form
+    if (!in->src || !in->src_index || in->src == p || in->src->c != c || !in->src->solved || in->index_stride < K)
+      return fail(c, MPLX_ERR_ARG, "%s: the gather form needs src (a filled poly of this context, not the target) and src_index with a stride >= n_prob", who);
+    if (out->taus && out->taus_stride < K) return fail(c, MPLX_ERR_ARG, "%s: a stride is smaller than n_prob", who);
+    return MPLX_OK;
+  }
+  if (K > 0 && (!in->coeff || !in->dts)) return fail(c, MPLX_ERR_ARG, "%s: NULL coeff or dts", who);
+  if (in->dt_stride < K || in->coeff_stride < K || (out->taus && out->taus_stride < K))
+    return fail(c, MPLX_ERR_ARG, "%s: a stride is smaller than n_prob", who);
+  return MPLX_OK;
+}
+
+int load_launch(mplx_poly *p, const mplx_poly_load_in *in, const mplx_poly_load_out *out) {
+  mplx_ctx *c = p->c;
+  p->n = in->n_prob;
+  p->w = in->w_max;
+  p->solved = true;
+  p->control = in->control;
+  const mplx::TrajArgs t = poly_table_args(p);
+  mplx::PolyLoadArgs a{};
+  a.n_prob = in->n_prob;
+  a.w_max = in->w_max;
+  a.n_segs = in->n_segs;
+  a.dts = in->dts; a.dt_stride = in->dt_stride;
+  a.coeff = in->coeff; a.coeff_stride = in->coeff_stride;
+  if (in->src_index) {
+    const mplx::TrajArgs st = poly_table_args(in->src);
+    a.src_index = in->src_index; a.index_stride = in->index_stride; a.src_n = in->src->n;
+    a.src_S = st.tab_S; a.src_seg = st.tab_seg; a.src_dt = st.tab_dt;
+  }
+  a.tab_S = t.tab_S; a.tab_status = t.tab_status; a.tab_T = t.tab_T; a.tab_tau = t.tab_tau; a.tab_seg = t.tab_seg;
+  a.tab_dt = (double *)t.tab_dt; a.tab_wp = (double *)t.tab_wp;
+  a.status = out->status; a.n_segs_out = out->n_segs; a.total_time = out->total_time;
+  a.taus_out = out->taus; a.taus_stride = out->taus_stride;
+  HIP_TRY(c, mplx::launch_poly_load(c->dim, a, c->stream));
+  return MPLX_OK;
+}
+
+int check_limits(mplx_poly *p, const char *who, const mplx_limits_in *in, const mplx_limits_out *out) {
+  mplx_ctx *c = p->c;
+  if (!in || !out) return fail(c, MPLX_ERR_ARG, "%s: NULL in / out", who);
+  if (in->mode != MPLX_LIMITS_REFERENCE && in->mode != MPLX_LIMITS_ALL_ROOTS)
+    return fail(c, MPLX_ERR_ARG, "%s: mode must be MPLX_LIMITS_REFERENCE or MPLX_LIMITS_ALL_ROOTS", who);
+  if (!p->solved) return fail(c, MPLX_ERR_STATE, "%s: nothing has been solved or loaded into this poly", who);
+  if ((out->max_vel || out->max_acc || out->max_jrk) && out->max_stride < p->n)
+    return fail(c, MPLX_ERR_ARG, "%s: max_stride < n_prob", who);
+  return MPLX_OK;
+}
+
+int limits_launch(mplx_poly *p, const mplx_limits_in *in, const mplx_limits_out *o) {
+  mplx_ctx *c = p->c;
+  const mplx::TrajArgs t = poly_table_args(p);
+  mplx::LimitsArgs a{};
+  a.n_prob = p->n;
+  a.s_max = p->w - 1;
+  a.control = p->control;
+  a.all_roots = in->mode == MPLX_LIMITS_ALL_ROOTS;
+  a.mv = in->mv; a.ma = in->ma; a.mj = in->mj;
+  a.tab_S = t.tab_S; a.tab_seg = t.tab_seg; a.tab_dt = t.tab_dt;
+  a.seg_max = (double *)((char *)p->mem.p + p->o_ws);  // (w - 1) * 3 D rows of the w_max * (9 + 3 D) there are
+  a.max_vel = o->max_vel; a.max_acc = o->max_acc; a.max_jrk = o->max_jrk; a.max_stride = o->max_stride;
+  a.exceed = o->exceed; a.valid = o->valid; a.first_bad = o->first_bad;
+  HIP_TRY(c, mplx::launch_poly_limits(c->dim, a, c->stream));
+  return MPLX_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mplx_poly_load_device(mplx_poly *p, const mplx_poly_load_in *d_in, const mplx_poly_load_out *d_out) {
+  if (!p) return MPLX_ERR_ARG;
+  if (int rc = check_load(p, "mplx_poly_load_device", d_in, d_out)) return rc;
+  if (d_in->n_prob == 0) return MPLX_OK;
+  if (int rc = bind_device(p->c)) return rc;
+  return load_launch(p, d_in, d_out);
+}
+
+int mplx_poly_load(mplx_poly *p, const mplx_poly_load_in *h_in, const mplx_poly_load_out *h_out) {
+  if (!p) return MPLX_ERR_ARG;
+  mplx_ctx *c = p->c;
+  if (int rc = check_load(p, "mplx_poly_load", h_in, h_out)) return rc;
+  if (h_in->n_prob == 0) return MPLX_OK;
+  MPLX_GUARD_BEGIN
+  if (int rc = bind_device(c)) return rc;
+  if (int rc = resolve_pending(c)) return rc;  // the arena is shared with the other host-pointer calls
+  const size_t n = (size_t)h_in->n_prob, W = (size_t)h_in->w_max, D = (size_t)c->dim, cr = (W - 1) * (D + 1) * 6;
+  StageLayout l;
+  const bool gather = h_in->src_index != nullptr;
+  const size_t i_S = l.add(h_in->n_segs && !gather ? n * 4 : 0), i_dts = l.add(gather ? 0 : (W - 1) * n * 8), i_c = l.add(gather ? 0 : cr * n * 8);
+  const size_t o_st = l.add(n), o_T = l.add(n * 8), o_t = l.add(h_out->taus ? W * n * 8 : 0);
+  if (int rc = stage_commit(c, &l)) return rc;
+  mplx_poly_load_in in = *h_in;
+  if (h_in->n_segs && !gather) {
+    HIP_TRY(c, stage_in(c, l.base + i_S, h_in->n_segs, n * 4));
+    in.n_segs = (const int32_t *)(l.base + i_S);
+  }
+  if (!gather) {
+    HIP_TRY(c, stage_in_rows(c, l.base + i_dts, h_in->dts, (size_t)h_in->dt_stride * 8, n * 8, W - 1));
+    in.dts = (const double *)(l.base + i_dts); in.dt_stride = (int64_t)n;
+    HIP_TRY(c, stage_in_rows(c, l.base + i_c, h_in->coeff, (size_t)h_in->coeff_stride * 8, n * 8, cr));
+    in.coeff = (const double *)(l.base + i_c); in.coeff_stride = (int64_t)n;
+  }
+  mplx_poly_load_out o{};
+  o.status = (uint8_t *)(l.base + o_st);
+  o.total_time = (double *)(l.base + o_T);  // (S_k is read from the poly's table below)
+  if (h_out->taus) { o.taus = (double *)(l.base + o_t); o.taus_stride = (int64_t)n; }
+  if (int rc = load_launch(p, &in, &o)) return rc;
+  std::vector<uint8_t> st(n);
+  std::vector<int32_t> S(n);
+  std::vector<double> T(n), ta(h_out->taus ? W * n : 0);
+  HIP_TRY(c, stage_out(c, st.data(), o.status, n));
+  HIP_TRY(c, stage_out(c, S.data(), (char *)p->mem.p + p->o_S, n * 4));  // (0 for a failed problem)
+  HIP_TRY(c, stage_out(c, T.data(), o.total_time, n * 8));
+  HIP_TRY(c, stage_out(c, ta.empty() ? nullptr : ta.data(), o.taus, ta.size() * 8));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  for (size_t k = 0; k < n; k++) {
+    if (h_out->status) h_out->status[k] = st[k];
+    const size_t Sk = (size_t)S[k];
+    if (Sk == 0) continue;  // a failed problem: its status only
+    if (h_out->n_segs) h_out->n_segs[k] = S[k];
+    if (h_out->total_time) h_out->total_time[k] = T[k];
+    for (size_t r = 0; r <= Sk && h_out->taus; r++) h_out->taus[(int64_t)r * h_out->taus_stride + (int64_t)k] = ta[r * n + k];
+  }
+  return MPLX_OK;
+  MPLX_GUARD_END(c)
+}
+
+int mplx_poly_limits_device(mplx_poly *p, const mplx_limits_in *in, const mplx_limits_out *d_out) {
+  if (!p) return MPLX_ERR_ARG;
+  if (int rc = check_limits(p, "mplx_poly_limits_device", in, d_out)) return rc;
+  if (int rc = bind_device(p->c)) return rc;
+  return limits_launch(p, in, d_out);
+}
+
+int mplx_poly_limits(mplx_poly *p, const mplx_limits_in *in, const mplx_limits_out *h_out) {
+  if (!p) return MPLX_ERR_ARG;
+  mplx_ctx *c = p->c;
+  if (int rc = check_limits(p, "mplx_poly_limits", in, h_out)) return rc;
+  MPLX_GUARD_BEGIN
+  if (int rc = bind_device(c)) return rc;
+  if (int rc = resolve_pending(c)) return rc;
+  const size_t n = (size_t)p->n, D = (size_t)c->dim;
+  double *const h_max[3] = {h_out->max_vel, h_out->max_acc, h_out->max_jrk};
+  StageLayout l;
+  size_t o_m[3];
+  for (int q = 0; q < 3; q++) o_m[q] = l.add(h_max[q] ? D * n * 8 : 0);
+  const size_t o_e = l.add(h_out->exceed ? n : 0), o_v = l.add(h_out->valid ? n : 0), o_f = l.add(h_out->first_bad ? n * 4 : 0);
+  if (int rc = stage_commit(c, &l)) return rc;
+  mplx_limits_out o{};
+  o.max_vel = h_max[0] ? (double *)(l.base + o_m[0]) : nullptr;
+  o.max_acc = h_max[1] ? (double *)(l.base + o_m[1]) : nullptr;
+  o.max_jrk = h_max[2] ? (double *)(l.base + o_m[2]) : nullptr;
+  o.max_stride = (int64_t)n;
+  o.exceed = h_out->exceed ? (uint8_t *)(l.base + o_e) : nullptr;
+  o.valid = h_out->valid ? (uint8_t *)(l.base + o_v) : nullptr;
+  o.first_bad = h_out->first_bad ? (int32_t *)(l.base + o_f) : nullptr;
+  if (int rc = limits_launch(p, in, &o)) return rc;
+  std::vector<int32_t> S(n), fb(h_out->first_bad ? n : 0);
+  std::vector<uint8_t> ex(h_out->exceed ? n : 0), va(h_out->valid ? n : 0);
+  std::vector<double> mx[3];
+  double *const d_max[3] = {o.max_vel, o.max_acc, o.max_jrk};
+  HIP_TRY(c, stage_out(c, S.data(), (char *)p->mem.p + p->o_S, n * 4));
+  for (int q = 0; q < 3; q++) {
+    mx[q].resize(h_max[q] ? D * n : 0);
+    HIP_TRY(c, stage_out(c, mx[q].empty() ? nullptr : mx[q].data(), d_max[q], mx[q].size() * 8));
+  }
+  HIP_TRY(c, stage_out(c, ex.empty() ? nullptr : ex.data(), o.exceed, ex.size()));
+  HIP_TRY(c, stage_out(c, va.empty() ? nullptr : va.data(), o.valid, va.size()));
+  HIP_TRY(c, stage_out(c, fb.empty() ? nullptr : fb.data(), o.first_bad, fb.size() * 4));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  for (size_t k = 0; k < n; k++) {
+    if (S[k] == 0) continue;  // a failed problem keeps the caller's bytes
+    for (int q = 0; q < 3; q++)
+      for (size_t i = 0; i < D && h_max[q]; i++) h_max[q][(int64_t)i * h_out->max_stride + (int64_t)k] = mx[q][i * n + k];
+    if (h_out->exceed) h_out->exceed[k] = ex[k];
+    if (h_out->valid) h_out->valid[k] = va[k];
+    if (h_out->first_bad) h_out->first_bad[k] = fb[k];
+  }
+  return MPLX_OK;
+  MPLX_GUARD_END(c)
+}
+
+}  // extern "C"
+
+namespace {
+
+int check_shortcut(mplx_poly *pairs, mplx_poly *res, const char *who, const mplx_shortcut_in *in, const mplx_shortcut_out *out, int64_t *np) {
+  mplx_ctx *c = pairs->c;
+  if (!res || !in || !out || res == pairs || res->c != c) return fail(c, MPLX_ERR_ARG, "%s: NULL or equal polys, polys of two contexts, NULL in / out", who);
+  const int ctl = in->control & 0x0f;
+  if ((in->control & ~0x1f) || (ctl != MPLX_VEL && ctl != MPLX_ACC && ctl != MPLX_JRK))
+    return fail(c, MPLX_ERR_ARG, "%s: control must be VEL, ACC or JRK (with or without the yaw bit)", who);
+  if (in->n_query < 0 || in->w_max < 2 || in->max_hop < 1 || in->w_max > res->w_max || in->n_query > res->k_cap)
+    return fail(c, MPLX_ERR_ARG, "%s: n_query < 0, w_max < 2, max_hop < 1, or a result poly smaller than Q x w_max", who);
+  const double npd = (double)in->n_query * (double)(in->w_max - 1) * (double)in->max_hop;
+  if (npd > (double)pairs->k_cap || npd > 2147483647.0)
+    return fail(c, MPLX_ERR_ARG, "%s: the pair poly holds fewer than Q (w_max - 1) max_hop problems", who);
+  *np = in->n_query * (in->w_max - 1) * in->max_hop;
+  if (in->n_query > 0 && !in->states) return fail(c, MPLX_ERR_ARG, "%s: NULL states", who);
+  if (in->stride < in->n_query || (out->keep && out->keep_stride < in->n_query)) return fail(c, MPLX_ERR_ARG, "%s: a stride is smaller than n_query", who);
+  if (!c->has_map) return fail(c, MPLX_ERR_STATE, "%s: set the map first", who);
+  if (!(c->prm.v_max > 0)) return fail(c, MPLX_ERR_STATE, "%s: v_max must be > 0 (env_map.h:231)", who);
+  return MPLX_OK;
+}
+
+// everything queued on the stream, no read-back: pairs -> solve -> info, limits, traverse -> costs, programme -> gather
+int shortcut_launch(mplx_poly *pairs, mplx_poly *res, const mplx_shortcut_in *in, const mplx_shortcut_out *out, int64_t NP) {
+  mplx_ctx *c = pairs->c;
+  const size_t P = (size_t)NP, Q = (size_t)in->n_query, W = (size_t)in->w_max, F = 4 * (size_t)c->dim + 2;
+  StageLayout l;  // (only the carving)
+  const size_t o_wp = l.add(F * 2 * P * 8), o_dt = l.add(P * 8), o_eff = l.add(5 * P * 8), o_trav = l.add(P * 8), o_ec = l.add(P * 8),
+               o_dist = l.add(W * Q * 8), o_nwp = l.add(P * 4), o_pred = l.add(W * Q * 4), o_src = l.add((W - 1) * Q * 4),
+               o_fl = l.add(2 * P), o_valid = l.add(P), o_st = l.add(P);
+  if (int rc = ensure(c, pairs->aux, l.total)) return rc;
+  char *b = (char *)pairs->aux.p;
+  mplx::ShortcutArgs a{};
+  a.n_query = in->n_query; a.w_max = in->w_max; a.max_hop = in->max_hop; a.order = control_order(in->control);
+  a.w = c->prm.w;
+  a.states = in->states; a.stride = in->stride; a.n_wp = in->n_wp;
+  a.pair_wp = (double *)(b + o_wp); a.pair_dt = (double *)(b + o_dt); a.pair_nwp = (int32_t *)(b + o_nwp); a.pair_flags = (uint8_t *)(b + o_fl);
+  a.pair_status = (uint8_t *)(b + o_st); a.pair_valid = (uint8_t *)(b + o_valid);
+  a.pair_effort = (double *)(b + o_eff); a.pair_trav = (double *)(b + o_trav);
+  a.dist = (double *)(b + o_dist); a.pred = (int32_t *)(b + o_pred); a.src_index = (int32_t *)(b + o_src);
+  a.status = out->status; a.n_keep = out->n_keep; a.keep = out->keep; a.keep_stride = out->keep_stride;
+  a.cost = out->cost; a.chain_cost = out->chain_cost;
+  a.edge_cost = out->edge_cost ? out->edge_cost : (double *)(b + o_ec);
+  HIP_TRY(c, mplx::launch_shortcut_pairs(c->dim, a, c->stream));
+  mplx_solve_in si{};
+  si.waypoints = a.pair_wp; si.n_prob = NP; si.w_max = 2; si.wp_stride = NP; si.n_wp = a.pair_nwp;
+  si.dts = a.pair_dt; si.dt_stride = NP; si.v = 1.0; si.control = in->control; si.yaw_control = MPLX_VEL;
+  si.wp_flags = a.pair_flags; si.flag_stride = NP;
+  mplx_solve_out so = out->pair_out ? *out->pair_out : mplx_solve_out{};
+  uint8_t *caller_status = so.status;
+  so.status = (uint8_t *)a.pair_status;
+  if (int rc = mplx_solve_device(pairs, &si, &so)) return rc;
+  if (caller_status) HIP_TRY(c, hipMemcpyAsync(caller_status, a.pair_status, P, hipMemcpyDeviceToDevice, c->stream));
+  a.pair_T = (const double *)((char *)pairs->mem.p + pairs->o_T);
+  mplx_traj_info_out io{};
+  io.effort = (double *)a.pair_effort; io.effort_stride = NP;
+  if (int rc = mplx_poly_info_device(pairs, &io)) return rc;
+  HIP_TRY(c, hipMemsetAsync((void *)a.pair_valid, 0, P, c->stream));  // (the limits skip a failed pair)
+  mplx_limits_in li{c->prm.v_max, c->prm.a_max, c->prm.j_max, MPLX_LIMITS_ALL_ROOTS};
+  mplx_limits_out lo{};
+  lo.valid = (uint8_t *)a.pair_valid;
+  if (int rc = mplx_poly_limits_device(pairs, &li, &lo)) return rc;
+  mplx_traj_traverse_out to{};
+  to.cost = (double *)a.pair_trav;
+  if (int rc = mplx_poly_traverse_device(pairs, 0, &to)) return rc;
+  HIP_TRY(c, mplx::launch_shortcut_dp(a, c->stream));
+  mplx_poly_load_in gi{};
+  gi.n_prob = in->n_query; gi.w_max = in->w_max; gi.control = in->control;
+  gi.src = pairs; gi.src_index = a.src_index; gi.index_stride = in->n_query;
+  mplx_poly_load_out go{};
+  return mplx_poly_load_device(res, &gi, &go);
+}
+
+}  // namespace
+
+extern "C" {
+
+int mplx_shortcut_device(mplx_poly *pairs, mplx_poly *res, const mplx_shortcut_in *d_in, const mplx_shortcut_out *d_out) {
+  if (!pairs) return MPLX_ERR_ARG;
+  int64_t NP = 0;
+  if (int rc = check_shortcut(pairs, res, "mplx_shortcut_device", d_in, d_out, &NP)) return rc;
+  if (NP == 0) return MPLX_OK;
+  if (int rc = bind_device(pairs->c)) return rc;
+  return shortcut_launch(pairs, res, d_in, d_out, NP);
+}
+
+int mplx_shortcut(mplx_poly *pairs, mplx_poly *res, const mplx_shortcut_in *h_in, const mplx_shortcut_out *h_out) {
+  if (!pairs) return MPLX_ERR_ARG;
+  mplx_ctx *c = pairs->c;
+  int64_t NP = 0;
+  if (int rc = check_shortcut(pairs, res, "mplx_shortcut", h_in, h_out, &NP)) return rc;
+  if (h_out->pair_out) return fail(c, MPLX_ERR_ARG, "mplx_shortcut: pair_out is for the _device form");
+  if (NP == 0) return MPLX_OK;
+  MPLX_GUARD_BEGIN
+  if (int rc = bind_device(c)) return rc;
+  if (int rc = resolve_pending(c)) return rc;
+  const size_t Q = (size_t)h_in->n_query, W = (size_t)h_in->w_max, F = 4 * (size_t)c->dim + 2, P = (size_t)NP;
+  StageLayout l;
+  const size_t i_st = l.add(F * W * Q * 8), i_n = l.add(h_in->n_wp ? Q * 4 : 0);
+  const size_t o_s = l.add(Q), o_nk = l.add(Q * 4), o_k = l.add(W * Q * 4), o_c = l.add(Q * 8), o_cc = l.add(Q * 8), o_e = l.add(P * 8);
+  if (int rc = stage_commit(c, &l)) return rc;
+  mplx_shortcut_in in = *h_in;
+  HIP_TRY(c, stage_in_rows(c, l.base + i_st, h_in->states, (size_t)h_in->stride * 8, Q * 8, F * W));
+  in.states = (const double *)(l.base + i_st); in.stride = (int64_t)Q;
+  if (h_in->n_wp) {
+    HIP_TRY(c, stage_in(c, l.base + i_n, h_in->n_wp, Q * 4));
+    in.n_wp = (const int32_t *)(l.base + i_n);
+  }
+  mplx_shortcut_out o{};
+  o.status = (uint8_t *)(l.base + o_s); o.n_keep = (int32_t *)(l.base + o_nk); o.keep = (int32_t *)(l.base + o_k); o.keep_stride = (int64_t)Q;
+  o.cost = (double *)(l.base + o_c); o.chain_cost = (double *)(l.base + o_cc); o.edge_cost = (double *)(l.base + o_e);
+  // (the calls inside stage nothing: they are device forms, rule 4 of the arena)
+  if (int rc = shortcut_launch(pairs, res, &in, &o, NP)) return rc;
+  std::vector<int32_t> keep(h_out->keep ? W * Q : 0);
+  HIP_TRY(c, stage_out(c, h_out->status, o.status, Q));
+  HIP_TRY(c, stage_out(c, h_out->n_keep, o.n_keep, Q * 4));
+  HIP_TRY(c, stage_out(c, keep.empty() ? nullptr : keep.data(), o.keep, keep.size() * 4));
+  HIP_TRY(c, stage_out(c, h_out->cost, o.cost, Q * 8));
+  HIP_TRY(c, stage_out(c, h_out->chain_cost, o.chain_cost, Q * 8));
+  HIP_TRY(c, stage_out(c, h_out->edge_cost, o.edge_cost, P * 8));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  for (size_t w = 0; w < W && h_out->keep; w++)
+    for (size_t k = 0; k < Q; k++) h_out->keep[(int64_t)w * h_out->keep_stride + (int64_t)k] = keep[w * Q + k];
+  return MPLX_OK;
+  MPLX_GUARD_END(c)
+}
+
+}  // extern "C"

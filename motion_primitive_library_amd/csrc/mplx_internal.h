@@ -532,6 +532,76 @@ struct SolveArgs {
 };
 hipError_t launch_solve(int dim, const SolveArgs &a, hipStream_t s);
 
+// Caller-given segments into a poly's table, and the dynamic limits of the set a table holds (limits_kernel.hip,
+// limits_api.cpp; include/mplx_limits.h).  The table is a TrajArgs with poly == 1 and stride n_prob.
+struct PolyLoadArgs {
+  int64_t n_prob;
+  int32_t w_max;
+  const int32_t *n_segs;     // [n_prob] or null: w_max - 1 each
+  const double *dts;         // [w_max - 1][dt_stride]
+  int64_t dt_stride;
+  const double *coeff;       // [((s (D + 1) + a) 6 + j) * coeff_stride + k]
+  int64_t coeff_stride;
+  // the gather form: src_index non-null; the source table (stride src_n) holds src_n problems
+  const int32_t *src_index;
+  int64_t index_stride, src_n;
+  const int32_t *src_S;
+  const double *src_seg, *src_dt;
+  int32_t *tab_S;
+  uint8_t *tab_status;
+  double *tab_T, *tab_tau, *tab_seg, *tab_dt, *tab_wp;
+  // outputs, any may be null
+  uint8_t *status;
+  int32_t *n_segs_out;
+  double *total_time, *taus_out;
+  int64_t taus_stride;
+};
+hipError_t launch_poly_load(int dim, const PolyLoadArgs &a, hipStream_t s);
+
+struct LimitsArgs {
+  int64_t n_prob;            // the stride of the table and of seg_max
+  int32_t s_max;             // w_max - 1 of the set
+  int32_t control, all_roots;
+  double mv, ma, mj;
+  const int32_t *tab_S;
+  const double *tab_seg, *tab_dt;
+  double *seg_max;           // scratch [s_max][3 D][n_prob]: per segment the axis maxima of vel, acc, jrk
+  // outputs, any may be null
+  double *max_vel, *max_acc, *max_jrk;
+  int64_t max_stride;
+  uint8_t *exceed, *valid;
+  int32_t *first_bad;
+};
+hipError_t launch_poly_limits(int dim, const LimitsArgs &a, hipStream_t s);
+
+// Shortcutting (include/mplx_limits.h): the pair problems of Q chains, and the dynamic programme over their costs.
+struct ShortcutArgs {
+  int64_t n_query;
+  int32_t w_max, max_hop, order;  // order: 1 VEL, 2 ACC, 3 JRK
+  double w;                       // the context's time weight
+  const double *states;           // [(f w_max + w) * stride + k]
+  int64_t stride;
+  const int32_t *n_wp;            // [Q] or null
+  // pair problems, P = Q (w_max - 1) max_hop, every array [row][P]
+  double *pair_wp;                // [4D+2][2][P]
+  double *pair_dt;                // [1][P]
+  int32_t *pair_nwp;              // [P] 2 or 0
+  uint8_t *pair_flags;            // [2][P]
+  // what the evaluation of the pairs left
+  const uint8_t *pair_status, *pair_valid;
+  const double *pair_T, *pair_effort, *pair_trav;  // effort [5][P]
+  // the programme
+  double *dist;                   // [w_max][Q]
+  int32_t *pred;                  // [w_max][Q]
+  int32_t *src_index;             // [w_max - 1][Q]
+  uint8_t *status;
+  int32_t *n_keep, *keep;
+  int64_t keep_stride;
+  double *cost, *chain_cost, *edge_cost;
+};
+hipError_t launch_shortcut_pairs(int dim, const ShortcutArgs &a, hipStream_t s);
+hipError_t launch_shortcut_dp(const ShortcutArgs &a, hipStream_t s);
+
 // The prior table of an open set (traj_kernel.hip, open_api.cpp; include/mplx_prior.h), built on the segment table of a
 // chain launch with the prior's controls and the `cost` of a traverse launch.
 struct PriorArgs {

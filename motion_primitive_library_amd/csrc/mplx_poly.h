@@ -1,0 +1,48 @@
+// mplx_poly.h -- the mplx_poly of include/mplx_solve.h as the sources that fill or read one see it (solve_api.cpp,
+// limits_api.cpp): the segment table of its last solve or load, laid out for the K of that call (every array [row][K]),
+// and the workspace of the elimination, which a limits call reuses for its per-segment maxima.
+#ifndef MPLX_POLY_H
+#define MPLX_POLY_H
+
+#include "mplx_ctx.h"
+#include "../../include/mplx_solve.h"
+
+struct mplx_poly {
+  mplx_ctx *c = nullptr;
+  int64_t k_cap = 0;
+  int32_t w_max = 0;
+  mplx_detail::DevBuf mem;
+  mplx_detail::DevBuf aux;  // scratch of mplx_shortcut when this poly is its pair set; grown on demand
+  size_t o_S = 0, o_st = 0, o_T = 0, o_tau = 0, o_seg = 0, o_dt = 0, o_wp = 0, o_ws = 0;
+  // the last solve or load
+  int64_t n = 0;
+  int32_t w = 0;  // its w_max
+  int32_t control = 0;
+  bool solved = false;
+};
+
+namespace mplx_detail {
+
+// the table of the poly's last solve or load as the trajectory kernels take it
+inline mplx::TrajArgs poly_table_args(mplx_poly *p) {
+  const mplx_succ none{};
+  mplx::TrajArgs a{};
+  a.env = expand_args(p->c, nullptr, 0, 0, &none);
+  char *base = (char *)p->mem.p;
+  a.n_traj = p->n;
+  a.horizon = p->w - 1;
+  a.yaw = 1;
+  a.poly = 1;
+  a.tab_S = (int32_t *)(base + p->o_S);
+  a.tab_n = nullptr;
+  a.tab_status = (uint8_t *)(base + p->o_st);
+  a.tab_T = (double *)(base + p->o_T);
+  a.tab_tau = (double *)(base + p->o_tau);
+  a.tab_seg = (double *)(base + p->o_seg);
+  a.tab_dt = (const double *)(base + p->o_dt);
+  a.tab_wp = (const double *)(base + p->o_wp);
+  return a;
+}
+
+}  // namespace mplx_detail
+#endif

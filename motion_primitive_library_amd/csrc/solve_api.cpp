@@ -1,49 +1,15 @@
 // solve_api.cpp -- C ABI of include/mplx_solve.h: the batched trajectory solver (solve_kernel.hip) and Trajectory<Dim>
 // on what it returns (the POLY instantiations of traj_kernel.hip).  An mplx_poly owns the segment table of its last
-// solve, laid out for the K of that solve (every array [row][K]), and the workspace of the elimination.  The
+// solve, laid out for the K of that solve (every array [row][K]), and the workspace of the elimination (mplx_poly.h).  The
 // host-pointer twins stage through the context's arena and scatter the compact device rows into the caller's strides.
-#include "mplx_ctx.h"
-#include "../../include/mplx_solve.h"
+#include "mplx_poly.h"
 
 #include <algorithm>
 #include <vector>
 
 using namespace mplx_detail;
 
-struct mplx_poly {
-  mplx_ctx *c = nullptr;
-  int64_t k_cap = 0;
-  int32_t w_max = 0;
-  DevBuf mem;
-  size_t o_S = 0, o_st = 0, o_T = 0, o_tau = 0, o_seg = 0, o_dt = 0, o_wp = 0, o_ws = 0;
-  // the last solve
-  int64_t n = 0;
-  int32_t w = 0;  // its w_max
-  bool solved = false;
-};
-
 namespace {
-
-// the table of the poly's last solve as the trajectory kernels take it
-mplx::TrajArgs table_args(mplx_poly *p) {
-  const mplx_succ none{};
-  mplx::TrajArgs a{};
-  a.env = expand_args(p->c, nullptr, 0, 0, &none);
-  char *base = (char *)p->mem.p;
-  a.n_traj = p->n;
-  a.horizon = p->w - 1;
-  a.yaw = 1;
-  a.poly = 1;
-  a.tab_S = (int32_t *)(base + p->o_S);
-  a.tab_n = nullptr;
-  a.tab_status = (uint8_t *)(base + p->o_st);
-  a.tab_T = (double *)(base + p->o_T);
-  a.tab_tau = (double *)(base + p->o_tau);
-  a.tab_seg = (double *)(base + p->o_seg);
-  a.tab_dt = (const double *)(base + p->o_dt);
-  a.tab_wp = (const double *)(base + p->o_wp);
-  return a;
-}
 
 int check_in(mplx_poly *p, const char *who, const mplx_solve_in *in, const mplx_solve_out *out, int *so) {
   mplx_ctx *c = p->c;
@@ -68,7 +34,8 @@ int solve_launch(mplx_poly *p, const mplx_solve_in *in, const mplx_solve_out *ou
   p->n = in->n_prob;
   p->w = in->w_max;
   p->solved = true;
-  const mplx::TrajArgs t = table_args(p);
+  p->control = in->control;
+  const mplx::TrajArgs t = poly_table_args(p);
   mplx::SolveArgs a{};
   a.n_prob = a.cap = in->n_prob;
   a.w_max = in->w_max;
@@ -124,7 +91,7 @@ int check_traverse(mplx_poly *p, const char *who, int32_t lanes) {
 }
 
 int info_launch(mplx_poly *p, const mplx_traj_info_out *o) {
-  mplx::TrajArgs a = table_args(p);
+  mplx::TrajArgs a = poly_table_args(p);
   a.status = o->status; a.n_segs = o->n_segs; a.total_time = o->total_time;
   a.effort = o->effort; a.effort_stride = o->effort_stride;
   a.seg_state = o->seg_state; a.seg_stride = o->seg_stride;
@@ -140,7 +107,7 @@ int sample_launch(mplx_poly *p, const mplx_traj_times *t, const mplx_traj_sample
     if (int rc = info_launch(p, &io)) return rc;
   }
   if (!o->out) return MPLX_OK;
-  mplx::TrajArgs a = table_args(p);
+  mplx::TrajArgs a = poly_table_args(p);
   a.n_uniform = t->n_uniform; a.times = t->times; a.time_stride = t->n_uniform > 0 ? 0 : t->time_stride; a.count = count;
   a.out = o->out; a.row_stride = o->row_stride; a.sample_stride = o->sample_stride;
   HIP_TRY(c, mplx::launch_traj_sample(c->dim, t->form, a, c->stream));
@@ -150,7 +117,7 @@ int sample_launch(mplx_poly *p, const mplx_traj_times *t, const mplx_traj_sample
 // lanes == 0: the durations are on the device, so no bound on the samples is known here; 16 lanes per trajectory, the
 // middle one of traj_api.cpp's rule
 int traverse_launch(mplx_poly *p, int32_t lanes, const mplx_traj_traverse_out *o) {
-  mplx::TrajArgs a = table_args(p);
+  mplx::TrajArgs a = poly_table_args(p);
   a.status = o->status; a.cost = o->cost; a.n_samples = o->n_samples; a.n_cells = o->n_cells; a.stop_sample = o->stop_sample;
   HIP_TRY(p->c, mplx::launch_traj_traverse(p->c->dim, lanes ? lanes : 16, a, p->c->stream));
   return MPLX_OK;
@@ -196,6 +163,7 @@ void mplx_poly_destroy(mplx_poly *p) {
   (void)hipSetDevice(p->c->device);
   (void)hipStreamSynchronize(p->c->stream);
   release(p->mem);
+  release(p->aux);
   delete p;
 }
 

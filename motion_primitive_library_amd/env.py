@@ -37,6 +37,9 @@ FLAG_GOAL_BLOCKED = _abi.FLAG_GOAL_BLOCKED
 TRAJ_EMPTY, TRAJ_BAD_ACTION, TRAJ_BAD = _abi.TRAJ_EMPTY, _abi.TRAJ_BAD_ACTION, _abi.TRAJ_BAD  # include/mplx_traj.h
 TRAJ_COMMAND, TRAJ_WAYPOINT = _abi.TRAJ_COMMAND, _abi.TRAJ_WAYPOINT
 SOLVE_EMPTY, SOLVE_BAD_TIME, SOLVE_SINGULAR = _abi.SOLVE_EMPTY, _abi.SOLVE_BAD_TIME, _abi.SOLVE_SINGULAR  # include/mplx_solve.h
+LIMITS_REFERENCE, LIMITS_ALL_ROOTS = _abi.LIMITS_REFERENCE, _abi.LIMITS_ALL_ROOTS  # include/mplx_limits.h
+EXCEED_VEL, EXCEED_ACC, EXCEED_JRK = _abi.EXCEED_VEL, _abi.EXCEED_ACC, _abi.EXCEED_JRK
+SHORTCUT_BAD_CHAIN = _abi.SHORTCUT_BAD_CHAIN
 USE_POS, USE_VEL, USE_ACC = _abi.USE_POS, _abi.USE_VEL, _abi.USE_ACC
 
 
@@ -381,6 +384,75 @@ class SolveOut:
             b.free()
 
 
+class LoadOut:
+    """HBM-resident rows of mplx_poly_load_out for n problems of up to w_max - 1 segments."""
+
+    def __init__(self, env, n, w_max):
+        self.n, self.w_max = int(n), int(w_max)
+        n = max(self.n, 1)
+        self.status, self.n_segs = DeviceArray(env, n), DeviceArray(env, n * 4)
+        self.total_time, self.taus = DeviceArray(env, n * 8), DeviceArray(env, self.w_max * n * 8)
+
+    def c_struct(self):
+        s = _abi.PolyLoadOut()
+        s.status, s.n_segs, s.total_time, s.taus, s.taus_stride = self.status.ptr, self.n_segs.ptr, self.total_time.ptr, self.taus.ptr, self.n
+        return s
+
+    def download(self):
+        """Rows the load did not own (failed problems, taus past S_k) hold whatever the buffers held."""
+        n = self.n
+        return {"status": self.status.download(np.uint8, (n,)), "n_segs": self.n_segs.download(np.int32, (n,)),
+                "total_time": self.total_time.download(np.float64, (n,)), "taus": self.taus.download(np.float64, (self.w_max, n))}
+
+    def free(self):
+        for b in (self.status, self.n_segs, self.total_time, self.taus):
+            b.free()
+
+
+class ShortcutResult:
+    """What EnvMap.shortcut / SearchResult.shortcut return (mplx_shortcut, include/mplx_limits.h).  poly: the PolyTrajSet of
+    the Q shortcut trajectories; pairs: the PolyTrajSet of the Q (w_max - 1) max_hop pair problems (pair (k, i, j) at
+    (k (w_max - 1) + i) max_hop + (j - i - 1)); per query status (0, SOLVE_EMPTY, SHORTCUT_BAD_CHAIN), keep (a list of
+    ascending state indices), cost, chain_cost; edge_cost [Q][w_max - 1][max_hop] (+inf: not admitted).  free() it."""
+
+    def __init__(self, poly, pairs, max_hop, rows):
+        self.poly, self.pairs, self.max_hop = poly, pairs, int(max_hop)
+        self.status, self.n_keep, self.cost, self.chain_cost = rows["status"], rows["n_keep"], rows["cost"], rows["chain_cost"]
+        self.keep = [rows["keep"][:n, k].copy() for k, n in enumerate(self.n_keep)]
+        self.edge_cost = rows["edge_cost"]
+
+    def free(self):
+        self.poly.free()
+        self.pairs.free()
+
+
+class PolyLimits:
+    """HBM-resident rows of mplx_limits_out for n trajectories."""
+
+    def __init__(self, env, n):
+        self.n, self.dim = int(n), env.dim
+        n = max(self.n, 1)
+        self.max_vel, self.max_acc, self.max_jrk = (DeviceArray(env, self.dim * n * 8) for _ in range(3))
+        self.exceed, self.valid, self.first_bad = DeviceArray(env, n), DeviceArray(env, n), DeviceArray(env, n * 4)
+
+    def c_struct(self):
+        s = _abi.LimitsOut()
+        s.max_vel, s.max_acc, s.max_jrk, s.max_stride = self.max_vel.ptr, self.max_acc.ptr, self.max_jrk.ptr, self.n
+        s.exceed, s.valid, s.first_bad = self.exceed.ptr, self.valid.ptr, self.first_bad.ptr
+        return s
+
+    def download(self):
+        """Entries of failed problems hold whatever the buffers held."""
+        n, D = self.n, self.dim
+        return {"max_vel": self.max_vel.download(np.float64, (D, n)), "max_acc": self.max_acc.download(np.float64, (D, n)),
+                "max_jrk": self.max_jrk.download(np.float64, (D, n)), "exceed": self.exceed.download(np.uint8, (n,)),
+                "valid": self.valid.download(np.uint8, (n,)), "first_bad": self.first_bad.download(np.int32, (n,))}
+
+    def free(self):
+        for b in (self.max_vel, self.max_acc, self.max_jrk, self.exceed, self.valid, self.first_bad):
+            b.free()
+
+
 class PolyTrajSet:
     """K solved trajectories on the device (mplx_poly of include/mplx_solve.h): what EnvMap.solve_traj returns and what
     EnvMap.solve_traj_resident solves into.  status [K] (SOLVE_EMPTY | SOLVE_BAD_TIME | SOLVE_SINGULAR; 0 = solved);
@@ -388,7 +460,7 @@ class PolyTrajSet:
 
     def __init__(self, env, k_cap, w_max):
         self._env, self.k_cap, self.w_max = env, int(k_cap), int(w_max)
-        self.n, self.so, self.n_wmax = 0, None, 0
+        self.n, self.so, self.n_wmax, self.control = 0, None, 0, None
         self._host, self._out = None, None
         h = C.c_void_p()
         _abi.check(env._ctx, _abi.lib().mplx_poly_create(env._ctx, self.k_cap, self.w_max, C.byref(h)))
@@ -409,20 +481,22 @@ class PolyTrajSet:
             pass
 
     def _rows(self):
-        """The rows of the last solve on the host: from the host-pointer solve, or downloaded from its SolveOut."""
+        """The rows of the last solve or load on the host: from the host-pointer call, or downloaded from the SolveOut /
+        LoadOut of the resident one."""
         if self._host is None:
             if self._out is None:
-                raise RuntimeError("PolyTrajSet: the solve kept no output rows (solve_traj_resident without out)")
+                raise RuntimeError("PolyTrajSet: the resident solve or load kept no output rows (no `out` was given)")
             self._env.synchronize()
             d = self._out.download()
             ok = d["status"] == 0
             d["n_segs"] = np.where(ok, d["n_segs"], 0)
             d["total_time"] = np.where(ok, d["total_time"], 0.0)
-            seg = np.arange(self._out.w_max - 1)[:, None] < d["n_segs"][None, :]
-            d["coeff"] = np.where(seg[:, None, None, :], d["coeff"], 0.0)
-            d["dts"] = np.where(seg, d["dts"], 0.0)
-            d["yaw_coeff"] = np.where(seg[:, None, :], d["yaw_coeff"], 0.0)
-            d["taus"] = np.where(np.arange(self._out.w_max)[:, None] <= d["n_segs"][None, :], d["taus"], 0.0) * ok[None, :]
+            if "coeff" in d:  # a SolveOut
+                seg = np.arange(self._out.w_max - 1)[:, None] < d["n_segs"][None, :]
+                d["coeff"] = np.where(seg[:, None, None, :], d["coeff"], 0.0)
+                d["dts"] = np.where(seg, d["dts"], 0.0)
+                d["yaw_coeff"] = np.where(seg[:, None, :], d["yaw_coeff"], 0.0)
+            d["taus"] = np.where((np.arange(self._out.w_max)[:, None] <= d["n_segs"][None, :]) & ok[None, :], d["taus"], 0.0)
             self._host = d
         return self._host
 
@@ -440,15 +514,42 @@ class PolyTrajSet:
 
     def coefficients(self):
         """PolyTraj::p() of every problem: [w_max - 1][N][D][K], coefficient r of axis i of segment s at [s][r][i][k]
-        (increasing powers of the segment's own time); zero past S_k and for a failed problem."""
+        (increasing powers of the segment's own time); zero past S_k and for a failed problem.  A solved set only."""
+        if "coeff" not in self._rows():
+            raise RuntimeError("PolyTrajSet: a loaded set has segments(), not the solver's coefficients()")
         return self._rows()["coeff"]
 
     def yaw_coefficients(self):
-        """The yaw solve's p: [w_max - 1][2][K]."""
+        """The yaw solve's p: [w_max - 1][2][K].  A solved set only."""
+        if "yaw_coeff" not in self._rows():
+            raise RuntimeError("PolyTrajSet: a loaded set has segments(), not the solver's yaw_coefficients()")
         return self._rows()["yaw_coeff"]
 
+    def segments(self):
+        """The primitives of every problem as EnvMap.load_traj takes them: [w_max - 1][D + 1][6][K], c(0) .. c(5) of
+        primitive.h:128-131 for axis a of segment s at [s][a][:][k], axis D the yaw primitive; zero past S_k.  A loaded set
+        returns what was loaded; a solved set PolyTraj::toPrimitives of its coefficients (c_j = p_{5-j} (5-j)!, the
+        multiplication the device made)."""
+        r = self._rows()
+        if "segments" not in r and "coeff" not in r:
+            raise RuntimeError("PolyTrajSet: a set loaded with load_traj_resident keeps its dts and segments on the device only")
+        if "segments" not in r:
+            p, yaw = r["coeff"], r["yaw_coeff"]
+            S, N, D, K = p.shape
+            seg = np.zeros((S, D + 1, 6, K))
+            fact = [1.0, 1.0, 2.0, 6.0, 24.0, 120.0]
+            for j in range(6):
+                if 5 - j < N:
+                    seg[:, :D, j, :] = p[:, 5 - j, :, :] * fact[5 - j]
+            seg[:, D, 4, :], seg[:, D, 5, :] = yaw[:, 1, :] * 1.0, yaw[:, 0, :] * 1.0
+            r["segments"] = seg
+        return r["segments"]
+
     def dts(self):
-        """[w_max - 1][K] segment durations (given, or allocate_time's); zero past S_k."""
+        """[w_max - 1][K] segment durations (given, or allocate_time's); zero past S_k.  Not for a set loaded from
+        device buffers (load_traj_resident): its segments and durations are the caller's own arrays."""
+        if "dts" not in self._rows():
+            raise RuntimeError("PolyTrajSet: a set loaded with load_traj_resident keeps its dts and segments on the device only")
         return self._rows()["dts"]
 
     def taus(self):
@@ -504,7 +605,41 @@ class PolyTrajSet:
         _abi.check(env._ctx, _abi.lib().mplx_poly_traverse(self._h, int(lanes), C.byref(o)))
         return out
 
+    def limits(self, v_max=None, a_max=None, j_max=None, all_roots=False):
+        """Primitive::max_vel / max_acc / max_jrk and validate_primitive of every trajectory (mplx_poly_limits;
+        synchronous).  Limits default to the EnvMap's; <= 0 means not checked.  all_roots=False is the reference, which
+        stops at the first root past the segment's end and so often misses the true peak; all_roots=True looks at every
+        root (include/mplx_limits.h).  Returns max_vel / max_acc / max_jrk [D][K] (per axis, the maximum over the
+        segments), exceed [K] (EXCEED_VEL | EXCEED_ACC | EXCEED_JRK), valid [K] (under the set's control) and first_bad
+        [K] (segment or -1); entries of failed problems are zero (valid 0, first_bad -1)."""
+        self._need()
+        K, env = self.n, self._env
+        out = {"max_vel": np.zeros((env.dim, K)), "max_acc": np.zeros((env.dim, K)), "max_jrk": np.zeros((env.dim, K)),
+               "exceed": np.zeros(K, np.uint8), "valid": np.zeros(K, np.uint8), "first_bad": np.full(K, -1, np.int32)}
+        o = _abi.LimitsOut()
+        for key in out:
+            setattr(o, key, out[key].ctypes.data)
+        o.max_stride = K
+        _abi.check(env._ctx, _abi.lib().mplx_poly_limits(self._h, C.byref(self._limits_in(v_max, a_max, j_max, all_roots)),
+                                                          C.byref(o)))
+        return out
+
+    def _limits_in(self, v_max, a_max, j_max, all_roots):
+        p, i = self._env._p, _abi.LimitsIn()
+        i.mv = float(p.v_max if v_max is None else v_max)
+        i.ma = float(p.a_max if a_max is None else a_max)
+        i.mj = float(p.j_max if j_max is None else j_max)
+        i.mode = LIMITS_ALL_ROOTS if all_roots else LIMITS_REFERENCE
+        return i
+
     # asynchronous forms on HBM-resident rows (env.TrajInfo / TrajSamples / TrajTraverse); synchronize() before reading
+    def limits_resident(self, out, v_max=None, a_max=None, j_max=None, all_roots=False):
+        """out: EnvMap.alloc_poly_limits(n)."""
+        self._need()
+        o = out.c_struct()
+        _abi.check(self._env._ctx, _abi.lib().mplx_poly_limits_device(self._h, C.byref(self._limits_in(v_max, a_max, j_max, all_roots)),
+                                                                       C.byref(o)))
+
     def info_resident(self, out):
         self._need()
         o = out.c_struct()
@@ -1524,7 +1659,7 @@ class EnvMap:
             o.coeff, o.dts_out, o.yaw_coeff, o.taus = (host[k].ctypes.data for k in ("coeff", "dts", "yaw_coeff", "taus"))
             o.coeff_stride = o.dts_out_stride = o.yaw_stride = o.taus_stride = K
             _abi.check(self._ctx, _abi.lib().mplx_solve(poly._h, C.byref(i), C.byref(o)))
-            poly.n, poly.so, poly.n_wmax, poly._host = K, so, W, host
+            poly.n, poly.so, poly.n_wmax, poly._host, poly.control = K, so, W, host, control
             return poly
         except Exception:
             poly.free()
@@ -1558,8 +1693,167 @@ class EnvMap:
         _abi.check(self._ctx, _abi.lib().mplx_solve_device(poly._h, C.byref(i), C.byref(o)))
         if poly._out is not None and poly._out is not out:
             poly._out.free()
-        poly.n, poly.so, poly.n_wmax, poly._host, poly._out = K, so, int(w_max), None, out
+        poly.n, poly.so, poly.n_wmax, poly._host, poly._out, poly.control = K, so, int(w_max), None, out, control
         return poly
+
+    # ---- caller-given trajectories and two-point primitives (include/mplx_limits.h)
+    def alloc_poly_limits(self, n):
+        return PolyLimits(self, n)
+
+    def load_traj(self, coeff, dts, n_segs=None, control=None):
+        """K trajectories from their primitives (Primitive(cs, t, control) / Trajectory(prs); mplx_poly_load;
+        synchronous).  coeff [S][D + 1][6][K]: c(0) .. c(5) of axis a of segment s at [s][a][:][k], axis D the yaw
+        primitive (of which c(4), the rate, and c(5) are kept), or [S][D][6][K] (no yaw); dts [S][K]; n_segs [K] or None
+        (S each); control: any of the eight flags (default: the EnvMap's).  Returns a PolyTrajSet: info / sample /
+        traverse / limits as on a solved set."""
+        self._flush()
+        control = int(self._p.control if control is None else control)
+        c = np.asarray(coeff, dtype=np.float64)
+        if c.ndim == 3:
+            c = c[..., None]
+        if c.ndim != 4 or c.shape[1] not in (self.dim, self.dim + 1) or c.shape[2] != 6 or c.shape[0] < 1:
+            raise ValueError("coeff must be [S >= 1][%d or %d][6][K]" % (self.dim, self.dim + 1))
+        S, K = c.shape[0], c.shape[3]
+        if c.shape[1] == self.dim:
+            c = np.concatenate([c, np.zeros((S, 1, 6, K))], axis=1)
+        c = np.ascontiguousarray(c)
+        dts = np.ascontiguousarray(np.asarray(dts, dtype=np.float64).reshape(S, K))
+        poly = PolyTrajSet(self, max(K, 1), S + 1)
+        try:
+            i = _abi.PolyLoadIn()
+            i.n_prob, i.w_max, i.control = K, S + 1, control
+            if n_segs is not None:
+                n_segs = np.ascontiguousarray(np.broadcast_to(np.asarray(n_segs, dtype=np.int32), (K,)))
+                i.n_segs = n_segs.ctypes.data
+            i.dts, i.dt_stride, i.coeff, i.coeff_stride = dts.ctypes.data, K, c.ctypes.data, K
+            host = {"status": np.zeros(K, np.uint8), "n_segs": np.zeros(K, np.int32), "total_time": np.zeros(K, np.float64),
+                    "taus": np.zeros((S + 1, K))}
+            o = _abi.PolyLoadOut()
+            o.status, o.n_segs, o.total_time = host["status"].ctypes.data, host["n_segs"].ctypes.data, host["total_time"].ctypes.data
+            o.taus, o.taus_stride = host["taus"].ctypes.data, K
+            _abi.check(self._ctx, _abi.lib().mplx_poly_load(poly._h, C.byref(i), C.byref(o)))
+            seg = np.arange(S)[:, None] < host["n_segs"][None, :]
+            host["dts"] = np.where(seg, dts, 0.0)
+            host["segments"] = np.where(seg[:, None, None, :], c, 0.0)
+            poly.n, poly.so, poly.n_wmax, poly._host, poly.control = K, None, S + 1, host, control
+            return poly
+        except Exception:
+            poly.free()
+            raise
+
+    def alloc_load_out(self, n, w_max):
+        return LoadOut(self, n, w_max)
+
+    def load_traj_resident(self, poly, coeff, dts, n_prob, w_max, n_segs=None, control=None, coeff_stride=None, dt_stride=None,
+                           out=None):
+        """Asynchronous on HBM-resident buffers (mplx_poly_load_device): coeff / dts / n_segs are DeviceArrays or anything
+        with .ptr / data_ptr(); strides default to n_prob.  poly: alloc_poly; out: alloc_load_out (then owned by poly, as
+        the `out` of solve_traj_resident: status / n_segs / total_time / taus() download from it) or None: nothing of the
+        set can be read on the host but what info / sample / traverse / limits return.  dts() and segments() are the
+        caller's own arrays and are not kept."""
+        self._flush()
+        control = int(self._p.control if control is None else control)
+        K = int(n_prob)
+        i = _abi.PolyLoadIn()
+        i.n_prob, i.w_max, i.control = K, int(w_max), control
+        if n_segs is not None:
+            i.n_segs = _device_ptr(n_segs)
+        i.dts, i.dt_stride = _device_ptr(dts), K if dt_stride is None else int(dt_stride)
+        i.coeff, i.coeff_stride = _device_ptr(coeff), K if coeff_stride is None else int(coeff_stride)
+        if out is not None and (out.n != K or out.w_max != int(w_max)):
+            raise ValueError("out was allocated for another problem count or w_max")
+        o = out.c_struct() if out is not None else _abi.PolyLoadOut()
+        _abi.check(self._ctx, _abi.lib().mplx_poly_load_device(poly._h, C.byref(i), C.byref(o)))
+        if poly._out is not None and poly._out is not out:
+            poly._out.free()
+        poly.n, poly.so, poly.n_wmax, poly._host, poly._out, poly.control = K, None, int(w_max), None, out, control
+        return poly
+
+    def shortcut_resident(self, states, n_query, w_max, n_wp=None, control=None, max_hop=None, stride=None):
+        """mplx_shortcut_device on chain states that are on the device already (the seg_state rows of
+        traj_info_resident(want_states=True): field f of state w of query k at [(f w_max + w) stride + k]); n_wp [Q] on
+        the device or None.  Everything is queued without a read-back; then counts, costs, statuses, the kept indices and
+        the edge costs are read.  Returns a ShortcutResult."""
+        self._flush()
+        control = int(self._p.control if control is None else control)
+        so = _solve_order(control)
+        Q, W = int(n_query), int(w_max)
+        hop = W - 1 if max_hop is None else int(max_hop)
+        if Q < 1 or W < 2 or hop < 1:
+            raise ValueError("shortcut: needs Q >= 1, w_max >= 2 and max_hop >= 1")
+        P = Q * (W - 1) * hop
+        pairs, res = PolyTrajSet(self, P, 2), PolyTrajSet(self, Q, W)
+        shapes = {"status": ((Q,), np.uint8), "n_keep": ((Q,), np.int32), "keep": ((W, Q), np.int32), "cost": ((Q,), np.float64),
+                  "chain_cost": ((Q,), np.float64), "edge_cost": ((Q, W - 1, hop), np.float64)}
+        bufs = {}
+        try:
+            pair_out = SolveOut(self, P, 2, so)
+            pairs._out = pair_out
+            i, o = _abi.ShortcutIn(), _abi.ShortcutOut()
+            i.states, i.n_query, i.w_max, i.control, i.max_hop = _device_ptr(states), Q, W, control, hop
+            i.stride = Q if stride is None else int(stride)
+            if n_wp is not None:
+                i.n_wp = _device_ptr(n_wp)
+            for key, (shape, dt) in shapes.items():
+                bufs[key] = DeviceArray(self, int(np.prod(shape)) * np.dtype(dt).itemsize)
+                setattr(o, key, bufs[key].ptr)
+            o.keep_stride = Q
+            po = pair_out.c_struct()
+            o.pair_out = C.pointer(po)
+            _abi.check(self._ctx, _abi.lib().mplx_shortcut_device(pairs._h, res._h, C.byref(i), C.byref(o)))
+            self.synchronize()
+            rows = {key: bufs[key].download(dt, shape) for key, (shape, dt) in shapes.items()}
+            pairs.n, pairs.so, pairs.n_wmax, pairs.control = P, so, 2, control
+            res.n, res.so, res.n_wmax, res.control = Q, None, W, control
+            info = res.info(want_states=True)
+            S = info["n_segs"]
+            taus = np.where(np.arange(W)[:, None] <= S[None, :], info["seg_state"][self.n_fields - 1], 0.0) * (S > 0)[None, :]
+            res._host = {"status": info["status"], "n_segs": S, "total_time": info["total_time"], "taus": taus}
+            return ShortcutResult(res, pairs, hop, rows)
+        except Exception:
+            pairs.free()
+            res.free()
+            raise
+        finally:
+            for b in bufs.values():
+                b.free()
+
+    def shortcut(self, states, n_wp=None, control=None, max_hop=None):
+        """Shortcuts Q chains of states by two-point primitives (mplx_shortcut, include/mplx_limits.h):
+        states [4D+2][w_max][Q] (the seg_state of traj_info(want_states=True)), n_wp [Q] or None (w_max each), control
+        VEL / ACC / JRK (default: the EnvMap's), max_hop (default: w_max - 1).  Needs a map and v_max > 0.  Returns a
+        ShortcutResult."""
+        st = np.ascontiguousarray(np.asarray(states, dtype=np.float64))
+        if st.ndim == 2:
+            st = st[:, :, None]
+        if st.ndim != 3 or st.shape[0] != self.n_fields:
+            raise ValueError("states must be [%d][w_max][Q]" % self.n_fields)
+        W, Q = st.shape[1], st.shape[2]
+        d_st = DeviceArray(self, max(st.nbytes, 8))
+        d_n = None
+        try:
+            d_st.upload(st)
+            if n_wp is not None:
+                n_wp = np.ascontiguousarray(np.broadcast_to(np.asarray(n_wp, dtype=np.int32), (Q,)))
+                d_n = DeviceArray(self, n_wp.nbytes)
+                d_n.upload(n_wp)
+            return self.shortcut_resident(d_st, Q, W, n_wp=d_n, control=control, max_hop=max_hop)
+        finally:
+            d_st.free()
+            if d_n is not None:
+                d_n.free()
+
+    def connect(self, p1_rows, p2_rows, T, control=None):
+        """K two-point primitives Primitive(p1, p2, t) (primitive.h:54-83, 283-302): state rows [4D+2][K] of the two ends
+        and durations T (a scalar or [K]) -> a PolyTrajSet of K one-segment trajectories, through solve_traj with every
+        derivative up to the control's order fixed at both ends.  The coefficients equal the reference's up to rounding,
+        not bit for bit: the reference forms A.inverse() * b with Eigen, this solver an elimination of its own."""
+        a, b = (np.asarray(x, dtype=np.float64).reshape(self.n_fields, -1) for x in (p1_rows, p2_rows))
+        K = a.shape[1]
+        wp = np.ascontiguousarray(np.stack([a, b], axis=1))  # [F][2][K]
+        dts = np.broadcast_to(np.asarray(T, dtype=np.float64), (K,)).reshape(1, K)
+        flags = np.full((2, K), USE_POS | USE_VEL | USE_ACC, np.uint8)
+        return self.solve_traj(wp, dts=dts, control=control, wp_flags=flags)
 
     # ---- the persistent node table (include/mplx_table.h; table.py): relax successor lists, emit the next frontier
     def alloc_table(self, capacity, slots_log2=0, n_queries=1):

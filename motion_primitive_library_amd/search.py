@@ -269,6 +269,53 @@ def _smooth(env, paths, v, control):
             info.free()
 
 
+def _shortcut(env, paths, max_hop, control):
+    """The paths [(start, actions) or None] of Q queries -> chain states on the device (mplx_traj_info_device, want_states)
+    -> mplx_shortcut_device; only counts, costs and statuses are read back.  A query without a path is an empty problem."""
+    from .env import DeviceArray
+    env._flush()
+    Q = len(paths)
+    H = max([len(p[1]) for p in paths if p is not None] + [1])
+    starts = np.zeros((env.n_fields, Q))
+    actions = np.full((H, Q), -1, np.int32)
+    n_wp = np.zeros(Q, np.int32)
+    for q, p in enumerate(paths):
+        if p is not None:
+            starts[:, q] = p[0]
+            actions[:len(p[1]), q] = p[1]
+            n_wp[q] = len(p[1]) + 1
+    bufs = [DeviceArray(env, a.nbytes) for a in (starts, actions, n_wp)]
+    info = None
+    try:
+        for b, a in zip(bufs, (starts, actions, n_wp)):
+            b.upload(a)
+        info = env.alloc_traj_info(Q, H, want_states=True)
+        env.traj_info_resident(bufs[0], bufs[1], info, H)
+        return env.shortcut_resident(info.seg_state, Q, H + 1, n_wp=bufs[2], control=control, max_hop=max_hop)
+    finally:
+        for b in bufs:
+            b.free()
+        if info is not None:
+            info.free()
+
+
+def pick_fastest(poly, Q, vs, v_max=None, a_max=None, j_max=None):
+    """Of the Q x n_v candidates smooth(v=vs) returned (problem vi * Q + q = path q at speed vs[vi]), per query the index
+    vi of the largest speed whose candidate was solved (status 0), is valid under PolyTrajSet.limits(all_roots=True)
+    with the given limits (default: the EnvMap's) and has a finite traverse cost on the map as it is now; -1 where no
+    candidate passes.  Returns an int array [Q]."""
+    vs = np.atleast_1d(np.asarray(vs, dtype=np.float64)).ravel()
+    Q = int(Q)
+    if poly.n != Q * len(vs):
+        raise ValueError("pick_fastest: the set holds %d problems, not Q x n_v = %d" % (poly.n, Q * len(vs)))
+    lim = poly.limits(v_max=v_max, a_max=a_max, j_max=j_max, all_roots=True)
+    trav = poly.traverse()
+    good = ((poly.status == 0) & (lim["valid"] == 1) & (trav["status"] == 0) & np.isfinite(trav["cost"])).reshape(len(vs), Q)
+    speed = np.where(good, vs[:, None], -np.inf)
+    best = np.argmax(speed, axis=0)
+    return np.where(good.any(axis=0), best, -1).astype(np.int64)
+
+
 class SearchResult:
     """What EnvMap.search returns.  status: FOUND, EMPTY (no open node left: the goal region is not reachable within
     g_max), MAX_ROUNDS or MAX_EXPAND (stopped early; the nodes selected last are open again); cost: g of the goal node
@@ -303,6 +350,12 @@ class SearchResult:
         """The path smoothed into a polynomial through its chain states (include/mplx_solve.h): v a scalar or [n_v]
         speeds of the time allocation -> a PolyTrajSet of n_v problems; control: of the ends (default: the EnvMap's)."""
         return _smooth(self._env, [self.path()], v, control)
+
+    def shortcut(self, max_hop=None, control=None):
+        """The path with runs of its short constant-control pieces replaced by two-point primitives between non-adjacent
+        chain states, where those stay within v_max / a_max / j_max and off the obstacles and cost less (mplx_shortcut,
+        include/mplx_limits.h): a ShortcutResult for one query.  max_hop: the longest hop in chain states (default: any)."""
+        return _shortcut(self._env, [self.path()], max_hop, control)
 
     def replan(self, root=None, advance=None, goal_row=None, check_edges=True, prior=None):
         """Plans again on the table of this search after the robot has moved and / or the map was edited
@@ -458,6 +511,11 @@ class MultiSearchResult:
         """SearchResult.smooth for every query in one solve: a PolyTrajSet of Q x n_v problems, problem vi * Q + q = the
         path of query q at speed v[vi]; a query without a path is SOLVE_EMPTY."""
         return _smooth(self._env, [self.path(q) if self.found[q] else None for q in range(self.n_queries)], v, control)
+
+    def shortcut(self, max_hop=None, control=None):
+        """SearchResult.shortcut for every query in one batch of launches: a ShortcutResult of Q queries; a query without
+        a path is SOLVE_EMPTY."""
+        return _shortcut(self._env, [self.path(q) if self.found[q] else None for q in range(self.n_queries)], max_hop, control)
 
     def replan(self, roots=None, advance=None, goal_rows=None, check_edges=True, priors=None):
         """SearchResult.replan for Q queries at once: roots [Q] (node ids; -1 or None: that query's seed), or advance
