@@ -12,6 +12,7 @@ from .env import (ACC, ACCxYAW, JRK, JRKxYAW, SNP, SNPxYAW, VEL, VELxYAW, SLOT_B
                   RAY_TRUNCATED, FLAG_GOAL_BLOCKED, TRAJ_EMPTY, TRAJ_BAD_ACTION, TRAJ_BAD, TRAJ_COMMAND,
                   TRAJ_WAYPOINT, SOLVE_EMPTY, SOLVE_BAD_TIME, SOLVE_SINGULAR, USE_POS, USE_VEL, USE_ACC, PolyTrajSet, SolveOut,
                   LIMITS_REFERENCE, LIMITS_ALL_ROOTS, EXCEED_VEL, EXCEED_ACC, EXCEED_JRK, PolyLimits, LoadOut, ShortcutResult, SHORTCUT_BAD_CHAIN,
+                  SCALE_REFERENCE, SCALE_ROBUST, LAMBDA_BAD_POINTS, LAMBDA_NOT_POSITIVE, LAMBDA_MAX_SEGS, LambdaRows,
                   TrajInfo, TrajSamples, TrajTraverse, Rays, DeviceArray, EnvMap, Lists, PackedLists,
                   Rollouts, Slots, Waypoint, lists_from_dense, pack_host_lists)
 
@@ -25,4 +26,5 @@ __all__ = ["MapPlanner", "MapUtil", "Trajectory", "EnvMap", "Waypoint", "Slots",
            "FLAG_GOAL_BLOCKED", "TRAJ_EMPTY", "TRAJ_BAD_ACTION", "TRAJ_BAD", "TRAJ_COMMAND", "TRAJ_WAYPOINT", "TrajInfo",
            "TrajSamples", "TrajTraverse", "NodeTable", "TableFrontier", "OpenSet", "SearchResult", "MultiSearchResult", "Prior",
            "PolyTrajSet", "SolveOut", "TrajSolver", "SOLVE_EMPTY", "SOLVE_BAD_TIME", "SOLVE_SINGULAR", "USE_POS", "USE_VEL", "USE_ACC",
-           "LIMITS_REFERENCE", "LIMITS_ALL_ROOTS", "EXCEED_VEL", "EXCEED_ACC", "EXCEED_JRK", "PolyLimits", "LoadOut", "ShortcutResult", "SHORTCUT_BAD_CHAIN", "pick_fastest"]
+           "LIMITS_REFERENCE", "LIMITS_ALL_ROOTS", "EXCEED_VEL", "EXCEED_ACC", "EXCEED_JRK", "PolyLimits", "LoadOut", "ShortcutResult", "SHORTCUT_BAD_CHAIN", "pick_fastest",
+           "SCALE_REFERENCE", "SCALE_ROBUST", "LAMBDA_BAD_POINTS", "LAMBDA_NOT_POSITIVE", "LAMBDA_MAX_SEGS", "LambdaRows"]

@@ -75,6 +75,13 @@ LIMITS_SYMBOLS = ["mplx_poly_load_device", "mplx_poly_load", "mplx_poly_limits_d
 SHORTCUT_BAD_CHAIN = 16
 LIMITS_REFERENCE, LIMITS_ALL_ROOTS = 0, 1
 EXCEED_VEL, EXCEED_ACC, EXCEED_JRK = 1, 2, 4
+# ... and the ones include/mplx_scale.h declares (time scaling of the set a poly holds: Lambda, scale, scale_down)
+SCALE_SYMBOLS = ["mplx_poly_set_lambda_device", "mplx_poly_set_lambda", "mplx_poly_scale_device", "mplx_poly_scale",
+                 "mplx_poly_scale_down_device", "mplx_poly_scale_down", "mplx_poly_tau_device", "mplx_poly_tau",
+                 "mplx_poly_clear_lambda"]
+SCALE_REFERENCE, SCALE_ROBUST = 0, 1
+LAMBDA_BAD_POINTS, LAMBDA_NOT_POSITIVE = 32, 64
+LAMBDA_MAX_SEGS, LAMBDA_NEWTON = 8, 3
 
 ROUTE_AUTO, ROUTE_DENSE, ROUTE_TILE, ROUTE_GRID = 0, 1, 2, 3
 
@@ -181,6 +188,31 @@ class LimitsIn(C.Structure):
 class LimitsOut(C.Structure):
     _fields_ = [("max_vel", C.c_void_p), ("max_acc", C.c_void_p), ("max_jrk", C.c_void_p), ("max_stride", C.c_int64),
                 ("exceed", C.c_void_p), ("valid", C.c_void_p), ("first_bad", C.c_void_p)]
+
+
+class LambdaOut(C.Structure):
+    _fields_ = [("status", C.c_void_p), ("n_lseg", C.c_void_p), ("total", C.c_void_p), ("Ts", C.c_void_p),
+                ("ts_stride", C.c_int64), ("segs", C.c_void_p), ("seg_stride", C.c_int64)]
+
+
+class LambdaIn(C.Structure):
+    _fields_ = [("pts", C.c_void_p), ("stride", C.c_int64), ("n_pts", C.c_void_p), ("mode", C.c_int32)]
+
+
+class ScaleIn(C.Structure):
+    _fields_ = [("ri", C.c_double), ("rf", C.c_double), ("ri_arr", C.c_void_p), ("rf_arr", C.c_void_p), ("mode", C.c_int32)]
+
+
+class ScaleDownIn(C.Structure):
+    _fields_ = [("mv", C.c_double), ("ma", C.c_double), ("ri", C.c_double), ("rf", C.c_double), ("mode", C.c_int32)]
+
+
+class ScaleDownOut(C.Structure):
+    _fields_ = [("scaled", C.c_void_p), ("max_l", C.c_void_p), ("t_lo", C.c_void_p), ("t_hi", C.c_void_p), ("lam", LambdaOut)]
+
+
+class TauOut(C.Structure):
+    _fields_ = [("tau", C.c_void_p), ("lam", C.c_void_p), ("lam_dot", C.c_void_p), ("found", C.c_void_p), ("stride", C.c_int64)]
 
 
 class TableView(C.Structure):
@@ -406,6 +438,15 @@ def lib():
         "mplx_poly_limits": (C.c_int, [vp, C.POINTER(LimitsIn), C.POINTER(LimitsOut)]),
         "mplx_shortcut_device": (C.c_int, [vp, vp, C.POINTER(ShortcutIn), C.POINTER(ShortcutOut)]),
         "mplx_shortcut": (C.c_int, [vp, vp, C.POINTER(ShortcutIn), C.POINTER(ShortcutOut)]),
+        "mplx_poly_set_lambda_device": (C.c_int, [vp, C.POINTER(LambdaIn), C.POINTER(LambdaOut)]),
+        "mplx_poly_set_lambda": (C.c_int, [vp, C.POINTER(LambdaIn), C.POINTER(LambdaOut)]),
+        "mplx_poly_scale_device": (C.c_int, [vp, C.POINTER(ScaleIn), C.POINTER(LambdaOut)]),
+        "mplx_poly_scale": (C.c_int, [vp, C.POINTER(ScaleIn), C.POINTER(LambdaOut)]),
+        "mplx_poly_scale_down_device": (C.c_int, [vp, C.POINTER(ScaleDownIn), C.POINTER(ScaleDownOut)]),
+        "mplx_poly_scale_down": (C.c_int, [vp, C.POINTER(ScaleDownIn), C.POINTER(ScaleDownOut)]),
+        "mplx_poly_tau_device": (C.c_int, [vp, C.POINTER(TrajTimes), C.POINTER(TauOut)]),
+        "mplx_poly_tau": (C.c_int, [vp, C.POINTER(TrajTimes), C.POINTER(TauOut)]),
+        "mplx_poly_clear_lambda": (C.c_int, [vp]),
         "mplx_table_create": (C.c_int, [vp, i64, i32, C.POINTER(vp)]),
         "mplx_table_destroy": (None, [vp]),
         "mplx_table_clear": (C.c_int, [vp]),
@@ -438,7 +479,7 @@ def lib():
         "mplx_open_prior_view_of": (C.c_int, [vp, C.POINTER(PriorView)]),
         "mplx_planner_prior_table": (C.c_int, [vp, vp, vp, i32, C.POINTER(i32), vp, C.POINTER(i32)]),
     }
-    for name in SYMBOLS + MAP_UTIL_SYMBOLS + ROLLOUT_SYMBOLS + RAY_SYMBOLS + TRAJ_SYMBOLS + TABLE_SYMBOLS + OPEN_SYMBOLS + MULTI_SYMBOLS + REPLAN_SYMBOLS + PRIOR_SYMBOLS + SOLVE_SYMBOLS + LIMITS_SYMBOLS:
+    for name in SYMBOLS + MAP_UTIL_SYMBOLS + ROLLOUT_SYMBOLS + RAY_SYMBOLS + TRAJ_SYMBOLS + TABLE_SYMBOLS + OPEN_SYMBOLS + MULTI_SYMBOLS + REPLAN_SYMBOLS + PRIOR_SYMBOLS + SOLVE_SYMBOLS + LIMITS_SYMBOLS + SCALE_SYMBOLS:
         fn = getattr(L, name)  # AttributeError if the library does not export it
         fn.restype, fn.argtypes = sig[name]
     _lib = L

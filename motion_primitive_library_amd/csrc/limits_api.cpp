@@ -36,6 +36,7 @@ int load_launch(mplx_poly *p, const mplx_poly_load_in *in, const mplx_poly_load_
   p->w = in->w_max;
   p->solved = true;
   p->control = in->control;
+  p->has_lambda = false;  // a load clears the Lambda, and the gather form does not copy the source's (include/mplx_scale.h)
   const mplx::TrajArgs t = poly_table_args(p);
   mplx::PolyLoadArgs a{};
   a.n_prob = in->n_prob;

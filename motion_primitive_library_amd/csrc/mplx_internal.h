@@ -495,6 +495,11 @@ struct TrajArgs {
   // [4D+2][horizon + 1][N]; horizon = w_max - 1
   int32_t poly;
   const double *tab_dt, *tab_wp;
+  // the Lambda of every problem of a solved set (include/mplx_scale.h; appended).  lam: 0 none, 1 REFERENCE, 2 ROBUST;
+  // lam_n[N] segments (0: the problem is unscaled), lam_seg: field f of segment s at [(s * 8 + f) * N + k], lam_total[N]
+  int32_t lam;
+  const int32_t *lam_n;
+  const double *lam_seg, *lam_total;
 };
 hipError_t launch_traj_chain(int dim, int control, const TrajArgs &a, hipStream_t s);
 hipError_t launch_traj_sample(int dim, int form, const TrajArgs &a, hipStream_t s);
@@ -573,6 +578,57 @@ struct LimitsArgs {
   int32_t *first_bad;
 };
 hipError_t launch_poly_limits(int dim, const LimitsArgs &a, hipStream_t s);
+
+// Time scaling of the set a table holds (scale_kernel.hip, scale_api.cpp; include/mplx_scale.h).  Every array is
+// problem-minor with stride n_prob unless it names its own.
+struct ScaleArgs {
+  int64_t n_prob;
+  int32_t w_max;             // of the set: S_k <= w_max - 1
+  int32_t robust;
+  const int32_t *tab_S;
+  const double *tab_T, *tab_tau, *tab_seg, *tab_dt;
+  // the poly's Lambda table
+  int32_t *lam_n;            // [n_prob]
+  uint8_t *lam_status;       // [n_prob]
+  double *lam_seg;           // [8][8][n_prob]
+  double *lam_Ts;            // [w_max][n_prob]
+  double *lam_total;         // [n_prob]
+  // virtual points the build reads: the caller's, or the scratch rows a scale / scale_down launch filled
+  const double *pts;         // [9][3][pts_stride]
+  int64_t pts_stride;
+  const int32_t *n_pts;      // [n_prob] or null: 9 each
+  const uint8_t *only;       // [n_prob] or null; 0: this problem gets no Lambda and writes nothing
+  // scale / scale_down: what fills the scratch points
+  double ri, rf;
+  const double *ri_arr, *rf_arr;
+  double mv, ma;
+  double *w_pts;             // [9][3][n_prob]
+  int32_t *w_npts;           // [n_prob]
+  uint8_t *w_scaled;         // [n_prob]
+  double *down_seg;          // [w_max - 1][3][n_prob]: max_l (0: no record), t_lo, t_hi of a segment
+  double *w_res;             // [3][n_prob]: max_l, t_lo, t_hi of a scaled problem
+  uint8_t *scaled;
+  double *max_l, *t_lo, *t_hi;
+  // outputs of the build, any may be null
+  uint8_t *status;
+  int32_t *n_lseg;
+  double *total, *Ts, *segs;
+  int64_t ts_stride, seg_stride;
+  // the inverse map: one lane per (problem, time)
+  int32_t n_uniform;
+  const double *times;
+  int64_t time_stride, count;
+  double *tau, *lam, *lam_dot;
+  uint8_t *found;
+  int64_t out_stride;
+  // info on a scaled set: total_time[k] = lam_total[k] where the problem holds a Lambda
+  double *total_time;
+};
+hipError_t launch_lambda_build(const ScaleArgs &a, hipStream_t s);
+hipError_t launch_lambda_scale(const ScaleArgs &a, hipStream_t s);              // points of scale(ri, rf), then the build
+hipError_t launch_lambda_scale_down(int dim, const ScaleArgs &a, hipStream_t s);  // records, points, then the build
+hipError_t launch_lambda_tau(const ScaleArgs &a, hipStream_t s);
+hipError_t launch_lambda_total(const ScaleArgs &a, hipStream_t s);
 
 // Shortcutting (include/mplx_limits.h): the pair problems of Q chains, and the dynamic programme over their costs.
 struct ShortcutArgs {

@@ -19,6 +19,12 @@ struct mplx_poly {
   int32_t w = 0;  // its w_max
   int32_t control = 0;
   bool solved = false;
+  // the Lambda of every problem (include/mplx_scale.h) and the scratch rows of the calls that build one; allocated on
+  // first use for k_cap problems, indexed with the stride n of the last solve or load.  A solve or load drops it.
+  mplx_detail::DevBuf lam;
+  size_t l_n = 0, l_st = 0, l_seg = 0, l_Ts = 0, l_total = 0, l_pts = 0, l_npts = 0, l_scaled = 0, l_down = 0, l_res = 0;
+  bool has_lambda = false;
+  int32_t lam_mode = 0;  // MPLX_SCALE_REFERENCE / MPLX_SCALE_ROBUST of the call that built it
 };
 
 namespace mplx_detail {
@@ -41,8 +47,18 @@ inline mplx::TrajArgs poly_table_args(mplx_poly *p) {
   a.tab_seg = (double *)(base + p->o_seg);
   a.tab_dt = (const double *)(base + p->o_dt);
   a.tab_wp = (const double *)(base + p->o_wp);
+  if (p->has_lambda) {
+    char *lb = (char *)p->lam.p;
+    a.lam = 1 + p->lam_mode;
+    a.lam_n = (const int32_t *)(lb + p->l_n);
+    a.lam_seg = (const double *)(lb + p->l_seg);
+    a.lam_total = (const double *)(lb + p->l_total);
+  }
   return a;
 }
+
+// scale_api.cpp: total_time[k] = the scaled total where problem k holds a Lambda (mplx_poly_info on a scaled set)
+int poly_lambda_total(mplx_poly *p, double *d_total_time);
 
 }  // namespace mplx_detail
 #endif

@@ -18,8 +18,10 @@ struct Sample {
 // seg: the segment's rows for this trajectory (stride N); t: tau - taus[id], finite and >= 0.
 // primitive.h:128-145 with c0 = 0 (its term is +0.0: the leading `0.0 +`), power by repeated multiply.
 // POLY: a solved segment, rows c0 .. c5 per axis: all six terms of primitive.h:128-145, operation for operation.
+// lambda, lambda_dot: Lambda::evaluate at the sample's virtual time (include/mplx_scale.h); 1 and 0 without a Lambda.
 template <int D, bool COMMAND, bool WANT_ALL, bool POLY = false>
-__device__ __forceinline__ void eval_segment(const double *seg, int64_t N, double t, Sample<D> &o) {
+__device__ __forceinline__ void eval_segment(const double *seg, int64_t N, double t, Sample<D> &o, const double lambda = 1.0,
+                                             const double lambda_dot = 0.0) {
   const double t3 = (t * t) * t, t4 = t3 * t;
   constexpr int NA = POLY ? 6 : 5;  // rows per axis
 #pragma unroll
@@ -44,8 +46,7 @@ __device__ __forceinline__ void eval_segment(const double *seg, int64_t N, doubl
       continue;
     }
     if (COMMAND) {
-      // trajectory.h:119-124 with lambda = 1, lambda_dot = 0, operation for operation
-      const double lambda = 1.0, lambda_dot = 0.0;
+      // trajectory.h:119-124, operation for operation
       const double l3 = (1.0 * lambda) * lambda * lambda, l4 = l3 * lambda;
       o.vel[i] = v / lambda;
       o.acc[i] = a / lambda / lambda - o.vel[i] * lambda_dot / lambda / lambda / lambda;

@@ -35,6 +35,7 @@ int solve_launch(mplx_poly *p, const mplx_solve_in *in, const mplx_solve_out *ou
   p->w = in->w_max;
   p->solved = true;
   p->control = in->control;
+  p->has_lambda = false;  // a new solve clears the Lambda (include/mplx_scale.h)
   const mplx::TrajArgs t = poly_table_args(p);
   mplx::SolveArgs a{};
   a.n_prob = a.cap = in->n_prob;
@@ -84,6 +85,7 @@ int check_times(mplx_poly *p, const char *who, const mplx_traj_times *t, const m
 int check_traverse(mplx_poly *p, const char *who, int32_t lanes) {
   mplx_ctx *c = p->c;
   if (lanes != 0 && lanes != 4 && lanes != 16 && lanes != 64) return fail(c, MPLX_ERR_ARG, "%s: lanes must be 0, 4, 16 or 64", who);
+  if (p->has_lambda) return fail(c, MPLX_ERR_STATE, "%s: the poly holds a Lambda; time scaling does not move the path: mplx_poly_clear_lambda first", who);
   if (!c->has_map) return fail(c, MPLX_ERR_STATE, "%s: set the map first", who);
   if (c->n_cells > 0x7fffffffLL) return fail(c, MPLX_ERR_STATE, "%s: the map has more cells than getIndex (int32) can number", who);
   if (!(c->prm.v_max > 0)) return fail(c, MPLX_ERR_STATE, "%s: v_max must be > 0 (env_map.h:231)", who);
@@ -96,6 +98,7 @@ int info_launch(mplx_poly *p, const mplx_traj_info_out *o) {
   a.effort = o->effort; a.effort_stride = o->effort_stride;
   a.seg_state = o->seg_state; a.seg_stride = o->seg_stride;
   HIP_TRY(p->c, mplx::launch_poly_info(p->c->dim, a, p->c->stream));
+  if (p->has_lambda && o->total_time) return poly_lambda_total(p, o->total_time);  // the scaled total (include/mplx_scale.h)
   return MPLX_OK;
 }
 
@@ -164,6 +167,7 @@ void mplx_poly_destroy(mplx_poly *p) {
   (void)hipStreamSynchronize(p->c->stream);
   release(p->mem);
   release(p->aux);
+  release(p->lam);
   delete p;
 }
 

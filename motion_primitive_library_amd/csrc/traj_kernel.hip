@@ -25,6 +25,7 @@
 // and are stated as the leading `0.0 +`; the effort formulas keep c0 as a variable.
 #include "mplx_internal.h"
 #include "mplx_pair_device.h"
+#include "mplx_scale_math.h"
 #include "mplx_traj_device.h"
 
 #include <math.h>
@@ -199,7 +200,9 @@ __device__ __forceinline__ int find_segment(const double *taus, int64_t N, int S
   return g;
 }
 
-template <int D, int FORM, bool POLY = false>
+// LAMBDA (a solved set that holds a Lambda, include/mplx_scale.h): the time is real time, tau = getTau(time) under the
+// Lambda's mode; a problem without one (lam_n == 0) is sampled as ever.
+template <int D, int FORM, bool POLY = false, bool LAMBDA = false>
 __global__ __launch_bounds__(kBlock) void traj_sample_kernel(const TrajArgs R) {
   const int64_t g = (int64_t)blockIdx.x * kBlock + threadIdx.x;
   const int64_t N = R.n_traj;
@@ -208,10 +211,12 @@ __global__ __launch_bounds__(kBlock) void traj_sample_kernel(const TrajArgs R) {
   const int S = R.tab_S[k];
   if (S == 0) return;
   const double T = R.tab_T[k];
+  const int nl = LAMBDA ? R.lam_n[k] : 0;
   double time;
   if (R.n_uniform > 0) {
-    const double step = T / (double)R.n_uniform;  // trajectory.h:233-234
-    time = (double)i * step;
+    const double total = nl > 0 ? R.lam_total[k] : T;
+    const double step = total / (double)R.n_uniform;  // trajectory.h:233-234
+    time = LAMBDA ? scale::uniform_time(i, R.n_uniform, step, total, nl > 0 && R.lam == 2) : (double)i * step;
   } else {
     time = R.times[k * R.time_stride + i];
   }
@@ -222,14 +227,21 @@ __global__ __launch_bounds__(kBlock) void traj_sample_kernel(const TrajArgs R) {
     for (int r = 0; r < kRows; r++) o[(int64_t)r * R.row_stride] = NAN;
     return;
   }
-  double tau = time;
-  if (tau < 0) tau = 0;
-  if (tau > T) tau = T;
+  double tau = time, lambda = 1.0, lambda_dot = 0.0;
+  if (nl > 0) {
+    const scale::TableLoader ld{R.lam_seg + k, N};
+    double raw;
+    bool found;
+    tau = scale::sample_tau(ld, nl, R.lam == 2, time, R.lam_total[k], T, &raw, &found, &lambda, &lambda_dot);
+  } else {
+    if (tau < 0) tau = 0;
+    if (tau > T) tau = T;
+  }
   const double *taus = R.tab_tau + k;
   const int id = find_segment<FORM == 0, POLY>(taus, N, S, tau, R.env.dt);
   tau -= taus[(int64_t)id * N];
   Sample<D> sm;
-  eval_segment<D, FORM == 0, true, POLY>(R.tab_seg + (int64_t)id * ((POLY ? 6 : 5) * D + 2) * N + k, N, tau, sm);
+  eval_segment<D, FORM == 0, true, POLY>(R.tab_seg + (int64_t)id * ((POLY ? 6 : 5) * D + 2) * N + k, N, tau, sm, lambda, lambda_dot);
 #pragma unroll
   for (int d = 0; d < D; d++) {
     o[(int64_t)(0 * D + d) * R.row_stride] = sm.pos[d];
@@ -524,7 +536,9 @@ template <int D, int FORM>
 hipError_t sample_one(const TrajArgs &a, hipStream_t s) {
   const int64_t blocks = (a.n_traj * a.count + kBlock - 1) / kBlock;
   if (blocks > 0x7fffffffLL) return hipErrorInvalidValue;
-  if (a.poly)
+  if (a.poly && a.lam)
+    hipLaunchKernelGGL((traj_sample_kernel<D, FORM, true, true>), dim3((unsigned)blocks), dim3(kBlock), 0, s, a);
+  else if (a.poly)
     hipLaunchKernelGGL((traj_sample_kernel<D, FORM, true>), dim3((unsigned)blocks), dim3(kBlock), 0, s, a);
   else
     hipLaunchKernelGGL((traj_sample_kernel<D, FORM>), dim3((unsigned)blocks), dim3(kBlock), 0, s, a);

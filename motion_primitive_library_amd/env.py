@@ -41,6 +41,8 @@ LIMITS_REFERENCE, LIMITS_ALL_ROOTS = _abi.LIMITS_REFERENCE, _abi.LIMITS_ALL_ROOT
 EXCEED_VEL, EXCEED_ACC, EXCEED_JRK = _abi.EXCEED_VEL, _abi.EXCEED_ACC, _abi.EXCEED_JRK
 SHORTCUT_BAD_CHAIN = _abi.SHORTCUT_BAD_CHAIN
 USE_POS, USE_VEL, USE_ACC = _abi.USE_POS, _abi.USE_VEL, _abi.USE_ACC
+SCALE_REFERENCE, SCALE_ROBUST = _abi.SCALE_REFERENCE, _abi.SCALE_ROBUST  # include/mplx_scale.h
+LAMBDA_BAD_POINTS, LAMBDA_NOT_POSITIVE, LAMBDA_MAX_SEGS = _abi.LAMBDA_BAD_POINTS, _abi.LAMBDA_NOT_POSITIVE, _abi.LAMBDA_MAX_SEGS
 
 
 class Waypoint:
@@ -453,6 +455,65 @@ class PolyLimits:
             b.free()
 
 
+class LambdaRows:
+    """HBM-resident rows of mplx_lambda_out / mplx_scale_down_out for n problems of up to w_max waypoints, and of
+    mplx_tau_out when count > 0 ([n][count] each)."""
+
+    def __init__(self, env, n, w_max, count=0):
+        self.n, self.w_max, self.count = int(n), int(w_max), int(count)
+        n = max(self.n, 1)
+        self.status, self.scaled = DeviceArray(env, n), DeviceArray(env, n)
+        self.n_lseg = DeviceArray(env, n * 4)
+        self.total, self.max_l, self.t_lo, self.t_hi = (DeviceArray(env, n * 8) for _ in range(4))
+        self.Ts = DeviceArray(env, self.w_max * n * 8)
+        self.segs = DeviceArray(env, 64 * n * 8)
+        m = max(n * self.count, 1)
+        self.tau, self.lam, self.lam_dot = (DeviceArray(env, m * 8) for _ in range(3))
+        self.found = DeviceArray(env, m)
+
+    def _all(self):
+        return (self.status, self.scaled, self.n_lseg, self.total, self.max_l, self.t_lo, self.t_hi, self.Ts, self.segs, self.tau,
+                self.lam, self.lam_dot, self.found)
+
+    def fill(self, byte):
+        """Every row set to `byte` (to see afterwards what a call wrote)."""
+        for b in self._all():
+            _abi.check(b._env._ctx, _abi.lib().mplx_memset(b._env._ctx, b.ptr, int(byte), b.nbytes))
+
+    def c_struct(self):
+        s = _abi.LambdaOut()
+        s.status, s.n_lseg, s.total, s.Ts, s.ts_stride, s.segs, s.seg_stride = (self.status.ptr, self.n_lseg.ptr, self.total.ptr,
+                                                                                 self.Ts.ptr, self.n, self.segs.ptr, self.n)
+        return s
+
+    def c_down(self):
+        s = _abi.ScaleDownOut()
+        s.scaled, s.max_l, s.t_lo, s.t_hi, s.lam = self.scaled.ptr, self.max_l.ptr, self.t_lo.ptr, self.t_hi.ptr, self.c_struct()
+        return s
+
+    def c_tau(self):
+        s = _abi.TauOut()
+        s.tau, s.lam, s.lam_dot, s.found, s.stride = self.tau.ptr, self.lam.ptr, self.lam_dot.ptr, self.found.ptr, self.count
+        return s
+
+    def download(self):
+        """Entries a call did not own hold whatever the buffers held."""
+        n, c = self.n, self.count
+        d = {"status": self.status.download(np.uint8, (n,)), "n_lseg": self.n_lseg.download(np.int32, (n,)),
+             "total": self.total.download(np.float64, (n,)), "Ts": self.Ts.download(np.float64, (self.w_max, n)),
+             "segs": self.segs.download(np.float64, (8, 8, n)), "scaled": self.scaled.download(np.uint8, (n,)),
+             "max_l": self.max_l.download(np.float64, (n,)), "t_lo": self.t_lo.download(np.float64, (n,)),
+             "t_hi": self.t_hi.download(np.float64, (n,))}
+        if c:
+            d.update({"tau": self.tau.download(np.float64, (n, c)), "lambda": self.lam.download(np.float64, (n, c)),
+                      "lambda_dot": self.lam_dot.download(np.float64, (n, c)), "found": self.found.download(np.uint8, (n, c))})
+        return d
+
+    def free(self):
+        for b in self._all():
+            b.free()
+
+
 class PolyTrajSet:
     """K solved trajectories on the device (mplx_poly of include/mplx_solve.h): what EnvMap.solve_traj returns and what
     EnvMap.solve_traj_resident solves into.  status [K] (SOLVE_EMPTY | SOLVE_BAD_TIME | SOLVE_SINGULAR; 0 = solved);
@@ -461,7 +522,7 @@ class PolyTrajSet:
     def __init__(self, env, k_cap, w_max):
         self._env, self.k_cap, self.w_max = env, int(k_cap), int(w_max)
         self.n, self.so, self.n_wmax, self.control = 0, None, 0, None
-        self._host, self._out = None, None
+        self._host, self._out, self._lambda = None, None, None
         h = C.c_void_p()
         _abi.check(env._ctx, _abi.lib().mplx_poly_create(env._ctx, self.k_cap, self.w_max, C.byref(h)))
         self._h = h
@@ -660,6 +721,185 @@ class PolyTrajSet:
         self._need()
         o = out.c_struct()
         _abi.check(self._env._ctx, _abi.lib().mplx_poly_traverse_device(self._h, int(lanes), C.byref(o)))
+
+    # ---- time scaling (include/mplx_scale.h): a Lambda per problem.  robust=False is the reference with its quirks (the
+    # 1e-5 clamp of its coefficients, a getTau that loses the end points); robust=True validates the points, applies
+    # no clamp and inverts the time map by Newton steps.  Afterwards sample() takes real times, info() reports the
+    # scaled total and traverse() is refused until clear_lambda().
+    def _lambda_host(self):
+        K = self.n
+        rows = {"status": np.zeros(K, np.uint8), "n_lseg": np.zeros(K, np.int32), "total": np.zeros(K, np.float64),
+                "Ts": np.zeros((self.n_wmax, K), np.float64), "segs": np.zeros((8, 8, K), np.float64)}
+        o = _abi.LambdaOut()
+        o.status, o.n_lseg, o.total = rows["status"].ctypes.data, rows["n_lseg"].ctypes.data, rows["total"].ctypes.data
+        o.Ts, o.ts_stride, o.segs, o.seg_stride = rows["Ts"].ctypes.data, K, rows["segs"].ctypes.data, K
+        return rows, o
+
+    def _keep_lambda(self, rows):
+        self._lambda = {k: rows[k] for k in ("status", "n_lseg", "total", "Ts", "segs")}
+        return rows
+
+    @staticmethod
+    def _mode(robust):
+        return SCALE_ROBUST if robust else SCALE_REFERENCE
+
+    def _scale_in(self, ri, rf, robust, keep):
+        i = _abi.ScaleIn()
+        i.mode = self._mode(robust)
+        for name, v in (("ri", ri), ("rf", rf)):
+            if np.ndim(v) == 0:
+                setattr(i, name, float(v))
+            else:
+                a = np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=np.float64), (self.n,)))
+                keep.append(a)
+                setattr(i, name + "_arr", a.ctypes.data)
+        return i
+
+    def scale(self, ri, rf, robust=True):
+        """Trajectory::scale(ri, rf) on every trajectory (mplx_poly_scale; synchronous): ri, rf scalars or [K] ratios at
+        the start and the end.  Returns status [K] (0, LAMBDA_BAD_POINTS, LAMBDA_NOT_POSITIVE), n_lseg, total, Ts, segs;
+        entries of failed problems are zero."""
+        self._need()
+        keep = []
+        rows, o = self._lambda_host()
+        i = self._scale_in(ri, rf, robust, keep)
+        _abi.check(self._env._ctx, _abi.lib().mplx_poly_scale(self._h, C.byref(i), C.byref(o)))
+        return self._keep_lambda(rows)
+
+    def _down_in(self, v_max, a_max, ri, rf, robust):
+        p, i = self._env._p, _abi.ScaleDownIn()
+        i.mv = float(p.v_max if v_max is None else v_max)
+        i.ma = float(p.a_max if a_max is None else a_max)
+        i.ri, i.rf, i.mode = float(ri), float(rf), self._mode(robust)
+        return i
+
+    def scale_down(self, v_max=None, a_max=None, ri=0.0, rf=0.0, robust=True):
+        """Slow every trajectory that breaks v_max / a_max (default: the EnvMap's; <= 0: not checked) down to them
+        (mplx_poly_scale_down; synchronous).  ri, rf: lambda at the two ends, <= 0: max_l, i.e. no ramp; with both the
+        scaling is uniform and within the limits by construction -- ramps are NOT checked against the limits.  Returns
+        scaled [K] (0: within the limits, left unscaled), max_l, t_lo, t_hi and the rows of scale()."""
+        self._need()
+        K = self.n
+        rows, lo = self._lambda_host()
+        rows.update({"scaled": np.zeros(K, np.uint8), "max_l": np.zeros(K), "t_lo": np.zeros(K), "t_hi": np.zeros(K)})
+        o = _abi.ScaleDownOut()
+        o.scaled, o.max_l, o.t_lo, o.t_hi, o.lam = (rows["scaled"].ctypes.data, rows["max_l"].ctypes.data, rows["t_lo"].ctypes.data,
+                                                    rows["t_hi"].ctypes.data, lo)
+        i = self._down_in(v_max, a_max, ri, rf, robust)
+        _abi.check(self._env._ctx, _abi.lib().mplx_poly_scale_down(self._h, C.byref(i), C.byref(o)))
+        return self._keep_lambda(rows)
+
+    @staticmethod
+    def _points(p, v, t, K):
+        """[9][3][K] rows of p, v, t given as [n_max][K] (or [n_max]: the same for every problem)."""
+        cols = [np.asarray(x, dtype=np.float64) for x in (p, v, t)]
+        cols = [np.broadcast_to(x[:, None], (x.shape[0], K)) if x.ndim == 1 else x for x in cols]
+        n_max = cols[0].shape[0]
+        if n_max > 9 or any(x.shape != (n_max, K) for x in cols):
+            raise ValueError("p, v, t must be [n <= 9][K] (or [n <= 9])")
+        pts = np.zeros((9, 3, K))
+        for f, x in enumerate(cols):
+            pts[:n_max, f, :] = x
+        return pts, n_max
+
+    def set_lambda(self, p, v, t, n_pts=None, robust=True):
+        """Lambda(vs) from virtual points (mplx_poly_set_lambda; synchronous): p, v, t [n_max][K] (or [n_max]), point j of
+        problem k at [j][k], j < n_pts[k] (None: n_max each).  Returns the rows of scale()."""
+        self._need()
+        K = self.n
+        pts, n_max = self._points(p, v, t, K)
+        n = np.ascontiguousarray(np.broadcast_to(np.asarray(n_max if n_pts is None else n_pts, dtype=np.int32), (K,)))
+        rows, o = self._lambda_host()
+        i = _abi.LambdaIn()
+        i.pts, i.stride, i.n_pts, i.mode = pts.ctypes.data, K, n.ctypes.data, self._mode(robust)
+        _abi.check(self._env._ctx, _abi.lib().mplx_poly_set_lambda(self._h, C.byref(i), C.byref(o)))
+        return self._keep_lambda(rows)
+
+    def clear_lambda(self):
+        """Every trajectory is unscaled again."""
+        self._need()
+        _abi.check(self._env._ctx, _abi.lib().mplx_poly_clear_lambda(self._h))
+        self._lambda = None
+
+    def _lambda_rows(self):
+        rows = self._lambda
+        if rows is None:
+            raise RuntimeError("PolyTrajSet: no Lambda (scale, scale_down or set_lambda first; the _resident forms keep theirs on the device)")
+        return rows
+
+    def lambda_segments(self):
+        """The Lambda of every problem as the last synchronous scale / scale_down / set_lambda left it: a [8][4][K] (a3 a2
+        a1 a0 of segment s at [s][:][k]), ti, tf, T0 (getT(ti)), dT [8][K], n_lseg [K], status [K]."""
+        r = self._lambda_rows()
+        g = r["segs"]
+        return {"a": g[:, 0:4, :], "ti": g[:, 4, :], "tf": g[:, 5, :], "T0": g[:, 6, :], "dT": g[:, 7, :], "n_lseg": r["n_lseg"],
+                "status": r["status"]}
+
+    def segment_times(self):
+        """Trajectory::getSegmentTimes: [w_max - 1][K], Ts[s + 1] - Ts[s]; zero past S_k and for a problem without a
+        Lambda status 0."""
+        r = self._lambda_rows()
+        Ts = r["Ts"]
+        ok = (np.arange(self.n_wmax - 1)[:, None] < self.n_segs[None, :]) & (r["n_lseg"] > 0)[None, :]
+        return np.where(ok, Ts[1:] - Ts[:-1], 0.0)
+
+    def tau(self, times=None, N=None):
+        """The inverse time map (mplx_poly_tau; synchronous): tau, lambda, lambda_dot [K][count] and found [K][count] at
+        the real times `times` ([Q] or [K][Q]) or at the N + 1 uniform ones."""
+        self._need()
+        K, env = self.n, self._env
+        t, tkeep, count = env._traj_times(N, times, TRAJ_COMMAND, K)
+        out = {"tau": np.zeros((K, count)), "lambda": np.zeros((K, count)), "lambda_dot": np.zeros((K, count)),
+               "found": np.zeros((K, count), np.uint8)}
+        o = _abi.TauOut()
+        o.tau, o.lam, o.lam_dot, o.found, o.stride = (out["tau"].ctypes.data, out["lambda"].ctypes.data, out["lambda_dot"].ctypes.data,
+                                                      out["found"].ctypes.data, count)
+        _abi.check(env._ctx, _abi.lib().mplx_poly_tau(self._h, C.byref(t), C.byref(o)))
+        return out
+
+    # asynchronous forms on HBM-resident rows (EnvMap.alloc_lambda_rows); synchronize() before reading
+    def scale_resident(self, out, ri, rf, robust=True):
+        """ri, rf: scalars, or DeviceArrays of [K] float64."""
+        self._need()
+        i = _abi.ScaleIn()
+        i.mode = self._mode(robust)
+        for name, v in (("ri", ri), ("rf", rf)):
+            if np.ndim(v) == 0 and not hasattr(v, "ptr") and not hasattr(v, "data_ptr"):
+                setattr(i, name, float(v))
+            else:
+                setattr(i, name + "_arr", _device_ptr(v))
+        o = out.c_struct()
+        _abi.check(self._env._ctx, _abi.lib().mplx_poly_scale_device(self._h, C.byref(i), C.byref(o)))
+        self._lambda = None
+
+    def scale_down_resident(self, out, v_max=None, a_max=None, ri=0.0, rf=0.0, robust=True):
+        self._need()
+        o = out.c_down()
+        i = self._down_in(v_max, a_max, ri, rf, robust)
+        _abi.check(self._env._ctx, _abi.lib().mplx_poly_scale_down_device(self._h, C.byref(i), C.byref(o)))
+        self._lambda = None
+
+    def set_lambda_resident(self, out, pts, n_pts=None, stride=None, robust=True):
+        """pts: [9][3][stride] float64 on the device; n_pts: [K] int32 on the device or None (9 each)."""
+        self._need()
+        i = _abi.LambdaIn()
+        i.pts, i.stride, i.mode = _device_ptr(pts), self.n if stride is None else int(stride), self._mode(robust)
+        if n_pts is not None:
+            i.n_pts = _device_ptr(n_pts)
+        o = out.c_struct()
+        _abi.check(self._env._ctx, _abi.lib().mplx_poly_set_lambda_device(self._h, C.byref(i), C.byref(o)))
+        self._lambda = None
+
+    def tau_resident(self, out, N=None, times=None, n_times=None, time_stride=0):
+        """out: alloc_lambda_rows(n, w_max, count) with count >= the sample count."""
+        self._need()
+        t = _abi.TrajTimes()
+        if N is not None:
+            t.n_uniform = int(N)
+        else:
+            t.times, t.n_times, t.time_stride = _device_ptr(times), int(n_times), int(time_stride)
+        o = out.c_tau()
+        _abi.check(self._env._ctx, _abi.lib().mplx_poly_tau_device(self._h, C.byref(t), C.byref(o)))
 
 
 STATE_ROW_PAD = 0  # default padding between the state rows of Lists, in entries (see Lists.state_stride)
@@ -1660,6 +1900,7 @@ class EnvMap:
             o.coeff_stride = o.dts_out_stride = o.yaw_stride = o.taus_stride = K
             _abi.check(self._ctx, _abi.lib().mplx_solve(poly._h, C.byref(i), C.byref(o)))
             poly.n, poly.so, poly.n_wmax, poly._host, poly.control = K, so, W, host, control
+            poly._lambda = None  # a new solve or load clears the Lambda
             return poly
         except Exception:
             poly.free()
@@ -1694,11 +1935,15 @@ class EnvMap:
         if poly._out is not None and poly._out is not out:
             poly._out.free()
         poly.n, poly.so, poly.n_wmax, poly._host, poly._out, poly.control = K, so, int(w_max), None, out, control
+        poly._lambda = None  # a new solve or load clears the Lambda
         return poly
 
     # ---- caller-given trajectories and two-point primitives (include/mplx_limits.h)
     def alloc_poly_limits(self, n):
         return PolyLimits(self, n)
+
+    def alloc_lambda_rows(self, n, w_max, count=0):
+        return LambdaRows(self, n, w_max, count)
 
     def load_traj(self, coeff, dts, n_segs=None, control=None):
         """K trajectories from their primitives (Primitive(cs, t, control) / Trajectory(prs); mplx_poly_load;
@@ -1736,6 +1981,7 @@ class EnvMap:
             host["dts"] = np.where(seg, dts, 0.0)
             host["segments"] = np.where(seg[:, None, None, :], c, 0.0)
             poly.n, poly.so, poly.n_wmax, poly._host, poly.control = K, None, S + 1, host, control
+            poly._lambda = None  # a new solve or load clears the Lambda
             return poly
         except Exception:
             poly.free()
@@ -1767,6 +2013,7 @@ class EnvMap:
         if poly._out is not None and poly._out is not out:
             poly._out.free()
         poly.n, poly.so, poly.n_wmax, poly._host, poly._out, poly.control = K, None, int(w_max), None, out, control
+        poly._lambda = None  # a new solve or load clears the Lambda
         return poly
 
     def shortcut_resident(self, states, n_query, w_max, n_wp=None, control=None, max_hop=None, stride=None):
