@@ -117,10 +117,13 @@ int mplx_poly_limits(mplx_poly *poly, const mplx_limits_in *in, const mplx_limit
  *   the smallest i; cost = dist[W - 1]; chain_cost = the sequential sum of the adjacent edges' costs.
  * Pair p = (k (w_max - 1) + i) max_hop + (j - i - 1); pairs with j >= W_k are empty problems.  `pairs` (k_cap >=
  * Q (w_max - 1) max_hop, w_max >= 2) holds the pair set afterwards, `result` (k_cap >= Q, the chain's w_max) the Q chosen
- * trajectories, gathered from the pairs without a second solve.  W_k < 2 is MPLX_SOLVE_EMPTY.  All launches are queued
- * on the context's stream with no read-back between them.  states / n_wp / every output: device memory (_device) or
- * host memory (the twin, synchronous).  Errors: MPLX_ERR_ARG for NULLs, polys of two contexts or too small, max_hop < 1,
- * a stride below Q, a control other than VEL / ACC / JRK; MPLX_ERR_STATE without a map or with v_max <= 0. */
+ * trajectories, gathered from the pairs without a second solve.  W_k < 2 is MPLX_SOLVE_EMPTY.  A MPLX_SHORTCUT_BAD_CHAIN
+ * query has no trajectory either: its identity chain holds the pair whose solve failed, which has no segment to gather,
+ * so its problem of `result` is MPLX_SOLVE_EMPTY (no segments, no samples), as that of an empty query.  All launches
+ * are queued on the context's stream with no read-back between them.  states / n_wp / every output: device memory
+ * (_device) or host memory (the twin, synchronous); every output is optional.  Errors: MPLX_ERR_ARG for NULLs, polys of
+ * two contexts or too small, max_hop < 1, a stride below Q, a control other than VEL / ACC / JRK; MPLX_ERR_STATE without a
+ * map or with v_max <= 0. */
 enum { MPLX_SHORTCUT_BAD_CHAIN = 16 };
 
 typedef struct {
@@ -130,7 +133,7 @@ typedef struct {
   int32_t w_max;
   int32_t control;         /* MPLX_VEL / ACC / JRK, with or without the yaw bit                                          */
   int64_t stride;
-  const int32_t *n_wp;     /* [Q] W_k, or NULL: w_max each                                                               */
+  const int32_t *n_wp;     /* [Q] W_k, or NULL: w_max each; a count above w_max behaves as w_max                         */
   int32_t max_hop;         /* >= 1                                                                                       */
 } mplx_shortcut_in;
 

@@ -415,11 +415,13 @@ class ShortcutResult:
     """What EnvMap.shortcut / SearchResult.shortcut return (mplx_shortcut, include/mplx_limits.h).  poly: the PolyTrajSet of
     the Q shortcut trajectories; pairs: the PolyTrajSet of the Q (w_max - 1) max_hop pair problems (pair (k, i, j) at
     (k (w_max - 1) + i) max_hop + (j - i - 1)); per query status (0, SOLVE_EMPTY, SHORTCUT_BAD_CHAIN), keep (a list of
-    ascending state indices), cost, chain_cost; edge_cost [Q][w_max - 1][max_hop] (+inf: not admitted).  free() it."""
+    ascending state indices; keep_rows: the call's own [w_max][Q] rows, -1 past n_keep), cost, chain_cost; edge_cost
+    [Q][w_max - 1][max_hop] (+inf: not admitted).  free() it."""
 
     def __init__(self, poly, pairs, max_hop, rows):
         self.poly, self.pairs, self.max_hop = poly, pairs, int(max_hop)
         self.status, self.n_keep, self.cost, self.chain_cost = rows["status"], rows["n_keep"], rows["cost"], rows["chain_cost"]
+        self.keep_rows = rows["keep"]
         self.keep = [rows["keep"][:n, k].copy() for k, n in enumerate(self.n_keep)]
         self.edge_cost = rows["edge_cost"]
 
