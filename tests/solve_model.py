@@ -2,7 +2,8 @@
 
 Why a model and not the reference's own binary: the solver of the reference (mpl_traj_solver) needs Eigen's
 partialPivLu, block and topRows; no Eigen exists on the build machine, oracle/stub_include has none of the three, and
-oracle/ is frozen.  The reference's program therefore cannot be compiled, and two restatements stand in for it:
+oracle/ is frozen.  The reference's program therefore cannot be compiled, and two restatements stand in for it (a third
+function restates the device, not the reference):
 
   solve_dense   src/mpl_traj_solver/poly_solver.cpp:23-221 line for line in float64: A, Q, the permutation table, M,
                 A^-1 M, R, Rpp / Rpf, Dp, and the per-segment solve.  lu_solve below stands in for
@@ -13,6 +14,10 @@ oracle/ is frozen.  The reference's program therefore cannot be compiled, and tw
                 waypoints with free end derivatives are solved (poly_solver.cpp:202-209 reads uninitialised memory).
   solve_exact   the same statement in fractions.Fraction with dense Gaussian elimination.  The inputs are doubles, hence
                 exact rationals: this is the exact minimiser, and the yardstick of both solve_dense and the device.
+
+  solve_block   not a model of the reference but a twin of the device: csrc/solve_kernel.hip's block elimination restated
+                in float64 in the kernel's own operation order, so that the device's coefficients for so >= 1 can be held
+                bit for bit.  It shares the kernel's derivation; solve_exact and solve_dense stay the yardstick of both.
 
 plus allocate_time (traj_solver.h:122-130), setTime (poly_traj.cpp:64-69), toPrimitives (poly_traj.cpp:72-88), and the
 six-coefficient primitive through tests/traj_model.py (poly_p / poly_v / poly_a / poly_j / effort_1d), class PolySet
@@ -390,3 +395,272 @@ def cpu_cases():
     pos = random_path(rng, 6, 3)
     out.append(("mixed_dt", path_vals(pos, np.round(rng.uniform(-1, 1, (2, 3)), 2)), np.array([1.1, 0.05, 4.9, 0.05, 4.9])))
     return out
+
+
+# ------------------------------------------------------------------------- the kernel's own elimination, restated
+HHAT = {1: [[1, -1], [-1, 1]],
+        2: [[12, 6, -12, 6], [6, 4, -6, 2], [-12, -6, 12, -6], [6, 2, -6, 4]],
+        3: [[720, 360, 60, -720, 360, -60], [360, 192, 36, -360, 168, -24], [60, 36, 9, -60, 24, -3],
+            [-720, -360, -60, 720, -360, 60], [360, 168, 24, -360, 192, -36], [-60, -24, -3, 60, -36, 9]]}
+BINV = {1: [[1.0]], 2: [[3, -1], [-2, 1]], 3: [[10, -4, 0.5], [-15, 7, -1], [6, -3, 0.5]]}
+
+
+def _falling(n, q):
+    """n! / (n - q)!"""
+    r = 1
+    for m in range(q):
+        r *= n - m
+    return r
+
+
+def solve_block(vals, flags, dts, so):
+    """solve_kernel<D, SO> (csrc/solve_kernel.hip) for one problem, in float64, one IEEE operation at a time, in the
+    kernel's own order: the same Hhat and B^-1 constants, H = Hhat / T^e with powers by repeated multiply, the
+    right-hand sides (carry, then the fixed derivatives of w through G, then those of w + 1 through H[0T]), the Schur
+    complement G - C_{w-1}^T Z_{w-1}, the LDL^T without pivoting, the two triangular solves with the division by the
+    pivots between them, x_w = z_w - Z_w x_{w+1}, the low half d_k / k! and the high half through binv, divided by
+    tp[h + j].  Returns p [S * N][D] as PolyTraj::p(), or None where the kernel reports a status: W < 2 (EMPTY), a
+    duration that is not finite or <= 0 (BAD_TIME), a pivot that is not finite or <= 0 (SINGULAR).
+
+    This is a TWIN of the kernel, not an independent reference: it shares the kernel's derivation and would share a
+    mistake in it.  solve_exact and solve_dense remain the yardstick of both; what the twin adds is that the device's
+    so >= 1 coefficients can be held bit for bit (the kernel is built with -ffp-contract=off and divides truly), so a
+    slip in the recursion that stays within the dense model's rounding noise cannot pass."""
+    f64 = np.float64
+    vals = np.asarray(vals, dtype=np.float64)
+    W, D = vals.shape[1], vals.shape[2]
+    if W < 2:
+        return None
+    h = so + 1
+    N = 2 * h
+    hh, bi = HHAT[h], BINV[h]
+    zero, one = f64(0.0), f64(1.0)
+    fl = [int(flags[w]) & ((1 << h) - 1) for w in range(W)]
+    fact = [f64(FACT[a]) for a in range(N)]
+    cur = [[f64(vals[a][0][i]) for i in range(D)] for a in range(h)]
+    nx = [[zero] * D for _ in range(h)]
+    gtt = [[zero] * h for _ in range(h)]
+    cp = [[zero] * h for _ in range(h)]
+    zp = [[zero] * h for _ in range(h)]
+    carry = [[zero] * D for _ in range(h)]
+    zr = [[zero] * D for _ in range(h)]
+    Zs, zs, Ts = [], [], []
+    fc = fl[0]
+    with np.errstate(all="ignore"):
+        for w in range(W):
+            last = w == W - 1
+            H00 = [[zero] * h for _ in range(h)]
+            H0T = [[zero] * h for _ in range(h)]
+            HTT = [[zero] * h for _ in range(h)]
+            fn = 0
+            if not last:
+                nx = [[f64(vals[a][w + 1][i]) for i in range(D)] for a in range(h)]
+                fn = fl[w + 1]
+                T = f64(dts[w])
+                if not (T > 0.0) or not np.isfinite(T):
+                    return None
+                Ts.append(T)
+                tp = [one]
+                for m in range(1, N):
+                    tp.append(tp[m - 1] * T)
+                for a in range(h):
+                    for b in range(h):
+                        e = tp[2 * h - 1 - a - b]
+                        H00[a][b] = f64(hh[a][b]) / e
+                        H0T[a][b] = f64(hh[a][h + b]) / e
+                        HTT[a][b] = f64(hh[h + a][h + b]) / e
+            G = [[gtt[a][c] + H00[a][c] for c in range(h)] for a in range(h)]
+            b = [[zero] * D for _ in range(h)]
+            for a in range(h):
+                for i in range(D):
+                    acc = carry[a][i]
+                    for j in range(h):
+                        if fc >> j & 1:
+                            acc = acc - G[a][j] * cur[j][i]
+                    for j in range(h):
+                        if not last and (fn >> j & 1):
+                            acc = acc - H0T[a][j] * nx[j][i]
+                    b[a][i] = cur[a][i] if (fc >> a & 1) else acc
+            C = [[zero] * h for _ in range(h)]
+            for a in range(h):
+                for c in range(h):
+                    C[a][c] = H0T[a][c] if (not last and not (fc >> a & 1) and not (fn >> c & 1)) else zero
+                    if (fc >> a & 1) or (fc >> c & 1):
+                        G[a][c] = one if a == c else zero
+            if w > 0:
+                for a in range(h):
+                    for c in range(a + 1):
+                        s = G[a][c]
+                        for m in range(h):
+                            s = s - cp[m][a] * zp[m][c]
+                        G[a][c] = s
+                        G[c][a] = s
+                    for i in range(D):
+                        s = b[a][i]
+                        for m in range(h):
+                            s = s - cp[m][a] * zr[m][i]
+                        b[a][i] = s
+            L = [[zero] * h for _ in range(h)]
+            dd = [zero] * h
+            bad = False
+            for j in range(h):
+                s = G[j][j]
+                for m in range(j):
+                    s = s - L[j][m] * L[j][m] * dd[m]
+                dd[j] = s
+                bad = bad or not (s > 0.0) or not np.isfinite(s)
+                for i in range(j + 1, h):
+                    q = G[i][j]
+                    for m in range(j):
+                        q = q - L[i][m] * L[j][m] * dd[m]
+                    L[i][j] = q / s
+            if bad:
+                return None
+            X = [[C[a][c] for c in range(h)] + [b[a][i] for i in range(D)] for a in range(h)]
+            for c in range(h + D):
+                for a in range(h):
+                    for m in range(a):
+                        X[a][c] = X[a][c] - L[a][m] * X[m][c]
+                for a in range(h):
+                    X[a][c] = X[a][c] / dd[a]
+                for a in range(h - 1, -1, -1):
+                    for m in range(a + 1, h):
+                        X[a][c] = X[a][c] - L[m][a] * X[m][c]
+            zp = [[X[a][c] for c in range(h)] for a in range(h)]
+            cp = C
+            zr = [[X[a][h + i] for i in range(D)] for a in range(h)]
+            Zs.append(zp)
+            zs.append(zr)
+            gtt = HTT
+            carry = [[zero] * D for _ in range(h)]
+            for a in range(h):
+                for i in range(D):
+                    acc = zero
+                    for j in range(h):
+                        if fc >> j & 1:
+                            acc = acc - H0T[j][a] * cur[j][i]
+                    carry[a][i] = acc
+            if not last:
+                cur = nx
+                fc = fn
+        S = W - 1
+        xn = [[cur[a][i] if (fc >> a & 1) else zr[a][i] for i in range(D)] for a in range(h)]
+        p = np.zeros((S * N, D))
+        for w in range(S - 1, -1, -1):
+            x = [[zero] * D for _ in range(h)]
+            for a in range(h):
+                for i in range(D):
+                    s = zs[w][a][i]
+                    for j in range(h):
+                        s = s - Zs[w][a][j] * xn[j][i]
+                    x[a][i] = f64(vals[a][w][i]) if (fl[w] >> a & 1) else s
+            T = Ts[w]
+            tp = [one]
+            for m in range(1, N):
+                tp.append(tp[m - 1] * T)
+            for i in range(D):
+                pl = [x[a][i] / fact[a] for a in range(h)]
+                pt = [pl[a] * tp[a] for a in range(h)]
+                r = []
+                for q in range(h):
+                    acc = xn[q][i] * tp[q]
+                    for m in range(q, h):
+                        acc = acc - f64(_falling(m, q)) * pt[m]
+                    r.append(acc)
+                for a in range(h):
+                    p[w * N + a, i] = pl[a]
+                for j in range(h):
+                    acc = f64(bi[j][0]) * r[0]
+                    for q in range(1, h):
+                        acc = acc + f64(bi[j][q]) * r[q]
+                    p[w * N + h + j, i] = acc / tp[h + j]
+            xn = x
+    return p
+
+
+# ------------------------------------------------------------------- inputs of tests/test_gpu_poly_long.py
+LONG_K, LONG_WMAX = 200, 33  # three full waves and eight lanes; up to 32 segments
+LONG_NWP = [0, 1, 2, 3, 8, 9, 16, 17, 24, 32, 33, 40]  # n_wp[k] cycles through these; 40 is clamped to w_max
+LONG_SEED = 300  # + D; chosen on the CPU with solve_block, see tests/test_gpu_poly_long.py
+# the problems that go against solve_exact (W <= 24, every duration pattern), per duration mode
+LONG_EXACT = {"given": [3, 6, 16, 19, 29, 32], "alloc_arr": [16, 29]}
+
+
+def long_w(k):
+    return min(LONG_NWP[k % len(LONG_NWP)], LONG_WMAX)
+
+
+def long_pattern(k):
+    """The second problem of every W class alternates 0.05 s / 4.9 s, the third grows geometrically from 0.05 s to 5 s."""
+    return {1: "alternating", 2: "geometric"}.get(k // len(LONG_NWP), "random")
+
+
+_LONG = {}
+
+
+def long_problems(D):
+    """wp [4D+2][33][200] state rows, n_wp [200], dts [32][200], v_arr [200]: computed once per D, never changed.
+    Derivative rows as test_gpu_solve.problems; durations random in [0.3, 2.0] rounded to 1e-3, and the two patterns of
+    long_pattern, whose problems lie along axis 0 with v = 1 so that allocate_time gives (nearly) the same durations."""
+    if D in _LONG:
+        return _LONG[D]
+    K, WM = LONG_K, LONG_WMAX
+    rng = np.random.default_rng(LONG_SEED + D)
+    wp = np.zeros((4 * D + 2, WM, K))
+    for k in range(K):
+        wp[:D, :, k] = random_path(rng, WM, D).T
+    wp[D:4 * D] = np.round(rng.uniform(-1, 1, (3 * D, WM, K)), 2)
+    wp[4 * D] = rng.uniform(-3, 3, (WM, K))
+    v_arr = np.round(rng.uniform(0.4, 2.5, K), 3)
+    dts = np.round(rng.uniform(0.3, 2.0, (WM - 1, K)), 3)
+    for k in range(K):
+        S, pat = long_w(k) - 1, long_pattern(k)
+        if S < 1 or pat == "random":
+            continue
+        dts[:S, k] = [(0.05, 4.9)[s % 2] for s in range(S)] if pat == "alternating" else np.geomspace(0.05, 5.0, S) if S > 1 else [0.05]
+        v_arr[k] = 1.0
+        step = np.zeros((WM - 1, D))
+        step[:, 0] = dts[:, k]
+        step[:, 1:] = 0.3 * dts[:, k][:, None]
+        wp[:D, 1:, k] = (wp[:D, 0, k][None, :] + np.cumsum(step, axis=0)).T
+    n_wp = np.array([LONG_NWP[k % len(LONG_NWP)] for k in range(K)], np.int32)
+    for a in (wp, n_wp, dts, v_arr):
+        a.setflags(write=False)
+    _LONG[D] = (wp, n_wp, dts, v_arr)
+    return _LONG[D]
+
+
+def long_vals(wp, k, W, D):
+    return np.stack([wp[a * D:(a + 1) * D, :W, k].T for a in range(3)])  # [3][W][D]
+
+
+def long_durations(D, mode, k):
+    wp, _, dts, v_arr = long_problems(D)
+    W = long_w(k)
+    if mode == "given":
+        return dts[:W - 1, k].copy()
+    return allocate_time(wp[:D, :W, k].T, v_arr[k])
+
+
+def long_flag_problems():
+    """The flags set of tests/test_gpu_poly_long.py, setWaypoints mode at W = 17, so = 2, D = 3, K = 5: wp [14][17][5],
+    flags [17][5], dts [16][5].  Problem 0: interior waypoints fix (pos); 1: (pos, vel); 2: (vel only) between position
+    waypoints; 3: (pos) with every fourth (pos, vel), and an end with a free acceleration; 4: no fixed position anywhere,
+    durations powers of two -- the free system is a scalar chain whose pivots stay exact, so the last one is an exact
+    zero, not a rounding residue."""
+    D, W, Kf = 3, 17, 5
+    P, V, A = USE_POS, USE_VEL, USE_ACC
+    flags = np.zeros((W, Kf), np.uint8)
+    flags[:, 0] = [7] + [P] * (W - 2) + [7]
+    flags[:, 1] = [7] + [P | V] * (W - 2) + [7]
+    flags[:, 2] = [7] + [P if w % 2 else V for w in range(1, W - 1)] + [7]
+    flags[:, 3] = [7] + [P | V if w % 4 == 0 else P for w in range(1, W - 1)] + [P | V]
+    flags[:, 4] = V | A
+    rng = np.random.default_rng(19)
+    wp = np.zeros((4 * D + 2, W, Kf))
+    for k in range(Kf):
+        wp[:D, :, k] = random_path(rng, W, D).T
+    wp[D:3 * D] = np.round(rng.uniform(-1, 1, (2 * D, W, Kf)), 2)
+    dts = np.round(rng.uniform(0.4, 1.8, (W - 1, Kf)), 3)
+    dts[:, 4] = [1.0, 2.0, 0.5, 1.0] * 4
+    return wp, flags, dts

@@ -5,7 +5,11 @@ solve_dense (poly_solver.cpp restated in float64) is held to solve_exact (the sa
 bound that comes from the problem, not from either model: an LU solve of a system of order n loses at most about
 n * eps * cond relative to its solution, and the dense solve chains two of them -- the free system Rpp and the
 segment's own N x N block of A -- so |dense - exact| <= (n_free * cond_2(Rpp) + N * max_s cond_2(A_s)) * 2^-52 * scale,
-with a floor of 64 * 2^-52 * scale (a handful of roundings per coefficient); scale is the largest exact coefficient."""
+with a floor of 64 * 2^-52 * scale (a handful of roundings per coefficient); scale is the largest exact coefficient.
+
+solve_block, the float64 twin of csrc/solve_kernel.hip's own elimination, is held to solve_exact by the bound the device
+is held to (tests/test_gpu_solve.py): e <= 8 * max(e_ref, 2^-52 * scale) with e_ref the error of solve_dense; at
+smoothing order 0 it is solve_dense bit for bit.  The worst ratios are printed (pytest -s)."""
 import ctypes as C
 import os
 import subprocess
@@ -153,3 +157,108 @@ def test_structs_and_symbols_match_the_header(engine):
     assert hasattr(engine.search.SearchResult, "smooth") and hasattr(engine.search.MultiSearchResult, "smooth")
     for name in ("setPath", "setWaypoints", "setV", "setDts", "solve", "getDts", "getWaypoints"):
         assert hasattr(engine.TrajSolver, name)
+
+
+# ------------------------------------------------------------------------------------- the twin of the kernel, solve_block
+FACTOR = 8.0  # the project's bound: e <= 8 * max(e_ref, 2^-52 * scale), tests/test_gpu_solve.py
+
+
+def block_ratio(vals, flags, dts, so, what):
+    """e_blk / max(e_ref, 2^-52 scale) of solve_block against solve_exact, e_ref that of solve_dense; asserts <= FACTOR."""
+    exact = SM.solve_exact(vals, flags, dts, so)
+    scale = SM.scale_of(exact)
+    e_ref, e_blk = SM.max_err(SM.solve_dense(vals, flags, dts, so), exact), SM.max_err(SM.solve_block(vals, flags, dts, so), exact)
+    floor = max(e_ref, EPS * scale)
+    assert e_blk <= FACTOR * floor, "%s: e_blk %.3g, e_ref %.3g, scale %.3g: ratio %.2f" % (what, e_blk, e_ref, scale, e_blk / floor)
+    return e_blk / floor
+
+
+@pytest.mark.parametrize("so", [0, 1, 2])
+def test_block_twin_on_the_cpu_cases(so):
+    worst = 0.0
+    for name, vals, dts in CASES:
+        worst = max(worst, block_ratio(vals, SM.path_flags(vals.shape[1], so), dts, so, name))
+    print("solve_block, cpu cases, so = %d: worst ratio %.3f" % (so, worst))
+
+
+@pytest.mark.parametrize("D,so", [(D, so) for D in (2, 3) for so in (1, 2)], ids=lambda x: str(x))
+def test_block_twin_on_the_k67_sets(D, so):
+    """The K = 67, w_max = 7 sets of tests/test_gpu_solve.py (given durations)."""
+    from test_gpu_solve import problems, vals_of, w_of
+    wp, _, dts, _ = problems(D)
+    worst = 0.0
+    for k in range(wp.shape[2]):
+        W = w_of(k)
+        if W >= 2:
+            worst = max(worst, block_ratio(vals_of(wp, k, W, D), SM.path_flags(W, so), dts[:W - 1, k], so, "problem %d" % k))
+    print("solve_block, K = 67 set, D = %d, so = %d: worst ratio %.3f" % (D, so, worst))
+
+
+@pytest.mark.parametrize("D,so", [(D, so) for D in (2, 3) for so in (1, 2)], ids=lambda x: str(x))
+def test_block_twin_on_the_exact_subset_of_the_long_set(D, so):
+    """solve_model.LONG_EXACT: the problems tests/test_gpu_poly_long.py holds to solve_exact on the device (W <= 24, every
+    duration pattern).  The seed of the long set was chosen with these ratios, all below FACTOR, before any device run."""
+    wp = SM.long_problems(D)[0]
+    for mode, ks in SM.LONG_EXACT.items():
+        worst = 0.0
+        for k in ks:
+            W = SM.long_w(k)
+            worst = max(worst, block_ratio(SM.long_vals(wp, k, W, D), SM.path_flags(W, so), SM.long_durations(D, mode, k), so,
+                                           "problem %d (W = %d, %s, %s)" % (k, W, SM.long_pattern(k), mode)))
+        print("solve_block, long set, D = %d, so = %d, %s: worst ratio %.3f" % (D, so, mode, worst))
+
+
+@pytest.mark.parametrize("D", [2, 3])
+def test_block_twin_is_the_dense_model_bit_for_bit_at_order_zero(D):
+    """so = 0 at every W and every duration pattern of the long set, given and allocated durations."""
+    wp = SM.long_problems(D)[0]
+    seen = set()
+    for k in range(3 * len(SM.LONG_NWP)):  # the first three problems of every W class: random, alternating, geometric
+        W = SM.long_w(k)
+        for mode in ("given", "alloc_arr"):
+            vals, flags = SM.long_vals(wp, k, W, D), SM.path_flags(W, 0)
+            if W < 2:
+                assert SM.solve_block(vals, flags, [], 0) is None and SM.solve_dense(vals, flags, [], 0) is None
+                continue
+            dts = SM.long_durations(D, mode, k)
+            assert np.array_equal(bits(SM.solve_block(vals, flags, dts, 0)), bits(SM.solve_dense(vals, flags, dts, 0))), (k, W, mode)
+            seen.add((W, SM.long_pattern(k)))
+    assert {w for w, _ in seen} == {2, 3, 8, 9, 16, 17, 24, 32, 33} and len(seen) == 27
+
+
+def flag_cases():
+    """The inputs of tests/test_gpu_solve.py::test_waypoint_flags (K = 5, W = 5, so = 2, D = 3), built as there."""
+    D, W, Kf = 3, 5, 5
+    P, V, A = SM.USE_POS, SM.USE_VEL, SM.USE_ACC
+    flags = np.array([[7, P, P, P, 7], [7, P | V, P | V, P | V, 7], [7, P, V, P, 7], [7, P, P | V, P, P | V],
+                      [V | A, V | A, V | A, V | A, V | A]], np.uint8).T.copy()
+    rng = np.random.default_rng(9)
+    wp = np.zeros((14, W, Kf))
+    for k in range(Kf):
+        wp[:D, :, k] = SM.random_path(rng, W, D).T
+    wp[D:3 * D] = np.round(rng.uniform(-1, 1, (2 * D, W, Kf)), 2)
+    dts = np.round(rng.uniform(0.4, 1.8, (W - 1, Kf)), 3)
+    dts[:, 4] = [1.0, 2.0, 0.5, 1.0]
+    return wp, flags, dts
+
+
+@pytest.mark.parametrize("inputs", [flag_cases, SM.long_flag_problems], ids=["W5", "W17"])
+def test_block_twin_with_waypoint_flags(inputs):
+    wp, flags, dts = inputs()
+    W, D = wp.shape[1], 3
+    for k in range(4):
+        ratio = block_ratio(SM.long_vals(wp, k, W, D), flags[:, k], dts[:, k], 2, "flags problem %d" % k)
+        print("solve_block, flags problem %d (W = %d): ratio %.3f" % (k, W, ratio))
+    # no fixed position anywhere: singular in exact arithmetic, and an exact zero pivot in the twin
+    vals = SM.long_vals(wp, 4, W, D)
+    assert SM.solve_exact(vals, flags[:, 4], dts[:, 4], 2) is None and SM.solve_block(vals, flags[:, 4], dts[:, 4], 2) is None
+
+
+def test_block_twin_reports_what_the_kernel_reports():
+    name, vals, dts = CASES[2]
+    flags = SM.path_flags(vals.shape[1], 2)
+    assert SM.solve_block(vals[:, :1], flags[:1], [], 2) is None  # EMPTY
+    for bad in (0.0, -0.4, np.nan, np.inf):  # BAD_TIME
+        d = np.array(dts, dtype=np.float64)
+        d[-1] = bad
+        assert SM.solve_block(vals, flags, d, 2) is None
