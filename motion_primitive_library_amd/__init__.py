@@ -13,11 +13,12 @@ from .env import (ACC, ACCxYAW, JRK, JRKxYAW, SNP, SNPxYAW, VEL, VELxYAW, SLOT_B
                   TRAJ_WAYPOINT, SOLVE_EMPTY, SOLVE_BAD_TIME, SOLVE_SINGULAR, USE_POS, USE_VEL, USE_ACC, PolyTrajSet, SolveOut,
                   LIMITS_REFERENCE, LIMITS_ALL_ROOTS, EXCEED_VEL, EXCEED_ACC, EXCEED_JRK, PolyLimits, LoadOut, ShortcutResult, SHORTCUT_BAD_CHAIN,
                   SCALE_REFERENCE, SCALE_ROBUST, LAMBDA_BAD_POINTS, LAMBDA_NOT_POSITIVE, LAMBDA_MAX_SEGS, LambdaRows,
+                  CONFLICT_PARK, CONFLICT_GONE, CONFLICT_BAD_INPUT, Conflicts, ConflictResult,
                   TrajInfo, TrajSamples, TrajTraverse, Rays, DeviceArray, EnvMap, Lists, PackedLists,
                   Rollouts, Slots, Waypoint, lists_from_dense, pack_host_lists)
 
 from .table import NodeTable, TableFrontier
-from .search import MultiSearchResult, OpenSet, Prior, SearchResult, pick_fastest
+from .search import MultiSearchResult, OpenSet, Prior, SearchResult, pick_fastest, stagger
 from .planner import MapPlanner, MapUtil, Trajectory, TrajSolver
 
 __all__ = ["MapPlanner", "MapUtil", "Trajectory", "EnvMap", "Waypoint", "Slots", "Lists", "lists_from_dense", "PackedLists", "pack_host_lists", "DeviceArray", "workloads", "VEL", "ACC", "JRK", "SNP", "VELxYAW",
@@ -27,4 +28,5 @@ __all__ = ["MapPlanner", "MapUtil", "Trajectory", "EnvMap", "Waypoint", "Slots",
            "TrajSamples", "TrajTraverse", "NodeTable", "TableFrontier", "OpenSet", "SearchResult", "MultiSearchResult", "Prior",
            "PolyTrajSet", "SolveOut", "TrajSolver", "SOLVE_EMPTY", "SOLVE_BAD_TIME", "SOLVE_SINGULAR", "USE_POS", "USE_VEL", "USE_ACC",
            "LIMITS_REFERENCE", "LIMITS_ALL_ROOTS", "EXCEED_VEL", "EXCEED_ACC", "EXCEED_JRK", "PolyLimits", "LoadOut", "ShortcutResult", "SHORTCUT_BAD_CHAIN", "pick_fastest",
-           "SCALE_REFERENCE", "SCALE_ROBUST", "LAMBDA_BAD_POINTS", "LAMBDA_NOT_POSITIVE", "LAMBDA_MAX_SEGS", "LambdaRows"]
+           "SCALE_REFERENCE", "SCALE_ROBUST", "LAMBDA_BAD_POINTS", "LAMBDA_NOT_POSITIVE", "LAMBDA_MAX_SEGS", "LambdaRows",
+           "CONFLICT_PARK", "CONFLICT_GONE", "CONFLICT_BAD_INPUT", "Conflicts", "ConflictResult", "stagger"]

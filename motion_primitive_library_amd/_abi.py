@@ -82,6 +82,10 @@ SCALE_SYMBOLS = ["mplx_poly_set_lambda_device", "mplx_poly_set_lambda", "mplx_po
 SCALE_REFERENCE, SCALE_ROBUST = 0, 1
 LAMBDA_BAD_POINTS, LAMBDA_NOT_POSITIVE = 32, 64
 LAMBDA_MAX_SEGS, LAMBDA_NEWTON = 8, 3
+# ... and the ones include/mplx_conflict.h declares (conflicts between the trajectories of one set on a common clock)
+CONFLICT_SYMBOLS = ["mplx_poly_conflicts_device", "mplx_poly_conflicts", "mplx_traj_conflicts_device", "mplx_traj_conflicts"]
+CONFLICT_PARK, CONFLICT_GONE = 0, 1
+CONFLICT_BAD_INPUT = 128
 
 ROUTE_AUTO, ROUTE_DENSE, ROUTE_TILE, ROUTE_GRID = 0, 1, 2, 3
 
@@ -213,6 +217,16 @@ class ScaleDownOut(C.Structure):
 
 class TauOut(C.Structure):
     _fields_ = [("tau", C.c_void_p), ("lam", C.c_void_p), ("lam_dot", C.c_void_p), ("found", C.c_void_p), ("stride", C.c_int64)]
+
+
+class ConflictIn(C.Structure):
+    _fields_ = [("step", C.c_double), ("n_steps", C.c_int32), ("mode", C.c_int32), ("t0", C.c_void_p), ("radius", C.c_void_p),
+                ("radius_all", C.c_double), ("group", C.c_void_p), ("rank", C.c_void_p), ("chunk_steps", C.c_int32)]
+
+
+class ConflictOut(C.Structure):
+    _fields_ = [("first_step", C.c_void_p), ("first_partner", C.c_void_p), ("min_d2", C.c_void_p), ("status", C.c_void_p),
+                ("pair_first", C.c_void_p), ("pair_stride", C.c_int64)]
 
 
 class TableView(C.Structure):
@@ -447,6 +461,10 @@ def lib():
         "mplx_poly_tau_device": (C.c_int, [vp, C.POINTER(TrajTimes), C.POINTER(TauOut)]),
         "mplx_poly_tau": (C.c_int, [vp, C.POINTER(TrajTimes), C.POINTER(TauOut)]),
         "mplx_poly_clear_lambda": (C.c_int, [vp]),
+        "mplx_poly_conflicts_device": (C.c_int, [vp, C.POINTER(ConflictIn), C.POINTER(ConflictOut)]),
+        "mplx_poly_conflicts": (C.c_int, [vp, C.POINTER(ConflictIn), C.POINTER(ConflictOut)]),
+        "mplx_traj_conflicts_device": (C.c_int, [vp, C.POINTER(TrajSet), C.POINTER(ConflictIn), C.POINTER(ConflictOut)]),
+        "mplx_traj_conflicts": (C.c_int, [vp, C.POINTER(TrajSet), C.POINTER(ConflictIn), C.POINTER(ConflictOut)]),
         "mplx_table_create": (C.c_int, [vp, i64, i32, C.POINTER(vp)]),
         "mplx_table_destroy": (None, [vp]),
         "mplx_table_clear": (C.c_int, [vp]),
@@ -479,7 +497,7 @@ def lib():
         "mplx_open_prior_view_of": (C.c_int, [vp, C.POINTER(PriorView)]),
         "mplx_planner_prior_table": (C.c_int, [vp, vp, vp, i32, C.POINTER(i32), vp, C.POINTER(i32)]),
     }
-    for name in SYMBOLS + MAP_UTIL_SYMBOLS + ROLLOUT_SYMBOLS + RAY_SYMBOLS + TRAJ_SYMBOLS + TABLE_SYMBOLS + OPEN_SYMBOLS + MULTI_SYMBOLS + REPLAN_SYMBOLS + PRIOR_SYMBOLS + SOLVE_SYMBOLS + LIMITS_SYMBOLS + SCALE_SYMBOLS:
+    for name in SYMBOLS + MAP_UTIL_SYMBOLS + ROLLOUT_SYMBOLS + RAY_SYMBOLS + TRAJ_SYMBOLS + TABLE_SYMBOLS + OPEN_SYMBOLS + MULTI_SYMBOLS + REPLAN_SYMBOLS + PRIOR_SYMBOLS + SOLVE_SYMBOLS + LIMITS_SYMBOLS + SCALE_SYMBOLS + CONFLICT_SYMBOLS:
         fn = getattr(L, name)  # AttributeError if the library does not export it
         fn.restype, fn.argtypes = sig[name]
     _lib = L

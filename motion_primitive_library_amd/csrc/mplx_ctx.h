@@ -6,6 +6,7 @@
 #include "../../include/mplx.h"
 #include "../../include/mplx_debug.h"
 #include "../../include/mplx_open.h"  // mplx_open, mplx_table_frontier: what open_push() below takes
+#include "../../include/mplx_traj.h"  // mplx_traj_set: what the traj_* helpers below take
 #include "mplx_internal.h"
 
 #include <cstdarg>
@@ -56,6 +57,7 @@ struct mplx_ctx {
   mplx_detail::DevBuf post_ws;                   // workspace of the partitioned identity pass (identity_kernel.hip)
   mplx_detail::DevBuf ray_work;                  // candidate worklist of mplx_goal_sight_device (ray_api.cpp)
   mplx_detail::DevBuf traj_tab;                  // segment table of the trajectory calls (traj_api.cpp); grow-only
+  mplx_detail::DevBuf conflict_ws;               // scratch of mplx_traj_conflicts (conflict_api.cpp); grow-only
   mplx_detail::DevBuf prep_lut, prep_a, prep_b;  // map preprocessing scratch (map_prep_api.cpp)
   bool blk_ok = false;   // blocked-bit map matches the current map + region
   bool u_factored = false;
@@ -348,6 +350,13 @@ void table_observe(mplx_table *t);
 int table_replan_args(mplx_table *t, const char *who, bool scratch, mplx_ctx **c, mplx::ReplanArgs *a);
 // open_api.cpp: mplx_open_push_device; closed: without IS_OPEN (mplx_open_push_closed_device, replan_api.cpp)
 int open_push(mplx_open *o, const char *who, const mplx_table_frontier *d_rows, int64_t n_max, double eps, int32_t sight, bool closed);
+
+// traj_api.cpp: the checks of a trajectory set, the chain launch into the context's segment table, and the staging of a
+// host set (rows carved by traj_set_rows, copied by traj_stage_set), for conflict_api.cpp.
+int traj_check_set(mplx_ctx *c, const char *who, const mplx_traj_set *s, const void *out);
+int traj_build_table(mplx_ctx *c, const mplx_traj_set *s, mplx::TrajArgs *out);
+void traj_set_rows(const mplx_ctx *c, const mplx_traj_set *s, StageLayout *l, size_t *starts, size_t *actions);
+int traj_stage_set(mplx_ctx *c, const mplx_traj_set *s, const StageLayout &l, size_t starts, size_t actions, mplx_traj_set *d);
 
 // mplx_api.cpp: a goal as the kernels take it (mplx_set_goal's checks and hash), for the goals of an open set.
 int goal_fuse_of(mplx_ctx *c, const char *who, const mplx_goal_spec *g, mplx::PostFuse *out);

@@ -630,6 +630,35 @@ hipError_t launch_lambda_scale_down(int dim, const ScaleArgs &a, hipStream_t s);
 hipError_t launch_lambda_tau(const ScaleArgs &a, hipStream_t s);
 hipError_t launch_lambda_total(const ScaleArgs &a, hipStream_t s);
 
+// Conflicts between the trajectories of one set (conflict_kernel.hip, conflict_api.cpp; include/mplx_conflict.h).  traj:
+// the segment table (an action chain's or a poly's, with its Lambda).  Every scratch array is trajectory-minor.
+struct ConflictArgs {
+  TrajArgs traj;
+  int64_t K;                 // traj.n_traj
+  double step;
+  int32_t n_steps, gone;     // gone: MPLX_CONFLICT_GONE
+  const double *t0, *radius; // [K] or null
+  double radius_all;
+  const int32_t *group, *rank;  // [K] or null
+  // scratch: what the init launch derives per trajectory, the accumulators, the positions of one chunk of instants
+  uint8_t *m_incl, *m_status;   // [K] included; status bits
+  double *m_r, *m_t0;           // [K]
+  int32_t *m_group, *m_rank;    // [K] (k / 0 where the caller gave none)
+  unsigned long long *acc_first, *acc_min;  // [K] (step << 32 | partner); the bit pattern of min d2
+  double *pos;                  // [D][chunk][K]
+  uint8_t *act;                 // [chunk][K]
+  int32_t c0, cn, chunk;        // the chunk: instants c0 .. c0 + cn - 1; the stride `chunk` of pos / act
+  // outputs, any may be null
+  int32_t *first_step, *first_partner;
+  double *min_d2;
+  uint8_t *status;
+  int32_t *pair_first;
+  int64_t pair_stride;
+};
+hipError_t launch_conflict_init(const ConflictArgs &a, hipStream_t s);
+hipError_t launch_conflict_chunk(int dim, const ConflictArgs &a, hipStream_t s);  // positions of the chunk, then the pairs
+hipError_t launch_conflict_final(const ConflictArgs &a, hipStream_t s);
+
 // Shortcutting (include/mplx_limits.h): the pair problems of Q chains, and the dynamic programme over their costs.
 struct ShortcutArgs {
   int64_t n_query;

@@ -25,6 +25,7 @@ struct mplx_poly {
   size_t l_n = 0, l_st = 0, l_seg = 0, l_Ts = 0, l_total = 0, l_pts = 0, l_npts = 0, l_scaled = 0, l_down = 0, l_res = 0;
   bool has_lambda = false;
   int32_t lam_mode = 0;  // MPLX_SCALE_REFERENCE / MPLX_SCALE_ROBUST of the call that built it
+  mplx_detail::DevBuf conf;  // scratch of mplx_poly_conflicts (conflict_api.cpp); grown on demand
 };
 
 namespace mplx_detail {

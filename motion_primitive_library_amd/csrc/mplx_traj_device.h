@@ -1,5 +1,5 @@
-// mplx_traj_device.h -- one evaluated sample of a stored segment, shared by the kernels that read a segment table
-// (traj_kernel.hip; limits_kernel.hip fills the waypoints of a loaded set with it).
+// mplx_traj_device.h -- the segment look-up and one evaluated sample of a stored segment, shared by the kernels that read
+// a segment table (traj_kernel.hip; limits_kernel.hip fills the waypoints of a loaded set with it; conflict_kernel.hip).
 #ifndef MPLX_TRAJ_DEVICE_H
 #define MPLX_TRAJ_DEVICE_H
 
@@ -62,6 +62,33 @@ __device__ __forceinline__ void eval_segment(const double *seg, int64_t N, doubl
     o.yaw = pair::wrap_angle((0.0 + uy * t) + y0);
     o.yaw_dot = pair::wrap_angle(0.0 + uy);  // (yes: normalize_angle of the yaw rate, trajectory.h:126)
   }
+}
+
+// COMMAND: the first id with tau >= taus[id] && tau <= taus[id+1]; WAYPOINT: ... && tau < taus[id+1], else the last.
+// taus grow strictly (dt > 0), so the first match is the smallest id whose upper end admits tau.
+// POLY (a solved set: every segment has its own duration): no guess, a bisection on the stored taus for the same id.
+template <bool COMMAND, bool POLY = false>
+__device__ __forceinline__ int find_segment(const double *taus, int64_t N, int S, double tau, double dt) {
+  if (POLY) {
+    int lo = 0, hi = S - 1;
+    while (lo < hi) {
+      const int mid = (lo + hi) >> 1;
+      const double up = taus[(int64_t)(mid + 1) * N];
+      if (COMMAND ? tau <= up : tau < up) hi = mid; else lo = mid + 1;
+    }
+    return lo;
+  }
+  double q = tau / dt;
+  q = q >= 0.0 ? q : 0.0;  // (a NaN goes to 0)
+  int g = q < (double)(S - 1) ? (int)q : S - 1;
+  if (COMMAND) {
+    while (g > 0 && tau <= taus[(int64_t)g * N]) g--;
+    while (g < S - 1 && !(tau <= taus[(int64_t)(g + 1) * N])) g++;
+  } else {
+    while (g > 0 && tau < taus[(int64_t)g * N]) g--;
+    while (g < S - 1 && !(tau < taus[(int64_t)(g + 1) * N])) g++;
+  }
+  return g;
 }
 
 }  // namespace traj

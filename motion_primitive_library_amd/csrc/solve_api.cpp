@@ -168,6 +168,7 @@ void mplx_poly_destroy(mplx_poly *p) {
   release(p->mem);
   release(p->aux);
   release(p->lam);
+  release(p->conf);
   delete p;
 }
 

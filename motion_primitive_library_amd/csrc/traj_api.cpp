@@ -128,6 +128,21 @@ int stage_set(mplx_ctx *c, const mplx_traj_set *s, const StageLayout &l, const S
 
 }  // namespace
 
+namespace mplx_detail {
+
+int traj_check_set(mplx_ctx *c, const char *who, const mplx_traj_set *s, const void *out) { return check_set(c, who, s, out); }
+int traj_build_table(mplx_ctx *c, const mplx_traj_set *s, mplx::TrajArgs *out) { return build(c, s, nullptr, out); }
+void traj_set_rows(const mplx_ctx *c, const mplx_traj_set *s, StageLayout *l, size_t *starts, size_t *actions) {
+  const SetRows r = set_rows(c, s, l);
+  *starts = r.starts;
+  *actions = r.actions;
+}
+int traj_stage_set(mplx_ctx *c, const mplx_traj_set *s, const StageLayout &l, size_t starts, size_t actions, mplx_traj_set *d) {
+  return stage_set(c, s, l, SetRows{starts, actions}, d);
+}
+
+}  // namespace mplx_detail
+
 extern "C" {
 
 int mplx_traj_info_device(mplx_ctx *c, const mplx_traj_set *d_set, const mplx_traj_info_out *d_out) {

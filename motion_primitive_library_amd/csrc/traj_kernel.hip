@@ -35,6 +35,7 @@ namespace {
 
 using traj::Sample;
 using traj::eval_segment;
+using traj::find_segment;
 
 constexpr int kBlock = 256;
 
@@ -171,33 +172,6 @@ __global__ __launch_bounds__(kBlock) void traj_chain_kernel(const TrajArgs R) {
 #pragma unroll
     for (int o = 0; o < 5; o++) R.effort[(int64_t)o * R.effort_stride + k] = e[o];
   }
-}
-
-// COMMAND: the first id with tau >= taus[id] && tau <= taus[id+1]; WAYPOINT: ... && tau < taus[id+1], else the last.
-// taus grow strictly (dt > 0), so the first match is the smallest id whose upper end admits tau.
-// POLY (a solved set: every segment has its own duration): no guess, a bisection on the stored taus for the same id.
-template <bool COMMAND, bool POLY = false>
-__device__ __forceinline__ int find_segment(const double *taus, int64_t N, int S, double tau, double dt) {
-  if (POLY) {
-    int lo = 0, hi = S - 1;
-    while (lo < hi) {
-      const int mid = (lo + hi) >> 1;
-      const double up = taus[(int64_t)(mid + 1) * N];
-      if (COMMAND ? tau <= up : tau < up) hi = mid; else lo = mid + 1;
-    }
-    return lo;
-  }
-  double q = tau / dt;
-  q = q >= 0.0 ? q : 0.0;  // (a NaN goes to 0)
-  int g = q < (double)(S - 1) ? (int)q : S - 1;
-  if (COMMAND) {
-    while (g > 0 && tau <= taus[(int64_t)g * N]) g--;
-    while (g < S - 1 && !(tau <= taus[(int64_t)(g + 1) * N])) g++;
-  } else {
-    while (g > 0 && tau < taus[(int64_t)g * N]) g--;
-    while (g < S - 1 && !(tau < taus[(int64_t)(g + 1) * N])) g++;
-  }
-  return g;
 }
 
 // LAMBDA (a solved set that holds a Lambda, include/mplx_scale.h): the time is real time, tau = getTau(time) under the

@@ -43,6 +43,7 @@ SHORTCUT_BAD_CHAIN = _abi.SHORTCUT_BAD_CHAIN
 USE_POS, USE_VEL, USE_ACC = _abi.USE_POS, _abi.USE_VEL, _abi.USE_ACC
 SCALE_REFERENCE, SCALE_ROBUST = _abi.SCALE_REFERENCE, _abi.SCALE_ROBUST  # include/mplx_scale.h
 LAMBDA_BAD_POINTS, LAMBDA_NOT_POSITIVE, LAMBDA_MAX_SEGS = _abi.LAMBDA_BAD_POINTS, _abi.LAMBDA_NOT_POSITIVE, _abi.LAMBDA_MAX_SEGS
+CONFLICT_PARK, CONFLICT_GONE, CONFLICT_BAD_INPUT = _abi.CONFLICT_PARK, _abi.CONFLICT_GONE, _abi.CONFLICT_BAD_INPUT  # include/mplx_conflict.h
 
 
 class Waypoint:
@@ -516,6 +517,122 @@ class LambdaRows:
             b.free()
 
 
+class Conflicts:
+    """HBM-resident rows of mplx_conflict_out for n trajectories; want_pairs: pair_first [n][n] int32 as well."""
+
+    def __init__(self, env, n, want_pairs=False):
+        self.n = int(n)
+        n = max(self.n, 1)
+        self.first_step, self.first_partner = DeviceArray(env, n * 4), DeviceArray(env, n * 4)
+        self.min_d2, self.status = DeviceArray(env, n * 8), DeviceArray(env, n)
+        self.pair_first = DeviceArray(env, n * n * 4) if want_pairs else None
+
+    def _all(self):
+        return [b for b in (self.first_step, self.first_partner, self.min_d2, self.status, self.pair_first) if b is not None]
+
+    def fill(self, byte):
+        """Every row set to `byte` (to see afterwards what a call wrote)."""
+        for b in self._all():
+            _abi.check(b._env._ctx, _abi.lib().mplx_memset(b._env._ctx, b.ptr, int(byte), b.nbytes))
+
+    def c_struct(self):
+        s = _abi.ConflictOut()
+        s.first_step, s.first_partner, s.min_d2, s.status = self.first_step.ptr, self.first_partner.ptr, self.min_d2.ptr, self.status.ptr
+        if self.pair_first is not None:
+            s.pair_first, s.pair_stride = self.pair_first.ptr, self.n
+        return s
+
+    def download(self):
+        n = self.n
+        d = {"first_step": self.first_step.download(np.int32, (n,)), "first_partner": self.first_partner.download(np.int32, (n,)),
+             "min_d2": self.min_d2.download(np.float64, (n,)), "status": self.status.download(np.uint8, (n,))}
+        if self.pair_first is not None:
+            d["pair_first"] = self.pair_first.download(np.int32, (n, n))
+        return d
+
+    def result(self, step):
+        """The rows as a ConflictResult (synchronize() first)."""
+        d = self.download()
+        return ConflictResult(step, d["first_step"], d["first_partner"], d["min_d2"], d["status"], d.get("pair_first"))
+
+    def free(self):
+        for b in self._all():
+            b.free()
+
+
+class ConflictResult:
+    """What conflicts() returns, per trajectory over the pairs charged to it (include/mplx_conflict.h): first_step (the
+    first instant with a conflict, -1: none), first_time (first_step * step; NaN: none), partner (the smallest index it
+    conflicts with at that instant, -1), min_d2 and min_dist = sqrt(min_d2) (the closest approach to a charged partner
+    while both are active; inf: none), status (the set's bits | CONFLICT_BAD_INPUT; a trajectory with any bit is
+    excluded: -1, -1, inf), and pairs [K][K] (want_pairs; the first instant at which two trajectories conflict regardless
+    of rank, symmetric, -1: never), else None."""
+
+    def __init__(self, step, first_step, partner, min_d2, status, pairs=None):
+        self.step = float(step)
+        self.first_step, self.partner, self.min_d2, self.status, self.pairs = first_step, partner, min_d2, status, pairs
+        self.first_time = np.where(first_step >= 0, first_step.astype(np.float64) * self.step, np.nan)
+        self.min_dist = np.sqrt(min_d2)
+
+    @property
+    def charged(self):
+        """[K] bool: the trajectory has a conflict charged to it."""
+        return self.first_step >= 0
+
+    def __repr__(self):
+        return "ConflictResult(%d of %d trajectories in conflict)" % (int(self.charged.sum()), len(self.first_step))
+
+
+def _conflict_in(K, step, n_steps, t0, radius, group, rank, park, chunk_steps, device):
+    """mplx_conflict_in from host arrays ([K] or a scalar to repeat) or, device=True, from device buffers; (struct, keep)."""
+    i, keep = _abi.ConflictIn(), []
+    i.step, i.n_steps, i.chunk_steps = float(step), int(n_steps), int(chunk_steps)
+    i.mode = CONFLICT_PARK if park else CONFLICT_GONE
+    if radius is None:
+        raise ValueError("conflicts: give a radius (a scalar or [K])")
+
+    def ptr(v, dtype):
+        if device:
+            return _device_ptr(v)
+        a = np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=dtype), (K,)))
+        keep.append(a)
+        return a.ctypes.data
+
+    if t0 is not None:
+        i.t0 = ptr(t0, np.float64)
+    if np.ndim(radius) == 0 and not hasattr(radius, "ptr") and not hasattr(radius, "data_ptr"):
+        i.radius_all = float(radius)
+    else:
+        i.radius = ptr(radius, np.float64)
+    if group is not None:
+        i.group = ptr(group, np.int32)
+    if rank is not None:
+        i.rank = ptr(rank, np.int32)
+    return i, keep
+
+
+def _conflict_steps(step, t0, total, ok):
+    """The smallest n_steps whose instants i * step cover max(t0 + total) over the trajectories without a status."""
+    if not (step > 0 and np.isfinite(step)):
+        raise ValueError("conflicts: step must be > 0 and finite")
+    K = len(total)
+    t0 = np.zeros(K) if t0 is None else np.broadcast_to(np.asarray(t0, dtype=np.float64), (K,))
+    end = np.where(np.asarray(ok, dtype=bool) & np.isfinite(t0), t0 + total, 0.0)
+    last = max(float(end.max()) if K else 0.0, 0.0)
+    return min(int(np.ceil(last / step)) + 1, 2 ** 31 - 1)
+
+
+def _conflict_host_out(K, want_pairs):
+    rows = {"first_step": np.full(K, -1, np.int32), "first_partner": np.full(K, -1, np.int32), "min_d2": np.full(K, np.inf),
+            "status": np.zeros(K, np.uint8)}
+    o = _abi.ConflictOut()
+    o.first_step, o.first_partner, o.min_d2, o.status = (rows[k].ctypes.data for k in ("first_step", "first_partner", "min_d2", "status"))
+    if want_pairs:
+        rows["pair_first"] = np.full((K, K), -1, np.int32)
+        o.pair_first, o.pair_stride = rows["pair_first"].ctypes.data, K
+    return rows, o
+
+
 class PolyTrajSet:
     """K solved trajectories on the device (mplx_poly of include/mplx_solve.h): what EnvMap.solve_traj returns and what
     EnvMap.solve_traj_resident solves into.  status [K] (SOLVE_EMPTY | SOLVE_BAD_TIME | SOLVE_SINGULAR; 0 = solved);
@@ -723,6 +840,34 @@ class PolyTrajSet:
         self._need()
         o = out.c_struct()
         _abi.check(self._env._ctx, _abi.lib().mplx_poly_traverse_device(self._h, int(lanes), C.byref(o)))
+
+    # ---- conflicts between the trajectories of the set on a common clock (include/mplx_conflict.h)
+    def conflicts(self, step, n_steps=None, t0=None, radius=None, group=None, rank=None, park=True, want_pairs=False, chunk_steps=0):
+        """Which trajectories come closer than the sum of their radii, when first and with whom (mplx_poly_conflicts;
+        synchronous).  Instant i is at i * step on a clock on which trajectory k starts at t0[k] (None: 0); positions are
+        those of sample() at i * step - t0[k].  n_steps=None: the smallest count that covers max(t0 + total), from the
+        totals on the host.  radius: a scalar or [K].  group [K]: trajectories of one group never conflict (the n_v
+        candidates of one robot in the Q x n_v layout of smooth(v=[...])).  rank [K]: a conflict is charged to a only if
+        rank[b] <= rank[a] (the larger rank yields, equal ranks both do); None: to both.  park=True: a robot waits at its
+        start before t0 and at its end afterwards; False: it exists only during its own trajectory.  chunk_steps: the
+        instants per pass, 0 automatic; no result depends on it.  Returns a ConflictResult."""
+        self._need()
+        K = self.n
+        if n_steps is None:
+            inf = self.info()
+            n_steps = _conflict_steps(float(step), t0, inf["total_time"], inf["status"] == 0)
+        i, keep = _conflict_in(K, step, n_steps, t0, radius, group, rank, park, chunk_steps, False)
+        rows, o = _conflict_host_out(K, want_pairs)
+        _abi.check(self._env._ctx, _abi.lib().mplx_poly_conflicts(self._h, C.byref(i), C.byref(o)))
+        return ConflictResult(step, rows["first_step"], rows["first_partner"], rows["min_d2"], rows["status"], rows.get("pair_first"))
+
+    def conflicts_resident(self, out, step, n_steps, t0=None, radius=None, group=None, rank=None, park=True, chunk_steps=0):
+        """Asynchronous (mplx_poly_conflicts_device).  out: EnvMap.alloc_conflicts(n, want_pairs); t0 / radius / group /
+        rank: device buffers of [K] (radius may be a scalar) or None; n_steps must be given: nothing is read back."""
+        self._need()
+        i, keep = _conflict_in(self.n, step, n_steps, t0, radius, group, rank, park, chunk_steps, True)
+        o = out.c_struct()
+        _abi.check(self._env._ctx, _abi.lib().mplx_poly_conflicts_device(self._h, C.byref(i), C.byref(o)))
 
     # ---- time scaling (include/mplx_scale.h): a Lambda per problem.  robust=False is the reference with its quirks (the
     # 1e-5 clamp of its coefficients, a getTau that loses the end points); robust=True validates the points, applies
@@ -1843,6 +1988,36 @@ class EnvMap:
                                   action_stride)
         o = out.c_struct()
         _abi.check(self._ctx, _abi.lib().mplx_traj_traverse_device(self._ctx, C.byref(s), int(lanes), C.byref(o)))
+
+    # ---- conflicts between K action chains on a common clock (include/mplx_conflict.h); no map is needed
+    def alloc_conflicts(self, n, want_pairs=False):
+        return Conflicts(self, n, want_pairs)
+
+    def traj_conflicts(self, starts, actions, step, n_steps=None, t0=None, radius=None, group=None, rank=None, park=True,
+                       want_pairs=False, chunk_steps=0):
+        """PolyTrajSet.conflicts for K action chains (starts / actions as traj_sample takes them; mplx_traj_conflicts;
+        synchronous): positions are those of traj_sample at i * step - t0[k]; an EMPTY or BAD_ACTION chain is excluded.
+        Returns a ConflictResult."""
+        self._flush()
+        s, keep, K, H = self._traj_host_set(starts, actions)
+        if n_steps is None:
+            inf = self.traj_info(starts, actions)
+            n_steps = _conflict_steps(float(step), t0, inf["total_time"], inf["status"] == 0)
+        i, ikeep = _conflict_in(K, step, n_steps, t0, radius, group, rank, park, chunk_steps, False)
+        rows, o = _conflict_host_out(K, want_pairs)
+        _abi.check(self._ctx, _abi.lib().mplx_traj_conflicts(self._ctx, C.byref(s), C.byref(i), C.byref(o)))
+        return ConflictResult(step, rows["first_step"], rows["first_partner"], rows["min_d2"], rows["status"], rows.get("pair_first"))
+
+    def traj_conflicts_resident(self, starts, actions, out, horizon, step, n_steps, t0=None, radius=None, group=None, rank=None,
+                                park=True, chunk_steps=0, n_traj=None, n_starts=None, start_stride=None, action_stride=None):
+        """Asynchronous (mplx_traj_conflicts_device); starts / actions as traj_sample_resident takes them, out:
+        alloc_conflicts(n, want_pairs); t0 / radius / group / rank: device buffers of [K] (radius may be a scalar)."""
+        self._flush()
+        n = out.n if n_traj is None else n_traj
+        s = self._traj_device_set(starts, actions, horizon, n, n_starts, start_stride, action_stride)
+        i, keep = _conflict_in(int(n), step, n_steps, t0, radius, group, rank, park, chunk_steps, True)
+        o = out.c_struct()
+        _abi.check(self._ctx, _abi.lib().mplx_traj_conflicts_device(self._ctx, C.byref(s), C.byref(i), C.byref(o)))
 
     # ---- the trajectory solver (include/mplx_solve.h): TrajSolver / PolySolver::solve for K problems in one launch
     def alloc_poly(self, k_cap, w_max):

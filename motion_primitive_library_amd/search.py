@@ -316,6 +316,51 @@ def pick_fastest(poly, Q, vs, v_max=None, a_max=None, j_max=None):
     return np.where(good.any(axis=0), best, -1).astype(np.int64)
 
 
+def _path_set(env, paths):
+    """The paths [(start, actions) or None] of Q queries as one trajectory set: starts [4D+2][Q], actions [H][Q]; a query
+    without a path is an empty chain (TRAJ_EMPTY)."""
+    Q = len(paths)
+    H = max([len(p[1]) for p in paths if p is not None] + [1])
+    starts = np.zeros((env.n_fields, Q))
+    actions = np.full((H, Q), -1, np.int32)
+    for q, p in enumerate(paths):
+        if p is not None:
+            starts[:, q] = p[0]
+            actions[:len(p[1]), q] = p[1]
+    return starts, actions
+
+
+def stagger(trajs, step, radius, rank=None, delay=None, max_rounds=64, park=False, group=None, t0=None):
+    """Prioritised delaying on top of conflicts(): trajs is anything with conflicts(step, t0=, radius=, group=, rank=,
+    park=) -- a PolyTrajSet, a MultiSearchResult.  Each round makes one conflicts call with `rank` (default: the index,
+    so trajectory 0 never yields) and adds `delay` (default 4 * step) to t0 of every trajectory with a conflict charged to
+    it; it stops when none is charged, or after max_rounds rounds.  Returns (t0 [K], resolved [K] bool -- no conflict
+    was charged in the last call made --, rounds = the calls made); t0 holds the delays added after that last call too.
+
+    Its limits: it only ever delays, along paths it does not change.  Under park=True a robot that waits -- at its start
+    or at its end -- in the way of a robot of higher priority is never resolved by delaying it, and is reported
+    unresolved at max_rounds; with park=False a robot does not exist outside its own trajectory, which resolves on
+    paper what a real robot standing at its goal would not.  Equal ranks are both charged and both delayed: they move
+    in lockstep and stay in conflict.  It is a helper on top of the kernel, not a multi-agent planner."""
+    K = _n_traj(trajs) if t0 is None else np.size(t0)
+    t = np.zeros(K) if t0 is None else np.array(t0, dtype=np.float64).ravel()
+    rank = np.arange(K, dtype=np.int32) if rank is None else np.asarray(rank, dtype=np.int32)
+    add = 4.0 * float(step) if delay is None else float(delay)
+    charged, rounds = np.zeros(K, dtype=bool), 0
+    for _ in range(int(max_rounds)):
+        res = trajs.conflicts(step, t0=t, radius=radius, group=group, rank=rank, park=park)
+        rounds += 1
+        charged = res.first_step >= 0
+        if not charged.any():
+            break
+        t = np.where(charged, t + add, t)
+    return t, ~charged, rounds
+
+
+def _n_traj(trajs):
+    return int(trajs.n_queries if hasattr(trajs, "n_queries") else trajs.n)
+
+
 class SearchResult:
     """What EnvMap.search returns.  status: FOUND, EMPTY (no open node left: the goal region is not reachable within
     g_max), MAX_ROUNDS or MAX_EXPAND (stopped early; the nodes selected last are open again); cost: g of the goal node
@@ -516,6 +561,14 @@ class MultiSearchResult:
         """SearchResult.shortcut for every query in one batch of launches: a ShortcutResult of Q queries; a query without
         a path is SOLVE_EMPTY."""
         return _shortcut(self._env, [self.path(q) if self.found[q] else None for q in range(self.n_queries)], max_hop, control)
+
+    def conflicts(self, step, n_steps=None, t0=None, radius=None, group=None, rank=None, park=True, want_pairs=False, chunk_steps=0):
+        """Conflicts between the Q raw paths on a common clock (EnvMap.traj_conflicts on the chains of path(q), with the
+        parameters and controls the EnvMap holds now): a ConflictResult of Q entries; a query without a path is excluded
+        (TRAJ_EMPTY)."""
+        starts, actions = _path_set(self._env, [self.path(q) if self.found[q] else None for q in range(self.n_queries)])
+        return self._env.traj_conflicts(starts, actions, step, n_steps=n_steps, t0=t0, radius=radius, group=group, rank=rank,
+                                        park=park, want_pairs=want_pairs, chunk_steps=chunk_steps)
 
     def replan(self, roots=None, advance=None, goal_rows=None, check_edges=True, priors=None):
         """SearchResult.replan for Q queries at once: roots [Q] (node ids; -1 or None: that query's seed), or advance
