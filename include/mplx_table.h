@@ -48,7 +48,20 @@
  * A table can also hold the nodes of several queries at once, a node then being a (query, hash) pair: that form, what
  * it changes for relax, and which of the calls below it refuses are in include/mplx_multi.h.  Planning again on the
  * same table after the robot has moved or the map was edited -- which nodes are kept, with their g -- is
- * include/mplx_replan.h.                                                                                             */
+ * include/mplx_replan.h.
+ *
+ * Time keys.  Among moving obstacles (include/mplx_reserve.h) one lattice state at two times is two nodes.  The
+ * reference has the switch, Waypoint::enable_t (waypoint.h:119-122): the time is the last hash_combine.  After
+ * mplx_table_set_time_keys(tab, 1) the KEY of a list entry or a seed is combine(hash, (int)std::round(t / 0.1)), with
+ * combine the classic boost::hash_combine the lattice hash is built from, hash the entry's hash row (a seed's: the
+ * hash of its state) and t the entry's own t row (field 4D+1 of its state column).  Every rule above and in
+ * include/mplx_multi.h then reads "key" for "hash": identity, creation order, the per-query regions.  The hash column
+ * of the view holds the key, mplx_table_find / _find_multi compare keys (mplx_time_key folds on the host), and the
+ * "same lattice state as the goal" test of an open set, which compares that column with the goal's hash, no longer
+ * fires.  The switch applies to an empty table only -- after create or clear, before the first seed or relax with
+ * entries; otherwise MPLX_ERR_STATE -- and survives mplx_table_clear.  With it off a table runs the launches and
+ * produces the bytes it always did; with it on a seed and a relax make one more launch, which writes the keys of the
+ * entries within their count into the table's scratch.  mplx_table_rebase_* on such a table: MPLX_ERR_STATE.       */
 #ifndef MPLX_TABLE_H
 #define MPLX_TABLE_H
 
@@ -88,6 +101,10 @@ int mplx_table_create(mplx_ctx *ctx, int64_t node_capacity, int32_t slots_log2, 
 void mplx_table_destroy(mplx_table *tab);
 /* Empties the table and its status; asynchronous on the context's stream.                                           */
 int mplx_table_clear(mplx_table *tab);
+/* Time keys on (on != 0) or off; an empty table only (see above).                                                   */
+int mplx_table_set_time_keys(mplx_table *tab, int32_t on);
+/* combine(hash, (int)std::round(t / 0.1)) on the host: the key of (hash, t) in a table with time keys.              */
+uint64_t mplx_time_key(uint64_t hash, double t);
 int mplx_table_view_of(mplx_table *tab, mplx_table_view *view);
 /* Number of nodes and the status bits; synchronises.  Either pointer may be NULL.                                   */
 int mplx_table_stats(mplx_table *tab, int64_t *n_nodes, uint32_t *status);

@@ -49,7 +49,8 @@ TRAJ_EMPTY, TRAJ_BAD_ACTION, TRAJ_BAD = 1, 2, 4
 TRAJ_COMMAND, TRAJ_WAYPOINT = 0, 1
 # ... and the ones include/mplx_table.h declares (the persistent node table: relax, frontier, path)
 TABLE_SYMBOLS = ["mplx_table_create", "mplx_table_destroy", "mplx_table_clear", "mplx_table_view_of", "mplx_table_stats",
-                 "mplx_table_seed", "mplx_table_relax_device", "mplx_table_find_device", "mplx_table_find", "mplx_table_path"]
+                 "mplx_table_seed", "mplx_table_relax_device", "mplx_table_find_device", "mplx_table_find", "mplx_table_path",
+                 "mplx_table_set_time_keys", "mplx_time_key"]
 TABLE_NODES_FULL, TABLE_PROBE_FULL, TABLE_FRONTIER_FULL = 1, 2, 4
 # ... and the ones include/mplx_open.h declares (the open set of a table: push, select)
 OPEN_SYMBOLS = ["mplx_open_create", "mplx_open_destroy", "mplx_open_clear", "mplx_open_view_of", "mplx_open_push_device",
@@ -86,6 +87,11 @@ LAMBDA_MAX_SEGS, LAMBDA_NEWTON = 8, 3
 CONFLICT_SYMBOLS = ["mplx_poly_conflicts_device", "mplx_poly_conflicts", "mplx_traj_conflicts_device", "mplx_traj_conflicts"]
 CONFLICT_PARK, CONFLICT_GONE = 0, 1
 CONFLICT_BAD_INPUT = 128
+# ... and the ones include/mplx_reserve.h declares (a reservation table and the check of successor lists against it)
+RESERVE_SYMBOLS = ["mplx_reserve_create", "mplx_reserve_destroy", "mplx_reserve_fill_poly_device", "mplx_reserve_fill_poly",
+                   "mplx_reserve_fill_traj_device", "mplx_reserve_fill_traj", "mplx_reserve_shape", "mplx_reserve_positions",
+                   "mplx_reserve_set_queries", "mplx_reserve_check_device"]
+RESERVE_MAX_BYTES = 1 << 30
 
 ROUTE_AUTO, ROUTE_DENSE, ROUTE_TILE, ROUTE_GRID = 0, 1, 2, 3
 
@@ -496,8 +502,20 @@ def lib():
         "mplx_open_clear_priors": (C.c_int, [vp]),
         "mplx_open_prior_view_of": (C.c_int, [vp, C.POINTER(PriorView)]),
         "mplx_planner_prior_table": (C.c_int, [vp, vp, vp, i32, C.POINTER(i32), vp, C.POINTER(i32)]),
+        "mplx_reserve_create": (C.c_int, [vp, C.POINTER(vp)]),
+        "mplx_reserve_destroy": (None, [vp]),
+        "mplx_reserve_fill_poly_device": (C.c_int, [vp, vp, C.POINTER(ConflictIn)]),
+        "mplx_reserve_fill_poly": (C.c_int, [vp, vp, C.POINTER(ConflictIn)]),
+        "mplx_reserve_fill_traj_device": (C.c_int, [vp, vp, C.POINTER(TrajSet), C.POINTER(ConflictIn)]),
+        "mplx_reserve_fill_traj": (C.c_int, [vp, vp, C.POINTER(TrajSet), C.POINTER(ConflictIn)]),
+        "mplx_reserve_shape": (C.c_int, [vp, C.POINTER(i64), C.POINTER(i32), C.POINTER(dbl)]),
+        "mplx_reserve_positions": (C.c_int, [vp, vp, vp, vp, vp, vp, vp]),
+        "mplx_reserve_set_queries": (C.c_int, [vp, i32, vp, vp, vp]),
+        "mplx_reserve_check_device": (C.c_int, [vp, vp, C.POINTER(SuccLists), i64, vp, vp, i64, vp, vp]),
+        "mplx_table_set_time_keys": (C.c_int, [vp, i32]),
+        "mplx_time_key": (C.c_uint64, [C.c_uint64, dbl]),
     }
-    for name in SYMBOLS + MAP_UTIL_SYMBOLS + ROLLOUT_SYMBOLS + RAY_SYMBOLS + TRAJ_SYMBOLS + TABLE_SYMBOLS + OPEN_SYMBOLS + MULTI_SYMBOLS + REPLAN_SYMBOLS + PRIOR_SYMBOLS + SOLVE_SYMBOLS + LIMITS_SYMBOLS + SCALE_SYMBOLS + CONFLICT_SYMBOLS:
+    for name in SYMBOLS + MAP_UTIL_SYMBOLS + ROLLOUT_SYMBOLS + RAY_SYMBOLS + TRAJ_SYMBOLS + TABLE_SYMBOLS + OPEN_SYMBOLS + MULTI_SYMBOLS + REPLAN_SYMBOLS + PRIOR_SYMBOLS + SOLVE_SYMBOLS + LIMITS_SYMBOLS + SCALE_SYMBOLS + CONFLICT_SYMBOLS + RESERVE_SYMBOLS:
         fn = getattr(L, name)  # AttributeError if the library does not export it
         fn.restype, fn.argtypes = sig[name]
     _lib = L

@@ -320,6 +320,25 @@ hipError_t launch_conflict_chunk(int dim, const ConflictArgs &a, hipStream_t s) 
   return hipErrorInvalidValue;
 }
 
+hipError_t launch_conflict_positions(int dim, const ConflictArgs &a, hipStream_t s) {
+  if (a.K == 0 || a.cn == 0) return hipSuccess;
+  if (dim != 2 && dim != 3) return hipErrorInvalidValue;
+  unsigned nb, pb;
+  if (!blocks_of(a.K, &nb) || !blocks_of(a.K * a.cn, &pb)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(conflict_init_kernel, dim3(nb), dim3(kBlock), 0, s, a);
+  const int v = (a.traj.poly && a.traj.lam) ? 2 : a.traj.poly ? 1 : 0;
+  if (dim == 2) {
+    if (v == 2) hipLaunchKernelGGL((conflict_pos_kernel<2, true, true>), dim3(pb), dim3(kBlock), 0, s, a);
+    else if (v == 1) hipLaunchKernelGGL((conflict_pos_kernel<2, true, false>), dim3(pb), dim3(kBlock), 0, s, a);
+    else hipLaunchKernelGGL((conflict_pos_kernel<2, false, false>), dim3(pb), dim3(kBlock), 0, s, a);
+  } else {
+    if (v == 2) hipLaunchKernelGGL((conflict_pos_kernel<3, true, true>), dim3(pb), dim3(kBlock), 0, s, a);
+    else if (v == 1) hipLaunchKernelGGL((conflict_pos_kernel<3, true, false>), dim3(pb), dim3(kBlock), 0, s, a);
+    else hipLaunchKernelGGL((conflict_pos_kernel<3, false, false>), dim3(pb), dim3(kBlock), 0, s, a);
+  }
+  return hipGetLastError();
+}
+
 hipError_t launch_conflict_final(const ConflictArgs &a, hipStream_t s) {
   if (a.K == 0) return hipSuccess;
   unsigned nb;

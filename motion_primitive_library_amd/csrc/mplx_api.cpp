@@ -134,6 +134,7 @@ int mplx_create(int dim, int device, mplx_ctx **out) {
     if (getenv("MPLX_DONE_FLAG")) c->tune.done_flag = env_int("MPLX_DONE_FLAG");
     if (env_int("MPLX_SERVICE_IDLE_US") > 0) c->tune.service_idle_us = env_int("MPLX_SERVICE_IDLE_US");
     if (env_int("MPLX_SERVICE_MAX_NODES") > 0) c->tune.service_max_nodes = env_int("MPLX_SERVICE_MAX_NODES");
+    if (env_int("MPLX_RESERVE_LANES") > 0) c->tune.reserve_lanes = env_int("MPLX_RESERVE_LANES");
   }
   if (c->tune.done_flag) {
     e = hipHostMalloc((void **)&c->done_host, 64, hipHostMallocCoherent);

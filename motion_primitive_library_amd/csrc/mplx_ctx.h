@@ -87,6 +87,7 @@ struct mplx_ctx {
     int service = 1;           // MPLX_SERVICE=0: every small batch is its own launch (mplx_service)
     int service_idle_us = 500;    // MPLX_SERVICE_IDLE_US: the resident kernel leaves after this long without a request
     int service_max_nodes = 256;  // MPLX_SERVICE_MAX_NODES: larger batches are launches of their own
+    int reserve_lanes = 0;        // MPLX_RESERVE_LANES: lanes of a wave over a row's entries in reserve_kernel.hip, a power of two (0 = automatic)
   } tune;
   int lists_route = MPLX_ROUTE_AUTO;
   int last_route = MPLX_ROUTE_AUTO;
@@ -348,6 +349,9 @@ void table_observe(mplx_table *t);
 // of the rebase passes (scratch: allocated here on the first call, for the table's capacity; the device is bound.  Without
 // it only the check, n_queries and n_bound)
 int table_replan_args(mplx_table *t, const char *who, bool scratch, mplx_ctx **c, mplx::ReplanArgs *a);
+// ... and as the check of a reservation table (reserve_api.cpp) sees it: the same check, the per-node query column (null
+// for one query), the number of queries and the node capacity
+int table_reserve_args(mplx_table *t, const char *who, mplx_ctx **c, const int32_t **d_query, int32_t *n_queries, int64_t *cap);
 // open_api.cpp: mplx_open_push_device; closed: without IS_OPEN (mplx_open_push_closed_device, replan_api.cpp)
 int open_push(mplx_open *o, const char *who, const mplx_table_frontier *d_rows, int64_t n_max, double eps, int32_t sight, bool closed);
 

@@ -658,6 +658,43 @@ struct ConflictArgs {
 hipError_t launch_conflict_init(const ConflictArgs &a, hipStream_t s);
 hipError_t launch_conflict_chunk(int dim, const ConflictArgs &a, hipStream_t s);  // positions of the chunk, then the pairs
 hipError_t launch_conflict_final(const ConflictArgs &a, hipStream_t s);
+// the init launch and the position launch of ONE chunk (c0, cn, chunk), without the pairs: what a reservation table keeps
+hipError_t launch_conflict_positions(int dim, const ConflictArgs &a, hipStream_t s);
+
+// Reservation table and the check of successor lists against it (reserve_kernel.hip, reserve_api.cpp;
+// include/mplx_reserve.h).  The table is what launch_conflict_positions left: pos [D][n_steps][B], act [n_steps][B].
+struct ReserveArgs {
+  const double *pos;
+  const uint8_t *act;
+  const uint8_t *incl;          // [B]
+  const double *r;              // [B]
+  const int32_t *group;         // [B]
+  int64_t B;
+  int32_t n_steps;
+  double step;
+  // the queries
+  const double *q_t0, *q_r;     // [Q]
+  const int32_t *q_ignore;      // [Q]
+  int32_t Q;
+  const int32_t *node_query;    // per node of the table its query, or null: every row is query 0
+  int64_t node_cap;             // entries of node_query
+  // the lists and their parents
+  const int32_t *count, *action;
+  double *cost;
+  int64_t n_rows, S;
+  const int32_t *parent_id;
+  const double *parent_state;   // [4D+2][parent_stride]
+  int64_t parent_stride;
+  const double *U;
+  int32_t nU, udim;
+  double dt;
+  int32_t n_scan;               // ceil(dt / step) + 3: the instants a row looks through
+  int32_t sp_log2;              // 2^sp_log2 lanes of a wave over a row's entries, the 64 >> sp_log2 groups split the reservations
+  // outputs, either may be null
+  long long *hit;               // [n_rows * S]
+  unsigned long long *n_blocked;
+};
+hipError_t launch_reserve_check(int dim, int control, const ReserveArgs &a, hipStream_t s);
 
 // Shortcutting (include/mplx_limits.h): the pair problems of Q chains, and the dynamic programme over their costs.
 struct ShortcutArgs {
@@ -763,6 +800,10 @@ constexpr int kTableTile = 4096;
 hipError_t launch_table_relax(const TableArgs &a, hipStream_t s);
 hipError_t launch_table_clear(const TableArgs &a, hipStream_t s);  // slots, control block and mirror
 hipError_t launch_table_hash(int dim, int control, const double *states, int64_t n, int64_t stride, uint64_t *hash, hipStream_t s);
+// time keys (mplx_table_set_time_keys): key[e] = hash_combine(hash[e], (int)round(t[e] / 0.1)) for the entries within
+// their count (count null: all n); key may be hash (in place)
+hipError_t launch_table_time_keys(const int32_t *count, int64_t S, int64_t n, const uint64_t *hash, const double *t, uint64_t *key,
+                                  hipStream_t s);
 // query: per hash its query (outside [0, n_queries): -1), or null on a table of one query
 hipError_t launch_table_find(const TableArgs &a, const uint64_t *hash, const int32_t *query, int64_t n, int32_t *id, hipStream_t s);
 // leaf first: ids[0 .. len], actions[0 .. len); *len < 0: -1 more than cap edges, -2 bad id, -3 no seed within n_nodes steps

@@ -64,6 +64,26 @@ __device__ __forceinline__ void eval_segment(const double *seg, int64_t N, doubl
   }
 }
 
+// One segment of a chain: the primitive of (state s, control row up) per axis (primitive.h:34-50 through pair::Axis) and
+// its rows c1 .. c5 per axis, then the yaw primitive's rate and yaw, stride N -- what eval_segment reads.  The chain
+// launch (traj_kernel.hip) stores into the segment table with it; reserve_kernel.hip into registers (N = 1).
+template <int D, int K>
+__device__ __forceinline__ void chain_segment(const double *s, const double *up, double uy, double cyaw, pair::Axis<K> (&ax)[D],
+                                              double *seg, int64_t N) {
+#pragma unroll
+  for (int i = 0; i < D; i++) ax[i].init(s[i], s[D + i], s[2 * D + i], s[3 * D + i], up[i]);
+#pragma unroll
+  for (int i = 0; i < D; i++) {
+    seg[(5 * i + 0) * N] = ax[i].c1;
+    seg[(5 * i + 1) * N] = ax[i].c2;
+    seg[(5 * i + 2) * N] = ax[i].c3;
+    seg[(5 * i + 3) * N] = ax[i].c4;
+    seg[(5 * i + 4) * N] = ax[i].c5;
+  }
+  seg[(5 * D) * N] = uy;
+  seg[(5 * D + 1) * N] = cyaw;
+}
+
 // COMMAND: the first id with tau >= taus[id] && tau <= taus[id+1]; WAYPOINT: ... && tau < taus[id+1], else the last.
 // taus grow strictly (dt > 0), so the first match is the smallest id whose upper end admits tau.
 // POLY (a solved set: every segment has its own duration): no guess, a bisection on the stored taus for the same id.

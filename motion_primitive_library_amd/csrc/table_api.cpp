@@ -25,6 +25,7 @@ struct mplx_table {
   uint32_t epoch = 0;                // calls since the last clear
   int64_t bound = 0;                 // upper bound of n_nodes: the mirror's value at the last wait + what the calls queued since can add
   bool poisoned = false;             // the host has seen a status bit
+  bool time_keys = false;            // mplx_table_set_time_keys: a node's key is hash_combine(hash, (int)round(t / 0.1))
 };
 
 namespace {
@@ -77,15 +78,19 @@ int check_frontier(mplx_ctx *c, const char *who, const mplx_table_frontier *f) {
 }
 
 // The passes of one call over n_rows * S entries; `seed_hashes` more bytes of scratch in front for a seed's hashes.
-int run_passes(mplx_table *t, mplx::TableArgs *a, const mplx_table_frontier *f, size_t seed_hashes, void **seed_hash_out) {
+// With time keys one more row of n keys, which the passes then read as the entries' hashes (*keys_out).
+int run_passes(mplx_table *t, mplx::TableArgs *a, const mplx_table_frontier *f, size_t seed_hashes, void **seed_hash_out,
+               uint64_t **keys_out = nullptr) {
   mplx_ctx *c = t->c;
   const int64_t n = a->n_rows * a->S;
   a->n_tiles = (n + mplx::kTableTile - 1) / mplx::kTableTile;
   StageLayout l;  // (only the carving: the table's own scratch, not the arena)
-  const size_t o_h = l.add(seed_hashes), o_ent = l.add((size_t)n * 4), o_mark = l.add((size_t)n), o_tot = l.add((size_t)a->n_tiles * 4);
+  const size_t o_h = l.add(seed_hashes), o_ent = l.add((size_t)n * 4), o_mark = l.add((size_t)n), o_tot = l.add((size_t)a->n_tiles * 4),
+               o_key = l.add(keys_out ? (size_t)n * 8 : 0);
   if (int rc = ensure(c, t->scratch, l.total)) return rc;
   char *base = (char *)t->scratch.p;
   if (seed_hash_out) *seed_hash_out = base + o_h;
+  if (keys_out) *keys_out = (uint64_t *)(base + o_key);
   a->ent = (uint32_t *)(base + o_ent);
   a->mark = (uint8_t *)(base + o_mark);
   a->tot = (uint32_t *)(base + o_tot);
@@ -130,6 +135,7 @@ void table_observe(mplx_table *t) { observe(t); }
 int table_replan_args(mplx_table *t, const char *who, bool scratch, mplx_ctx **c, mplx::ReplanArgs *a) {
   *c = t->c;
   if (int rc = usable(t, who)) return rc;
+  if (t->time_keys) return fail(t->c, MPLX_ERR_STATE, "%s: the table has time keys (mplx_table_set_time_keys): it cannot be rebased", who);
   a->n_queries = t->Q;
   a->n_bound = t->bound;
   if (!scratch) return MPLX_OK;
@@ -159,6 +165,15 @@ int table_replan_args(mplx_table *t, const char *who, bool scratch, mplx_ctx **c
   a->n_fields = t->F;
   a->cap = t->cap;
   a->n_bound = t->bound;
+  return MPLX_OK;
+}
+
+int table_reserve_args(mplx_table *t, const char *who, mplx_ctx **c, const int32_t **d_query, int32_t *n_queries, int64_t *cap) {
+  *c = t->c;
+  if (int rc = usable(t, who)) return rc;
+  *d_query = (const int32_t *)t->query.p;
+  *n_queries = t->Q;
+  *cap = t->cap;
   return MPLX_OK;
 }
 
@@ -276,6 +291,19 @@ int mplx_table_clear(mplx_table *t) {
   return MPLX_OK;
 }
 
+int mplx_table_set_time_keys(mplx_table *t, int32_t on) {
+  if (!t) return MPLX_ERR_ARG;
+  if (t->epoch != 0 || t->bound != 0)
+    return fail(t->c, MPLX_ERR_STATE, "mplx_table_set_time_keys: the table is not empty: only after mplx_table_create or mplx_table_clear");
+  t->time_keys = on != 0;
+  return MPLX_OK;
+}
+
+uint64_t mplx_time_key(uint64_t hash, double t) {
+  const int id = (int)std::round(t / 0.1);  // waypoint.h:119-122
+  return hash ^ ((uint64_t)(int64_t)id + 0x9e3779b9ULL + (hash << 6) + (hash >> 2));
+}
+
 int mplx_table_view_of(mplx_table *t, mplx_table_view *v) {
   if (!t) return MPLX_ERR_ARG;
   if (!v) return fail(t->c, MPLX_ERR_ARG, "mplx_table_view_of: NULL view");
@@ -324,7 +352,12 @@ int mplx_table_relax_device(mplx_table *t, const mplx_succ_lists *L, int64_t n_n
   a.count = L->count; a.action = L->action; a.cost = L->cost; a.src_hash = L->hash; a.src_state = L->state; a.src_sstride = L->state_stride;
   a.n_rows = n_nodes; a.S = S; a.parent_id = d_parent_id; a.parent_g = d_parent_g; a.g_max = g_max;
   a.entry_id = d_entry_id;
-  if (int rc = run_passes(t, &a, d_next, 0, nullptr)) return rc;
+  uint64_t *keys = nullptr;
+  if (int rc = run_passes(t, &a, d_next, 0, nullptr, t->time_keys ? &keys : nullptr)) return rc;
+  if (keys) {  // the entry's own t row
+    HIP_TRY(c, mplx::launch_table_time_keys(L->count, S, n_nodes * S, L->hash, L->state + (int64_t)(t->F - 1) * L->state_stride, keys, c->stream));
+    a.src_hash = keys;
+  }
   HIP_TRY(c, mplx::launch_table_relax(a, c->stream));
   return h_count ? read_count(t, d_next, h_count) : MPLX_OK;
 }
@@ -360,6 +393,8 @@ static int seed_table(mplx_table *t, const char *who, const double *h_states, in
   if (int rc = run_passes(t, &a, d_frontier, (size_t)n * 8, &hashes)) return rc;
   a.src_hash = (const uint64_t *)hashes;
   HIP_TRY(c, mplx::launch_table_hash(c->dim, c->prm.control, a.src_state, n, n, (uint64_t *)hashes, c->stream));
+  if (t->time_keys)  // in place: every entry reads its own hash
+    HIP_TRY(c, mplx::launch_table_time_keys(nullptr, 1, n, (const uint64_t *)hashes, a.src_state + (int64_t)(t->F - 1) * n, (uint64_t *)hashes, c->stream));
   HIP_TRY(c, mplx::launch_table_relax(a, c->stream));
   int64_t count = 0;
   if (int rc = read_count(t, d_frontier, &count)) return rc;  // (the arena is free again: the stream is idle)

@@ -304,6 +304,20 @@ __global__ __launch_bounds__(kBlock) void table_hash_kernel(const double *states
   hash[k] = pair::lattice_hash<D, K, YAW>(s, s + D, s + 2 * D, s + 3 * D, s[4 * D]);
 }
 
+// Time keys (mplx_table_set_time_keys): the last hash_combine of Waypoint::enable_t (waypoint.h:119-122)
+__global__ __launch_bounds__(kBlock) void table_time_key_kernel(const int32_t *count, int64_t S, int64_t n, const uint64_t *hash,
+                                                                const double *t, uint64_t *key) {
+  const int64_t e = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (e >= n) return;
+  if (count) {
+    const int64_t k = e / S;
+    if ((int)(e - k * S) >= count[k]) return;  // nothing of an entry past count[k] is read
+  }
+  uint64_t h = hash[e];
+  pair::fold(h, pair::quantise(t[e], 0.1));
+  key[e] = h;
+}
+
 template <int D>
 hipError_t hash_dim(int control, const double *states, int64_t n, int64_t stride, uint64_t *hash, hipStream_t s) {
   const dim3 grid((unsigned)((n + kBlock - 1) / kBlock)), block(kBlock);
@@ -410,6 +424,13 @@ hipError_t launch_table_hash(int dim, int control, const double *states, int64_t
   if (dim == 2) return hash_dim<2>(control, states, n, stride, hash, s);
   if (dim == 3) return hash_dim<3>(control, states, n, stride, hash, s);
   return hipErrorInvalidValue;
+}
+
+hipError_t launch_table_time_keys(const int32_t *count, int64_t S, int64_t n, const uint64_t *hash, const double *t, uint64_t *key,
+                                  hipStream_t s) {
+  if (n <= 0) return hipSuccess;
+  hipLaunchKernelGGL(table_time_key_kernel, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, count, S, n, hash, t, key);
+  return hipGetLastError();
 }
 
 hipError_t launch_table_find(const TableArgs &a, const uint64_t *hash, const int32_t *query, int64_t n, int32_t *id, hipStream_t s) {

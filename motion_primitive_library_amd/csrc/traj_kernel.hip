@@ -103,21 +103,8 @@ __global__ __launch_bounds__(kBlock) void traj_chain_kernel(const TrajArgs R) {
     const double *up = A.U + (int64_t)a * A.udim;
     const double uy = R.yaw ? up[D] : 0.0, cyaw = R.yaw ? s[4 * D] : 0.0;  // (no yaw bit: pr_yaw_ stays all zero)
     pair::Axis<K> ax[D];
-#pragma unroll
-    for (int i = 0; i < D; i++) ax[i].init(s[i], s[D + i], s[2 * D + i], s[3 * D + i], up[i]);
-
     R.tab_tau[(int64_t)h * N + k] = tau;
-    double *seg = R.tab_seg + (int64_t)h * NC * N + k;
-#pragma unroll
-    for (int i = 0; i < D; i++) {
-      seg[(5 * i + 0) * N] = ax[i].c1;
-      seg[(5 * i + 1) * N] = ax[i].c2;
-      seg[(5 * i + 2) * N] = ax[i].c3;
-      seg[(5 * i + 3) * N] = ax[i].c4;
-      seg[(5 * i + 4) * N] = ax[i].c5;
-    }
-    seg[(5 * D) * N] = uy;
-    seg[(5 * D + 1) * N] = cyaw;
+    traj::chain_segment<D, K>(s, up, uy, cyaw, ax, R.tab_seg + (int64_t)h * NC * N + k, N);
     if (R.seg_state) {
       double *o = R.seg_state + (int64_t)h * R.seg_stride + k;
 #pragma unroll

@@ -2333,7 +2333,8 @@ class EnvMap:
 
     def search(self, start, goal_row, eps=1.0, delta=None, g_max=float("inf"), max_rounds=None, max_expand=None,
                capacity=1 << 16, max_frontier=None, lists_stride=None, sight=True, tol_pos=0.5, tol_vel=-1.0, tol_acc=-1.0,
-               tol_yaw=-1.0, w=None, v_max=None, start_g=0.0, prior=None):
+               tol_yaw=-1.0, w=None, v_max=None, start_g=0.0, prior=None, avoid=None, t0=0.0, radius=None, ignore_group=-1,
+               time_keys=None):
         """A goal-directed search from `start` (one 4D+2 state) to the goal region of `goal_row` that stays on the
         device: set_goal, seed, push; then per round one select (the round's only read-back, 48 bytes), and while it
         selects: expand the selection, relax its lists against the table, push the nodes whose g fell.  Keys are
@@ -2347,14 +2348,23 @@ class EnvMap:
         start_g: the cost-to-come the start is seeded with (what a SearchResult.replan from a node with that g is
         compared against).  result.replan(...) plans again on the same table after a move or a map edit.
         prior: a search.Prior (e.g. another result's as_prior()): the heuristic follows the prior trajectory at the
-        node's own time and the goal moves to the prior's end (include/mplx_prior.h)."""
+        node's own time and the goal moves to the prior's end (include/mplx_prior.h).
+        avoid: a search.Reservations (alloc_reservations): every round checks its lists against the reserved trajectories
+        between the expansion and the relax, and the edges that come closer to one than radius + its radius cost +inf
+        (include/mplx_reserve.h).  The robot starts at t0 on the table's clock (its clock is t0 + t, so `start` must
+        have t = 0), has `radius` and ignores the reservations of ignore_group (-1: none).  time_keys (default: on with
+        avoid, else off): a node is a (lattice state, time) pair (mplx_table_set_time_keys) -- what waiting for a moving
+        obstacle to pass needs.  Without avoid and time keys the search issues exactly the calls it always did.  A
+        result of a search with avoid or time keys cannot replan()."""
         from .search import run_search
         return run_search(self, start, goal_row, eps, delta, g_max, max_rounds, max_expand, capacity, max_frontier,
-                          lists_stride, sight, tol_pos, tol_vel, tol_acc, tol_yaw, w, v_max, start_g, prior)
+                          lists_stride, sight, tol_pos, tol_vel, tol_acc, tol_yaw, w, v_max, start_g, prior, avoid, t0, radius,
+                          ignore_group, time_keys)
 
     def search_many(self, starts, goal_rows, eps=1.0, delta=None, g_max=float("inf"), max_rounds=None, max_expand=None,
                     capacity=1 << 16, max_frontier=None, lists_stride=None, sight=True, tol_pos=0.5, tol_vel=-1.0,
-                    tol_acc=-1.0, tol_yaw=-1.0, w=None, v_max=None, start_g=0.0, priors=None):
+                    tol_acc=-1.0, tol_yaw=-1.0, w=None, v_max=None, start_g=0.0, priors=None, avoid=None, t0=0.0, radius=None,
+                    ignore_group=-1, time_keys=None):
         """Q searches of EnvMap.search at once, sharing every launch of a round (include/mplx_multi.h): starts
         [4D+2][Q], goal_rows [Q][4D+2], query q from starts[:, q] to the goal region of goal_rows[q].  One table of
         `capacity` nodes and one open set hold all of them; a round selects, expands, relaxes and pushes the union of
@@ -2362,10 +2372,21 @@ class EnvMap:
         all queries together.  As long as no selection is cut at max_frontier every query does exactly what its own
         EnvMap.search does.  Returns a MultiSearchResult (search.py) that owns the table and the open set.  start_g: one
         cost-to-come for every start, or [Q].  priors: [Q] search.Prior or None (no prior for that query), e.g. another
-        result's as_priors(): one mplx_open_set_priors_device for all of them (include/mplx_prior.h)."""
+        result's as_priors(): one mplx_open_set_priors_device for all of them (include/mplx_prior.h).
+        avoid, t0, radius, ignore_group (one value for all queries or [Q]) and time_keys: as EnvMap.search takes them;
+        every query has its own start on the clock, radius and ignored group, and one check serves them all."""
         from .search import run_search_many
         return run_search_many(self, starts, goal_rows, eps, delta, g_max, max_rounds, max_expand, capacity, max_frontier,
-                               lists_stride, sight, tol_pos, tol_vel, tol_acc, tol_yaw, w, v_max, start_g, priors)
+                               lists_stride, sight, tol_pos, tol_vel, tol_acc, tol_yaw, w, v_max, start_g, priors, avoid, t0,
+                               radius, ignore_group, time_keys)
+
+    def alloc_reservations(self, trajs, step, n_steps=None, t0=None, radius=None, group=None, park=True):
+        """A reservation table on the device (include/mplx_reserve.h; search.Reservations): the positions of the
+        trajectories `trajs` -- a PolyTrajSet, or (starts, actions) chains as traj_conflicts takes them -- at the instants
+        i * step of a common clock, with t0 / radius / group / park as conflicts() takes them.  n_steps=None covers
+        max(t0 + total), as conflicts() does.  The `avoid` of search / search_many."""
+        from .search import Reservations
+        return Reservations(self, trajs, step, n_steps, t0, radius, group, park)
 
     def synchronize(self):
         _abi.check(self._ctx, _abi.lib().mplx_synchronize(self._ctx))

@@ -361,6 +361,171 @@ def _n_traj(trajs):
     return int(trajs.n_queries if hasattr(trajs, "n_queries") else trajs.n)
 
 
+class Reservations:
+    """mplx_reserve of an EnvMap's context (include/mplx_reserve.h): the positions of B reserved trajectories at the
+    instants i * step of a common clock, kept on the device, and the check of successor lists against them.  trajs: a
+    PolyTrajSet, or (starts, actions) chains as EnvMap.traj_conflicts takes them; t0 / radius / group / park as
+    conflicts() takes them.  The `avoid` of EnvMap.search / search_many.  free() it before the EnvMap is closed."""
+
+    def __init__(self, env, trajs, step, n_steps=None, t0=None, radius=None, group=None, park=True):
+        self._env, self._res = env, None
+        self._q = None
+        r = C.c_void_p()
+        _abi.check(env._ctx, _abi.lib().mplx_reserve_create(env._ctx, C.byref(r)))
+        self._res = r
+        try:
+            self.fill(trajs, step, n_steps, t0, radius, group, park)
+        except Exception:
+            self.free()
+            raise
+
+    def _check(self, rc):
+        _abi.check(self._env._ctx, rc)
+
+    def fill(self, trajs, step, n_steps=None, t0=None, radius=None, group=None, park=True):
+        """Fills the table again (mplx_reserve_fill_poly / _fill_traj; synchronous).  n_steps=None: the smallest count
+        whose instants cover max(t0 + total), as conflicts() takes it."""
+        from .env import _conflict_in, _conflict_steps
+        env = self._env
+        env._flush()
+        if hasattr(trajs, "_h"):  # a PolyTrajSet
+            trajs._need()
+            K = trajs.n
+            if n_steps is None:
+                inf = trajs.info()
+                n_steps = _conflict_steps(float(step), t0, inf["total_time"], inf["status"] == 0)
+            i, keep = _conflict_in(K, step, n_steps, t0, radius, group, None, park, 0, False)
+            self._check(_abi.lib().mplx_reserve_fill_poly(self._res, trajs._h, C.byref(i)))
+        else:
+            starts, actions = trajs
+            s, keep2, K, H = env._traj_host_set(starts, actions)
+            if n_steps is None:
+                inf = env.traj_info(starts, actions) if K else {"total_time": np.zeros(0), "status": np.zeros(0, np.uint8)}
+                n_steps = _conflict_steps(float(step), t0, inf["total_time"], inf["status"] == 0)
+            i, keep = _conflict_in(K, step, n_steps, t0, radius, group, None, park, 0, False)
+            self._check(_abi.lib().mplx_reserve_fill_traj(self._res, env._ctx, C.byref(s), C.byref(i)))
+        self.n, self.n_steps, self.step = int(K), int(n_steps), float(step)
+
+    def set_queries(self, t0, radius, ignore_group=None):
+        """mplx_reserve_set_queries: per planning robot its start on the clock, its radius and the group whose
+        reservations it ignores (-1 / None: none); [Q] each, or scalars for one query."""
+        t0 = np.ascontiguousarray(np.atleast_1d(np.asarray(t0, dtype=np.float64)))
+        Q = t0.size
+        rad = np.ascontiguousarray(np.broadcast_to(np.asarray(radius, dtype=np.float64), (Q,)))
+        ign = None if ignore_group is None else np.ascontiguousarray(np.broadcast_to(np.asarray(ignore_group, dtype=np.int32), (Q,)))
+        self._check(_abi.lib().mplx_reserve_set_queries(self._res, Q, t0.ctypes.data, rad.ctypes.data,
+                                                        None if ign is None else ign.ctypes.data))
+        self.n_queries = Q
+
+    def check(self, frontier, lists, n, table=None, hit=None, n_blocked=None):
+        """mplx_reserve_check_device on the lists the expansion of `frontier` (its first n rows) left: the entries that
+        come too close to a reservation get cost +inf.  table: the NodeTable whose query column says whose a row is
+        (needed with more than one query).  hit: a device buffer of lists.n_slots int64, n_blocked: one of 8 bytes that
+        the call adds to; either may be None.  Asynchronous."""
+        from .env import _device_ptr
+        s = lists.c_struct()
+        self._check(_abi.lib().mplx_reserve_check_device(
+            self._res, None if table is None else table._tab, C.byref(s), int(n), _device_ptr(frontier.id), int(frontier.ptr),
+            int(frontier.n_nodes), None if hit is None else _device_ptr(hit), None if n_blocked is None else _device_ptr(n_blocked)))
+
+    def positions(self):
+        """The table (a download, for tests): {"pos" [n_steps][D][B], "active" [n_steps][B], "included" [B], "radius"
+        [B], "group" [B], "status" [B]}."""
+        B, n, D = self.n, self.n_steps, self._env.dim
+        out = {"pos": np.zeros((n, D, B)), "active": np.zeros((n, B), np.uint8), "included": np.zeros(B, np.uint8),
+               "radius": np.zeros(B), "group": np.zeros(B, np.int32), "status": np.zeros(B, np.uint8)}
+        self._check(_abi.lib().mplx_reserve_positions(self._res, *[out[k].ctypes.data for k in
+                                                                   ("pos", "active", "included", "radius", "group", "status")]))
+        return out
+
+    def free(self):
+        res = self._res
+        self._res = None
+        if res and self._env._ctx:
+            _abi.lib().mplx_reserve_destroy(res)
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+def time_key(hashes, t):
+    """mplx_time_key: the key of (lattice hash, t) in a table with time keys, element-wise."""
+    h, tt = np.broadcast_arrays(np.asarray(hashes, dtype=np.uint64), np.asarray(t, dtype=np.float64))
+    fn = _abi.lib().mplx_time_key
+    return np.array([fn(int(a), float(b)) for a, b in zip(h.ravel(), tt.ravel())], dtype=np.uint64).reshape(h.shape)
+
+
+def plan_prioritised(env, starts, goal_rows, step, radius, order=None, delays=(0.0,), park=True, **search_kw):
+    """Prioritised planning of R robots on one map: robot r plans against the trajectories of the robots planned
+    before it, as obstacles that move on the common clock of conflicts().  starts [4D+2][R] (t = 0 each), goal_rows
+    [R][4D+2], radius a scalar or [R]; step: the clock's.  Robots are planned in `order` (default: the index, so a lower
+    index has the higher priority).  Robot r is ONE search_many whose queries are its len(delays) start-delay
+    candidates -- the same start and goal, t0[q] = delays[q], time keys on -- which share every launch; the winner is
+    the found candidate with the smallest delays[q] + total time (ties: the smaller q).  Its chain joins the reservation
+    table, which is refilled from the chosen chains with their t0.  search_kw goes to search_many; `n_steps` in it sets
+    the table's horizon in instants (default: what covers max(delays) + 256 primitives); an edge past the horizon is
+    blocked.
+
+    Returns {"paths": [R] (start, actions) or None, "t0" [R], "status" [R] (of the winning candidate, else of
+    candidate 0), "cost" [R] (g of the winner, inf), "conflicts": a final conflicts() over all chosen chains at `step`
+    with rank = the position in `order`}.
+
+    Its limits: a robot that finds no path is reported and not reserved.  Waiting at rest is not an edge (the expansion
+    drops a successor equal to its parent, compared without t): `delays` is how a robot waits, at its start only.
+    Nothing is checked after a robot's own trajectory ends: under park=True a later robot is routed around the parked
+    one, but an earlier robot is not protected against a later one parking in its way, which the final conflicts
+    shows."""
+    starts = np.ascontiguousarray(starts, dtype=np.float64)
+    goal_rows = np.ascontiguousarray(goal_rows, dtype=np.float64)
+    R = starts.shape[1]
+    order = list(range(R)) if order is None else [int(r) for r in order]
+    delays = np.atleast_1d(np.asarray(delays, dtype=np.float64))
+    Q = delays.size
+    rad = np.broadcast_to(np.asarray(radius, dtype=np.float64), (R,))
+    dt = float(env._p.dt)
+    n_steps = search_kw.pop("n_steps", None)
+    if n_steps is None:
+        n_steps = int(math.ceil((float(delays.max()) + 256 * dt) / float(step))) + 1
+    paths, t0, status, cost = [None] * R, np.zeros(R), [None] * R, np.full(R, math.inf)
+    planned = []
+    res = None
+    try:
+        for r in order:
+            st, ac = _path_set(env, [paths[k] for k in planned])
+            fill = ((st, ac), step, n_steps, t0[planned], rad[planned] if planned else 0.0, None, park)
+            if res is None:
+                res = Reservations(env, *fill)
+            else:
+                res.fill(*fill)
+            out = env.search_many(np.repeat(starts[:, r:r + 1], Q, axis=1), np.repeat(goal_rows[r:r + 1], Q, axis=0), avoid=res,
+                                  t0=delays, radius=float(rad[r]), time_keys=True, **search_kw)
+            try:
+                best = None
+                for q in range(Q):
+                    if out.found[q]:
+                        p = out.path(q)
+                        end = float(delays[q]) + len(p[1]) * dt
+                        if best is None or end < best[0]:
+                            best = (end, q, p)
+                status[r] = out.status[0 if best is None else best[1]]
+                if best is not None:
+                    paths[r], t0[r], cost[r] = best[2], float(delays[best[1]]), out.cost[best[1]]
+                    planned.append(r)
+            finally:
+                out.free()
+    finally:
+        if res is not None:
+            res.free()
+    rank = np.zeros(R, np.int32)
+    rank[order] = np.arange(len(order), dtype=np.int32)
+    st, ac = _path_set(env, paths)
+    final = env.traj_conflicts(st, ac, step, t0=t0, radius=rad, rank=rank, park=park)
+    return {"paths": paths, "t0": t0, "status": status, "cost": cost, "conflicts": final}
+
+
 class SearchResult:
     """What EnvMap.search returns.  status: FOUND, EMPTY (no open node left: the goal region is not reachable within
     g_max), MAX_ROUNDS or MAX_EXPAND (stopped early; the nodes selected last are open again); cost: g of the goal node
@@ -413,6 +578,7 @@ class SearchResult:
         gives one again.  Returns a new SearchResult that owns the table and the open set; this one no longer does."""
         if self.table is None or self._params is None:
             raise RuntimeError("replan: this result does not own a table (it was replanned or freed)")
+        _no_replan(self._params)
         if root is not None and advance is not None:
             raise ValueError("replan: give root or advance, not both")
         if advance is not None:
@@ -432,6 +598,28 @@ class SearchResult:
         return "SearchResult(%s, cost=%r, rounds=%d, expanded=%d)" % (STATUS_NAMES[self.status], self.cost, self.rounds, self.expanded)
 
 
+def _no_replan(prm):
+    if prm.get("avoid") or prm.get("time_keys"):
+        raise RuntimeError("replan: the search ran among reservations or with time keys; replanning such a table is not "
+                           "built (include/mplx_replan.h)")
+
+
+def _avoid_setup(who, avoid, time_keys, starts, Q, t0, radius, ignore_group, tab, prm):
+    """The `avoid` / `time_keys` arguments of a search: checks, the queries of the reservation table, the table's keys."""
+    time_keys = (avoid is not None) if time_keys is None else bool(time_keys)
+    prm["avoid"], prm["time_keys"] = avoid is not None, time_keys
+    if avoid is not None:
+        if radius is None:
+            raise ValueError("%s: avoid needs a radius" % who)
+        if np.any(np.asarray(starts)[-1] != 0.0):
+            raise ValueError("%s: with avoid a start state must have t = 0 (the robot's clock is t0 + t)" % who)
+        avoid.set_queries(np.broadcast_to(np.asarray(t0, dtype=np.float64), (Q,)),
+                          np.broadcast_to(np.asarray(radius, dtype=np.float64), (Q,)),
+                          np.broadcast_to(np.asarray(ignore_group, dtype=np.int32), (Q,)))
+    if time_keys:
+        tab.set_time_keys(True)
+
+
 def _table_check(tab, who, where):
     status = tab.stats()[1]  # (the stream is idle: no copy, no wait)
     if status:
@@ -439,11 +627,12 @@ def _table_check(tab, who, where):
                            % (who, status, where))
 
 
-def _search_loop(env, who, multi, tab, opn, sel, imp, lists, prm, total, rounds, expanded):
+def _search_loop(env, who, multi, tab, opn, sel, imp, lists, prm, total, rounds, expanded, avoid=None):
     """The rounds of a search from its first select on: select (the round's only read-back), and while any query
     selects: expand the selection, relax its lists against the table, push the nodes whose g fell.  rounds / expanded:
-    per query (one entry for a table of one query), counted on from what they hold.  Returns (status per query, the
-    results of the last select, relax calls made)."""
+    per query (one entry for a table of one query), counted on from what they hold.  avoid: a Reservations whose check
+    runs between the expansion and the relax (the edges it blocks cost +inf, which the relax skips); None: the calls of a
+    search without one.  Returns (status per query, the results of the last select, relax calls made)."""
     eps, delta, g_max, sight = prm["eps"], prm["delta"], prm["g_max"], prm["sight"]
     max_rounds, max_expand = prm["max_rounds"], prm["max_expand"]
     limit = None
@@ -464,6 +653,8 @@ def _search_loop(env, who, multi, tab, opn, sel, imp, lists, prm, total, rounds,
             opn.push(sel, n_max=n, eps=eps, sight=sight)  # the selection is open again: same g, same keys
             break
         env.expand_lists_resident(sel, lists, n_nodes=n)
+        if avoid is not None:
+            avoid.check(sel, lists, n, table=tab)
         tab.relax(lists, sel.id, sel.g, g_max, frontier=imp, n_nodes=n, want_count=False)
         opn.push(imp, n_max=n * lists.stride, eps=eps, sight=sight)
         total += 1
@@ -486,7 +677,8 @@ def _params(env, eps, delta, g_max, max_rounds, max_expand, capacity, max_fronti
 
 
 def run_search(env, start, goal_row, eps, delta, g_max, max_rounds, max_expand, capacity, max_frontier, lists_stride, sight,
-               tol_pos, tol_vel, tol_acc, tol_yaw, w, v_max, start_g=0.0, prior=None):
+               tol_pos, tol_vel, tol_acc, tol_yaw, w, v_max, start_g=0.0, prior=None, avoid=None, t0=0.0, radius=None,
+               ignore_group=-1, time_keys=None):
     env._flush()
     prm = _params(env, eps, delta, g_max, max_rounds, max_expand, capacity, max_frontier, lists_stride, sight,
                   dict(w=w, v_max=v_max, tol_pos=tol_pos, tol_vel=tol_vel, tol_acc=tol_acc, tol_yaw=tol_yaw))
@@ -497,6 +689,9 @@ def run_search(env, start, goal_row, eps, delta, g_max, max_rounds, max_expand, 
     tab = NodeTable(env, capacity)
     opn = sel = imp = lists = None
     try:
+        if avoid is not None or time_keys:
+            _avoid_setup("search", avoid, time_keys, np.asarray(start, dtype=np.float64).reshape(-1, 1), 1, t0, radius,
+                         ignore_group, tab, prm)
         opn = OpenSet(env, tab)
         if prior is not None:
             opn.set_goals(prm["goal_row"].reshape(1, -1), **prm["goal_kw"])
@@ -508,7 +703,7 @@ def run_search(env, start, goal_row, eps, delta, g_max, max_rounds, max_expand, 
         _table_check(tab, "search", "after seeding")
         opn.push(imp, n_max=count, eps=eps, sight=sight)
         rounds, expanded = [0], [0]
-        status, res, total = _search_loop(env, "search", False, tab, opn, sel, imp, lists, prm, 0, rounds, expanded)
+        status, res, total = _search_loop(env, "search", False, tab, opn, sel, imp, lists, prm, 0, rounds, expanded, avoid)
         return SearchResult(status[0], res[0], tab, opn, total, expanded[0], env, prm)
     except Exception:
         if opn is not None:
@@ -577,6 +772,7 @@ class MultiSearchResult:
         MultiSearchResult that owns the table and the open set; this one no longer does."""
         if self.table is None or self._params is None:
             raise RuntimeError("replan: this result does not own a table (it was replanned or freed)")
+        _no_replan(self._params)
         if roots is not None and advance is not None:
             raise ValueError("replan: give roots or advance, not both")
         Q = self.n_queries
@@ -601,7 +797,8 @@ class MultiSearchResult:
 
 
 def run_search_many(env, starts, goal_rows, eps, delta, g_max, max_rounds, max_expand, capacity, max_frontier, lists_stride,
-                    sight, tol_pos, tol_vel, tol_acc, tol_yaw, w, v_max, start_g=0.0, priors=None):
+                    sight, tol_pos, tol_vel, tol_acc, tol_yaw, w, v_max, start_g=0.0, priors=None, avoid=None, t0=0.0,
+                    radius=None, ignore_group=-1, time_keys=None):
     env._flush()
     starts = np.ascontiguousarray(starts, dtype=np.float64)
     goal_rows = np.ascontiguousarray(goal_rows, dtype=np.float64)
@@ -619,6 +816,8 @@ def run_search_many(env, starts, goal_rows, eps, delta, g_max, max_rounds, max_e
     tab = NodeTable(env, capacity, n_queries=Q)
     opn = sel = imp = lists = None
     try:
+        if avoid is not None or time_keys:
+            _avoid_setup("search_many", avoid, time_keys, starts, Q, t0, radius, ignore_group, tab, prm)
         opn = OpenSet(env, tab)
         opn.set_goals(goal_rows, **prm["goal_kw"])
         if priors is not None:
@@ -629,7 +828,7 @@ def run_search_many(env, starts, goal_rows, eps, delta, g_max, max_rounds, max_e
         _table_check(tab, "search_many", "after seeding")
         opn.push(imp, n_max=count, eps=eps, sight=sight)
         rounds, expanded = [0] * Q, [0] * Q
-        status, res, total = _search_loop(env, "search_many", True, tab, opn, sel, imp, lists, prm, 0, rounds, expanded)
+        status, res, total = _search_loop(env, "search_many", True, tab, opn, sel, imp, lists, prm, 0, rounds, expanded, avoid)
         return MultiSearchResult(status, res, tab, opn, rounds, expanded, total, env, prm)
     except Exception:
         if opn is not None:

@@ -125,6 +125,10 @@ class NodeTable:
     def clear(self):
         self._check(_abi.lib().mplx_table_clear(self._tab))
 
+    def set_time_keys(self, on=True):
+        """mplx_table_set_time_keys: a node's key is combine(hash, round(t / 0.1)); an empty table only."""
+        self._check(_abi.lib().mplx_table_set_time_keys(self._tab, 1 if on else 0))
+
     def stats(self):
         """(number of nodes, status bits); synchronises."""
         n, st = C.c_int64(), C.c_uint32()
