@@ -61,11 +61,35 @@
  * be 1), n_nodes < 0, lists without count / action / cost, node_stride < 1, more than 2^31 - 2 list entries,
  * parent_stride < n_nodes; MPLX_ERR_STATE for a poly without a solve or load, chains without params / controls, a check
  * before a fill or before mplx_reserve_set_queries, and a positions call before a fill.  A fill with K == 0 leaves an
- * empty table (every later check blocks nothing but the horizon); n_nodes == 0 is a no-op. */
+ * empty table (every later check blocks nothing but the horizon); n_nodes == 0 is a no-op.
+ *
+ * Park-safe goals.  The check looks at an edge during [tp, tc] only; a robot that has arrived stays where it is, and
+ *   the goal bit of an open set (include/mplx_open.h) is a test of geometry.  mplx_reserve_park_device, called right
+ *   after mplx_open_push_device on the same frontier, takes the goal bit from the nodes that cannot stay: it walks rows
+ *   r < min(*d_rows->count, n_max, d_rows->capacity).  A row IS LOOKED AT iff its id is in [0, n_nodes) of the open
+ *   set's table and flags[id] has MPLX_OPEN_IS_GOAL; on a table with several queries also: its query in [0, Q) (else
+ *   q = 0).  For such a row, t_node = the row's t (state row 4D+1) and pos = its state rows 0 .. D-1:
+ *   Instants.  Every i in [0, n_steps) with tl_i = (double)i * step - t0[q] >= t_node.  Closed at t_node.  A node past the
+ *              horizon (or with a t that is NaN) has no instants and is not vetoed.  (The kernel finds the first instant
+ *              from a guess and a scan of at most 4 instants; the set is the one stated.)
+ *   Pair test. The check's: against every b that is included, active at i and has group[b] != ignore[q], d2 (dx = pos -
+ *              pos_b) and rr = radius[q] + radius[b]; a conflict iff d2 < rr * rr.  Strict; a NaN is no conflict.
+ *   Result.    On any conflict the node is VETOED: flags[id] &= ~MPLX_OPEN_IS_GOAL.  Nothing else of the open set
+ *              changes: the node stays open (or closed) with its key and is expanded like any other -- with wait edges
+ *              (include/mplx_wait.h) and time keys the same lattice state can be reached later.  hit[r] (optional,
+ *              [capacity of d_rows] int64) = the minimum of ((int64)i << 32 | b) over the row's conflicts, -1 for a row
+ *              without one and for a walked row that is not looked at; rows that are not walked are not written.
+ *              *n_vetoed (optional, one int64) grows by the rows vetoed.  A frontier holds every id once.
+ *   All outputs are minima and integer sums: pure functions of the inputs.  Asynchronous on the context's stream, no
+ *   host read.  Errors as the check's (NULL res / open / frontier, n_max < 0, a frontier without id / state / count or
+ *   with state_stride < capacity, an open set of another context or whose table has a number of queries other than Q:
+ *   MPLX_ERR_ARG; before a fill or mplx_reserve_set_queries, or on a table with a status bit: MPLX_ERR_STATE).
+ *   n_max == 0 and a frontier of capacity 0 are no-ops.  Protection holds to the table's horizon only. */
 #ifndef MPLX_RESERVE_H
 #define MPLX_RESERVE_H
 
 #include "mplx_conflict.h"
+#include "mplx_open.h"
 #include "mplx_solve.h"
 #include "mplx_table.h"
 
@@ -101,6 +125,10 @@ int mplx_reserve_set_queries(mplx_reserve *res, int32_t Q, const double *h_t0, c
 int mplx_reserve_check_device(mplx_reserve *res, mplx_table *tab_or_null, const mplx_succ_lists *d_lists, int64_t n_nodes,
                               const int32_t *d_parent_id, const double *d_parent_state, int64_t parent_stride,
                               int64_t *d_hit_or_null, int64_t *d_n_blocked_or_null);
+
+/* d_rows: the frontier that was just pushed into `open`; d_hit_or_null: [capacity of d_rows].                        */
+int mplx_reserve_park_device(mplx_reserve *res, mplx_open *open, const mplx_table_frontier *d_rows, int64_t n_max,
+                             int64_t *d_hit_or_null, int64_t *d_n_vetoed_or_null);
 
 #ifdef __cplusplus
 }

@@ -90,8 +90,10 @@ CONFLICT_BAD_INPUT = 128
 # ... and the ones include/mplx_reserve.h declares (a reservation table and the check of successor lists against it)
 RESERVE_SYMBOLS = ["mplx_reserve_create", "mplx_reserve_destroy", "mplx_reserve_fill_poly_device", "mplx_reserve_fill_poly",
                    "mplx_reserve_fill_traj_device", "mplx_reserve_fill_traj", "mplx_reserve_shape", "mplx_reserve_positions",
-                   "mplx_reserve_set_queries", "mplx_reserve_check_device"]
+                   "mplx_reserve_set_queries", "mplx_reserve_check_device", "mplx_reserve_park_device"]
 RESERVE_MAX_BYTES = 1 << 30
+# ... and the one include/mplx_wait.h declares (the zero control's entry appended to the lists of an expansion)
+WAIT_SYMBOLS = ["mplx_lists_add_wait_device"]
 
 ROUTE_AUTO, ROUTE_DENSE, ROUTE_TILE, ROUTE_GRID = 0, 1, 2, 3
 
@@ -512,10 +514,12 @@ def lib():
         "mplx_reserve_positions": (C.c_int, [vp, vp, vp, vp, vp, vp, vp]),
         "mplx_reserve_set_queries": (C.c_int, [vp, i32, vp, vp, vp]),
         "mplx_reserve_check_device": (C.c_int, [vp, vp, C.POINTER(SuccLists), i64, vp, vp, i64, vp, vp]),
+        "mplx_reserve_park_device": (C.c_int, [vp, vp, C.POINTER(TableFrontier), i64, vp, vp]),
+        "mplx_lists_add_wait_device": (C.c_int, [vp, C.POINTER(SuccLists), i64, vp, i64, vp, vp]),
         "mplx_table_set_time_keys": (C.c_int, [vp, i32]),
         "mplx_time_key": (C.c_uint64, [C.c_uint64, dbl]),
     }
-    for name in SYMBOLS + MAP_UTIL_SYMBOLS + ROLLOUT_SYMBOLS + RAY_SYMBOLS + TRAJ_SYMBOLS + TABLE_SYMBOLS + OPEN_SYMBOLS + MULTI_SYMBOLS + REPLAN_SYMBOLS + PRIOR_SYMBOLS + SOLVE_SYMBOLS + LIMITS_SYMBOLS + SCALE_SYMBOLS + CONFLICT_SYMBOLS + RESERVE_SYMBOLS:
+    for name in SYMBOLS + MAP_UTIL_SYMBOLS + ROLLOUT_SYMBOLS + RAY_SYMBOLS + TRAJ_SYMBOLS + TABLE_SYMBOLS + OPEN_SYMBOLS + MULTI_SYMBOLS + REPLAN_SYMBOLS + PRIOR_SYMBOLS + SOLVE_SYMBOLS + LIMITS_SYMBOLS + SCALE_SYMBOLS + CONFLICT_SYMBOLS + RESERVE_SYMBOLS + WAIT_SYMBOLS:
         fn = getattr(L, name)  # AttributeError if the library does not export it
         fn.restype, fn.argtypes = sig[name]
     _lib = L

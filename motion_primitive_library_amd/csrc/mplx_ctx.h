@@ -354,6 +354,9 @@ int table_replan_args(mplx_table *t, const char *who, bool scratch, mplx_ctx **c
 int table_reserve_args(mplx_table *t, const char *who, mplx_ctx **c, const int32_t **d_query, int32_t *n_queries, int64_t *cap);
 // open_api.cpp: mplx_open_push_device; closed: without IS_OPEN (mplx_open_push_closed_device, replan_api.cpp)
 int open_push(mplx_open *o, const char *who, const mplx_table_frontier *d_rows, int64_t n_max, double eps, int32_t sight, bool closed);
+// open_api.cpp: the open set as the park veto of a reservation table (reserve_api.cpp) sees it: its context and table
+// (set whatever it answers), MPLX_ERR_STATE for a table with a status bit, else the table fields and the flags of `a`
+int open_park_args(mplx_open *o, const char *who, mplx_ctx **c, mplx_table **tab, mplx::OpenArgs *a);
 
 // traj_api.cpp: the checks of a trajectory set, the chain launch into the context's segment table, and the staging of a
 // host set (rows carved by traj_set_rows, copied by traj_stage_set), for conflict_api.cpp.

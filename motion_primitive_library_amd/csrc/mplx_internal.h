@@ -696,6 +696,42 @@ struct ReserveArgs {
 };
 hipError_t launch_reserve_check(int dim, int control, const ReserveArgs &a, hipStream_t s);
 
+// Park-safe goals (reserve_kernel.hip; mplx_reserve_park_device of include/mplx_reserve.h): the goal-region rows of a
+// pushed frontier against the table from the row's t on.  The table and query fields of `res` are used; its lists are not.
+struct ParkArgs {
+  ReserveArgs res;
+  const int32_t *t_n_nodes;     // the open set's table: its node count (TableCtl::n_nodes, device memory)
+  uint8_t *flags;               // the open set's flags, [node capacity]
+  const int32_t *f_id;          // the frontier
+  const double *f_state;        // [4D+2][f_stride]
+  int64_t f_stride, f_cap;
+  const int64_t *f_count;
+  int64_t n_max;
+  int32_t n_scan;               // instants looked through for the first one at or after a row's t
+  long long *hit;               // [f_cap] or null
+  unsigned long long *n_vetoed; // or null
+};
+hipError_t launch_reserve_park(int dim, const ParkArgs &a, int64_t rows, hipStream_t s);
+
+// Wait edges (wait_kernel.hip, wait_api.cpp; include/mplx_wait.h): one lane per list row appends the zero control's entry.
+struct WaitArgs {
+  ExpandArgs env;               // parameters and controls as expand_args() fills them; map, nodes and slots unused
+  int32_t a0;                   // the zero row of the control table
+  int32_t *count, *action;
+  double *cost;
+  uint64_t *hash;
+  double *state;
+  int64_t state_stride;
+  int32_t *iters;
+  int64_t n_rows, S;
+  const int32_t *parent_id;     // or null
+  const double *parent_state;   // [4D+2][parent_stride]
+  int64_t parent_stride;
+  PostFuse post;                // goal of mplx_set_goal; heur / flags = the lists' rows or null
+  unsigned long long *n_added;  // or null
+};
+hipError_t launch_lists_add_wait(int dim, int control, const WaitArgs &a, hipStream_t s);
+
 // Shortcutting (include/mplx_limits.h): the pair problems of Q chains, and the dynamic programme over their costs.
 struct ShortcutArgs {
   int64_t n_query;

@@ -139,6 +139,12 @@ int mplx_open_push_device(mplx_open *o, const mplx_table_frontier *d_rows, int64
 
 }  // extern "C"
 
+int mplx_detail::open_park_args(mplx_open *o, const char *who, mplx_ctx **c, mplx_table **tab, mplx::OpenArgs *a) {
+  *c = o->c;
+  *tab = o->tab;
+  return open_args(o, who, a);
+}
+
 int mplx_detail::open_push(mplx_open *o, const char *who, const mplx_table_frontier *d_rows, int64_t n_max, double eps, int32_t sight,
                            bool closed) {
   mplx_ctx *c = o->c;

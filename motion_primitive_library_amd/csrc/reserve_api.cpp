@@ -312,4 +312,44 @@ int mplx_reserve_check_device(mplx_reserve *r, mplx_table *tab, const mplx_succ_
   return MPLX_OK;
 }
 
+int mplx_reserve_park_device(mplx_reserve *r, mplx_open *o, const mplx_table_frontier *f, int64_t n_max, int64_t *d_hit,
+                             int64_t *d_n_vetoed) {
+  if (!r) return MPLX_ERR_ARG;
+  mplx_ctx *c = r->c;
+  const char *who = "mplx_reserve_park_device";
+  if (!o || n_max < 0) return fail(c, MPLX_ERR_ARG, "%s: NULL open set or n_max < 0", who);
+  if (!f || !f->id || !f->state || !f->count || f->capacity < 0 || f->state_stride < f->capacity)
+    return fail(c, MPLX_ERR_ARG, "%s: the frontier needs id, state and count, and state_stride >= capacity >= 0", who);
+  mplx_ctx *oc = nullptr;
+  mplx_table *tab = nullptr;
+  mplx::OpenArgs oa{};
+  const int orc = open_park_args(o, who, &oc, &tab, &oa);  // (sets oc whatever it answers)
+  if (oc != c) return fail(c, MPLX_ERR_ARG, "%s: the open set belongs to another context", who);
+  if (orc) return orc;
+  if (!r->filled) return fail(c, MPLX_ERR_STATE, "%s: the table has not been filled", who);
+  if (r->Q < 1) return fail(c, MPLX_ERR_STATE, "%s: mplx_reserve_set_queries has not been called", who);
+  if (oa.n_queries != r->Q) return fail(c, MPLX_ERR_ARG, "%s: %d queries were set, the table has %d", who, (int)r->Q, (int)oa.n_queries);
+  const int64_t rows = std::min(n_max, f->capacity);
+  if (rows == 0) return MPLX_OK;
+  if (int rc = bind_device(c)) return rc;
+  const char *b = (const char *)r->mem.p, *qb = (const char *)r->queries.p;
+  mplx::ParkArgs a{};
+  a.res.pos = (const double *)(b + r->o_pos); a.res.act = (const uint8_t *)(b + r->o_act); a.res.incl = (const uint8_t *)(b + r->o_incl);
+  a.res.r = (const double *)(b + r->o_r); a.res.group = (const int32_t *)(b + r->o_g);
+  a.res.B = r->B; a.res.n_steps = r->n_steps; a.res.step = r->step;
+  a.res.q_t0 = (const double *)(qb + r->q_t0); a.res.q_r = (const double *)(qb + r->q_r); a.res.q_ignore = (const int32_t *)(qb + r->q_ign);
+  a.res.Q = r->Q;
+  a.res.node_query = oa.n_queries > 1 ? oa.t_query : nullptr;
+  a.res.node_cap = oa.cap;
+  a.t_n_nodes = &oa.t_ctl->n_nodes;
+  a.flags = oa.flags;
+  a.f_id = f->id; a.f_state = f->state; a.f_stride = f->state_stride; a.f_cap = f->capacity; a.f_count = f->count;
+  a.n_max = n_max;
+  a.n_scan = 4;  // the guess is floor(x) - 1 with x within a few ulps of the first instant's index
+  a.hit = (long long *)d_hit;
+  a.n_vetoed = (unsigned long long *)d_n_vetoed;
+  HIP_TRY(c, mplx::launch_reserve_park(c->dim, a, rows, c->stream));
+  return MPLX_OK;
+}
+
 }  // extern "C"

@@ -19,6 +19,8 @@
 // Every output is a minimum or a sum of integers, hence a pure function of the inputs.  No workgroup waits for another;
 // every loop is bounded by S, n_scan, n_steps or B; the barriers are inside loops whose trip counts are wave-uniform
 // and the workgroup is one wave.  LDS: kTile * (D + 1) * 8 bytes = 8 KB at D = 3.
+//
+// reserve_park_kernel<D> (mplx_reserve_park_device, park-safe goals) is described where it stands, below the check.
 #include "mplx_internal.h"
 #include "mplx_pair_device.h"
 #include "mplx_traj_device.h"
@@ -162,7 +164,145 @@ hipError_t check_dim(int order, const ReserveArgs &a, hipStream_t s) {
   return hipGetLastError();
 }
 
+// reserve_park_kernel<D>: the goal-region rows of a pushed frontier against the table from the row's t on
+// (mplx_reserve_park_device).  Goal rows are few among the rows of a frontier, so a wave takes 64 rows: each lane reads
+// its row's id and the node's flag, a ballot gathers the rows to look at and the wave walks them together, one after
+// the other.  For one row the lanes stride over the reservations (coalesced reads of pos[d][i][.] and active[i][.]),
+// kParkInst instants per pass so that the reads of a pass are in flight together; a lane keeps the smallest
+// (i << 32 | b) it meets, a wave minimum makes the pass's smallest, and since instants ascend the first pass with a hit
+// ends the row.  What a lane needs of its first kParkKeep reservations (radius sum,
+// or NaN where the reservation is excluded or of the ignored group) is computed once per row and kept in registers.
+// The first instant at or after the row's t is found from a guess, (t + t0) / step, and a scan of at most n_scan
+// instants (tl_i is monotone in i).  Loops are bounded by 64, n_scan, n_steps and B; no workgroup waits for another;
+// the node's flag is cleared by the one lane that owns the row.
+constexpr int kParkKeep = 4;
+constexpr int kParkInst = 8;  // instants per pass
+constexpr unsigned kIsGoalBit = 2;  // MPLX_OPEN_IS_GOAL
+
+template <int D>
+__global__ __launch_bounds__(kWave) void reserve_park_kernel(const ParkArgs P) {
+  const ReserveArgs &A = P.res;
+  const int lane = threadIdx.x;
+  const int64_t r = (int64_t)blockIdx.x * kWave + lane;
+  int64_t n = *P.f_count;
+  n = n < P.n_max ? n : P.n_max;
+  n = n < P.f_cap ? n : P.f_cap;
+  int64_t n_nodes = *P.t_n_nodes;
+  n_nodes = n_nodes < 0 ? 0 : (n_nodes < A.node_cap ? n_nodes : A.node_cap);
+  constexpr int F = 4 * D + 2;
+
+  // ---- this lane's row
+  const bool walked = r < n;
+  int32_t id = -1, q = 0;
+  bool look = false;
+  if (walked) {
+    id = P.f_id[r];
+    if (id >= 0 && (int64_t)id < n_nodes) {
+      look = (P.flags[id] & kIsGoalBit) != 0;
+      if (look && A.node_query) q = A.node_query[id];
+      if (q < 0 || q >= A.Q) {
+        look = false;
+        q = 0;
+      }
+    }
+  }
+  long long my_hit = -1;
+  unsigned long long todo = __ballot(look);
+  while (todo) {
+    const int owner = __ffsll((long long)todo) - 1;
+    todo &= todo - 1;
+    // ---- the row (wave-uniform: every lane reads the owner's row)
+    const int64_t ro = (int64_t)blockIdx.x * kWave + owner;
+    const int32_t qo = __shfl(q, owner);
+    const double t0 = A.q_t0[qo], rq = A.q_r[qo];
+    const int32_t ign = A.q_ignore[qo];
+    double p[D];
+#pragma unroll
+    for (int d = 0; d < D; d++) p[d] = P.f_state[(int64_t)d * P.f_stride + ro];
+    const double tn = P.f_state[(int64_t)(F - 1) * P.f_stride + ro];
+    // the first instant with tl_i >= tn; n_steps: none (a NaN or a t past the horizon)
+    int i_first = A.n_steps;
+    {
+      const double x = (tn + t0) / A.step;
+      int64_t g = 0;  // (a NaN goes to 0)
+      if (x >= 1.0) g = x < 2147483647.0 ? (int64_t)x - 1 : (int64_t)A.n_steps;
+      for (int s = 0; s < P.n_scan; s++) {
+        const int64_t i = g + s;
+        if (i >= A.n_steps) break;
+        if ((double)i * A.step - t0 >= tn) {
+          i_first = (int)i;
+          break;
+        }
+      }
+    }
+    double rrk[kParkKeep];
+#pragma unroll
+    for (int j = 0; j < kParkKeep; j++) {
+      const int64_t b = (int64_t)j * kWave + lane;
+      rrk[j] = NAN;
+      if (b < A.B && A.incl[b] != 0 && A.group[b] != ign) rrk[j] = rq + A.r[b];
+    }
+    long long key = kNoHit;
+    for (int i = i_first; i < A.n_steps && key == kNoHit; i += kParkInst) {
+      long long mine = kNoHit;
+      int j = 0;
+      for (int64_t b = lane; b < A.B; b += kWave, j++) {
+        double rr;
+        if (j < kParkKeep) {
+          rr = j == 0 ? rrk[0] : j == 1 ? rrk[1] : j == 2 ? rrk[2] : rrk[3];
+        } else {
+          rr = (A.incl[b] != 0 && A.group[b] != ign) ? rq + A.r[b] : NAN;
+        }
+        const double rr2 = rr * rr;
+        // kParkInst instants at once, without a branch that depends on a load: their reads are in flight together
+#pragma unroll
+        for (int u = 0; u < kParkInst; u++) {
+          const int iu = i + u;
+          if (iu < A.n_steps) {  // (wave-uniform)
+            const int64_t at = (int64_t)iu * A.B + b;
+            const bool on = A.act[at] != 0;
+            const double dx = p[0] - A.pos[at], dy = p[1] - A.pos[(int64_t)A.n_steps * A.B + at];
+            double d2 = (dx * dx) + dy * dy;
+            if (D == 3) {
+              const double dz = p[D - 1] - A.pos[(int64_t)(D - 1) * A.n_steps * A.B + at];
+              d2 = d2 + dz * dz;
+            }
+            const long long cand = ((long long)iu << 32) | (long long)b;
+            if (on && d2 < rr2 && cand < mine) mine = cand;  // (a NaN on either side compares false)
+          }
+        }
+      }
+      // instants and reservations both ascend in the key: the minimum over the block is the row's smallest
+      if (__ballot(mine != kNoHit) != 0ull) {
+        for (int m = 1; m < kWave; m <<= 1) {
+          const long long o = __shfl_xor(mine, m);
+          mine = o < mine ? o : mine;
+        }
+        key = mine;
+      }
+    }
+    if (lane == owner && key != kNoHit) {
+      my_hit = key;
+      P.flags[id] = (uint8_t)(P.flags[id] & ~kIsGoalBit);
+    }
+  }
+  if (walked && P.hit) P.hit[r] = my_hit;
+  const unsigned long long vetoed = __ballot(my_hit != -1);
+  if (P.n_vetoed && lane == 0 && vetoed) atomicAdd(P.n_vetoed, (unsigned long long)__popcll(vetoed));
+}
+
 }  // namespace
+
+hipError_t launch_reserve_park(int dim, const ParkArgs &a, int64_t rows, hipStream_t s) {
+  if (rows <= 0) return hipSuccess;
+  const int64_t blocks = (rows + kWave - 1) / kWave;
+  if (blocks > 0x7fffffffLL || a.n_scan < 1) return hipErrorInvalidValue;
+  const dim3 grid((unsigned)blocks), block(kWave);
+  if (dim == 2) hipLaunchKernelGGL((reserve_park_kernel<2>), grid, block, 0, s, a);
+  else if (dim == 3) hipLaunchKernelGGL((reserve_park_kernel<3>), grid, block, 0, s, a);
+  else return hipErrorInvalidValue;
+  return hipGetLastError();
+}
 
 hipError_t launch_reserve_check(int dim, int control, const ReserveArgs &a, hipStream_t s) {
   if (a.n_rows <= 0) return hipSuccess;

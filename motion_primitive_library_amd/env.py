@@ -2334,7 +2334,7 @@ class EnvMap:
     def search(self, start, goal_row, eps=1.0, delta=None, g_max=float("inf"), max_rounds=None, max_expand=None,
                capacity=1 << 16, max_frontier=None, lists_stride=None, sight=True, tol_pos=0.5, tol_vel=-1.0, tol_acc=-1.0,
                tol_yaw=-1.0, w=None, v_max=None, start_g=0.0, prior=None, avoid=None, t0=0.0, radius=None, ignore_group=-1,
-               time_keys=None):
+               time_keys=None, wait=False, park_goal=False):
         """A goal-directed search from `start` (one 4D+2 state) to the goal region of `goal_row` that stays on the
         device: set_goal, seed, push; then per round one select (the round's only read-back, 48 bytes), and while it
         selects: expand the selection, relax its lists against the table, push the nodes whose g fell.  Keys are
@@ -2355,16 +2355,21 @@ class EnvMap:
         have t = 0), has `radius` and ignores the reservations of ignore_group (-1: none).  time_keys (default: on with
         avoid, else off): a node is a (lattice state, time) pair (mplx_table_set_time_keys) -- what waiting for a moving
         obstacle to pass needs.  Without avoid and time keys the search issues exactly the calls it always did.  A
-        result of a search with avoid or time keys cannot replan()."""
+        result of a search with avoid or time keys cannot replan().
+        wait=True (needs time keys, else ValueError): every round appends the wait edge -- the all-zero control from a
+        state it leaves where it is, which the expansion drops -- to its lists before the check (include/mplx_wait.h).
+        park_goal=True (needs avoid, else ValueError): after every push a goal-region node at which the robot could not
+        stay to the table's horizon loses its goal bit (mplx_reserve_park_device, include/mplx_reserve.h) and is
+        expanded like any other.  With both off the search issues exactly the calls it issued before they existed."""
         from .search import run_search
         return run_search(self, start, goal_row, eps, delta, g_max, max_rounds, max_expand, capacity, max_frontier,
                           lists_stride, sight, tol_pos, tol_vel, tol_acc, tol_yaw, w, v_max, start_g, prior, avoid, t0, radius,
-                          ignore_group, time_keys)
+                          ignore_group, time_keys, wait, park_goal)
 
     def search_many(self, starts, goal_rows, eps=1.0, delta=None, g_max=float("inf"), max_rounds=None, max_expand=None,
                     capacity=1 << 16, max_frontier=None, lists_stride=None, sight=True, tol_pos=0.5, tol_vel=-1.0,
                     tol_acc=-1.0, tol_yaw=-1.0, w=None, v_max=None, start_g=0.0, priors=None, avoid=None, t0=0.0, radius=None,
-                    ignore_group=-1, time_keys=None):
+                    ignore_group=-1, time_keys=None, wait=False, park_goal=False):
         """Q searches of EnvMap.search at once, sharing every launch of a round (include/mplx_multi.h): starts
         [4D+2][Q], goal_rows [Q][4D+2], query q from starts[:, q] to the goal region of goal_rows[q].  One table of
         `capacity` nodes and one open set hold all of them; a round selects, expands, relaxes and pushes the union of
@@ -2373,12 +2378,12 @@ class EnvMap:
         EnvMap.search does.  Returns a MultiSearchResult (search.py) that owns the table and the open set.  start_g: one
         cost-to-come for every start, or [Q].  priors: [Q] search.Prior or None (no prior for that query), e.g. another
         result's as_priors(): one mplx_open_set_priors_device for all of them (include/mplx_prior.h).
-        avoid, t0, radius, ignore_group (one value for all queries or [Q]) and time_keys: as EnvMap.search takes them;
+        avoid, t0, radius, ignore_group (one value for all queries or [Q]), time_keys, wait and park_goal: as EnvMap.search takes them;
         every query has its own start on the clock, radius and ignored group, and one check serves them all."""
         from .search import run_search_many
         return run_search_many(self, starts, goal_rows, eps, delta, g_max, max_rounds, max_expand, capacity, max_frontier,
                                lists_stride, sight, tol_pos, tol_vel, tol_acc, tol_yaw, w, v_max, start_g, priors, avoid, t0,
-                               radius, ignore_group, time_keys)
+                               radius, ignore_group, time_keys, wait, park_goal)
 
     def alloc_reservations(self, trajs, step, n_steps=None, t0=None, radius=None, group=None, park=True):
         """A reservation table on the device (include/mplx_reserve.h; search.Reservations): the positions of the

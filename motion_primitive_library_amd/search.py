@@ -428,6 +428,29 @@ class Reservations:
             self._res, None if table is None else table._tab, C.byref(s), int(n), _device_ptr(frontier.id), int(frontier.ptr),
             int(frontier.n_nodes), None if hit is None else _device_ptr(hit), None if n_blocked is None else _device_ptr(n_blocked)))
 
+    def add_waits(self, frontier, lists, n, n_added=None):
+        """mplx_lists_add_wait_device (include/mplx_wait.h) on the lists the expansion of `frontier` (its first n rows)
+        left, before check(): every row whose parent stands still under the all-zero control gets that control's entry,
+        the last of its list -- "wait for one primitive", which the expansion drops.  n_added: a device buffer of 8
+        bytes that the call adds to, or None.  The call reads nothing of the reservation table; it lives here because a
+        wait is only worth an edge among reservations.  A `zero_rows` mask of `lists` stays valid.  Asynchronous."""
+        from .env import _device_ptr
+        s = lists.c_struct()
+        self._check(_abi.lib().mplx_lists_add_wait_device(
+            self._env._ctx, C.byref(s), int(n), int(frontier.ptr), int(frontier.n_nodes), _device_ptr(frontier.id),
+            None if n_added is None else _device_ptr(n_added)))
+
+    def park(self, open_set, frontier, n_max, hit=None, n_vetoed=None):
+        """mplx_reserve_park_device right after open_set.push(frontier, n_max): a goal-region node at which the robot
+        could not stay -- a reservation comes too close at some instant from the node's t on -- loses IS_GOAL and stays
+        an ordinary open node.  hit: a device buffer of frontier.capacity int64, n_vetoed: one of 8 bytes that the call
+        adds to; either may be None.  Asynchronous."""
+        from .env import _device_ptr
+        f = frontier.c_struct()
+        self._check(_abi.lib().mplx_reserve_park_device(
+            self._res, open_set._open, C.byref(f), int(n_max), None if hit is None else _device_ptr(hit),
+            None if n_vetoed is None else _device_ptr(n_vetoed)))
+
     def positions(self):
         """The table (a download, for tests): {"pos" [n_steps][D][B], "active" [n_steps][B], "included" [B], "radius"
         [B], "group" [B], "status" [B]}."""
@@ -458,7 +481,8 @@ def time_key(hashes, t):
     return np.array([fn(int(a), float(b)) for a, b in zip(h.ravel(), tt.ravel())], dtype=np.uint64).reshape(h.shape)
 
 
-def plan_prioritised(env, starts, goal_rows, step, radius, order=None, delays=(0.0,), park=True, **search_kw):
+def plan_prioritised(env, starts, goal_rows, step, radius, order=None, delays=(0.0,), park=True, wait=False, park_goal=False,
+                     **search_kw):
     """Prioritised planning of R robots on one map: robot r plans against the trajectories of the robots planned
     before it, as obstacles that move on the common clock of conflicts().  starts [4D+2][R] (t = 0 each), goal_rows
     [R][4D+2], radius a scalar or [R]; step: the clock's.  Robots are planned in `order` (default: the index, so a lower
@@ -473,11 +497,19 @@ def plan_prioritised(env, starts, goal_rows, step, radius, order=None, delays=(0
     candidate 0), "cost" [R] (g of the winner, inf), "conflicts": a final conflicts() over all chosen chains at `step`
     with rank = the position in `order`}.
 
-    Its limits: a robot that finds no path is reported and not reserved.  Waiting at rest is not an edge (the expansion
-    drops a successor equal to its parent, compared without t): `delays` is how a robot waits, at its start only.
-    Nothing is checked after a robot's own trajectory ends: under park=True a later robot is routed around the parked
-    one, but an earlier robot is not protected against a later one parking in its way, which the final conflicts
-    shows."""
+    wait / park_goal go to search_many (EnvMap.search states them).  wait=True: standing still for one primitive is an
+    edge (include/mplx_wait.h), so a robot can leave a lane, let another pass and go on, or stop short of a crossing;
+    without it `delays` is the only way to wait, at the start only.  park_goal=True: a goal-region node counts as the
+    goal only if the robot can stay there to the table's horizon without coming too close to a reservation
+    (mplx_reserve_park_device); without it nothing is checked after a robot's own trajectory ends, and a later robot may
+    park in the way of an earlier one, which only the final conflicts shows.  The two belong together: a robot whose
+    early arrival is vetoed arrives later at the same lattice state through wait edges.
+
+    Its limits: a robot that finds no path is reported and not reserved.  Protection holds to the table's horizon
+    (`n_steps`) only.  An earlier robot is never re-planned when a later one cannot avoid it.  A chain with waits is not
+    what rollout() / MapPlanner.checkTraj accept (they stop at a wait with SKIP_SAME), and smooth() / shortcut() of a
+    path with repeated chain states are not covered; traj_info / traj_sample / traj_traverse / conflicts take it as it
+    is."""
     starts = np.ascontiguousarray(starts, dtype=np.float64)
     goal_rows = np.ascontiguousarray(goal_rows, dtype=np.float64)
     R = starts.shape[1]
@@ -501,7 +533,7 @@ def plan_prioritised(env, starts, goal_rows, step, radius, order=None, delays=(0
             else:
                 res.fill(*fill)
             out = env.search_many(np.repeat(starts[:, r:r + 1], Q, axis=1), np.repeat(goal_rows[r:r + 1], Q, axis=0), avoid=res,
-                                  t0=delays, radius=float(rad[r]), time_keys=True, **search_kw)
+                                  t0=delays, radius=float(rad[r]), time_keys=True, wait=wait, park_goal=park_goal, **search_kw)
             try:
                 best = None
                 for q in range(Q):
@@ -604,10 +636,16 @@ def _no_replan(prm):
                            "built (include/mplx_replan.h)")
 
 
-def _avoid_setup(who, avoid, time_keys, starts, Q, t0, radius, ignore_group, tab, prm):
-    """The `avoid` / `time_keys` arguments of a search: checks, the queries of the reservation table, the table's keys."""
+def _avoid_setup(who, avoid, time_keys, starts, Q, t0, radius, ignore_group, tab, prm, wait=False, park_goal=False):
+    """The `avoid` / `time_keys` / `wait` / `park_goal` arguments of a search: checks, the queries of the reservation
+    table, the table's keys."""
     time_keys = (avoid is not None) if time_keys is None else bool(time_keys)
+    if wait and not time_keys:
+        raise ValueError("%s: wait needs time keys (the key of a wait would be its parent's)" % who)
+    if park_goal and avoid is None:
+        raise ValueError("%s: park_goal needs avoid (the reservation table a goal node is held against)" % who)
     prm["avoid"], prm["time_keys"] = avoid is not None, time_keys
+    prm["wait"], prm["park_goal"] = bool(wait), bool(park_goal)
     if avoid is not None:
         if radius is None:
             raise ValueError("%s: avoid needs a radius" % who)
@@ -632,8 +670,12 @@ def _search_loop(env, who, multi, tab, opn, sel, imp, lists, prm, total, rounds,
     selects: expand the selection, relax its lists against the table, push the nodes whose g fell.  rounds / expanded:
     per query (one entry for a table of one query), counted on from what they hold.  avoid: a Reservations whose check
     runs between the expansion and the relax (the edges it blocks cost +inf, which the relax skips); None: the calls of a
-    search without one.  Returns (status per query, the results of the last select, relax calls made)."""
+    search without one.  prm["wait"]: wait edges join the lists before the check (include/mplx_wait.h); prm["park_goal"]:
+    every push is followed by the park veto of `avoid` (mplx_reserve_park_device).  With both off the loop issues exactly
+    the calls it issued before they existed.  Returns (status per query, the results of the last select, relax calls
+    made)."""
     eps, delta, g_max, sight = prm["eps"], prm["delta"], prm["g_max"], prm["sight"]
+    wait, park = bool(prm.get("wait")), bool(prm.get("park_goal")) and avoid is not None
     max_rounds, max_expand = prm["max_rounds"], prm["max_expand"]
     limit = None
     while True:
@@ -651,12 +693,18 @@ def _search_loop(env, who, multi, tab, opn, sel, imp, lists, prm, total, rounds,
             MAX_EXPAND if (max_expand is not None and sum(expanded) + n > max_expand) else None
         if limit is not None:
             opn.push(sel, n_max=n, eps=eps, sight=sight)  # the selection is open again: same g, same keys
+            if park:
+                avoid.park(opn, sel, n)
             break
         env.expand_lists_resident(sel, lists, n_nodes=n)
+        if wait:
+            _add_waits(env, avoid, sel, lists, n)
         if avoid is not None:
             avoid.check(sel, lists, n, table=tab)
         tab.relax(lists, sel.id, sel.g, g_max, frontier=imp, n_nodes=n, want_count=False)
         opn.push(imp, n_max=n * lists.stride, eps=eps, sight=sight)
+        if park:
+            avoid.park(opn, imp, n * lists.stride)
         total += 1
         for q, r in enumerate(res):
             if r["status"] == SELECTED:
@@ -664,6 +712,18 @@ def _search_loop(env, who, multi, tab, opn, sel, imp, lists, prm, total, rounds,
                 expanded[q] += r["count"]
     status = [limit if (r["status"] == SELECTED and limit is not None) else r["status"] for r in res]
     return status, res, total
+
+
+def _add_waits(env, avoid, sel, lists, n):
+    """The wait edges of a round: Reservations.add_waits, or the same call without a reservation table (a search with
+    time keys and wait but no avoid)."""
+    if avoid is not None:
+        avoid.add_waits(sel, lists, n)
+        return
+    from .env import _device_ptr
+    s = lists.c_struct()
+    _abi.check(env._ctx, _abi.lib().mplx_lists_add_wait_device(env._ctx, C.byref(s), int(n), int(sel.ptr), int(sel.n_nodes),
+                                                               _device_ptr(sel.id), None))
 
 
 def _params(env, eps, delta, g_max, max_rounds, max_expand, capacity, max_frontier, lists_stride, sight, goal_kw):
@@ -678,7 +738,7 @@ def _params(env, eps, delta, g_max, max_rounds, max_expand, capacity, max_fronti
 
 def run_search(env, start, goal_row, eps, delta, g_max, max_rounds, max_expand, capacity, max_frontier, lists_stride, sight,
                tol_pos, tol_vel, tol_acc, tol_yaw, w, v_max, start_g=0.0, prior=None, avoid=None, t0=0.0, radius=None,
-               ignore_group=-1, time_keys=None):
+               ignore_group=-1, time_keys=None, wait=False, park_goal=False):
     env._flush()
     prm = _params(env, eps, delta, g_max, max_rounds, max_expand, capacity, max_frontier, lists_stride, sight,
                   dict(w=w, v_max=v_max, tol_pos=tol_pos, tol_vel=tol_vel, tol_acc=tol_acc, tol_yaw=tol_yaw))
@@ -689,9 +749,9 @@ def run_search(env, start, goal_row, eps, delta, g_max, max_rounds, max_expand, 
     tab = NodeTable(env, capacity)
     opn = sel = imp = lists = None
     try:
-        if avoid is not None or time_keys:
+        if avoid is not None or time_keys or wait or park_goal:
             _avoid_setup("search", avoid, time_keys, np.asarray(start, dtype=np.float64).reshape(-1, 1), 1, t0, radius,
-                         ignore_group, tab, prm)
+                         ignore_group, tab, prm, wait, park_goal)
         opn = OpenSet(env, tab)
         if prior is not None:
             opn.set_goals(prm["goal_row"].reshape(1, -1), **prm["goal_kw"])
@@ -702,6 +762,8 @@ def run_search(env, start, goal_row, eps, delta, g_max, max_rounds, max_expand, 
         count = tab.seed(start, None if (start_g is None or float(start_g) == 0.0) else float(start_g), frontier=imp)
         _table_check(tab, "search", "after seeding")
         opn.push(imp, n_max=count, eps=eps, sight=sight)
+        if park_goal:
+            avoid.park(opn, imp, count)
         rounds, expanded = [0], [0]
         status, res, total = _search_loop(env, "search", False, tab, opn, sel, imp, lists, prm, 0, rounds, expanded, avoid)
         return SearchResult(status[0], res[0], tab, opn, total, expanded[0], env, prm)
@@ -798,7 +860,7 @@ class MultiSearchResult:
 
 def run_search_many(env, starts, goal_rows, eps, delta, g_max, max_rounds, max_expand, capacity, max_frontier, lists_stride,
                     sight, tol_pos, tol_vel, tol_acc, tol_yaw, w, v_max, start_g=0.0, priors=None, avoid=None, t0=0.0,
-                    radius=None, ignore_group=-1, time_keys=None):
+                    radius=None, ignore_group=-1, time_keys=None, wait=False, park_goal=False):
     env._flush()
     starts = np.ascontiguousarray(starts, dtype=np.float64)
     goal_rows = np.ascontiguousarray(goal_rows, dtype=np.float64)
@@ -816,8 +878,8 @@ def run_search_many(env, starts, goal_rows, eps, delta, g_max, max_rounds, max_e
     tab = NodeTable(env, capacity, n_queries=Q)
     opn = sel = imp = lists = None
     try:
-        if avoid is not None or time_keys:
-            _avoid_setup("search_many", avoid, time_keys, starts, Q, t0, radius, ignore_group, tab, prm)
+        if avoid is not None or time_keys or wait or park_goal:
+            _avoid_setup("search_many", avoid, time_keys, starts, Q, t0, radius, ignore_group, tab, prm, wait, park_goal)
         opn = OpenSet(env, tab)
         opn.set_goals(goal_rows, **prm["goal_kw"])
         if priors is not None:
@@ -827,6 +889,8 @@ def run_search_many(env, starts, goal_rows, eps, delta, g_max, max_rounds, max_e
         count = tab.seed(starts, g0, frontier=imp, query=np.arange(Q, dtype=np.int32))
         _table_check(tab, "search_many", "after seeding")
         opn.push(imp, n_max=count, eps=eps, sight=sight)
+        if park_goal:
+            avoid.park(opn, imp, count)
         rounds, expanded = [0] * Q, [0] * Q
         status, res, total = _search_loop(env, "search_many", True, tab, opn, sel, imp, lists, prm, 0, rounds, expanded, avoid)
         return MultiSearchResult(status, res, tab, opn, rounds, expanded, total, env, prm)
