@@ -94,6 +94,10 @@ RESERVE_SYMBOLS = ["mplx_reserve_create", "mplx_reserve_destroy", "mplx_reserve_
 RESERVE_MAX_BYTES = 1 << 30
 # ... and the one include/mplx_wait.h declares (the zero control's entry appended to the lists of an expansion)
 WAIT_SYMBOLS = ["mplx_lists_add_wait_device"]
+# ... and the ones include/mplx_field.h declares (goal distance fields and the push of an open set that reads one)
+FIELD_SYMBOLS = ["mplx_field_create", "mplx_field_destroy", "mplx_field_build", "mplx_field_shape", "mplx_field_view_of",
+                 "mplx_field_download", "mplx_field_is_stale", "mplx_field_passes", "mplx_open_set_field", "mplx_open_clear_field"]
+FIELD_MAX_BYTES = 1 << 30
 
 ROUTE_AUTO, ROUTE_DENSE, ROUTE_TILE, ROUTE_GRID = 0, 1, 2, 3
 
@@ -267,6 +271,10 @@ class PriorInfo(C.Structure):
 class PriorView(C.Structure):
     _fields_ = [("n_steps", C.c_void_p), ("pos", C.c_void_p), ("togo", C.c_void_p), ("goal_row", C.c_void_p),
                 ("goal_hash", C.c_void_p), ("step_capacity", C.c_int64)]
+
+
+class FieldView(C.Structure):
+    _fields_ = [("dist", C.c_void_p), ("F", C.c_int32), ("n_cells", C.c_int64)]
 
 
 class RebaseResult(C.Structure):
@@ -516,10 +524,20 @@ def lib():
         "mplx_reserve_check_device": (C.c_int, [vp, vp, C.POINTER(SuccLists), i64, vp, vp, i64, vp, vp]),
         "mplx_reserve_park_device": (C.c_int, [vp, vp, C.POINTER(TableFrontier), i64, vp, vp]),
         "mplx_lists_add_wait_device": (C.c_int, [vp, C.POINTER(SuccLists), i64, vp, i64, vp, vp]),
+        "mplx_field_create": (C.c_int, [vp, C.POINTER(vp)]),
+        "mplx_field_destroy": (None, [vp]),
+        "mplx_field_build": (C.c_int, [vp, i32, vp, vp]),
+        "mplx_field_shape": (C.c_int, [vp, C.POINTER(i32), C.POINTER(i64)]),
+        "mplx_field_view_of": (C.c_int, [vp, C.POINTER(FieldView)]),
+        "mplx_field_download": (C.c_int, [vp, vp]),
+        "mplx_field_is_stale": (C.c_int, [vp]),
+        "mplx_field_passes": (C.c_int, [vp, C.POINTER(i64)]),
+        "mplx_open_set_field": (C.c_int, [vp, vp, vp]),
+        "mplx_open_clear_field": (C.c_int, [vp]),
         "mplx_table_set_time_keys": (C.c_int, [vp, i32]),
         "mplx_time_key": (C.c_uint64, [C.c_uint64, dbl]),
     }
-    for name in SYMBOLS + MAP_UTIL_SYMBOLS + ROLLOUT_SYMBOLS + RAY_SYMBOLS + TRAJ_SYMBOLS + TABLE_SYMBOLS + OPEN_SYMBOLS + MULTI_SYMBOLS + REPLAN_SYMBOLS + PRIOR_SYMBOLS + SOLVE_SYMBOLS + LIMITS_SYMBOLS + SCALE_SYMBOLS + CONFLICT_SYMBOLS + RESERVE_SYMBOLS + WAIT_SYMBOLS:
+    for name in SYMBOLS + MAP_UTIL_SYMBOLS + ROLLOUT_SYMBOLS + RAY_SYMBOLS + TRAJ_SYMBOLS + TABLE_SYMBOLS + OPEN_SYMBOLS + MULTI_SYMBOLS + REPLAN_SYMBOLS + PRIOR_SYMBOLS + SOLVE_SYMBOLS + LIMITS_SYMBOLS + SCALE_SYMBOLS + CONFLICT_SYMBOLS + RESERVE_SYMBOLS + WAIT_SYMBOLS + FIELD_SYMBOLS:
         fn = getattr(L, name)  # AttributeError if the library does not export it
         fn.restype, fn.argtypes = sig[name]
     _lib = L

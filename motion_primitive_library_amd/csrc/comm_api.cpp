@@ -175,6 +175,7 @@ int mplx_comm_broadcast_map(mplx_ctx *c, int32_t root) {
   c->has_pot = flags[0] != 0;
   c->has_region = flags[1] != 0;
   c->blk_ok = false;
+  c->blk_epoch++;
   return MPLX_OK;
 }
 

@@ -415,7 +415,7 @@ static int rebuild_sat(mplx_ctx *c) {
   return MPLX_OK;
 }
 
-static int ensure_blocked_bits(mplx_ctx *c) {
+int ensure_blocked_bits(mplx_ctx *c) {
   if (c->blk_ok) return MPLX_OK;
   c->sat_stale = false;
   const int64_t words = (c->n_cells + 31) >> 5;

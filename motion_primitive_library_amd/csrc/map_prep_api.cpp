@@ -69,6 +69,7 @@ int mplx_edit_map(mplx_ctx *c, const int64_t *cell_index, const int8_t *values, 
   HIP_TRY(c, mplx::launch_edit_map((const int64_t *)(l.base + o_idx), (const int8_t *)(l.base + ib), n, c->n_cells, (int8_t *)c->map.p, blk,
                                    c->has_region ? (const uint32_t *)c->region_bits.p : nullptr, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));  // the caller may free its arrays on return
+  c->blk_epoch++;  // (the bits were patched, or will be rebuilt: a goal field of the old map is stale, include/mplx_field.h)
   if (blk && c->sat_ok) {
     // the summed-area table (free-box shortcut of the factorised kernels) changes in every entry behind an edited cell:
     // it is switched off and rebuilt by the first launch large enough to be worth it (lists_route.cpp, lists_grid)
@@ -168,6 +169,7 @@ int mplx_update_potential_map(mplx_ctx *c, const double *pos, const double *radi
   HIP_TRY(c, hipStreamSynchronize(c->stream));  // the host-side mask buffer goes out of scope
   c->has_pot = true;
   c->blk_ok = false;
+  c->blk_epoch++;
   return MPLX_OK;
 }
 
@@ -246,6 +248,7 @@ int mplx_set_search_region_path(mplx_ctx *c, const double *path, int32_t n_point
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   c->has_region = true;
   c->blk_ok = false;
+  c->blk_epoch++;
   return MPLX_OK;
 }
 

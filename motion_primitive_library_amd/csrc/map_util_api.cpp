@@ -30,6 +30,7 @@ int end_map_change(mplx_ctx *c, int8_t *h_map_out) {
   if (h_map_out) HIP_TRY(c, hipMemcpyAsync(h_map_out, c->map.p, (size_t)c->n_cells, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   if (!c->has_pot) c->blk_ok = false;
+  c->blk_epoch++;
   return MPLX_OK;
 }
 

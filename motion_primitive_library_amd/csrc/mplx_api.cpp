@@ -234,6 +234,7 @@ int mplx_set_map(mplx_ctx *c, const int8_t *cells, const int32_t *dim, const dou
   c->n_cells = n;
   c->has_map = true;
   c->blk_ok = false;
+  c->blk_epoch++;
   return MPLX_OK;
 }
 
@@ -244,6 +245,7 @@ int mplx_set_potential(mplx_ctx *c, const int8_t *cells) {
     c->svc.streak = 0;
     if (int rc = mplx_detail::svc_stop(c)) return rc;  // (no resident kernel serves a potential map today: kept in step with mplx_set_region)
     c->blk_ok = c->blk_ok && !c->has_pot;
+    c->blk_epoch++;
     c->has_pot = false;
     return MPLX_OK;
   }
@@ -255,6 +257,7 @@ int mplx_set_potential(mplx_ctx *c, const int8_t *cells) {
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   c->has_pot = true;
   c->blk_ok = false;
+  c->blk_epoch++;
   return MPLX_OK;
 }
 
@@ -265,6 +268,7 @@ int mplx_set_region(mplx_ctx *c, const uint8_t *cells) {
     c->svc.streak = 0;
     if (int rc = mplx_detail::svc_stop(c)) return rc;  // a resident kernel carries the region in its arguments
     c->blk_ok = c->blk_ok && !c->has_region;
+    c->blk_epoch++;
     c->has_region = false;
     return MPLX_OK;
   }
@@ -280,6 +284,7 @@ int mplx_set_region(mplx_ctx *c, const uint8_t *cells) {
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   c->has_region = true;
   c->blk_ok = false;
+  c->blk_epoch++;
   return MPLX_OK;
 }
 

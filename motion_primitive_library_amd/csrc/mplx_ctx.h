@@ -60,6 +60,7 @@ struct mplx_ctx {
   mplx_detail::DevBuf conflict_ws;               // scratch of mplx_traj_conflicts (conflict_api.cpp); grow-only
   mplx_detail::DevBuf prep_lut, prep_a, prep_b;  // map preprocessing scratch (map_prep_api.cpp)
   bool blk_ok = false;   // blocked-bit map matches the current map + region
+  uint64_t blk_epoch = 0;  // bumped wherever blk_ok is cleared or the bits are patched: what a goal field was built at (include/mplx_field.h)
   bool u_factored = false;
   bool u_wide = false;   // 17 .. 32 distinct values on some axis: only the lexicographic kernel (expand_lex_kernel.hip) takes the table
   bool u_lex = false;    // the table is the full Cartesian product of its per-axis values in lexicographic order
@@ -170,6 +171,18 @@ struct mplx_ctx {
   int comm_rank = 0, comm_world = 1;
   mplx_detail::DevBuf comm_meta;  // [world + 1][MPLX_COMM_META] int64: the meta record of every rank, then the own one
   std::vector<double> h_state;  // mplx_get_succ: the state rows of its one node
+};
+
+// include/mplx_field.h (field_api.cpp); open_api.cpp reads it for the push of an open set with a field
+struct mplx_field {
+  mplx_ctx *c = nullptr;
+  mplx_detail::DevBuf dist, active, counter;
+  mplx_detail::DevBuf bits;  // with a potential map installed: the field's own blocked bits (field_kernel.hip says why)
+  std::vector<mplx_open *> users;  // the open sets it is in force in: told when it is destroyed (open_field_gone)
+  int32_t F = 0;           // 0: empty
+  int64_t n_cells = 0;     // ... of the map the field was built on
+  uint64_t epoch = 0;      // mplx_ctx::blk_epoch at the build
+  int64_t passes = 0;      // of the last build (diagnostic)
 };
 
 namespace mplx_detail {
@@ -314,6 +327,7 @@ struct TilePlan {
 };
 TilePlan plan_tile(const mplx_ctx *c);
 int ensure_tables(mplx_ctx *c);
+int ensure_blocked_bits(mplx_ctx *c);  // the blocked-bit map of the current map + region + potential, built if not current
 mplx::ExpandArgs expand_args(mplx_ctx *c, const double *d_nodes, int64_t n_nodes, int64_t node_stride, const mplx_succ *o);
 mplx::TileArgs tile_args(mplx_ctx *c, const TilePlan &tp, const double *d_nodes, int64_t n_nodes, int64_t node_stride,
                          const mplx_succ_lists *o);
@@ -357,6 +371,9 @@ int open_push(mplx_open *o, const char *who, const mplx_table_frontier *d_rows, 
 // open_api.cpp: the open set as the park veto of a reservation table (reserve_api.cpp) sees it: its context and table
 // (set whatever it answers), MPLX_ERR_STATE for a table with a status bit, else the table fields and the flags of `a`
 int open_park_args(mplx_open *o, const char *who, mplx_ctx **c, mplx_table **tab, mplx::OpenArgs *a);
+// open_api.cpp: the field in force in `o` is being destroyed (field_api.cpp): every later push is MPLX_ERR_STATE until the
+// open set is given another field, clear_field or new goals
+void open_field_gone(mplx_open *o);
 
 // traj_api.cpp: the checks of a trajectory set, the chain launch into the context's segment table, and the staging of a
 // host set (rows carved by traj_set_rows, copied by traj_stage_set), for conflict_api.cpp.

@@ -897,7 +897,32 @@ struct OpenArgs {
   const double *prior_togo;        // [n_queries][prior_cap]
   int64_t prior_cap;
   double prior_dt;                 // the searching context's dt
+  // push with a goal field (include/mplx_field.h; appended): null = no field in force
+  const int32_t *field_dist;       // [F][field_cells]
+  const int32_t *field_of_query;   // [n_queries] in device memory: the field of a query, or -1
+  int32_t field_F;
+  int64_t field_cells;
+  int32_t field_dim[3];
+  double field_org[3], field_res;
 };
+
+// Goal distance fields (field_kernel.hip, field_api.cpp; include/mplx_field.h).  Tiles: 32 x 32 cells in 2-D, 8 x 8 x 8 in 3-D.
+struct FieldArgs {
+  int32_t *dist;                   // [F][n_cells]
+  const uint32_t *blk;             // the context's blocked-bit map
+  const int32_t *box;              // [F][6]: lo[3], hi[3], clipped to the map (lo > hi on an axis: no seed)
+  int32_t F, dim;
+  int32_t mdim[3];
+  int32_t tiles[3];                // tiles per axis
+  int64_t n_cells, n_tiles;        // n_tiles = tiles[0] * tiles[1] * tiles[2]
+  uint8_t *active_cur, *active_next;  // [F * n_tiles] each: a byte per (field, tile)
+  unsigned long long *counter;     // (field, tile)s that marked a neighbour, summed over the passes so far
+};
+constexpr int kFieldTile2 = 32, kFieldTile3 = 8;
+// blocked bits of a context WITH a potential map, for the field: value >= 100 (env_map.h:117), outside the region, padding
+hipError_t launch_field_pot_bits(const int8_t *pot, const uint32_t *region, int64_t n_cells, uint32_t *out, hipStream_t s);
+hipError_t launch_field_init(const FieldArgs &a, hipStream_t s);
+hipError_t launch_field_pass(const FieldArgs &a, hipStream_t s);
 hipError_t launch_open_clear(const OpenArgs &a, hipStream_t s);  // ctl: 2 * n_queries control blocks
 // closed: the push of include/mplx_replan.h -- the rows get SEEN (and IS_GOAL) but not IS_OPEN
 hipError_t launch_open_push(int dim, int pass, const OpenArgs &a, int64_t rows, hipStream_t s, bool closed = false);  // pass 0: all (or up to the row flags); 1: after the ray trace

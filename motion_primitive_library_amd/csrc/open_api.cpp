@@ -2,6 +2,7 @@
 // control blocks and scratch are its own; launches go to the stream of the table's context.  No call touches the
 // staging arena: push and select take device pointers only.
 #include "mplx_ctx.h"
+#include "../../include/mplx_field.h"
 #include "../../include/mplx_multi.h"
 #include "../../include/mplx_prior.h"
 #include "../../include/mplx_ray.h"
@@ -32,13 +33,30 @@ struct mplx_open {
   bool has_priors = false;
   int64_t pr_cap = 0;                   // steps per query the table is laid out for
   double pr_dt = 0.0;                   // the searching context's dt when the table was built
+  // include/mplx_field.h: the goal field in force, the field of every query (device, [Q]) and the largest entry
+  mplx_field *fld = nullptr;
+  DevBuf fld_q;
+  int32_t fld_max = -1;
+  bool fld_gone = false;                // the field was destroyed while in force: a push is an error
+  double goals_vmin = 0.0;              // the smallest v_max among the goals of mplx_open_set_goals
 };
 
 namespace {
 
+// the field of `o` is no longer in force (cleared, replaced, dropped by new goals, or the open set goes)
+void drop_field(mplx_open *o) {
+  if (o->fld) {
+    std::vector<mplx_open *> &u = o->fld->users;
+    u.erase(std::remove(u.begin(), u.end(), o), u.end());
+  }
+  o->fld = nullptr;
+  o->fld_gone = false;
+}
+
 void release_open(mplx_open *o) {
+  drop_field(o);
   for (DevBuf *b : {&o->f, &o->flags, &o->ctl, &o->mark, &o->tot, &o->rows, &o->goals, &o->goals0, &o->pr_n, &o->pr_pos, &o->pr_togo,
-                    &o->pr_status, &o->pr_sidx, &o->pr_sterm, &o->pr_costs, &o->pr_trav, &o->pr_grow, &o->pr_ghash})
+                    &o->pr_status, &o->pr_sidx, &o->pr_sterm, &o->pr_costs, &o->pr_trav, &o->pr_grow, &o->pr_ghash, &o->fld_q})
     release(*b);
   if (o->mirror) (void)hipHostFree(o->mirror);
   delete o;
@@ -139,6 +157,11 @@ int mplx_open_push_device(mplx_open *o, const mplx_table_frontier *d_rows, int64
 
 }  // extern "C"
 
+void mplx_detail::open_field_gone(mplx_open *o) {
+  o->fld = nullptr;
+  o->fld_gone = true;
+}
+
 int mplx_detail::open_park_args(mplx_open *o, const char *who, mplx_ctx **c, mplx_table **tab, mplx::OpenArgs *a) {
   *c = o->c;
   *tab = o->tab;
@@ -169,6 +192,23 @@ int mplx_detail::open_push(mplx_open *o, const char *who, const mplx_table_front
     a.prior_togo = (const double *)o->pr_togo.p;
     a.prior_cap = o->pr_cap;
     a.prior_dt = o->pr_dt;
+  }
+  if (o->fld_gone) return fail(c, MPLX_ERR_STATE, "%s: the goal field in force was destroyed (mplx_open_clear_field, or set another)", who);
+  if (o->fld) {  // include/mplx_field.h
+    const mplx_field *fl = o->fld;
+    if (fl->epoch != c->blk_epoch) return fail(c, MPLX_ERR_STATE, "%s: the goal field is stale (the map changed since mplx_field_build)", who);
+    if (fl->F < 1 || o->fld_max >= fl->F || fl->n_cells != c->n_cells)
+      return fail(c, MPLX_ERR_STATE, "%s: the goal field is empty, or was rebuilt with fewer fields than the queries use", who);
+    if (!((o->has_goals ? o->goals_vmin : c->goal_fuse.v_max) > 0)) return fail(c, MPLX_ERR_STATE, "%s: a goal field needs v_max > 0", who);
+    a.field_dist = (const int32_t *)fl->dist.p;
+    a.field_of_query = (const int32_t *)o->fld_q.p;
+    a.field_F = fl->F;
+    a.field_cells = fl->n_cells;
+    for (int i = 0; i < 3; i++) {
+      a.field_dim[i] = c->mdim[i];
+      a.field_org[i] = c->origin[i];
+    }
+    a.field_res = c->res;
   }
   if (!sight) {
     HIP_TRY(c, mplx::launch_open_push(c->dim, 0, a, rows, c->stream, closed));
@@ -234,10 +274,11 @@ int mplx_open_set_goals(mplx_open *o, const mplx_goal_spec *h_goals, int32_t n) 
   if (n != o->Q) return fail(c, MPLX_ERR_ARG, "%s: %d goals for a table of %d queries", who, (int)n, (int)o->Q);
   MPLX_GUARD_BEGIN
   std::vector<mplx::PostFuse> f((size_t)n);
-  double tol = 0.0;
+  double tol = 0.0, vmin = 0.0;
   for (int32_t q = 0; q < n; q++) {
     if (int rc = goal_fuse_of(c, who, &h_goals[q], &f[(size_t)q])) return rc;
     tol = std::max(tol, f[(size_t)q].tol_pos);
+    vmin = (q == 0 || !(f[(size_t)q].v_max >= vmin)) ? f[(size_t)q].v_max : vmin;
   }
   if (int rc = bind_device(c)) return rc;
   if (int rc = resolve_pending(c)) return rc;  // the arena is shared with the other host-pointer calls
@@ -252,8 +293,10 @@ int mplx_open_set_goals(mplx_open *o, const mplx_goal_spec *h_goals, int32_t n) 
   HIP_TRY(c, hipMemcpyAsync(o->goals0.p, l.base + o_g, bytes, hipMemcpyDeviceToDevice, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));  // (f leaves scope; the arena is free again)
   o->has_priors = false;  // a new goal: the old prior no longer leads to it (include/mplx_prior.h)
+  drop_field(o);          // ... and neither does the old field (include/mplx_field.h)
   o->has_goals = true;
   o->goals_tol = tol;
+  o->goals_vmin = vmin;
   return MPLX_OK;
   MPLX_GUARD_END(c)
 }
@@ -304,6 +347,7 @@ int mplx_open_set_priors_device(mplx_open *o, const mplx_prior_source *src, cons
       !s->starts || !s->actions)
     return fail(c, MPLX_ERR_ARG, "%s: bad trajectory set (horizon >= 1, starts, actions, strides >= counts)", who);
   if (!o->has_goals) return fail(c, MPLX_ERR_STATE, "%s: no goals of the open set's own (mplx_open_set_goals)", who);
+  if (o->fld) return fail(c, MPLX_ERR_STATE, "%s: a goal field is in force (mplx_open_clear_field first)", who);
   if (!c->has_params) return fail(c, MPLX_ERR_STATE, "%s: mplx_set_params has not been called", who);
   if (!c->has_map) return fail(c, MPLX_ERR_STATE, "%s: set the map first", who);
   if (c->n_cells > 0x7fffffffLL) return fail(c, MPLX_ERR_STATE, "%s: the map has more cells than getIndex (int32) can number", who);
@@ -387,6 +431,54 @@ int mplx_open_clear_priors(mplx_open *o) {
   o->has_priors = false;
   if (o->has_goals)
     HIP_TRY(c, hipMemcpyAsync(o->goals.p, o->goals0.p, (size_t)o->Q * sizeof(mplx::PostFuse), hipMemcpyDeviceToDevice, c->stream));
+  return MPLX_OK;
+}
+
+// ---- include/mplx_field.h ----------------------------------------------------------------------------------------------
+
+int mplx_open_set_field(mplx_open *o, mplx_field *fld, const int32_t *h_field_of_query) {
+  if (!o) return MPLX_ERR_ARG;
+  mplx_ctx *c = o->c;
+  const char *who = "mplx_open_set_field";
+  if (!fld) return fail(c, MPLX_ERR_ARG, "%s: NULL field", who);
+  if (fld->c != c) return fail(c, MPLX_ERR_ARG, "%s: the field belongs to another context", who);
+  if (o->has_priors) return fail(c, MPLX_ERR_STATE, "%s: priors are in force (mplx_open_clear_priors first)", who);
+  if (fld->F < 1) return fail(c, MPLX_ERR_STATE, "%s: the field is empty (mplx_field_build)", who);
+  if (!o->has_goals && !c->has_goal) return fail(c, MPLX_ERR_STATE, "%s: no goal (mplx_set_goal, mplx_open_set_goals)", who);
+  if (!((o->has_goals ? o->goals_vmin : c->goal_fuse.v_max) > 0)) return fail(c, MPLX_ERR_STATE, "%s: a goal field needs v_max > 0", who);
+  MPLX_GUARD_BEGIN
+  std::vector<int32_t> fq((size_t)o->Q);
+  int32_t top = -1;
+  for (int32_t q = 0; q < o->Q; q++) {
+    const int32_t v = h_field_of_query ? h_field_of_query[q] : q;
+    if (v < -1 || v >= fld->F) return fail(c, MPLX_ERR_ARG, "%s: query %d asks for field %d of %d", who, (int)q, (int)v, (int)fld->F);
+    fq[(size_t)q] = v;
+    top = std::max(top, v);
+  }
+  if (int rc = bind_device(c)) return rc;
+  if (int rc = resolve_pending(c)) return rc;  // the arena is shared with the other host-pointer calls
+  const size_t bytes = (size_t)o->Q * 4;
+  if (int rc = ensure(c, o->fld_q, bytes)) return rc;
+  StageLayout l;
+  const size_t o_q = l.add(bytes);
+  if (int rc = stage_commit(c, &l)) return rc;
+  HIP_TRY(c, stage_in(c, l.base + o_q, fq.data(), bytes));
+  HIP_TRY(c, hipMemcpyAsync(o->fld_q.p, l.base + o_q, bytes, hipMemcpyDeviceToDevice, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));  // (fq leaves scope; the arena is free again)
+  if (o->fld != fld) {
+    fld->users.push_back(o);  // (first: if it throws nothing has changed)
+    drop_field(o);
+  }
+  o->fld = fld;
+  o->fld_gone = false;
+  o->fld_max = top;
+  return MPLX_OK;
+  MPLX_GUARD_END(c)
+}
+
+int mplx_open_clear_field(mplx_open *o) {
+  if (!o) return MPLX_ERR_ARG;
+  drop_field(o);
   return MPLX_OK;
 }
 

@@ -30,6 +30,10 @@
 //
 // With priors (include/mplx_prior.h) the push is the same kernel again with the heuristic of a guided query read from the
 // open set's prior table (built by traj_kernel.hip); the instantiations without priors are untouched by that.
+//
+// With a goal field (include/mplx_field.h) it is the same kernel once more: the heuristic of a query with a field takes the
+// larger of the default's Linf distance and the grid distance the field holds for the row's cell; the instantiations
+// without a field are untouched by that.
 #include "mplx_internal.h"
 #include "mplx_device_common.h"
 
@@ -80,7 +84,9 @@ __device__ __forceinline__ Decision decide(const OpenArgs &A) { return decide(A.
 // CLOSED: the push of include/mplx_replan.h -- key and goal bit as ever, but the node is not opened
 // PRIOR: include/mplx_prior.h -- a query with a prior table takes its heuristic from where the prior is at the row's time
 // (env_base.h:46-53); the instantiations without it are the kernels they were
-template <int D, bool MULTI, bool CLOSED, bool PRIOR>
+// FIELD: include/mplx_field.h -- a query with a goal field takes max(Linf, res * (dist - 1)) where the default takes Linf,
+// and +inf on a cell no chain leaves; likewise
+template <int D, bool MULTI, bool CLOSED, bool PRIOR, bool FIELD>
 __global__ __launch_bounds__(kBlock) void open_push_kernel(const OpenArgs A, int64_t rows, int pass) {
   if (A.t_ctl->status) return;
   const int64_t r = (int64_t)blockIdx.x * kBlock + threadIdx.x;
@@ -130,6 +136,34 @@ __global__ __launch_bounds__(kBlock) void open_push_kernel(const OpenArgs A, int
       }
       const double lin = PG.v_max > 0 ? PG.w * m / PG.v_max : PG.w * m;
       h = lin + A.prior_togo[(int64_t)q * A.prior_cap + k];
+    }
+  }
+  if (FIELD && !(fl & 2u)) {  // (bit 1: the goal's own lattice state keeps h = 0)
+    const int32_t fq = A.field_of_query[q];
+    if (fq >= 0 && fq < A.field_F) {  // (the host checked the entries: never out of range)
+      bool inside = true;
+      int64_t idx = 0, mul = 1;
+#pragma unroll
+      for (int i = 0; i < D; i++) {
+        const double c = round((s[i] - A.field_org[i]) / A.field_res - 0.5);  // map_util.h:103-108
+        const bool in = c >= 0.0 && c < (double)A.field_dim[i];  // compared as a double: NaN and huge values are outside
+        inside = inside && in;
+        idx += (in ? (int64_t)c : 0) * mul;
+        mul *= A.field_dim[i];
+      }
+      const int32_t n = inside ? A.field_dist[(int64_t)fq * A.field_cells + idx] : -1;
+      if (n < 0) {
+        h = __longlong_as_double((long long)kInfBits);
+      } else {
+        double L = 0;  // post_eval's lpNorm<Infinity> of pos - goal.pos
+#pragma unroll
+        for (int i = 0; i < D; i++) {
+          const double d = fabs(s[i] - PG.g[i]);
+          L = d > L ? d : L;
+        }
+        const double G = A.field_res * (double)(n - 1 > 0 ? n - 1 : 0);
+        if (G > L) h = PG.v_max > 0 ? PG.w * G / PG.v_max : PG.w * G;  // (G <= L: post_eval's h, bit for bit)
+      }
     }
   }
   const double g = A.f_g[r];
@@ -507,17 +541,26 @@ hipError_t launch_open_clear(const OpenArgs &a, hipStream_t s) {
   return hipGetLastError();
 }
 
-template <int D, bool MULTI, bool PRIOR = false>
+template <int D, bool MULTI, bool PRIOR = false, bool FIELD = false>
 void push_closed(bool closed, dim3 grid, dim3 block, hipStream_t s, const OpenArgs &a, int64_t rows, int pass) {
-  if (closed) hipLaunchKernelGGL((open_push_kernel<D, MULTI, true, PRIOR>), grid, block, 0, s, a, rows, pass);
-  else hipLaunchKernelGGL((open_push_kernel<D, MULTI, false, PRIOR>), grid, block, 0, s, a, rows, pass);
+  if (closed) hipLaunchKernelGGL((open_push_kernel<D, MULTI, true, PRIOR, FIELD>), grid, block, 0, s, a, rows, pass);
+  else hipLaunchKernelGGL((open_push_kernel<D, MULTI, false, PRIOR, FIELD>), grid, block, 0, s, a, rows, pass);
 }
 
 hipError_t launch_open_push(int dim, int pass, const OpenArgs &a, int64_t rows, hipStream_t s, bool closed) {
   if (rows <= 0) return hipSuccess;
   const dim3 grid((unsigned)((rows + kBlock - 1) / kBlock)), block(kBlock);
   if (dim != 2 && dim != 3) return hipErrorInvalidValue;
-  if (a.prior_n) {  // (priors need goals of the open set's own: open_api.cpp)
+  if (a.field_dist) {  // (never together with priors: open_api.cpp)
+    if (a.prior_n || !a.field_of_query || a.field_F < 1 || a.field_cells < 1 || !(a.field_res > 0)) return hipErrorInvalidValue;
+    if (a.goals) {
+      if (dim == 2) push_closed<2, true, false, true>(closed, grid, block, s, a, rows, pass);
+      else push_closed<3, true, false, true>(closed, grid, block, s, a, rows, pass);
+    } else {
+      if (dim == 2) push_closed<2, false, false, true>(closed, grid, block, s, a, rows, pass);
+      else push_closed<3, false, false, true>(closed, grid, block, s, a, rows, pass);
+    }
+  } else if (a.prior_n) {  // (priors need goals of the open set's own: open_api.cpp)
     if (!a.goals || !a.prior_pos || !a.prior_togo || a.prior_cap < 1) return hipErrorInvalidValue;
     if (dim == 2) push_closed<2, true, true>(closed, grid, block, s, a, rows, pass);
     else push_closed<3, true, true>(closed, grid, block, s, a, rows, pass);

@@ -2331,10 +2331,16 @@ class EnvMap:
         from .search import OpenSet
         return OpenSet(self, table)
 
+    def alloc_field(self):
+        """An empty search.GoalField (include/mplx_field.h): build(goal_rows, tol_pos) makes it the grid distance of
+        every cell to a goal region; the `field` of search / search_many, or OpenSet.set_field."""
+        from .search import GoalField
+        return GoalField(self)
+
     def search(self, start, goal_row, eps=1.0, delta=None, g_max=float("inf"), max_rounds=None, max_expand=None,
                capacity=1 << 16, max_frontier=None, lists_stride=None, sight=True, tol_pos=0.5, tol_vel=-1.0, tol_acc=-1.0,
                tol_yaw=-1.0, w=None, v_max=None, start_g=0.0, prior=None, avoid=None, t0=0.0, radius=None, ignore_group=-1,
-               time_keys=None, wait=False, park_goal=False):
+               time_keys=None, wait=False, park_goal=False, field=None, field_of_query=None):
         """A goal-directed search from `start` (one 4D+2 state) to the goal region of `goal_row` that stays on the
         device: set_goal, seed, push; then per round one select (the round's only read-back, 48 bytes), and while it
         selects: expand the selection, relax its lists against the table, push the nodes whose g fell.  Keys are
@@ -2360,16 +2366,20 @@ class EnvMap:
         state it leaves where it is, which the expansion drops -- to its lists before the check (include/mplx_wait.h).
         park_goal=True (needs avoid, else ValueError): after every push a goal-region node at which the robot could not
         stay to the table's horizon loses its goal bit (mplx_reserve_park_device, include/mplx_reserve.h) and is
-        expanded like any other.  With both off the search issues exactly the calls it issued before they existed."""
+        expanded like any other.  With both off the search issues exactly the calls it issued before they existed.
+        field: None -- the calls of a search without one.  True: a goal distance field (include/mplx_field.h) is built for
+        the goal, set after the goal and freed with the result: the heuristic becomes w * max(Linf, res * (dist - 1)) / v_max,
+        which sees walls and dead ends and stays admissible.  A search.GoalField (alloc_field; with field_of_query, default
+        [0]) is used as given and not freed.  field together with prior is a ValueError."""
         from .search import run_search
         return run_search(self, start, goal_row, eps, delta, g_max, max_rounds, max_expand, capacity, max_frontier,
                           lists_stride, sight, tol_pos, tol_vel, tol_acc, tol_yaw, w, v_max, start_g, prior, avoid, t0, radius,
-                          ignore_group, time_keys, wait, park_goal)
+                          ignore_group, time_keys, wait, park_goal, field, field_of_query)
 
     def search_many(self, starts, goal_rows, eps=1.0, delta=None, g_max=float("inf"), max_rounds=None, max_expand=None,
                     capacity=1 << 16, max_frontier=None, lists_stride=None, sight=True, tol_pos=0.5, tol_vel=-1.0,
                     tol_acc=-1.0, tol_yaw=-1.0, w=None, v_max=None, start_g=0.0, priors=None, avoid=None, t0=0.0, radius=None,
-                    ignore_group=-1, time_keys=None, wait=False, park_goal=False):
+                    ignore_group=-1, time_keys=None, wait=False, park_goal=False, field=None, field_of_query=None):
         """Q searches of EnvMap.search at once, sharing every launch of a round (include/mplx_multi.h): starts
         [4D+2][Q], goal_rows [Q][4D+2], query q from starts[:, q] to the goal region of goal_rows[q].  One table of
         `capacity` nodes and one open set hold all of them; a round selects, expands, relaxes and pushes the union of
@@ -2379,11 +2389,13 @@ class EnvMap:
         cost-to-come for every start, or [Q].  priors: [Q] search.Prior or None (no prior for that query), e.g. another
         result's as_priors(): one mplx_open_set_priors_device for all of them (include/mplx_prior.h).
         avoid, t0, radius, ignore_group (one value for all queries or [Q]), time_keys, wait and park_goal: as EnvMap.search takes them;
-        every query has its own start on the clock, radius and ignored group, and one check serves them all."""
+        every query has its own start on the clock, radius and ignored group, and one check serves them all.
+        field: as EnvMap.search takes it; True builds one field per DISTINCT goal row (the delay candidates of one robot
+        share one); a GoalField is used with field_of_query [Q] (default: query q uses field q; -1: the default heuristic)."""
         from .search import run_search_many
         return run_search_many(self, starts, goal_rows, eps, delta, g_max, max_rounds, max_expand, capacity, max_frontier,
                                lists_stride, sight, tol_pos, tol_vel, tol_acc, tol_yaw, w, v_max, start_g, priors, avoid, t0,
-                               radius, ignore_group, time_keys, wait, park_goal)
+                               radius, ignore_group, time_keys, wait, park_goal, field, field_of_query)
 
     def alloc_reservations(self, trajs, step, n_steps=None, t0=None, radius=None, group=None, park=True):
         """A reservation table on the device (include/mplx_reserve.h; search.Reservations): the positions of the

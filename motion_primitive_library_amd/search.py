@@ -15,6 +15,8 @@
 is EnvMap.search.  With a table of Q queries (include/mplx_multi.h), opn.set_goals(goal_rows) and opn.select_many the
 same loop runs Q searches at once: EnvMap.search_many.  opn.set_priors(...) (include/mplx_prior.h) steers every query by
 a prior trajectory -- coarse-to-fine planning is two searches, the second with priors=first.as_priors().
+env.alloc_field() gives a GoalField (include/mplx_field.h): the grid distance of every cell to a goal region, which
+opn.set_field(...) -- search(..., field=True) -- puts under the heuristic so that it sees walls and dead ends.
 """
 import ctypes as C
 import math
@@ -54,6 +56,150 @@ def _prior_of(result, q):
     return Prior(start, act, prm["control"], prm["U"], prm["dt"])
 
 
+def float_to_int(x, origin, res):
+    """MapUtil::floatToInt (map_util.h:103-108) of one coordinate: (int)round((x - origin) / res - 0.5), halves away from
+    zero as C's round takes them."""
+    v = (np.float64(x) - np.float64(origin)) / np.float64(res) - np.float64(0.5)
+    if not np.isfinite(v) or abs(v) >= 2.0 ** 31:
+        raise ValueError("float_to_int: %r is not a cell of any map" % (x,))
+    r = math.floor(v)
+    d = v - r  # (exact)
+    return int(r + 1 if (d >= 0.5 if v >= 0 else d > 0.5) else r)
+
+
+class GoalField:
+    """mplx_field of an EnvMap (include/mplx_field.h): F goal distance fields over the map's cells.  Build it after the
+    map, the search region and the potential map are what the search will see; anything that can change a blocked bit
+    afterwards makes it stale, and a push with a stale field is an error.  With a potential map installed a cell blocks at
+    a value >= 100; cells of 1 .. 99 cost and are traversable.  Free it (or let it go) before the EnvMap is closed; an open
+    set it is still in force in refuses its pushes from then on."""
+
+    def __init__(self, env):
+        self._env = env
+        self._fld = None
+        f = C.c_void_p()
+        _abi.check(env._ctx, _abi.lib().mplx_field_create(env._ctx, C.byref(f)))
+        self._fld = f
+
+    def _check(self, rc):
+        _abi.check(self._env._ctx, rc)
+
+    def build_boxes(self, lo, hi):
+        """mplx_field_build: lo, hi [F][D] inclusive seed boxes in cell indices (clipped to the map by the call)."""
+        env = self._env
+        env._flush()
+        lo = np.ascontiguousarray(np.asarray(lo, dtype=np.int32).reshape(-1, env.dim))
+        hi = np.ascontiguousarray(np.asarray(hi, dtype=np.int32).reshape(-1, env.dim))
+        if lo.shape != hi.shape:
+            raise ValueError("build_boxes: lo and hi must both be [F][%d]" % env.dim)
+        self._check(_abi.lib().mplx_field_build(self._fld, lo.shape[0], lo.ctypes.data, hi.ctypes.data))
+        return self
+
+    def build(self, goal_rows, tol_pos=0.5):
+        """One field per goal row ([F][4D+2], or [F][D] positions) with the seed box floatToInt(goal - tol) - 1 ..
+        floatToInt(goal + tol) + 1: one cell wider than the goal region on every side, so that no rounding of goal -+ tol
+        leaves a goal-region cell unseeded (extra seeds only lower dist).  tol_pos: one value or [F]."""
+        env = self._env
+        if env._geometry is None:
+            raise RuntimeError("GoalField.build: set the map first")
+        _, origin, res = env._geometry
+        rows = np.atleast_2d(np.asarray(goal_rows, dtype=np.float64))
+        tol = np.broadcast_to(np.asarray(tol_pos, dtype=np.float64), (rows.shape[0],))
+        lo = [[float_to_int(rows[f, i] - tol[f], origin[i], res) - 1 for i in range(env.dim)] for f in range(rows.shape[0])]
+        hi = [[float_to_int(rows[f, i] + tol[f], origin[i], res) + 1 for i in range(env.dim)] for f in range(rows.shape[0])]
+        return self.build_boxes(lo, hi)
+
+    @property
+    def shape(self):
+        """(F, n_cells); (0, 0) while the field is empty."""
+        F, n = C.c_int32(), C.c_int64()
+        self._check(_abi.lib().mplx_field_shape(self._fld, C.byref(F), C.byref(n)))
+        return int(F.value), int(n.value)
+
+    @property
+    def F(self):
+        return self.shape[0]
+
+    @property
+    def stale(self):
+        return _abi.lib().mplx_field_is_stale(self._fld) == 1
+
+    @property
+    def passes(self):
+        """Passes of the last build (diagnostic: part of no result)."""
+        n = C.c_int64()
+        self._check(_abi.lib().mplx_field_passes(self._fld, C.byref(n)))
+        return int(n.value)
+
+    def view(self):
+        v = _abi.FieldView()
+        self._check(_abi.lib().mplx_field_view_of(self._fld, C.byref(v)))
+        return v
+
+    def dist(self):
+        """A download: int32 [F][n_cells], cell index as MapUtil::getIndex."""
+        F, n = self.shape
+        out = np.empty((F, n), np.int32)
+        if F:
+            self._check(_abi.lib().mplx_field_download(self._fld, out.ctypes.data))
+        return out
+
+    def free(self):
+        if self._fld and self._env._ctx:
+            _abi.lib().mplx_field_destroy(self._fld)
+        self._fld = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+def _distinct_goals(goal_rows, tol_pos):
+    """(rows [F][.], tol [F], field_of_query [Q]): one entry per distinct (goal row, tol_pos), in order of appearance."""
+    rows = np.atleast_2d(np.asarray(goal_rows, dtype=np.float64))
+    tol = np.broadcast_to(np.asarray(tol_pos, dtype=np.float64), (rows.shape[0],))
+    seen, foq, keep = {}, [], []
+    for q in range(rows.shape[0]):
+        key = (rows[q].tobytes(), float(tol[q]))
+        if key not in seen:
+            seen[key] = len(keep)
+            keep.append(q)
+        foq.append(seen[key])
+    return rows[keep], tol[keep], np.array(foq, np.int32)
+
+
+def _field_setup(who, env, opn, field, field_of_query, goal_rows, tol_pos, prior):
+    """The `field` argument of a search, after the goals are set: (field, owned, field_of_query)."""
+    if field is None or field is False:
+        return None, False, None
+    if prior is not None:
+        raise ValueError("%s: field and prior(s) exclude each other" % who)
+    owned = field is True
+    if owned:
+        rows, tol, field_of_query = _distinct_goals(goal_rows, tol_pos)
+        field = GoalField(env)
+    try:
+        if owned:
+            field.build(rows, tol)
+        opn.set_field(field, field_of_query)
+    except Exception:
+        if owned:
+            field.free()
+        raise
+    foq = None if field_of_query is None else np.array(field_of_query, np.int32).ravel()
+    return field, owned, foq
+
+
+def _hand_field(new, old_or_none, field=None, owned=False, foq=None):
+    """The field of a result: from the search that made it, or handed on by a replan."""
+    if old_or_none is not None:
+        field, owned, foq = old_or_none.field, old_or_none._owns_field, old_or_none._field_of_query
+        old_or_none.field, old_or_none._owns_field = None, False
+    new.field, new._owns_field, new._field_of_query = field, owned, foq
+
+
 class OpenSet:
     """mplx_open of a NodeTable.  Free it (or let it go) before the table."""
 
@@ -61,6 +207,7 @@ class OpenSet:
         self._env = env
         self._table = table  # (kept alive: the open set reads the table's arrays)
         self._open = None
+        self._field = None  # (kept alive while it is in force)
         self.capacity = table.capacity
         self.n_queries = getattr(table, "n_queries", 1)
         o = C.c_void_p()
@@ -125,6 +272,7 @@ class OpenSet:
             g.w, g.v_max = float(ws[q]), float(vs[q])
             g.tol_pos, g.tol_vel, g.tol_acc, g.tol_yaw = float(tp[q]), float(tv[q]), float(ta[q]), float(ty[q])
         self._check(_abi.lib().mplx_open_set_goals(self._open, specs, n))
+        self._field = None  # (dropped by the call)
 
     def select_many(self, delta, frontier, want_result=True, d_results=None):
         """mplx_open_select_multi_device into `frontier`.  Returns the Q results as a list of dicts (one
@@ -194,6 +342,23 @@ class OpenSet:
 
     def clear_priors(self):
         self._check(_abi.lib().mplx_open_clear_priors(self._open))
+
+    def set_field(self, field, field_of_query=None):
+        """mplx_open_set_field: every push takes the heuristic of query q from field field_of_query[q] of `field` (a
+        GoalField); None: query q uses field q; -1: that query keeps the default heuristic.  In force until clear_field or
+        set_goals; clear() leaves it."""
+        self._env._flush()
+        foq = None
+        if field_of_query is not None:
+            foq = np.ascontiguousarray(field_of_query, dtype=np.int32).ravel()
+            if foq.size != self.n_queries:
+                raise ValueError("field_of_query: %d entries for %d queries" % (foq.size, self.n_queries))
+        self._check(_abi.lib().mplx_open_set_field(self._open, field._fld, None if foq is None else foq.ctypes.data))
+        self._field = field
+
+    def clear_field(self):
+        self._check(_abi.lib().mplx_open_clear_field(self._open))
+        self._field = None
 
     def priors(self):
         """The prior table in force (a download): {"n_steps" [Q], "pos": [Q] arrays [n_steps][D], "togo": [Q] arrays,
@@ -482,7 +647,7 @@ def time_key(hashes, t):
 
 
 def plan_prioritised(env, starts, goal_rows, step, radius, order=None, delays=(0.0,), park=True, wait=False, park_goal=False,
-                     **search_kw):
+                     field=False, **search_kw):
     """Prioritised planning of R robots on one map: robot r plans against the trajectories of the robots planned
     before it, as obstacles that move on the common clock of conflicts().  starts [4D+2][R] (t = 0 each), goal_rows
     [R][4D+2], radius a scalar or [R]; step: the clock's.  Robots are planned in `order` (default: the index, so a lower
@@ -505,6 +670,9 @@ def plan_prioritised(env, starts, goal_rows, step, radius, order=None, delays=(0
     park in the way of an earlier one, which only the final conflicts shows.  The two belong together: a robot whose
     early arrival is vetoed arrives later at the same lattice state through wait edges.
 
+    field=True: the R goal distance fields (include/mplx_field.h) are built in one GoalField.build up front, and robot r
+    searches with its own for every delay candidate.
+
     Its limits: a robot that finds no path is reported and not reserved.  Protection holds to the table's horizon
     (`n_steps`) only.  An earlier robot is never re-planned when a later one cannot avoid it.  A chain with waits is not
     what rollout() / MapPlanner.checkTraj accept (they stop at a wait with SKIP_SAME), and smooth() / shortcut() of a
@@ -524,8 +692,14 @@ def plan_prioritised(env, starts, goal_rows, step, radius, order=None, delays=(0
     paths, t0, status, cost = [None] * R, np.zeros(R), [None] * R, np.full(R, math.inf)
     planned = []
     res = None
+    fld = None
     try:
+        if field:
+            fld = GoalField(env).build(goal_rows, search_kw.get("tol_pos", 0.5))
+            search_kw = dict(search_kw, field=fld)
         for r in order:
+            if fld is not None:
+                search_kw["field_of_query"] = [r] * Q
             st, ac = _path_set(env, [paths[k] for k in planned])
             fill = ((st, ac), step, n_steps, t0[planned], rad[planned] if planned else 0.0, None, park)
             if res is None:
@@ -551,6 +725,8 @@ def plan_prioritised(env, starts, goal_rows, step, radius, order=None, delays=(0
     finally:
         if res is not None:
             res.free()
+        if fld is not None:
+            fld.free()
     rank = np.zeros(R, np.int32)
     rank[order] = np.arange(len(order), dtype=np.int32)
     st, ac = _path_set(env, paths)
@@ -575,6 +751,7 @@ class SearchResult:
         self.open = open_set
         self.rounds = rounds
         self.expanded = expanded
+        self.field, self._owns_field, self._field_of_query = None, False, None  # (search(field=): _hand_field)
 
     def path(self):
         """(start_state, actions) of the chain of best predecessors from the seed to the goal node: the `starts` and
@@ -607,7 +784,10 @@ class SearchResult:
         original start --, all of them are expanded once in a forced round (in chunks of max_frontier rows), then the
         loop of EnvMap.search finishes.  goal_row: a new goal; keys and goal bits of the kept nodes are recomputed
         anyway.  A search with a prior replans with it (the open set keeps it); a new goal_row drops it unless `prior`
-        gives one again.  Returns a new SearchResult that owns the table and the open set; this one no longer does."""
+        gives one again.  A search with a field replans with it: a field the search built itself (field=True) is rebuilt in
+        place when it is stale or a new goal_row is given; a caller's field that is stale, or a new goal_row with a
+        caller's field, raises -- rebuild the field and search anew.  Returns a new SearchResult that owns the table and
+        the open set; this one no longer does."""
         if self.table is None or self._params is None:
             raise RuntimeError("replan: this result does not own a table (it was replanned or freed)")
         _no_replan(self._params)
@@ -625,6 +805,9 @@ class SearchResult:
         if self.table is not None:
             self.table.free()
         self.open = self.table = None
+        if self._owns_field and self.field is not None:
+            self.field.free()
+        self.field, self._owns_field = None, False
 
     def __repr__(self):
         return "SearchResult(%s, cost=%r, rounds=%d, expanded=%d)" % (STATUS_NAMES[self.status], self.cost, self.rounds, self.expanded)
@@ -738,11 +921,14 @@ def _params(env, eps, delta, g_max, max_rounds, max_expand, capacity, max_fronti
 
 def run_search(env, start, goal_row, eps, delta, g_max, max_rounds, max_expand, capacity, max_frontier, lists_stride, sight,
                tol_pos, tol_vel, tol_acc, tol_yaw, w, v_max, start_g=0.0, prior=None, avoid=None, t0=0.0, radius=None,
-               ignore_group=-1, time_keys=None, wait=False, park_goal=False):
+               ignore_group=-1, time_keys=None, wait=False, park_goal=False, field=None, field_of_query=None):
+    if field is not None and field is not False and prior is not None:
+        raise ValueError("search: field and prior exclude each other")
     env._flush()
     prm = _params(env, eps, delta, g_max, max_rounds, max_expand, capacity, max_frontier, lists_stride, sight,
                   dict(w=w, v_max=v_max, tol_pos=tol_pos, tol_vel=tol_vel, tol_acc=tol_acc, tol_yaw=tol_yaw))
     prm["goal_row"] = np.array(goal_row, dtype=np.float64)
+    fld, fld_owned = None, False
     prm["own_goals"] = prior is not None  # the open set carries its goal itself (priors need that): replan keeps it so
     fcap = prm["fcap"]
     env.set_goal(goal_row, **prm["goal_kw"])
@@ -756,6 +942,8 @@ def run_search(env, start, goal_row, eps, delta, g_max, max_rounds, max_expand, 
         if prior is not None:
             opn.set_goals(prm["goal_row"].reshape(1, -1), **prm["goal_kw"])
             opn.set_prior_list([prior])
+        if field is not None and field is not False:
+            fld, fld_owned, field_of_query = _field_setup("search", env, opn, field, field_of_query, prm["goal_row"], tol_pos, prior)
         sel, imp = TableFrontier(env, fcap), TableFrontier(env, int(capacity))  # (no more nodes can improve than exist)
         lists = env.alloc_lists(fcap, want_state=True, stride=lists_stride)
         # (g = None is the call without a g row: the bytes of a search before start_g existed)
@@ -766,11 +954,15 @@ def run_search(env, start, goal_row, eps, delta, g_max, max_rounds, max_expand, 
             avoid.park(opn, imp, count)
         rounds, expanded = [0], [0]
         status, res, total = _search_loop(env, "search", False, tab, opn, sel, imp, lists, prm, 0, rounds, expanded, avoid)
-        return SearchResult(status[0], res[0], tab, opn, total, expanded[0], env, prm)
+        out = SearchResult(status[0], res[0], tab, opn, total, expanded[0], env, prm)
+        _hand_field(out, None, fld, fld_owned, field_of_query)
+        return out
     except Exception:
         if opn is not None:
             opn.free()
         tab.free()
+        if fld_owned:
+            fld.free()
         raise
     finally:
         for b in (sel, imp, lists):
@@ -797,6 +989,7 @@ class MultiSearchResult:
         self.rounds = list(rounds)
         self.expanded = list(expanded)
         self.total_rounds = total_rounds
+        self.field, self._owns_field, self._field_of_query = None, False, None  # (search_many(field=): _hand_field)
 
     def path(self, q):
         """(start_state, actions) of query q, as SearchResult.path."""
@@ -852,6 +1045,9 @@ class MultiSearchResult:
         if self.table is not None:
             self.table.free()
         self.open = self.table = None
+        if self._owns_field and self.field is not None:
+            self.field.free()
+        self.field, self._owns_field = None, False
 
     def __repr__(self):
         return "MultiSearchResult(%s, rounds=%d, expanded=%d)" % (
@@ -860,7 +1056,9 @@ class MultiSearchResult:
 
 def run_search_many(env, starts, goal_rows, eps, delta, g_max, max_rounds, max_expand, capacity, max_frontier, lists_stride,
                     sight, tol_pos, tol_vel, tol_acc, tol_yaw, w, v_max, start_g=0.0, priors=None, avoid=None, t0=0.0,
-                    radius=None, ignore_group=-1, time_keys=None, wait=False, park_goal=False):
+                    radius=None, ignore_group=-1, time_keys=None, wait=False, park_goal=False, field=None, field_of_query=None):
+    if field is not None and field is not False and priors is not None:
+        raise ValueError("search_many: field and priors exclude each other")
     env._flush()
     starts = np.ascontiguousarray(starts, dtype=np.float64)
     goal_rows = np.ascontiguousarray(goal_rows, dtype=np.float64)
@@ -872,6 +1070,8 @@ def run_search_many(env, starts, goal_rows, eps, delta, g_max, max_rounds, max_e
     prm = _params(env, eps, delta, g_max, max_rounds, max_expand, capacity, max_frontier, lists_stride, sight,
                   dict(w=w, v_max=v_max, tol_pos=tol_pos, tol_vel=tol_vel, tol_acc=tol_acc, tol_yaw=tol_yaw))
     fcap = prm["fcap"]
+    prm["goal_rows"] = goal_rows.copy()
+    fld, fld_owned = None, False
     g0 = None if start_g is None else np.broadcast_to(np.asarray(start_g, dtype=np.float64), (Q,))
     if g0 is not None and not g0.any():
         g0 = None  # (the call without a g row: the bytes of a search before start_g existed)
@@ -884,6 +1084,8 @@ def run_search_many(env, starts, goal_rows, eps, delta, g_max, max_rounds, max_e
         opn.set_goals(goal_rows, **prm["goal_kw"])
         if priors is not None:
             opn.set_prior_list(list(priors))
+        if field is not None and field is not False:
+            fld, fld_owned, field_of_query = _field_setup("search_many", env, opn, field, field_of_query, goal_rows, tol_pos, priors)
         sel, imp = TableFrontier(env, fcap), TableFrontier(env, int(capacity))  # (no more nodes can improve than exist)
         lists = env.alloc_lists(fcap, want_state=True, stride=lists_stride)
         count = tab.seed(starts, g0, frontier=imp, query=np.arange(Q, dtype=np.int32))
@@ -893,11 +1095,15 @@ def run_search_many(env, starts, goal_rows, eps, delta, g_max, max_rounds, max_e
             avoid.park(opn, imp, count)
         rounds, expanded = [0] * Q, [0] * Q
         status, res, total = _search_loop(env, "search_many", True, tab, opn, sel, imp, lists, prm, 0, rounds, expanded, avoid)
-        return MultiSearchResult(status, res, tab, opn, rounds, expanded, total, env, prm)
+        out = MultiSearchResult(status, res, tab, opn, rounds, expanded, total, env, prm)
+        _hand_field(out, None, fld, fld_owned, field_of_query)
+        return out
     except Exception:
         if opn is not None:
             opn.free()
         tab.free()
+        if fld_owned:
+            fld.free()
         raise
     finally:
         for b in (sel, imp, lists):
@@ -914,8 +1120,15 @@ def run_replan(old, multi, roots, goal_rows, check_edges, priors=None):
     env._flush()
     eps, g_max, sight, fcap, capacity = prm["eps"], prm["g_max"], prm["sight"], prm["fcap"], prm["capacity"]
     Q = tab.n_queries
+    fld = getattr(old, "field", None)
+    if fld is not None:
+        if priors is not None:
+            raise ValueError("replan: field and prior(s) exclude each other")
+        if not old._owns_field and (fld.stale or goal_rows is not None):
+            raise RuntimeError("replan: the caller's goal field is stale or the goal is new: rebuild the field and search anew")
     if goal_rows is not None:
         if multi:
+            prm = dict(prm, goal_rows=np.ascontiguousarray(goal_rows, dtype=np.float64))
             opn.set_goals(goal_rows, **prm["goal_kw"])  # (drops the priors)
         else:
             prm = dict(prm, goal_row=np.array(goal_rows, dtype=np.float64))
@@ -928,6 +1141,13 @@ def run_replan(old, multi, roots, goal_rows, check_edges, priors=None):
         opn.set_prior_list(list(priors))
     if not multi:
         env.set_goal(prm["goal_row"], **prm["goal_kw"])  # (the context's goal may have been moved since the search)
+    if fld is not None:  # before the first push: an owned field follows the map and the goal; set_goals dropped it
+        foq = old._field_of_query
+        if old._owns_field and (fld.stale or goal_rows is not None):
+            rows, tol, foq = _distinct_goals(prm["goal_rows"] if multi else prm["goal_row"], prm["goal_kw"]["tol_pos"])
+            fld.build(rows, tol)
+            old._field_of_query = foq
+        opn.set_field(fld, foq)
     kept = sel = imp = lists = None
     try:
         kept, sel, imp = TableFrontier(env, capacity), TableFrontier(env, fcap), TableFrontier(env, capacity)
@@ -966,6 +1186,7 @@ def run_replan(old, multi, roots, goal_rows, check_edges, priors=None):
         else:
             new = SearchResult(status[0], res[0], tab, opn, total, expanded[0], env, prm)
         new.rebase_info = info
+        _hand_field(new, old)
         old.table = old.open = None  # the new result owns them
         return new
     finally:
