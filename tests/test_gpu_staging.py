@@ -26,12 +26,17 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import staging_walk
 from motion_primitive_library_amd import workloads as W
+from staging_walk import CONFIGS, POISON, SIZES, assert_same_bytes, fill, poisoned, raw  # noqa: F401 (the walks import them here)
 
-POISON = 0xA5
-SIZES = (1, 3, 65, 257, 1000)
 KINDS = ("expand", "expand_lists", "edges_cap0", "edges_cap3", "read_cells", "edit_map", "rollout", "rollout_goal",
          "ray_trace", "traj_info", "sample_uniform", "sample_times", "traj_traverse")
+# the C entry points a kind stages through (tests/test_gpu_staging_sets.py checks the three walks against csrc/)
+ENTRY_POINTS = {"expand": ("mplx_expand",), "expand_lists": ("mplx_expand_lists",), "edges_cap0": ("mplx_check_edges",),
+                "edges_cap3": ("mplx_check_edges",), "read_cells": ("mplx_read_cells",), "edit_map": ("mplx_edit_map", "mplx_read_cells"),
+                "rollout": ("mplx_rollout",), "rollout_goal": ("mplx_rollout",), "ray_trace": ("mplx_ray_trace",), "traj_info": ("mplx_traj_info",),
+                "sample_uniform": ("mplx_traj_sample",), "sample_times": ("mplx_traj_sample",), "traj_traverse": ("mplx_traj_traverse",)}
 TWINNED = ("expand", "expand_lists", "rollout", "rollout_goal", "ray_trace", "traj_info", "sample_uniform", "sample_times",
            "traj_traverse")
 H = 3           # horizon of rollouts and trajectories
@@ -43,28 +48,11 @@ _SET = ("nodes", "actions")
 NEEDS = {"expand": ("nodes",), "expand_lists": ("nodes",), "edges_cap0": ("nodes", "edge_actions"), "edges_cap3": ("nodes", "edge_actions"),
          "read_cells": ("cell_index",), "edit_map": ("cell_index", "cell_values"), "rollout": _SET, "rollout_goal": _SET,
          "ray_trace": ("p1", "p2"), "traj_info": _SET, "sample_uniform": _SET, "sample_times": _SET + ("times",), "traj_traverse": _SET}
-CONFIGS = {"2d_acc_yaw": (2, W.ACCxYAW, (48, 40)), "3d_acc": (3, W.ACC, (20, 18, 16))}
 
 
 def schedule():
     """[(kind, n, visit)]: visit counts the earlier steps of the same kind (variant() picks the form of a call by it)."""
-    k = len(KINDS)
-    rng = np.random.default_rng(SEED)
-    out = {a: [int(b) for b in rng.permutation([b for b in range(k) if b != a])] for a in range(k)}
-    stack, walk = [0], []
-    while stack:  # Hierholzer: a closed walk over every arc of the complete digraph
-        v = stack[-1]
-        if out[v]:
-            stack.append(out[v].pop())
-        else:
-            walk.append(stack.pop())
-    steps, visits = [], [0] * k
-    for v in reversed(walk):
-        if visits[v] < len(SIZES) - 1:
-            steps.append((KINDS[v], SIZES[(visits[v] + v) % (len(SIZES) - 1)], 2 * visits[v]))
-        steps.append((KINDS[v], SIZES[-1], 2 * visits[v] + 1 if visits[v] < len(SIZES) - 1 else visits[v] + len(SIZES) - 1))
-        visits[v] += 1
-    return steps
+    return staging_walk.schedule(KINDS, SEED)
 
 
 def variant(kind, visit):
@@ -93,27 +81,7 @@ def test_every_kind_runs_directly_after_every_other_kinds_largest_size():
 
 
 # ---- the world of a configuration and the inputs of a step (numpy only; the same for both contexts and the twin)
-class World:
-    def __init__(self, name):
-        self.dim, self.control, self.map_dim = CONFIGS[name]
-        self.res, self.origin = 0.1, [0.0] * self.dim
-        self.cells = W.box_map(self.map_dim, self.res, 0.15, 1017, side_m=(0.2, 0.8))  # [z][y][x]; editMap steps change it
-        yaw = [-0.5, 0.0, 0.5] if self.control & 0x10 else None
-        self.U = W.grid_controls([-1, 0, 1], self.dim, yaw_rates=yaw)
-        self.params = {"v_max": 2.0, "yaw_max": 0.5} if yaw else {"v_max": 2.0}
-        self.F, self.nU = 4 * self.dim + 2, self.U.shape[0]
-        probe = W.random_frontier(self.cells, self.origin, self.res, 1, 7, self.control, 2.0, 0.5)
-        self.goal = probe[:, 0].copy()
-
-    def configure(self, env):
-        env.setMap(self.origin, list(self.map_dim), self.cells, self.res)
-        env.set_control(self.control)
-        env.set_u(self.U)
-        for k, v in self.params.items():
-            getattr(env, "set_" + k)(v)
-        env.set_goal(self.goal, tol_pos=1.0)
-        env._flush()
-
+class World(staging_walk.World):
     def inputs(self, i, kind, n, visit):
         rng = np.random.default_rng(SEED + i)
         x = {"nodes": W.random_frontier(self.cells, self.origin, self.res, n, SEED + i, self.control, 2.0, 0.5)}
@@ -129,12 +97,6 @@ class World:
         x["p2"] = np.ascontiguousarray(p2 if per_item else p2[:, 0])
         x["times"] = np.ascontiguousarray(rng.uniform(-0.5, H + 0.5, size=(n, Q) if per_item else (Q,)))
         return {k: v for k, v in x.items() if k in NEEDS[kind] or k == "form"}
-
-
-def poisoned(dtype, shape):
-    a = np.empty(shape, dtype=dtype)
-    a.view(np.uint8)[...] = POISON
-    return a
 
 
 def out_spec(w, kind, n, x):
@@ -167,14 +129,6 @@ def out_spec(w, kind, n, x):
         return {"out": ("<f8", (4 * w.dim + 3, n, count)), "status": ("u1", (n,))}
     assert kind == "traj_traverse"
     return {"status": ("u1", (n,)), "cost": ("<f8", (n,)), "n_samples": ("<i4", (n,)), "n_cells": ("<i4", (n,)), "stop_sample": ("<i4", (n,))}
-
-
-def fill(struct, ptrs, **extra):
-    for k, p in ptrs.items():
-        setattr(struct, k, p)
-    for k, v in extra.items():
-        setattr(struct, k, v)
-    return struct
 
 
 def call(abi, env, w, kind, n, x, ptrs, inp, device):
@@ -248,17 +202,6 @@ def device_call(engine, env, w, kind, n, x):
     for b in list(rows.values()) + list(inp.values()):
         b.free()
     return out
-
-
-def raw(a):
-    return np.ascontiguousarray(a).view(np.uint8)
-
-
-def assert_same_bytes(got, want, what):
-    assert sorted(got) == sorted(want), what
-    for k in got:
-        assert np.array_equal(raw(got[k]), raw(want[k])), "%s: row `%s` differs in %d bytes" % (
-            what, k, int((raw(got[k]) != raw(want[k])).sum()))
 
 
 def assert_equals_twin(w, kind, n, host, dev, what):
