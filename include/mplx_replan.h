@@ -59,8 +59,10 @@
  * Errors: MPLX_ERR_ARG for NULL required pointers, root_id < -1 and a frontier without id / g / state / count or with
  * state_stride < capacity or capacity < 0; MPLX_ERR_STATE for a table with a status bit (calls queued before the host
  * saw the bit do nothing), for check_edges != 0 without map, parameters or controls, and for mplx_table_rebase_device
- * on a table with Q > 1, and for either rebase on a table with time keys (mplx_table_set_time_keys: its kept nodes would
- * keep times measured from the old start; replanning among reservations is not built).  A table without nodes is a successful no-op with count 0.  mplx_table_rebase_multi_device
+ * on a table with Q > 1, and for either rebase on a table with time keys (mplx_table_set_time_keys: the identity test here
+ * compares lattice hashes, and nothing here knows wait edges or reservations; mplx_table_rebase_timed_device of
+ * include/mplx_replan_timed.h rebases such a table -- its kept nodes go on measuring t, like g, from the original start).
+ * A table without nodes is a successful no-op with count 0.  mplx_table_rebase_multi_device
  * accepts a table of one query and then gives the bytes of the plain call.                                           */
 #ifndef MPLX_REPLAN_H
 #define MPLX_REPLAN_H

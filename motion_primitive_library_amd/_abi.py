@@ -94,6 +94,8 @@ RESERVE_SYMBOLS = ["mplx_reserve_create", "mplx_reserve_destroy", "mplx_reserve_
 RESERVE_MAX_BYTES = 1 << 30
 # ... and the one include/mplx_wait.h declares (the zero control's entry appended to the lists of an expansion)
 WAIT_SYMBOLS = ["mplx_lists_add_wait_device"]
+# ... and the one include/mplx_replan_timed.h declares (the rebase of a table with time keys, waits and reservations)
+REPLAN_TIMED_SYMBOLS = ["mplx_table_rebase_timed_device"]
 # ... and the ones include/mplx_field.h declares (goal distance fields and the push of an open set that reads one)
 FIELD_SYMBOLS = ["mplx_field_create", "mplx_field_destroy", "mplx_field_build", "mplx_field_shape", "mplx_field_view_of",
                  "mplx_field_download", "mplx_field_is_stale", "mplx_field_passes", "mplx_open_set_field", "mplx_open_clear_field"]
@@ -524,6 +526,8 @@ def lib():
         "mplx_reserve_check_device": (C.c_int, [vp, vp, C.POINTER(SuccLists), i64, vp, vp, i64, vp, vp]),
         "mplx_reserve_park_device": (C.c_int, [vp, vp, C.POINTER(TableFrontier), i64, vp, vp]),
         "mplx_lists_add_wait_device": (C.c_int, [vp, C.POINTER(SuccLists), i64, vp, i64, vp, vp]),
+        "mplx_table_rebase_timed_device": (C.c_int, [vp, vp, i32, i32, vp, C.POINTER(TableFrontier), vp, vp, vp,
+                                                    C.POINTER(RebaseResult)]),
         "mplx_field_create": (C.c_int, [vp, C.POINTER(vp)]),
         "mplx_field_destroy": (None, [vp]),
         "mplx_field_build": (C.c_int, [vp, i32, vp, vp]),
@@ -537,7 +541,7 @@ def lib():
         "mplx_table_set_time_keys": (C.c_int, [vp, i32]),
         "mplx_time_key": (C.c_uint64, [C.c_uint64, dbl]),
     }
-    for name in SYMBOLS + MAP_UTIL_SYMBOLS + ROLLOUT_SYMBOLS + RAY_SYMBOLS + TRAJ_SYMBOLS + TABLE_SYMBOLS + OPEN_SYMBOLS + MULTI_SYMBOLS + REPLAN_SYMBOLS + PRIOR_SYMBOLS + SOLVE_SYMBOLS + LIMITS_SYMBOLS + SCALE_SYMBOLS + CONFLICT_SYMBOLS + RESERVE_SYMBOLS + WAIT_SYMBOLS + FIELD_SYMBOLS:
+    for name in SYMBOLS + MAP_UTIL_SYMBOLS + ROLLOUT_SYMBOLS + RAY_SYMBOLS + TRAJ_SYMBOLS + TABLE_SYMBOLS + OPEN_SYMBOLS + MULTI_SYMBOLS + REPLAN_SYMBOLS + PRIOR_SYMBOLS + SOLVE_SYMBOLS + LIMITS_SYMBOLS + SCALE_SYMBOLS + CONFLICT_SYMBOLS + RESERVE_SYMBOLS + WAIT_SYMBOLS + REPLAN_TIMED_SYMBOLS + FIELD_SYMBOLS:
         fn = getattr(L, name)  # AttributeError if the library does not export it
         fn.restype, fn.argtypes = sig[name]
     _lib = L

@@ -16,7 +16,8 @@
 #include <string>
 #include <vector>
 
-struct mplx_table;  // include/mplx_table.h
+struct mplx_table;    // include/mplx_table.h
+struct mplx_reserve;  // include/mplx_reserve.h
 
 namespace mplx_detail {
 
@@ -362,7 +363,14 @@ void table_observe(mplx_table *t);
 // ... and as a rebase (replan_api.cpp) sees it: the same check, the table's arrays, its bound of n_nodes and the scratch
 // of the rebase passes (scratch: allocated here on the first call, for the table's capacity; the device is bound.  Without
 // it only the check, n_queries and n_bound)
-int table_replan_args(mplx_table *t, const char *who, bool scratch, mplx_ctx **c, mplx::ReplanArgs *a);
+// time_keys: null refuses a table with time keys (the untimed rebases); else it receives whether the table has them
+int table_replan_args(mplx_table *t, const char *who, bool scratch, mplx_ctx **c, mplx::ReplanArgs *a, int32_t *time_keys = nullptr);
+// reserve_api.cpp: a reservation table as the timed rebase (replan_api.cpp) sees it: its context (set whatever it
+// answers), MPLX_ERR_STATE before a fill or before mplx_reserve_set_queries, else the table, query, control and scan
+// fields of `a` (the lists stay empty)
+int reserve_table_args(mplx_reserve *r, const char *who, mplx_ctx **c, mplx::ReserveArgs *a);
+// wait_api.cpp: the zero action of include/mplx_wait.h -- the smallest all-zero row of the control table -- or -1
+int32_t zero_action(const mplx_ctx *c);
 // ... and as the check of a reservation table (reserve_api.cpp) sees it: the same check, the per-node query column (null
 // for one query), the number of queries and the node capacity
 int table_reserve_args(mplx_table *t, const char *who, mplx_ctx **c, const int32_t **d_query, int32_t *n_queries, int64_t *cap);

@@ -965,6 +965,20 @@ struct ReplanArgs {
   int64_t *f_count;
 };
 hipError_t launch_replan_rebase(int dim, int control, const ReplanArgs &a, int passes, hipStream_t s);
+// The timed rebase (include/mplx_replan_timed.h): the rebase above with the edge pass's key fold and wait rule, and with
+// the kept edges tested against a reservation table.  A struct of its own: the launches of the untimed rebase take the
+// arguments they took.
+struct ReplanTimedArgs {
+  ReplanArgs R;              // check_edges: the edge pass runs
+  int32_t time_keys;         // the hash column holds mplx_time_key(h_next, tp + dt)
+  int32_t allow_wait;
+  int32_t a0;                // the zero action of include/mplx_wait.h, or -1: the control table has none
+  int32_t use_res;           // the reservation pass runs: the table, query, control and scan fields of `res`
+  ReserveArgs res;           // (its lists are not used)
+  long long *hit;            // [node capacity] or null
+  unsigned long long *n_blocked;  // or null
+};
+hipError_t launch_replan_rebase_timed(int dim, int control, const ReplanTimedArgs &a, int passes, hipStream_t s);
 // table_kernel.hip: the scan of tile counts tot[n_tiles] in place, the frontier count (FRONTIER_FULL when it exceeds
 // f_cap), ctl->emit and the pinned mirror -- the second scan of a relax, for a pass that marked per tile itself
 hipError_t launch_table_scan_frontier(const TableArgs &a, hipStream_t s);

@@ -363,6 +363,24 @@ struct Pair {
     *cost_out = cost;
     *iters_out = iters;
   }
+
+  // Wait edges (include/mplx_wait.h), for the zero control: the pair is the successor get_succ drops, it is valid
+  // (heading and limits) and the position does not move at all.  wait_kernel.hip appends the entry by these two; the
+  // timed rebase (replan_kernel.hip) tests a kept wait edge by them.
+  __device__ __forceinline__ bool wait_eligible(bool valid) const {
+    bool same_pos = true;
+#pragma unroll
+    for (int i = 0; i < D; i++) same_pos = same_pos && (cpos[i] == npos[i]);
+    return h_next == h_curr && valid && same_pos;
+  }
+  // env_map.h:164-165 with a traversal cost of 0 (classify's expression)
+  __device__ __forceinline__ double wait_cost(const ExpandArgs &A) const {
+    double J = 0;
+#pragma unroll
+    for (int i = 0; i < D; i++) J += ax[i].effort(A.dt);
+    const double c = 0;
+    return c + (J + A.w * A.dt);
+  }
 };
 
 }  // namespace pair

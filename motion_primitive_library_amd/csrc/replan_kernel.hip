@@ -19,13 +19,20 @@
 //            back-pointer; kept nodes marked and counted per tile (and, one atomicAdd per tile, in all)
 //   scan     table_kernel.hip's second scan: prefix sums of the tile counts, the frontier count or FRONTIER_FULL
 //   emit     kept nodes in id order -> id, g and the state rows gathered from the table
+// The timed rebase (include/mplx_replan_timed.h) is the same launches with two differences: its edge pass is the TIMED
+// instantiation of the edge kernel (the key fold of a table with time keys, the wait rule), and between the edge pass
+// and init a reservation pass (replan_reserve_kernel, described where it stands) tests every kept edge against a
+// reservation table and sets bad[id] where it conflicts or leaves the horizon.
 // Every index is checked where it is formed: ids and predecessors against the table's own node count, rows against the
 // frontier's capacity, actions against the control table.  A table with a status bit makes every pass return at its
 // first instruction.
 #include "mplx_internal.h"
 #include "mplx_pair_device.h"
+#include "mplx_traj_device.h"
 
 #include <math.h>
+
+#include <type_traits>
 
 namespace mplx {
 namespace {
@@ -52,8 +59,15 @@ __device__ __forceinline__ bool is_root(const ReplanArgs &R, int64_t id) {
   return r >= 0 ? id == (int64_t)r : R.pred[id] == -1;
 }
 
-template <int D, int K, bool YAW>
-__global__ __launch_bounds__(kBlock) void replan_edge_kernel(const ReplanArgs R) {
+__device__ __forceinline__ const ReplanArgs &base_of(const ReplanArgs &a) { return a; }
+__device__ __forceinline__ const ReplanArgs &base_of(const ReplanTimedArgs &a) { return a.R; }
+
+// TIMED (include/mplx_replan_timed.h): the identity test compares the key the hash column holds -- with time keys
+// mplx_time_key(h_next, tp + dt), table_kernel.hip's fold --, and the zero action's dropped successor is a wait edge,
+// held by the eligibility and the cost of wait_kernel.hip.  Without TIMED the kernel is the untimed rebase's.
+template <int D, int K, bool YAW, bool TIMED>
+__global__ __launch_bounds__(kBlock) void replan_edge_kernel(const std::conditional_t<TIMED, ReplanTimedArgs, ReplanArgs> X) {
+  const ReplanArgs &R = base_of(X);
   if (R.ctl->status) return;
   const int64_t id = (int64_t)blockIdx.x * kBlock + threadIdx.x, n = node_count(R);
   if (id >= n) return;
@@ -88,7 +102,19 @@ __global__ __launch_bounds__(kBlock) void replan_edge_kernel(const ReplanArgs R)
       double cost;
       int iters;
       P.classify(A, valid, &st, &cost, &iters);
-      if (st != 1 || P.h_next != R.hash[id] || (amb && R.band)) {
+      uint64_t key = P.h_next;
+      bool holds = st == 1 && !(amb && R.band);
+      if constexpr (TIMED) {
+        if (a == X.a0 && P.h_next == P.h_curr) {  // a wait edge (a0 = -1: there is none)
+          holds = X.allow_wait != 0 && P.wait_eligible(valid);
+          cost = P.wait_cost(A);
+        }
+        if (X.time_keys) {
+          const double tc = R.state[(int64_t)(4 * D + 1) * R.cap + p] + A.dt;
+          pair::fold(key, pair::quantise(tc, 0.1));
+        }
+      }
+      if (!holds || key != R.hash[id]) {
         bad = 1;
       } else {
         const double cand = __longlong_as_double((long long)R.g[p]) + cost;
@@ -203,33 +229,146 @@ __global__ __launch_bounds__(kBlock) void replan_emit_kernel(const ReplanArgs R)
   }
 }
 
-template <int D>
-hipError_t edge_dim(int control, const ReplanArgs &a, dim3 grid, hipStream_t s) {
+template <int D, bool TIMED>
+hipError_t edge_dim(int control, const std::conditional_t<TIMED, ReplanTimedArgs, ReplanArgs> &a, dim3 grid, hipStream_t s) {
   const dim3 block(kBlock);
   switch (control) {
-    case 0x01: hipLaunchKernelGGL((replan_edge_kernel<D, 1, false>), grid, block, 0, s, a); break;
-    case 0x03: hipLaunchKernelGGL((replan_edge_kernel<D, 2, false>), grid, block, 0, s, a); break;
-    case 0x07: hipLaunchKernelGGL((replan_edge_kernel<D, 3, false>), grid, block, 0, s, a); break;
-    case 0x0f: hipLaunchKernelGGL((replan_edge_kernel<D, 4, false>), grid, block, 0, s, a); break;
-    case 0x11: hipLaunchKernelGGL((replan_edge_kernel<D, 1, true>), grid, block, 0, s, a); break;
-    case 0x13: hipLaunchKernelGGL((replan_edge_kernel<D, 2, true>), grid, block, 0, s, a); break;
-    case 0x17: hipLaunchKernelGGL((replan_edge_kernel<D, 3, true>), grid, block, 0, s, a); break;
-    case 0x1f: hipLaunchKernelGGL((replan_edge_kernel<D, 4, true>), grid, block, 0, s, a); break;
+    case 0x01: hipLaunchKernelGGL((replan_edge_kernel<D, 1, false, TIMED>), grid, block, 0, s, a); break;
+    case 0x03: hipLaunchKernelGGL((replan_edge_kernel<D, 2, false, TIMED>), grid, block, 0, s, a); break;
+    case 0x07: hipLaunchKernelGGL((replan_edge_kernel<D, 3, false, TIMED>), grid, block, 0, s, a); break;
+    case 0x0f: hipLaunchKernelGGL((replan_edge_kernel<D, 4, false, TIMED>), grid, block, 0, s, a); break;
+    case 0x11: hipLaunchKernelGGL((replan_edge_kernel<D, 1, true, TIMED>), grid, block, 0, s, a); break;
+    case 0x13: hipLaunchKernelGGL((replan_edge_kernel<D, 2, true, TIMED>), grid, block, 0, s, a); break;
+    case 0x17: hipLaunchKernelGGL((replan_edge_kernel<D, 3, true, TIMED>), grid, block, 0, s, a); break;
+    case 0x1f: hipLaunchKernelGGL((replan_edge_kernel<D, 4, true, TIMED>), grid, block, 0, s, a); break;
     default: return hipErrorInvalidValue;
   }
   return hipGetLastError();
 }
 
-}  // namespace
+// replan_reserve_kernel<D, K>: the ONE edge (state[pred], U[pred_action]) of every non-root node against the reservation
+// table as it is now (include/mplx_replan_timed.h), exactly as reserve_kernel.hip looks at a finite list entry of a row
+// whose parent is pred.  One wave per node, four nodes per workgroup; a wave whose node is not looked at leaves at a
+// wave-uniform branch.  The lanes are 64 consecutive reservations: pos[d][i][b0 + lane] is one contiguous 512-byte
+// request, active[i][b0 + lane] 64 bytes; no LDS, no barrier.  Every lane evaluates the one position of the instant
+// (traj::chain_segment / eval_segment in registers, as the check).  Instants ascend in the outer loop and tiles of 64 in
+// the inner one, so the first non-zero ballot gives the minimum of (i << 32 | b) directly and ends the wave.  What a lane
+// needs of its reservation (its radius, or NaN where it is excluded or of the query's ignored group) is loaded once
+// when B <= 64.  The instants are the check's guess and scan of n_scan = ceil(dt / step) + 3.  Loops are bounded by
+// n_scan, n_steps and B; no workgroup waits for another; bad[id], hit[id] and the count are written by lane 0 of the
+// wave that owns the node (the count by an order-free integer atomic).
+constexpr int kWave = 64;
+constexpr int kResNodes = kBlock / kWave;
+constexpr long long kNoHit = 0x7fffffffffffffffLL;
 
-hipError_t launch_replan_rebase(int dim, int control, const ReplanArgs &a, int passes, hipStream_t s) {
-  const int64_t n = a.n_bound > 0 ? a.n_bound : 1;
-  const dim3 per_node((unsigned)((n + kBlock - 1) / kBlock)), per_tile((unsigned)a.n_tiles), block(kBlock);
-  if (hipError_t e = hipMemsetAsync(a.counters, 0, sizeof(ReplanResult), s)) return e;
-  if (a.check_edges) {
-    hipError_t e = dim == 2 ? edge_dim<2>(control, a, per_node, s) : dim == 3 ? edge_dim<3>(control, a, per_node, s) : hipErrorInvalidValue;
-    if (e != hipSuccess) return e;
+template <int D, int K>
+__global__ __launch_bounds__(kBlock) void replan_reserve_kernel(const ReplanTimedArgs X) {
+  const ReplanArgs &R = X.R;
+  const ReserveArgs &A = X.res;
+  if (R.ctl->status) return;
+  const int lane = threadIdx.x & (kWave - 1);
+  const int64_t id = (int64_t)blockIdx.x * kResNodes + (threadIdx.x >> 6), n = node_count(R);
+  if (id >= n) return;  // (wave-uniform, as every branch on the node below)
+  const int32_t p = R.pred[id], a = R.pred_action[id];
+  bool look = p >= 0 && p < n && a >= 0 && a < A.nU && !is_root(R, id);
+  int32_t q = 0;
+  if (look && A.node_query) q = A.node_query[id];
+  if (q < 0 || q >= A.Q) {
+    look = false;
+    q = 0;
   }
+  if (!look) {
+    if (X.hit && lane == 0) X.hit[id] = -1LL;
+    return;
+  }
+  const double t0 = A.q_t0[q], rq = A.q_r[q];
+  const int32_t ign = A.q_ignore[q];
+  constexpr int F = 4 * D + 2;
+  double ps[4 * D];
+#pragma unroll
+  for (int f = 0; f < 4 * D; f++) ps[f] = R.state[(int64_t)f * R.cap + p];
+  const double tp = R.state[(int64_t)(F - 1) * R.cap + p];
+  const double tc = tp + A.dt;
+  const bool horizon = (double)(A.n_steps - 1) * A.step - t0 < tc;
+  long long key = kNoHit;
+  if (!horizon) {
+    // the instants [i0, i0 + ni): reserve_check_kernel's guess and scan
+    int i0 = 0, ni = 0;
+    const double x = (tp + t0) / A.step;
+    int64_t g = 0;  // (a NaN goes to 0)
+    if (x >= 1.0) g = x < 2147483647.0 ? (int64_t)x - 1 : (int64_t)A.n_steps;
+    for (int s = 0; s < A.n_scan; s++) {
+      const int64_t i = g + s;
+      if (i >= A.n_steps) break;
+      const double tl = (double)i * A.step - t0;
+      if (tl > tc) break;
+      if (tl >= tp) {
+        if (ni == 0) i0 = (int)i;
+        ni++;
+      }
+    }
+    double seg[5 * D + 2];
+    {
+      pair::Axis<K> ax[D];
+      traj::chain_segment<D, K>(ps, A.U + (int64_t)a * A.udim, 0.0, 0.0, ax, seg, 1);
+    }
+    const bool one_tile = A.B <= kWave;
+    double r0 = NAN;
+    if (one_tile && lane < A.B && A.incl[lane] != 0 && A.group[lane] != ign) r0 = A.r[lane];
+    for (int ii = 0; ii < ni && key == kNoHit; ii++) {
+      const int i = i0 + ii;
+      const double tl = (double)i * A.step - t0;
+      traj::Sample<D> sm;
+      traj::eval_segment<D, true, false>(seg, 1, tl - tp, sm);
+      for (int64_t b0 = 0; b0 < A.B; b0 += kWave) {
+        const int64_t b = b0 + lane;
+        bool conf = false;
+        if (b < A.B) {
+          const int64_t at = (int64_t)i * A.B + b;
+          double rb = one_tile ? r0 : ((A.incl[b] != 0 && A.group[b] != ign) ? A.r[b] : NAN);
+          if (A.act[at] == 0) rb = NAN;
+          const double dx = sm.pos[0] - A.pos[at], dy = sm.pos[1] - A.pos[(int64_t)A.n_steps * A.B + at];
+          double d2 = (dx * dx) + dy * dy;
+          if (D == 3) {
+            const double dz = sm.pos[D - 1] - A.pos[(int64_t)(D - 1) * A.n_steps * A.B + at];
+            d2 = d2 + dz * dz;
+          }
+          const double rr = rq + rb;
+          conf = d2 < rr * rr;  // (a NaN on either side compares false)
+        }
+        const unsigned long long bal = __ballot(conf);
+        if (bal) {
+          key = ((long long)i << 32) | (long long)(b0 + (__ffsll((long long)bal) - 1));
+          break;
+        }
+      }
+    }
+  }
+  if (lane != 0) return;
+  const bool blocked = horizon || key != kNoHit;
+  if (X.hit) X.hit[id] = blocked ? (horizon ? -2LL : key) : -1LL;
+  if (blocked) {
+    R.bad[id] = 1;  // (OR: the edge pass, an earlier launch, may have set it already)
+    if (X.n_blocked) atomicAdd(X.n_blocked, 1ull);
+  }
+}
+
+template <int D>
+hipError_t reserve_dim(int order, const ReplanTimedArgs &a, dim3 grid, hipStream_t s) {
+  const dim3 block(kBlock);
+  switch (order) {
+    case 1: hipLaunchKernelGGL((replan_reserve_kernel<D, 1>), grid, block, 0, s, a); break;
+    case 2: hipLaunchKernelGGL((replan_reserve_kernel<D, 2>), grid, block, 0, s, a); break;
+    case 3: hipLaunchKernelGGL((replan_reserve_kernel<D, 3>), grid, block, 0, s, a); break;
+    case 4: hipLaunchKernelGGL((replan_reserve_kernel<D, 4>), grid, block, 0, s, a); break;
+    default: return hipErrorInvalidValue;
+  }
+  return hipGetLastError();
+}
+
+// the passes after the bad-edge bytes are final: init, resolve, apply, scan, emit
+hipError_t rebase_tail(const ReplanArgs &a, int passes, dim3 per_node, dim3 per_tile, hipStream_t s) {
+  const dim3 block(kBlock);
   hipLaunchKernelGGL(replan_init_kernel, per_node, block, 0, s, a);
   for (int k = 0; k < passes; k++) hipLaunchKernelGGL(replan_resolve_kernel, per_node, block, 0, s, a, k & 1);
   hipLaunchKernelGGL(replan_apply_kernel, per_tile, block, 0, s, a, passes & 1);
@@ -244,6 +383,43 @@ hipError_t launch_replan_rebase(int dim, int control, const ReplanArgs &a, int p
   if (hipError_t e = launch_table_scan_frontier(t, s)) return e;
   hipLaunchKernelGGL(replan_emit_kernel, per_tile, block, 0, s, a);
   return hipGetLastError();
+}
+
+}  // namespace
+
+hipError_t launch_replan_rebase(int dim, int control, const ReplanArgs &a, int passes, hipStream_t s) {
+  const int64_t n = a.n_bound > 0 ? a.n_bound : 1;
+  const dim3 per_node((unsigned)((n + kBlock - 1) / kBlock)), per_tile((unsigned)a.n_tiles);
+  if (hipError_t e = hipMemsetAsync(a.counters, 0, sizeof(ReplanResult), s)) return e;
+  if (a.check_edges) {
+    hipError_t e = dim == 2 ? edge_dim<2, false>(control, a, per_node, s) : dim == 3 ? edge_dim<3, false>(control, a, per_node, s) : hipErrorInvalidValue;
+    if (e != hipSuccess) return e;
+  }
+  return rebase_tail(a, passes, per_node, per_tile, s);
+}
+
+// The edge pass writes bad[id] for every id (or, without check_edges, a memset clears it); the reservation pass, the
+// next launch, ORs into it; the init pass then reads the union.
+hipError_t launch_replan_rebase_timed(int dim, int control, const ReplanTimedArgs &a, int passes, hipStream_t s) {
+  const ReplanArgs &r = a.R;
+  const int64_t n = r.n_bound > 0 ? r.n_bound : 1;
+  const dim3 per_node((unsigned)((n + kBlock - 1) / kBlock)), per_tile((unsigned)r.n_tiles);
+  if (dim != 2 && dim != 3) return hipErrorInvalidValue;
+  if (hipError_t e = hipMemsetAsync(r.counters, 0, sizeof(ReplanResult), s)) return e;
+  if (r.check_edges) {
+    if (hipError_t e = dim == 2 ? edge_dim<2, true>(control, a, per_node, s) : edge_dim<3, true>(control, a, per_node, s)) return e;
+  } else if (a.use_res) {
+    if (hipError_t e = hipMemsetAsync(r.bad, 0, (size_t)n, s)) return e;
+  }
+  if (a.use_res) {
+    const int ctl = control & 0x0f;
+    const int order = ctl == 0x01 ? 1 : ctl == 0x03 ? 2 : ctl == 0x07 ? 3 : ctl == 0x0f ? 4 : 0;
+    const dim3 grid((unsigned)((n + kResNodes - 1) / kResNodes));
+    if (hipError_t e = dim == 2 ? reserve_dim<2>(order, a, grid, s) : reserve_dim<3>(order, a, grid, s)) return e;
+  }
+  ReplanArgs t = r;
+  t.check_edges = (r.check_edges || a.use_res) ? 1 : 0;  // the init pass reads bad[]
+  return rebase_tail(t, passes, per_node, per_tile, s);
 }
 
 }  // namespace mplx

@@ -116,6 +116,24 @@ int check_traj(mplx_reserve *r, mplx_ctx *ctx, const char *who, const mplx_traj_
 
 }  // namespace
 
+int mplx_detail::reserve_table_args(mplx_reserve *r, const char *who, mplx_ctx **c, mplx::ReserveArgs *a) {
+  *c = r->c;
+  if (!r->filled) return fail(r->c, MPLX_ERR_STATE, "%s: the reservation table has not been filled", who);
+  if (r->Q < 1) return fail(r->c, MPLX_ERR_STATE, "%s: mplx_reserve_set_queries has not been called", who);
+  const char *b = (const char *)r->mem.p, *qb = (const char *)r->queries.p;
+  a->pos = (const double *)(b + r->o_pos); a->act = (const uint8_t *)(b + r->o_act); a->incl = (const uint8_t *)(b + r->o_incl);
+  a->r = (const double *)(b + r->o_r); a->group = (const int32_t *)(b + r->o_g);
+  a->B = r->B; a->n_steps = r->n_steps; a->step = r->step;
+  a->q_t0 = (const double *)(qb + r->q_t0); a->q_r = (const double *)(qb + r->q_r); a->q_ignore = (const int32_t *)(qb + r->q_ign);
+  a->Q = r->Q;
+  mplx_ctx *x = r->c;
+  a->U = (const double *)x->U.p; a->nU = x->nU; a->udim = x->udim;
+  a->dt = x->prm.dt;
+  const double scan = std::ceil(x->prm.dt / r->step) + 3.0;  // as mplx_reserve_check_device
+  a->n_scan = scan < 2147483647.0 ? (int32_t)scan : 0x7fffffff;
+  return MPLX_OK;
+}
+
 extern "C" {
 
 int mplx_reserve_create(mplx_ctx *c, mplx_reserve **out) {

@@ -132,10 +132,11 @@ int table_open_args(mplx_table *t, const char *who, mplx_ctx **c, mplx::OpenArgs
 
 void table_observe(mplx_table *t) { observe(t); }
 
-int table_replan_args(mplx_table *t, const char *who, bool scratch, mplx_ctx **c, mplx::ReplanArgs *a) {
+int table_replan_args(mplx_table *t, const char *who, bool scratch, mplx_ctx **c, mplx::ReplanArgs *a, int32_t *time_keys) {
   *c = t->c;
   if (int rc = usable(t, who)) return rc;
-  if (t->time_keys) return fail(t->c, MPLX_ERR_STATE, "%s: the table has time keys (mplx_table_set_time_keys): it cannot be rebased", who);
+  if (time_keys) *time_keys = t->time_keys ? 1 : 0;
+  else if (t->time_keys) return fail(t->c, MPLX_ERR_STATE, "%s: the table has time keys (mplx_table_set_time_keys): it cannot be rebased (mplx_table_rebase_timed_device can)", who);
   a->n_queries = t->Q;
   a->n_bound = t->bound;
   if (!scratch) return MPLX_OK;

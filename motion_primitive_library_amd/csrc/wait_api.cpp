@@ -9,8 +9,10 @@ namespace {
 
 constexpr int64_t kMaxEntries = 0x7ffffffeLL;  // as the node table's relax
 
+}  // namespace
+
 // the smallest row of the control table whose every entry is == 0.0 (-0.0 counts), or -1
-int32_t zero_action(const mplx_ctx *c) {
+int32_t mplx_detail::zero_action(const mplx_ctx *c) {
   for (int32_t a = 0; a < c->nU; a++) {
     bool zero = true;
     for (int32_t j = 0; j < c->udim && zero; j++) zero = c->h_U[(size_t)a * c->udim + j] == 0.0;
@@ -18,8 +20,6 @@ int32_t zero_action(const mplx_ctx *c) {
   }
   return -1;
 }
-
-}  // namespace
 
 extern "C" int mplx_lists_add_wait_device(mplx_ctx *c, const mplx_succ_lists *L, int64_t n_nodes, const double *d_parent_state,
                                           int64_t parent_stride, const int32_t *d_parent_id, int64_t *d_n_added) {

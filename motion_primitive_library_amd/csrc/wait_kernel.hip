@@ -47,19 +47,11 @@ __global__ __launch_bounds__(kBlock) void lists_add_wait_kernel(const WaitArgs W
       valid = P.heading_valid(nullptr, 0, cos(A.yaw_max), A.yaw.margin, A.yaw.tie_yaw, &amb);
     }
     valid = P.limits_valid(A, valid);
-    bool same_pos = true;
-#pragma unroll
-    for (int i = 0; i < D; i++) same_pos = same_pos && (P.cpos[i] == P.npos[i]);
     const int cnt = W.count[k];
-    if (P.h_next == P.h_curr && valid && same_pos && cnt >= 0 && (int64_t)cnt < W.S) {
+    if (P.wait_eligible(valid) && cnt >= 0 && (int64_t)cnt < W.S) {
       const int64_t e = k * W.S + cnt;
-      // env_map.h:164-165 with a traversal cost of 0 (Pair::classify's expression)
-      double J = 0;
-#pragma unroll
-      for (int i = 0; i < D; i++) J += P.ax[i].effort(A.dt);
-      const double c = 0;
       W.action[e] = W.a0;
-      W.cost[e] = c + (J + A.w * A.dt);
+      W.cost[e] = P.wait_cost(A);  // env_map.h:164-165 with a traversal cost of 0
       if (W.hash) W.hash[e] = P.h_next;
       if (W.state) {
         double *o = W.state + e;

@@ -2361,7 +2361,7 @@ class EnvMap:
         have t = 0), has `radius` and ignores the reservations of ignore_group (-1: none).  time_keys (default: on with
         avoid, else off): a node is a (lattice state, time) pair (mplx_table_set_time_keys) -- what waiting for a moving
         obstacle to pass needs.  Without avoid and time keys the search issues exactly the calls it always did.  A
-        result of a search with avoid or time keys cannot replan().
+        result of a search with avoid or time keys replans with replan_timed() (include/mplx_replan_timed.h), not replan().
         wait=True (needs time keys, else ValueError): every round appends the wait edge -- the all-zero control from a
         state it leaves where it is, which the expansion drops -- to its lists before the check (include/mplx_wait.h).
         park_goal=True (needs avoid, else ValueError): after every push a goal-region node at which the robot could not

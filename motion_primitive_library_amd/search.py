@@ -647,7 +647,7 @@ def time_key(hashes, t):
 
 
 def plan_prioritised(env, starts, goal_rows, step, radius, order=None, delays=(0.0,), park=True, wait=False, park_goal=False,
-                     field=False, **search_kw):
+                     field=False, keep=False, **search_kw):
     """Prioritised planning of R robots on one map: robot r plans against the trajectories of the robots planned
     before it, as obstacles that move on the common clock of conflicts().  starts [4D+2][R] (t = 0 each), goal_rows
     [R][4D+2], radius a scalar or [R]; step: the clock's.  Robots are planned in `order` (default: the index, so a lower
@@ -660,7 +660,9 @@ def plan_prioritised(env, starts, goal_rows, step, radius, order=None, delays=(0
 
     Returns {"paths": [R] (start, actions) or None, "t0" [R], "status" [R] (of the winning candidate, else of
     candidate 0), "cost" [R] (g of the winner, inf), "conflicts": a final conflicts() over all chosen chains at `step`
-    with rank = the position in `order`}.
+    with rank = the position in `order`}.  keep=True: additionally "results" [R] -- each robot's MultiSearchResult, not
+    freed and owned by the caller (free() them) --, "winner" [R] (the winning candidate, -1 without one), and "order",
+    "n_steps" and "radius": what replan_prioritised continues with.  Without keep the function does what it always did.
 
     wait / park_goal go to search_many (EnvMap.search states them).  wait=True: standing still for one primitive is an
     edge (include/mplx_wait.h), so a robot can leave a lane, let another pass and go on, or stop short of a crossing;
@@ -674,7 +676,8 @@ def plan_prioritised(env, starts, goal_rows, step, radius, order=None, delays=(0
     searches with its own for every delay candidate.
 
     Its limits: a robot that finds no path is reported and not reserved.  Protection holds to the table's horizon
-    (`n_steps`) only.  An earlier robot is never re-planned when a later one cannot avoid it.  A chain with waits is not
+    (`n_steps`) only.  An earlier robot is never re-planned when a later one cannot avoid it (replan_prioritised replans every robot,
+    in the same order, after the world has changed).  A chain with waits is not
     what rollout() / MapPlanner.checkTraj accept (they stop at a wait with SKIP_SAME), and smooth() / shortcut() of a
     path with repeated chain states are not covered; traj_info / traj_sample / traj_traverse / conflicts take it as it
     is."""
@@ -690,6 +693,7 @@ def plan_prioritised(env, starts, goal_rows, step, radius, order=None, delays=(0
     if n_steps is None:
         n_steps = int(math.ceil((float(delays.max()) + 256 * dt) / float(step))) + 1
     paths, t0, status, cost = [None] * R, np.zeros(R), [None] * R, np.full(R, math.inf)
+    results, winner = [None] * R, [-1] * R
     planned = []
     res = None
     fld = None
@@ -720,18 +724,95 @@ def plan_prioritised(env, starts, goal_rows, step, radius, order=None, delays=(0
                 if best is not None:
                     paths[r], t0[r], cost[r] = best[2], float(delays[best[1]]), out.cost[best[1]]
                     planned.append(r)
+                    winner[r] = best[1]
+                if keep:
+                    results[r], out = out, None
             finally:
-                out.free()
+                if out is not None:
+                    out.free()
+    except Exception:
+        for o in results:
+            if o is not None:
+                o.free()
+        raise
     finally:
         if res is not None:
             res.free()
-        if fld is not None:
+        if fld is not None and not keep:  # (kept results go on searching with it: the caller frees it, plan["field"])
             fld.free()
     rank = np.zeros(R, np.int32)
     rank[order] = np.arange(len(order), dtype=np.int32)
     st, ac = _path_set(env, paths)
     final = env.traj_conflicts(st, ac, step, t0=t0, radius=rad, rank=rank, park=park)
-    return {"paths": paths, "t0": t0, "status": status, "cost": cost, "conflicts": final}
+    out = {"paths": paths, "t0": t0, "status": status, "cost": cost, "conflicts": final}
+    if keep:
+        out.update({"results": results, "winner": winner, "order": order, "n_steps": n_steps, "radius": rad.copy(), "field": fld})
+    return out
+
+
+def replan_prioritised(env, plan, now, step, radius=None, order=None, park=True, n_steps=None):
+    """Replans a fleet that plan_prioritised(..., keep=True) planned, at time `now` of the common clock, after robots
+    have moved, the map was edited or both: every robot, in the plan's order, runs replan_timed on its own table
+    against the CURRENT plans of the robots before it.  Robot r finishes the primitive it is in: its root is chain state
+    k_r = clip(ceil((now - t0_r) / dt), 0, len) of its full_path(); its t0 does not change.  The reservation table is
+    refilled from the full_path()s of the robots already replanned, with their t0.  Of a robot's delay candidates only
+    the winner is replanned; every loser gets a root that is out of range, which keeps nothing of it (it ends EMPTY).
+    A robot without a path is reported (its old status) and skipped.  radius / order / n_steps default to the plan's.
+
+    Returns the dict of plan_prioritised(keep=True) -- paths are full_path()s from the original starts, "results" the
+    new MultiSearchResults (the plan's own entries are consumed: use the returned ones, and free() them) -- plus
+    "rebase" [R]: the rebase result of each robot with "n_blocked", or None.
+
+    plan["results"] is updated IN PLACE, entry by entry, as the robots are replanned (a replan consumes the result it
+    is called on): if a later robot's replan raises, the plan still holds every live result -- the new ones of the
+    robots already replanned, the old ones of the rest -- and the caller can free them or call again.
+
+    Its limits: one table per robot stays allocated between calls.  The priority order is not revised: a robot is never
+    asked to yield to one behind it.  A robot whose replan finds no path is not reserved, as in plan_prioritised, AND
+    IS SKIPPED BY EVERY LATER CALL: its result has no path to advance along, so it stays where the failed replan left it
+    until the caller plans it anew.  A plan made with field=True cannot be replanned after a map edit: its results
+    search with the plan's GoalField (plan["field"], the caller's to free), which the edit makes stale, and replan_timed
+    then raises RuntimeError as replan() does for a caller's stale field.  After a map edit such a fleet is planned anew."""
+    results, winner, t0 = plan["results"], list(plan["winner"]), np.array(plan["t0"], dtype=np.float64)
+    R = len(results)
+    order = list(plan["order"]) if order is None else [int(r) for r in order]
+    rad = np.broadcast_to(np.asarray(plan["radius"] if radius is None else radius, dtype=np.float64), (R,))
+    n_steps = int(plan["n_steps"] if n_steps is None else n_steps)
+    dt = float(env._p.dt)
+    paths, status, cost, rebase = [None] * R, list(plan["status"]), np.full(R, math.inf), [None] * R
+    planned = []
+    res = None
+    try:
+        for r in order:
+            old, q = results[r], winner[r]
+            if old is None or q < 0 or not old.found[q]:
+                continue
+            done = getattr(old, "_executed", None)
+            n_done = 0 if done is None or done[q] is None else len(done[q][1])
+            ids = old.table.path(old.goal_id[q])[0]
+            k = int(min(max(math.ceil((float(now) - t0[r]) / dt), 0), n_done + len(ids) - 1))
+            roots = [old.table.capacity] * old.n_queries  # (out of range: nothing of a loser is kept)
+            roots[q] = int(ids[max(k - n_done, 0)])
+            st, ac = _path_set(env, [paths[j] for j in planned])
+            fill = ((st, ac), step, n_steps, t0[planned], rad[planned] if planned else 0.0, None, park)
+            if res is None:
+                res = Reservations(env, *fill)
+            else:
+                res.fill(*fill)
+            new = old.replan_timed(avoid=res, roots=roots)
+            results[r], rebase[r], status[r] = new, new.rebase_info, new.status[q]
+            if new.found[q]:
+                paths[r], cost[r] = new.full_path(q), new.cost[q]
+                planned.append(r)
+    finally:
+        if res is not None:
+            res.free()
+    rank = np.zeros(R, np.int32)
+    rank[order] = np.arange(len(order), dtype=np.int32)
+    st, ac = _path_set(env, paths)
+    final = env.traj_conflicts(st, ac, step, t0=t0, radius=rad, rank=rank, park=park)
+    return {"paths": paths, "t0": t0, "status": status, "cost": cost, "conflicts": final, "results": results, "winner": winner,
+            "order": order, "n_steps": n_steps, "radius": rad.copy(), "field": plan.get("field"), "rebase": rebase}
 
 
 class SearchResult:
@@ -799,6 +880,38 @@ class SearchResult:
             root = int(self.table.path(self.goal_id)[0][int(advance)])
         return run_replan(self, False, [-1 if root is None else int(root)], goal_row, check_edges, None if prior is None else [prior])
 
+    def replan_timed(self, avoid=None, root=None, advance=None, goal_row=None, check_edges=True):
+        """replan() for a search that ran with time keys and / or among reservations (include/mplx_replan_timed.h;
+        DESIGN.md 4.22).  The robot's clock does not move: g and t go on being measured from the original start and the
+        t0 the search ran with stays, so t0 + t is still the common clock of conflicts() and the time keys of the kept
+        nodes are still right.  avoid: the Reservations as they are NOW (the same object refilled, or another one);
+        required iff the search ran with avoid.  Its queries are set again from the t0, radius and ignore_group of the
+        search.  A kept edge must still hold on the map (check_edges), a wait edge by the wait's own rule, and must
+        keep clear of the reservations; the kept nodes are pushed closed, vetoed where the robot could not stay
+        (park_goal) and expanded once in a forced round with the waits, the check and the veto of the search.  A
+        search without time keys and without avoid is refused with ValueError: replan() is for it.  root / advance /
+        goal_row and the handling of priors and fields: as replan().  Returns a new SearchResult that owns the table
+        and the open set; its path() starts at the root, whose t is not 0 -- full_path() is the chain from the original
+        start."""
+        if self.table is None or self._params is None:
+            raise RuntimeError("replan_timed: this result does not own a table (it was replanned or freed)")
+        _need_timed(self._params, avoid)
+        if root is not None and advance is not None:
+            raise ValueError("replan_timed: give root or advance, not both")
+        if advance is not None:
+            if not self.found:
+                raise RuntimeError("replan_timed: advance needs a path (status %s)" % STATUS_NAMES[self.status])
+            root = int(self.table.path(self.goal_id)[0][int(advance)])
+        return run_replan(self, False, [-1 if root is None else int(root)], goal_row, check_edges, None, True, avoid)
+
+    def full_path(self):
+        """(start_state, actions) from the ORIGINAL start (t = 0): the actions executed up to the root of every
+        replan_timed so far, then those of path().  This is the chain conflicts() and a reservation fill take with the
+        robot's unchanged t0; for a result that was never replanned it is path().  The positions the check computed
+        along it and those of traj_sample agree bit for bit: both evaluate the segment of (chain state, control) at the
+        local time tl_i - t of that state."""
+        return _full_path(self, None)
+
     def free(self):
         if self.open is not None:
             self.open.free()
@@ -813,10 +926,28 @@ class SearchResult:
         return "SearchResult(%s, cost=%r, rounds=%d, expanded=%d)" % (STATUS_NAMES[self.status], self.cost, self.rounds, self.expanded)
 
 
+def _need_timed(prm, avoid):
+    if not (prm.get("avoid") or prm.get("time_keys")):
+        raise ValueError("replan_timed: the search ran without time keys and without avoid: use replan")
+    if prm.get("avoid") and avoid is None:
+        raise ValueError("replan_timed: the search ran with avoid: give the Reservations as they are now")
+    if avoid is not None and not prm.get("avoid"):
+        raise ValueError("replan_timed: the search ran without avoid (no t0 / radius to check with)")
+
+
+def _full_path(result, q):
+    start, act = result.path() if q is None else result.path(q)
+    done = getattr(result, "_executed", None)
+    done = None if done is None else done[0 if q is None else q]
+    if done is None:
+        return start, act
+    return done[0].copy(), np.concatenate([done[1], act]).astype(np.int32)
+
+
 def _no_replan(prm):
     if prm.get("avoid") or prm.get("time_keys"):
-        raise RuntimeError("replan: the search ran among reservations or with time keys; replanning such a table is not "
-                           "built (include/mplx_replan.h)")
+        raise RuntimeError("replan: the search ran among reservations or with time keys: use replan_timed "
+                           "(include/mplx_replan_timed.h)")
 
 
 def _avoid_setup(who, avoid, time_keys, starts, Q, t0, radius, ignore_group, tab, prm, wait=False, park_goal=False):
@@ -834,9 +965,11 @@ def _avoid_setup(who, avoid, time_keys, starts, Q, t0, radius, ignore_group, tab
             raise ValueError("%s: avoid needs a radius" % who)
         if np.any(np.asarray(starts)[-1] != 0.0):
             raise ValueError("%s: with avoid a start state must have t = 0 (the robot's clock is t0 + t)" % who)
-        avoid.set_queries(np.broadcast_to(np.asarray(t0, dtype=np.float64), (Q,)),
-                          np.broadcast_to(np.asarray(radius, dtype=np.float64), (Q,)),
-                          np.broadcast_to(np.asarray(ignore_group, dtype=np.int32), (Q,)))
+        # (kept for replan_timed, which sets the queries of its reservation table again)
+        prm["t0"] = np.array(np.broadcast_to(np.asarray(t0, dtype=np.float64), (Q,)))
+        prm["radius"] = np.array(np.broadcast_to(np.asarray(radius, dtype=np.float64), (Q,)))
+        prm["ignore_group"] = np.array(np.broadcast_to(np.asarray(ignore_group, dtype=np.int32), (Q,)))
+        avoid.set_queries(prm["t0"], prm["radius"], prm["ignore_group"])
     if time_keys:
         tab.set_time_keys(True)
 
@@ -1039,6 +1172,29 @@ class MultiSearchResult:
             r = [int(self.table.path(self.goal_id[q])[0][int(ks[q])]) if self.found[q] else -1 for q in range(Q)]
         return run_replan(self, True, r, goal_rows, check_edges, priors)
 
+    def replan_timed(self, avoid=None, roots=None, advance=None, goal_rows=None, check_edges=True):
+        """SearchResult.replan_timed for Q queries at once: roots [Q] (node ids; -1 or None: that query's seed; an id
+        that is out of range keeps nothing of the query, which then ends EMPTY), or advance (one k for all or [Q]; a
+        query without a path keeps its seed), goal_rows [Q][4D+2] or None.  Returns a new MultiSearchResult that owns
+        the table and the open set; this one no longer does."""
+        if self.table is None or self._params is None:
+            raise RuntimeError("replan_timed: this result does not own a table (it was replanned or freed)")
+        _need_timed(self._params, avoid)
+        if roots is not None and advance is not None:
+            raise ValueError("replan_timed: give roots or advance, not both")
+        Q = self.n_queries
+        r = [-1] * Q
+        if roots is not None:
+            r = [-1 if x is None else int(x) for x in np.broadcast_to(np.asarray(roots, dtype=object), (Q,))]
+        if advance is not None:
+            ks = np.broadcast_to(np.asarray(advance, dtype=np.int64), (Q,))
+            r = [int(self.table.path(self.goal_id[q])[0][int(ks[q])]) if self.found[q] else -1 for q in range(Q)]
+        return run_replan(self, True, r, goal_rows, check_edges, None, True, avoid)
+
+    def full_path(self, q):
+        """SearchResult.full_path of query q."""
+        return _full_path(self, q)
+
     def free(self):
         if self.open is not None:
             self.open.free()
@@ -1111,12 +1267,35 @@ def run_search_many(env, starts, goal_rows, eps, delta, g_max, max_rounds, max_e
                 b.free()
 
 
-def run_replan(old, multi, roots, goal_rows, check_edges, priors=None):
+def _executed(old, tab, roots):
+    """Per query (original start state, actions executed so far), or None: what `old` holds, extended by the chain from
+    the table's current root to the new one -- taken before the rebase cuts it."""
+    Q = len(roots)
+    before = getattr(old, "_executed", None) or [None] * Q
+    n = tab.stats()[0]
+    out = []
+    for q, r in enumerate(roots):
+        done = before[q]
+        if 0 <= r < n:
+            ids, act = tab.path(r)
+            if done is None:
+                done = (tab.state_of(ids[0]), np.zeros(0, np.int32))
+            done = (done[0], np.concatenate([done[1], act]).astype(np.int32))
+        out.append(done)
+    return out
+
+
+def run_replan(old, multi, roots, goal_rows, check_edges, priors=None, timed=False, avoid=None):
     """SearchResult.replan / MultiSearchResult.replan: rebase into a frontier of the table's capacity, clear the open
     set, push the kept nodes closed, expand all of them in chunks of max_frontier rows (the forced round), then the
-    loop of the search.  The forced chunks count as rounds and expansions."""
+    loop of the search.  The forced chunks count as rounds and expansions.  timed: replan_timed -- the rebase is
+    rebase_timed against `avoid`, and the forced round runs the waits, the check and the park veto of the search's
+    rounds; without it the calls are those of replan."""
     env, prm, tab, opn = old._env, old._params, old.table, old.open
-    who = "replan"
+    who = "replan_timed" if timed else "replan"
+    wait, park = timed and bool(prm.get("wait")), timed and bool(prm.get("park_goal")) and avoid is not None
+    if timed and avoid is not None:
+        avoid.set_queries(prm["t0"], prm["radius"], prm["ignore_group"])
     env._flush()
     eps, g_max, sight, fcap, capacity = prm["eps"], prm["g_max"], prm["sight"], prm["fcap"], prm["capacity"]
     Q = tab.n_queries
@@ -1152,12 +1331,18 @@ def run_replan(old, multi, roots, goal_rows, check_edges, priors=None):
     try:
         kept, sel, imp = TableFrontier(env, capacity), TableFrontier(env, fcap), TableFrontier(env, capacity)
         lists = env.alloc_lists(fcap, want_state=True, stride=prm["lists_stride"])
-        info = tab.rebase(roots=roots, check_edges=check_edges, frontier=kept) if multi else \
-            tab.rebase(root=roots[0], check_edges=check_edges, frontier=kept)
+        if timed:
+            executed = _executed(old, tab, roots)
+            info = tab.rebase_timed(roots, check_edges=check_edges, allow_wait=wait, avoid=avoid, frontier=kept)
+        else:
+            info = tab.rebase(roots=roots, check_edges=check_edges, frontier=kept) if multi else \
+                tab.rebase(root=roots[0], check_edges=check_edges, frontier=kept)
         _table_check(tab, who, "after the rebase")
         n_kept = info["n_kept"]
         opn.clear()
         opn.push(kept, n_max=n_kept, eps=eps, sight=sight, closed=True)
+        if park:
+            avoid.park(opn, kept, n_kept)
         rounds, expanded = [0] * Q, [0] * Q
         query = None
         if multi and n_kept:  # whose the kept rows are: the forced chunks are counted per query
@@ -1168,8 +1353,14 @@ def run_replan(old, multi, roots, goal_rows, check_edges, priors=None):
             n = min(fcap, n_kept - first)
             rows = kept.rows(first, n)
             env.expand_lists_resident(rows, lists, n_nodes=n)
+            if wait:
+                _add_waits(env, avoid, rows, lists, n)
+            if timed and avoid is not None:
+                avoid.check(rows, lists, n, table=tab)
             tab.relax(lists, rows.id, rows.g, g_max, frontier=imp, n_nodes=n, want_count=False)
             opn.push(imp, n_max=n * lists.stride, eps=eps, sight=sight)
+            if park:
+                avoid.park(opn, imp, n * lists.stride)
             total += 1
             if query is None:
                 rounds[0] += 1
@@ -1180,12 +1371,15 @@ def run_replan(old, multi, roots, goal_rows, check_edges, priors=None):
                     if per[q]:
                         rounds[q] += 1
                         expanded[q] += int(per[q])
-        status, res, total = _search_loop(env, who, multi, tab, opn, sel, imp, lists, prm, total, rounds, expanded)
+        status, res, total = _search_loop(env, who, multi, tab, opn, sel, imp, lists, prm, total, rounds, expanded,
+                                          avoid if timed else None)
         if multi:
             new = MultiSearchResult(status, res, tab, opn, rounds, expanded, total, env, prm)
         else:
             new = SearchResult(status[0], res[0], tab, opn, total, expanded[0], env, prm)
         new.rebase_info = info
+        if timed:
+            new._executed = executed
         _hand_field(new, old)
         old.table = old.open = None  # the new result owns them
         return new

@@ -204,6 +204,51 @@ class NodeTable:
             return None
         return {"n_kept": int(r.n_kept), "n_bad_edges": int(r.n_bad_edges), "n_roots": int(r.n_roots)}
 
+    def rebase_timed(self, roots, check_edges=True, allow_wait=False, avoid=None, frontier=None, want_hit=False, want_result=True):
+        """mplx_table_rebase_timed_device (include/mplx_replan_timed.h): rebase(roots=) for a table with time keys, wait
+        edges and reservations.  roots: one root per query ([Q] or one for all; -1 = that query's seeds).  An edge is bad
+        as rebase() has it -- the identity test on the time key where the table has time keys, a wait edge held by the
+        wait's eligibility and cost if allow_wait, bad otherwise -- or, with avoid (a Reservations, filled and with its
+        queries set), if it comes too close to a reservation or leaves the table's horizon.  Returns {"n_kept",
+        "n_bad_edges", "n_roots"}, with avoid also "n_blocked", with want_hit also "hit" (int64 [n_nodes]: the smallest
+        (i << 32 | b) of the edge's conflicts, -2 for the horizon, -1) (one synchronisation); None with
+        want_result=False -- the call is then asynchronous."""
+        if frontier is None:
+            raise ValueError("rebase_timed needs a frontier to write (EnvMap.alloc_table_frontier)")
+        if want_hit and not want_result:
+            raise ValueError("rebase_timed: want_hit needs want_result")
+        self._env._flush()
+        f = frontier.c_struct()
+        r = _abi.RebaseResult()
+        h = np.ascontiguousarray(np.broadcast_to(np.asarray(roots, dtype=np.int32), (self.n_queries,)))
+        if self._roots is None:
+            self._roots = DeviceArray(self._env, 4 * self.n_queries)
+        self._roots.upload(h)
+        hit = blocked = None
+        try:
+            if avoid is not None and want_result:
+                blocked = DeviceArray(self._env, 8)
+                blocked.upload(np.zeros(1, np.int64))
+                if want_hit:
+                    hit = DeviceArray(self._env, 8 * self.capacity)
+            self._check(_abi.lib().mplx_table_rebase_timed_device(
+                self._tab, self._roots.ptr, 1 if check_edges else 0, 1 if allow_wait else 0, None if avoid is None else avoid._res,
+                C.byref(f), None if hit is None else hit.ptr, None if blocked is None else blocked.ptr, None,
+                C.byref(r) if want_result else None))
+            if not want_result:
+                return None
+            out = {"n_kept": int(r.n_kept), "n_bad_edges": int(r.n_bad_edges), "n_roots": int(r.n_roots)}
+            if blocked is not None:
+                out["n_blocked"] = int(blocked.download(np.int64, (1,))[0])
+            if want_hit:
+                n = self.stats()[0]
+                out["hit"] = hit.download(np.int64, (self.capacity,))[:n].copy() if hit is not None else np.full(n, -1, np.int64)
+            return out
+        finally:
+            for b in (hit, blocked):
+                if b is not None:
+                    b.free()
+
     def find(self, hashes, query=None):
         """Node id of every hash (with query: of every (query, hash) pair; [n] or one for all), -1 for one the table
         does not hold."""
