@@ -48,7 +48,7 @@ def leaves_horizon(step, n_steps, t0, tc):
 
 
 def primitive_pos(p, v, a, j, u, order, t):
-    """Position of the forward primitive of control order 1 .. 3 from (p, v, a, j) under input u at time t, per axis:
+    """Position of the forward primitive of control order 1 .. 4 from (p, v, a, j) under input u at time t, per axis:
     traj::eval_segment without c0, operation for operation."""
     p, v, a, j, u, t = (np.asarray(x, dtype=F) for x in (p, v, a, j, u, t))
     z = np.zeros_like(p)
@@ -59,6 +59,8 @@ def primitive_pos(p, v, a, j, u, order, t):
         c4, c3 = v, u
     elif order == 3:
         c4, c3, c2 = v, a, u
+    elif order == 4:
+        c4, c3, c2, c1 = v, a, j, u
     else:
         raise ValueError(order)
     t3 = (t * t) * t

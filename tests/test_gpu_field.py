@@ -4,6 +4,7 @@ the plain search's optimal costs, and the search that uses it (search / search_m
 import numpy as np
 import pytest
 
+import control_matrix as CM
 import field_model as FM
 
 pytestmark = pytest.mark.gpu
@@ -320,6 +321,10 @@ def push_rows(D, dims, res, goals, n_fields, yaw, order, foq):
             is_goal = j == len(pts) - 7
             if order >= 2 and not is_goal:
                 s[D:2 * D] = rng.choice([-0.5, 0.0, 0.5], size=D)
+            if order >= 3 and not is_goal:
+                s[2 * D:3 * D] = rng.choice([-0.5, 0.0, 0.25], size=D)
+            if order >= 4 and not is_goal:
+                s[3 * D:4 * D] = rng.choice([-0.3, 0.0, 0.6], size=D)
             if yaw and not is_goal:
                 s[4 * D] = rng.choice([0.0, 0.1, -0.2])
             cols.append(s)
@@ -328,13 +333,14 @@ def push_rows(D, dims, res, goals, n_fields, yaw, order, foq):
 
 
 PUSH_CASES = [(2, "VEL", 1), (2, "ACC", 3), (2, "ACCxYAW", 3), (3, "VEL", 3), (3, "ACC", 1), (3, "ACCxYAW", 1)]
+PUSH_CASES = PUSH_CASES + CM.PUSH_ADDED  # SNP and JRKxYAW: rows with live acc and jerk (tests/control_matrix.py)
 
 
 @pytest.mark.parametrize("D,control,Q", PUSH_CASES, ids=["%dd-%s-Q%d" % c for c in PUSH_CASES])
 def test_push_equals_the_model(engine, D, control, Q):
     m = engine
     yaw = control.endswith("YAW")
-    order = 1 if control == "VEL" else 2
+    order = CM.order_of(control)
     dims, res, cells = push_world(D)
     W, VMAX = 10.0, 2.0
     env = map_env(m, dims, cells, res=res, control=getattr(m, control), vals=(-0.5, 0.0, 0.5), v_max=VMAX, yaw=yaw)

@@ -8,10 +8,11 @@ import math
 import numpy as np
 import pytest
 
+import control_matrix as CM
 import multi_model as MM
 import open_model as OM
-from helpers import engine_env
-from table_model import EMPTY, F2, TableModel
+from helpers import engine_env, oracle_env
+from table_model import EMPTY, F2, TableModel, oracle_provider
 from test_gpu_open import (assert_open_equal, assert_result_equal, assert_spare_untouched, corridor_env, patterned_frontier,
                            rest_env, small_world_goal, upload_frontier, _goals)
 from test_gpu_parity import _small_world
@@ -181,10 +182,15 @@ def wall_in(wl, pos):
 WORLDS = {(2, 0x03, 56.0, 32), (3, 0x07, 46.0, 64)}
 
 
+# 2D SNP from live acc and jerk rows (tests/control_matrix.py) -> per third query: the statuses and total rounds of
+# tests/multi_model.py on the oracle's lists
+SNP_MODEL = {"inside": ([OM.FOUND, OM.FOUND, OM.FOUND], 4), "walled": ([OM.FOUND, OM.FOUND, OM.EMPTY], 11)}
+
+
 @pytest.mark.parametrize("third", ["inside", "walled"])
-@pytest.mark.parametrize("world", sorted(WORLDS))
+@pytest.mark.parametrize("world", sorted(WORLDS) + [pytest.param(CM.SNP_WORLD, id="2d-snp")])
 def test_search_round_by_round(engine, oracle_lib, world, third):
-    """2D ACC and 3D JRK, Q = 3, with the ray trace, every round compared.  Queries 0 and 1 cross (q0's start is q1's
+    """2D ACC, 3D JRK and 2D SNP, Q = 3, with the ray trace, every round compared.  Queries 0 and 1 cross (q0's start is q1's
     goal and the other way round).  Query 2 either starts inside its own goal region -- FOUND at the first select and
     the same result in every later round -- or aims at a goal that is walled in: EMPTY while the others go on."""
     m, O = engine, oracle_lib
@@ -204,9 +210,19 @@ def test_search_round_by_round(engine, oracle_lib, world, third):
         wall_in(wl, goals[2, :dim])
     env = engine_env(m, wl)
     table, model, hashes = world_model(O, wl, dim, control, env, starts, goals, wl.res)
+    if world not in WORLDS:  # the pinned numbers are the model's on the oracle: held before the device runs
+        t2, m2, _ = world_model(O, wl, dim, control, env, starts, goals, wl.res)
+        out = MM.search_many(t2, m2, oracle_provider(O, oracle_env(wl)), starts, hashes, 1.0, 5.0, 8192, g_max, True)
+        closed = sum(1 for fl in m2.flags.values() if fl & OM.SEEN and not fl & OM.IS_OPEN)
+        print("model on the oracle:", world, third, out["status"], out["total_rounds"], "closed", closed, "nodes", t2.n_nodes)
+        assert (out["status"], out["total_rounds"]) == SNP_MODEL[third] and out["total_rounds"] >= 3
+        assert closed >= 1 and 100 <= t2.n_nodes <= 20000
     tab, opn, got, rounds, history = device_search_many(m, env, table, model, starts, hashes, 1.0, 5.0, 8192, g_max, True, 10 ** 6)
     print(world, third, rounds, [r["status"] for r in got], table.n_nodes)
-    # (the way back ends at rest at q0's start: within g_max the 2D ACC world reaches it, the 3D JRK world does not)
+    if world not in WORLDS:
+        assert ([r["status"] for r in got], rounds) == SNP_MODEL[third]
+    # (the way back ends at rest at q0's start: within g_max the 2D ACC world reaches it, the 3D JRK world does not; in
+    # the 2D SNP world it does)
     assert got[0]["status"] == OM.FOUND and got[1]["status"] == (OM.FOUND if dim == 2 else OM.EMPTY) and rounds >= 3
     if third == "inside":
         assert all(h[2]["status"] == OM.FOUND and h[2] == history[0][2] for h in history)
@@ -334,15 +350,25 @@ def test_more_queries_than_lanes(engine, oracle_lib):
 
 
 def test_four_rounds_with_yaw_controls(engine, oracle_lib):
-    m, O = engine, oracle_lib
-    wl = _small_world(m, 2, 0x13, seed=5, edge=32)
+    four_rounds_with_yaw(engine, oracle_lib, 0x13)
+
+
+def test_four_rounds_with_jrk_yaw_controls(engine, oracle_lib):
+    """The JRKxYAW twin, from a live acc row."""
+    four_rounds_with_yaw(engine, oracle_lib, 0x17, live=True)
+
+
+def four_rounds_with_yaw(m, O, control, live=False):
+    wl = _small_world(m, 2, control, seed=5, edge=32)
     start = small_start(wl)
+    if live:
+        start = np.array(CM.live_start(start, 2, control))
     starts = np.stack([start, start], axis=1)
     goals = np.zeros((2, 10))
     goals[0, :2] = start[:2] + [1.2, -0.8]
     goals[1, :2] = start[:2] + [-0.9, 0.7]
     env = engine_env(m, wl)
-    table, model, hashes = world_model(O, wl, 2, 0x13, env, starts, goals, wl.res)
+    table, model, hashes = world_model(O, wl, 2, control, env, starts, goals, wl.res)
     tab, opn, got, rounds, _ = device_search_many(m, env, table, model, starts, hashes, 1.0, 2.0, 8192, math.inf, True, 4)
     assert rounds == 4 and table.n_nodes > 60 and [r["status"] for r in got] == [OM.SELECTED] * 2
     opn.free()

@@ -7,6 +7,7 @@ import math
 import numpy as np
 import pytest
 
+import control_matrix as CM
 import open_model as OM
 from helpers import engine_env, oracle_env
 from table_model import TableModel, oracle_provider, sweep
@@ -230,6 +231,8 @@ def small_world_goal(m, O, dim, control, g_max, edge):
     model sweep bounded by g_max."""
     wl = _small_world(m, dim, control, seed=5, edge=edge)
     start = small_start(wl)
+    if control & 0x08:  # the SNP worlds start with live acc and jerk rows
+        start = np.array(CM.live_start(start, dim, control))
     h0 = O.lattice_hash(dim, control, start)
     t = TableModel(4 * dim + 2)
     sweep(t, oracle_provider(O, oracle_env(wl)), start, [h0], g_max=g_max)
@@ -243,13 +246,41 @@ def small_world_goal(m, O, dim, control, g_max, edge):
 # lists: the rounds of the issue's prototype)
 WORLDS = {(2, 0x03, 56.0, 32): {(1.0, 0.0, 8192): (95, 0), (1.0, 5.0, 16): (16, 13), (3.0, 5.0, 8192): (4, 0)},
           (3, 0x07, 46.0, 64): {(1.0, 0.0, 8192): (45, 0), (1.0, 5.0, 16): (15, 13), (3.0, 5.0, 8192): (4, 0)}}
+OLD_WORLDS = sorted(WORLDS)
+WORLDS[CM.SNP_WORLD] = CM.SNP_WORLD_ROUNDS  # 2D SNP from live acc and jerk rows (tests/control_matrix.py)
 _goals = {}
 
 
+def model_search_on_oracle(O, wl, dim, control, start, h0, goal, eps, delta, cap, g_max, w, v_max, max_rounds=10 ** 6):
+    """The loop of device_search on the models alone, fed with the oracle's lists (no GPU).  Returns (status, rounds,
+    truncated selections, closed nodes at the end, re-opened nodes, nodes)."""
+    provider = oracle_provider(O, oracle_env(wl))
+    table = TableModel(4 * dim + 2)
+    model = OM.OpenModel(table, dim, goal, O.lattice_hash(dim, control, goal), w, v_max, tol_pos=wl.res,
+                         blocked=OM.ray_blocked(wl.grid, wl.map_dim, wl.origin, wl.res, goal[:dim]))
+    imp, _ = table.seed(start, [h0])
+    model.push(imp, imp["count"], eps, True)
+    rounds = truncated = reopened = 0
+    while True:
+        got, sel = model.select(delta, cap)
+        n = got["count"]
+        if got["status"] != OM.SELECTED or rounds >= max_rounds:
+            break
+        truncated += n == cap and any(fl & OM.IS_OPEN and model.f[i] <= got["f_min"] + delta for i, fl in model.flags.items())
+        lists = provider(sel["state"])
+        imp, _ = table.relax(lists, sel["id"], sel["g"], g_max)
+        reopened += sum(1 for i in imp["id"] if int(i) in model.flags and not model.flags[int(i)] & OM.IS_OPEN)
+        model.push(imp, n * int(lists["stride"]), eps, True)
+        rounds += 1
+    closed = sum(1 for fl in model.flags.values() if fl & OM.SEEN and not fl & OM.IS_OPEN)
+    return got["status"], rounds, truncated, closed, reopened, table.n_nodes
+
+
 @pytest.mark.parametrize("case", [(1.0, 0.0, 8192), (1.0, 5.0, 16), (3.0, 5.0, 8192)])
-@pytest.mark.parametrize("world", sorted(WORLDS))
+@pytest.mark.parametrize("world", OLD_WORLDS + [pytest.param(CM.SNP_WORLD, id="2d-snp")])
 def test_search_round_by_round(engine, oracle_lib, world, case):
-    """2D ACC and 3D JRK to FOUND, with the ray trace, every round compared; the rounds are the model's on the oracle."""
+    """2D ACC, 3D JRK and 2D SNP to FOUND, with the ray trace, every round compared; the rounds are the model's on the
+    oracle."""
     m, O = engine, oracle_lib
     dim, control, g_max, edge = world
     eps, delta, cap = case
@@ -261,6 +292,12 @@ def test_search_round_by_round(engine, oracle_lib, world, case):
     table = TableModel(4 * dim + 2)
     model = OM.OpenModel(table, dim, goal, O.lattice_hash(dim, control, goal), env._p.w, env._p.v_max, tol_pos=wl.res,
                          blocked=OM.ray_blocked(wl.grid, wl.map_dim, wl.origin, wl.res, goal[:dim]))
+    if world not in OLD_WORLDS:  # the pinned numbers are the model's on the oracle: held before the device runs
+        status, n_rounds, n_trunc, closed, reopened, nodes = model_search_on_oracle(
+            O, wl, dim, control, start, h0, goal, eps, delta, cap, g_max, env._p.w, env._p.v_max)
+        print("model on the oracle:", world, case, status, n_rounds, n_trunc, "closed", closed, "re-opened", reopened, "nodes", nodes)
+        assert status == OM.FOUND and (n_rounds, n_trunc) == WORLDS[world][case] and n_rounds >= 3
+        assert closed + reopened >= 1 and 100 <= nodes <= 20000
     tab, opn, got, rounds, truncated = device_search(m, env, table, model, start, h0, eps, delta, cap, g_max, True, 10 ** 6)
     print(world, case, rounds, truncated, got)
     assert got["status"] == OM.FOUND and (rounds, truncated) == WORLDS[world][case]
@@ -272,24 +309,35 @@ def test_search_round_by_round(engine, oracle_lib, world, case):
     env.close()
 
 
-def test_four_rounds_with_yaw_controls(engine, oracle_lib):
-    m, O = engine, oracle_lib
-    wl = _small_world(m, 2, 0x13, seed=5, edge=32)
+def four_rounds_with_yaw(m, O, control, live=False):
+    wl = _small_world(m, 2, control, seed=5, edge=32)
     start = small_start(wl)
+    if live:
+        start = np.array(CM.live_start(start, 2, control))
     goal = np.zeros(10)
     goal[:2] = start[:2] + [1.2, -0.8]
     env = engine_env(m, wl)
     env.set_goal(goal, tol_pos=wl.res)
     table = TableModel(10)
-    model = OM.OpenModel(table, 2, goal, O.lattice_hash(2, 0x13, goal), env._p.w, env._p.v_max, tol_pos=wl.res,
+    model = OM.OpenModel(table, 2, goal, O.lattice_hash(2, control, goal), env._p.w, env._p.v_max, tol_pos=wl.res,
                          blocked=OM.ray_blocked(wl.grid, wl.map_dim, wl.origin, wl.res, goal[:2]))
-    tab, opn, got, rounds, _ = device_search(m, env, table, model, start, O.lattice_hash(2, 0x13, start), 1.0, 2.0, 8192,
+    tab, opn, got, rounds, _ = device_search(m, env, table, model, start, O.lattice_hash(2, control, start), 1.0, 2.0, 8192,
                                              math.inf, True, 4)
     assert rounds == 4 and table.n_nodes > 30 and got["status"] == OM.SELECTED
     assert_table_equal(tab, table)
     opn.free()
     tab.free()
     env.close()
+
+
+def test_four_rounds_with_yaw_controls(engine, oracle_lib):
+    four_rounds_with_yaw(engine, oracle_lib, 0x13)
+
+
+def test_four_rounds_with_jrk_yaw_controls(engine, oracle_lib):
+    """The JRKxYAW twin, from a live acc row: the seed's hash folds it and K = 3 with a heading limit runs the relax and
+    the push."""
+    four_rounds_with_yaw(engine, oracle_lib, 0x17, live=True)
 
 
 def corridor_env(m, cells=None):

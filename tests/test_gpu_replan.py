@@ -8,12 +8,13 @@ import math
 import numpy as np
 import pytest
 
+import control_matrix as CM
 import multi_model as MM
 import open_model as OM
 import replan_model as RM
 from helpers import engine_env
 from table_model import TableModel, oracle_provider
-from test_gpu_open import (WORLDS, assert_open_equal, assert_spare_untouched, corridor_env, patterned_frontier, rest_env,
+from test_gpu_open import (OLD_WORLDS, assert_open_equal, assert_spare_untouched, corridor_env, patterned_frontier, rest_env,
                            small_world_goal)
 from test_gpu_parity import _small_world
 from test_gpu_table import assert_frontier_equal, bits
@@ -118,7 +119,7 @@ def rebase_both(m, env, tab, d0, edges_of, nU, what, root=-1, roots=None, check_
 
 
 # ---- 1. rebase against the model on the two small worlds
-@pytest.mark.parametrize("world_key", sorted(WORLDS))
+@pytest.mark.parametrize("world_key", OLD_WORLDS + [pytest.param(CM.SNP_WORLD, id="2d-snp"), pytest.param(CM.SNP_WORLD_3D, id="3d-snp")])
 def test_rebase_against_the_model(engine, oracle_lib, world_key):
     m, O = engine, oracle_lib
     dim, control, g_max, edge = world_key
@@ -392,17 +393,27 @@ def test_replan_many_end_to_end(engine):
 YAW_GOAL = (0.75, -1.25)  # from the start; reachable under the heading limit (three edges on the unedited map)
 
 
-def yaw_world(m):
-    wl = _small_world(m, 2, 0x13, seed=5, edge=32)
+def yaw_world(m, control=0x13, live=False):
+    wl = _small_world(m, 2, control, seed=5, edge=32)
     start = small_start(wl)
+    if live:
+        start = np.array(CM.live_start(start, 2, control))
     goal = np.zeros(10)
     goal[:2] = start[:2] + YAW_GOAL
     return wl, start, goal
 
 
 def test_yaw_controls(engine, oracle_lib):
-    m, O = engine, oracle_lib
-    wl, start, goal = yaw_world(m)
+    yaw_controls(engine, oracle_lib, 0x13, False)
+
+
+def test_yaw_controls_jrk(engine, oracle_lib):
+    """The JRKxYAW twin, from a live acc row: replan_edge_kernel<2, 3, true, false>."""
+    yaw_controls(engine, oracle_lib, 0x17, True)
+
+
+def yaw_controls(m, O, control, live):
+    wl, start, goal = yaw_world(m, control, live)
     far = np.zeros(10)
     far[:2] = start[:2] + [1.2, -0.8]  # (the goal of test_four_rounds_with_yaw_controls: not reached in four rounds)
     env = engine_env(m, wl)

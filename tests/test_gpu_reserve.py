@@ -4,10 +4,12 @@ search.plan_prioritised), on the device, against tests/reserve_model.py, tests/t
 import ctypes as C
 import math
 import os
+from fractions import Fraction
 
 import numpy as np
 import pytest
 
+import control_matrix as CM
 import reserve_model as RM
 from table_model import TableModel, hand_case
 from test_gpu_open import corridor_env
@@ -51,7 +53,7 @@ def reserved_chains(rng, dim, F, nU, B, H):
     return starts, actions
 
 
-NINE = [-1.0, -0.75, -0.5, -0.25, 0.0, 0.25, 0.5, 0.75, 1.0]
+NINE = CM.NINE
 # (dim, control, axis values, yaw, S, B, park, step, Q, lanes); lanes: another split of a wave between a row's entries and
 # slices of the reservations than the automatic one -- the same bytes
 CASES = [
@@ -66,6 +68,28 @@ CASES = [
 ]
 IDS = ["2d-acc-S9-B15", "2d-acc-81of96-B70-gone", "3d-vel-B257-Q3", "2d-yaw-B1-gone", "3d-acc-B70-Q3", "2d-vel-S9-B257-gone",
        "S9-all-lanes-on-entries", "81of96-eight-lanes-on-entries"]
+# K = 3, K = 4 and the yaw flags (tests/control_matrix.py): parents with live acc and jerk rows
+CASES = CASES + CM.RESERVE_ADDED
+IDS = IDS + CM.RESERVE_ADDED_IDS
+MIN_SENSITIVE = 10  # looked-at entries whose hit a zeroed acc (K >= 3) or jerk (K = 4) row has to change
+
+
+def exact_positions(pst, U, act, times, dim, order):
+    """p + v s + a s^2/2 + j s^3/6 + u s^4/24 without the terms past the order (the control takes the place of the first
+    row the order does not hold), in exact rationals from the same doubles.  pst [4D+2][E], act [E], times [E][C].
+    Returns (positions [D][E][C] as Fractions, sum of the terms' magnitudes [D][E][C])."""
+    E, Cn = times.shape
+    fact = [1, 1, 2, 6, 24]
+    pos = np.empty((dim, E, Cn), dtype=object)
+    mag = np.empty((dim, E, Cn), dtype=object)
+    for e in range(E):
+        for d in range(dim):
+            coef = [Fraction(float(pst[k * dim + d, e])) for k in range(order)] + [Fraction(float(U[act[e]][d]))]
+            for c in range(Cn):
+                sx = Fraction(float(times[e, c]))
+                terms = [coef[k] * sx ** k / fact[k] for k in range(order + 1)]
+                pos[d, e, c], mag[d, e, c] = sum(terms), sum(abs(t) for t in terms)
+    return pos, mag
 
 
 @pytest.mark.parametrize("dim,control,vals,yaw,S,B,park,step,Q,lanes", CASES, ids=IDS)
@@ -114,9 +138,15 @@ def test_check_equals_the_model(engine, dim, control, vals, yaw, S, B, park, ste
     # ---- parents and lists
     pst = np.zeros((F, n_alloc))
     pst[:dim, :n] = rng.uniform(2.0, 6.0, size=(dim, n))
-    order = {"VEL": 1, "ACC": 2, "ACCxYAW": 2}[control]
+    order = CM.order_of(control)
     if order >= 2:
         pst[dim:2 * dim, :n] = rng.uniform(-0.5, 0.5, size=(dim, n))
+    # (the check applies no dynamic limits: within dt = 1 an acc of 1.5 moves an edge by up to 0.75 m and a jerk of 3 by up
+    # to 0.5 m, against pair radii of about 0.2 .. 0.8 m)
+    if order >= 3:
+        pst[2 * dim:3 * dim, :n] = rng.uniform(-1.5, 1.5, size=(dim, n))
+    if order >= 4:
+        pst[3 * dim:4 * dim, :n] = rng.uniform(-3.0, 3.0, size=(dim, n))
     pst[F - 1, :n] = (np.arange(n) % 7) * dt  # differing parent times; tp = 6: past the horizon
     count = rng.integers(0, min(S, nU) + 1, size=n_alloc).astype(np.int32)
     count[:3] = [min(S, nU), 0, 1]
@@ -160,6 +190,30 @@ def test_check_equals_the_model(engine, dim, control, vals, yaw, S, B, park, ste
 
     want_cost, want_hit, want_nb, looked = RM.check(count[:n], action[:n * S], cost[:n * S], S, parent_id, pst[F - 1, :n], dt, nU,
                                                     step, n_steps, table, (q_t0, q_r, q_ign), edge_pos, row_query)
+    if order >= 3:
+        # ---- the sampler at this order against the polynomial in exact rationals: 2^-50 * sum |term| (five terms of at
+        # most four rounded operations each, four rounded additions)
+        rows = np.nonzero(looked)[0]
+        exact, mag = exact_positions(e_starts[:, rows], np.asarray(U), e_act[rows], times[rows], dim, order)
+        worst = Fraction(0)
+        for d in range(dim):
+            for r, e in enumerate(rows):
+                for c in range(times.shape[1]):
+                    err = abs(Fraction(float(smp[d, e, c])) - exact[d, r, c])
+                    assert err <= mag[d, r, c] / 2 ** 50, (d, e, c, float(err), float(mag[d, r, c]))
+                    worst = max(worst, err / mag[d, r, c] if mag[d, r, c] else worst)
+        print("sampler vs exact polynomial, order %d: %d entries, worst error %.3g of sum |term|" % (order, len(rows), float(worst)))
+        # ---- the higher-order rows decide hits: with them zeroed in the sampler's parents, entries change their hit
+        for name, lo in (("acc", 2 * dim),) + ((("jrk", 3 * dim),) if order >= 4 else ()):
+            z_starts = e_starts.copy()
+            z_starts[lo:lo + dim] = 0.0
+            z_smp = env.traj_sample(z_starts, e_act.reshape(1, -1), times=times)["samples"]
+            z_pos = lambda k, j, i, s_: z_smp[:dim, k * S + j, int(np.nonzero(inst[k] == i)[0][0])]
+            _, z_hit, _, z_looked = RM.check(count[:n], action[:n * S], cost[:n * S], S, parent_id, pst[F - 1, :n], dt, nU,
+                                             step, n_steps, table, (q_t0, q_r, q_ign), z_pos, row_query)
+            changed = int((z_hit[looked] != want_hit[looked]).sum())
+            print("%s rows zeroed: %d of %d looked-at entries change their hit" % (name, changed, looked.sum()))
+            assert np.array_equal(z_looked, looked) and changed >= MIN_SENSITIVE, (name, changed)
     res.check(fr, L, n, table=tab, hit=d_hit, n_blocked=d_nb)
     env.synchronize()
     got_hit, got_cost = d_hit.download(np.int64, (N,)), L.cost.download(np.float64, (N,))

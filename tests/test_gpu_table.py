@@ -7,6 +7,8 @@ import math
 import numpy as np
 import pytest
 
+import control_matrix as CM
+import prior_model
 from helpers import engine_env, oracle_env
 from table_model import EMPTY, F2, TableModel, dijkstra, hand_case, hand_lists, oracle_provider, sweep
 from test_gpu_parity import _small_world
@@ -242,14 +244,28 @@ def device_sweep(m, env, model, start, h0, g_max, max_rounds, capacity, fcap):
     return tab, rounds
 
 
-@pytest.mark.parametrize("dim,control,g_max,max_rounds,edge", [(2, 0x03, 56.0, 99, 32), (3, 0x07, 46.0, 99, 64), (2, 0x13, math.inf, 4, 32)])
+@pytest.mark.parametrize("dim,control,g_max,max_rounds,edge", [(2, 0x03, 56.0, 99, 32), (3, 0x07, 46.0, 99, 64), (2, 0x13, math.inf, 4, 32)] +
+                         [pytest.param(*c[1:], id=c[0]) for c in CM.SWEEP_ADDED])
 def test_sweeps_round_by_round(engine, oracle_lib, dim, control, g_max, max_rounds, edge):
     """2D ACC (six rounds, six candidates per node) and 3D JRK (five rounds; a 3.2 m map ends every third step outside)
-    to the fixed point inside g_max, and four rounds of 2D ACC x YAW."""
+    to the fixed point inside g_max, and four rounds of 2D ACC x YAW.  The cases of tests/control_matrix.py: 2D and 3D SNP
+    to the fixed point, four rounds of 2D JRK x YAW, 3D VEL x YAW and 2D SNP x YAW, all from a start whose acc and jerk rows
+    are live where the order has them."""
     m, O = engine, oracle_lib
     wl = _small_world(m, dim, control, seed=5, edge=edge)
-    env = engine_env(m, wl)
     start = small_start(wl)
+    added = [c for c in CM.SWEEP_ADDED if c[1:] == (dim, control, g_max, max_rounds, edge)]
+    if added:
+        start = np.array(CM.live_start(start, dim, control))
+        # the choice of g_max and the map edge, on the model fed with the oracle's lists, before the device runs
+        probe = TableModel(4 * dim + 2)
+        n_rounds, _ = sweep(probe, oracle_provider(O, oracle_env(wl)), start, [O.lattice_hash(dim, control, start)], g_max=g_max,
+                            max_rounds=max_rounds)
+        print("model on the oracle:", added[0][0], "rounds", n_rounds, "nodes", probe.n_nodes)
+        assert n_rounds >= 3 and 100 < probe.n_nodes <= 20000
+        if CM.SWEEP_MODEL[added[0][0]] is not None:
+            assert (n_rounds, probe.n_nodes) == CM.SWEEP_MODEL[added[0][0]]
+    env = engine_env(m, wl)
     h0 = O.lattice_hash(dim, control, start)
     model = TableModel(4 * dim + 2)
     tab, rounds = device_sweep(m, env, model, start, h0, g_max, max_rounds, capacity=1 << 15, fcap=1 << 13)
@@ -266,6 +282,56 @@ def test_sweeps_round_by_round(engine, oracle_lib, dim, control, g_max, max_roun
     with pytest.raises(m._abi.MplxError) as err:
         tab.path(last, cap=len(act) - 1)
     assert err.value.code == m._abi.ERR_ARG
+    tab.free()
+    env.close()
+
+
+def hash_states(dim, control, n=70):
+    """n states whose every row the hash of `control` folds is live: values across many bins, on the bins' edges (halves
+    round away from zero), negative and signed zeros."""
+    rng = np.random.default_rng(31 * dim + control)
+    s = np.zeros((4 * dim + 2, n))
+    s[:dim] = np.round(rng.uniform(-3.0, 9.0, size=(dim, n)), 3)
+    s[dim:4 * dim] = np.round(rng.uniform(-2.0, 2.0, size=(3 * dim, n)), 2)
+    s[4 * dim] = np.round(rng.uniform(-3.1, 3.1, size=n), 2)
+    s[:dim, 1], s[dim:4 * dim, 1], s[4 * dim, 1] = 0.005, 0.05, 0.05     # every row on a bin edge
+    s[:dim, 2], s[dim:4 * dim, 2], s[4 * dim, 2] = -0.015, -0.25, -0.15
+    s[:4 * dim + 1, 3] = -0.0
+    s[3 * dim:4 * dim, 4:10] = 0.1 * np.arange(1, 7)                      # one jerk bin apart, everything else as in column 4
+    s[:3 * dim, 5:10] = s[:3 * dim, 4:5]
+    s[4 * dim, 5:10] = s[4 * dim, 4]
+    s[4 * dim + 1] = np.arange(n) * 0.5
+    return s
+
+
+@pytest.mark.parametrize("dim,control", CM.PAIRS, ids=["%dd-%s" % (d, c.lower()) for d, c in CM.PAIRS])
+def test_seed_hashes_equal_the_oracle(engine, oracle_lib, dim, control):
+    """table_hash_kernel<D, K, YAW> for all 16 (dim, control): the hash column of seeded states against the oracle's
+    lattice hash and the restatement of tests/prior_model.py, state by state."""
+    m, O = engine, oracle_lib
+    flag = CM.FLAGS[control]
+    env = m.EnvMap(dim)
+    env.setMap([0.0] * dim, [8] * dim, np.zeros(8 ** dim, np.int8), 1.0)
+    env.set_control(flag)
+    env.set_u(m.workloads.grid_controls([-0.5, 0.0, 0.5], dim, yaw_rates=[-0.3, 0.0, 0.3]) if flag & 0x10 else
+              m.workloads.grid_controls([-0.5, 0.0, 0.5], dim))
+    env.set_dt(1.0)
+    states = hash_states(dim, flag)
+    n = states.shape[1]
+    want = np.array([O.lattice_hash(dim, flag, states[:, k]) for k in range(n)], dtype=np.uint64)
+    assert want.tolist() == [prior_model.lattice_hash(dim, flag, states[:, k]) for k in range(n)]
+    first = {}
+    for k, h in enumerate(want.tolist()):
+        first.setdefault(h, k)
+    # the jerk row decides at order 4 and only there: six states one jerk bin apart
+    assert len(set(want[4:10].tolist())) == (6 if CM.order_of(flag) == 4 else 1)
+    tab = env.alloc_table(256)
+    fr = m.TableFrontier(env, n)
+    assert tab.seed(states, frontier=fr) == len(first)  # a state whose hash an earlier one has is that node
+    got = tab.download()
+    assert got["n_nodes"] == len(first) and np.array_equal(got["hash"], want[sorted(first.values())])
+    assert np.array_equal(bits(got["state"]), bits(states[:, sorted(first.values())]))
+    fr.free()
     tab.free()
     env.close()
 

@@ -10,6 +10,7 @@ import math
 import numpy as np
 import pytest
 
+import control_matrix as CM
 import replan_model as RP
 import timed_replan_model as TR
 from test_gpu_open import assert_spare_untouched, patterned_frontier
@@ -67,12 +68,16 @@ def rebase_raw(m, env, tab, roots, check, allow_wait, res, fr):
 
 
 # ------------------------------------------------------------------------------------------------------ the worlds
-def controls(dim, control):
+def controls(dim, control, small=False):
+    """small: two values per axis and two yaw rates, 2^(dim + 1) controls -- so that a table of 65 nodes holds nodes two
+    edges deep although the equal keys of a round are expanded together."""
     axes = [THREE] * dim + ([(-0.3, 0.0, 0.3)] if control & YAW else [])
+    if small:
+        axes = [(0.0, 0.5)] * dim + ([(0.0, 0.3)] if control & YAW else [])
     return np.array(list(itertools.product(*axes)), dtype=np.float64)
 
 
-def world(m, O, dim, control):
+def world(m, O, dim, control, small=False, j_max=0.0, yaw_max=0.0):
     """A free map with a few blocked cells, the engine's EnvMap and the oracle's Env of the same world."""
     n = 24 if dim == 2 else 12
     dims = [n] * dim
@@ -81,7 +86,7 @@ def world(m, O, dim, control):
     grid[rng.choice(n ** dim, size=n, replace=False)] = 100
     for q in range(3):  # the starts of the queries stand on free cells
         grid[cell_index(dims, [0.0] * dim, 1.0, [n / 2 + 0.5 + 2.0 * q] + [n / 2 + 0.5] * (dim - 1))] = 0
-    U = controls(dim, control)
+    U = controls(dim, control, small)
     env = m.EnvMap(dim)
     env.setMap([0.0] * dim, dims, grid, 1.0)
     env.set_control(control)
@@ -89,30 +94,40 @@ def world(m, O, dim, control):
     env.set_v_max(1.0)
     env.set_a_max(1.0)
     env.set_dt(1.0)
+    if j_max > 0:
+        env.set_j_max(j_max)
+    if yaw_max > 0:
+        env.set_yaw_max(yaw_max)
     if control & YAW:
         env.set_wyaw(0.0)  # (the yaw term of the cost goes through the device's cos / sin: out of this comparison)
 
     def oenv(g):
+        more = dict(j_max=j_max) if j_max > 0 else {}
+        if yaw_max > 0:
+            more["yaw_max"] = yaw_max
         return O.Env(dim, control, U, g, dims, [0.0] * dim, 1.0, dt=1.0, w=float(env._p.w), wyaw=0.0 if control & YAW else 1.0,
-                     v_max=1.0, a_max=1.0)
-    cfg = TR.Config(dim, control, U, 1.0, float(env._p.w), (1.0, 1.0, 0.0, 0.0))
+                     v_max=1.0, a_max=1.0, **more)
+    cfg = TR.Config(dim, control, U, 1.0, float(env._p.w), (1.0, 1.0, j_max, yaw_max))
     return env, grid, dims, oenv, cfg
 
 
-def standing(m, env, dim, control, positions, H):
+def standing(m, env, dim, control, positions, H, small=False):
     """Chains that stand still: the zero action H times from rest at `positions` [B][D]."""
-    a0 = TR.WM.zero_action(controls(dim, control))
+    a0 = TR.WM.zero_action(controls(dim, control, small))
     starts = np.stack([m.Waypoint(dim, control, pos=list(p)).to_row() for p in positions], axis=1)
     return starts, np.full((H, len(positions)), a0, np.int32)
 
 
-def restore_all(m, tab, d):
-    """restore() and the t row of the states (what poked_table_classes alters besides g and pred)."""
+def restore_all(m, tab, d, jerk_rows=False):
+    """restore() and the t row of the states (what poked_table_classes alters besides g and pred); jerk_rows: and the
+    jerk rows, which it alters at order 4."""
     restore(m, tab, d)
     v, n = tab.view(), d["n_nodes"]
-    t = np.ascontiguousarray(d["state"][-1, :n])
-    m._abi.check(tab._env._ctx, m._abi.lib().mplx_memcpy_h2d(tab._env._ctx, int(v.state + 8 * (tab.n_fields - 1) * v.state_stride),
-                                                             t.ctypes.data, t.nbytes))
+    D = (tab.n_fields - 2) // 4
+    for f in [tab.n_fields - 1] + (list(range(3 * D, 4 * D)) if jerk_rows else []):
+        row = np.ascontiguousarray(d["state"][f, :n])
+        m._abi.check(tab._env._ctx, m._abi.lib().mplx_memcpy_h2d(tab._env._ctx, int(v.state + 8 * f * v.state_stride), row.ctypes.data,
+                                                                 row.nbytes))
 
 
 def is_wait_edge(T, cfg, i):
@@ -170,6 +185,57 @@ def poked_table_classes(m, O, env, tab, d0, Q, cfg, oenv, roots, wait, res, tabl
     fr.free()
 
 
+def poked_jerk_rows(m, O, env, tab, d0, Q, cfg, oenv, roots, wait, res, table, queries, n_steps, n0, name):
+    """Order 4: the jerk row of up to three parents moved by one hash bin, nothing else.  Edge by edge, the edges that held
+    and no longer do are exactly the children of those parents -- some of them by their key alone, on an edge the map and
+    the limits still accept --, and the rebase drops them as the model says.  The call is made without the reservation
+    table: in the small tables every edge is blocked or past the horizon, which would drop the children whatever the edge
+    kernel says of them."""
+    D = cfg.dim
+    T0 = TR.multi_table(d0, Q)
+    e0 = RP.OracleEdges(O, oenv, T0)
+    held = lambda T, e, i: not TR.edge_is_bad(T, i, e, cfg, True, wait)
+    edges = [i for i in range(n0) if 0 <= T0.pred[i] < n0 and math.isfinite(T0.g[i]) and i not in roots]
+    e0.prepare([T0.pred[i] for i in edges])
+    good = [i for i in edges if held(T0, e0, i)]
+    jerked = sorted(set(T0.pred[i] for i in good))[:3]
+    assert jerked, name
+    d1 = {k: (np.array(v, copy=True) if isinstance(v, np.ndarray) else v) for k, v in d0.items()}
+    d1["state"][3 * D, jerked] += 0.1
+    T1 = TR.multi_table(d1, Q)
+    e1 = RP.OracleEdges(O, oenv, T1)
+    e1.prepare([T1.pred[i] for i in edges])
+    children = [i for i in good if T0.pred[i] in jerked]
+    assert [i for i in good if not held(T1, e1, i)] == children and len(children) >= 2, (name, children)
+    by_key = []
+    for i in children:
+        if T0.pred_action[i] == cfg.a0 and is_wait_edge(T0, cfg, i):
+            continue
+        st, h, _ = e1(T0.pred[i], T0.pred_action[i])
+        if st == RP.SLOT_FINITE and TR.RM.time_key(h, float(np.float64(T1.state[T0.pred[i]][-1]) + np.float64(cfg.dt))) != T1.hash[i]:
+            by_key.append(i)
+    assert by_key, name + ": no child of a parent with an altered jerk row is dropped by its key alone"
+    restore_all(m, tab, d1, jerk_rows=True)
+    # (the same call on the unaltered table keeps them: what drops them is the moved jerk row)
+    Tk = TR.multi_table(d0, Q)
+    TR.rebase_timed(Tk, e0, cfg, roots, True, wait, True, None, queries, n_steps)
+    kept_before = [i for i in children if math.isfinite(Tk.g[i])]
+    assert kept_before, name
+    want_fr, want, want_hit, want_nb, status = TR.rebase_timed(T1, e1, cfg, roots, True, wait, True, None, queries, n_steps)
+    assert status == 0 and all(math.isinf(T1.g[i]) for i in children), name
+    fr = patterned_frontier(m, env, d0["n_nodes"], 32)
+    rc, got, hit, nb, dres = rebase_raw(m, env, tab, roots, True, wait, None, fr)
+    what = name + " jerk rows of %s moved by one bin" % jerked
+    print(what, want, "children", len(children), "by key alone", len(by_key))
+    assert rc == 0 and got == want, "%s: %r != %r" % (what, got, want)
+    assert_frontier_equal(fr.download(), want_fr, what)
+    assert_rebased_equal(tab, T1, what)
+    assert want_hit is None and nb == want_nb == 0, what
+    assert_spare_untouched(fr, what)
+    fr.free()
+    restore_all(m, tab, d0, jerk_rows=True)
+
+
 # name, dim, control, Q, B, step, wait, n nodes, park (False: GONE, reservations end)
 CASES = [
     ("2d-acc-n1-B1", 2, ACC, 1, 1, 0.25, True, 1, True),
@@ -180,19 +246,23 @@ CASES = [
     ("2d-jrk-n4100-B64-Q3", 2, JRK, 3, 64, 0.25, True, 4100, True),
     ("3d-vel-n4100-B15-nowait", 3, VEL, 1, 15, 0.3, False, 4100, True),
 ]
+# SNP, the yaw flags and K = 3 in 3-D (tests/control_matrix.py)
+CASES = CASES + CM.TIMED_ADDED
 
 
 @pytest.mark.parametrize("name,dim,control,Q,B,step,wait,n_target,park", CASES, ids=[c[0] for c in CASES])
 def test_rebase_timed_equals_the_model(engine, oracle_lib, name, dim, control, Q, B, step, wait, n_target, park):
     m, O = engine, oracle_lib
-    env, grid, dims, oenv_of, cfg = world(m, O, dim, control)
+    small = name in CM.TIMED_SMALL_U
+    j_max, yaw_max = CM.TIMED_LIMITS.get(name, (0.0, 0.0))
+    env, grid, dims, oenv_of, cfg = world(m, O, dim, control, small, j_max, yaw_max)
     n = dims[0]
     rng = np.random.default_rng(len(name) + n_target)
     centre = np.full(dim, n / 2 + 0.5)
     starts = np.stack([m.Waypoint(dim, control, pos=list(centre + (np.arange(dim) == 0) * 2.0 * q)).to_row() for q in range(Q)], axis=1)
     goals = np.stack([m.Waypoint(dim, control, pos=[n - 1.5] * dim).to_row() for _ in range(Q)])
     q_t0, q_r, q_ign = [0.0, 0.5, 1.0][:Q], [0.2] * Q, [-1, 1, 2][:Q]
-    st, ac = standing(m, env, dim, control, [centre + 3.0, centre - 3.0], 3)
+    st, ac = standing(m, env, dim, control, [centre + 3.0, centre - 3.0], 3, small)
     res = m.search.Reservations(env, (st, ac), step, 200, None, 0.2, None, True)
     # ---- a time-keyed table of at most n_target nodes from a short search, padded to n_target with seeds
     # (delta = 0: a round expands one key's nodes, so the node count grows in small steps; the largest max_rounds whose
@@ -245,7 +315,7 @@ def test_rebase_timed_equals_the_model(engine, oracle_lib, name, dim, control, Q
     below = [i for i in range(n0) if dep[i] >= 1]
     where = [T0.state[i][:dim] for i in below[::max(len(below) // 6, 1)][:min(B, 6)]]
     where += [rng.uniform(1.0, n - 1.0, dim) for _ in range(B - len(where))]
-    st, ac = standing(m, env, dim, control, where, 8)
+    st, ac = standing(m, env, dim, control, where, 8, small)
     b_t0 = np.array([0.0] * min(B, 6) + [float(x) for x in rng.integers(0, 8, B - min(B, 6)) * 0.5])[:B]
     b_r = np.full(B, 0.2)
     b_r[4::5] = -1.0  # excluded (BAD_INPUT): they block nothing
@@ -299,6 +369,8 @@ def test_rebase_timed_equals_the_model(engine, oracle_lib, name, dim, control, Q
     else:
         assert all(seen.values()), (name, seen)
         poked_table_classes(m, O, env, tab, d0, Q, cfg, oenv, roots, wait, res, table, queries, n_steps, n0, name)
+        if cfg.K == 4:
+            poked_jerk_rows(m, O, env, tab, d0, Q, cfg, oenv, roots, wait, res, table, queries, n_steps, n0, name)
         # a frontier one row too small
         restore_all(m, tab, d0)
         T = TR.multi_table(d0, Q)

@@ -7,6 +7,7 @@ import math
 import numpy as np
 import pytest
 
+import control_matrix as CM
 import reserve_model as RM
 import wait_model as WM
 
@@ -49,8 +50,7 @@ def code(m, fn):
 
 
 # ------------------------------------------------------------------------------------------------------ add_wait
-NINE = [-1.0, -0.75, -0.5, -0.25, 0.0, 0.25, 0.5, 0.75, 1.0]
-THREE = [-0.5, 0.0, 0.5]
+NINE, THREE = CM.NINE, CM.THREE
 # (dim, control, axis values, yaw, nU, S)
 WAIT_CASES = [
     (2, "VEL", THREE, False, 9, 9),
@@ -64,13 +64,22 @@ WAIT_CASES = [
 ]
 WAIT_IDS = ["2d-vel-S9", "2d-acc-S9", "3d-acc-27of32", "2d-acc-81of96", "2d-yaw-27of32", "3d-jrk-27of32", "2d-jrk-81of96",
             "3d-vel-27of32"]
+# the other nine instantiations of lists_add_wait_kernel (tests/control_matrix.py): their parents carry live acc and jerk rows
+WAIT_CASES = WAIT_CASES + [(d, c, THREE, y, nU, S) for (d, c, y, nU, S) in CM.WAIT_ADDED]
+WAIT_IDS = WAIT_IDS + [CM.wait_id(*c) for c in CM.WAIT_ADDED]
 N_ROWS, N_ALLOC = 70, 72  # more than one wave of lanes; two rows behind n_nodes that no call may touch
+MIN_SENSITIVE = 5         # parents whose answer a zeroed acc (order >= 3) or jerk (order 4) row has to change
 
 
-def wait_inputs(rng, dim, order, yaw, F, nU, S):
+def wait_inputs(rng, dim, order, yaw, F, nU, S, live_rows=False):
     """70 parents of the kinds: at rest (eligible), moving, same hash with a moved position, too slow to move at all
     (eligible), and with yaw controls a velocity the heading limit refuses; counts with 0 and -- where S == nU -- S among
-    them; two rows with parent_id = -1."""
+    them; two rows with parent_id = -1.
+
+    live_rows (the added cases): eight parents at rest each become kind 5 (order >= 3: an acceleration inside the hash bin
+    of 0 that moves the position; not eligible), kind 6 (order 4: vel == acc == 0 and a jerk inside the hash bin of 0
+    that moves the position; not eligible) and kind 7 (order 4: a jerk of 1e-20, eligible, and the successor's vel, acc
+    and jrk rows carry it); half of the movers of order 4 carry a jerk as well."""
     n = N_ROWS
     pst = np.zeros((F, N_ALLOC))
     pst[:dim, :n] = np.round(rng.uniform(1.0, 7.0, size=(dim, n)), 2)
@@ -102,12 +111,58 @@ def wait_inputs(rng, dim, order, yaw, F, nU, S):
     if order == 1:  # a VEL state has no velocity and every parent is eligible: rows without a parent keep the share down
         parent_id[:n][rng.random(n) < 0.3] = -1
         parent_id[0] = 0
+    if live_rows and order >= 3:  # (after every draw of the cases above: their inputs are what they were)
+        rest = [k for k in np.nonzero(kind == 0)[0] if k >= 5 and parent_id[k] >= 0 and 0 < count[k] < S]  # (rows that are written)
+        assert len(rest) >= (24 if order >= 4 else 8), len(rest)
+        new_kinds = {5: (2 * dim, 0.004)}
+        if order >= 4:
+            new_kinds.update({6: (3 * dim, 0.004), 7: (3 * dim, 1e-20)})
+            jerked = (kind == 1) & (rng.random(n) < 0.5)
+            for k in np.nonzero(jerked)[0]:
+                pst[3 * dim + ax[k], k] = rng.choice([-0.5, 0.5])
+        for which, (row, value) in sorted(new_kinds.items()):
+            for k in rest[:8]:
+                kind[k] = which
+                pst[row + ax[k], k] = value
+            rest = rest[8:]
     return pst, kind, count, parent_id
 
 
-@pytest.mark.parametrize("dim,control,vals,yaw,nU,S", WAIT_CASES, ids=WAIT_IDS)
-def test_add_wait_equals_the_model(engine, dim, control, vals, yaw, nU, S):
-    m = engine
+def wait_sensitivity(pst, parent_id, count, dim, flag, U, w, yaw, goal, F, S):
+    """On the model alone: per parent, has the answer (eligibility, or any byte of its list row) changed with the acc
+    rows zeroed, and for order 4 with the jerk rows zeroed?  {row name: number of parents}."""
+    n, N, order = N_ROWS, N_ALLOC * S, WM.order_of(flag)
+
+    def answer(states):
+        host = {"stride": S, "count": count.copy(), "action": poison(np.int32, N), "cost": poison(np.float64, N),
+                "hash": poison(np.uint64, N), "state": poison(np.float64, F * N).reshape(F, N), "heur": poison(np.float64, N),
+                "flags": poison(np.uint8, N), "iters": poison(np.int32, N)}
+        _, eligible = WM.add_wait(host, n, states, parent_id, dim, flag, U, 1.0, w, 3.0, 3.0, 0.0, 0.5 if yaw else 0.0, goal)
+        rows = [b"".join(np.ascontiguousarray(host[key][..., k * S:(k + 1) * S]).tobytes() for key in
+                         ("action", "cost", "hash", "state", "heur", "flags", "iters")) + bytes([int(eligible[k])]) + host["count"][k].tobytes()
+                for k in range(n)]
+        return rows
+    base = answer(pst)
+    out = {}
+    for name, lo in (("acc", 2 * dim),) + ((("jrk", 3 * dim),) if order >= 4 else ()):
+        z = pst.copy()
+        z[lo:lo + dim] = 0.0
+        out[name] = sum(a != b for a, b in zip(base, answer(z)))
+    return out
+
+
+def eligible_of(pst, rows, dim, flag, U, yaw):
+    """The pair's three conditions for the parents `rows` (a mask), from the model."""
+    u0 = np.asarray(U)[WM.zero_action(U)]
+    out = []
+    for k in np.nonzero(rows)[0]:
+        p = WM.pair_eval(dim, flag, pst[:, k], u0, 1.0, 3.0, 3.0, 0.0, 0.5 if yaw else 0.0)
+        out.append(p["h_next"] == p["h_curr"] and p["valid"] and p["same_pos"])
+    return np.array(out, dtype=bool)
+
+
+def wait_case(m, dim, control, vals, yaw, nU, S, w=10.0):
+    """The inputs of one case, without a device: (U, flag, order, F, goal, pst, kind, count, parent_id, a0)."""
     rng = np.random.default_rng(7 * dim + S + len(control))
     U = m.workloads.grid_controls(vals, dim, yaw_rates=[-0.3, 0.0, 0.3]) if yaw else m.workloads.grid_controls(vals, dim)
     assert len(U) == nU
@@ -115,23 +170,45 @@ def test_add_wait_equals_the_model(engine, dim, control, vals, yaw, nU, S):
     U = np.ascontiguousarray(np.asarray(U)[perm])
     flag = getattr(m, control)
     order = WM.order_of(flag)
-    env = plain_env(m, dim, flag, U)
-    if yaw:
-        env.set_yaw_max(0.5)
-    F = env.n_fields
+    F = 4 * dim + 2
     goal_row = np.zeros(F)
     goal_row[:dim] = 4.0
-    env.set_goal(goal_row, w=10.0, v_max=3.0, tol_pos=1.5)
-    goal = dict(row=goal_row, hash=WM.lattice_hash(dim, flag, goal_row), w=10.0, v_max=3.0, tol_pos=1.5, tol_vel=-1.0, tol_acc=-1.0,
+    goal = dict(row=goal_row, hash=WM.lattice_hash(dim, flag, goal_row), w=w, v_max=3.0, tol_pos=1.5, tol_vel=-1.0, tol_acc=-1.0,
                 tol_yaw=-1.0)
-    pst, kind, count, parent_id = wait_inputs(rng, dim, order, yaw, F, nU, S)
+    added_case = (dim, control, yaw, nU, S) in CM.WAIT_ADDED  # (by the case, not the pair: JRK has old and added cases)
+    pst, kind, count, parent_id = wait_inputs(rng, dim, order, yaw, F, nU, S, live_rows=added_case)
     pst[:dim, 0] = 4.0  # one wait inside the goal region, on the goal's own lattice state
     if yaw:
         pst[4 * dim, 0] = 0.0
-    n, N = N_ROWS, N_ALLOC * S
     a0 = WM.zero_action(U)
-    assert a0 == int(np.nonzero(np.all(U == 0, axis=1))[0][0]) and env.nU == nU
+    assert a0 == int(np.nonzero(np.all(U == 0, axis=1))[0][0])
+    return U, flag, order, F, goal, pst, kind, count, parent_id, a0
 
+
+def assert_wait_case_is_sensitive(dim, control, yaw, nU, S, U, flag, order, F, goal, pst, kind, count, parent_id, w=10.0):
+    """The higher-order rows decide something: on the model alone (tests/test_control_matrix.py runs it without a device)."""
+    moved = wait_sensitivity(pst, parent_id, count, dim, flag, U, w, yaw, goal, F, S)
+    print("%dd %s: parents whose answer a zeroed row changes: %s" % (dim, control, moved))
+    if (dim, control, yaw, nU, S) in CM.WAIT_ADDED:  # (the two old JRK cases keep their inputs and only print; the -live ones assert)
+        assert all(v >= MIN_SENSITIVE for v in moved.values()), moved
+        assert (kind == 5).sum() == 8 and not eligible_of(pst, kind == 5, dim, flag, U, yaw).any()
+        if order >= 4:
+            assert not eligible_of(pst, kind == 6, dim, flag, U, yaw).any() and eligible_of(pst, kind == 7, dim, flag, U, yaw).all()
+    return moved
+
+
+@pytest.mark.parametrize("dim,control,vals,yaw,nU,S", WAIT_CASES, ids=WAIT_IDS)
+def test_add_wait_equals_the_model(engine, dim, control, vals, yaw, nU, S):
+    m = engine
+    U, flag, order, F, goal, pst, kind, count, parent_id, a0 = wait_case(m, dim, control, vals, yaw, nU, S)
+    if order >= 3:  # asserted before the device runs
+        assert_wait_case_is_sensitive(dim, control, yaw, nU, S, U, flag, order, F, goal, pst, kind, count, parent_id)
+    env = plain_env(m, dim, flag, U)
+    if yaw:
+        env.set_yaw_max(0.5)
+    assert F == env.n_fields and float(env._p.w) == goal["w"] and env.nU == nU
+    env.set_goal(goal["row"], w=10.0, v_max=3.0, tol_pos=1.5)
+    n, N = N_ROWS, N_ALLOC * S
     for full in (True, False):  # every row of the lists; then only count / action / cost
         host = {"stride": S, "count": count.copy(), "action": poison(np.int32, N), "cost": poison(np.float64, N)}
         if full:

@@ -81,7 +81,8 @@ def bad_edges(table, is_root, edge, cfg, time_keys, allow_wait):
 def edge_position(table, cfg, p, a, s):
     """traj::eval_segment (positions only) of the segment of (state[p], U[a]) at local time s."""
     st, D, z = table.state[p], cfg.dim, np.zeros(cfg.dim)
-    return RM.primitive_pos(st[:D], st[D:2 * D] if cfg.K >= 2 else z, st[2 * D:3 * D] if cfg.K >= 3 else z, z, cfg.U[a][:D], cfg.K, s)
+    return RM.primitive_pos(st[:D], st[D:2 * D] if cfg.K >= 2 else z, st[2 * D:3 * D] if cfg.K >= 3 else z,
+                            st[3 * D:4 * D] if cfg.K >= 4 else z, cfg.U[a][:D], cfg.K, s)
 
 
 def reserve_hits(table, is_root, cfg, res, queries, n_steps, edge_pos=None):
@@ -185,7 +186,8 @@ def timed_lists(provider, cfg, table, ids, states, wait, time_keys, res, queries
         def edge_pos(k, j, i, s):
             st, D, z = states[:, k], cfg.dim, np.zeros(cfg.dim)
             u = cfg.U[int(lists["action"][k * S + j])][:D]
-            return RM.primitive_pos(st[:D], st[D:2 * D] if cfg.K >= 2 else z, st[2 * D:3 * D] if cfg.K >= 3 else z, z, u, cfg.K, s)
+            return RM.primitive_pos(st[:D], st[D:2 * D] if cfg.K >= 2 else z, st[2 * D:3 * D] if cfg.K >= 3 else z,
+                                    st[3 * D:4 * D] if cfg.K >= 4 else z, u, cfg.K, s)
         lists["cost"] = RM.check(lists["count"], lists["action"], lists["cost"], S, np.zeros(n, np.int32), states[-1], cfg.dt, cfg.nU,
                                  res["step"], n_steps, res, queries, edge_pos, row_q)[0]
     if time_keys:

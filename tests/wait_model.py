@@ -2,7 +2,7 @@
 include/mplx_reserve.h (mplx_reserve_park_device), and the loop of EnvMap.search_many with both on tests/multi_model.py
 and tests/reserve_model.py.
 
-The pair arithmetic (primitive, successor state, lattice hashes, limits) is restated for control orders 1 .. 3 in Python
+The pair arithmetic (primitive, successor state, lattice hashes, limits) is restated for control orders 1 .. 4 in Python
 floats: IEEE doubles, one operation per operator, nothing contracted, in the order csrc/mplx_pair_device.h writes it.
 Test infrastructure: nothing shared with the engine."""
 import math
@@ -38,11 +38,11 @@ def wrap_angle(a):
 
 
 class Axis:
-    """pair::Axis<K> for K in 1 .. 3."""
+    """pair::Axis<K> for K in 1 .. 4."""
 
-    def __init__(self, K, p, v, a, u):
+    def __init__(self, K, p, v, a, u, j=0.0):
         self.K = K
-        self.c2 = self.c3 = self.c4 = 0.0
+        self.c1 = self.c2 = self.c3 = self.c4 = 0.0
         self.c5 = p
         if K == 1:
             self.c4 = u
@@ -50,9 +50,12 @@ class Axis:
             self.c4, self.c3 = v, u
         elif K == 3:
             self.c4, self.c3, self.c2 = v, a, u
+        elif K == 4:
+            self.c4, self.c3, self.c2, self.c1 = v, a, j, u
         else:
-            raise ValueError("the model covers VEL, ACC and JRK")
+            raise ValueError("the model covers VEL, ACC, JRK and SNP")
         self.c3_2, self.c2_6, self.c2_2 = self.c3 / 2, self.c2 / 6, self.c2 / 2
+        self.c1_24, self.c1_6, self.c1_2 = self.c1 / 24, self.c1 / 6, self.c1 / 2
         self.u = u
 
     def pos(self, t):  # EXACT
@@ -61,7 +64,10 @@ class Axis:
             return (0.0 + self.c4 * t) + self.c5
         if K == 2:
             return ((0.0 + (self.c3_2 * t) * t) + self.c4 * t) + self.c5
-        return (((0.0 + self.c2_6 * ((t * t) * t)) + (self.c3_2 * t) * t) + self.c4 * t) + self.c5
+        if K == 3:
+            return (((0.0 + self.c2_6 * ((t * t) * t)) + (self.c3_2 * t) * t) + self.c4 * t) + self.c5
+        t3 = (t * t) * t
+        return ((((0.0 + self.c1_24 * (t3 * t)) + self.c2_6 * t3) + (self.c3_2 * t) * t) + self.c4 * t) + self.c5
 
     def vel(self, t):  # EXACT (the forms without the leading 0.0 differ in the sign of a zero only)
         K = self.K
@@ -69,7 +75,9 @@ class Axis:
             return 0.0 + self.c4
         if K == 2:
             return (0.0 + self.c3 * t) + self.c4
-        return ((0.0 + (self.c2_2 * t) * t) + self.c3 * t) + self.c4
+        if K == 3:
+            return ((0.0 + (self.c2_2 * t) * t) + self.c3 * t) + self.c4
+        return (((0.0 + self.c1_6 * ((t * t) * t)) + (self.c2_2 * t) * t) + self.c3 * t) + self.c4
 
     def acc(self, t):
         K = self.K
@@ -77,21 +85,46 @@ class Axis:
             return 0.0
         if K == 2:
             return 0.0 + self.c3
-        return (0.0 + self.c2 * t) + self.c3
+        if K == 3:
+            return (0.0 + self.c2 * t) + self.c3
+        return ((0.0 + (self.c1_2 * t) * t) + self.c2 * t) + self.c3
 
     def jrk(self, t):
-        return 0.0 if self.K <= 2 else 0.0 + self.c2
+        if self.K <= 2:
+            return 0.0
+        return 0.0 + self.c2 if self.K == 3 else (0.0 + self.c1 * t) + self.c2
 
     def max_vel(self, T):
         m = max(abs(self.c4), abs(self.vel(T)))  # (v0 < vT ? vT : v0; NaNs do not occur in the tests)
-        if self.K == 3 and self.c2 != 0:
-            r = -self.c3 / self.c2
-            if 0 < r < T:
-                m = max(m, abs(self.vel(r)))
+        if self.K == 3 or (self.K == 4 and self.c1_2 == 0):
+            if self.c2 != 0:
+                r = -self.c3 / self.c2
+                if 0 < r < T:
+                    m = max(m, abs(self.vel(r)))
+        elif self.K == 4:  # the roots of v'(t) = c1/2 t^2 + c2 t + c3 in solver order; the scan stops at a root >= T
+            disc = self.c2 * self.c2 - 4 * self.c1_2 * self.c3
+            if not disc < 0:
+                sq = math.sqrt(disc)
+                r1, r2 = (-self.c2 - sq) / (2 * self.c1_2), (-self.c2 + sq) / (2 * self.c1_2)
+                go_on = True
+                if 0 < r1 < T:
+                    m = max(m, abs(self.vel(r1)))
+                elif r1 >= T:
+                    go_on = False
+                if go_on and 0 < r2 < T:
+                    m = max(m, abs(self.vel(r2)))
         return m
 
     def max_acc(self, T):
-        return max(abs(self.c3), abs(self.acc(T)))
+        m = max(abs(self.c3), abs(self.acc(T)))
+        if self.K == 4 and self.c1 != 0:
+            r = -self.c2 / self.c1
+            if 0 < r < T:
+                m = max(m, abs(self.acc(r)))
+        return m
+
+    def max_jrk(self, T):
+        return max(abs(self.c2), abs(self.jrk(T)))
 
     def effort(self, T):
         return self.u * self.u * T
@@ -103,7 +136,8 @@ def pair_eval(dim, control, row, u, dt, v_max=0.0, a_max=0.0, j_max=0.0, yaw_max
     D, K, yaw = dim, order_of(control), bool(control & 16)
     row = [float(x) for x in row]
     g = lambda o, i: row[o * D + i]
-    ax = [Axis(K, g(0, i), g(1, i) if K >= 2 else 0.0, g(2, i) if K >= 3 else 0.0, float(u[i])) for i in range(D)]
+    ax = [Axis(K, g(0, i), g(1, i) if K >= 2 else 0.0, g(2, i) if K >= 3 else 0.0, float(u[i]), g(3, i) if K >= 4 else 0.0)
+          for i in range(D)]
     cyaw = row[4 * D] if yaw else 0.0
     uyaw = float(u[D]) if yaw else 0.0
     T = float(dt)
@@ -118,7 +152,8 @@ def pair_eval(dim, control, row, u, dt, v_max=0.0, a_max=0.0, j_max=0.0, yaw_max
             cur[D + i] = 0.0
         if K < 3:
             cur[2 * D + i] = 0.0
-        cur[3 * D + i] = 0.0
+        if K < 4:
+            cur[3 * D + i] = 0.0
     cur[4 * D] = cyaw
     valid = True
     if yaw and yaw_max > 0:
@@ -137,6 +172,8 @@ def pair_eval(dim, control, row, u, dt, v_max=0.0, a_max=0.0, j_max=0.0, yaw_max
         valid = valid and all(not (a.max_vel(T) > v_max) for a in ax)
     if K >= 3 and a_max > 0:
         valid = valid and all(not (a.max_acc(T) > a_max) for a in ax)
+    if K >= 4 and j_max > 0:
+        valid = valid and all(not (a.max_jrk(T) > j_max) for a in ax)
     J = 0.0
     for a in ax:
         J += a.effort(T)
@@ -302,7 +339,8 @@ def chain_table(dim, control, U, dt, starts, actions, step, n_steps, t0, radius,
             s = states[k]
             v = s[dim:2 * dim] if K >= 2 else np.zeros(dim)
             a_ = s[2 * dim:3 * dim] if K >= 3 else np.zeros(dim)
-            pos[i, :, b] = RM.primitive_pos(s[:dim], v, a_, np.zeros(dim), np.asarray(U, dtype=F)[acts[k]][:dim], K, t - k * float(dt))
+            j_ = s[3 * dim:4 * dim] if K >= 4 else np.zeros(dim)
+            pos[i, :, b] = RM.primitive_pos(s[:dim], v, a_, j_, np.asarray(U, dtype=F)[acts[k]][:dim], K, t - k * float(dt))
     return {"pos": pos, "active": cm.active_mask(tl, total, mode).astype(np.uint8), "included": np.ones(B, np.uint8),
             "radius": np.broadcast_to(np.asarray(radius, dtype=F), (B,)).copy(), "group": np.arange(B, dtype=np.int32),
             "step": float(step)}
@@ -363,7 +401,8 @@ def search_many(provider, dim, control, U, dt, w, limits, starts, start_hashes, 
             st = states[:, k]
             u = U[int(lists["action"][k * S + j])][:dim]
             z = np.zeros(dim)
-            return RM.primitive_pos(st[:dim], st[dim:2 * dim] if K >= 2 else z, st[2 * dim:3 * dim] if K >= 3 else z, z, u, K, s)
+            return RM.primitive_pos(st[:dim], st[dim:2 * dim] if K >= 2 else z, st[2 * dim:3 * dim] if K >= 3 else z,
+                                    st[3 * dim:4 * dim] if K >= 4 else z, u, K, s)
         cost, _, _, _ = RM.check(lists["count"], lists["action"], lists["cost"], S, np.zeros(n, np.int32), states[-1], dt, len(U),
                                  step, n_steps, res, queries, edge_pos, row_q)
         lists["cost"] = cost
