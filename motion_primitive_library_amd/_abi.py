@@ -100,6 +100,21 @@ REPLAN_TIMED_SYMBOLS = ["mplx_table_rebase_timed_device"]
 FIELD_SYMBOLS = ["mplx_field_create", "mplx_field_destroy", "mplx_field_build", "mplx_field_shape", "mplx_field_view_of",
                  "mplx_field_download", "mplx_field_is_stale", "mplx_field_passes", "mplx_open_set_field", "mplx_open_clear_field"]
 FIELD_MAX_BYTES = 1 << 30
+# ... and the ones include/mplx_heur.h declares (the dynamics-aware heuristic: batches of states, the push of an open set)
+HEUR_SYMBOLS = ["mplx_heur_eval", "mplx_heur_eval_device", "mplx_open_set_heur", "mplx_planner_set_heur_dynamics"]
+HEUR_DEFAULT, HEUR_REFERENCE, HEUR_ROBUST = 0, 1, 2
+HEUR_BISECT = 56
+
+
+def heur_mode(mode):
+    """None / "default" / "reference" / "robust" (or the constant itself) -> MPLX_HEUR_*; anything else is passed on as
+    an int for the library to refuse."""
+    names = {None: HEUR_DEFAULT, False: HEUR_DEFAULT, "default": HEUR_DEFAULT, "reference": HEUR_REFERENCE, "robust": HEUR_ROBUST}
+    if isinstance(mode, str) or mode is None:
+        if mode not in names:
+            raise ValueError("heuristic mode %r: None, 'default', 'reference' or 'robust'" % (mode,))
+        return names[mode]
+    return int(mode)
 
 ROUTE_AUTO, ROUTE_DENSE, ROUTE_TILE, ROUTE_GRID = 0, 1, 2, 3
 
@@ -538,10 +553,14 @@ def lib():
         "mplx_field_passes": (C.c_int, [vp, C.POINTER(i64)]),
         "mplx_open_set_field": (C.c_int, [vp, vp, vp]),
         "mplx_open_clear_field": (C.c_int, [vp]),
+        "mplx_heur_eval": (C.c_int, [vp, C.POINTER(GoalSpec), i32, vp, i64, i64, vp]),
+        "mplx_heur_eval_device": (C.c_int, [vp, C.POINTER(GoalSpec), i32, vp, i64, i64, vp]),
+        "mplx_open_set_heur": (C.c_int, [vp, i32]),
+        "mplx_planner_set_heur_dynamics": (C.c_int, [vp, i32]),
         "mplx_table_set_time_keys": (C.c_int, [vp, i32]),
         "mplx_time_key": (C.c_uint64, [C.c_uint64, dbl]),
     }
-    for name in SYMBOLS + MAP_UTIL_SYMBOLS + ROLLOUT_SYMBOLS + RAY_SYMBOLS + TRAJ_SYMBOLS + TABLE_SYMBOLS + OPEN_SYMBOLS + MULTI_SYMBOLS + REPLAN_SYMBOLS + PRIOR_SYMBOLS + SOLVE_SYMBOLS + LIMITS_SYMBOLS + SCALE_SYMBOLS + CONFLICT_SYMBOLS + RESERVE_SYMBOLS + WAIT_SYMBOLS + REPLAN_TIMED_SYMBOLS + FIELD_SYMBOLS:
+    for name in SYMBOLS + MAP_UTIL_SYMBOLS + ROLLOUT_SYMBOLS + RAY_SYMBOLS + TRAJ_SYMBOLS + TABLE_SYMBOLS + OPEN_SYMBOLS + MULTI_SYMBOLS + REPLAN_SYMBOLS + PRIOR_SYMBOLS + SOLVE_SYMBOLS + LIMITS_SYMBOLS + SCALE_SYMBOLS + CONFLICT_SYMBOLS + RESERVE_SYMBOLS + WAIT_SYMBOLS + REPLAN_TIMED_SYMBOLS + FIELD_SYMBOLS + HEUR_SYMBOLS:
         fn = getattr(L, name)  # AttributeError if the library does not export it
         fn.restype, fn.argtypes = sig[name]
     _lib = L

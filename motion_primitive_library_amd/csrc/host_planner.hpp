@@ -39,6 +39,11 @@
 #include <immintrin.h>
 #endif
 
+#if defined(__HIPCC__)
+#include <hip/hip_runtime.h>  // (the qualifiers of MPLX_HD)
+#endif
+#include "mplx_heur_math.h"  // include/mplx_heur.h: cal_heur with the dynamics on
+
 namespace mplx {
 namespace host {
 
@@ -725,7 +730,17 @@ class Planner {
     return 0;
   }
   // env_base::get_heur for a state at position `s` and time `t` whose lattice hash differs from the goal's
+  // include/mplx_heur.h: MPLX_HEUR_REFERENCE / _ROBUST -- cal_heur with heur_ignore_dynamics_ == false; `s` is then a full
+  // state.  A prior trajectory together with a mode is refused where either is set (planner_capi.cpp), so none is here.
+  int heur_mode = 0;
   double heur_at(const double *s, double t, const double *goal) const {
+    if (heur_mode != 0 && !has_prior()) {
+      const int gc = effective_goal_control();
+      bool unsupported = false;  // (a JRK state space in REFERENCE: refused before the search starts)
+      if (heur_mode == 1)
+        return dim == 2 ? heur::reference<2>(s, goal, control, gc, w, v_max, &unsupported) : heur::reference<3>(s, goal, control, gc, w, v_max, &unsupported);
+      return dim == 2 ? heur::robust<2>(s, goal, control, gc, w, v_max) : heur::robust<3>(s, goal, control, gc, w, v_max);
+    }
     auto linf = [&](const double *b) {
       double m = 0;
       for (int i = 0; i < dim; i++) m = std::max(m, std::abs(s[i] - b[i]));
@@ -943,9 +958,10 @@ class Planner {
           c_curr = &coords[(size_t)cold[curr].coord * (size_t)f];  // (coords may have moved)
         }
         if (eps == 0 || key == goal_key) nd.h = 0;
-        else if (sv.heur && !has_prior()) { nd.h = sv.heur[s]; last.heur_from_provider++; }  // computed where the successor was made
+        else if (sv.heur && !has_prior() && heur_mode == 0) { nd.h = sv.heur[s]; last.heur_from_provider++; }  // computed where the successor was made
         else {
-          if (!have_sc) forward_pos(dim, control, c_curr, &U[(size_t)sv.act[s] * udim], dt, sc);
+          if (!have_sc && heur_mode != 0) forward_state(dim, control, c_curr, &U[(size_t)sv.act[s] * udim], dt, sc);  // (velocity and acceleration too)
+          else if (!have_sc) forward_pos(dim, control, c_curr, &U[(size_t)sv.act[s] * udim], dt, sc);
           nd.h = heur_at(sc, c_curr[4 * dim + 1] + dt, goal);  // (the successor's time: env_map.h:161)
         }
       }

@@ -183,7 +183,7 @@ void mplx_destroy(mplx_ctx *c) {
   if (c->done_host) (void)hipHostFree(c->done_host);
   release(c->done_count);
   for (DevBuf *b : {&c->map, &c->pot, &c->region_bits, &c->region_bytes, &c->U, &c->tables,
-                    &c->d_status, &c->d_cost, &c->d_hash, &c->d_state, &c->d_iters, &c->uvals, &c->uidx, &c->blk, &c->sat, &c->prep_lut, &c->prep_a, &c->prep_b, &c->post_keys, &c->post_ws, &c->ray_work, &c->traj_tab, &c->conflict_ws, &c->live_list, &c->live_ctr})
+                    &c->d_status, &c->d_cost, &c->d_hash, &c->d_state, &c->d_iters, &c->uvals, &c->uidx, &c->blk, &c->sat, &c->prep_lut, &c->prep_a, &c->prep_b, &c->post_keys, &c->post_ws, &c->ray_work, &c->heur_ws, &c->traj_tab, &c->conflict_ws, &c->live_list, &c->live_ctr})
     release(*b);
   (void)mplx_comm_destroy(c);
   release(c->comm_meta);
@@ -314,6 +314,8 @@ int mplx_set_goal(mplx_ctx *c, const mplx_goal_spec *g) {
     c->goal_fuse = f;
     c->has_goal = has;
   }
+  c->goal_ctl[0] = g ? g->control : 0;
+  c->goal_ctl[1] = g ? g->goal_control : 0;
   return MPLX_OK;
 }
 

@@ -43,6 +43,7 @@ struct mplx_ctx {
   // mplx_set_goal: the goal the heur / flags rows of mplx_succ_lists refer to (PostFuse without its output pointers)
   bool has_goal = false;
   mplx::PostFuse goal_fuse{};
+  int32_t goal_ctl[2] = {0, 0};  // control and goal_control of that goal (include/mplx_heur.h: the push with ROBUST)
   int32_t mdim[3] = {1, 1, 1};
   double origin[3] = {0, 0, 0};
   double res = 0;
@@ -57,6 +58,7 @@ struct mplx_ctx {
   mplx_detail::DevBuf post_keys;                 // node-identity table (post_api.cpp)
   mplx_detail::DevBuf post_ws;                   // workspace of the partitioned identity pass (identity_kernel.hip)
   mplx_detail::DevBuf ray_work;                  // candidate worklist of mplx_goal_sight_device (ray_api.cpp)
+  mplx_detail::DevBuf heur_ws;                   // state rows and h of mplx_heur_eval (heur_api.cpp): its own block, not the arena
   mplx_detail::DevBuf traj_tab;                  // segment table of the trajectory calls (traj_api.cpp); grow-only
   mplx_detail::DevBuf conflict_ws;               // scratch of mplx_traj_conflicts (conflict_api.cpp); grow-only
   mplx_detail::DevBuf prep_lut, prep_a, prep_b;  // map preprocessing scratch (map_prep_api.cpp)

@@ -904,7 +904,24 @@ struct OpenArgs {
   int64_t field_cells;
   int32_t field_dim[3];
   double field_org[3], field_res;
+  // push with the dynamics-aware heuristic (include/mplx_heur.h; appended): dyn == 0 = the default heuristic
+  int32_t dyn;                     // MPLX_HEUR_ROBUST, or 0
+  int32_t dyn_control[2];          // control and goal_control of `goal`
+  const int32_t *dyn_controls;     // [n_queries][2] in device memory: those of `goals`
 };
+
+// The dynamics-aware heuristic of a batch of resident states (heur_kernel.hip, heur_api.cpp; include/mplx_heur.h).
+struct HeurArgs {
+  const double *states;            // [4D+2][stride]
+  int64_t n, stride;
+  double *out;                     // [n]
+  double goal[14];                 // the goal waypoint's rows
+  uint64_t goal_hash;              // under the goal's own flag
+  int32_t control, goal_control;   // the states' flag; the goal's, 0 = the states'
+  int32_t mode;                    // MPLX_HEUR_DEFAULT or MPLX_HEUR_ROBUST
+  double w, v_max;
+};
+hipError_t launch_heur_eval(int dim, const HeurArgs &a, hipStream_t s);
 
 // Goal distance fields (field_kernel.hip, field_api.cpp; include/mplx_field.h).  Tiles: 32 x 32 cells in 2-D, 8 x 8 x 8 in 3-D.
 struct FieldArgs {

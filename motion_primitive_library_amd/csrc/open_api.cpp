@@ -3,6 +3,7 @@
 // staging arena: push and select take device pointers only.
 #include "mplx_ctx.h"
 #include "../../include/mplx_field.h"
+#include "../../include/mplx_heur.h"
 #include "../../include/mplx_multi.h"
 #include "../../include/mplx_prior.h"
 #include "../../include/mplx_ray.h"
@@ -39,6 +40,10 @@ struct mplx_open {
   int32_t fld_max = -1;
   bool fld_gone = false;                // the field was destroyed while in force: a push is an error
   double goals_vmin = 0.0;              // the smallest v_max among the goals of mplx_open_set_goals
+  // include/mplx_heur.h: the mode of the pushes; control and goal_control of every goal (device, [Q][2]); the smallest w
+  int32_t heur_mode = 0;
+  DevBuf dyn_ctl;
+  double goals_wmin = 0.0;
 };
 
 namespace {
@@ -56,7 +61,7 @@ void drop_field(mplx_open *o) {
 void release_open(mplx_open *o) {
   drop_field(o);
   for (DevBuf *b : {&o->f, &o->flags, &o->ctl, &o->mark, &o->tot, &o->rows, &o->goals, &o->goals0, &o->pr_n, &o->pr_pos, &o->pr_togo,
-                    &o->pr_status, &o->pr_sidx, &o->pr_sterm, &o->pr_costs, &o->pr_trav, &o->pr_grow, &o->pr_ghash, &o->fld_q})
+                    &o->pr_status, &o->pr_sidx, &o->pr_sterm, &o->pr_costs, &o->pr_trav, &o->pr_grow, &o->pr_ghash, &o->fld_q, &o->dyn_ctl})
     release(*b);
   if (o->mirror) (void)hipHostFree(o->mirror);
   delete o;
@@ -210,6 +215,14 @@ int mplx_detail::open_push(mplx_open *o, const char *who, const mplx_table_front
     }
     a.field_res = c->res;
   }
+  if (o->heur_mode == MPLX_HEUR_ROBUST) {  // include/mplx_heur.h
+    if (o->has_priors) return fail(c, MPLX_ERR_STATE, "%s: MPLX_HEUR_ROBUST with priors in force (mplx_open_clear_priors, or mplx_open_set_heur(DEFAULT))", who);
+    if (!((o->has_goals ? o->goals_wmin : c->goal_fuse.w) > 0)) return fail(c, MPLX_ERR_STATE, "%s: MPLX_HEUR_ROBUST needs w > 0", who);
+    a.dyn = MPLX_HEUR_ROBUST;
+    a.dyn_control[0] = c->goal_ctl[0];
+    a.dyn_control[1] = c->goal_ctl[1];
+    a.dyn_controls = o->has_goals ? (const int32_t *)o->dyn_ctl.p : nullptr;
+  }
   if (!sight) {
     HIP_TRY(c, mplx::launch_open_push(c->dim, 0, a, rows, c->stream, closed));
     return MPLX_OK;
@@ -274,21 +287,28 @@ int mplx_open_set_goals(mplx_open *o, const mplx_goal_spec *h_goals, int32_t n) 
   if (n != o->Q) return fail(c, MPLX_ERR_ARG, "%s: %d goals for a table of %d queries", who, (int)n, (int)o->Q);
   MPLX_GUARD_BEGIN
   std::vector<mplx::PostFuse> f((size_t)n);
-  double tol = 0.0, vmin = 0.0;
+  std::vector<int32_t> ctl(2 * (size_t)n);
+  double tol = 0.0, vmin = 0.0, wmin = 0.0;
   for (int32_t q = 0; q < n; q++) {
     if (int rc = goal_fuse_of(c, who, &h_goals[q], &f[(size_t)q])) return rc;
     tol = std::max(tol, f[(size_t)q].tol_pos);
     vmin = (q == 0 || !(f[(size_t)q].v_max >= vmin)) ? f[(size_t)q].v_max : vmin;
+    wmin = (q == 0 || !(f[(size_t)q].w >= wmin)) ? f[(size_t)q].w : wmin;
+    ctl[2 * (size_t)q] = h_goals[q].control;
+    ctl[2 * (size_t)q + 1] = h_goals[q].goal_control;
   }
   if (int rc = bind_device(c)) return rc;
   if (int rc = resolve_pending(c)) return rc;  // the arena is shared with the other host-pointer calls
   const size_t bytes = (size_t)n * sizeof(mplx::PostFuse);
   if (int rc = ensure(c, o->goals, bytes)) return rc;
   if (int rc = ensure(c, o->goals0, bytes)) return rc;
+  if (int rc = ensure(c, o->dyn_ctl, ctl.size() * 4)) return rc;
   StageLayout l;
-  const size_t o_g = l.add(bytes);
+  const size_t o_g = l.add(bytes), o_c = l.add(ctl.size() * 4);
   if (int rc = stage_commit(c, &l)) return rc;
   HIP_TRY(c, stage_in(c, l.base + o_g, f.data(), bytes));
+  HIP_TRY(c, stage_in(c, l.base + o_c, ctl.data(), ctl.size() * 4));
+  HIP_TRY(c, hipMemcpyAsync(o->dyn_ctl.p, l.base + o_c, ctl.size() * 4, hipMemcpyDeviceToDevice, c->stream));
   HIP_TRY(c, hipMemcpyAsync(o->goals.p, l.base + o_g, bytes, hipMemcpyDeviceToDevice, c->stream));
   HIP_TRY(c, hipMemcpyAsync(o->goals0.p, l.base + o_g, bytes, hipMemcpyDeviceToDevice, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));  // (f leaves scope; the arena is free again)
@@ -297,6 +317,7 @@ int mplx_open_set_goals(mplx_open *o, const mplx_goal_spec *h_goals, int32_t n) 
   o->has_goals = true;
   o->goals_tol = tol;
   o->goals_vmin = vmin;
+  o->goals_wmin = wmin;
   return MPLX_OK;
   MPLX_GUARD_END(c)
 }
@@ -347,6 +368,7 @@ int mplx_open_set_priors_device(mplx_open *o, const mplx_prior_source *src, cons
       !s->starts || !s->actions)
     return fail(c, MPLX_ERR_ARG, "%s: bad trajectory set (horizon >= 1, starts, actions, strides >= counts)", who);
   if (!o->has_goals) return fail(c, MPLX_ERR_STATE, "%s: no goals of the open set's own (mplx_open_set_goals)", who);
+  if (o->heur_mode != MPLX_HEUR_DEFAULT) return fail(c, MPLX_ERR_STATE, "%s: MPLX_HEUR_ROBUST is in force (mplx_open_set_heur(DEFAULT) first)", who);
   if (o->fld) return fail(c, MPLX_ERR_STATE, "%s: a goal field is in force (mplx_open_clear_field first)", who);
   if (!c->has_params) return fail(c, MPLX_ERR_STATE, "%s: mplx_set_params has not been called", who);
   if (!c->has_map) return fail(c, MPLX_ERR_STATE, "%s: set the map first", who);
@@ -479,6 +501,25 @@ int mplx_open_set_field(mplx_open *o, mplx_field *fld, const int32_t *h_field_of
 int mplx_open_clear_field(mplx_open *o) {
   if (!o) return MPLX_ERR_ARG;
   drop_field(o);
+  return MPLX_OK;
+}
+
+// ---- include/mplx_heur.h -----------------------------------------------------------------------------------------------
+
+int mplx_open_set_heur(mplx_open *o, int32_t mode) {
+  if (!o) return MPLX_ERR_ARG;
+  mplx_ctx *c = o->c;
+  const char *who = "mplx_open_set_heur";
+  if (mode == MPLX_HEUR_REFERENCE)
+    return fail(c, MPLX_ERR_ARG, "%s: MPLX_HEUR_REFERENCE is host only (the planner's mode): the device takes DEFAULT and ROBUST", who);
+  if (mode != MPLX_HEUR_DEFAULT && mode != MPLX_HEUR_ROBUST) return fail(c, MPLX_ERR_ARG, "%s: unknown mode %d", who, (int)mode);
+  if (mode == MPLX_HEUR_ROBUST) {
+    if (o->has_priors) return fail(c, MPLX_ERR_STATE, "%s: priors are in force (mplx_open_clear_priors first)", who);
+    // (a goal set later is checked by the push)
+    if ((o->has_goals || c->has_goal) && !((o->has_goals ? o->goals_wmin : c->goal_fuse.w) > 0))
+      return fail(c, MPLX_ERR_ARG, "%s: MPLX_HEUR_ROBUST needs w > 0", who);
+  }
+  o->heur_mode = mode;
   return MPLX_OK;
 }
 

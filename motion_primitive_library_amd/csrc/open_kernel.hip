@@ -34,8 +34,14 @@
 // With a goal field (include/mplx_field.h) it is the same kernel once more: the heuristic of a query with a field takes the
 // larger of the default's Linf distance and the grid distance the field holds for the row's cell; the instantiations
 // without a field are untouched by that.
+//
+// With the dynamics-aware heuristic (include/mplx_heur.h) it is the same kernel a last time: heur::robust of
+// csrc/mplx_heur_math.h on the row's state and its query's goal, never below the default; with a field the larger of the
+// two.  ROBUST only: the reference's closed forms go through cbrt / acos / cos, whose bits are not the host's.  The
+// instantiations without it are untouched by that.
 #include "mplx_internal.h"
 #include "mplx_device_common.h"
+#include "mplx_heur_math.h"
 
 namespace mplx {
 namespace {
@@ -86,7 +92,8 @@ __device__ __forceinline__ Decision decide(const OpenArgs &A) { return decide(A.
 // (env_base.h:46-53); the instantiations without it are the kernels they were
 // FIELD: include/mplx_field.h -- a query with a goal field takes max(Linf, res * (dist - 1)) where the default takes Linf,
 // and +inf on a cell no chain leaves; likewise
-template <int D, bool MULTI, bool CLOSED, bool PRIOR, bool FIELD>
+// DYN: include/mplx_heur.h -- h = max(heur::robust, what the kernel had); a NaN (non-finite rows) makes the row ignored; likewise
+template <int D, bool MULTI, bool CLOSED, bool PRIOR, bool FIELD, bool DYN>
 __global__ __launch_bounds__(kBlock) void open_push_kernel(const OpenArgs A, int64_t rows, int pass) {
   if (A.t_ctl->status) return;
   const int64_t r = (int64_t)blockIdx.x * kBlock + threadIdx.x;
@@ -121,6 +128,11 @@ __global__ __launch_bounds__(kBlock) void open_push_kernel(const OpenArgs A, int
   double h;
   unsigned int fl;
   dev::post_eval<D>(PG, A.t_hash[id], s, s + D, s + 2 * D, s[4 * D], &h, &fl);
+  double h_dyn = 0.0;
+  if (DYN && !(fl & 2u)) {  // (bit 1: the goal's own lattice state keeps h = 0, env_base.h:47)
+    const int32_t *ctl = (MULTI && A.dyn_controls) ? A.dyn_controls + 2 * (int64_t)q : A.dyn_control;
+    h_dyn = heur::robust<D>(s, PG.g, ctl[0], ctl[1], PG.w, PG.v_max);
+  }
   if (PRIOR && !(fl & 2u)) {  // (bit 1: the goal's own lattice state keeps h = 0, env_base.h:47)
     const int32_t ns = A.prior_n[q];
     const double x = t_row > 0 ? t_row / A.prior_dt : 0.0;  // env_base.h:48
@@ -166,6 +178,7 @@ __global__ __launch_bounds__(kBlock) void open_push_kernel(const OpenArgs A, int
       }
     }
   }
+  if (DYN && !(h_dyn <= h)) h = h_dyn;  // the larger; a NaN stays
   const double g = A.f_g[r];
   double f = g;
   if (A.eps != 0.0) {
@@ -541,17 +554,34 @@ hipError_t launch_open_clear(const OpenArgs &a, hipStream_t s) {
   return hipGetLastError();
 }
 
-template <int D, bool MULTI, bool PRIOR = false, bool FIELD = false>
+template <int D, bool MULTI, bool PRIOR = false, bool FIELD = false, bool DYN = false>
 void push_closed(bool closed, dim3 grid, dim3 block, hipStream_t s, const OpenArgs &a, int64_t rows, int pass) {
-  if (closed) hipLaunchKernelGGL((open_push_kernel<D, MULTI, true, PRIOR, FIELD>), grid, block, 0, s, a, rows, pass);
-  else hipLaunchKernelGGL((open_push_kernel<D, MULTI, false, PRIOR, FIELD>), grid, block, 0, s, a, rows, pass);
+  if (closed) hipLaunchKernelGGL((open_push_kernel<D, MULTI, true, PRIOR, FIELD, DYN>), grid, block, 0, s, a, rows, pass);
+  else hipLaunchKernelGGL((open_push_kernel<D, MULTI, false, PRIOR, FIELD, DYN>), grid, block, 0, s, a, rows, pass);
+}
+
+// include/mplx_heur.h: never together with priors (open_api.cpp)
+template <int D>
+void push_dyn(bool closed, dim3 grid, dim3 block, hipStream_t s, const OpenArgs &a, int64_t rows, int pass) {
+  if (a.field_dist) {
+    if (a.goals) push_closed<D, true, false, true, true>(closed, grid, block, s, a, rows, pass);
+    else push_closed<D, false, false, true, true>(closed, grid, block, s, a, rows, pass);
+  } else {
+    if (a.goals) push_closed<D, true, false, false, true>(closed, grid, block, s, a, rows, pass);
+    else push_closed<D, false, false, false, true>(closed, grid, block, s, a, rows, pass);
+  }
 }
 
 hipError_t launch_open_push(int dim, int pass, const OpenArgs &a, int64_t rows, hipStream_t s, bool closed) {
   if (rows <= 0) return hipSuccess;
   const dim3 grid((unsigned)((rows + kBlock - 1) / kBlock)), block(kBlock);
   if (dim != 2 && dim != 3) return hipErrorInvalidValue;
-  if (a.field_dist) {  // (never together with priors: open_api.cpp)
+  if (a.dyn) {
+    if (a.dyn != 2 || a.prior_n || (a.goals && !a.dyn_controls)) return hipErrorInvalidValue;  // MPLX_HEUR_ROBUST
+    if (a.field_dist && (!a.field_of_query || a.field_F < 1 || a.field_cells < 1 || !(a.field_res > 0))) return hipErrorInvalidValue;
+    if (dim == 2) push_dyn<2>(closed, grid, block, s, a, rows, pass);
+    else push_dyn<3>(closed, grid, block, s, a, rows, pass);
+  } else if (a.field_dist) {  // (never together with priors: open_api.cpp)
     if (a.prior_n || !a.field_of_query || a.field_F < 1 || a.field_cells < 1 || !(a.field_res > 0)) return hipErrorInvalidValue;
     if (a.goals) {
       if (dim == 2) push_closed<2, true, false, true>(closed, grid, block, s, a, rows, pass);

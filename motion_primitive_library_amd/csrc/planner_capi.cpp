@@ -3,6 +3,7 @@
 #include "../../include/mplx.h"
 #include "../../include/mplx_debug.h"
 #include "../../include/mplx_prior.h"
+#include "../../include/mplx_heur.h"
 #include "host_planner.hpp"
 #include "host_lpastar.hpp"
 #include "mplx_ctx.h"
@@ -190,7 +191,17 @@ int mplx_planner_plan(mplx_planner *p, const double *start, const double *goal, 
   if (p->pl.nU <= 0) return fail(p, MPLX_ERR_STATE, "mplx_planner_plan: controls not set");
   if (!p->pl.single && !p->pl.batched && !p->pl.packed) return fail(p, MPLX_ERR_STATE, "mplx_planner_plan: no successor provider attached");
   p->device_heur = false;
-  if (p->ctx && p->pl.packed && p->pl.eps != 0 && p->want_device_heur && !p->pl.has_prior()) {
+  if (p->pl.heur_mode != MPLX_HEUR_DEFAULT) {  // include/mplx_heur.h
+    const int base = p->pl.control & 0x0f;
+    if (p->pl.has_prior())
+      return fail(p, MPLX_ERR_STATE, "mplx_planner_plan: a prior trajectory together with a dynamics-aware heuristic (mplx_planner_set_heur_dynamics)");
+    if (!(p->pl.w > 0)) return fail(p, MPLX_ERR_STATE, "mplx_planner_plan: a dynamics-aware heuristic needs w > 0");
+    if (p->pl.heur_mode == MPLX_HEUR_REFERENCE && (base == MPLX_JRK || base == MPLX_SNP))
+      return fail(p, MPLX_ERR_STATE, "mplx_planner_plan: MPLX_HEUR_REFERENCE covers VEL and ACC state spaces (the reference's JRK branches need "
+                                     "Eigen's PolynomialSolver); MPLX_HEUR_ROBUST covers JRK");
+  }
+  // (while a mode is on the planner evaluates new nodes itself: the lists' heur row stays the default heuristic)
+  if (p->ctx && p->pl.packed && p->pl.eps != 0 && p->want_device_heur && !p->pl.has_prior() && p->pl.heur_mode == MPLX_HEUR_DEFAULT) {
     // env_base::set_goal for the device (planner_base.h:301): the kernels compute what graph_search.h:84-88 asks of
     // the env for every new successor -- the default heuristic -- while the successor is in registers.
     // OFF by default (mplx_planner_use_device_heuristic / MPLX_PLAN_DEVICE_HEUR=1): one successor in fifteen creates a
@@ -247,6 +258,17 @@ int mplx_planner_use_device_heuristic(mplx_planner *p, int on) {
   return MPLX_OK;
 }
 
+// include/mplx_heur.h: PlannerBase::setHeurIgnoreDynamics for A* and LPA* (both evaluate through Planner::heur_at)
+int mplx_planner_set_heur_dynamics(mplx_planner *p, int32_t mode) {
+  if (!p) return MPLX_ERR_ARG;
+  if (mode != MPLX_HEUR_DEFAULT && mode != MPLX_HEUR_REFERENCE && mode != MPLX_HEUR_ROBUST)
+    return fail(p, MPLX_ERR_ARG, "mplx_planner_set_heur_dynamics: unknown mode");
+  if (mode != MPLX_HEUR_DEFAULT && p->pl.has_prior())
+    return fail(p, MPLX_ERR_STATE, "mplx_planner_set_heur_dynamics: a prior trajectory is set (clear it first)");
+  p->pl.heur_mode = mode;
+  return MPLX_OK;
+}
+
 // include/mplx_prior.h: the table set_prior_trajectory() left, for comparison with the device's
 int mplx_planner_prior_table(const mplx_planner *p, double *pos, double *togo, int32_t cap, int32_t *n, double *goal_row, int32_t *control) {
   if (!p || cap < 0) return MPLX_ERR_ARG;
@@ -263,6 +285,8 @@ int mplx_planner_prior_table(const mplx_planner *p, double *pos, double *togo, i
 int mplx_planner_set_prior_trajectory(mplx_planner *p, const mplx_planner *from) {
   if (!p) return MPLX_ERR_ARG;
   if (!from) { p->pl.clear_prior(); return MPLX_OK; }
+  if (p->pl.heur_mode != MPLX_HEUR_DEFAULT)
+    return fail(p, MPLX_ERR_STATE, "mplx_planner_set_prior_trajectory: a dynamics-aware heuristic is on (mplx_planner_set_heur_dynamics(p, 0) first)");
   const mplx::host::PlanResult &r = from->result();
   if (!r.ok || r.traj_actions.empty()) return fail(p, MPLX_ERR_STATE, "mplx_planner_set_prior_trajectory: the other planner holds no trajectory");
   if (from->pl.dim != p->pl.dim) return fail(p, MPLX_ERR_ARG, "mplx_planner_set_prior_trajectory: dimensions differ");
@@ -293,6 +317,8 @@ int mplx_planner_set_prior_trajectory_potential(mplx_planner *p, const mplx_plan
                                                 double potential_weight, double gradient_weight) {
   if (!p) return MPLX_ERR_ARG;
   if (!from) { p->pl.clear_prior(); return MPLX_OK; }
+  if (p->pl.heur_mode != MPLX_HEUR_DEFAULT)
+    return fail(p, MPLX_ERR_STATE, "mplx_planner_set_prior_trajectory_potential: a dynamics-aware heuristic is on (mplx_planner_set_heur_dynamics(p, 0) first)");
   const mplx::host::PlanResult &r = from->result();
   if (!r.ok || r.traj_actions.empty()) return fail(p, MPLX_ERR_STATE, "mplx_planner_set_prior_trajectory_potential: the other planner holds no trajectory");
   if (from->pl.dim != p->pl.dim) return fail(p, MPLX_ERR_ARG, "mplx_planner_set_prior_trajectory_potential: dimensions differ");

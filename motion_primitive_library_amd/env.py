@@ -2340,7 +2340,7 @@ class EnvMap:
     def search(self, start, goal_row, eps=1.0, delta=None, g_max=float("inf"), max_rounds=None, max_expand=None,
                capacity=1 << 16, max_frontier=None, lists_stride=None, sight=True, tol_pos=0.5, tol_vel=-1.0, tol_acc=-1.0,
                tol_yaw=-1.0, w=None, v_max=None, start_g=0.0, prior=None, avoid=None, t0=0.0, radius=None, ignore_group=-1,
-               time_keys=None, wait=False, park_goal=False, field=None, field_of_query=None):
+               time_keys=None, wait=False, park_goal=False, field=None, field_of_query=None, heur=None):
         """A goal-directed search from `start` (one 4D+2 state) to the goal region of `goal_row` that stays on the
         device: set_goal, seed, push; then per round one select (the round's only read-back, 48 bytes), and while it
         selects: expand the selection, relax its lists against the table, push the nodes whose g fell.  Keys are
@@ -2370,16 +2370,20 @@ class EnvMap:
         field: None -- the calls of a search without one.  True: a goal distance field (include/mplx_field.h) is built for
         the goal, set after the goal and freed with the result: the heuristic becomes w * max(Linf, res * (dist - 1)) / v_max,
         which sees walls and dead ends and stays admissible.  A search.GoalField (alloc_field; with field_of_query, default
-        [0]) is used as given and not freed.  field together with prior is a ValueError."""
+        [0]) is used as given and not freed.  field together with prior is a ValueError.
+        heur: None -- the default heuristic and the calls of a search without the argument.  "robust": the pushes take
+        the dynamics-aware heuristic (include/mplx_heur.h; OpenSet.set_heur): the cost of the unconstrained connection to
+        the goal STATE minimised over the arrival time, never below the default; with a field the larger of the two.  A
+        replan keeps the mode.  heur together with prior is a ValueError."""
         from .search import run_search
         return run_search(self, start, goal_row, eps, delta, g_max, max_rounds, max_expand, capacity, max_frontier,
                           lists_stride, sight, tol_pos, tol_vel, tol_acc, tol_yaw, w, v_max, start_g, prior, avoid, t0, radius,
-                          ignore_group, time_keys, wait, park_goal, field, field_of_query)
+                          ignore_group, time_keys, wait, park_goal, field, field_of_query, heur)
 
     def search_many(self, starts, goal_rows, eps=1.0, delta=None, g_max=float("inf"), max_rounds=None, max_expand=None,
                     capacity=1 << 16, max_frontier=None, lists_stride=None, sight=True, tol_pos=0.5, tol_vel=-1.0,
                     tol_acc=-1.0, tol_yaw=-1.0, w=None, v_max=None, start_g=0.0, priors=None, avoid=None, t0=0.0, radius=None,
-                    ignore_group=-1, time_keys=None, wait=False, park_goal=False, field=None, field_of_query=None):
+                    ignore_group=-1, time_keys=None, wait=False, park_goal=False, field=None, field_of_query=None, heur=None):
         """Q searches of EnvMap.search at once, sharing every launch of a round (include/mplx_multi.h): starts
         [4D+2][Q], goal_rows [Q][4D+2], query q from starts[:, q] to the goal region of goal_rows[q].  One table of
         `capacity` nodes and one open set hold all of them; a round selects, expands, relaxes and pushes the union of
@@ -2391,11 +2395,51 @@ class EnvMap:
         avoid, t0, radius, ignore_group (one value for all queries or [Q]), time_keys, wait and park_goal: as EnvMap.search takes them;
         every query has its own start on the clock, radius and ignored group, and one check serves them all.
         field: as EnvMap.search takes it; True builds one field per DISTINCT goal row (the delay candidates of one robot
-        share one); a GoalField is used with field_of_query [Q] (default: query q uses field q; -1: the default heuristic)."""
+        share one); a GoalField is used with field_of_query [Q] (default: query q uses field q; -1: the default heuristic).
+        heur: as EnvMap.search takes it; every query's own goal is the one its rows are measured against."""
         from .search import run_search_many
         return run_search_many(self, starts, goal_rows, eps, delta, g_max, max_rounds, max_expand, capacity, max_frontier,
                                lists_stride, sight, tol_pos, tol_vel, tol_acc, tol_yaw, w, v_max, start_g, priors, avoid, t0,
-                               radius, ignore_group, time_keys, wait, park_goal, field, field_of_query)
+                               radius, ignore_group, time_keys, wait, park_goal, field, field_of_query, heur)
+
+    def _heur_goal(self, goal_row, goal_control, w, v_max):
+        goal = np.ascontiguousarray(goal_row, dtype=np.float64)
+        if goal.shape != (self.n_fields,):
+            raise ValueError("goal_row must have %d entries" % self.n_fields)
+        g = _abi.GoalSpec()
+        g.goal, g.control, g.goal_control = goal.ctypes.data, int(self._p.control), int(goal_control)
+        g.w = float(self._p.w if w is None else w)
+        g.v_max = float(self._p.v_max if v_max is None else v_max)
+        g.tol_pos, g.tol_vel, g.tol_acc, g.tol_yaw = 0.0, -1.0, -1.0, -1.0
+        return g, goal
+
+    def heur_eval(self, states, goal_row, mode="robust", goal_control=0, w=None, v_max=None):
+        """mplx_heur_eval (include/mplx_heur.h): get_heur of the state columns `states` ([4D+2][K], or one state) against
+        `goal_row` under `mode` ("robust", or "default"; "reference" is the host planner's and refused here), with the
+        context's control flag, w and v_max unless given.  Returns h [K]."""
+        self._flush()
+        st = np.ascontiguousarray(np.asarray(states, dtype=np.float64).reshape(self.n_fields, -1))
+        K = st.shape[1]
+        g, keep = self._heur_goal(goal_row, goal_control, w, v_max)
+        out = np.zeros(K)
+        _abi.check(self._ctx, _abi.lib().mplx_heur_eval(self._ctx, C.byref(g), _abi.heur_mode(mode), st.ctypes.data, K, K,
+                                                        out.ctypes.data))
+        return out
+
+    def heur_eval_resident(self, states, goal_row, out, n=None, stride=None, mode="robust", goal_control=0, w=None, v_max=None):
+        """mplx_heur_eval_device: the same on resident rows -- `states` a TableFrontier (its state rows, n = its capacity
+        unless given) or a device buffer [4D+2][stride]; `out` a device buffer of n doubles.  Asynchronous."""
+        self._flush()
+        if hasattr(states, "state_stride"):  # a TableFrontier
+            ptr, stride, n = states.state.ptr, states.state_stride, (states.capacity if n is None else n)
+        else:
+            ptr = _device_ptr(states)
+            if stride is None:
+                raise ValueError("heur_eval_resident: a device buffer needs its stride")
+            n = stride if n is None else n
+        g, keep = self._heur_goal(goal_row, goal_control, w, v_max)
+        _abi.check(self._ctx, _abi.lib().mplx_heur_eval_device(self._ctx, C.byref(g), _abi.heur_mode(mode), ptr, int(n),
+                                                               int(stride), _device_ptr(out)))
 
     def alloc_reservations(self, trajs, step, n_steps=None, t0=None, radius=None, group=None, park=True):
         """A reservation table on the device (include/mplx_reserve.h; search.Reservations): the positions of the

@@ -444,6 +444,16 @@ class MapPlanner:
         search's own evaluation: same search, see mplx_planner_use_device_heuristic."""
         self._check(self._L.mplx_planner_use_device_heuristic(self._p, 1 if on else 0))
 
+    def setHeurIgnoreDynamics(self, ignore=True, robust=False):
+        """PlannerBase::setHeurIgnoreDynamics (planner_base.h; env_base::cal_heur): ignore=True -- the default heuristic
+        w * Linf / v_max.  ignore=False -- the cost of the unconstrained connection from the state to the goal state,
+        minimised over the arrival time (include/mplx_heur.h): robust=False is the REFERENCE mode, what the reference
+        returns expression for expression (VEL and ACC state spaces; not admissible), robust=True the
+        ROBUST mode, the true minimum (VEL, ACC and JRK; never below the default).  For A* and LPA*; a prior trajectory
+        excludes both."""
+        mode = _abi.HEUR_DEFAULT if ignore else (_abi.HEUR_ROBUST if robust else _abi.HEUR_REFERENCE)
+        self._check(self._L.mplx_planner_set_heur_dynamics(self._p, mode))
+
     def timing(self):
         """Where the wall time of the last plan() went (ms) and what its relaxation loop did (mplx_plan_timing)."""
         t = _abi.PlanTiming()

@@ -265,10 +265,11 @@ class OpenSet:
         per = lambda v, default=None: np.broadcast_to(np.asarray(default if v is None else v, dtype=np.float64), (n,))
         ws, vs = per(w, env._p.w), per(v_max, env._p.v_max)
         tp, tv, ta, ty = per(tol_pos), per(tol_vel), per(tol_acc), per(tol_yaw)
+        gcs = np.broadcast_to(np.asarray(goal_control, dtype=np.int64), (n,))  # (one flag for all queries, or [Q])
         specs = (_abi.GoalSpec * max(n, 1))()
         for q in range(n):
             g = specs[q]
-            g.goal, g.control, g.goal_control = rows[q].ctypes.data, int(env._p.control), int(goal_control)
+            g.goal, g.control, g.goal_control = rows[q].ctypes.data, int(env._p.control), int(gcs[q])
             g.w, g.v_max = float(ws[q]), float(vs[q])
             g.tol_pos, g.tol_vel, g.tol_acc, g.tol_yaw = float(tp[q]), float(tv[q]), float(ta[q]), float(ty[q])
         self._check(_abi.lib().mplx_open_set_goals(self._open, specs, n))
@@ -359,6 +360,12 @@ class OpenSet:
     def clear_field(self):
         self._check(_abi.lib().mplx_open_clear_field(self._open))
         self._field = None
+
+    def set_heur(self, mode):
+        """mplx_open_set_heur (include/mplx_heur.h): "robust" -- every push from now on takes its heuristic from the
+        dynamics-aware ROBUST form (never below the default; with a field the larger of the two); None / "default" -- the
+        default again.  clear() keeps the mode; priors exclude it."""
+        self._check(_abi.lib().mplx_open_set_heur(self._open, _abi.heur_mode(mode)))
 
     def priors(self):
         """The prior table in force (a download): {"n_steps" [Q], "pos": [Q] arrays [n_steps][D], "togo": [Q] arrays,
@@ -1054,9 +1061,11 @@ def _params(env, eps, delta, g_max, max_rounds, max_expand, capacity, max_fronti
 
 def run_search(env, start, goal_row, eps, delta, g_max, max_rounds, max_expand, capacity, max_frontier, lists_stride, sight,
                tol_pos, tol_vel, tol_acc, tol_yaw, w, v_max, start_g=0.0, prior=None, avoid=None, t0=0.0, radius=None,
-               ignore_group=-1, time_keys=None, wait=False, park_goal=False, field=None, field_of_query=None):
+               ignore_group=-1, time_keys=None, wait=False, park_goal=False, field=None, field_of_query=None, heur=None):
     if field is not None and field is not False and prior is not None:
         raise ValueError("search: field and prior exclude each other")
+    if heur is not None and prior is not None:
+        raise ValueError("search: heur and prior exclude each other")
     env._flush()
     prm = _params(env, eps, delta, g_max, max_rounds, max_expand, capacity, max_frontier, lists_stride, sight,
                   dict(w=w, v_max=v_max, tol_pos=tol_pos, tol_vel=tol_vel, tol_acc=tol_acc, tol_yaw=tol_yaw))
@@ -1077,6 +1086,8 @@ def run_search(env, start, goal_row, eps, delta, g_max, max_rounds, max_expand, 
             opn.set_prior_list([prior])
         if field is not None and field is not False:
             fld, fld_owned, field_of_query = _field_setup("search", env, opn, field, field_of_query, prm["goal_row"], tol_pos, prior)
+        if heur is not None:  # (the open set keeps the mode: a replan pushes with it)
+            opn.set_heur(heur)
         sel, imp = TableFrontier(env, fcap), TableFrontier(env, int(capacity))  # (no more nodes can improve than exist)
         lists = env.alloc_lists(fcap, want_state=True, stride=lists_stride)
         # (g = None is the call without a g row: the bytes of a search before start_g existed)
@@ -1212,9 +1223,12 @@ class MultiSearchResult:
 
 def run_search_many(env, starts, goal_rows, eps, delta, g_max, max_rounds, max_expand, capacity, max_frontier, lists_stride,
                     sight, tol_pos, tol_vel, tol_acc, tol_yaw, w, v_max, start_g=0.0, priors=None, avoid=None, t0=0.0,
-                    radius=None, ignore_group=-1, time_keys=None, wait=False, park_goal=False, field=None, field_of_query=None):
+                    radius=None, ignore_group=-1, time_keys=None, wait=False, park_goal=False, field=None, field_of_query=None,
+                    heur=None):
     if field is not None and field is not False and priors is not None:
         raise ValueError("search_many: field and priors exclude each other")
+    if heur is not None and priors is not None:
+        raise ValueError("search_many: heur and priors exclude each other")
     env._flush()
     starts = np.ascontiguousarray(starts, dtype=np.float64)
     goal_rows = np.ascontiguousarray(goal_rows, dtype=np.float64)
@@ -1242,6 +1256,8 @@ def run_search_many(env, starts, goal_rows, eps, delta, g_max, max_rounds, max_e
             opn.set_prior_list(list(priors))
         if field is not None and field is not False:
             fld, fld_owned, field_of_query = _field_setup("search_many", env, opn, field, field_of_query, goal_rows, tol_pos, priors)
+        if heur is not None:
+            opn.set_heur(heur)
         sel, imp = TableFrontier(env, fcap), TableFrontier(env, int(capacity))  # (no more nodes can improve than exist)
         lists = env.alloc_lists(fcap, want_state=True, stride=lists_stride)
         count = tab.seed(starts, g0, frontier=imp, query=np.arange(Q, dtype=np.int32))
