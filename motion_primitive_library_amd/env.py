@@ -25,6 +25,10 @@ import ctypes as C
 import numpy as np
 
 from . import _abi
+# the device allocations and output rows (rows.py) and the trajectory sets (poly.py), under the names they always had here
+from .rows import (DeviceArray, DeviceArrayView, _alloc, _device_ptr, Rollouts, Rays, TrajInfo, TrajSamples,  # noqa: F401
+                   TrajTraverse, SolveOut, LoadOut, PolyLimits, LambdaRows, Conflicts, ConflictResult)
+from .poly import PolyTrajSet, ShortcutResult, _conflict_in, _conflict_steps, _conflict_host_out  # noqa: F401
 
 # Control::Control (reference include/mpl_basis/control.h:10-20)
 VEL, ACC, JRK, SNP = 0x01, 0x03, 0x07, 0x0F
@@ -76,59 +80,6 @@ class Waypoint:
             self.pos.tolist(), self.vel.tolist(), self.acc.tolist(), self.jrk.tolist(), self.yaw, self.t)
 
 
-class DeviceArray:
-    """An HBM allocation made through the C ABI (mplx_device_alloc)."""
-
-    def __init__(self, env, nbytes):
-        self._env = env
-        self.nbytes = int(nbytes)
-        p = C.c_void_p()
-        _abi.check(env._ctx, _abi.lib().mplx_device_alloc(env._ctx, self.nbytes, C.byref(p)))
-        self.ptr = p.value
-
-    def upload(self, host):
-        host = np.ascontiguousarray(host)
-        assert host.nbytes <= self.nbytes
-        _abi.check(self._env._ctx, _abi.lib().mplx_memcpy_h2d(self._env._ctx, self.ptr, host.ctypes.data, host.nbytes))
-
-    def download(self, dtype, shape, offset=0):
-        """Copy `shape` elements of `dtype` starting `offset` BYTES into the allocation back to the host."""
-        out = np.empty(shape, dtype=dtype)
-        assert int(offset) + out.nbytes <= self.nbytes
-        _abi.check(self._env._ctx, _abi.lib().mplx_memcpy_d2h(self._env._ctx, out.ctypes.data, self.ptr + int(offset),
-                                                               out.nbytes))
-        return out
-
-    def free(self):
-        if self.ptr and self._env._ctx:
-            _abi.lib().mplx_device_free(self._env._ctx, self.ptr)
-        self.ptr = None
-
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
-
-
-def _alloc(env, nbytes, alloc=None):
-    """An HBM allocation for the engine: through the C ABI by default, or from `alloc(nbytes)` -- any object with
-    .ptr / .nbytes / .download / .free, e.g. shard.TorchArray, so that torch.distributed can move the same memory."""
-    return DeviceArray(env, nbytes) if alloc is None else alloc(int(nbytes))
-
-
-class DeviceArrayView:
-    """A raw device pointer the engine did not allocate (e.g. a field of a ready C struct): read-back helper."""
-
-    def __init__(self, env, ptr):
-        self._env, self.ptr = env, int(ptr)
-
-    def download_i64(self, index):
-        out = np.empty(1, dtype=np.int64)
-        _abi.check(self._env._ctx, _abi.lib().mplx_memcpy_d2h(self._env._ctx, out.ctypes.data, self.ptr + 8 * int(index), 8))
-        return out[0]
-
-
 class Slots:
     """HBM-resident dense successor slots for n_nodes x nU pairs."""
 
@@ -169,884 +120,12 @@ class Slots:
                 b.free()
 
 
-def _device_ptr(buf):
-    """The device address of a DeviceArray (or anything with .ptr) or of a torch tensor (data_ptr())."""
-    if hasattr(buf, "ptr"):
-        return int(buf.ptr)
-    if hasattr(buf, "data_ptr"):
-        return int(buf.data_ptr())
-    raise TypeError("need a device buffer with .ptr or .data_ptr(), got %r" % type(buf))
-
-
-class Rollouts:
-    """HBM-resident output rows of n rollouts (mplx_rollout_out)."""
-
-    def __init__(self, env, n_rollouts, want_end=True, want_goal_rows=False):
-        self.n = int(n_rollouts)
-        self.n_fields = env.n_fields
-        n = max(self.n, 1)
-        self.status = DeviceArray(env, n)
-        self.steps = DeviceArray(env, n * 4)
-        self.cost = DeviceArray(env, n * 8)
-        self.prefix_cost = DeviceArray(env, n * 8)
-        self.end_state = DeviceArray(env, n * 8 * self.n_fields) if want_end else None
-        self.end_hash = DeviceArray(env, n * 8) if want_end else None
-        self.end_heur = DeviceArray(env, n * 8) if want_goal_rows else None
-        self.end_flags = DeviceArray(env, n) if want_goal_rows else None
-
-    def c_struct(self):
-        s = _abi.RolloutOut()
-        s.status, s.steps, s.cost, s.prefix_cost = self.status.ptr, self.steps.ptr, self.cost.ptr, self.prefix_cost.ptr
-        s.end_state = self.end_state.ptr if self.end_state else None
-        s.end_stride = self.n
-        s.end_hash = self.end_hash.ptr if self.end_hash else None
-        s.end_heur = self.end_heur.ptr if self.end_heur else None
-        s.end_flags = self.end_flags.ptr if self.end_flags else None
-        return s
-
-    def download(self):
-        n = self.n
-        out = {"status": self.status.download(np.uint8, (n,)), "steps": self.steps.download(np.int32, (n,)),
-               "cost": self.cost.download(np.float64, (n,)), "prefix_cost": self.prefix_cost.download(np.float64, (n,))}
-        if self.end_state:
-            out["end_state"] = self.end_state.download(np.float64, (self.n_fields, n))
-            out["end_hash"] = self.end_hash.download(np.uint64, (n,))
-        if self.end_heur:
-            out["end_heur"] = self.end_heur.download(np.float64, (n,))
-            out["end_flags"] = self.end_flags.download(np.uint8, (n,))
-        return out
-
-    def free(self):
-        for b in (self.status, self.steps, self.cost, self.prefix_cost, self.end_state, self.end_hash, self.end_heur,
-                  self.end_flags):
-            if b is not None:
-                b.free()
-
-
-class Rays:
-    """HBM-resident output rows of n rays (mplx_ray_out); cells only with cell_cap > 0."""
-
-    def __init__(self, env, n, cell_cap=0, want_counts=True):
-        self.n, self.cell_cap = int(n), int(cell_cap)
-        n = max(self.n, 1)
-        self.status = DeviceArray(env, n)
-        self.n_cells = DeviceArray(env, n * 4) if want_counts else None
-        self.first_hit = DeviceArray(env, n * 4) if want_counts else None
-        self.cells = DeviceArray(env, n * self.cell_cap * 4) if self.cell_cap > 0 else None
-
-    def c_struct(self):
-        s = _abi.RayOut()
-        s.status = self.status.ptr
-        s.n_cells = self.n_cells.ptr if self.n_cells else None
-        s.first_hit = self.first_hit.ptr if self.first_hit else None
-        s.cells = self.cells.ptr if self.cells else None
-        s.cell_cap = self.cell_cap
-        return s
-
-    def download(self):
-        out = {"status": self.status.download(np.uint8, (self.n,))}
-        if self.n_cells:
-            out["n_cells"] = self.n_cells.download(np.int32, (self.n,))
-            out["first_hit"] = self.first_hit.download(np.int32, (self.n,))
-        if self.cells:
-            out["cells"] = self.cells.download(np.int32, (self.n, self.cell_cap))
-        return out
-
-    def free(self):
-        for b in (self.status, self.n_cells, self.first_hit, self.cells):
-            if b is not None:
-                b.free()
-
-
-class TrajInfo:
-    """HBM-resident rows of mplx_traj_info_out for n trajectories of up to `horizon` segments."""
-
-    def __init__(self, env, n, horizon, want_states=False):
-        self.n, self.horizon, self.n_fields = int(n), int(horizon), env.n_fields
-        n = max(self.n, 1)
-        self.status = DeviceArray(env, n)
-        self.n_segs = DeviceArray(env, n * 4)
-        self.total_time = DeviceArray(env, n * 8)
-        self.effort = DeviceArray(env, 5 * n * 8)
-        self.seg_state = DeviceArray(env, self.n_fields * (self.horizon + 1) * n * 8) if want_states else None
-
-    def c_struct(self):
-        s = _abi.TrajInfoOut()
-        s.status, s.n_segs, s.total_time, s.effort = self.status.ptr, self.n_segs.ptr, self.total_time.ptr, self.effort.ptr
-        s.effort_stride = s.seg_stride = self.n
-        s.seg_state = self.seg_state.ptr if self.seg_state else None
-        return s
-
-    def download(self):
-        n = self.n
-        out = {"status": self.status.download(np.uint8, (n,)), "n_segs": self.n_segs.download(np.int32, (n,)),
-               "total_time": self.total_time.download(np.float64, (n,)), "effort": self.effort.download(np.float64, (5, n))}
-        if self.seg_state:
-            out["seg_state"] = self.seg_state.download(np.float64, (self.n_fields, self.horizon + 1, n))
-        return out
-
-    def free(self):
-        for b in (self.status, self.n_segs, self.total_time, self.effort, self.seg_state):
-            if b is not None:
-                b.free()
-
-
-class TrajSamples:
-    """HBM-resident sample rows (mplx_traj_sample_out): [4D+3][n_stride][sample_stride] float64, and status [n]."""
-
-    def __init__(self, env, n, count, n_stride=None, sample_stride=None):
-        self.n, self.count, self.rows = int(n), int(count), 4 * env.dim + 3
-        self.n_stride = self.n if n_stride is None else int(n_stride)
-        self.sample_stride = self.count if sample_stride is None else int(sample_stride)
-        self.out = DeviceArray(env, max(self.rows * self.n_stride * self.sample_stride, 1) * 8)
-        self.status = DeviceArray(env, max(self.n, 1))
-
-    def c_struct(self):
-        s = _abi.TrajSampleOut()
-        s.out, s.status = self.out.ptr, self.status.ptr
-        s.row_stride, s.sample_stride = self.n_stride * self.sample_stride, self.sample_stride
-        return s
-
-    def download(self):
-        return {"samples": self.out.download(np.float64, (self.rows, self.n_stride, self.sample_stride)),
-                "status": self.status.download(np.uint8, (self.n,))}
-
-    def free(self):
-        self.out.free()
-        self.status.free()
-
-
-class TrajTraverse:
-    """HBM-resident rows of mplx_traj_traverse_out for n trajectories."""
-
-    def __init__(self, env, n):
-        self.n = int(n)
-        n = max(self.n, 1)
-        self.status = DeviceArray(env, n)
-        self.cost = DeviceArray(env, n * 8)
-        self.n_samples, self.n_cells, self.stop_sample = (DeviceArray(env, n * 4) for _ in range(3))
-
-    def c_struct(self):
-        s = _abi.TrajTraverseOut()
-        s.status, s.cost = self.status.ptr, self.cost.ptr
-        s.n_samples, s.n_cells, s.stop_sample = self.n_samples.ptr, self.n_cells.ptr, self.stop_sample.ptr
-        return s
-
-    def download(self):
-        n = self.n
-        return {"status": self.status.download(np.uint8, (n,)), "cost": self.cost.download(np.float64, (n,)),
-                "n_samples": self.n_samples.download(np.int32, (n,)), "n_cells": self.n_cells.download(np.int32, (n,)),
-                "stop_sample": self.stop_sample.download(np.int32, (n,))}
-
-    def free(self):
-        for b in (self.status, self.cost, self.n_samples, self.n_cells, self.stop_sample):
-            b.free()
-
-
 def _solve_order(control):
     """Smoothing order of a control flag (traj_solver.h:22-27): 0 VEL, 1 ACC, 2 JRK."""
     try:
         return {VEL: 0, ACC: 1, JRK: 2}[int(control) & 0x0F]
     except KeyError:
         raise ValueError("the trajectory solver takes VEL, ACC or JRK controls, got %#x" % int(control))
-
-
-class SolveOut:
-    """HBM-resident rows of mplx_solve_out for n problems of up to w_max waypoints with smoothing order so."""
-
-    def __init__(self, env, n, w_max, so):
-        self.n, self.w_max, self.so, self.dim = int(n), int(w_max), int(so), env.dim
-        n, S = max(self.n, 1), self.w_max - 1
-        self.rows = S * 2 * (self.so + 1) * self.dim
-        self.status = DeviceArray(env, n)
-        self.n_segs = DeviceArray(env, n * 4)
-        self.total_time = DeviceArray(env, n * 8)
-        self.coeff = DeviceArray(env, max(self.rows, 1) * n * 8)
-        self.dts = DeviceArray(env, S * n * 8)
-        self.yaw_coeff = DeviceArray(env, 2 * S * n * 8)
-        self.taus = DeviceArray(env, self.w_max * n * 8)
-
-    def c_struct(self):
-        s = _abi.SolveOut()
-        s.status, s.n_segs, s.total_time = self.status.ptr, self.n_segs.ptr, self.total_time.ptr
-        s.coeff, s.dts_out, s.yaw_coeff, s.taus = self.coeff.ptr, self.dts.ptr, self.yaw_coeff.ptr, self.taus.ptr
-        s.coeff_stride = s.dts_out_stride = s.yaw_stride = s.taus_stride = self.n
-        return s
-
-    def download(self):
-        """Rows the solve did not own (failed problems, segments past S_k) hold whatever the buffers held."""
-        n, S = self.n, self.w_max - 1
-        return {"status": self.status.download(np.uint8, (n,)), "n_segs": self.n_segs.download(np.int32, (n,)),
-                "total_time": self.total_time.download(np.float64, (n,)),
-                "coeff": self.coeff.download(np.float64, (S, 2 * (self.so + 1), self.dim, n)),
-                "dts": self.dts.download(np.float64, (S, n)), "yaw_coeff": self.yaw_coeff.download(np.float64, (S, 2, n)),
-                "taus": self.taus.download(np.float64, (self.w_max, n))}
-
-    def free(self):
-        for b in (self.status, self.n_segs, self.total_time, self.coeff, self.dts, self.yaw_coeff, self.taus):
-            b.free()
-
-
-class LoadOut:
-    """HBM-resident rows of mplx_poly_load_out for n problems of up to w_max - 1 segments."""
-
-    def __init__(self, env, n, w_max):
-        self.n, self.w_max = int(n), int(w_max)
-        n = max(self.n, 1)
-        self.status, self.n_segs = DeviceArray(env, n), DeviceArray(env, n * 4)
-        self.total_time, self.taus = DeviceArray(env, n * 8), DeviceArray(env, self.w_max * n * 8)
-
-    def c_struct(self):
-        s = _abi.PolyLoadOut()
-        s.status, s.n_segs, s.total_time, s.taus, s.taus_stride = self.status.ptr, self.n_segs.ptr, self.total_time.ptr, self.taus.ptr, self.n
-        return s
-
-    def download(self):
-        """Rows the load did not own (failed problems, taus past S_k) hold whatever the buffers held."""
-        n = self.n
-        return {"status": self.status.download(np.uint8, (n,)), "n_segs": self.n_segs.download(np.int32, (n,)),
-                "total_time": self.total_time.download(np.float64, (n,)), "taus": self.taus.download(np.float64, (self.w_max, n))}
-
-    def free(self):
-        for b in (self.status, self.n_segs, self.total_time, self.taus):
-            b.free()
-
-
-class ShortcutResult:
-    """What EnvMap.shortcut / SearchResult.shortcut return (mplx_shortcut, include/mplx_limits.h).  poly: the PolyTrajSet of
-    the Q shortcut trajectories; pairs: the PolyTrajSet of the Q (w_max - 1) max_hop pair problems (pair (k, i, j) at
-    (k (w_max - 1) + i) max_hop + (j - i - 1)); per query status (0, SOLVE_EMPTY, SHORTCUT_BAD_CHAIN), keep (a list of
-    ascending state indices; keep_rows: the call's own [w_max][Q] rows, -1 past n_keep), cost, chain_cost; edge_cost
-    [Q][w_max - 1][max_hop] (+inf: not admitted).  free() it."""
-
-    def __init__(self, poly, pairs, max_hop, rows):
-        self.poly, self.pairs, self.max_hop = poly, pairs, int(max_hop)
-        self.status, self.n_keep, self.cost, self.chain_cost = rows["status"], rows["n_keep"], rows["cost"], rows["chain_cost"]
-        self.keep_rows = rows["keep"]
-        self.keep = [rows["keep"][:n, k].copy() for k, n in enumerate(self.n_keep)]
-        self.edge_cost = rows["edge_cost"]
-
-    def free(self):
-        self.poly.free()
-        self.pairs.free()
-
-
-class PolyLimits:
-    """HBM-resident rows of mplx_limits_out for n trajectories."""
-
-    def __init__(self, env, n):
-        self.n, self.dim = int(n), env.dim
-        n = max(self.n, 1)
-        self.max_vel, self.max_acc, self.max_jrk = (DeviceArray(env, self.dim * n * 8) for _ in range(3))
-        self.exceed, self.valid, self.first_bad = DeviceArray(env, n), DeviceArray(env, n), DeviceArray(env, n * 4)
-
-    def c_struct(self):
-        s = _abi.LimitsOut()
-        s.max_vel, s.max_acc, s.max_jrk, s.max_stride = self.max_vel.ptr, self.max_acc.ptr, self.max_jrk.ptr, self.n
-        s.exceed, s.valid, s.first_bad = self.exceed.ptr, self.valid.ptr, self.first_bad.ptr
-        return s
-
-    def download(self):
-        """Entries of failed problems hold whatever the buffers held."""
-        n, D = self.n, self.dim
-        return {"max_vel": self.max_vel.download(np.float64, (D, n)), "max_acc": self.max_acc.download(np.float64, (D, n)),
-                "max_jrk": self.max_jrk.download(np.float64, (D, n)), "exceed": self.exceed.download(np.uint8, (n,)),
-                "valid": self.valid.download(np.uint8, (n,)), "first_bad": self.first_bad.download(np.int32, (n,))}
-
-    def free(self):
-        for b in (self.max_vel, self.max_acc, self.max_jrk, self.exceed, self.valid, self.first_bad):
-            b.free()
-
-
-class LambdaRows:
-    """HBM-resident rows of mplx_lambda_out / mplx_scale_down_out for n problems of up to w_max waypoints, and of
-    mplx_tau_out when count > 0 ([n][count] each)."""
-
-    def __init__(self, env, n, w_max, count=0):
-        self.n, self.w_max, self.count = int(n), int(w_max), int(count)
-        n = max(self.n, 1)
-        self.status, self.scaled = DeviceArray(env, n), DeviceArray(env, n)
-        self.n_lseg = DeviceArray(env, n * 4)
-        self.total, self.max_l, self.t_lo, self.t_hi = (DeviceArray(env, n * 8) for _ in range(4))
-        self.Ts = DeviceArray(env, self.w_max * n * 8)
-        self.segs = DeviceArray(env, 64 * n * 8)
-        m = max(n * self.count, 1)
-        self.tau, self.lam, self.lam_dot = (DeviceArray(env, m * 8) for _ in range(3))
-        self.found = DeviceArray(env, m)
-
-    def _all(self):
-        return (self.status, self.scaled, self.n_lseg, self.total, self.max_l, self.t_lo, self.t_hi, self.Ts, self.segs, self.tau,
-                self.lam, self.lam_dot, self.found)
-
-    def fill(self, byte):
-        """Every row set to `byte` (to see afterwards what a call wrote)."""
-        for b in self._all():
-            _abi.check(b._env._ctx, _abi.lib().mplx_memset(b._env._ctx, b.ptr, int(byte), b.nbytes))
-
-    def c_struct(self):
-        s = _abi.LambdaOut()
-        s.status, s.n_lseg, s.total, s.Ts, s.ts_stride, s.segs, s.seg_stride = (self.status.ptr, self.n_lseg.ptr, self.total.ptr,
-                                                                                 self.Ts.ptr, self.n, self.segs.ptr, self.n)
-        return s
-
-    def c_down(self):
-        s = _abi.ScaleDownOut()
-        s.scaled, s.max_l, s.t_lo, s.t_hi, s.lam = self.scaled.ptr, self.max_l.ptr, self.t_lo.ptr, self.t_hi.ptr, self.c_struct()
-        return s
-
-    def c_tau(self):
-        s = _abi.TauOut()
-        s.tau, s.lam, s.lam_dot, s.found, s.stride = self.tau.ptr, self.lam.ptr, self.lam_dot.ptr, self.found.ptr, self.count
-        return s
-
-    def download(self):
-        """Entries a call did not own hold whatever the buffers held."""
-        n, c = self.n, self.count
-        d = {"status": self.status.download(np.uint8, (n,)), "n_lseg": self.n_lseg.download(np.int32, (n,)),
-             "total": self.total.download(np.float64, (n,)), "Ts": self.Ts.download(np.float64, (self.w_max, n)),
-             "segs": self.segs.download(np.float64, (8, 8, n)), "scaled": self.scaled.download(np.uint8, (n,)),
-             "max_l": self.max_l.download(np.float64, (n,)), "t_lo": self.t_lo.download(np.float64, (n,)),
-             "t_hi": self.t_hi.download(np.float64, (n,))}
-        if c:
-            d.update({"tau": self.tau.download(np.float64, (n, c)), "lambda": self.lam.download(np.float64, (n, c)),
-                      "lambda_dot": self.lam_dot.download(np.float64, (n, c)), "found": self.found.download(np.uint8, (n, c))})
-        return d
-
-    def free(self):
-        for b in self._all():
-            b.free()
-
-
-class Conflicts:
-    """HBM-resident rows of mplx_conflict_out for n trajectories; want_pairs: pair_first [n][n] int32 as well."""
-
-    def __init__(self, env, n, want_pairs=False):
-        self.n = int(n)
-        n = max(self.n, 1)
-        self.first_step, self.first_partner = DeviceArray(env, n * 4), DeviceArray(env, n * 4)
-        self.min_d2, self.status = DeviceArray(env, n * 8), DeviceArray(env, n)
-        self.pair_first = DeviceArray(env, n * n * 4) if want_pairs else None
-
-    def _all(self):
-        return [b for b in (self.first_step, self.first_partner, self.min_d2, self.status, self.pair_first) if b is not None]
-
-    def fill(self, byte):
-        """Every row set to `byte` (to see afterwards what a call wrote)."""
-        for b in self._all():
-            _abi.check(b._env._ctx, _abi.lib().mplx_memset(b._env._ctx, b.ptr, int(byte), b.nbytes))
-
-    def c_struct(self):
-        s = _abi.ConflictOut()
-        s.first_step, s.first_partner, s.min_d2, s.status = self.first_step.ptr, self.first_partner.ptr, self.min_d2.ptr, self.status.ptr
-        if self.pair_first is not None:
-            s.pair_first, s.pair_stride = self.pair_first.ptr, self.n
-        return s
-
-    def download(self):
-        n = self.n
-        d = {"first_step": self.first_step.download(np.int32, (n,)), "first_partner": self.first_partner.download(np.int32, (n,)),
-             "min_d2": self.min_d2.download(np.float64, (n,)), "status": self.status.download(np.uint8, (n,))}
-        if self.pair_first is not None:
-            d["pair_first"] = self.pair_first.download(np.int32, (n, n))
-        return d
-
-    def result(self, step):
-        """The rows as a ConflictResult (synchronize() first)."""
-        d = self.download()
-        return ConflictResult(step, d["first_step"], d["first_partner"], d["min_d2"], d["status"], d.get("pair_first"))
-
-    def free(self):
-        for b in self._all():
-            b.free()
-
-
-class ConflictResult:
-    """What conflicts() returns, per trajectory over the pairs charged to it (include/mplx_conflict.h): first_step (the
-    first instant with a conflict, -1: none), first_time (first_step * step; NaN: none), partner (the smallest index it
-    conflicts with at that instant, -1), min_d2 and min_dist = sqrt(min_d2) (the closest approach to a charged partner
-    while both are active; inf: none), status (the set's bits | CONFLICT_BAD_INPUT; a trajectory with any bit is
-    excluded: -1, -1, inf), and pairs [K][K] (want_pairs; the first instant at which two trajectories conflict regardless
-    of rank, symmetric, -1: never), else None."""
-
-    def __init__(self, step, first_step, partner, min_d2, status, pairs=None):
-        self.step = float(step)
-        self.first_step, self.partner, self.min_d2, self.status, self.pairs = first_step, partner, min_d2, status, pairs
-        self.first_time = np.where(first_step >= 0, first_step.astype(np.float64) * self.step, np.nan)
-        self.min_dist = np.sqrt(min_d2)
-
-    @property
-    def charged(self):
-        """[K] bool: the trajectory has a conflict charged to it."""
-        return self.first_step >= 0
-
-    def __repr__(self):
-        return "ConflictResult(%d of %d trajectories in conflict)" % (int(self.charged.sum()), len(self.first_step))
-
-
-def _conflict_in(K, step, n_steps, t0, radius, group, rank, park, chunk_steps, device):
-    """mplx_conflict_in from host arrays ([K] or a scalar to repeat) or, device=True, from device buffers; (struct, keep)."""
-    i, keep = _abi.ConflictIn(), []
-    i.step, i.n_steps, i.chunk_steps = float(step), int(n_steps), int(chunk_steps)
-    i.mode = CONFLICT_PARK if park else CONFLICT_GONE
-    if radius is None:
-        raise ValueError("conflicts: give a radius (a scalar or [K])")
-
-    def ptr(v, dtype):
-        if device:
-            return _device_ptr(v)
-        a = np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=dtype), (K,)))
-        keep.append(a)
-        return a.ctypes.data
-
-    if t0 is not None:
-        i.t0 = ptr(t0, np.float64)
-    if np.ndim(radius) == 0 and not hasattr(radius, "ptr") and not hasattr(radius, "data_ptr"):
-        i.radius_all = float(radius)
-    else:
-        i.radius = ptr(radius, np.float64)
-    if group is not None:
-        i.group = ptr(group, np.int32)
-    if rank is not None:
-        i.rank = ptr(rank, np.int32)
-    return i, keep
-
-
-def _conflict_steps(step, t0, total, ok):
-    """The smallest n_steps whose instants i * step cover max(t0 + total) over the trajectories without a status."""
-    if not (step > 0 and np.isfinite(step)):
-        raise ValueError("conflicts: step must be > 0 and finite")
-    K = len(total)
-    t0 = np.zeros(K) if t0 is None else np.broadcast_to(np.asarray(t0, dtype=np.float64), (K,))
-    end = np.where(np.asarray(ok, dtype=bool) & np.isfinite(t0), t0 + total, 0.0)
-    last = max(float(end.max()) if K else 0.0, 0.0)
-    return min(int(np.ceil(last / step)) + 1, 2 ** 31 - 1)
-
-
-def _conflict_host_out(K, want_pairs):
-    rows = {"first_step": np.full(K, -1, np.int32), "first_partner": np.full(K, -1, np.int32), "min_d2": np.full(K, np.inf),
-            "status": np.zeros(K, np.uint8)}
-    o = _abi.ConflictOut()
-    o.first_step, o.first_partner, o.min_d2, o.status = (rows[k].ctypes.data for k in ("first_step", "first_partner", "min_d2", "status"))
-    if want_pairs:
-        rows["pair_first"] = np.full((K, K), -1, np.int32)
-        o.pair_first, o.pair_stride = rows["pair_first"].ctypes.data, K
-    return rows, o
-
-
-class PolyTrajSet:
-    """K solved trajectories on the device (mplx_poly of include/mplx_solve.h): what EnvMap.solve_traj returns and what
-    EnvMap.solve_traj_resident solves into.  status [K] (SOLVE_EMPTY | SOLVE_BAD_TIME | SOLVE_SINGULAR; 0 = solved);
-    a failed problem has no samples and traverses as an empty trajectory.  free() it before the EnvMap is closed."""
-
-    def __init__(self, env, k_cap, w_max):
-        self._env, self.k_cap, self.w_max = env, int(k_cap), int(w_max)
-        self.n, self.so, self.n_wmax, self.control = 0, None, 0, None
-        self._host, self._out, self._lambda = None, None, None
-        h = C.c_void_p()
-        _abi.check(env._ctx, _abi.lib().mplx_poly_create(env._ctx, self.k_cap, self.w_max, C.byref(h)))
-        self._h = h
-
-    def free(self):
-        if self._h is not None and self._env._ctx:
-            _abi.lib().mplx_poly_destroy(self._h)
-        self._h = None
-        if self._out is not None:
-            self._out.free()
-            self._out = None
-
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
-
-    def _rows(self):
-        """The rows of the last solve or load on the host: from the host-pointer call, or downloaded from the SolveOut /
-        LoadOut of the resident one."""
-        if self._host is None:
-            if self._out is None:
-                raise RuntimeError("PolyTrajSet: the resident solve or load kept no output rows (no `out` was given)")
-            self._env.synchronize()
-            d = self._out.download()
-            ok = d["status"] == 0
-            d["n_segs"] = np.where(ok, d["n_segs"], 0)
-            d["total_time"] = np.where(ok, d["total_time"], 0.0)
-            if "coeff" in d:  # a SolveOut
-                seg = np.arange(self._out.w_max - 1)[:, None] < d["n_segs"][None, :]
-                d["coeff"] = np.where(seg[:, None, None, :], d["coeff"], 0.0)
-                d["dts"] = np.where(seg, d["dts"], 0.0)
-                d["yaw_coeff"] = np.where(seg[:, None, :], d["yaw_coeff"], 0.0)
-            d["taus"] = np.where((np.arange(self._out.w_max)[:, None] <= d["n_segs"][None, :]) & ok[None, :], d["taus"], 0.0)
-            self._host = d
-        return self._host
-
-    @property
-    def status(self):
-        return self._rows()["status"]
-
-    @property
-    def n_segs(self):
-        return self._rows()["n_segs"]
-
-    @property
-    def total_time(self):
-        return self._rows()["total_time"]
-
-    def coefficients(self):
-        """PolyTraj::p() of every problem: [w_max - 1][N][D][K], coefficient r of axis i of segment s at [s][r][i][k]
-        (increasing powers of the segment's own time); zero past S_k and for a failed problem.  A solved set only."""
-        if "coeff" not in self._rows():
-            raise RuntimeError("PolyTrajSet: a loaded set has segments(), not the solver's coefficients()")
-        return self._rows()["coeff"]
-
-    def yaw_coefficients(self):
-        """The yaw solve's p: [w_max - 1][2][K].  A solved set only."""
-        if "yaw_coeff" not in self._rows():
-            raise RuntimeError("PolyTrajSet: a loaded set has segments(), not the solver's yaw_coefficients()")
-        return self._rows()["yaw_coeff"]
-
-    def segments(self):
-        """The primitives of every problem as EnvMap.load_traj takes them: [w_max - 1][D + 1][6][K], c(0) .. c(5) of
-        primitive.h:128-131 for axis a of segment s at [s][a][:][k], axis D the yaw primitive; zero past S_k.  A loaded set
-        returns what was loaded; a solved set PolyTraj::toPrimitives of its coefficients (c_j = p_{5-j} (5-j)!, the
-        multiplication the device made)."""
-        r = self._rows()
-        if "segments" not in r and "coeff" not in r:
-            raise RuntimeError("PolyTrajSet: a set loaded with load_traj_resident keeps its dts and segments on the device only")
-        if "segments" not in r:
-            p, yaw = r["coeff"], r["yaw_coeff"]
-            S, N, D, K = p.shape
-            seg = np.zeros((S, D + 1, 6, K))
-            fact = [1.0, 1.0, 2.0, 6.0, 24.0, 120.0]
-            for j in range(6):
-                if 5 - j < N:
-                    seg[:, :D, j, :] = p[:, 5 - j, :, :] * fact[5 - j]
-            seg[:, D, 4, :], seg[:, D, 5, :] = yaw[:, 1, :] * 1.0, yaw[:, 0, :] * 1.0
-            r["segments"] = seg
-        return r["segments"]
-
-    def dts(self):
-        """[w_max - 1][K] segment durations (given, or allocate_time's); zero past S_k.  Not for a set loaded from
-        device buffers (load_traj_resident): its segments and durations are the caller's own arrays."""
-        if "dts" not in self._rows():
-            raise RuntimeError("PolyTrajSet: a set loaded with load_traj_resident keeps its dts and segments on the device only")
-        return self._rows()["dts"]
-
-    def taus(self):
-        """[w_max][K]: taus[0 .. S_k] by sequential addition of dts."""
-        return self._rows()["taus"]
-
-    def _need(self):
-        if self._h is None or self.n == 0:
-            raise RuntimeError("PolyTrajSet: nothing solved (or freed)")
-        self._env._flush()
-
-    def info(self, want_states=False):
-        """status, n_segs, total_time, effort [5][K] = J(VEL), J(ACC), J(JRK), J(SNP), Jyaw of the solved primitives;
-        want_states: seg_state [4D+2][w_max][K], the waypoints (mplx_poly_info; synchronous)."""
-        self._need()
-        K, env = self.n, self._env
-        out = {"status": np.zeros(K, np.uint8), "n_segs": np.zeros(K, np.int32), "total_time": np.zeros(K, np.float64),
-               "effort": np.zeros((5, K), np.float64)}
-        o = _abi.TrajInfoOut()
-        o.status, o.n_segs, o.total_time = out["status"].ctypes.data, out["n_segs"].ctypes.data, out["total_time"].ctypes.data
-        o.effort, o.effort_stride = out["effort"].ctypes.data, K
-        if want_states:
-            out["seg_state"] = np.zeros((env.n_fields, self.n_wmax, K), np.float64)
-            o.seg_state, o.seg_stride = out["seg_state"].ctypes.data, K
-        _abi.check(env._ctx, _abi.lib().mplx_poly_info(self._h, C.byref(o)))
-        return out
-
-    def sample(self, N=None, times=None, form=TRAJ_COMMAND, out=None):
-        """As EnvMap.traj_sample on the solved set (mplx_poly_sample; synchronous): samples [4D+3][K][count], status."""
-        self._need()
-        K, env = self.n, self._env
-        t, tkeep, count = env._traj_times(N, times, form, K)
-        rows = 4 * env.dim + 3
-        if out is None:
-            out = np.zeros((rows, K, max(count, 0)), np.float64)
-        if out.dtype != np.float64 or not out.flags.c_contiguous or out.ndim != 3 or out.shape[0] != rows or out.shape[1] < K:
-            raise ValueError("out must be a C-contiguous float64 [%d][>= K][count']" % rows)
-        status = np.zeros(K, np.uint8)
-        o = _abi.TrajSampleOut()
-        o.out, o.row_stride, o.sample_stride, o.status = out.ctypes.data, out.shape[1] * out.shape[2], out.shape[2], status.ctypes.data
-        _abi.check(env._ctx, _abi.lib().mplx_poly_sample(self._h, C.byref(t), C.byref(o)))
-        return {"samples": out, "status": status}
-
-    def traverse(self, lanes=0):
-        """As EnvMap.traj_traverse on the solved set, on the maps the device holds now (mplx_poly_traverse)."""
-        self._need()
-        K, env = self.n, self._env
-        out = {"status": np.zeros(K, np.uint8), "cost": np.zeros(K, np.float64), "n_samples": np.zeros(K, np.int32),
-               "n_cells": np.zeros(K, np.int32), "stop_sample": np.zeros(K, np.int32)}
-        o = _abi.TrajTraverseOut()
-        for key in out:
-            setattr(o, key, out[key].ctypes.data)
-        _abi.check(env._ctx, _abi.lib().mplx_poly_traverse(self._h, int(lanes), C.byref(o)))
-        return out
-
-    def limits(self, v_max=None, a_max=None, j_max=None, all_roots=False):
-        """Primitive::max_vel / max_acc / max_jrk and validate_primitive of every trajectory (mplx_poly_limits;
-        synchronous).  Limits default to the EnvMap's; <= 0 means not checked.  all_roots=False is the reference, which
-        stops at the first root past the segment's end and so often misses the true peak; all_roots=True looks at every
-        root (include/mplx_limits.h).  Returns max_vel / max_acc / max_jrk [D][K] (per axis, the maximum over the
-        segments), exceed [K] (EXCEED_VEL | EXCEED_ACC | EXCEED_JRK), valid [K] (under the set's control) and first_bad
-        [K] (segment or -1); entries of failed problems are zero (valid 0, first_bad -1)."""
-        self._need()
-        K, env = self.n, self._env
-        out = {"max_vel": np.zeros((env.dim, K)), "max_acc": np.zeros((env.dim, K)), "max_jrk": np.zeros((env.dim, K)),
-               "exceed": np.zeros(K, np.uint8), "valid": np.zeros(K, np.uint8), "first_bad": np.full(K, -1, np.int32)}
-        o = _abi.LimitsOut()
-        for key in out:
-            setattr(o, key, out[key].ctypes.data)
-        o.max_stride = K
-        _abi.check(env._ctx, _abi.lib().mplx_poly_limits(self._h, C.byref(self._limits_in(v_max, a_max, j_max, all_roots)),
-                                                          C.byref(o)))
-        return out
-
-    def _limits_in(self, v_max, a_max, j_max, all_roots):
-        p, i = self._env._p, _abi.LimitsIn()
-        i.mv = float(p.v_max if v_max is None else v_max)
-        i.ma = float(p.a_max if a_max is None else a_max)
-        i.mj = float(p.j_max if j_max is None else j_max)
-        i.mode = LIMITS_ALL_ROOTS if all_roots else LIMITS_REFERENCE
-        return i
-
-    # asynchronous forms on HBM-resident rows (env.TrajInfo / TrajSamples / TrajTraverse); synchronize() before reading
-    def limits_resident(self, out, v_max=None, a_max=None, j_max=None, all_roots=False):
-        """out: EnvMap.alloc_poly_limits(n)."""
-        self._need()
-        o = out.c_struct()
-        _abi.check(self._env._ctx, _abi.lib().mplx_poly_limits_device(self._h, C.byref(self._limits_in(v_max, a_max, j_max, all_roots)),
-                                                                       C.byref(o)))
-
-    def info_resident(self, out):
-        self._need()
-        o = out.c_struct()
-        _abi.check(self._env._ctx, _abi.lib().mplx_poly_info_device(self._h, C.byref(o)))
-
-    def sample_resident(self, out, N=None, times=None, n_times=None, time_stride=0, form=TRAJ_COMMAND):
-        self._need()
-        t = _abi.TrajTimes()
-        t.form = int(form)
-        if N is not None:
-            t.n_uniform = int(N)
-        else:
-            t.times, t.n_times, t.time_stride = _device_ptr(times), int(n_times), int(time_stride)
-        o = out.c_struct()
-        _abi.check(self._env._ctx, _abi.lib().mplx_poly_sample_device(self._h, C.byref(t), C.byref(o)))
-
-    def traverse_resident(self, out, lanes=0):
-        self._need()
-        o = out.c_struct()
-        _abi.check(self._env._ctx, _abi.lib().mplx_poly_traverse_device(self._h, int(lanes), C.byref(o)))
-
-    # ---- conflicts between the trajectories of the set on a common clock (include/mplx_conflict.h)
-    def conflicts(self, step, n_steps=None, t0=None, radius=None, group=None, rank=None, park=True, want_pairs=False, chunk_steps=0):
-        """Which trajectories come closer than the sum of their radii, when first and with whom (mplx_poly_conflicts;
-        synchronous).  Instant i is at i * step on a clock on which trajectory k starts at t0[k] (None: 0); positions are
-        those of sample() at i * step - t0[k].  n_steps=None: the smallest count that covers max(t0 + total), from the
-        totals on the host.  radius: a scalar or [K].  group [K]: trajectories of one group never conflict (the n_v
-        candidates of one robot in the Q x n_v layout of smooth(v=[...])).  rank [K]: a conflict is charged to a only if
-        rank[b] <= rank[a] (the larger rank yields, equal ranks both do); None: to both.  park=True: a robot waits at its
-        start before t0 and at its end afterwards; False: it exists only during its own trajectory.  chunk_steps: the
-        instants per pass, 0 automatic; no result depends on it.  Returns a ConflictResult."""
-        self._need()
-        K = self.n
-        if n_steps is None:
-            inf = self.info()
-            n_steps = _conflict_steps(float(step), t0, inf["total_time"], inf["status"] == 0)
-        i, keep = _conflict_in(K, step, n_steps, t0, radius, group, rank, park, chunk_steps, False)
-        rows, o = _conflict_host_out(K, want_pairs)
-        _abi.check(self._env._ctx, _abi.lib().mplx_poly_conflicts(self._h, C.byref(i), C.byref(o)))
-        return ConflictResult(step, rows["first_step"], rows["first_partner"], rows["min_d2"], rows["status"], rows.get("pair_first"))
-
-    def conflicts_resident(self, out, step, n_steps, t0=None, radius=None, group=None, rank=None, park=True, chunk_steps=0):
-        """Asynchronous (mplx_poly_conflicts_device).  out: EnvMap.alloc_conflicts(n, want_pairs); t0 / radius / group /
-        rank: device buffers of [K] (radius may be a scalar) or None; n_steps must be given: nothing is read back."""
-        self._need()
-        i, keep = _conflict_in(self.n, step, n_steps, t0, radius, group, rank, park, chunk_steps, True)
-        o = out.c_struct()
-        _abi.check(self._env._ctx, _abi.lib().mplx_poly_conflicts_device(self._h, C.byref(i), C.byref(o)))
-
-    # ---- time scaling (include/mplx_scale.h): a Lambda per problem.  robust=False is the reference with its quirks (the
-    # 1e-5 clamp of its coefficients, a getTau that loses the end points); robust=True validates the points, applies
-    # no clamp and inverts the time map by Newton steps.  Afterwards sample() takes real times, info() reports the
-    # scaled total and traverse() is refused until clear_lambda().
-    def _lambda_host(self):
-        K = self.n
-        rows = {"status": np.zeros(K, np.uint8), "n_lseg": np.zeros(K, np.int32), "total": np.zeros(K, np.float64),
-                "Ts": np.zeros((self.n_wmax, K), np.float64), "segs": np.zeros((8, 8, K), np.float64)}
-        o = _abi.LambdaOut()
-        o.status, o.n_lseg, o.total = rows["status"].ctypes.data, rows["n_lseg"].ctypes.data, rows["total"].ctypes.data
-        o.Ts, o.ts_stride, o.segs, o.seg_stride = rows["Ts"].ctypes.data, K, rows["segs"].ctypes.data, K
-        return rows, o
-
-    def _keep_lambda(self, rows):
-        self._lambda = {k: rows[k] for k in ("status", "n_lseg", "total", "Ts", "segs")}
-        return rows
-
-    @staticmethod
-    def _mode(robust):
-        return SCALE_ROBUST if robust else SCALE_REFERENCE
-
-    def _scale_in(self, ri, rf, robust, keep):
-        i = _abi.ScaleIn()
-        i.mode = self._mode(robust)
-        for name, v in (("ri", ri), ("rf", rf)):
-            if np.ndim(v) == 0:
-                setattr(i, name, float(v))
-            else:
-                a = np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=np.float64), (self.n,)))
-                keep.append(a)
-                setattr(i, name + "_arr", a.ctypes.data)
-        return i
-
-    def scale(self, ri, rf, robust=True):
-        """Trajectory::scale(ri, rf) on every trajectory (mplx_poly_scale; synchronous): ri, rf scalars or [K] ratios at
-        the start and the end.  Returns status [K] (0, LAMBDA_BAD_POINTS, LAMBDA_NOT_POSITIVE), n_lseg, total, Ts, segs;
-        entries of failed problems are zero."""
-        self._need()
-        keep = []
-        rows, o = self._lambda_host()
-        i = self._scale_in(ri, rf, robust, keep)
-        _abi.check(self._env._ctx, _abi.lib().mplx_poly_scale(self._h, C.byref(i), C.byref(o)))
-        return self._keep_lambda(rows)
-
-    def _down_in(self, v_max, a_max, ri, rf, robust):
-        p, i = self._env._p, _abi.ScaleDownIn()
-        i.mv = float(p.v_max if v_max is None else v_max)
-        i.ma = float(p.a_max if a_max is None else a_max)
-        i.ri, i.rf, i.mode = float(ri), float(rf), self._mode(robust)
-        return i
-
-    def scale_down(self, v_max=None, a_max=None, ri=0.0, rf=0.0, robust=True):
-        """Slow every trajectory that breaks v_max / a_max (default: the EnvMap's; <= 0: not checked) down to them
-        (mplx_poly_scale_down; synchronous).  ri, rf: lambda at the two ends, <= 0: max_l, i.e. no ramp; with both the
-        scaling is uniform and within the limits by construction -- ramps are NOT checked against the limits.  Returns
-        scaled [K] (0: within the limits, left unscaled), max_l, t_lo, t_hi and the rows of scale()."""
-        self._need()
-        K = self.n
-        rows, lo = self._lambda_host()
-        rows.update({"scaled": np.zeros(K, np.uint8), "max_l": np.zeros(K), "t_lo": np.zeros(K), "t_hi": np.zeros(K)})
-        o = _abi.ScaleDownOut()
-        o.scaled, o.max_l, o.t_lo, o.t_hi, o.lam = (rows["scaled"].ctypes.data, rows["max_l"].ctypes.data, rows["t_lo"].ctypes.data,
-                                                    rows["t_hi"].ctypes.data, lo)
-        i = self._down_in(v_max, a_max, ri, rf, robust)
-        _abi.check(self._env._ctx, _abi.lib().mplx_poly_scale_down(self._h, C.byref(i), C.byref(o)))
-        return self._keep_lambda(rows)
-
-    @staticmethod
-    def _points(p, v, t, K):
-        """[9][3][K] rows of p, v, t given as [n_max][K] (or [n_max]: the same for every problem)."""
-        cols = [np.asarray(x, dtype=np.float64) for x in (p, v, t)]
-        cols = [np.broadcast_to(x[:, None], (x.shape[0], K)) if x.ndim == 1 else x for x in cols]
-        n_max = cols[0].shape[0]
-        if n_max > 9 or any(x.shape != (n_max, K) for x in cols):
-            raise ValueError("p, v, t must be [n <= 9][K] (or [n <= 9])")
-        pts = np.zeros((9, 3, K))
-        for f, x in enumerate(cols):
-            pts[:n_max, f, :] = x
-        return pts, n_max
-
-    def set_lambda(self, p, v, t, n_pts=None, robust=True):
-        """Lambda(vs) from virtual points (mplx_poly_set_lambda; synchronous): p, v, t [n_max][K] (or [n_max]), point j of
-        problem k at [j][k], j < n_pts[k] (None: n_max each).  Returns the rows of scale()."""
-        self._need()
-        K = self.n
-        pts, n_max = self._points(p, v, t, K)
-        n = np.ascontiguousarray(np.broadcast_to(np.asarray(n_max if n_pts is None else n_pts, dtype=np.int32), (K,)))
-        rows, o = self._lambda_host()
-        i = _abi.LambdaIn()
-        i.pts, i.stride, i.n_pts, i.mode = pts.ctypes.data, K, n.ctypes.data, self._mode(robust)
-        _abi.check(self._env._ctx, _abi.lib().mplx_poly_set_lambda(self._h, C.byref(i), C.byref(o)))
-        return self._keep_lambda(rows)
-
-    def clear_lambda(self):
-        """Every trajectory is unscaled again."""
-        self._need()
-        _abi.check(self._env._ctx, _abi.lib().mplx_poly_clear_lambda(self._h))
-        self._lambda = None
-
-    def _lambda_rows(self):
-        rows = self._lambda
-        if rows is None:
-            raise RuntimeError("PolyTrajSet: no Lambda (scale, scale_down or set_lambda first; the _resident forms keep theirs on the device)")
-        return rows
-
-    def lambda_segments(self):
-        """The Lambda of every problem as the last synchronous scale / scale_down / set_lambda left it: a [8][4][K] (a3 a2
-        a1 a0 of segment s at [s][:][k]), ti, tf, T0 (getT(ti)), dT [8][K], n_lseg [K], status [K]."""
-        r = self._lambda_rows()
-        g = r["segs"]
-        return {"a": g[:, 0:4, :], "ti": g[:, 4, :], "tf": g[:, 5, :], "T0": g[:, 6, :], "dT": g[:, 7, :], "n_lseg": r["n_lseg"],
-                "status": r["status"]}
-
-    def segment_times(self):
-        """Trajectory::getSegmentTimes: [w_max - 1][K], Ts[s + 1] - Ts[s]; zero past S_k and for a problem without a
-        Lambda status 0."""
-        r = self._lambda_rows()
-        Ts = r["Ts"]
-        ok = (np.arange(self.n_wmax - 1)[:, None] < self.n_segs[None, :]) & (r["n_lseg"] > 0)[None, :]
-        return np.where(ok, Ts[1:] - Ts[:-1], 0.0)
-
-    def tau(self, times=None, N=None):
-        """The inverse time map (mplx_poly_tau; synchronous): tau, lambda, lambda_dot [K][count] and found [K][count] at
-        the real times `times` ([Q] or [K][Q]) or at the N + 1 uniform ones."""
-        self._need()
-        K, env = self.n, self._env
-        t, tkeep, count = env._traj_times(N, times, TRAJ_COMMAND, K)
-        out = {"tau": np.zeros((K, count)), "lambda": np.zeros((K, count)), "lambda_dot": np.zeros((K, count)),
-               "found": np.zeros((K, count), np.uint8)}
-        o = _abi.TauOut()
-        o.tau, o.lam, o.lam_dot, o.found, o.stride = (out["tau"].ctypes.data, out["lambda"].ctypes.data, out["lambda_dot"].ctypes.data,
-                                                      out["found"].ctypes.data, count)
-        _abi.check(env._ctx, _abi.lib().mplx_poly_tau(self._h, C.byref(t), C.byref(o)))
-        return out
-
-    # asynchronous forms on HBM-resident rows (EnvMap.alloc_lambda_rows); synchronize() before reading
-    def scale_resident(self, out, ri, rf, robust=True):
-        """ri, rf: scalars, or DeviceArrays of [K] float64."""
-        self._need()
-        i = _abi.ScaleIn()
-        i.mode = self._mode(robust)
-        for name, v in (("ri", ri), ("rf", rf)):
-            if np.ndim(v) == 0 and not hasattr(v, "ptr") and not hasattr(v, "data_ptr"):
-                setattr(i, name, float(v))
-            else:
-                setattr(i, name + "_arr", _device_ptr(v))
-        o = out.c_struct()
-        _abi.check(self._env._ctx, _abi.lib().mplx_poly_scale_device(self._h, C.byref(i), C.byref(o)))
-        self._lambda = None
-
-    def scale_down_resident(self, out, v_max=None, a_max=None, ri=0.0, rf=0.0, robust=True):
-        self._need()
-        o = out.c_down()
-        i = self._down_in(v_max, a_max, ri, rf, robust)
-        _abi.check(self._env._ctx, _abi.lib().mplx_poly_scale_down_device(self._h, C.byref(i), C.byref(o)))
-        self._lambda = None
-
-    def set_lambda_resident(self, out, pts, n_pts=None, stride=None, robust=True):
-        """pts: [9][3][stride] float64 on the device; n_pts: [K] int32 on the device or None (9 each)."""
-        self._need()
-        i = _abi.LambdaIn()
-        i.pts, i.stride, i.mode = _device_ptr(pts), self.n if stride is None else int(stride), self._mode(robust)
-        if n_pts is not None:
-            i.n_pts = _device_ptr(n_pts)
-        o = out.c_struct()
-        _abi.check(self._env._ctx, _abi.lib().mplx_poly_set_lambda_device(self._h, C.byref(i), C.byref(o)))
-        self._lambda = None
-
-    def tau_resident(self, out, N=None, times=None, n_times=None, time_stride=0):
-        """out: alloc_lambda_rows(n, w_max, count) with count >= the sample count."""
-        self._need()
-        t = _abi.TrajTimes()
-        if N is not None:
-            t.n_uniform = int(N)
-        else:
-            t.times, t.n_times, t.time_stride = _device_ptr(times), int(n_times), int(time_stride)
-        o = out.c_tau()
-        _abi.check(self._env._ctx, _abi.lib().mplx_poly_tau_device(self._h, C.byref(t), C.byref(o)))
 
 
 STATE_ROW_PAD = 0  # default padding between the state rows of Lists, in entries (see Lists.state_stride)
@@ -1727,19 +806,7 @@ class EnvMap:
             starts = starts.reshape(-1, 1)
         if starts.shape[0] != self.n_fields or starts.shape[1] not in (1, K):
             raise ValueError("starts must be [%d][%d] or one state" % (self.n_fields, K))
-        out = {"status": np.zeros(K, np.uint8), "steps": np.zeros(K, np.int32), "cost": np.zeros(K, np.float64),
-               "prefix_cost": np.zeros(K, np.float64)}
-        o = _abi.RolloutOut()
-        o.status, o.steps, o.cost = out["status"].ctypes.data, out["steps"].ctypes.data, out["cost"].ctypes.data
-        o.prefix_cost = out["prefix_cost"].ctypes.data
-        if want_end:
-            out["end_state"] = np.zeros((self.n_fields, K), np.float64)
-            out["end_hash"] = np.zeros(K, np.uint64)
-            o.end_state, o.end_stride, o.end_hash = out["end_state"].ctypes.data, K, out["end_hash"].ctypes.data
-        if want_goal_rows:
-            out["end_heur"] = np.zeros(K, np.float64)
-            out["end_flags"] = np.zeros(K, np.uint8)
-            o.end_heur, o.end_flags = out["end_heur"].ctypes.data, out["end_flags"].ctypes.data
+        out, o = Rollouts.host(self, K, want_end, want_goal_rows)
         _abi.check(self._ctx, _abi.lib().mplx_rollout(self._ctx, starts.ctypes.data, starts.shape[1], starts.shape[1],
                                                        actions.ctypes.data, K, H, K, C.byref(o)))
         return out
@@ -1792,16 +859,11 @@ class EnvMap:
             p2_stride = n
         else:
             raise ValueError("p2 must be [%d][%d] or one point" % (D, n))
-        out = {"status": np.zeros(n, np.uint8), "n_cells": np.zeros(n, np.int32), "first_hit": np.zeros(n, np.int32)}
-        o = _abi.RayOut()
-        o.status, o.n_cells, o.first_hit = out["status"].ctypes.data, out["n_cells"].ctypes.data, out["first_hit"].ctypes.data
-        if cell_cap > 0:
-            if cells is None:
-                cells = np.zeros((n, int(cell_cap)), np.int32)
+        out, o = Rays.host(self, n, cell_cap)
+        if cell_cap > 0 and cells is not None:  # the caller's array instead of zeros
             if cells.shape != (n, int(cell_cap)) or cells.dtype != np.int32 or not cells.flags.c_contiguous:
                 raise ValueError("cells must be a contiguous int32 [%d][%d]" % (n, cell_cap))
-            out["cells"] = cells
-            o.cells, o.cell_cap = cells.ctypes.data, int(cell_cap)
+            out["cells"], o.cells = cells, cells.ctypes.data
         _abi.check(self._ctx, _abi.lib().mplx_ray_trace(self._ctx, p1.ctypes.data, p2.ctypes.data, n, n, p2_stride,
                                                          int(lanes), C.byref(o)))
         return out
@@ -1879,14 +941,7 @@ class EnvMap:
         No validity check of any kind is made (mplx_traj_info; synchronous)."""
         self._flush()
         s, keep, K, H = self._traj_host_set(starts, actions)
-        out = {"status": np.zeros(K, np.uint8), "n_segs": np.zeros(K, np.int32), "total_time": np.zeros(K, np.float64),
-               "effort": np.zeros((5, K), np.float64)}
-        o = _abi.TrajInfoOut()
-        o.status, o.n_segs, o.total_time = out["status"].ctypes.data, out["n_segs"].ctypes.data, out["total_time"].ctypes.data
-        o.effort, o.effort_stride = out["effort"].ctypes.data, K
-        if want_states:
-            out["seg_state"] = np.zeros((self.n_fields, H + 1, K), np.float64)
-            o.seg_state, o.seg_stride = out["seg_state"].ctypes.data, K
+        out, o = TrajInfo.host(self, K, H, want_states)
         _abi.check(self._ctx, _abi.lib().mplx_traj_info(self._ctx, C.byref(s), C.byref(o)))
         return out
 
@@ -1937,11 +992,7 @@ class EnvMap:
         lanes: 0 (automatic) or 4 / 16 / 64 lanes of a wavefront per trajectory; the results do not depend on it."""
         self._flush()
         s, keep, K, H = self._traj_host_set(starts, actions)
-        out = {"status": np.zeros(K, np.uint8), "cost": np.zeros(K, np.float64), "n_samples": np.zeros(K, np.int32),
-               "n_cells": np.zeros(K, np.int32), "stop_sample": np.zeros(K, np.int32)}
-        o = _abi.TrajTraverseOut()
-        for key in out:
-            setattr(o, key, out[key].ctypes.data)
+        out, o = TrajTraverse.host(self, K)
         _abi.check(self._ctx, _abi.lib().mplx_traj_traverse(self._ctx, C.byref(s), int(lanes), C.byref(o)))
         return out
 
@@ -2067,14 +1118,7 @@ class EnvMap:
                 wp_flags = np.ascontiguousarray(np.asarray(wp_flags, dtype=np.uint8).reshape(W, K))
                 i.wp_flags, i.flag_stride = wp_flags.ctypes.data, K
             i.control, i.yaw_control = control, int(yaw_control)
-            N, S = 2 * (so + 1), W - 1
-            host = {"status": np.zeros(K, np.uint8), "n_segs": np.zeros(K, np.int32), "total_time": np.zeros(K, np.float64),
-                    "coeff": np.zeros((S, N, self.dim, K)), "dts": np.zeros((S, K)), "yaw_coeff": np.zeros((S, 2, K)),
-                    "taus": np.zeros((W, K))}
-            o = _abi.SolveOut()
-            o.status, o.n_segs, o.total_time = host["status"].ctypes.data, host["n_segs"].ctypes.data, host["total_time"].ctypes.data
-            o.coeff, o.dts_out, o.yaw_coeff, o.taus = (host[k].ctypes.data for k in ("coeff", "dts", "yaw_coeff", "taus"))
-            o.coeff_stride = o.dts_out_stride = o.yaw_stride = o.taus_stride = K
+            host, o = SolveOut.host(self, K, W, so)
             _abi.check(self._ctx, _abi.lib().mplx_solve(poly._h, C.byref(i), C.byref(o)))
             poly.n, poly.so, poly.n_wmax, poly._host, poly.control = K, so, W, host, control
             poly._lambda = None  # a new solve or load clears the Lambda
@@ -2148,11 +1192,7 @@ class EnvMap:
                 n_segs = np.ascontiguousarray(np.broadcast_to(np.asarray(n_segs, dtype=np.int32), (K,)))
                 i.n_segs = n_segs.ctypes.data
             i.dts, i.dt_stride, i.coeff, i.coeff_stride = dts.ctypes.data, K, c.ctypes.data, K
-            host = {"status": np.zeros(K, np.uint8), "n_segs": np.zeros(K, np.int32), "total_time": np.zeros(K, np.float64),
-                    "taus": np.zeros((S + 1, K))}
-            o = _abi.PolyLoadOut()
-            o.status, o.n_segs, o.total_time = host["status"].ctypes.data, host["n_segs"].ctypes.data, host["total_time"].ctypes.data
-            o.taus, o.taus_stride = host["taus"].ctypes.data, K
+            host, o = LoadOut.host(self, K, S + 1)
             _abi.check(self._ctx, _abi.lib().mplx_poly_load(poly._h, C.byref(i), C.byref(o)))
             seg = np.arange(S)[:, None] < host["n_segs"][None, :]
             host["dts"] = np.where(seg, dts, 0.0)
@@ -2376,9 +1416,11 @@ class EnvMap:
         the goal STATE minimised over the arrival time, never below the default; with a field the larger of the two.  A
         replan keeps the mode.  heur together with prior is a ValueError."""
         from .search import run_search
-        return run_search(self, start, goal_row, eps, delta, g_max, max_rounds, max_expand, capacity, max_frontier,
-                          lists_stride, sight, tol_pos, tol_vel, tol_acc, tol_yaw, w, v_max, start_g, prior, avoid, t0, radius,
-                          ignore_group, time_keys, wait, park_goal, field, field_of_query, heur)
+        return run_search(self, start, goal_row, prior=prior, eps=eps, delta=delta, g_max=g_max, max_rounds=max_rounds,
+                          max_expand=max_expand, capacity=capacity, max_frontier=max_frontier, lists_stride=lists_stride,
+                          sight=sight, tol_pos=tol_pos, tol_vel=tol_vel, tol_acc=tol_acc, tol_yaw=tol_yaw, w=w, v_max=v_max,
+                          start_g=start_g, avoid=avoid, t0=t0, radius=radius, ignore_group=ignore_group, time_keys=time_keys,
+                          wait=wait, park_goal=park_goal, field=field, field_of_query=field_of_query, heur=heur)
 
     def search_many(self, starts, goal_rows, eps=1.0, delta=None, g_max=float("inf"), max_rounds=None, max_expand=None,
                     capacity=1 << 16, max_frontier=None, lists_stride=None, sight=True, tol_pos=0.5, tol_vel=-1.0,
@@ -2398,9 +1440,12 @@ class EnvMap:
         share one); a GoalField is used with field_of_query [Q] (default: query q uses field q; -1: the default heuristic).
         heur: as EnvMap.search takes it; every query's own goal is the one its rows are measured against."""
         from .search import run_search_many
-        return run_search_many(self, starts, goal_rows, eps, delta, g_max, max_rounds, max_expand, capacity, max_frontier,
-                               lists_stride, sight, tol_pos, tol_vel, tol_acc, tol_yaw, w, v_max, start_g, priors, avoid, t0,
-                               radius, ignore_group, time_keys, wait, park_goal, field, field_of_query, heur)
+        return run_search_many(self, starts, goal_rows, priors=priors, eps=eps, delta=delta, g_max=g_max, max_rounds=max_rounds,
+                               max_expand=max_expand, capacity=capacity, max_frontier=max_frontier, lists_stride=lists_stride,
+                               sight=sight, tol_pos=tol_pos, tol_vel=tol_vel, tol_acc=tol_acc, tol_yaw=tol_yaw, w=w,
+                               v_max=v_max, start_g=start_g, avoid=avoid, t0=t0, radius=radius, ignore_group=ignore_group,
+                               time_keys=time_keys, wait=wait, park_goal=park_goal, field=field, field_of_query=field_of_query,
+                               heur=heur)
 
     def _heur_goal(self, goal_row, goal_control, w, v_max):
         goal = np.ascontiguousarray(goal_row, dtype=np.float64)

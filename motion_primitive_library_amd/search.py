@@ -18,12 +18,15 @@ a prior trajectory -- coarse-to-fine planning is two searches, the second with p
 env.alloc_field() gives a GoalField (include/mplx_field.h): the grid distance of every cell to a goal region, which
 opn.set_field(...) -- search(..., field=True) -- puts under the heuristic so that it sees walls and dead ends.
 """
+import contextlib
 import ctypes as C
 import math
 
 import numpy as np
 
 from . import _abi
+from .poly import _conflict_in, _conflict_steps
+from .rows import DeviceArray, _device_ptr
 from .table import NodeTable, TableFrontier
 
 IS_OPEN, IS_GOAL, SEEN = _abi.OPEN_IS_OPEN, _abi.OPEN_IS_GOAL, _abi.OPEN_SEEN
@@ -192,14 +195,6 @@ def _field_setup(who, env, opn, field, field_of_query, goal_rows, tol_pos, prior
     return field, owned, foq
 
 
-def _hand_field(new, old_or_none, field=None, owned=False, foq=None):
-    """The field of a result: from the search that made it, or handed on by a replan."""
-    if old_or_none is not None:
-        field, owned, foq = old_or_none.field, old_or_none._owns_field, old_or_none._field_of_query
-        old_or_none.field, old_or_none._owns_field = None, False
-    new.field, new._owns_field, new._field_of_query = field, owned, foq
-
-
 class OpenSet:
     """mplx_open of a NodeTable.  Free it (or let it go) before the table."""
 
@@ -300,7 +295,6 @@ class OpenSet:
         U = np.ascontiguousarray(U, dtype=np.float64)
         if U.ndim != 2:
             raise ValueError("U must be [nU][udim]")
-        from .env import DeviceArray
         bufs = [DeviceArray(env, max(a.nbytes, 8)) for a in (starts_h, actions_h, U)]
         try:
             for b, a in zip(bufs, (starts_h, actions_h, U)):
@@ -397,7 +391,6 @@ def _smooth(env, paths, v, control):
     """The paths [(start, actions) or None] of Q queries -> chain states on the device (mplx_traj_info_device, want_states)
     -> one mplx_solve_device for Q x n_v problems, problem vi * Q + q = path q at speed v[vi]; the states never visit the
     host.  A query without a path is an empty problem (SOLVE_EMPTY)."""
-    from .env import DeviceArray
     env._flush()
     vs = np.atleast_1d(np.asarray(v, dtype=np.float64)).ravel()
     Q, nv = len(paths), len(vs)
@@ -444,7 +437,6 @@ def _smooth(env, paths, v, control):
 def _shortcut(env, paths, max_hop, control):
     """The paths [(start, actions) or None] of Q queries -> chain states on the device (mplx_traj_info_device, want_states)
     -> mplx_shortcut_device; only counts, costs and statuses are read back.  A query without a path is an empty problem."""
-    from .env import DeviceArray
     env._flush()
     Q = len(paths)
     H = max([len(p[1]) for p in paths if p is not None] + [1])
@@ -557,7 +549,6 @@ class Reservations:
     def fill(self, trajs, step, n_steps=None, t0=None, radius=None, group=None, park=True):
         """Fills the table again (mplx_reserve_fill_poly / _fill_traj; synchronous).  n_steps=None: the smallest count
         whose instants cover max(t0 + total), as conflicts() takes it."""
-        from .env import _conflict_in, _conflict_steps
         env = self._env
         env._flush()
         if hasattr(trajs, "_h"):  # a PolyTrajSet
@@ -594,7 +585,6 @@ class Reservations:
         come too close to a reservation get cost +inf.  table: the NodeTable whose query column says whose a row is
         (needed with more than one query).  hit: a device buffer of lists.n_slots int64, n_blocked: one of 8 bytes that
         the call adds to; either may be None.  Asynchronous."""
-        from .env import _device_ptr
         s = lists.c_struct()
         self._check(_abi.lib().mplx_reserve_check_device(
             self._res, None if table is None else table._tab, C.byref(s), int(n), _device_ptr(frontier.id), int(frontier.ptr),
@@ -606,7 +596,6 @@ class Reservations:
         the last of its list -- "wait for one primitive", which the expansion drops.  n_added: a device buffer of 8
         bytes that the call adds to, or None.  The call reads nothing of the reservation table; it lives here because a
         wait is only worth an edge among reservations.  A `zero_rows` mask of `lists` stays valid.  Asynchronous."""
-        from .env import _device_ptr
         s = lists.c_struct()
         self._check(_abi.lib().mplx_lists_add_wait_device(
             self._env._ctx, C.byref(s), int(n), int(frontier.ptr), int(frontier.n_nodes), _device_ptr(frontier.id),
@@ -617,7 +606,6 @@ class Reservations:
         could not stay -- a reservation comes too close at some instant from the node's t on -- loses IS_GOAL and stays
         an ordinary open node.  hit: a device buffer of frontier.capacity int64, n_vetoed: one of 8 bytes that the call
         adds to; either may be None.  Asynchronous."""
-        from .env import _device_ptr
         f = frontier.c_struct()
         self._check(_abi.lib().mplx_reserve_park_device(
             self._res, open_set._open, C.byref(f), int(n_max), None if hit is None else _device_ptr(hit),
@@ -822,47 +810,145 @@ def replan_prioritised(env, plan, now, step, radius=None, order=None, park=True,
             "order": order, "n_steps": n_steps, "radius": rad.copy(), "field": plan.get("field"), "rebase": rebase}
 
 
-class SearchResult:
+class _Result:
+    """What SearchResult and MultiSearchResult share.  It owns the table, the open set and (search(field=True)) the goal
+    field, and frees them; it holds the front end of replan / replan_timed and the paths of smooth / shortcut.  The
+    two classes are views on it: MultiSearchResult shows per-query lists, SearchResult the values of its one query."""
+
+    _multi, _who, _prior_word = True, "search_many", "priors"
+    rebase_info = None  # of the rebase that made this result (a replan sets it)
+    _executed = None  # per query (original start state, actions executed up to the root), set by replan_timed
+
+    def __init__(self, status, last, table, open_set, rounds, expanded, total_rounds, env=None, params=None):
+        self._env, self._params = env, params  # what replan() runs again with
+        self.n_queries = len(status)
+        self.status = list(status)
+        self.found = [st == FOUND for st in status]
+        self.goal_id = [r["goal_id"] if ok else -1 for r, ok in zip(last, self.found)]
+        self.cost = [r["goal_g"] if ok else math.inf for r, ok in zip(last, self.found)]
+        self.last_select = last
+        self.table = table
+        self.open = open_set
+        self.rounds = list(rounds)
+        self.expanded = list(expanded)
+        self.total_rounds = total_rounds
+        self.field, self._owns_field, self._field_of_query = None, False, None  # (search(field=): _hand_field)
+
+    @classmethod
+    def _of(cls, status, last, table, open_set, rounds, expanded, total_rounds, env, params):
+        """The result of a run that counted per query."""
+        return cls(status, last, table, open_set, rounds, expanded, total_rounds, env, params)
+
+    def _per_query(self, name):
+        v = getattr(self, name)
+        return v if self._multi else [v]
+
+    def _chain(self, goal_id):
+        ids, act = self.table.path(goal_id)
+        return self.table.state_of(ids[0]), act
+
+    def _full_path(self, q):
+        start, act = self._path_of(q)
+        done = None if self._executed is None else self._executed[q]
+        if done is None:
+            return start, act
+        return done[0].copy(), np.concatenate([done[1], act]).astype(np.int32)
+
+    def smooth(self, v=1.0, control=None):
+        """The path(s) smoothed into polynomials through their chain states (include/mplx_solve.h): v a scalar or [n_v]
+        speeds of the time allocation -> a PolyTrajSet of Q x n_v problems in one solve, problem vi * Q + q = the path of
+        query q at speed v[vi] (Q = 1 for a SearchResult); control: of the ends (default: the EnvMap's).  Of a
+        MultiSearchResult a query without a path is SOLVE_EMPTY."""
+        return _smooth(self._env, self._paths(), v, control)
+
+    def shortcut(self, max_hop=None, control=None):
+        """The path(s) with runs of their short constant-control pieces replaced by two-point primitives between
+        non-adjacent chain states, where those stay within v_max / a_max / j_max and off the obstacles and cost less
+        (mplx_shortcut, include/mplx_limits.h): a ShortcutResult of Q queries in one batch of launches.  max_hop: the
+        longest hop in chain states (default: any).  Of a MultiSearchResult a query without a path is SOLVE_EMPTY."""
+        return _shortcut(self._env, self._paths(), max_hop, control)
+
+    def _roots(self, who, roots, advance):
+        """The node id every query is re-rooted at: roots [Q] (-1 or None: that query's seed), or ids[advance] of the
+        chain its path follows."""
+        Q = self.n_queries
+        r = [-1] * Q
+        if roots is not None:
+            r = [-1 if x is None else int(x) for x in np.broadcast_to(np.asarray(roots, dtype=object), (Q,))]
+        if advance is not None:
+            found, goal_id = self._per_query("found"), self._per_query("goal_id")
+            if not self._multi and not found[0]:
+                raise RuntimeError("%s: advance needs a path (status %s)" % (who, STATUS_NAMES[self.status]))
+            ks = np.broadcast_to(np.asarray(advance, dtype=np.int64), (Q,))
+            r = [int(self.table.path(goal_id[q])[0][int(ks[q])]) if found[q] else -1 for q in range(Q)]
+        return r
+
+    def _replan(self, who, roots, advance, goal_rows, check_edges, priors, timed=False, avoid=None):
+        if self.table is None or self._params is None:
+            raise RuntimeError("%s: this result does not own a table (it was replanned or freed)" % who)
+        if timed:
+            _need_timed(self._params, avoid)
+        else:
+            _no_replan(self._params)
+        if roots is not None and advance is not None:
+            raise ValueError("%s: give %s or advance, not both" % (who, "roots" if self._multi else "root"))
+        return run_replan(self, self._multi, self._roots(who, roots, advance), goal_rows, check_edges, priors, timed, avoid)
+
+    def _hand_field(self, old=None, field=None, owned=False, foq=None):
+        """The field of this result: from the search that made it, or handed on by the result `old` a replan consumed."""
+        if old is not None:
+            field, owned, foq = old.field, old._owns_field, old._field_of_query
+            old.field, old._owns_field = None, False
+        self.field, self._owns_field, self._field_of_query = field, owned, foq
+
+    def free(self):
+        if self.open is not None:
+            self.open.free()
+        if self.table is not None:
+            self.table.free()
+        self.open = self.table = None
+        if self._owns_field and self.field is not None:
+            self.field.free()
+        self.field, self._owns_field = None, False
+
+
+def _one_goal(goal_row):
+    return None if goal_row is None else np.array(goal_row, dtype=np.float64).reshape(1, -1)
+
+
+class SearchResult(_Result):
     """What EnvMap.search returns.  status: FOUND, EMPTY (no open node left: the goal region is not reachable within
     g_max), MAX_ROUNDS or MAX_EXPAND (stopped early; the nodes selected last are open again); cost: g of the goal node
     (inf unless FOUND); rounds = relax calls made; expanded = nodes expanded (a re-opened node counts again); table and
     open: the NodeTable and OpenSet, owned by the result -- free() it (or let it go) before the EnvMap is closed."""
 
+    _multi, _who, _prior_word = False, "search", "prior"
+
     def __init__(self, status, last, table, open_set, rounds, expanded, env=None, params=None):
-        self._env, self._params = env, params  # what replan() runs again with
-        self.status = status
-        self.found = status == FOUND
-        self.goal_id = last["goal_id"] if self.found else -1
-        self.cost = last["goal_g"] if self.found else math.inf
-        self.last_select = last
-        self.table = table
-        self.open = open_set
-        self.rounds = rounds
-        self.expanded = expanded
-        self.field, self._owns_field, self._field_of_query = None, False, None  # (search(field=): _hand_field)
+        super().__init__([status], [last], table, open_set, [rounds], [expanded], rounds, env, params)
+        self.status, self.found, self.goal_id, self.cost = self.status[0], self.found[0], self.goal_id[0], self.cost[0]
+        self.last_select, self.rounds, self.expanded = last, rounds, expanded
+
+    @classmethod
+    def _of(cls, status, last, table, open_set, rounds, expanded, total_rounds, env, params):
+        return cls(status[0], last[0], table, open_set, total_rounds, expanded[0], env, params)
 
     def path(self):
         """(start_state, actions) of the chain of best predecessors from the seed to the goal node: the `starts` and
         `actions` (reshape(-1, 1)) of EnvMap.rollout / traj_*."""
         if not self.found:
             raise RuntimeError("search: no path (status %s)" % STATUS_NAMES[self.status])
-        ids, act = self.table.path(self.goal_id)
-        return self.table.state_of(ids[0]), act
+        return self._chain(self.goal_id)
+
+    def _path_of(self, q):
+        return self.path()
+
+    def _paths(self):
+        return [self.path()]
 
     def as_prior(self):
         """This result's path as the Prior of a later search (with the control set this search ran with)."""
         return _prior_of(self, None)
-
-    def smooth(self, v=1.0, control=None):
-        """The path smoothed into a polynomial through its chain states (include/mplx_solve.h): v a scalar or [n_v]
-        speeds of the time allocation -> a PolyTrajSet of n_v problems; control: of the ends (default: the EnvMap's)."""
-        return _smooth(self._env, [self.path()], v, control)
-
-    def shortcut(self, max_hop=None, control=None):
-        """The path with runs of its short constant-control pieces replaced by two-point primitives between non-adjacent
-        chain states, where those stay within v_max / a_max / j_max and off the obstacles and cost less (mplx_shortcut,
-        include/mplx_limits.h): a ShortcutResult for one query.  max_hop: the longest hop in chain states (default: any)."""
-        return _shortcut(self._env, [self.path()], max_hop, control)
 
     def replan(self, root=None, advance=None, goal_row=None, check_edges=True, prior=None):
         """Plans again on the table of this search after the robot has moved and / or the map was edited
@@ -876,16 +962,7 @@ class SearchResult:
         place when it is stale or a new goal_row is given; a caller's field that is stale, or a new goal_row with a
         caller's field, raises -- rebuild the field and search anew.  Returns a new SearchResult that owns the table and
         the open set; this one no longer does."""
-        if self.table is None or self._params is None:
-            raise RuntimeError("replan: this result does not own a table (it was replanned or freed)")
-        _no_replan(self._params)
-        if root is not None and advance is not None:
-            raise ValueError("replan: give root or advance, not both")
-        if advance is not None:
-            if not self.found:
-                raise RuntimeError("replan: advance needs a path (status %s)" % STATUS_NAMES[self.status])
-            root = int(self.table.path(self.goal_id)[0][int(advance)])
-        return run_replan(self, False, [-1 if root is None else int(root)], goal_row, check_edges, None if prior is None else [prior])
+        return self._replan("replan", root, advance, _one_goal(goal_row), check_edges, None if prior is None else [prior])
 
     def replan_timed(self, avoid=None, root=None, advance=None, goal_row=None, check_edges=True):
         """replan() for a search that ran with time keys and / or among reservations (include/mplx_replan_timed.h;
@@ -900,16 +977,7 @@ class SearchResult:
         goal_row and the handling of priors and fields: as replan().  Returns a new SearchResult that owns the table
         and the open set; its path() starts at the root, whose t is not 0 -- full_path() is the chain from the original
         start."""
-        if self.table is None or self._params is None:
-            raise RuntimeError("replan_timed: this result does not own a table (it was replanned or freed)")
-        _need_timed(self._params, avoid)
-        if root is not None and advance is not None:
-            raise ValueError("replan_timed: give root or advance, not both")
-        if advance is not None:
-            if not self.found:
-                raise RuntimeError("replan_timed: advance needs a path (status %s)" % STATUS_NAMES[self.status])
-            root = int(self.table.path(self.goal_id)[0][int(advance)])
-        return run_replan(self, False, [-1 if root is None else int(root)], goal_row, check_edges, None, True, avoid)
+        return self._replan("replan_timed", root, advance, _one_goal(goal_row), check_edges, None, True, avoid)
 
     def full_path(self):
         """(start_state, actions) from the ORIGINAL start (t = 0): the actions executed up to the root of every
@@ -917,20 +985,62 @@ class SearchResult:
         robot's unchanged t0; for a result that was never replanned it is path().  The positions the check computed
         along it and those of traj_sample agree bit for bit: both evaluate the segment of (chain state, control) at the
         local time tl_i - t of that state."""
-        return _full_path(self, None)
-
-    def free(self):
-        if self.open is not None:
-            self.open.free()
-        if self.table is not None:
-            self.table.free()
-        self.open = self.table = None
-        if self._owns_field and self.field is not None:
-            self.field.free()
-        self.field, self._owns_field = None, False
+        return self._full_path(0)
 
     def __repr__(self):
         return "SearchResult(%s, cost=%r, rounds=%d, expanded=%d)" % (STATUS_NAMES[self.status], self.cost, self.rounds, self.expanded)
+
+
+class MultiSearchResult(_Result):
+    """What EnvMap.search_many returns: per query q status[q] (FOUND, EMPTY, MAX_ROUNDS or MAX_EXPAND), found[q], cost[q]
+    (inf unless FOUND), goal_id[q] (a global node id, -1 unless FOUND), rounds[q] (the rounds in which q selected) and
+    expanded[q]; total_rounds = relax calls made.  last_select: the Q results of the last select.  table and open are
+    owned by the result: free() it (or let it go) before the EnvMap is closed."""
+
+    def path(self, q):
+        """(start_state, actions) of query q, as SearchResult.path."""
+        if not self.found[q]:
+            raise RuntimeError("search_many: no path for query %d (status %s)" % (q, STATUS_NAMES[self.status[q]]))
+        return self._chain(self.goal_id[q])
+
+    _path_of = path
+
+    def _paths(self):
+        return [self.path(q) if self.found[q] else None for q in range(self.n_queries)]
+
+    def as_priors(self):
+        """[Q] Prior (None for a query without a path): the `priors` of a later search_many."""
+        return [_prior_of(self, q) if self.found[q] else None for q in range(self.n_queries)]
+
+    def conflicts(self, step, n_steps=None, t0=None, radius=None, group=None, rank=None, park=True, want_pairs=False, chunk_steps=0):
+        """Conflicts between the Q raw paths on a common clock (EnvMap.traj_conflicts on the chains of path(q), with the
+        parameters and controls the EnvMap holds now): a ConflictResult of Q entries; a query without a path is excluded
+        (TRAJ_EMPTY)."""
+        starts, actions = _path_set(self._env, self._paths())
+        return self._env.traj_conflicts(starts, actions, step, n_steps=n_steps, t0=t0, radius=radius, group=group, rank=rank,
+                                        park=park, want_pairs=want_pairs, chunk_steps=chunk_steps)
+
+    def replan(self, roots=None, advance=None, goal_rows=None, check_edges=True, priors=None):
+        """SearchResult.replan for Q queries at once: roots [Q] (node ids; -1 or None: that query's seed), or advance
+        (one k for all or [Q]; a query without a path keeps its seed), goal_rows [Q][4D+2] or None.  Every launch of
+        the rebase, of the forced round and of the rounds after it is shared by the queries.  Returns a new
+        MultiSearchResult that owns the table and the open set; this one no longer does."""
+        return self._replan("replan", roots, advance, goal_rows, check_edges, priors)
+
+    def replan_timed(self, avoid=None, roots=None, advance=None, goal_rows=None, check_edges=True):
+        """SearchResult.replan_timed for Q queries at once: roots [Q] (node ids; -1 or None: that query's seed; an id
+        that is out of range keeps nothing of the query, which then ends EMPTY), or advance (one k for all or [Q]; a
+        query without a path keeps its seed), goal_rows [Q][4D+2] or None.  Returns a new MultiSearchResult that owns
+        the table and the open set; this one no longer does."""
+        return self._replan("replan_timed", roots, advance, goal_rows, check_edges, None, True, avoid)
+
+    def full_path(self, q):
+        """SearchResult.full_path of query q."""
+        return self._full_path(q)
+
+    def __repr__(self):
+        return "MultiSearchResult(%s, rounds=%d, expanded=%d)" % (
+            [STATUS_NAMES[st] for st in self.status], self.total_rounds, sum(self.expanded))
 
 
 def _need_timed(prm, avoid):
@@ -940,15 +1050,6 @@ def _need_timed(prm, avoid):
         raise ValueError("replan_timed: the search ran with avoid: give the Reservations as they are now")
     if avoid is not None and not prm.get("avoid"):
         raise ValueError("replan_timed: the search ran without avoid (no t0 / radius to check with)")
-
-
-def _full_path(result, q):
-    start, act = result.path() if q is None else result.path(q)
-    done = getattr(result, "_executed", None)
-    done = None if done is None else done[0 if q is None else q]
-    if done is None:
-        return start, act
-    return done[0].copy(), np.concatenate([done[1], act]).astype(np.int32)
 
 
 def _no_replan(prm):
@@ -988,17 +1089,36 @@ def _table_check(tab, who, where):
                            % (who, status, where))
 
 
+def _edges(prm, avoid):
+    """(wait, park) of a round: wait edges join the lists before the check (include/mplx_wait.h); every push is followed
+    by the park veto of `avoid` (mplx_reserve_park_device)."""
+    return bool(prm.get("wait")), bool(prm.get("park_goal")) and avoid is not None
+
+
+def _round(env, tab, opn, avoid, rows, imp, lists, n, prm, wait, park):
+    """One round on the n rows of `rows` (a selection, or a chunk of the nodes a rebase kept): expand them, append the
+    wait edges, check the lists against the reservations of `avoid` (the edges it blocks cost +inf, which the relax
+    skips), relax the lists against the table, push the nodes whose g fell, veto the goal nodes the robot could not stay
+    at.  With avoid None and wait and park off these are the calls of a search without them."""
+    env.expand_lists_resident(rows, lists, n_nodes=n)
+    if wait:
+        _add_waits(env, avoid, rows, lists, n)
+    if avoid is not None:
+        avoid.check(rows, lists, n, table=tab)
+    tab.relax(lists, rows.id, rows.g, prm["g_max"], frontier=imp, n_nodes=n, want_count=False)
+    opn.push(imp, n_max=n * lists.stride, eps=prm["eps"], sight=prm["sight"])
+    if park:
+        avoid.park(opn, imp, n * lists.stride)
+
+
 def _search_loop(env, who, multi, tab, opn, sel, imp, lists, prm, total, rounds, expanded, avoid=None):
     """The rounds of a search from its first select on: select (the round's only read-back), and while any query
-    selects: expand the selection, relax its lists against the table, push the nodes whose g fell.  rounds / expanded:
-    per query (one entry for a table of one query), counted on from what they hold.  avoid: a Reservations whose check
-    runs between the expansion and the relax (the edges it blocks cost +inf, which the relax skips); None: the calls of a
-    search without one.  prm["wait"]: wait edges join the lists before the check (include/mplx_wait.h); prm["park_goal"]:
-    every push is followed by the park veto of `avoid` (mplx_reserve_park_device).  With both off the loop issues exactly
-    the calls it issued before they existed.  Returns (status per query, the results of the last select, relax calls
-    made)."""
-    eps, delta, g_max, sight = prm["eps"], prm["delta"], prm["g_max"], prm["sight"]
-    wait, park = bool(prm.get("wait")), bool(prm.get("park_goal")) and avoid is not None
+    selects: one _round on the selection.  rounds / expanded: per query (one entry for a table of one query), counted
+    on from what they hold.  avoid: a Reservations whose check runs between the expansion and the relax; None: the calls
+    of a search without one.  prm["wait"] / prm["park_goal"]: _edges.  With both off the loop issues exactly the calls it
+    issued before they existed.  Returns (status per query, the results of the last select, relax calls made)."""
+    eps, delta, sight = prm["eps"], prm["delta"], prm["sight"]
+    wait, park = _edges(prm, avoid)
     max_rounds, max_expand = prm["max_rounds"], prm["max_expand"]
     limit = None
     while True:
@@ -1019,15 +1139,7 @@ def _search_loop(env, who, multi, tab, opn, sel, imp, lists, prm, total, rounds,
             if park:
                 avoid.park(opn, sel, n)
             break
-        env.expand_lists_resident(sel, lists, n_nodes=n)
-        if wait:
-            _add_waits(env, avoid, sel, lists, n)
-        if avoid is not None:
-            avoid.check(sel, lists, n, table=tab)
-        tab.relax(lists, sel.id, sel.g, g_max, frontier=imp, n_nodes=n, want_count=False)
-        opn.push(imp, n_max=n * lists.stride, eps=eps, sight=sight)
-        if park:
-            avoid.park(opn, imp, n * lists.stride)
+        _round(env, tab, opn, avoid, sel, imp, lists, n, prm, wait, park)
         total += 1
         for q, r in enumerate(res):
             if r["status"] == SELECTED:
@@ -1043,7 +1155,6 @@ def _add_waits(env, avoid, sel, lists, n):
     if avoid is not None:
         avoid.add_waits(sel, lists, n)
         return
-    from .env import _device_ptr
     s = lists.c_struct()
     _abi.check(env._ctx, _abi.lib().mplx_lists_add_wait_device(env._ctx, C.byref(s), int(n), int(sel.ptr), int(sel.n_nodes),
                                                                _device_ptr(sel.id), None))
@@ -1059,235 +1170,103 @@ def _params(env, eps, delta, g_max, max_rounds, max_expand, capacity, max_fronti
             "control": int(env._p.control), "U": getattr(env, "_U_host", None), "dt": float(env._p.dt)}
 
 
-def run_search(env, start, goal_row, eps, delta, g_max, max_rounds, max_expand, capacity, max_frontier, lists_stride, sight,
-               tol_pos, tol_vel, tol_acc, tol_yaw, w, v_max, start_g=0.0, prior=None, avoid=None, t0=0.0, radius=None,
-               ignore_group=-1, time_keys=None, wait=False, park_goal=False, field=None, field_of_query=None, heur=None):
-    if field is not None and field is not False and prior is not None:
-        raise ValueError("search: field and prior exclude each other")
-    if heur is not None and prior is not None:
-        raise ValueError("search: heur and prior exclude each other")
-    env._flush()
-    prm = _params(env, eps, delta, g_max, max_rounds, max_expand, capacity, max_frontier, lists_stride, sight,
-                  dict(w=w, v_max=v_max, tol_pos=tol_pos, tol_vel=tol_vel, tol_acc=tol_acc, tol_yaw=tol_yaw))
-    prm["goal_row"] = np.array(goal_row, dtype=np.float64)
-    fld, fld_owned = None, False
-    prm["own_goals"] = prior is not None  # the open set carries its goal itself (priors need that): replan keeps it so
-    fcap = prm["fcap"]
-    env.set_goal(goal_row, **prm["goal_kw"])
-    tab = NodeTable(env, capacity)
-    opn = sel = imp = lists = None
-    try:
-        if avoid is not None or time_keys or wait or park_goal:
-            _avoid_setup("search", avoid, time_keys, np.asarray(start, dtype=np.float64).reshape(-1, 1), 1, t0, radius,
-                         ignore_group, tab, prm, wait, park_goal)
-        opn = OpenSet(env, tab)
-        if prior is not None:
-            opn.set_goals(prm["goal_row"].reshape(1, -1), **prm["goal_kw"])
-            opn.set_prior_list([prior])
-        if field is not None and field is not False:
-            fld, fld_owned, field_of_query = _field_setup("search", env, opn, field, field_of_query, prm["goal_row"], tol_pos, prior)
-        if heur is not None:  # (the open set keeps the mode: a replan pushes with it)
-            opn.set_heur(heur)
-        sel, imp = TableFrontier(env, fcap), TableFrontier(env, int(capacity))  # (no more nodes can improve than exist)
-        lists = env.alloc_lists(fcap, want_state=True, stride=lists_stride)
-        # (g = None is the call without a g row: the bytes of a search before start_g existed)
-        count = tab.seed(start, None if (start_g is None or float(start_g) == 0.0) else float(start_g), frontier=imp)
-        _table_check(tab, "search", "after seeding")
-        opn.push(imp, n_max=count, eps=eps, sight=sight)
-        if park_goal:
-            avoid.park(opn, imp, count)
-        rounds, expanded = [0], [0]
-        status, res, total = _search_loop(env, "search", False, tab, opn, sel, imp, lists, prm, 0, rounds, expanded, avoid)
-        out = SearchResult(status[0], res[0], tab, opn, total, expanded[0], env, prm)
-        _hand_field(out, None, fld, fld_owned, field_of_query)
-        return out
-    except Exception:
-        if opn is not None:
-            opn.free()
-        tab.free()
-        if fld_owned:
-            fld.free()
-        raise
-    finally:
-        for b in (sel, imp, lists):
-            if b is not None:
-                b.free()
+def _own(stack, obj):
+    """`obj` is freed when the ExitStack `stack` unwinds (unless its pop_all() was called first)."""
+    stack.callback(obj.free)
+    return obj
 
 
-class MultiSearchResult:
-    """What EnvMap.search_many returns: per query q status[q] (FOUND, EMPTY, MAX_ROUNDS or MAX_EXPAND), found[q], cost[q]
-    (inf unless FOUND), goal_id[q] (a global node id, -1 unless FOUND), rounds[q] (the rounds in which q selected) and
-    expanded[q]; total_rounds = relax calls made.  last_select: the Q results of the last select.  table and open are
-    owned by the result: free() it (or let it go) before the EnvMap is closed."""
+class _Scratch(list):
+    """The frontiers and lists of one run, freed together in the order they were made."""
 
-    def __init__(self, status, last, table, open_set, rounds, expanded, total_rounds, env=None, params=None):
-        self._env, self._params = env, params  # what replan() runs again with
-        self.n_queries = len(status)
-        self.status = list(status)
-        self.found = [st == FOUND for st in status]
-        self.goal_id = [r["goal_id"] if ok else -1 for r, ok in zip(last, self.found)]
-        self.cost = [r["goal_g"] if ok else math.inf for r, ok in zip(last, self.found)]
-        self.last_select = last
-        self.table = table
-        self.open = open_set
-        self.rounds = list(rounds)
-        self.expanded = list(expanded)
-        self.total_rounds = total_rounds
-        self.field, self._owns_field, self._field_of_query = None, False, None  # (search_many(field=): _hand_field)
-
-    def path(self, q):
-        """(start_state, actions) of query q, as SearchResult.path."""
-        if not self.found[q]:
-            raise RuntimeError("search_many: no path for query %d (status %s)" % (q, STATUS_NAMES[self.status[q]]))
-        ids, act = self.table.path(self.goal_id[q])
-        return self.table.state_of(ids[0]), act
-
-    def as_priors(self):
-        """[Q] Prior (None for a query without a path): the `priors` of a later search_many."""
-        return [_prior_of(self, q) if self.found[q] else None for q in range(self.n_queries)]
-
-    def smooth(self, v=1.0, control=None):
-        """SearchResult.smooth for every query in one solve: a PolyTrajSet of Q x n_v problems, problem vi * Q + q = the
-        path of query q at speed v[vi]; a query without a path is SOLVE_EMPTY."""
-        return _smooth(self._env, [self.path(q) if self.found[q] else None for q in range(self.n_queries)], v, control)
-
-    def shortcut(self, max_hop=None, control=None):
-        """SearchResult.shortcut for every query in one batch of launches: a ShortcutResult of Q queries; a query without
-        a path is SOLVE_EMPTY."""
-        return _shortcut(self._env, [self.path(q) if self.found[q] else None for q in range(self.n_queries)], max_hop, control)
-
-    def conflicts(self, step, n_steps=None, t0=None, radius=None, group=None, rank=None, park=True, want_pairs=False, chunk_steps=0):
-        """Conflicts between the Q raw paths on a common clock (EnvMap.traj_conflicts on the chains of path(q), with the
-        parameters and controls the EnvMap holds now): a ConflictResult of Q entries; a query without a path is excluded
-        (TRAJ_EMPTY)."""
-        starts, actions = _path_set(self._env, [self.path(q) if self.found[q] else None for q in range(self.n_queries)])
-        return self._env.traj_conflicts(starts, actions, step, n_steps=n_steps, t0=t0, radius=radius, group=group, rank=rank,
-                                        park=park, want_pairs=want_pairs, chunk_steps=chunk_steps)
-
-    def replan(self, roots=None, advance=None, goal_rows=None, check_edges=True, priors=None):
-        """SearchResult.replan for Q queries at once: roots [Q] (node ids; -1 or None: that query's seed), or advance
-        (one k for all or [Q]; a query without a path keeps its seed), goal_rows [Q][4D+2] or None.  Every launch of
-        the rebase, of the forced round and of the rounds after it is shared by the queries.  Returns a new
-        MultiSearchResult that owns the table and the open set; this one no longer does."""
-        if self.table is None or self._params is None:
-            raise RuntimeError("replan: this result does not own a table (it was replanned or freed)")
-        _no_replan(self._params)
-        if roots is not None and advance is not None:
-            raise ValueError("replan: give roots or advance, not both")
-        Q = self.n_queries
-        r = [-1] * Q
-        if roots is not None:
-            r = [-1 if x is None else int(x) for x in np.broadcast_to(np.asarray(roots, dtype=object), (Q,))]
-        if advance is not None:
-            ks = np.broadcast_to(np.asarray(advance, dtype=np.int64), (Q,))
-            r = [int(self.table.path(self.goal_id[q])[0][int(ks[q])]) if self.found[q] else -1 for q in range(Q)]
-        return run_replan(self, True, r, goal_rows, check_edges, priors)
-
-    def replan_timed(self, avoid=None, roots=None, advance=None, goal_rows=None, check_edges=True):
-        """SearchResult.replan_timed for Q queries at once: roots [Q] (node ids; -1 or None: that query's seed; an id
-        that is out of range keeps nothing of the query, which then ends EMPTY), or advance (one k for all or [Q]; a
-        query without a path keeps its seed), goal_rows [Q][4D+2] or None.  Returns a new MultiSearchResult that owns
-        the table and the open set; this one no longer does."""
-        if self.table is None or self._params is None:
-            raise RuntimeError("replan_timed: this result does not own a table (it was replanned or freed)")
-        _need_timed(self._params, avoid)
-        if roots is not None and advance is not None:
-            raise ValueError("replan_timed: give roots or advance, not both")
-        Q = self.n_queries
-        r = [-1] * Q
-        if roots is not None:
-            r = [-1 if x is None else int(x) for x in np.broadcast_to(np.asarray(roots, dtype=object), (Q,))]
-        if advance is not None:
-            ks = np.broadcast_to(np.asarray(advance, dtype=np.int64), (Q,))
-            r = [int(self.table.path(self.goal_id[q])[0][int(ks[q])]) if self.found[q] else -1 for q in range(Q)]
-        return run_replan(self, True, r, goal_rows, check_edges, None, True, avoid)
-
-    def full_path(self, q):
-        """SearchResult.full_path of query q."""
-        return _full_path(self, q)
+    def add(self, buf):
+        self.append(buf)
+        return buf
 
     def free(self):
-        if self.open is not None:
-            self.open.free()
-        if self.table is not None:
-            self.table.free()
-        self.open = self.table = None
-        if self._owns_field and self.field is not None:
-            self.field.free()
-        self.field, self._owns_field = None, False
-
-    def __repr__(self):
-        return "MultiSearchResult(%s, rounds=%d, expanded=%d)" % (
-            [STATUS_NAMES[st] for st in self.status], self.total_rounds, sum(self.expanded))
+        for b in self:
+            b.free()
 
 
-def run_search_many(env, starts, goal_rows, eps, delta, g_max, max_rounds, max_expand, capacity, max_frontier, lists_stride,
-                    sight, tol_pos, tol_vel, tol_acc, tol_yaw, w, v_max, start_g=0.0, priors=None, avoid=None, t0=0.0,
-                    radius=None, ignore_group=-1, time_keys=None, wait=False, park_goal=False, field=None, field_of_query=None,
-                    heur=None):
-    if field is not None and field is not False and priors is not None:
-        raise ValueError("search_many: field and priors exclude each other")
-    if heur is not None and priors is not None:
-        raise ValueError("search_many: heur and priors exclude each other")
-    env._flush()
+def run_search(env, start, goal_row, prior=None, **opts):
+    """EnvMap.search: the query as [4D+2][1] / [1][4D+2]."""
+    return _run(env, False, np.asarray(start, dtype=np.float64).reshape(-1, 1), _one_goal(goal_row),
+                dict(opts, priors=None if prior is None else [prior]))
+
+
+def run_search_many(env, starts, goal_rows, **opts):
     starts = np.ascontiguousarray(starts, dtype=np.float64)
     goal_rows = np.ascontiguousarray(goal_rows, dtype=np.float64)
     if starts.ndim != 2 or goal_rows.ndim != 2 or starts.shape[0] != env.n_fields or goal_rows.shape != (starts.shape[1], env.n_fields):
         raise ValueError("search_many: starts must be [%d][Q] and goal_rows [Q][%d]" % (env.n_fields, env.n_fields))
-    Q = starts.shape[1]
-    if Q < 1:
+    if starts.shape[1] < 1:
         raise ValueError("search_many: no query")
-    prm = _params(env, eps, delta, g_max, max_rounds, max_expand, capacity, max_frontier, lists_stride, sight,
-                  dict(w=w, v_max=v_max, tol_pos=tol_pos, tol_vel=tol_vel, tol_acc=tol_acc, tol_yaw=tol_yaw))
-    fcap = prm["fcap"]
-    prm["goal_rows"] = goal_rows.copy()
-    fld, fld_owned = None, False
-    g0 = None if start_g is None else np.broadcast_to(np.asarray(start_g, dtype=np.float64), (Q,))
+    return _run(env, True, starts, goal_rows.copy(), opts)
+
+
+def _run(env, multi, starts, goal_rows, opts):
+    """EnvMap.search (multi=False) and EnvMap.search_many: starts [4D+2][Q], goal_rows [Q][4D+2], opts: the keyword
+    arguments of EnvMap.search_many.  The two differ in the calls named at the branches on `multi` (here, in
+    _search_loop and in run_replan) and in nothing else: a search of one query keeps its goal on the context, has no
+    query column and selects with mplx_open_select_device."""
+    cls = MultiSearchResult if multi else SearchResult
+    who, prior_word = cls._who, cls._prior_word
+    priors, field, heur, avoid, park_goal = opts["priors"], opts["field"], opts["heur"], opts["avoid"], opts["park_goal"]
+    if field is not None and field is not False and priors is not None:
+        raise ValueError("%s: field and %s exclude each other" % (who, prior_word))
+    if heur is not None and priors is not None:
+        raise ValueError("%s: heur and %s exclude each other" % (who, prior_word))
+    env._flush()
+    Q = starts.shape[1]
+    prm = _params(env, *(opts[k] for k in ("eps", "delta", "g_max", "max_rounds", "max_expand", "capacity", "max_frontier",
+                                           "lists_stride", "sight")),
+                  {k: opts[k] for k in ("w", "v_max", "tol_pos", "tol_vel", "tol_acc", "tol_yaw")})
+    prm["goal_rows"] = goal_rows
+    # the open set carries its goals itself (several queries and priors need that): replan keeps it so
+    prm["own_goals"] = multi or priors is not None
+    eps, sight, fcap, capacity = prm["eps"], prm["sight"], prm["fcap"], prm["capacity"]
+    g0 = None if opts["start_g"] is None else np.broadcast_to(np.asarray(opts["start_g"], dtype=np.float64), (Q,))
     if g0 is not None and not g0.any():
         g0 = None  # (the call without a g row: the bytes of a search before start_g existed)
-    tab = NodeTable(env, capacity, n_queries=Q)
-    opn = sel = imp = lists = None
-    try:
-        if avoid is not None or time_keys or wait or park_goal:
-            _avoid_setup("search_many", avoid, time_keys, starts, Q, t0, radius, ignore_group, tab, prm, wait, park_goal)
-        opn = OpenSet(env, tab)
-        opn.set_goals(goal_rows, **prm["goal_kw"])
+    if not multi:
+        env.set_goal(goal_rows[0], **prm["goal_kw"])
+    with contextlib.ExitStack() as always, contextlib.ExitStack() as owned:  # (owned: freed on failure only)
+        scratch = _own(always, _Scratch())
+        tab = _own(owned, NodeTable(env, capacity, n_queries=Q))
+        if avoid is not None or opts["time_keys"] or opts["wait"] or park_goal:
+            _avoid_setup(who, avoid, opts["time_keys"], starts, Q, opts["t0"], opts["radius"], opts["ignore_group"], tab, prm,
+                         opts["wait"], park_goal)
+        opn = _own(owned, OpenSet(env, tab))
+        if prm["own_goals"]:
+            opn.set_goals(goal_rows, **prm["goal_kw"])
         if priors is not None:
             opn.set_prior_list(list(priors))
-        if field is not None and field is not False:
-            fld, fld_owned, field_of_query = _field_setup("search_many", env, opn, field, field_of_query, goal_rows, tol_pos, priors)
-        if heur is not None:
+        fld, fld_owned, foq = _field_setup(who, env, opn, field, opts["field_of_query"], goal_rows, opts["tol_pos"], priors)
+        if fld_owned:
+            owned.callback(fld.free)
+        if heur is not None:  # (the open set keeps the mode: a replan pushes with it)
             opn.set_heur(heur)
-        sel, imp = TableFrontier(env, fcap), TableFrontier(env, int(capacity))  # (no more nodes can improve than exist)
-        lists = env.alloc_lists(fcap, want_state=True, stride=lists_stride)
-        count = tab.seed(starts, g0, frontier=imp, query=np.arange(Q, dtype=np.int32))
-        _table_check(tab, "search_many", "after seeding")
+        # (imp: no more nodes can improve than exist)
+        sel, imp = scratch.add(TableFrontier(env, fcap)), scratch.add(TableFrontier(env, capacity))
+        lists = scratch.add(env.alloc_lists(fcap, want_state=True, stride=prm["lists_stride"]))
+        count = tab.seed(starts, g0, frontier=imp, query=np.arange(Q, dtype=np.int32) if multi else None)
+        _table_check(tab, who, "after seeding")
         opn.push(imp, n_max=count, eps=eps, sight=sight)
         if park_goal:
             avoid.park(opn, imp, count)
         rounds, expanded = [0] * Q, [0] * Q
-        status, res, total = _search_loop(env, "search_many", True, tab, opn, sel, imp, lists, prm, 0, rounds, expanded, avoid)
-        out = MultiSearchResult(status, res, tab, opn, rounds, expanded, total, env, prm)
-        _hand_field(out, None, fld, fld_owned, field_of_query)
+        status, res, total = _search_loop(env, who, multi, tab, opn, sel, imp, lists, prm, 0, rounds, expanded, avoid)
+        out = cls._of(status, res, tab, opn, rounds, expanded, total, env, prm)
+        out._hand_field(None, fld, fld_owned, foq)
+        owned.pop_all()  # the result owns them now
         return out
-    except Exception:
-        if opn is not None:
-            opn.free()
-        tab.free()
-        if fld_owned:
-            fld.free()
-        raise
-    finally:
-        for b in (sel, imp, lists):
-            if b is not None:
-                b.free()
 
 
 def _executed(old, tab, roots):
     """Per query (original start state, actions executed so far), or None: what `old` holds, extended by the chain from
     the table's current root to the new one -- taken before the rebase cuts it."""
     Q = len(roots)
-    before = getattr(old, "_executed", None) or [None] * Q
+    before = old._executed or [None] * Q
     n = tab.stats()[0]
     out = []
     for q, r in enumerate(roots):
@@ -1303,50 +1282,48 @@ def _executed(old, tab, roots):
 
 def run_replan(old, multi, roots, goal_rows, check_edges, priors=None, timed=False, avoid=None):
     """SearchResult.replan / MultiSearchResult.replan: rebase into a frontier of the table's capacity, clear the open
-    set, push the kept nodes closed, expand all of them in chunks of max_frontier rows (the forced round), then the
-    loop of the search.  The forced chunks count as rounds and expansions.  timed: replan_timed -- the rebase is
-    rebase_timed against `avoid`, and the forced round runs the waits, the check and the park veto of the search's
-    rounds; without it the calls are those of replan."""
+    set, push the kept nodes closed, expand all of them in chunks of max_frontier rows (the forced round: one _round per
+    chunk), then the loop of the search.  The forced chunks count as rounds and expansions.  timed: replan_timed -- the
+    rebase is rebase_timed against `avoid`, and the forced round runs the waits, the check and the park veto of the
+    search's rounds; without it the calls are those of replan.  roots [Q] node ids, goal_rows [Q][4D+2] or None."""
     env, prm, tab, opn = old._env, old._params, old.table, old.open
     who = "replan_timed" if timed else "replan"
-    wait, park = timed and bool(prm.get("wait")), timed and bool(prm.get("park_goal")) and avoid is not None
-    if timed and avoid is not None:
+    if not timed:
+        avoid = None
+    wait, park = _edges(prm, avoid)
+    if avoid is not None:
         avoid.set_queries(prm["t0"], prm["radius"], prm["ignore_group"])
     env._flush()
-    eps, g_max, sight, fcap, capacity = prm["eps"], prm["g_max"], prm["sight"], prm["fcap"], prm["capacity"]
+    eps, sight, fcap, capacity = prm["eps"], prm["sight"], prm["fcap"], prm["capacity"]
     Q = tab.n_queries
-    fld = getattr(old, "field", None)
+    fld = old.field
     if fld is not None:
         if priors is not None:
             raise ValueError("replan: field and prior(s) exclude each other")
         if not old._owns_field and (fld.stale or goal_rows is not None):
             raise RuntimeError("replan: the caller's goal field is stale or the goal is new: rebuild the field and search anew")
     if goal_rows is not None:
-        if multi:
-            prm = dict(prm, goal_rows=np.ascontiguousarray(goal_rows, dtype=np.float64))
-            opn.set_goals(goal_rows, **prm["goal_kw"])  # (drops the priors)
-        else:
-            prm = dict(prm, goal_row=np.array(goal_rows, dtype=np.float64))
-            if prm.get("own_goals"):  # a search with a prior: the open set's own goal decides, not the context's
-                opn.set_goals(prm["goal_row"].reshape(1, -1), **prm["goal_kw"])
+        prm = dict(prm, goal_rows=np.ascontiguousarray(goal_rows, dtype=np.float64))
+        if prm["own_goals"]:  # (drops the priors); without: the context's goal decides, set below
+            opn.set_goals(prm["goal_rows"], **prm["goal_kw"])
     if priors is not None:
-        if not multi and not prm.get("own_goals"):
+        if not prm["own_goals"]:  # a prior needs the open set's own goal
             prm = dict(prm, own_goals=True)
-            opn.set_goals(prm["goal_row"].reshape(1, -1), **prm["goal_kw"])
+            opn.set_goals(prm["goal_rows"], **prm["goal_kw"])
         opn.set_prior_list(list(priors))
     if not multi:
-        env.set_goal(prm["goal_row"], **prm["goal_kw"])  # (the context's goal may have been moved since the search)
+        env.set_goal(prm["goal_rows"][0], **prm["goal_kw"])  # (the context's goal may have been moved since the search)
     if fld is not None:  # before the first push: an owned field follows the map and the goal; set_goals dropped it
         foq = old._field_of_query
         if old._owns_field and (fld.stale or goal_rows is not None):
-            rows, tol, foq = _distinct_goals(prm["goal_rows"] if multi else prm["goal_row"], prm["goal_kw"]["tol_pos"])
+            rows, tol, foq = _distinct_goals(prm["goal_rows"], prm["goal_kw"]["tol_pos"])
             fld.build(rows, tol)
             old._field_of_query = foq
         opn.set_field(fld, foq)
-    kept = sel = imp = lists = None
-    try:
-        kept, sel, imp = TableFrontier(env, capacity), TableFrontier(env, fcap), TableFrontier(env, capacity)
-        lists = env.alloc_lists(fcap, want_state=True, stride=prm["lists_stride"])
+    with contextlib.ExitStack() as always:
+        scratch = _own(always, _Scratch())
+        kept, sel, imp = (scratch.add(TableFrontier(env, c)) for c in (capacity, fcap, capacity))
+        lists = scratch.add(env.alloc_lists(fcap, want_state=True, stride=prm["lists_stride"]))
         if timed:
             executed = _executed(old, tab, roots)
             info = tab.rebase_timed(roots, check_edges=check_edges, allow_wait=wait, avoid=avoid, frontier=kept)
@@ -1360,46 +1337,24 @@ def run_replan(old, multi, roots, goal_rows, check_edges, priors=None, timed=Fal
         if park:
             avoid.park(opn, kept, n_kept)
         rounds, expanded = [0] * Q, [0] * Q
-        query = None
-        if multi and n_kept:  # whose the kept rows are: the forced chunks are counted per query
-            query = tab._read(tab.query_ptr(), np.int32, tab.stats()[0])[kept.id.download(np.int32, (n_kept,))] if tab.query_ptr() \
-                else np.zeros(n_kept, np.int32)
+        query = np.zeros(n_kept, np.int32)  # whose the kept rows are: the forced chunks are counted per query
+        if multi and n_kept and tab.query_ptr():
+            query = tab._read(tab.query_ptr(), np.int32, tab.stats()[0])[kept.id.download(np.int32, (n_kept,))]
         total = 0
         for first in range(0, n_kept, max(fcap, 1)):
             n = min(fcap, n_kept - first)
-            rows = kept.rows(first, n)
-            env.expand_lists_resident(rows, lists, n_nodes=n)
-            if wait:
-                _add_waits(env, avoid, rows, lists, n)
-            if timed and avoid is not None:
-                avoid.check(rows, lists, n, table=tab)
-            tab.relax(lists, rows.id, rows.g, g_max, frontier=imp, n_nodes=n, want_count=False)
-            opn.push(imp, n_max=n * lists.stride, eps=eps, sight=sight)
-            if park:
-                avoid.park(opn, imp, n * lists.stride)
+            _round(env, tab, opn, avoid, kept.rows(first, n), imp, lists, n, prm, wait, park)
             total += 1
-            if query is None:
-                rounds[0] += 1
-                expanded[0] += n
-            else:
-                per = np.bincount(query[first:first + n], minlength=Q)
-                for q in range(Q):
-                    if per[q]:
-                        rounds[q] += 1
-                        expanded[q] += int(per[q])
-        status, res, total = _search_loop(env, who, multi, tab, opn, sel, imp, lists, prm, total, rounds, expanded,
-                                          avoid if timed else None)
-        if multi:
-            new = MultiSearchResult(status, res, tab, opn, rounds, expanded, total, env, prm)
-        else:
-            new = SearchResult(status[0], res[0], tab, opn, total, expanded[0], env, prm)
+            per = np.bincount(query[first:first + n], minlength=Q)
+            for q in range(Q):
+                if per[q]:
+                    rounds[q] += 1
+                    expanded[q] += int(per[q])
+        status, res, total = _search_loop(env, who, multi, tab, opn, sel, imp, lists, prm, total, rounds, expanded, avoid)
+        new = type(old)._of(status, res, tab, opn, rounds, expanded, total, env, prm)
         new.rebase_info = info
         if timed:
             new._executed = executed
-        _hand_field(new, old)
+        new._hand_field(old)
         old.table = old.open = None  # the new result owns them
         return new
-    finally:
-        for b in (kept, sel, imp, lists):
-            if b is not None:
-                b.free()
