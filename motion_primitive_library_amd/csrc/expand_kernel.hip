@@ -9,29 +9,25 @@
 // This is the device side of MPL::env_map<Dim>::get_succ
 //   reference include/mpl_planner/env/env_map.h:147-172 (get_succ)
 //   reference include/mpl_planner/env/env_map.h:90-132  (traverse_primitive)
-// written against the arithmetic specification in SURVEY.md Appendix A.  The
-// result must be bit-identical to the CPU path, so:
-//   * the file is compiled with -ffp-contract=off (no FMA contraction) and
-//     without any fast-math flag; every product / sum below is one IEEE
-//     binary64 operation in the reference's evaluation order;
-//   * divisions are true divisions (never multiplication by a reciprocal);
-//   * the sample time is accumulated (t += dt), never computed as k*dt
-//     (env_map.h:97-99 runs n or n+1 iterations depending on rounding);
-//   * structurally-zero coefficient terms are dropped only where that cannot
-//     change a bit of the result; the emitted
-//     successor state keeps the leading `0.0 +` so that signed zeros match.
-//
-// Polynomial layout (reference include/mpl_basis/primitive.h:34-50): per axis
-//   p(t) = c0/120 t^5 + c1/24 t^4 + c2/6 t^3 + c3/2 t^2 + c4 t + c5
-// and for a forward primitive of control order K (1 VEL, 2 ACC, 3 JRK, 4 SNP)
-// only c[5-K] .. c5 are non-zero: c5 = pos, c4 = vel (or u for K = 1), ...
+// The arithmetic and the rules that keep it bit-identical to the CPU path are
+// stated in mplx_pair_device.h; the polynomial (dev::Ax), the lattice hash,
+// the heading check and wrap_angle are the shared ones.  The kernel body below
+// still spells the steps of pair::Pair out (init, heading_valid, limits_valid,
+// classify, in that order and expression for expression): built on the struct
+// it is 3 % slower on C4, see the note in mplx_pair_device.h.
+// Final outputs stream past L2 (never re-read by this kernel); scratch for the
+// compaction stays cached.
 #include "mplx_internal.h"
-#include "mplx_device_common.h"  // near_limit / flag_node of the yaw pinning
+#include "mplx_pair_device.h"
 
 #include <math.h>
 
 namespace mplx {
 namespace {
+
+using dev::wrap_angle;
+using pair::heading_ok;
+using pair::lattice_hash;
 
 constexpr int kBlock = 256;
 
@@ -39,185 +35,6 @@ template <typename T>
 __device__ __forceinline__ void st_out(T *p, T v, bool stream) {
   if (stream) __builtin_nontemporal_store(v, p);
   else *p = v;
-}
-
-// ---------------------------------------------------------------- lattice hash
-// boost::hash_combine in its classic (< 1.81) form with hash_value(int) =
-// sign-extending conversion; reference include/mpl_basis/waypoint.h:93-125.
-__device__ __forceinline__ void fold(uint64_t &seed, int id) {
-  seed ^= (uint64_t)(int64_t)id + 0x9e3779b9ULL + (seed << 6) + (seed >> 2);
-}
-// `int id = std::round(x / q)`: round half away from zero, then value-convert.
-__device__ __forceinline__ int quantise(double x, double q) { return (int)round(x / q); }
-
-template <int D, int K, bool YAW>
-__device__ __forceinline__ uint64_t lattice_hash(const double *pos, const double *vel,
-                                                 const double *acc, const double *jrk, double yaw) {
-  uint64_t h = 0;
-#pragma unroll
-  for (int i = 0; i < D; i++) {
-    fold(h, quantise(pos[i], 0.01));
-    if (K >= 2) fold(h, quantise(vel[i], 0.1));
-    if (K >= 3) fold(h, quantise(acc[i], 0.1));
-    if (K >= 4) fold(h, quantise(jrk[i], 0.1));
-  }
-  if (YAW) fold(h, quantise(yaw, 0.1));
-  return h;
-}
-
-// reference include/mpl_basis/math.h:15-19
-__device__ __forceinline__ double wrap_angle(double a) {
-  while (a > M_PI) a -= 2.0 * M_PI;
-  while (a < -M_PI) a += 2.0 * M_PI;
-  return a;
-}
-
-// ------------------------------------------------------------ one axis, order K
-// Hoisted per-pair constants of one axis.  c1..c5 are the reference
-// coefficients; the quotients are the `c_k / const` sub-expressions of
-// primitive.h:128-145, each computed once (bit-exact hoist).
-template <int K>
-struct Axis {
-  double c1, c2, c3, c4, c5;
-  double c1_24, c1_6, c1_2, c2_6, c2_2, c3_2;
-
-  __device__ __forceinline__ void init(double p, double v, double a, double j, double u) {
-    c1 = c2 = c3 = c4 = 0.0;
-    c5 = p;
-    if (K == 1) { c4 = u; }
-    if (K == 2) { c4 = v; c3 = u; }
-    if (K == 3) { c4 = v; c3 = a; c2 = u; }
-    if (K == 4) { c4 = v; c3 = a; c2 = j; c1 = u; }
-    c3_2 = c3 / 2;
-    c2_6 = c2 / 6;
-    c2_2 = c2 / 2;
-    c1_24 = c1 / 24;
-    c1_6 = c1 / 6;
-    c1_2 = c1 / 2;
-  }
-
-  // Z = 0.0 gives the exact reference value including the sign of a zero
-  // result (the dropped leading terms sum to +0.0); pass Z = -0.0 (the additive
-  // identity, folded away) on paths where the sign of zero cannot matter.
-  // primitive.h:128-131
-  template <bool EXACT>
-  __device__ __forceinline__ double pos(double t) const {
-    double s;
-    if (K == 1) { s = c4 * t; if (EXACT) s = 0.0 + s; return s + c5; }
-    if (K == 2) { s = (c3_2 * t) * t; if (EXACT) s = 0.0 + s; return (s + c4 * t) + c5; }
-    if (K == 3) {
-      s = c2_6 * ((t * t) * t);
-      if (EXACT) s = 0.0 + s;
-      return ((s + (c3_2 * t) * t) + c4 * t) + c5;
-    }
-    const double t3 = (t * t) * t;
-    s = c1_24 * (t3 * t);
-    if (EXACT) s = 0.0 + s;
-    return (((s + c2_6 * t3) + (c3_2 * t) * t) + c4 * t) + c5;
-  }
-  // primitive.h:134-137
-  template <bool EXACT>
-  __device__ __forceinline__ double vel(double t) const {
-    double s;
-    if (K == 1) { return EXACT ? 0.0 + c4 : c4; }
-    if (K == 2) { s = c3 * t; if (EXACT) s = 0.0 + s; return s + c4; }
-    if (K == 3) { s = (c2_2 * t) * t; if (EXACT) s = 0.0 + s; return (s + c3 * t) + c4; }
-    s = c1_6 * ((t * t) * t);
-    if (EXACT) s = 0.0 + s;
-    return ((s + (c2_2 * t) * t) + c3 * t) + c4;
-  }
-  // primitive.h:140-142
-  template <bool EXACT>
-  __device__ __forceinline__ double acc(double t) const {
-    double s;
-    if (K == 1) return 0.0;
-    if (K == 2) { return EXACT ? 0.0 + c3 : c3; }
-    if (K == 3) { s = c2 * t; if (EXACT) s = 0.0 + s; return s + c3; }
-    s = (c1_2 * t) * t;
-    if (EXACT) s = 0.0 + s;
-    return (s + c2 * t) + c3;
-  }
-  // primitive.h:145
-  template <bool EXACT>
-  __device__ __forceinline__ double jrk(double t) const {
-    double s;
-    if (K <= 2) return 0.0;
-    if (K == 3) { return EXACT ? 0.0 + c2 : c2; }
-    s = c1 * t;
-    if (EXACT) s = 0.0 + s;
-    return s + c2;
-  }
-
-  // primitive.h:353-363 with extrema_v :152-162 and solve/quad math.h:117-131,
-  // :22-32.  |v(0)| is |c4| for every K (the other terms are exact zeros).
-  __device__ __forceinline__ double max_vel(double T) const {
-    const double v0 = fabs(c4), vT = fabs(vel<false>(T));
-    double m = (v0 < vT) ? vT : v0;
-    if (K == 3) {
-      if (c2 != 0) {
-        const double r = -c3 / c2;
-        if (r > 0 && r < T) { const double v = fabs(vel<false>(r)); m = v > m ? v : m; }
-      }
-    }
-    if (K == 4) {
-      if (c1_2 != 0) {
-        const double disc = c2 * c2 - 4 * c1_2 * c3;
-        if (!(disc < 0)) {
-          const double sq = sqrt(disc);
-          const double r1 = (-c2 - sq) / (2 * c1_2);
-          const double r2 = (-c2 + sq) / (2 * c1_2);
-          // roots are visited in solver order; the scan stops at the first
-          // root >= T (primitive.h:156-160)
-          bool go_on = true;
-          if (r1 > 0 && r1 < T) { const double v = fabs(vel<false>(r1)); m = v > m ? v : m; }
-          else if (r1 >= T) go_on = false;
-          if (go_on && r2 > 0 && r2 < T) { const double v = fabs(vel<false>(r2)); m = v > m ? v : m; }
-        }
-      } else if (c2 != 0) {
-        const double r = -c3 / c2;
-        if (r > 0 && r < T) { const double v = fabs(vel<false>(r)); m = v > m ? v : m; }
-      }
-    }
-    return m;
-  }
-  // primitive.h:369-379 with extrema_a :169-179
-  __device__ __forceinline__ double max_acc(double T) const {
-    const double a0 = fabs(c3), aT = fabs(acc<false>(T));
-    double m = (a0 < aT) ? aT : a0;
-    if (K == 4) {
-      if (c1 != 0) {
-        const double r = -c2 / c1;
-        if (r > 0 && r < T) { const double a = fabs(acc<false>(r)); m = a > m ? a : m; }
-      }
-    }
-    return m;
-  }
-  // primitive.h:384-394; extrema_j :186-193 has no root because c0 == 0
-  __device__ __forceinline__ double max_jrk(double T) const {
-    const double j0 = fabs(c2), jT = fabs(jrk<false>(T));
-    return (j0 < jT) ? jT : j0;
-  }
-  // Control effort of this axis, primitive.h:92-122.  For a forward primitive
-  // every term but the last is an exact +/-0 and the partial sums stay +0, so
-  // J = (u*u)*T bit-for-bit.
-  __device__ __forceinline__ double effort(double T) const {
-    const double u = (K == 1) ? c4 : (K == 2) ? c3 : (K == 3) ? c2 : c1;
-    return u * u * T;
-  }
-};
-
-// primitive.h:504-525, one end of the primitive.  cs: the host libm's {cos(yaw), sin(yaw)} in the override pass of
-// the yaw pinning (YawPin, mplx_internal.h), else null; *amb: the decision is within `margin` of the threshold.
-__device__ __forceinline__ bool heading_ok(double vx, double vy, double yaw, double cos_lim, const double *cs,
-                                           double margin, double tie_yaw, bool *amb) {
-  if (vx != 0 || vy != 0) {
-    const double s = sqrt(vx * vx + vy * vy);
-    const double c = cs ? cs[0] : cos(yaw), sn = cs ? cs[1] : sin(yaw);
-    const double d = vx / s * c + vy / s * sn;
-    *amb = *amb || mplx::dev::near_limit(d, cos_lim, margin, vy, yaw, tie_yaw);
-    if (d < cos_lim) return false;
-  }
-  return true;
 }
 
 // ------------------------------------------------------------------ the kernel
@@ -246,7 +63,7 @@ __global__ __launch_bounds__(kBlock) void expand_kernel(const ExpandArgs A) {
   const double *u = A.U + (int64_t)ci * A.udim;
 
   const double T = A.dt;
-  Axis<K> ax[D];
+  dev::Ax<K> ax[D];
 #pragma unroll
   for (int i = 0; i < D; i++) ax[i].init(cpos[i], cvel[i], cacc[i], cjrk[i], u[i]);
   const double uyaw = YAW ? u[D] : 0.0;

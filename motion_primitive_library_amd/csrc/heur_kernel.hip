@@ -24,12 +24,12 @@ __device__ __forceinline__ uint64_t state_hash(int control, const double *s) {
   uint64_t h = 0;
 #pragma unroll
   for (int i = 0; i < D; i++) {
-    if (control & 1) pair::fold(h, pair::quantise(s[i], 0.01));
-    if (control & 2) pair::fold(h, pair::quantise(s[D + i], 0.1));
-    if (control & 4) pair::fold(h, pair::quantise(s[2 * D + i], 0.1));
-    if (control & 8) pair::fold(h, pair::quantise(s[3 * D + i], 0.1));
+    if (control & 1) dev::fold(h, pair::quantise(s[i], 0.01));
+    if (control & 2) dev::fold(h, pair::quantise(s[D + i], 0.1));
+    if (control & 4) dev::fold(h, pair::quantise(s[2 * D + i], 0.1));
+    if (control & 8) dev::fold(h, pair::quantise(s[3 * D + i], 0.1));
   }
-  if (control & 16) pair::fold(h, pair::quantise(s[4 * D], 0.1));
+  if (control & 16) dev::fold(h, pair::quantise(s[4 * D], 0.1));
   return h;
 }
 

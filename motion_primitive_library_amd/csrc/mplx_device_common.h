@@ -1,10 +1,10 @@
-// mplx_device_common.h -- device helpers shared by the list-producing kernels
-// (expand_tile_kernel.hip, expand_grid_kernel.hip): the hoisted exact division,
-// the lattice hash (reference include/mpl_basis/waypoint.h:93-125) and the
+// mplx_device_common.h -- device helpers shared by every kernel that evaluates
+// primitives: the hoisted exact division, the lattice hash of the list kernels
+// (reference include/mpl_basis/waypoint.h:93-125), normalize_angle and the
 // per-axis polynomial of a forward primitive (reference
-// include/mpl_basis/primitive.h:34-50,128-145,353-394).  Derivations of every
-// expression are in expand_kernel.hip.  Compile with -ffp-contract=off; the only
-// fused operations are the explicit fma's of the division tail.
+// include/mpl_basis/primitive.h:34-50,128-145,353-394), each stated once, with
+// its derivation next to the expression.  Compile with -ffp-contract=off; the
+// only fused operations are the explicit fma's of the division tail.
 #ifndef MPLX_DEVICE_COMMON_H
 #define MPLX_DEVICE_COMMON_H
 
@@ -32,12 +32,22 @@ __device__ __forceinline__ double refined_rcp(double d) {
   return r;
 }
 
+// boost::hash_combine in its classic (< 1.81) form with hash_value(int) =
+// sign-extending conversion; reference include/mpl_basis/waypoint.h:93-125.
 __device__ __forceinline__ void fold(uint64_t &seed, int id) {
   seed ^= (uint64_t)(int64_t)id + 0x9e3779b9ULL + (seed << 6) + (seed >> 2);
 }
 // `int id = std::round(x / q)` (waypoint.h:95-112), division by a constant
+// (the refined reciprocal, no yaw: not pair::quantise's true division on purpose)
 __device__ __forceinline__ int quantise(double x, double q, double Rq) {
   return (int)round(div_by(x, q, Rq));
+}
+
+// reference include/mpl_basis/math.h:15-19
+__device__ __forceinline__ double wrap_angle(double a) {
+  while (a > M_PI) a -= 2.0 * M_PI;
+  while (a < -M_PI) a += 2.0 * M_PI;
+  return a;
 }
 
 // ---- wave-wide min / max of an int over all 64 lanes (all lanes must be active), result uniform.  Seven DPP moves
@@ -129,8 +139,14 @@ __device__ __forceinline__ uint64_t lattice_hash(const double *pos, const double
   return h;
 }
 
-// Per-axis polynomial of a forward primitive, see expand_kernel.hip for the
-// derivation of every expression (primitive.h:128-145, 353-394).
+// ------------------------------------------------------------ one axis, order K
+// Per-axis polynomial of a forward primitive (reference include/mpl_basis/primitive.h:34-50):
+//   p(t) = c0/120 t^5 + c1/24 t^4 + c2/6 t^3 + c3/2 t^2 + c4 t + c5
+// and for control order K (1 VEL, 2 ACC, 3 JRK, 4 SNP) only c[5-K] .. c5 are non-zero: c5 = pos, c4 = vel (or u for
+// K = 1), ...  c1..c5 are the reference coefficients; the quotients `c_k / const` are the sub-expressions of
+// primitive.h:128-145, true divisions written where the reference has them (the compiler computes each once per pair).
+// Structurally-zero coefficient terms are dropped only where that cannot change a bit of the result (SURVEY.md
+// Appendix A-7).
 template <int K>
 struct Ax {
   double c1, c2, c3, c4, c5;
@@ -142,6 +158,10 @@ struct Ax {
     if (K == 3) { c4 = v; c3 = a; c2 = u; }
     if (K == 4) { c4 = v; c3 = a; c2 = j; c1 = u; }
   }
+  // EXACT (the leading `0.0 +`) gives the exact reference value including the sign of a zero result (the dropped
+  // leading terms sum to +0.0): the emitted successor state.  Without it the addition of the identity is left out, on
+  // paths where the sign of zero cannot matter.
+  // primitive.h:128-131
   template <bool EXACT>
   __device__ __forceinline__ double pos(double t) const {
     double s;
@@ -167,6 +187,7 @@ struct Ax {
     return (((qtop * (t3 * t) + (c2 / 6) * t3) + ((c3 / 2) * t) * t) + c4 * t) + c5;
   }
   __device__ __forceinline__ double top_quotient() const { return K == 3 ? c2 / 6 : (K == 4 ? c1 / 24 : 0.0); }
+  // primitive.h:134-137
   template <bool EXACT>
   __device__ __forceinline__ double vel(double t) const {
     double s;
@@ -177,6 +198,7 @@ struct Ax {
     if (EXACT) s = 0.0 + s;
     return ((s + ((c2 / 2) * t) * t) + c3 * t) + c4;
   }
+  // primitive.h:140-142
   template <bool EXACT>
   __device__ __forceinline__ double acc(double t) const {
     double s;
@@ -187,6 +209,7 @@ struct Ax {
     if (EXACT) s = 0.0 + s;
     return (s + c2 * t) + c3;
   }
+  // primitive.h:145
   template <bool EXACT>
   __device__ __forceinline__ double jrk(double t) const {
     double s;
@@ -196,6 +219,9 @@ struct Ax {
     if (EXACT) s = 0.0 + s;
     return s + c2;
   }
+  // primitive.h:353-363 with extrema_v :152-162 and solve/quad math.h:117-131, :22-32.  |v(0)| is |c4| for every K (the
+  // other terms are exact zeros).  K = 4: the roots are visited in solver order (r1, then r2) and the scan stops at
+  // the first root >= T (primitive.h:156-160).
   __device__ __forceinline__ double max_vel(double T) const {
     const double v0 = fabs(c4), vT = fabs(vel<false>(T));
     double m = (v0 < vT) ? vT : v0;
@@ -225,6 +251,7 @@ struct Ax {
     }
     return m;
   }
+  // primitive.h:369-379 with extrema_a :169-179
   __device__ __forceinline__ double max_acc(double T) const {
     const double a0 = fabs(c3), aT = fabs(acc<false>(T));
     double m = (a0 < aT) ? aT : a0;
@@ -236,10 +263,13 @@ struct Ax {
     }
     return m;
   }
+  // primitive.h:384-394; extrema_j :186-193 has no root because c0 == 0
   __device__ __forceinline__ double max_jrk(double T) const {
     const double j0 = fabs(c2), jT = fabs(jrk<false>(T));
     return (j0 < jT) ? jT : j0;
   }
+  // Control effort of this axis, primitive.h:92-122.  For a forward primitive every term but the last is an exact +/-0
+  // and the partial sums stay +0, so J = (u*u)*T bit-for-bit.
   __device__ __forceinline__ double effort(double T) const {
     const double u = (K == 1) ? c4 : (K == 2) ? c3 : (K == 3) ? c2 : c1;
     return u * u * T;

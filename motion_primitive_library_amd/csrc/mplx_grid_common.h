@@ -171,13 +171,6 @@ __device__ __forceinline__ int pair_flags(const int *s_eflag, int ndp, int j0, i
 // misc words of a wave
 enum { M_BASE = 0, M_NV = 6, M_NODEQ = 12, M_VL = 24, M_YQ = 36, M_VLC = 37, M_WORDS = 49 };  // NV: valid entries per axis; NODEQ: [D][4]; VL: [D][16] bytes; YQ: the node's yaw integer; VLC: [D][16] bytes, the entries whose row the current sample count needs
 
-// reference include/mpl_basis/math.h:15-19
-__device__ __forceinline__ double wrap_angle(double a) {
-  while (a > M_PI) a -= 2.0 * M_PI;
-  while (a < -M_PI) a += 2.0 * M_PI;
-  return a;
-}
-
 }  // namespace
 }  // namespace mplx
 #endif

@@ -59,16 +59,16 @@ __device__ __forceinline__ void eval_segment(const double *seg, int64_t N, doubl
   }
   if (WANT_ALL) {
     const double uy = seg[(NA * D) * N], y0 = seg[(NA * D + 1) * N];
-    o.yaw = pair::wrap_angle((0.0 + uy * t) + y0);
-    o.yaw_dot = pair::wrap_angle(0.0 + uy);  // (yes: normalize_angle of the yaw rate, trajectory.h:126)
+    o.yaw = dev::wrap_angle((0.0 + uy * t) + y0);
+    o.yaw_dot = dev::wrap_angle(0.0 + uy);  // (yes: normalize_angle of the yaw rate, trajectory.h:126)
   }
 }
 
-// One segment of a chain: the primitive of (state s, control row up) per axis (primitive.h:34-50 through pair::Axis) and
+// One segment of a chain: the primitive of (state s, control row up) per axis (primitive.h:34-50 through dev::Ax) and
 // its rows c1 .. c5 per axis, then the yaw primitive's rate and yaw, stride N -- what eval_segment reads.  The chain
 // launch (traj_kernel.hip) stores into the segment table with it; reserve_kernel.hip into registers (N = 1).
 template <int D, int K>
-__device__ __forceinline__ void chain_segment(const double *s, const double *up, double uy, double cyaw, pair::Axis<K> (&ax)[D],
+__device__ __forceinline__ void chain_segment(const double *s, const double *up, double uy, double cyaw, dev::Ax<K> (&ax)[D],
                                               double *seg, int64_t N) {
 #pragma unroll
   for (int i = 0; i < D; i++) ax[i].init(s[i], s[D + i], s[2 * D + i], s[3 * D + i], up[i]);

@@ -111,7 +111,7 @@ __global__ __launch_bounds__(kBlock) void replan_edge_kernel(const std::conditio
         }
         if (X.time_keys) {
           const double tc = R.state[(int64_t)(4 * D + 1) * R.cap + p] + A.dt;
-          pair::fold(key, pair::quantise(tc, 0.1));
+          dev::fold(key, pair::quantise(tc, 0.1));
         }
       }
       if (!holds || key != R.hash[id]) {
@@ -309,7 +309,7 @@ __global__ __launch_bounds__(kBlock) void replan_reserve_kernel(const ReplanTime
     }
     double seg[5 * D + 2];
     {
-      pair::Axis<K> ax[D];
+      dev::Ax<K> ax[D];
       traj::chain_segment<D, K>(ps, A.U + (int64_t)a * A.udim, 0.0, 0.0, ax, seg, 1);
     }
     const bool one_tile = A.B <= kWave;

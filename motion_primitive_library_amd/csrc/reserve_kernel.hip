@@ -98,7 +98,7 @@ __global__ __launch_bounds__(kWave) void reserve_check_kernel(const ReserveArgs 
     double seg[5 * D + 2];
     {
       const double *up = A.U + (int64_t)(looked ? a : 0) * A.udim;  // (row 0 of a table that has one: nothing of it is used)
-      pair::Axis<K> ax[D];
+      dev::Ax<K> ax[D];
       traj::chain_segment<D, K>(ps, up, 0.0, 0.0, ax, seg, 1);
     }
     long long key = kNoHit;

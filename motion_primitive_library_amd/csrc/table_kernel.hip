@@ -314,7 +314,7 @@ __global__ __launch_bounds__(kBlock) void table_time_key_kernel(const int32_t *c
     if ((int)(e - k * S) >= count[k]) return;  // nothing of an entry past count[k] is read
   }
   uint64_t h = hash[e];
-  pair::fold(h, pair::quantise(t[e], 0.1));
+  dev::fold(h, pair::quantise(t[e], 0.1));
   key[e] = h;
 }
 

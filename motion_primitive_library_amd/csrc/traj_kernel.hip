@@ -3,7 +3,7 @@
 // (include/mplx_traj.h; reference include/mpl_basis/trajectory.h, primitive.h:92-145, env_map.h:229-255).
 //
 // traj_chain_kernel<D, K>: one lane per trajectory, the shape of rollout_kernel.  The state stays in registers; a step
-// is the successor evaluation of mplx_pair_device.h (Axis<K>, the `0.0 +` forms; no validity check of any kind) and
+// is the successor evaluation of mplx_pair_device.h (dev::Ax<K>, the `0.0 +` forms; no validity check of any kind) and
 // writes one row set of the segment table (TrajArgs, mplx_internal.h): coefficients c1 .. c5 per axis, the yaw
 // primitive, tau.  The five efforts are summed per segment in the reference's order with its expression trees.
 //
@@ -102,7 +102,7 @@ __global__ __launch_bounds__(kBlock) void traj_chain_kernel(const TrajArgs R) {
     }
     const double *up = A.U + (int64_t)a * A.udim;
     const double uy = R.yaw ? up[D] : 0.0, cyaw = R.yaw ? s[4 * D] : 0.0;  // (no yaw bit: pr_yaw_ stays all zero)
-    pair::Axis<K> ax[D];
+    dev::Ax<K> ax[D];
     R.tab_tau[(int64_t)h * N + k] = tau;
     traj::chain_segment<D, K>(s, up, uy, cyaw, ax, R.tab_seg + (int64_t)h * NC * N + k, N);
     if (R.seg_state) {
@@ -133,7 +133,7 @@ __global__ __launch_bounds__(kBlock) void traj_chain_kernel(const TrajArgs R) {
       s[2 * D + i] = ax[i].template acc<true>(T);
       s[3 * D + i] = ax[i].template jrk<true>(T);
     }
-    s[4 * D] = R.yaw ? pair::wrap_angle((0.0 + uy * T) + cyaw) : 0.0;
+    s[4 * D] = R.yaw ? dev::wrap_angle((0.0 + uy * T) + cyaw) : 0.0;
     s[4 * D + 1] = s[4 * D + 1] + T;
     tau = T + tau;  // trajectory.h:54
     S++;
@@ -381,12 +381,12 @@ __device__ __forceinline__ uint64_t prior_goal_hash(int control, const Sample<D>
   uint64_t h = 0;
 #pragma unroll
   for (int i = 0; i < D; i++) {
-    if (control & 1) pair::fold(h, pair::quantise(sm.pos[i], 0.01));
-    if (control & 2) pair::fold(h, pair::quantise(sm.vel[i], 0.1));
-    if (control & 4) pair::fold(h, pair::quantise(sm.acc[i], 0.1));
-    if (control & 8) pair::fold(h, pair::quantise(sm.jrk[i], 0.1));
+    if (control & 1) dev::fold(h, pair::quantise(sm.pos[i], 0.01));
+    if (control & 2) dev::fold(h, pair::quantise(sm.vel[i], 0.1));
+    if (control & 4) dev::fold(h, pair::quantise(sm.acc[i], 0.1));
+    if (control & 8) dev::fold(h, pair::quantise(sm.jrk[i], 0.1));
   }
-  if (control & 16) pair::fold(h, pair::quantise(sm.yaw, 0.1));
+  if (control & 16) dev::fold(h, pair::quantise(sm.yaw, 0.1));
   return h;
 }
 

@@ -38,7 +38,7 @@ def wrap_angle(a):
 
 
 class Axis:
-    """pair::Axis<K> for K in 1 .. 4."""
+    """dev::Ax<K> for K in 1 .. 4."""
 
     def __init__(self, K, p, v, a, u, j=0.0):
         self.K = K
