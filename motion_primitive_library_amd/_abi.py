@@ -92,6 +92,9 @@ RESERVE_SYMBOLS = ["mplx_reserve_create", "mplx_reserve_destroy", "mplx_reserve_
                    "mplx_reserve_fill_traj_device", "mplx_reserve_fill_traj", "mplx_reserve_shape", "mplx_reserve_positions",
                    "mplx_reserve_set_queries", "mplx_reserve_check_device", "mplx_reserve_park_device"]
 RESERVE_MAX_BYTES = 1 << 30
+# ... and the ones include/mplx_reserve_poly.h declares (a solved set against a reservation table, the timed shortcut)
+RESERVE_POLY_SYMBOLS = ["mplx_reserve_check_poly_device", "mplx_reserve_check_poly", "mplx_shortcut_timed_device",
+                        "mplx_shortcut_timed"]
 # ... and the one include/mplx_wait.h declares (the zero control's entry appended to the lists of an expansion)
 WAIT_SYMBOLS = ["mplx_lists_add_wait_device"]
 # ... and the one include/mplx_replan_timed.h declares (the rebase of a table with time keys, waits and reservations)
@@ -251,6 +254,14 @@ class TauOut(C.Structure):
 class ConflictIn(C.Structure):
     _fields_ = [("step", C.c_double), ("n_steps", C.c_int32), ("mode", C.c_int32), ("t0", C.c_void_p), ("radius", C.c_void_p),
                 ("radius_all", C.c_double), ("group", C.c_void_p), ("rank", C.c_void_p), ("chunk_steps", C.c_int32)]
+
+
+class ReservePolyIn(C.Structure):
+    _fields_ = [("t_start", C.c_void_p), ("radius", C.c_void_p), ("radius_all", C.c_double), ("ignore_group", C.c_void_p)]
+
+
+class ReservePolyOut(C.Structure):
+    _fields_ = [("hit", C.c_void_p), ("status", C.c_void_p), ("n_hit", C.c_void_p)]
 
 
 class ConflictOut(C.Structure):
@@ -540,6 +551,10 @@ def lib():
         "mplx_reserve_set_queries": (C.c_int, [vp, i32, vp, vp, vp]),
         "mplx_reserve_check_device": (C.c_int, [vp, vp, C.POINTER(SuccLists), i64, vp, vp, i64, vp, vp]),
         "mplx_reserve_park_device": (C.c_int, [vp, vp, C.POINTER(TableFrontier), i64, vp, vp]),
+        "mplx_reserve_check_poly_device": (C.c_int, [vp, vp, C.POINTER(ReservePolyIn), C.POINTER(ReservePolyOut)]),
+        "mplx_reserve_check_poly": (C.c_int, [vp, vp, C.POINTER(ReservePolyIn), C.POINTER(ReservePolyOut)]),
+        "mplx_shortcut_timed_device": (C.c_int, [vp, vp, C.POINTER(ShortcutIn), C.POINTER(ShortcutOut), vp, vp]),
+        "mplx_shortcut_timed": (C.c_int, [vp, vp, C.POINTER(ShortcutIn), C.POINTER(ShortcutOut), vp, vp]),
         "mplx_lists_add_wait_device": (C.c_int, [vp, C.POINTER(SuccLists), i64, vp, i64, vp, vp]),
         "mplx_table_rebase_timed_device": (C.c_int, [vp, vp, i32, i32, vp, C.POINTER(TableFrontier), vp, vp, vp,
                                                     C.POINTER(RebaseResult)]),
@@ -560,7 +575,7 @@ def lib():
         "mplx_table_set_time_keys": (C.c_int, [vp, i32]),
         "mplx_time_key": (C.c_uint64, [C.c_uint64, dbl]),
     }
-    for name in SYMBOLS + MAP_UTIL_SYMBOLS + ROLLOUT_SYMBOLS + RAY_SYMBOLS + TRAJ_SYMBOLS + TABLE_SYMBOLS + OPEN_SYMBOLS + MULTI_SYMBOLS + REPLAN_SYMBOLS + PRIOR_SYMBOLS + SOLVE_SYMBOLS + LIMITS_SYMBOLS + SCALE_SYMBOLS + CONFLICT_SYMBOLS + RESERVE_SYMBOLS + WAIT_SYMBOLS + REPLAN_TIMED_SYMBOLS + FIELD_SYMBOLS + HEUR_SYMBOLS:
+    for name in SYMBOLS + MAP_UTIL_SYMBOLS + ROLLOUT_SYMBOLS + RAY_SYMBOLS + TRAJ_SYMBOLS + TABLE_SYMBOLS + OPEN_SYMBOLS + MULTI_SYMBOLS + REPLAN_SYMBOLS + PRIOR_SYMBOLS + SOLVE_SYMBOLS + LIMITS_SYMBOLS + SCALE_SYMBOLS + CONFLICT_SYMBOLS + RESERVE_SYMBOLS + RESERVE_POLY_SYMBOLS + WAIT_SYMBOLS + REPLAN_TIMED_SYMBOLS + FIELD_SYMBOLS + HEUR_SYMBOLS:
         fn = getattr(L, name)  # AttributeError if the library does not export it
         fn.restype, fn.argtypes = sig[name]
     _lib = L

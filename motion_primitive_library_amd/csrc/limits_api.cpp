@@ -1,8 +1,10 @@
 // limits_api.cpp -- C ABI of include/mplx_limits.h: caller-given segments into an mplx_poly (poly_load_kernel) and the
 // dynamic limits of the set a poly holds (poly_limits_kernel), both in limits_kernel.hip.  The host-pointer twins stage
 // through the context's arena and scatter the compact device rows into the caller's strides, as solve_api.cpp does.
+// The timed shortcut of include/mplx_reserve_poly.h is the shortcut with a reservation table, and stands next to it.
 #include "mplx_poly.h"
 #include "../../include/mplx_limits.h"
+#include "../../include/mplx_reserve_poly.h"
 
 #include <vector>
 
@@ -225,14 +227,33 @@ int check_shortcut(mplx_poly *pairs, mplx_poly *res, const char *who, const mplx
   return MPLX_OK;
 }
 
-// everything queued on the stream, no read-back: pairs -> solve -> info, limits, traverse -> costs, programme -> gather
-int shortcut_launch(mplx_poly *pairs, mplx_poly *res, const mplx_shortcut_in *in, const mplx_shortcut_out *out, int64_t NP) {
+// the reservation table of a timed shortcut: NULL res / another context / a number of queries other than n_query:
+// MPLX_ERR_ARG; before a fill or mplx_reserve_set_queries: MPLX_ERR_STATE
+int check_table(mplx_poly *pairs, const char *who, const mplx_shortcut_in *in, mplx_reserve *table, mplx::ReserveArgs *t) {
+  mplx_ctx *c = pairs->c;
+  if (!table) return fail(c, MPLX_ERR_ARG, "%s: NULL reservation table", who);
+  mplx_ctx *tc = nullptr;
+  const int rc = reserve_table_args(table, who, &tc, t);  // (sets tc whatever it answers)
+  if (tc != c) return fail(c, MPLX_ERR_ARG, "%s: the reservation table belongs to another context", who);
+  if (rc) return rc;
+  if (t->Q != in->n_query)
+    return fail(c, MPLX_ERR_ARG, "%s: %d queries were set, the shortcut has %lld", who, (int)t->Q, (long long)in->n_query);
+  return MPLX_OK;
+}
+
+// everything queued on the stream, no read-back: pairs -> solve -> info, limits, traverse -> costs, programme -> gather.
+// table (optional): after the solve the rows of the pair set and its check against the table (include/mplx_reserve_poly.h);
+// without it exactly the launches of mplx_shortcut_device.
+int shortcut_launch(mplx_poly *pairs, mplx_poly *res, const mplx_shortcut_in *in, const mplx_shortcut_out *out, int64_t NP,
+                    const mplx::ReserveArgs *table = nullptr, int64_t *d_chain_hit = nullptr) {
   mplx_ctx *c = pairs->c;
   const size_t P = (size_t)NP, Q = (size_t)in->n_query, W = (size_t)in->w_max, F = 4 * (size_t)c->dim + 2;
   StageLayout l;  // (only the carving)
   const size_t o_wp = l.add(F * 2 * P * 8), o_dt = l.add(P * 8), o_eff = l.add(5 * P * 8), o_trav = l.add(P * 8), o_ec = l.add(P * 8),
                o_dist = l.add(W * Q * 8), o_nwp = l.add(P * 4), o_pred = l.add(W * Q * 4), o_src = l.add((W - 1) * Q * 4),
                o_fl = l.add(2 * P), o_valid = l.add(P), o_st = l.add(P);
+  const size_t o_ts = l.add(table ? P * 8 : 0), o_rad = l.add(table ? P * 8 : 0), o_ign = l.add(table ? P * 4 : 0),
+               o_hit = l.add(table ? P * 8 : 0);
   if (int rc = ensure(c, pairs->aux, l.total)) return rc;
   char *b = (char *)pairs->aux.p;
   mplx::ShortcutArgs a{};
@@ -257,6 +278,18 @@ int shortcut_launch(mplx_poly *pairs, mplx_poly *res, const mplx_shortcut_in *in
   if (int rc = mplx_solve_device(pairs, &si, &so)) return rc;
   if (caller_status) HIP_TRY(c, hipMemcpyAsync(caller_status, a.pair_status, P, hipMemcpyDeviceToDevice, c->stream));
   a.pair_T = (const double *)((char *)pairs->mem.p + pairs->o_T);
+  if (table) {
+    mplx::PairRowsArgs ra{};
+    ra.n_query = in->n_query; ra.w_max = in->w_max; ra.max_hop = in->max_hop;
+    ra.t_row = in->states + (int64_t)(F - 1) * in->w_max * in->stride; ra.stride = in->stride;
+    ra.q_t0 = table->q_t0; ra.q_r = table->q_r; ra.q_ignore = table->q_ignore;
+    ra.t_start = (double *)(b + o_ts); ra.radius = (double *)(b + o_rad); ra.ignore = (int32_t *)(b + o_ign);
+    HIP_TRY(c, mplx::launch_reserve_pair_rows(ra, c->stream));
+    if (int rc = reserve_check_poly_launch(*table, pairs, ra.t_start, ra.radius, 0.0, ra.ignore, (int64_t *)(b + o_hit), nullptr, nullptr))
+      return rc;
+    a.pair_hit = (const long long *)(b + o_hit);
+    a.chain_hit = (long long *)d_chain_hit;
+  }
   mplx_traj_info_out io{};
   io.effort = (double *)a.pair_effort; io.effort_stride = NP;
   if (int rc = mplx_poly_info_device(pairs, &io)) return rc;
@@ -274,6 +307,47 @@ int shortcut_launch(mplx_poly *pairs, mplx_poly *res, const mplx_shortcut_in *in
   gi.src = pairs; gi.src_index = a.src_index; gi.index_stride = in->n_query;
   mplx_poly_load_out go{};
   return mplx_poly_load_device(res, &gi, &go);
+}
+
+// the host rows of mplx_shortcut / mplx_shortcut_timed: carved, then (base known) copied in, the launches, copied out
+struct HostRows { size_t i_st, i_n, o_s, o_nk, o_k, o_c, o_cc, o_e, o_ch; };
+HostRows host_rows(mplx_ctx *c, const mplx_shortcut_in *h_in, int64_t NP, bool chain_hit, StageLayout *l) {
+  const size_t Q = (size_t)h_in->n_query, W = (size_t)h_in->w_max, F = 4 * (size_t)c->dim + 2, P = (size_t)NP;
+  HostRows r;
+  r.i_st = l->add(F * W * Q * 8); r.i_n = l->add(h_in->n_wp ? Q * 4 : 0);
+  r.o_s = l->add(Q); r.o_nk = l->add(Q * 4); r.o_k = l->add(W * Q * 4); r.o_c = l->add(Q * 8); r.o_cc = l->add(Q * 8); r.o_e = l->add(P * 8);
+  r.o_ch = l->add(chain_hit ? Q * 8 : 0);
+  return r;
+}
+
+int shortcut_staged(mplx_poly *pairs, mplx_poly *res, const mplx_shortcut_in *h_in, const mplx_shortcut_out *h_out, int64_t NP,
+                    const StageLayout &l, const HostRows &r, const mplx::ReserveArgs *table, int64_t *h_chain_hit) {
+  mplx_ctx *c = pairs->c;
+  const size_t Q = (size_t)h_in->n_query, W = (size_t)h_in->w_max, F = 4 * (size_t)c->dim + 2, P = (size_t)NP;
+  mplx_shortcut_in in = *h_in;
+  HIP_TRY(c, stage_in_rows(c, l.base + r.i_st, h_in->states, (size_t)h_in->stride * 8, Q * 8, F * W));
+  in.states = (const double *)(l.base + r.i_st); in.stride = (int64_t)Q;
+  if (h_in->n_wp) {
+    HIP_TRY(c, stage_in(c, l.base + r.i_n, h_in->n_wp, Q * 4));
+    in.n_wp = (const int32_t *)(l.base + r.i_n);
+  }
+  mplx_shortcut_out o{};
+  o.status = (uint8_t *)(l.base + r.o_s); o.n_keep = (int32_t *)(l.base + r.o_nk); o.keep = (int32_t *)(l.base + r.o_k); o.keep_stride = (int64_t)Q;
+  o.cost = (double *)(l.base + r.o_c); o.chain_cost = (double *)(l.base + r.o_cc); o.edge_cost = (double *)(l.base + r.o_e);
+  int64_t *d_ch = table && h_chain_hit ? (int64_t *)(l.base + r.o_ch) : nullptr;
+  if (int rc = shortcut_launch(pairs, res, &in, &o, NP, table, d_ch)) return rc;
+  std::vector<int32_t> keep(h_out->keep ? W * Q : 0);
+  HIP_TRY(c, stage_out(c, h_out->status, o.status, Q));
+  HIP_TRY(c, stage_out(c, h_out->n_keep, o.n_keep, Q * 4));
+  HIP_TRY(c, stage_out(c, keep.empty() ? nullptr : keep.data(), o.keep, keep.size() * 4));
+  HIP_TRY(c, stage_out(c, h_out->cost, o.cost, Q * 8));
+  HIP_TRY(c, stage_out(c, h_out->chain_cost, o.chain_cost, Q * 8));
+  HIP_TRY(c, stage_out(c, h_out->edge_cost, o.edge_cost, P * 8));
+  HIP_TRY(c, stage_out(c, d_ch ? h_chain_hit : nullptr, d_ch, Q * 8));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  for (size_t w = 0; w < W && h_out->keep; w++)
+    for (size_t k = 0; k < Q; k++) h_out->keep[(int64_t)w * h_out->keep_stride + (int64_t)k] = keep[w * Q + k];
+  return MPLX_OK;
 }
 
 }  // namespace
@@ -299,34 +373,46 @@ int mplx_shortcut(mplx_poly *pairs, mplx_poly *res, const mplx_shortcut_in *h_in
   MPLX_GUARD_BEGIN
   if (int rc = bind_device(c)) return rc;
   if (int rc = resolve_pending(c)) return rc;
-  const size_t Q = (size_t)h_in->n_query, W = (size_t)h_in->w_max, F = 4 * (size_t)c->dim + 2, P = (size_t)NP;
   StageLayout l;
-  const size_t i_st = l.add(F * W * Q * 8), i_n = l.add(h_in->n_wp ? Q * 4 : 0);
-  const size_t o_s = l.add(Q), o_nk = l.add(Q * 4), o_k = l.add(W * Q * 4), o_c = l.add(Q * 8), o_cc = l.add(Q * 8), o_e = l.add(P * 8);
+  const HostRows r = host_rows(c, h_in, NP, false, &l);
   if (int rc = stage_commit(c, &l)) return rc;
-  mplx_shortcut_in in = *h_in;
-  HIP_TRY(c, stage_in_rows(c, l.base + i_st, h_in->states, (size_t)h_in->stride * 8, Q * 8, F * W));
-  in.states = (const double *)(l.base + i_st); in.stride = (int64_t)Q;
-  if (h_in->n_wp) {
-    HIP_TRY(c, stage_in(c, l.base + i_n, h_in->n_wp, Q * 4));
-    in.n_wp = (const int32_t *)(l.base + i_n);
-  }
-  mplx_shortcut_out o{};
-  o.status = (uint8_t *)(l.base + o_s); o.n_keep = (int32_t *)(l.base + o_nk); o.keep = (int32_t *)(l.base + o_k); o.keep_stride = (int64_t)Q;
-  o.cost = (double *)(l.base + o_c); o.chain_cost = (double *)(l.base + o_cc); o.edge_cost = (double *)(l.base + o_e);
   // (the calls inside stage nothing: they are device forms, rule 4 of the arena)
-  if (int rc = shortcut_launch(pairs, res, &in, &o, NP)) return rc;
-  std::vector<int32_t> keep(h_out->keep ? W * Q : 0);
-  HIP_TRY(c, stage_out(c, h_out->status, o.status, Q));
-  HIP_TRY(c, stage_out(c, h_out->n_keep, o.n_keep, Q * 4));
-  HIP_TRY(c, stage_out(c, keep.empty() ? nullptr : keep.data(), o.keep, keep.size() * 4));
-  HIP_TRY(c, stage_out(c, h_out->cost, o.cost, Q * 8));
-  HIP_TRY(c, stage_out(c, h_out->chain_cost, o.chain_cost, Q * 8));
-  HIP_TRY(c, stage_out(c, h_out->edge_cost, o.edge_cost, P * 8));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  for (size_t w = 0; w < W && h_out->keep; w++)
-    for (size_t k = 0; k < Q; k++) h_out->keep[(int64_t)w * h_out->keep_stride + (int64_t)k] = keep[w * Q + k];
-  return MPLX_OK;
+  return shortcut_staged(pairs, res, h_in, h_out, NP, l, r, nullptr, nullptr);
+  MPLX_GUARD_END(c)
+}
+
+int mplx_shortcut_timed_device(mplx_poly *pairs, mplx_poly *res, const mplx_shortcut_in *d_in, const mplx_shortcut_out *d_out,
+                               mplx_reserve *table, int64_t *d_chain_hit) {
+  if (!pairs) return MPLX_ERR_ARG;
+  const char *who = "mplx_shortcut_timed_device";
+  int64_t NP = 0;
+  if (int rc = check_shortcut(pairs, res, who, d_in, d_out, &NP)) return rc;
+  mplx::ReserveArgs t{};
+  if (int rc = check_table(pairs, who, d_in, table, &t)) return rc;
+  if (NP == 0) return MPLX_OK;
+  if (int rc = bind_device(pairs->c)) return rc;
+  return shortcut_launch(pairs, res, d_in, d_out, NP, &t, d_chain_hit);
+}
+
+// The host rows lie in the reservation table's own row buffer, not in the context's arena: see mplx_reserve_check_poly.
+int mplx_shortcut_timed(mplx_poly *pairs, mplx_poly *res, const mplx_shortcut_in *h_in, const mplx_shortcut_out *h_out,
+                        mplx_reserve *table, int64_t *h_chain_hit) {
+  if (!pairs) return MPLX_ERR_ARG;
+  mplx_ctx *c = pairs->c;
+  const char *who = "mplx_shortcut_timed";
+  int64_t NP = 0;
+  if (int rc = check_shortcut(pairs, res, who, h_in, h_out, &NP)) return rc;
+  if (h_out->pair_out) return fail(c, MPLX_ERR_ARG, "%s: pair_out is for the _device form", who);
+  mplx::ReserveArgs t{};
+  if (int rc = check_table(pairs, who, h_in, table, &t)) return rc;
+  if (NP == 0) return MPLX_OK;
+  MPLX_GUARD_BEGIN
+  if (int rc = bind_device(c)) return rc;
+  if (int rc = resolve_pending(c)) return rc;
+  StageLayout l;
+  const HostRows r = host_rows(c, h_in, NP, h_chain_hit != nullptr, &l);
+  if (int rc = reserve_host_rows(table, l.total, &l.base)) return rc;
+  return shortcut_staged(pairs, res, h_in, h_out, NP, l, r, &t, h_chain_hit);
   MPLX_GUARD_END(c)
 }
 

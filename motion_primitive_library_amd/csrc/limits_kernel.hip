@@ -226,7 +226,9 @@ __global__ __launch_bounds__(kBlock) void shortcut_cost_kernel(const ShortcutArg
       if (!isfinite(trav)) trav = 0.0;
       c = base + trav;
     } else {
-      c = (P.pair_valid[p] == 1 && isfinite(trav)) ? base + trav : (double)INFINITY;
+      // (a timed shortcut, include/mplx_reserve_poly.h: ... and clear of the reservations, inside the table's horizon)
+      const bool clear = !P.pair_hit || P.pair_hit[p] == -1;
+      c = (P.pair_valid[p] == 1 && isfinite(trav) && clear) ? base + trav : (double)INFINITY;
     }
   }
   P.edge_cost[p] = c;
@@ -241,6 +243,14 @@ __global__ __launch_bounds__(kBlock) void shortcut_dp_kernel(const ShortcutArgs 
   const int wm = P.w_max, mh = P.max_hop;
   int W = P.n_wp ? P.n_wp[k] : wm;
   if (W > wm) W = wm;
+  if (P.chain_hit) {  // a timed shortcut: the smallest conflict of the chain's own edges, else -2 past the horizon, else -1
+    long long ch = -1;
+    for (int i = 0; i + 1 < W; i++) {
+      const long long h = P.pair_hit[(k * (wm - 1) + i) * mh];
+      if (h >= 0 ? (ch < 0 || h < ch) : (h == -2 && ch == -1)) ch = h;
+    }
+    P.chain_hit[k] = ch;
+  }
   for (int s = 0; s < wm - 1; s++) P.src_index[(int64_t)s * Q + k] = -1;
   if (P.keep)
     for (int w = 0; w < wm; w++) P.keep[(int64_t)w * P.keep_stride + k] = -1;

@@ -371,6 +371,12 @@ int table_replan_args(mplx_table *t, const char *who, bool scratch, mplx_ctx **c
 // answers), MPLX_ERR_STATE before a fill or before mplx_reserve_set_queries, else the table, query, control and scan
 // fields of `a` (the lists stay empty)
 int reserve_table_args(mplx_reserve *r, const char *who, mplx_ctx **c, mplx::ReserveArgs *a);
+// ... and as the check of a solved set (reserve_poly_api.cpp) sees it: MPLX_ERR_STATE before a fill only; the table
+// fields, Q (0 before mplx_reserve_set_queries) and, where Q >= 1, the query fields
+int reserve_fill_args(mplx_reserve *r, const char *who, mplx_ctx **c, mplx::ReserveArgs *a);
+// ... and `bytes` of the table's own row buffer, where the host-pointer calls of include/mplx_reserve_poly.h lay out their
+// rows with a StageLayout (they end in a synchronise; the buffer is the table's, not the context's arena)
+int reserve_host_rows(mplx_reserve *r, size_t bytes, char **base);
 // wait_api.cpp: the zero action of include/mplx_wait.h -- the smallest all-zero row of the control table -- or -1
 int32_t zero_action(const mplx_ctx *c);
 // ... and as the check of a reservation table (reserve_api.cpp) sees it: the same check, the per-node query column (null

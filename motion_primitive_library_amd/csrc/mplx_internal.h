@@ -713,6 +713,38 @@ struct ParkArgs {
 };
 hipError_t launch_reserve_park(int dim, const ParkArgs &a, int64_t rows, hipStream_t s);
 
+// Polynomial trajectories against a reservation table (reserve_poly_kernel.hip, reserve_poly_api.cpp;
+// include/mplx_reserve_poly.h).  The table fields of `res` are used (and its query fields by the pair rows); traj: the
+// segment table of the poly, with its Lambda.
+struct ReservePolyArgs {
+  ReserveArgs res;
+  TrajArgs traj;
+  int64_t K;                    // traj.n_traj
+  const double *t_start;        // [K]
+  const double *radius;         // [K] or null: radius_all
+  double radius_all;
+  const int32_t *ignore;        // [K] or null: -1
+  // outputs, any may be null
+  long long *hit;               // [K]
+  uint8_t *status;              // [K]
+  unsigned long long *n_hit;
+};
+hipError_t launch_reserve_check_poly(int dim, const ReservePolyArgs &a, hipStream_t s);
+
+// The [P] rows of a timed shortcut's pair set, one lane per pair p = (k (w_max - 1) + i) max_hop + h:
+// t_start = q_t0[k] + t_i, radius = q_r[k], ignore = q_ignore[k].
+struct PairRowsArgs {
+  int64_t n_query;
+  int32_t w_max, max_hop;
+  const double *t_row;          // the t row of the chain states: [w_max][stride]
+  int64_t stride;
+  const double *q_t0, *q_r;     // [Q]
+  const int32_t *q_ignore;      // [Q]
+  double *t_start, *radius;     // [P]
+  int32_t *ignore;              // [P]
+};
+hipError_t launch_reserve_pair_rows(const PairRowsArgs &a, hipStream_t s);
+
 // Wait edges (wait_kernel.hip, wait_api.cpp; include/mplx_wait.h): one lane per list row appends the zero control's entry.
 struct WaitArgs {
   ExpandArgs env;               // parameters and controls as expand_args() fills them; map, nodes and slots unused
@@ -756,6 +788,9 @@ struct ShortcutArgs {
   int32_t *n_keep, *keep;
   int64_t keep_stride;
   double *cost, *chain_cost, *edge_cost;
+  // the timed shortcut (include/mplx_reserve_poly.h; appended), both null without a reservation table
+  const long long *pair_hit;      // [P] hit of the pair set's check: a non-adjacent edge needs -1
+  long long *chain_hit;           // [Q] or null
 };
 hipError_t launch_shortcut_pairs(int dim, const ShortcutArgs &a, hipStream_t s);
 hipError_t launch_shortcut_dp(const ShortcutArgs &a, hipStream_t s);

@@ -61,5 +61,10 @@ inline mplx::TrajArgs poly_table_args(mplx_poly *p) {
 // scale_api.cpp: total_time[k] = the scaled total where problem k holds a Lambda (mplx_poly_info on a scaled set)
 int poly_lambda_total(mplx_poly *p, double *d_total_time);
 
+// reserve_poly_api.cpp: the launch of mplx_reserve_check_poly_device on table `a` (reserve_fill_args), device pointers,
+// nothing validated: what the timed shortcut (limits_api.cpp) queues for its pair set
+int reserve_check_poly_launch(const mplx::ReserveArgs &a, mplx_poly *p, const double *d_t_start, const double *d_radius,
+                              double radius_all, const int32_t *d_ignore, int64_t *d_hit, uint8_t *d_status, int64_t *d_n_hit);
+
 }  // namespace mplx_detail
 #endif

@@ -15,6 +15,7 @@ struct mplx_reserve {
   mplx_ctx *c = nullptr;
   DevBuf mem;      // the per-trajectory rows, then pos [D][n_steps][B] and act [n_steps][B]
   DevBuf queries;  // t0 [Q], radius [Q], ignore [Q]
+  DevBuf rows;     // the host rows of the host-pointer calls of include/mplx_reserve_poly.h; grown on demand
   bool filled = false;
   int32_t Q = 0;
   int64_t B = 0;
@@ -116,16 +117,28 @@ int check_traj(mplx_reserve *r, mplx_ctx *ctx, const char *who, const mplx_traj_
 
 }  // namespace
 
-int mplx_detail::reserve_table_args(mplx_reserve *r, const char *who, mplx_ctx **c, mplx::ReserveArgs *a) {
+int mplx_detail::reserve_fill_args(mplx_reserve *r, const char *who, mplx_ctx **c, mplx::ReserveArgs *a) {
   *c = r->c;
   if (!r->filled) return fail(r->c, MPLX_ERR_STATE, "%s: the reservation table has not been filled", who);
-  if (r->Q < 1) return fail(r->c, MPLX_ERR_STATE, "%s: mplx_reserve_set_queries has not been called", who);
   const char *b = (const char *)r->mem.p, *qb = (const char *)r->queries.p;
   a->pos = (const double *)(b + r->o_pos); a->act = (const uint8_t *)(b + r->o_act); a->incl = (const uint8_t *)(b + r->o_incl);
   a->r = (const double *)(b + r->o_r); a->group = (const int32_t *)(b + r->o_g);
   a->B = r->B; a->n_steps = r->n_steps; a->step = r->step;
-  a->q_t0 = (const double *)(qb + r->q_t0); a->q_r = (const double *)(qb + r->q_r); a->q_ignore = (const int32_t *)(qb + r->q_ign);
   a->Q = r->Q;
+  if (r->Q < 1) return MPLX_OK;
+  a->q_t0 = (const double *)(qb + r->q_t0); a->q_r = (const double *)(qb + r->q_r); a->q_ignore = (const int32_t *)(qb + r->q_ign);
+  return MPLX_OK;
+}
+
+int mplx_detail::reserve_host_rows(mplx_reserve *r, size_t bytes, char **base) {
+  if (int rc = ensure(r->c, r->rows, std::max<size_t>(bytes, 256))) return rc;
+  *base = (char *)r->rows.p;
+  return MPLX_OK;
+}
+
+int mplx_detail::reserve_table_args(mplx_reserve *r, const char *who, mplx_ctx **c, mplx::ReserveArgs *a) {
+  if (int rc = reserve_fill_args(r, who, c, a)) return rc;
+  if (r->Q < 1) return fail(r->c, MPLX_ERR_STATE, "%s: mplx_reserve_set_queries has not been called", who);
   mplx_ctx *x = r->c;
   a->U = (const double *)x->U.p; a->nU = x->nU; a->udim = x->udim;
   a->dt = x->prm.dt;
@@ -154,6 +167,7 @@ void mplx_reserve_destroy(mplx_reserve *r) {
   (void)hipStreamSynchronize(r->c->stream);
   release(r->mem);
   release(r->queries);
+  release(r->rows);
   delete r;
 }
 

@@ -1233,11 +1233,18 @@ class EnvMap:
         poly._lambda = None  # a new solve or load clears the Lambda
         return poly
 
-    def shortcut_resident(self, states, n_query, w_max, n_wp=None, control=None, max_hop=None, stride=None):
+    def shortcut_resident(self, states, n_query, w_max, n_wp=None, control=None, max_hop=None, stride=None, avoid=None, t0=None,
+                          radius=None, ignore_group=None):
         """mplx_shortcut_device on chain states that are on the device already (the seg_state rows of
         traj_info_resident(want_states=True): field f of state w of query k at [(f w_max + w) stride + k]); n_wp [Q] on
         the device or None.  Everything is queued without a read-back; then counts, costs, statuses, the kept indices and
-        the edge costs are read.  Returns a ShortcutResult."""
+        the edge costs are read.  Returns a ShortcutResult.
+
+        avoid: a search.Reservations: the timed shortcut (mplx_shortcut_timed_device, include/mplx_reserve_poly.h).  Chain
+        k starts at t0[k] on the table's clock (its clock is t0 + the t row of its states), has radius[k] and ignores
+        the reservations of ignore_group[k] (host values, [Q] or scalars; t0 default 0, radius required): they become the
+        table's queries.  A hop is admitted only if it stays clear of the reservations inside the table's horizon; the
+        chain's own edges stay admitted and ShortcutResult.chain_hit [Q] reports the first of them in conflict."""
         self._flush()
         control = int(self._p.control if control is None else control)
         so = _solve_order(control)
@@ -1249,6 +1256,13 @@ class EnvMap:
         pairs, res = PolyTrajSet(self, P, 2), PolyTrajSet(self, Q, W)
         shapes = {"status": ((Q,), np.uint8), "n_keep": ((Q,), np.int32), "keep": ((W, Q), np.int32), "cost": ((Q,), np.float64),
                   "chain_cost": ((Q,), np.float64), "edge_cost": ((Q, W - 1, hop), np.float64)}
+        if avoid is not None:
+            if radius is None:
+                raise ValueError("shortcut: avoid needs a radius")
+            avoid.set_queries(np.broadcast_to(np.asarray(0.0 if t0 is None else t0, dtype=np.float64), (Q,)), radius, ignore_group)
+            shapes["chain_hit"] = ((Q,), np.int64)
+        elif t0 is not None or radius is not None or ignore_group is not None:
+            raise ValueError("shortcut: t0 / radius / ignore_group go with avoid")
         bufs = {}
         try:
             pair_out = SolveOut(self, P, 2, so)
@@ -1260,11 +1274,16 @@ class EnvMap:
                 i.n_wp = _device_ptr(n_wp)
             for key, (shape, dt) in shapes.items():
                 bufs[key] = DeviceArray(self, int(np.prod(shape)) * np.dtype(dt).itemsize)
-                setattr(o, key, bufs[key].ptr)
+                if key != "chain_hit":
+                    setattr(o, key, bufs[key].ptr)
             o.keep_stride = Q
             po = pair_out.c_struct()
             o.pair_out = C.pointer(po)
-            _abi.check(self._ctx, _abi.lib().mplx_shortcut_device(pairs._h, res._h, C.byref(i), C.byref(o)))
+            if avoid is None:
+                _abi.check(self._ctx, _abi.lib().mplx_shortcut_device(pairs._h, res._h, C.byref(i), C.byref(o)))
+            else:
+                _abi.check(self._ctx, _abi.lib().mplx_shortcut_timed_device(pairs._h, res._h, C.byref(i), C.byref(o), avoid._res,
+                                                                          bufs["chain_hit"].ptr))
             self.synchronize()
             rows = {key: bufs[key].download(dt, shape) for key, (shape, dt) in shapes.items()}
             pairs.n, pairs.so, pairs.n_wmax, pairs.control = P, so, 2, control
@@ -1282,11 +1301,11 @@ class EnvMap:
             for b in bufs.values():
                 b.free()
 
-    def shortcut(self, states, n_wp=None, control=None, max_hop=None):
+    def shortcut(self, states, n_wp=None, control=None, max_hop=None, avoid=None, t0=None, radius=None, ignore_group=None):
         """Shortcuts Q chains of states by two-point primitives (mplx_shortcut, include/mplx_limits.h):
         states [4D+2][w_max][Q] (the seg_state of traj_info(want_states=True)), n_wp [Q] or None (w_max each), control
         VEL / ACC / JRK (default: the EnvMap's), max_hop (default: w_max - 1).  Needs a map and v_max > 0.  Returns a
-        ShortcutResult."""
+        ShortcutResult.  avoid / t0 / radius / ignore_group: the timed shortcut, as shortcut_resident takes them."""
         st = np.ascontiguousarray(np.asarray(states, dtype=np.float64))
         if st.ndim == 2:
             st = st[:, :, None]
@@ -1301,7 +1320,8 @@ class EnvMap:
                 n_wp = np.ascontiguousarray(np.broadcast_to(np.asarray(n_wp, dtype=np.int32), (Q,)))
                 d_n = DeviceArray(self, n_wp.nbytes)
                 d_n.upload(n_wp)
-            return self.shortcut_resident(d_st, Q, W, n_wp=d_n, control=control, max_hop=max_hop)
+            return self.shortcut_resident(d_st, Q, W, n_wp=d_n, control=control, max_hop=max_hop, avoid=avoid, t0=t0, radius=radius,
+                                          ignore_group=ignore_group)
         finally:
             d_st.free()
             if d_n is not None:

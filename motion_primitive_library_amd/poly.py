@@ -16,7 +16,9 @@ class ShortcutResult:
     the Q shortcut trajectories; pairs: the PolyTrajSet of the Q (w_max - 1) max_hop pair problems (pair (k, i, j) at
     (k (w_max - 1) + i) max_hop + (j - i - 1)); per query status (0, SOLVE_EMPTY, SHORTCUT_BAD_CHAIN), keep (a list of
     ascending state indices; keep_rows: the call's own [w_max][Q] rows, -1 past n_keep), cost, chain_cost; edge_cost
-    [Q][w_max - 1][max_hop] (+inf: not admitted).  free() it."""
+    [Q][w_max - 1][max_hop] (+inf: not admitted).  chain_hit: None, or after a timed shortcut (avoid=; include/
+    mplx_reserve_poly.h) per query the smallest (instant << 32 | reservation) at which one of the chain's OWN edges meets the
+    table as it is now, -2 if none does but one leaves the table's horizon, -1 if the chain still holds.  free() it."""
 
     def __init__(self, poly, pairs, max_hop, rows):
         self.poly, self.pairs, self.max_hop = poly, pairs, int(max_hop)
@@ -24,6 +26,14 @@ class ShortcutResult:
         self.keep_rows = rows["keep"]
         self.keep = [rows["keep"][:n, k].copy() for k, n in enumerate(self.n_keep)]
         self.edge_cost = rows["edge_cost"]
+        self.chain_hit = rows.get("chain_hit")
+
+    def segments(self, k):
+        """The shortcut trajectory of query k on the host, as EnvMap.load_traj takes one: (coeff [S][D + 1][6], dts [S]),
+        segment s the pair problem between the kept states keep[k][s] and keep[k][s + 1]."""
+        keep, w1 = self.keep[k], self.poly.n_wmax - 1
+        idx = [(k * w1 + int(i)) * self.max_hop + int(j - i - 1) for i, j in zip(keep[:-1], keep[1:])]
+        return self.pairs.segments()[0][:, :, idx].transpose(2, 0, 1).copy(), self.pairs.dts()[0, idx].copy()
 
     def free(self):
         self.poly.free()

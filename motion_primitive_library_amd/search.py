@@ -434,9 +434,60 @@ def _smooth(env, paths, v, control):
             info.free()
 
 
-def _shortcut(env, paths, max_hop, control):
+def _smooth_timed(env, paths, control, avoid, t0, radius, ignore_group):
+    """smooth(timed=True): one solve per path with dts = the differences of the chain states' own t row (the dts path
+    EnvMap.connect uses; repeated waypoints, as wait edges leave them, are legal there), so the polynomial passes every
+    chain state at the chain's own time.  The t row is read back, differenced on the host and uploaded.  With avoid: a
+    Reservations.check_poly of the result with the robots' t0 / radius / ignore_group; its dict is poly.reserve_hit."""
+    env._flush()
+    Q = len(paths)
+    H = max([len(p[1]) for p in paths if p is not None] + [1])
+    starts = np.zeros((env.n_fields, Q))
+    actions = np.full((H, Q), -1, np.int32)
+    n_wp = np.zeros(Q, np.int32)
+    for q, p in enumerate(paths):
+        if p is not None:
+            starts[:, q] = p[0]
+            actions[:len(p[1]), q] = p[1]
+            n_wp[q] = len(p[1]) + 1
+    bufs = [DeviceArray(env, a.nbytes) for a in (starts, actions, n_wp, np.zeros((H, Q)))]
+    info = poly = None
+    try:
+        for b, a in zip(bufs[:3], (starts, actions, n_wp)):
+            b.upload(a)
+        info = env.alloc_traj_info(Q, H, want_states=True)
+        env.traj_info_resident(bufs[0], bufs[1], info, H)
+        env.synchronize()
+        t = info.seg_state.download(np.float64, (H + 1, Q), offset=(env.n_fields - 1) * (H + 1) * Q * 8)
+        dts = np.where(np.arange(H)[:, None] + 1 < n_wp[None, :], t[1:] - t[:-1], 0.0)
+        bufs[3].upload(dts)
+        poly = env.alloc_poly(Q, H + 1)
+        out = env.alloc_solve_out(Q, H + 1, control)
+        try:
+            env.solve_traj_resident(poly, info.seg_state, Q, H + 1, n_wp=bufs[2], dts=bufs[3], control=control, out=out)
+        except Exception:
+            out.free()
+            raise
+        env.synchronize()
+        poly.chain_times, poly.reserve_hit = t, None
+        if avoid is not None:
+            poly.reserve_hit = avoid.check_poly(poly, t0, radius, ignore_group)
+        return poly
+    except Exception:
+        if poly is not None:
+            poly.free()
+        raise
+    finally:
+        for b in bufs:
+            b.free()
+        if info is not None:
+            info.free()
+
+
+def _shortcut(env, paths, max_hop, control, avoid=None, t0=None, radius=None, ignore_group=None):
     """The paths [(start, actions) or None] of Q queries -> chain states on the device (mplx_traj_info_device, want_states)
-    -> mplx_shortcut_device; only counts, costs and statuses are read back.  A query without a path is an empty problem."""
+    -> mplx_shortcut_device (with avoid: mplx_shortcut_timed_device); only counts, costs and statuses are read back.  A
+    query without a path is an empty problem."""
     env._flush()
     Q = len(paths)
     H = max([len(p[1]) for p in paths if p is not None] + [1])
@@ -455,7 +506,8 @@ def _shortcut(env, paths, max_hop, control):
             b.upload(a)
         info = env.alloc_traj_info(Q, H, want_states=True)
         env.traj_info_resident(bufs[0], bufs[1], info, H)
-        return env.shortcut_resident(info.seg_state, Q, H + 1, n_wp=bufs[2], control=control, max_hop=max_hop)
+        return env.shortcut_resident(info.seg_state, Q, H + 1, n_wp=bufs[2], control=control, max_hop=max_hop, avoid=avoid, t0=t0,
+                                     radius=radius, ignore_group=ignore_group)
     finally:
         for b in bufs:
             b.free()
@@ -523,6 +575,13 @@ def stagger(trajs, step, radius, rank=None, delay=None, max_rounds=64, park=Fals
 
 def _n_traj(trajs):
     return int(trajs.n_queries if hasattr(trajs, "n_queries") else trajs.n)
+
+
+def _unpack_hits(hit, status, n_hit):
+    """The dict Reservations.check_poly returns: instant and partner unpacked from hit, -1 where hit < 0."""
+    some = hit >= 0
+    return {"hit": hit, "instant": np.where(some, hit >> 32, -1).astype(np.int32),
+            "partner": np.where(some, hit & 0xffffffff, -1).astype(np.int32), "status": status, "n_hit": n_hit}
 
 
 class Reservations:
@@ -611,6 +670,50 @@ class Reservations:
             self._res, open_set._open, C.byref(f), int(n_max), None if hit is None else _device_ptr(hit),
             None if n_vetoed is None else _device_ptr(n_vetoed)))
 
+    def check_poly(self, poly, t_start, radius=None, ignore_group=None):
+        """mplx_reserve_check_poly (include/mplx_reserve_poly.h; synchronous): the K trajectories of the PolyTrajSet
+        `poly`, trajectory k starting at t_start[k] on the table's clock, against the reservations.  t_start [K] or a
+        scalar (finite, may be negative), radius [K] or a scalar (None: 0), ignore_group [K], a scalar or None (-1).
+        Returns {"hit" [K] int64: the smallest (instant << 32 | reservation) in conflict, -1 none, -2 the trajectory
+        leaves the table's horizon; "instant", "partner" [K] int32 unpacked from it, -1 where there is none; "status"
+        [K]: the set's status bits | CONFLICT_BAD_INPUT; "n_hit": the problems with hit != -1}."""
+        self._env._flush()
+        poly._need()
+        K = int(poly.n)
+        ts = np.ascontiguousarray(np.broadcast_to(np.asarray(t_start, dtype=np.float64), (K,)))
+        i, o = _abi.ReservePolyIn(), _abi.ReservePolyOut()
+        i.t_start = ts.ctypes.data
+        keep = [ts]
+        if radius is None or np.ndim(radius) == 0:
+            i.radius_all = 0.0 if radius is None else float(radius)
+        else:
+            keep.append(np.ascontiguousarray(np.broadcast_to(np.asarray(radius, dtype=np.float64), (K,))))
+            i.radius = keep[-1].ctypes.data
+        if ignore_group is not None:
+            keep.append(np.ascontiguousarray(np.broadcast_to(np.asarray(ignore_group, dtype=np.int32), (K,))))
+            i.ignore_group = keep[-1].ctypes.data
+        hit, status, n_hit = np.full(K, -1, np.int64), np.zeros(K, np.uint8), np.zeros(1, np.int64)
+        o.hit, o.status, o.n_hit = hit.ctypes.data, status.ctypes.data, n_hit.ctypes.data
+        self._check(_abi.lib().mplx_reserve_check_poly(self._res, poly._h, C.byref(i), C.byref(o)))
+        return _unpack_hits(hit, status, int(n_hit[0]))
+
+    def check_poly_resident(self, poly, t_start, radius=None, ignore_group=None, hit=None, status=None, n_hit=None):
+        """mplx_reserve_check_poly_device: asynchronous, on device buffers.  t_start: [K] doubles; radius: [K] doubles, a
+        host scalar or None (0); ignore_group: [K] int32 or None; hit [K] int64, status [K] bytes, n_hit 8 bytes that the
+        call adds to; each output may be None."""
+        i, o = _abi.ReservePolyIn(), _abi.ReservePolyOut()
+        i.t_start = _device_ptr(t_start)
+        if radius is None or np.ndim(radius) == 0 and not hasattr(radius, "ptr") and not hasattr(radius, "data_ptr"):
+            i.radius_all = 0.0 if radius is None else float(radius)
+        else:
+            i.radius = _device_ptr(radius)
+        if ignore_group is not None:
+            i.ignore_group = _device_ptr(ignore_group)
+        for key, v in (("hit", hit), ("status", status), ("n_hit", n_hit)):
+            if v is not None:
+                setattr(o, key, _device_ptr(v))
+        self._check(_abi.lib().mplx_reserve_check_poly_device(self._res, poly._h, C.byref(i), C.byref(o)))
+
     def positions(self):
         """The table (a download, for tests): {"pos" [n_steps][D][B], "active" [n_steps][B], "included" [B], "radius"
         [B], "group" [B], "status" [B]}."""
@@ -632,6 +735,77 @@ class Reservations:
             self.free()
         except Exception:
             pass
+
+
+def load_traj_rows(env, rows, control=None):
+    """One PolyTrajSet from host-side trajectories of different lengths (EnvMap.load_traj): rows = [(coeff [S_k][D + 1][6],
+    dts [S_k])], as ShortcutResult.segments(k) returns them; trajectory k keeps its S_k segments."""
+    S = max(len(d) for _, d in rows)
+    c = np.zeros((S, env.dim + 1, 6, len(rows)))
+    dts = np.ones((S, len(rows)))
+    for k, (ck, dk) in enumerate(rows):
+        c[:len(dk), :, :, k], dts[:len(dk), k] = ck, dk
+    return env.load_traj(c, dts, n_segs=[len(d) for _, d in rows], control=control)
+
+
+def refine_prioritised(env, plan, step, max_hop=None, control=None):
+    """Shortcuts the robots of a plan_prioritised(keep=True) plan one after the other on the plan's clock, each against
+    the CURRENT trajectories of all the others -- refined where already processed, raw otherwise -- held as one
+    PolyTrajSet (load_traj_rows) in a reservation table filled PARK with the plan's t0 / radius / n_steps; the robot
+    ignores its own group (mplx_shortcut_timed, include/mplx_reserve_poly.h).  A raw trajectory is the chain's own edges
+    re-solved (a shortcut with max_hop = 1).  Robots are taken in the plan's order.  The pair test is symmetric and the
+    instants are common, and a shortcut keeps a robot's ends and its total time, so the current set stays pairwise
+    conflict-free at the instants as long as every chain_hit is -1.
+
+    Returns {"trajs": the refined PolyTrajSet (free() it), "robots": the robot of each of its trajectories, "t0",
+    "radius" [of those], "cost_before", "cost_after" [R] (the shortcut's chain_cost and cost; nan without a path),
+    "chain_hit" [R] (-1: the chain holds), "refined" [R] bool, "conflicts": conflicts() over the refined set, PARK, rank =
+    the position in the order}.
+
+    Its limits: protection ends at the table's horizon (a hop that leaves it is not admitted; a chain that leaves it is
+    reported with chain_hit -2); a robot with a chain hit keeps its raw chain and is reported, not replanned
+    (replan_prioritised does that); the order is not revised, and a robot refined early is only ever refined against
+    the RAW trajectories of the robots after it, so it cannot use room they give up later."""
+    R = len(plan["paths"])
+    order, rad, t0, n_steps = plan["order"], np.asarray(plan["radius"], dtype=np.float64), plan["t0"], plan["n_steps"]
+    chains = {r: plan["results"][r].full_path(plan["winner"][r]) for r in order if plan["paths"][r] is not None}
+    before, after, hit = np.full(R, np.nan), np.full(R, np.nan), np.full(R, -1, np.int64)
+    refined = np.zeros(R, dtype=bool)
+    cur = {}
+    for r, chain in chains.items():
+        sc = _shortcut(env, [chain], 1, control)
+        try:
+            cur[r], before[r] = sc.segments(0), sc.cost[0]
+        finally:
+            sc.free()
+    ctl = control
+    for r, chain in chains.items():
+        others = [k for k in cur if k != r]
+        trajs = table = sc = None
+        try:
+            if others:
+                trajs = load_traj_rows(env, [cur[k] for k in others], ctl)
+                table = Reservations(env, trajs, step, n_steps, t0[others], rad[others], np.asarray(others, np.int32), True)
+            else:
+                table = Reservations(env, (np.zeros((env.n_fields, 0)), np.zeros((1, 0), np.int32)), step, n_steps, None, 0.0, None, True)
+            sc = _shortcut(env, [chain], max_hop, control, table, [t0[r]], [rad[r]], [r])
+            hit[r] = sc.chain_hit[0]
+            after[r] = before[r]
+            if hit[r] == -1 and sc.status[0] == 0:
+                cur[r], after[r], refined[r] = sc.segments(0), sc.cost[0], True
+        finally:
+            for x in (sc, table, trajs):
+                if x is not None:
+                    x.free()
+    robots = list(cur)
+    out = {"robots": robots, "t0": t0[robots], "radius": rad[robots], "cost_before": before, "cost_after": after, "chain_hit": hit,
+           "refined": refined, "trajs": None, "conflicts": None}
+    if robots:
+        rank = np.zeros(R, np.int32)
+        rank[order] = np.arange(len(order), dtype=np.int32)
+        out["trajs"] = load_traj_rows(env, [cur[k] for k in robots], ctl)
+        out["conflicts"] = out["trajs"].conflicts(step, n_steps, t0=out["t0"], radius=out["radius"], rank=rank[robots], park=True)
+    return out
 
 
 def time_key(hashes, t):
@@ -674,8 +848,9 @@ def plan_prioritised(env, starts, goal_rows, step, radius, order=None, delays=(0
     (`n_steps`) only.  An earlier robot is never re-planned when a later one cannot avoid it (replan_prioritised replans every robot,
     in the same order, after the world has changed).  A chain with waits is not
     what rollout() / MapPlanner.checkTraj accept (they stop at a wait with SKIP_SAME), and smooth() / shortcut() of a
-    path with repeated chain states are not covered; traj_info / traj_sample / traj_traverse / conflicts take it as it
-    is."""
+    path with repeated chain states only as shortcut(avoid=) and smooth(timed=True) take them (refine_prioritised; smooth(v=)
+    re-allocates time and fails at a repeated state with SOLVE_BAD_TIME); traj_info / traj_sample / traj_traverse /
+    conflicts take it as it is."""
     starts = np.ascontiguousarray(starts, dtype=np.float64)
     goal_rows = np.ascontiguousarray(goal_rows, dtype=np.float64)
     R = starts.shape[1]
@@ -854,19 +1029,51 @@ class _Result:
             return start, act
         return done[0].copy(), np.concatenate([done[1], act]).astype(np.int32)
 
-    def smooth(self, v=1.0, control=None):
+    def smooth(self, v=1.0, control=None, timed=False, avoid=None):
         """The path(s) smoothed into polynomials through their chain states (include/mplx_solve.h): v a scalar or [n_v]
         speeds of the time allocation -> a PolyTrajSet of Q x n_v problems in one solve, problem vi * Q + q = the path of
         query q at speed v[vi] (Q = 1 for a SearchResult); control: of the ends (default: the EnvMap's).  Of a
-        MultiSearchResult a query without a path is SOLVE_EMPTY."""
-        return _smooth(self._env, self._paths(), v, control)
+        MultiSearchResult a query without a path is SOLVE_EMPTY.
 
-    def shortcut(self, max_hop=None, control=None):
+        timed=True: the chain's own times instead of a time allocation (v must be left at its default): Q problems, the
+        chain full_path(q), segment s lasts t_{s+1} - t_s of the chain states, so the robot stays on the clock it was
+        planned on and the repeated states of wait edges are legal.  The set's chain_times [w_max][Q] are those t.  avoid
+        (with timed): a Reservations; the result is checked against it with the t0 / radius / ignore_group the search
+        ran with (Reservations.check_poly) and the dict is the set's reserve_hit -- a smoothed trajectory is NOT kept
+        clear of the reservations, only reported."""
+        if not timed:
+            if avoid is not None:
+                raise ValueError("smooth: avoid goes with timed=True")
+            return _smooth(self._env, self._paths(), v, control)
+        if np.ndim(v) != 0 or float(v) != 1.0:
+            raise ValueError("smooth: timed=True keeps the chain's own times: leave v at its default")
+        prm = self._params or {}
+        if avoid is not None and not prm.get("avoid"):
+            raise ValueError("smooth: the search ran without avoid (no t0 / radius to check with)")
+        return _smooth_timed(self._env, self._full_paths(), control, avoid, prm.get("t0"), prm.get("radius"), prm.get("ignore_group"))
+
+    def _full_paths(self):
+        return [self._full_path(q) if self.found[q] else None for q in range(self.n_queries)]
+
+    def shortcut(self, max_hop=None, control=None, avoid=None):
         """The path(s) with runs of their short constant-control pieces replaced by two-point primitives between
         non-adjacent chain states, where those stay within v_max / a_max / j_max and off the obstacles and cost less
         (mplx_shortcut, include/mplx_limits.h): a ShortcutResult of Q queries in one batch of launches.  max_hop: the
-        longest hop in chain states (default: any).  Of a MultiSearchResult a query without a path is SOLVE_EMPTY."""
-        return _shortcut(self._env, self._paths(), max_hop, control)
+        longest hop in chain states (default: any).  Of a MultiSearchResult a query without a path is SOLVE_EMPTY.
+
+        avoid: a Reservations as they are now: the timed shortcut (mplx_shortcut_timed, include/mplx_reserve_poly.h) with
+        the t0 / radius / ignore_group the search ran with, on the chain full_path(q), whose clock is the original
+        start's: a hop is admitted only if it stays clear of the reservations inside the table's horizon, and
+        ShortcutResult.chain_hit reports a chain that no longer holds (replan_timed then).  A search that ran with avoid
+        must be shortcut with it: an untimed hop across its waits would drift into what the search waited for."""
+        prm = self._params or {}
+        if prm.get("avoid") and avoid is None:
+            raise ValueError("shortcut: the search ran with avoid: give the Reservations as they are now")
+        if avoid is None:
+            return _shortcut(self._env, self._paths(), max_hop, control)
+        if not prm.get("avoid"):
+            raise ValueError("shortcut: the search ran without avoid (no t0 / radius to check with)")
+        return _shortcut(self._env, self._full_paths(), max_hop, control, avoid, prm["t0"], prm["radius"], prm["ignore_group"])
 
     def _roots(self, who, roots, advance):
         """The node id every query is re-rooted at: roots [Q] (-1 or None: that query's seed), or ids[advance] of the
