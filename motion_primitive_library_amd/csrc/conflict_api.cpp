@@ -62,55 +62,24 @@ int run(mplx_ctx *c, DevBuf &ws, const mplx::TrajArgs &t, const mplx_conflict_in
   return MPLX_OK;
 }
 
-// the [K] rows of a host call in the arena
-struct Rows { size_t t0, radius, group, rank, first, partner, d2, status, pairs; };
-Rows rows_of(size_t K, const mplx_conflict_in *in, const mplx_conflict_out *o, StageLayout *l) {
+// the [K] rows of a host call in the arena; after the commit, the device forms of `h_in` and `h_out`
+struct Rows { StageRows::Row t0, radius, group, rank, first, partner, d2, status, pairs; };
+Rows rows_of(size_t K, const mplx_conflict_in *in, const mplx_conflict_out *o, StageRows *s) {
   Rows r;
-  r.t0 = l->add(in->t0 ? K * 8 : 0); r.radius = l->add(in->radius ? K * 8 : 0);
-  r.group = l->add(in->group ? K * 4 : 0); r.rank = l->add(in->rank ? K * 4 : 0);
-  r.first = l->add(o->first_step ? K * 4 : 0); r.partner = l->add(o->first_partner ? K * 4 : 0);
-  r.d2 = l->add(o->min_d2 ? K * 8 : 0); r.status = l->add(o->status ? K : 0);
-  r.pairs = l->add(o->pair_first ? K * K * 4 : 0);
+  r.t0 = s->in(in->t0, K * 8); r.radius = s->in(in->radius, K * 8);
+  r.group = s->in(in->group, K * 4); r.rank = s->in(in->rank, K * 4);
+  r.first = s->out(o->first_step, K * 4); r.partner = s->out(o->first_partner, K * 4);
+  r.d2 = s->out(o->min_d2, K * 8); r.status = s->out(o->status, K);
+  r.pairs = s->out_rows(o->pair_first, (size_t)o->pair_stride * 4, K * 4, K);
   return r;
 }
-
-int stage_rows(mplx_ctx *c, size_t K, const StageLayout &l, const Rows &r, const mplx_conflict_in *h_in, const mplx_conflict_out *h_out,
-               mplx_conflict_in *in, mplx_conflict_out *o) {
+void staged(const StageRows &s, const Rows &r, size_t K, const mplx_conflict_in *h_in, mplx_conflict_in *in, mplx_conflict_out *o) {
   *in = *h_in;
-  if (h_in->t0) {
-    HIP_TRY(c, stage_in(c, l.base + r.t0, h_in->t0, K * 8));
-    in->t0 = (const double *)(l.base + r.t0);
-  }
-  if (h_in->radius) {
-    HIP_TRY(c, stage_in(c, l.base + r.radius, h_in->radius, K * 8));
-    in->radius = (const double *)(l.base + r.radius);
-  }
-  if (h_in->group) {
-    HIP_TRY(c, stage_in(c, l.base + r.group, h_in->group, K * 4));
-    in->group = (const int32_t *)(l.base + r.group);
-  }
-  if (h_in->rank) {
-    HIP_TRY(c, stage_in(c, l.base + r.rank, h_in->rank, K * 4));
-    in->rank = (const int32_t *)(l.base + r.rank);
-  }
+  in->t0 = s.dev<double>(r.t0); in->radius = s.dev<double>(r.radius); in->group = s.dev<int32_t>(r.group); in->rank = s.dev<int32_t>(r.rank);
   *o = mplx_conflict_out{};
-  o->first_step = h_out->first_step ? (int32_t *)(l.base + r.first) : nullptr;
-  o->first_partner = h_out->first_partner ? (int32_t *)(l.base + r.partner) : nullptr;
-  o->min_d2 = h_out->min_d2 ? (double *)(l.base + r.d2) : nullptr;
-  o->status = h_out->status ? (uint8_t *)(l.base + r.status) : nullptr;
-  o->pair_first = h_out->pair_first ? (int32_t *)(l.base + r.pairs) : nullptr;
+  o->first_step = s.dev<int32_t>(r.first); o->first_partner = s.dev<int32_t>(r.partner); o->min_d2 = s.dev<double>(r.d2);
+  o->status = s.dev<uint8_t>(r.status); o->pair_first = s.dev<int32_t>(r.pairs);
   o->pair_stride = (int64_t)K;
-  return MPLX_OK;
-}
-
-int read_rows(mplx_ctx *c, size_t K, const mplx_conflict_out *d, const mplx_conflict_out *h) {
-  HIP_TRY(c, stage_out(c, h->first_step, d->first_step, K * 4));
-  HIP_TRY(c, stage_out(c, h->first_partner, d->first_partner, K * 4));
-  HIP_TRY(c, stage_out(c, h->min_d2, d->min_d2, K * 8));
-  HIP_TRY(c, stage_out(c, h->status, d->status, K));
-  HIP_TRY(c, stage_out_rows(c, h->pair_first, (size_t)h->pair_stride * 4, d->pair_first, K * 4, K));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  return MPLX_OK;
 }
 
 int check_poly(mplx_poly *p, const char *who, const mplx_conflict_in *in, const mplx_conflict_out *out) {
@@ -145,14 +114,14 @@ int mplx_poly_conflicts(mplx_poly *p, const mplx_conflict_in *h_in, const mplx_c
   if (int rc = bind_device(c)) return rc;
   if (int rc = resolve_pending(c)) return rc;  // the arena is shared with the other host-pointer calls
   const size_t K = (size_t)p->n;
-  StageLayout l;
-  const Rows r = rows_of(K, h_in, h_out, &l);
-  if (int rc = stage_commit(c, &l)) return rc;
+  StageRows s;
+  const Rows r = rows_of(K, h_in, h_out, &s);
+  if (int rc = stage_commit(c, &s)) return rc;
   mplx_conflict_in in;
   mplx_conflict_out o;
-  if (int rc = stage_rows(c, K, l, r, h_in, h_out, &in, &o)) return rc;
+  staged(s, r, K, h_in, &in, &o);
   if (int rc = run(c, p->conf, poly_table_args(p), &in, &o)) return rc;
-  return read_rows(c, K, &o, h_out);
+  return stage_fetch(c, &s);
 }
 
 int mplx_traj_conflicts_device(mplx_ctx *c, const mplx_traj_set *d_set, const mplx_conflict_in *d_in, const mplx_conflict_out *d_out) {
@@ -172,20 +141,18 @@ int mplx_traj_conflicts(mplx_ctx *c, const mplx_traj_set *h_set, const mplx_conf
   if (int rc = bind_device(c)) return rc;
   if (int rc = resolve_pending(c)) return rc;
   const size_t K = (size_t)h_set->n_traj;
-  StageLayout l;
-  size_t o_starts, o_actions;
-  traj_set_rows(c, h_set, &l, &o_starts, &o_actions);
-  const Rows r = rows_of(K, h_in, h_out, &l);
-  if (int rc = stage_commit(c, &l)) return rc;
-  mplx_traj_set d;
-  if (int rc = traj_stage_set(c, h_set, l, o_starts, o_actions, &d)) return rc;
+  StageRows s;
+  const TrajSetRows set = traj_set_rows(c, h_set, &s);
+  const Rows r = rows_of(K, h_in, h_out, &s);
+  if (int rc = stage_commit(c, &s)) return rc;
+  const mplx_traj_set d = traj_set_view(h_set, s, set);
   mplx_conflict_in in;
   mplx_conflict_out o;
-  if (int rc = stage_rows(c, K, l, r, h_in, h_out, &in, &o)) return rc;
+  staged(s, r, K, h_in, &in, &o);
   mplx::TrajArgs t;
   if (int rc = traj_build_table(c, &d, &t)) return rc;
   if (int rc = run(c, c->conflict_ws, t, &in, &o)) return rc;
-  return read_rows(c, K, &o, h_out);
+  return stage_fetch(c, &s);
 }
 
 }  // extern "C"

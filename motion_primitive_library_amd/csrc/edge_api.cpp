@@ -18,13 +18,11 @@ extern "C" int mplx_check_edges(mplx_ctx *c, const double *h_parents, const int3
   if (int rc = bind_device(c)) return rc;
   const int F = 4 * c->dim + 2;
   const size_t n = (size_t)n_edges, cell_bytes = h_out->cells ? n * (size_t)h_out->cell_cap * 4 : 0;
-  StageLayout l;
-  const size_t o_parents = l.add((size_t)F * n * 8), o_action = l.add(n * 4), o_free = l.add(h_out->free_flag ? n : 0),
-               o_outside = l.add(h_out->outside ? n : 0), o_cost = l.add(h_out->cost ? n * 8 : 0),
-               o_count = l.add(h_out->cell_count ? n * 4 : 0), o_cells = l.add(cell_bytes);
-  if (int rc = stage_commit(c, &l)) return rc;
-  HIP_TRY(c, stage_in_rows(c, l.base + o_parents, h_parents, (size_t)stride * 8, n * 8, F));
-  HIP_TRY(c, stage_in(c, l.base + o_action, h_actions, n * 4));
+  StageRows s;
+  const auto i_parents = s.in_rows(h_parents, (size_t)stride * 8, n * 8, F), i_action = s.in(h_actions, n * 4),
+             o_free = s.out(h_out->free_flag, n), o_outside = s.out(h_out->outside, n), o_cost = s.out(h_out->cost, n * 8),
+             o_count = s.out(h_out->cell_count, n * 4), o_cells = s.out(h_out->cells, cell_bytes);
+  if (int rc = stage_commit(c, &s)) return rc;
   mplx::EdgeArgs a{};
   a.map = (const int8_t *)c->map.p;
   a.region = c->has_region ? (const uint32_t *)c->region_bits.p : nullptr;
@@ -34,20 +32,12 @@ extern "C" int mplx_check_edges(mplx_ctx *c, const double *h_parents, const int3
   a.dt = c->prm.dt; a.w = c->prm.w;
   a.U = (const double *)c->U.p;
   a.nU = c->nU; a.udim = c->udim;
-  a.parents = (const double *)(l.base + o_parents);
-  a.action = (const int32_t *)(l.base + o_action);
+  a.parents = s.dev<double>(i_parents);
+  a.action = s.dev<int32_t>(i_action);
   a.n_edges = n_edges; a.stride = n_edges;
-  if (h_out->free_flag) a.free_out = (uint8_t *)(l.base + o_free);
-  if (h_out->outside) a.outside_out = (uint8_t *)(l.base + o_outside);
-  if (h_out->cost) a.cost = (double *)(l.base + o_cost);
-  if (h_out->cell_count) a.cell_count = (int32_t *)(l.base + o_count);
-  if (h_out->cells) { a.cells = (int32_t *)(l.base + o_cells); a.cell_cap = h_out->cell_cap; }
+  a.free_out = s.dev<uint8_t>(o_free); a.outside_out = s.dev<uint8_t>(o_outside); a.cost = s.dev<double>(o_cost);
+  a.cell_count = s.dev<int32_t>(o_count);
+  if (h_out->cells) { a.cells = s.dev<int32_t>(o_cells); a.cell_cap = h_out->cell_cap; }
   HIP_TRY(c, mplx::launch_check_edges(c->dim, c->prm.control, a, c->stream));
-  HIP_TRY(c, stage_out(c, h_out->outside, a.outside_out, n));
-  HIP_TRY(c, stage_out(c, h_out->free_flag, a.free_out, n));
-  HIP_TRY(c, stage_out(c, h_out->cost, a.cost, n * 8));
-  HIP_TRY(c, stage_out(c, h_out->cell_count, a.cell_count, n * 4));
-  HIP_TRY(c, stage_out(c, h_out->cells, a.cells, cell_bytes));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  return MPLX_OK;
+  return stage_fetch(c, &s);
 }

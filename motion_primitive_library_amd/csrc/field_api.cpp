@@ -79,10 +79,9 @@ int mplx_field_build(mplx_field *fld, int32_t F, const int32_t *h_lo, const int3
   if (int rc = ensure(c, fld->dist, cells * 4)) return rc;
   if (int rc = ensure(c, fld->active, 2 * half)) return rc;
   if (int rc = ensure(c, fld->counter, 8)) return rc;
-  StageLayout l;
-  const size_t o_box = l.add(box.size() * 4);
-  if (int rc = stage_commit(c, &l)) return rc;
-  HIP_TRY(c, stage_in(c, l.base + o_box, box.data(), box.size() * 4));
+  StageRows s;  // (no output row: every pass below ends in its own read-back and synchronise)
+  const auto i_box = s.in(box.data(), box.size() * 4);
+  if (int rc = stage_commit(c, &s)) return rc;
   HIP_TRY(c, hipMemsetAsync(fld->active.p, 0, 2 * half, c->stream));
   HIP_TRY(c, hipMemsetAsync(fld->counter.p, 0, 8, c->stream));
   a.dist = (int32_t *)fld->dist.p;
@@ -90,7 +89,7 @@ int mplx_field_build(mplx_field *fld, int32_t F, const int32_t *h_lo, const int3
   if (c->has_pot)
     HIP_TRY(c, mplx::launch_field_pot_bits((const int8_t *)c->pot.p, c->has_region ? (const uint32_t *)c->region_bits.p : nullptr, c->n_cells,
                                            (uint32_t *)fld->bits.p, c->stream));
-  a.box = (const int32_t *)(l.base + o_box);
+  a.box = s.dev<int32_t>(i_box);
   a.counter = (unsigned long long *)fld->counter.p;
   uint8_t *act[2] = {(uint8_t *)fld->active.p, (uint8_t *)fld->active.p + half};
   a.active_cur = act[0];

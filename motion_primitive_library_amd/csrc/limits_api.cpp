@@ -6,8 +6,6 @@
 #include "../../include/mplx_limits.h"
 #include "../../include/mplx_reserve_poly.h"
 
-#include <vector>
-
 using namespace mplx_detail;
 
 namespace {
@@ -104,39 +102,31 @@ int mplx_poly_load(mplx_poly *p, const mplx_poly_load_in *h_in, const mplx_poly_
   mplx_ctx *c = p->c;
   if (int rc = check_load(p, "mplx_poly_load", h_in, h_out)) return rc;
   if (h_in->n_prob == 0) return MPLX_OK;
-  MPLX_GUARD_BEGIN
   if (int rc = bind_device(c)) return rc;
   if (int rc = resolve_pending(c)) return rc;  // the arena is shared with the other host-pointer calls
   const size_t n = (size_t)h_in->n_prob, W = (size_t)h_in->w_max, D = (size_t)c->dim, cr = (W - 1) * (D + 1) * 6;
-  StageLayout l;
-  const bool gather = h_in->src_index != nullptr;
-  const size_t i_S = l.add(h_in->n_segs && !gather ? n * 4 : 0), i_dts = l.add(gather ? 0 : (W - 1) * n * 8), i_c = l.add(gather ? 0 : cr * n * 8);
-  const size_t o_st = l.add(n), o_T = l.add(n * 8), o_t = l.add(h_out->taus ? W * n * 8 : 0);
-  if (int rc = stage_commit(c, &l)) return rc;
+  const bool gather = h_in->src_index != nullptr;  // (the gather form stages no input: src_index is device memory)
+  StageRows s;
+  const auto i_S = s.in(gather ? nullptr : h_in->n_segs, n * 4), i_dts = s.in_rows(gather ? nullptr : h_in->dts, (size_t)h_in->dt_stride * 8, n * 8, W - 1),
+             i_c = s.in_rows(gather ? nullptr : h_in->coeff, (size_t)h_in->coeff_stride * 8, n * 8, cr);
+  const auto o_st = s.landed(n), o_T = s.landed(n * 8), o_t = s.landed(h_out->taus, W * n * 8),
+             t_S = s.landed_from((char *)p->mem.p + p->o_S, n * 4);  // (S_k is read from the poly's table: 0 for a failed problem)
+  if (int rc = stage_commit(c, &s)) return rc;
   mplx_poly_load_in in = *h_in;
-  if (h_in->n_segs && !gather) {
-    HIP_TRY(c, stage_in(c, l.base + i_S, h_in->n_segs, n * 4));
-    in.n_segs = (const int32_t *)(l.base + i_S);
-  }
   if (!gather) {
-    HIP_TRY(c, stage_in_rows(c, l.base + i_dts, h_in->dts, (size_t)h_in->dt_stride * 8, n * 8, W - 1));
-    in.dts = (const double *)(l.base + i_dts); in.dt_stride = (int64_t)n;
-    HIP_TRY(c, stage_in_rows(c, l.base + i_c, h_in->coeff, (size_t)h_in->coeff_stride * 8, n * 8, cr));
-    in.coeff = (const double *)(l.base + i_c); in.coeff_stride = (int64_t)n;
+    in.n_segs = s.dev<int32_t>(i_S);
+    in.dts = s.dev<double>(i_dts); in.dt_stride = (int64_t)n;
+    in.coeff = s.dev<double>(i_c); in.coeff_stride = (int64_t)n;
   }
   mplx_poly_load_out o{};
-  o.status = (uint8_t *)(l.base + o_st);
-  o.total_time = (double *)(l.base + o_T);  // (S_k is read from the poly's table below)
-  if (h_out->taus) { o.taus = (double *)(l.base + o_t); o.taus_stride = (int64_t)n; }
+  o.status = s.dev<uint8_t>(o_st);
+  o.total_time = s.dev<double>(o_T);
+  o.taus = s.dev<double>(o_t); o.taus_stride = (int64_t)n;
   if (int rc = load_launch(p, &in, &o)) return rc;
-  std::vector<uint8_t> st(n);
-  std::vector<int32_t> S(n);
-  std::vector<double> T(n), ta(h_out->taus ? W * n : 0);
-  HIP_TRY(c, stage_out(c, st.data(), o.status, n));
-  HIP_TRY(c, stage_out(c, S.data(), (char *)p->mem.p + p->o_S, n * 4));  // (0 for a failed problem)
-  HIP_TRY(c, stage_out(c, T.data(), o.total_time, n * 8));
-  HIP_TRY(c, stage_out(c, ta.empty() ? nullptr : ta.data(), o.taus, ta.size() * 8));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  if (int rc = stage_fetch(c, &s)) return rc;
+  const uint8_t *st = s.host<uint8_t>(o_st);
+  const int32_t *S = s.host<int32_t>(t_S);
+  const double *T = s.host<double>(o_T), *ta = s.host<double>(o_t);
   for (size_t k = 0; k < n; k++) {
     if (h_out->status) h_out->status[k] = st[k];
     const size_t Sk = (size_t)S[k];
@@ -146,7 +136,6 @@ int mplx_poly_load(mplx_poly *p, const mplx_poly_load_in *h_in, const mplx_poly_
     for (size_t r = 0; r <= Sk && h_out->taus; r++) h_out->taus[(int64_t)r * h_out->taus_stride + (int64_t)k] = ta[r * n + k];
   }
   return MPLX_OK;
-  MPLX_GUARD_END(c)
 }
 
 int mplx_poly_limits_device(mplx_poly *p, const mplx_limits_in *in, const mplx_limits_out *d_out) {
@@ -160,38 +149,24 @@ int mplx_poly_limits(mplx_poly *p, const mplx_limits_in *in, const mplx_limits_o
   if (!p) return MPLX_ERR_ARG;
   mplx_ctx *c = p->c;
   if (int rc = check_limits(p, "mplx_poly_limits", in, h_out)) return rc;
-  MPLX_GUARD_BEGIN
   if (int rc = bind_device(c)) return rc;
   if (int rc = resolve_pending(c)) return rc;
   const size_t n = (size_t)p->n, D = (size_t)c->dim;
   double *const h_max[3] = {h_out->max_vel, h_out->max_acc, h_out->max_jrk};
-  StageLayout l;
-  size_t o_m[3];
-  for (int q = 0; q < 3; q++) o_m[q] = l.add(h_max[q] ? D * n * 8 : 0);
-  const size_t o_e = l.add(h_out->exceed ? n : 0), o_v = l.add(h_out->valid ? n : 0), o_f = l.add(h_out->first_bad ? n * 4 : 0);
-  if (int rc = stage_commit(c, &l)) return rc;
+  StageRows s;
+  const StageRows::Row o_m[3] = {s.landed(h_max[0], D * n * 8), s.landed(h_max[1], D * n * 8), s.landed(h_max[2], D * n * 8)};
+  const auto o_e = s.landed(h_out->exceed, n), o_v = s.landed(h_out->valid, n), o_f = s.landed(h_out->first_bad, n * 4),
+             t_S = s.landed_from((char *)p->mem.p + p->o_S, n * 4);
+  if (int rc = stage_commit(c, &s)) return rc;
   mplx_limits_out o{};
-  o.max_vel = h_max[0] ? (double *)(l.base + o_m[0]) : nullptr;
-  o.max_acc = h_max[1] ? (double *)(l.base + o_m[1]) : nullptr;
-  o.max_jrk = h_max[2] ? (double *)(l.base + o_m[2]) : nullptr;
+  o.max_vel = s.dev<double>(o_m[0]); o.max_acc = s.dev<double>(o_m[1]); o.max_jrk = s.dev<double>(o_m[2]);
   o.max_stride = (int64_t)n;
-  o.exceed = h_out->exceed ? (uint8_t *)(l.base + o_e) : nullptr;
-  o.valid = h_out->valid ? (uint8_t *)(l.base + o_v) : nullptr;
-  o.first_bad = h_out->first_bad ? (int32_t *)(l.base + o_f) : nullptr;
+  o.exceed = s.dev<uint8_t>(o_e); o.valid = s.dev<uint8_t>(o_v); o.first_bad = s.dev<int32_t>(o_f);
   if (int rc = limits_launch(p, in, &o)) return rc;
-  std::vector<int32_t> S(n), fb(h_out->first_bad ? n : 0);
-  std::vector<uint8_t> ex(h_out->exceed ? n : 0), va(h_out->valid ? n : 0);
-  std::vector<double> mx[3];
-  double *const d_max[3] = {o.max_vel, o.max_acc, o.max_jrk};
-  HIP_TRY(c, stage_out(c, S.data(), (char *)p->mem.p + p->o_S, n * 4));
-  for (int q = 0; q < 3; q++) {
-    mx[q].resize(h_max[q] ? D * n : 0);
-    HIP_TRY(c, stage_out(c, mx[q].empty() ? nullptr : mx[q].data(), d_max[q], mx[q].size() * 8));
-  }
-  HIP_TRY(c, stage_out(c, ex.empty() ? nullptr : ex.data(), o.exceed, ex.size()));
-  HIP_TRY(c, stage_out(c, va.empty() ? nullptr : va.data(), o.valid, va.size()));
-  HIP_TRY(c, stage_out(c, fb.empty() ? nullptr : fb.data(), o.first_bad, fb.size() * 4));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  if (int rc = stage_fetch(c, &s)) return rc;
+  const int32_t *S = s.host<int32_t>(t_S), *fb = s.host<int32_t>(o_f);
+  const uint8_t *ex = s.host<uint8_t>(o_e), *va = s.host<uint8_t>(o_v);
+  const double *const mx[3] = {s.host<double>(o_m[0]), s.host<double>(o_m[1]), s.host<double>(o_m[2])};
   for (size_t k = 0; k < n; k++) {
     if (S[k] == 0) continue;  // a failed problem keeps the caller's bytes
     for (int q = 0; q < 3; q++)
@@ -201,7 +176,6 @@ int mplx_poly_limits(mplx_poly *p, const mplx_limits_in *in, const mplx_limits_o
     if (h_out->first_bad) h_out->first_bad[k] = fb[k];
   }
   return MPLX_OK;
-  MPLX_GUARD_END(c)
 }
 
 }  // extern "C"
@@ -309,43 +283,31 @@ int shortcut_launch(mplx_poly *pairs, mplx_poly *res, const mplx_shortcut_in *in
   return mplx_poly_load_device(res, &gi, &go);
 }
 
-// the host rows of mplx_shortcut / mplx_shortcut_timed: carved, then (base known) copied in, the launches, copied out
-struct HostRows { size_t i_st, i_n, o_s, o_nk, o_k, o_c, o_cc, o_e, o_ch; };
-HostRows host_rows(mplx_ctx *c, const mplx_shortcut_in *h_in, int64_t NP, bool chain_hit, StageLayout *l) {
-  const size_t Q = (size_t)h_in->n_query, W = (size_t)h_in->w_max, F = 4 * (size_t)c->dim + 2, P = (size_t)NP;
-  HostRows r;
-  r.i_st = l->add(F * W * Q * 8); r.i_n = l->add(h_in->n_wp ? Q * 4 : 0);
-  r.o_s = l->add(Q); r.o_nk = l->add(Q * 4); r.o_k = l->add(W * Q * 4); r.o_c = l->add(Q * 8); r.o_cc = l->add(Q * 8); r.o_e = l->add(P * 8);
-  r.o_ch = l->add(chain_hit ? Q * 8 : 0);
-  return r;
-}
-
-int shortcut_staged(mplx_poly *pairs, mplx_poly *res, const mplx_shortcut_in *h_in, const mplx_shortcut_out *h_out, int64_t NP,
-                    const StageLayout &l, const HostRows &r, const mplx::ReserveArgs *table, int64_t *h_chain_hit) {
+// mplx_shortcut / mplx_shortcut_timed on host rows: they differ in the table and the chain_hit row it adds, and in
+// nothing else.  The calls inside stage nothing: they are device forms (rule 4 of the arena).
+int shortcut_host(mplx_poly *pairs, mplx_poly *res, const mplx_shortcut_in *h_in, const mplx_shortcut_out *h_out, int64_t NP,
+                  const mplx::ReserveArgs *table, int64_t *h_chain_hit) {
   mplx_ctx *c = pairs->c;
+  if (int rc = bind_device(c)) return rc;
+  if (int rc = resolve_pending(c)) return rc;
   const size_t Q = (size_t)h_in->n_query, W = (size_t)h_in->w_max, F = 4 * (size_t)c->dim + 2, P = (size_t)NP;
+  StageRows s;
+  const auto i_st = s.in_rows(h_in->states, (size_t)h_in->stride * 8, Q * 8, F * W), i_n = s.in(h_in->n_wp, Q * 4);
+  const auto o_s = s.out_or_scratch(h_out->status, Q), o_nk = s.out_or_scratch(h_out->n_keep, Q * 4),
+             o_k = s.landed_or_scratch(h_out->keep, W * Q * 4), o_c = s.out_or_scratch(h_out->cost, Q * 8),
+             o_cc = s.out_or_scratch(h_out->chain_cost, Q * 8), o_e = s.out_or_scratch(h_out->edge_cost, P * 8),
+             o_ch = s.out(table ? h_chain_hit : nullptr, Q * 8);
+  if (int rc = stage_commit(c, &s)) return rc;
   mplx_shortcut_in in = *h_in;
-  HIP_TRY(c, stage_in_rows(c, l.base + r.i_st, h_in->states, (size_t)h_in->stride * 8, Q * 8, F * W));
-  in.states = (const double *)(l.base + r.i_st); in.stride = (int64_t)Q;
-  if (h_in->n_wp) {
-    HIP_TRY(c, stage_in(c, l.base + r.i_n, h_in->n_wp, Q * 4));
-    in.n_wp = (const int32_t *)(l.base + r.i_n);
-  }
+  in.states = s.dev<double>(i_st); in.stride = (int64_t)Q;
+  in.n_wp = s.dev<int32_t>(i_n);
   mplx_shortcut_out o{};
-  o.status = (uint8_t *)(l.base + r.o_s); o.n_keep = (int32_t *)(l.base + r.o_nk); o.keep = (int32_t *)(l.base + r.o_k); o.keep_stride = (int64_t)Q;
-  o.cost = (double *)(l.base + r.o_c); o.chain_cost = (double *)(l.base + r.o_cc); o.edge_cost = (double *)(l.base + r.o_e);
-  int64_t *d_ch = table && h_chain_hit ? (int64_t *)(l.base + r.o_ch) : nullptr;
-  if (int rc = shortcut_launch(pairs, res, &in, &o, NP, table, d_ch)) return rc;
-  std::vector<int32_t> keep(h_out->keep ? W * Q : 0);
-  HIP_TRY(c, stage_out(c, h_out->status, o.status, Q));
-  HIP_TRY(c, stage_out(c, h_out->n_keep, o.n_keep, Q * 4));
-  HIP_TRY(c, stage_out(c, keep.empty() ? nullptr : keep.data(), o.keep, keep.size() * 4));
-  HIP_TRY(c, stage_out(c, h_out->cost, o.cost, Q * 8));
-  HIP_TRY(c, stage_out(c, h_out->chain_cost, o.chain_cost, Q * 8));
-  HIP_TRY(c, stage_out(c, h_out->edge_cost, o.edge_cost, P * 8));
-  HIP_TRY(c, stage_out(c, d_ch ? h_chain_hit : nullptr, d_ch, Q * 8));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  for (size_t w = 0; w < W && h_out->keep; w++)
+  o.status = s.dev<uint8_t>(o_s); o.n_keep = s.dev<int32_t>(o_nk); o.keep = s.dev<int32_t>(o_k); o.keep_stride = (int64_t)Q;
+  o.cost = s.dev<double>(o_c); o.chain_cost = s.dev<double>(o_cc); o.edge_cost = s.dev<double>(o_e);
+  if (int rc = shortcut_launch(pairs, res, &in, &o, NP, table, s.dev<int64_t>(o_ch))) return rc;
+  if (int rc = stage_fetch(c, &s)) return rc;
+  const int32_t *keep = s.host<int32_t>(o_k);
+  for (size_t w = 0; w < W && keep; w++)
     for (size_t k = 0; k < Q; k++) h_out->keep[(int64_t)w * h_out->keep_stride + (int64_t)k] = keep[w * Q + k];
   return MPLX_OK;
 }
@@ -370,15 +332,7 @@ int mplx_shortcut(mplx_poly *pairs, mplx_poly *res, const mplx_shortcut_in *h_in
   if (int rc = check_shortcut(pairs, res, "mplx_shortcut", h_in, h_out, &NP)) return rc;
   if (h_out->pair_out) return fail(c, MPLX_ERR_ARG, "mplx_shortcut: pair_out is for the _device form");
   if (NP == 0) return MPLX_OK;
-  MPLX_GUARD_BEGIN
-  if (int rc = bind_device(c)) return rc;
-  if (int rc = resolve_pending(c)) return rc;
-  StageLayout l;
-  const HostRows r = host_rows(c, h_in, NP, false, &l);
-  if (int rc = stage_commit(c, &l)) return rc;
-  // (the calls inside stage nothing: they are device forms, rule 4 of the arena)
-  return shortcut_staged(pairs, res, h_in, h_out, NP, l, r, nullptr, nullptr);
-  MPLX_GUARD_END(c)
+  return shortcut_host(pairs, res, h_in, h_out, NP, nullptr, nullptr);
 }
 
 int mplx_shortcut_timed_device(mplx_poly *pairs, mplx_poly *res, const mplx_shortcut_in *d_in, const mplx_shortcut_out *d_out,
@@ -394,7 +348,6 @@ int mplx_shortcut_timed_device(mplx_poly *pairs, mplx_poly *res, const mplx_shor
   return shortcut_launch(pairs, res, d_in, d_out, NP, &t, d_chain_hit);
 }
 
-// The host rows lie in the reservation table's own row buffer, not in the context's arena: see mplx_reserve_check_poly.
 int mplx_shortcut_timed(mplx_poly *pairs, mplx_poly *res, const mplx_shortcut_in *h_in, const mplx_shortcut_out *h_out,
                         mplx_reserve *table, int64_t *h_chain_hit) {
   if (!pairs) return MPLX_ERR_ARG;
@@ -406,14 +359,7 @@ int mplx_shortcut_timed(mplx_poly *pairs, mplx_poly *res, const mplx_shortcut_in
   mplx::ReserveArgs t{};
   if (int rc = check_table(pairs, who, h_in, table, &t)) return rc;
   if (NP == 0) return MPLX_OK;
-  MPLX_GUARD_BEGIN
-  if (int rc = bind_device(c)) return rc;
-  if (int rc = resolve_pending(c)) return rc;
-  StageLayout l;
-  const HostRows r = host_rows(c, h_in, NP, h_chain_hit != nullptr, &l);
-  if (int rc = reserve_host_rows(table, l.total, &l.base)) return rc;
-  return shortcut_staged(pairs, res, h_in, h_out, NP, l, r, &t, h_chain_hit);
-  MPLX_GUARD_END(c)
+  return shortcut_host(pairs, res, h_in, h_out, NP, &t, h_chain_hit);
 }
 
 }  // extern "C"

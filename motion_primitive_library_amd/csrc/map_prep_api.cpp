@@ -57,18 +57,16 @@ int mplx_edit_map(mplx_ctx *c, const int64_t *cell_index, const int8_t *values, 
   if (int rc = bind_device(c)) return rc;
   if (int rc = resolve_pending(c)) return rc;  // a pending launch read the old cells
   if (int rc = svc_stop(c)) return rc;         // a resident kernel may hold the old cells in its XCD's L2
-  StageLayout l;
-  const size_t o_idx = l.add((size_t)n * 8), ib = l.add((size_t)n);
-  if (int rc = stage_commit(c, &l)) return rc;
-  HIP_TRY(c, stage_in(c, l.base + o_idx, cell_index, (size_t)n * 8));
-  HIP_TRY(c, stage_in(c, l.base + ib, values, (size_t)n));
+  StageRows s;
+  const auto i_idx = s.in(cell_index, (size_t)n * 8), i_val = s.in(values, (size_t)n);
+  if (int rc = stage_commit(c, &s)) return rc;
   c->map_upload_bytes += (uint64_t)n * 9;
   // the blocked bits follow the occupancy map cell by cell; with a potential map installed they are derived from THAT
   // map (env_map.h:113-118 does not consult the occupancy), so the occupancy edit leaves them alone
   uint32_t *blk = (c->blk_ok && !c->has_pot) ? (uint32_t *)c->blk.p : nullptr;
-  HIP_TRY(c, mplx::launch_edit_map((const int64_t *)(l.base + o_idx), (const int8_t *)(l.base + ib), n, c->n_cells, (int8_t *)c->map.p, blk,
+  HIP_TRY(c, mplx::launch_edit_map(s.dev<int64_t>(i_idx), s.dev<int8_t>(i_val), n, c->n_cells, (int8_t *)c->map.p, blk,
                                    c->has_region ? (const uint32_t *)c->region_bits.p : nullptr, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));  // the caller may free its arrays on return
+  if (int rc = stage_fetch(c, &s)) return rc;  // (no output row: the synchronise -- the caller may free its arrays on return)
   c->blk_epoch++;  // (the bits were patched, or will be rebuilt: a goal field of the old map is stale, include/mplx_field.h)
   if (blk && c->sat_ok) {
     // the summed-area table (free-box shortcut of the factorised kernels) changes in every entry behind an edited cell:
@@ -88,14 +86,11 @@ int mplx_read_cells(mplx_ctx *c, int which, const int64_t *cell_index, int64_t n
       return fail(c, MPLX_ERR_ARG, "mplx_read_cells: cell index %lld outside the map of %lld cells", (long long)cell_index[i], (long long)c->n_cells);
   if (n == 0) return MPLX_OK;
   if (int rc = bind_device(c)) return rc;
-  StageLayout l;
-  const size_t o_idx = l.add((size_t)n * 8), ib = l.add((size_t)n);
-  if (int rc = stage_commit(c, &l)) return rc;
-  HIP_TRY(c, stage_in(c, l.base + o_idx, cell_index, (size_t)n * 8));
-  HIP_TRY(c, mplx::launch_gather_cells((const int8_t *)(which == 0 ? c->map.p : c->pot.p), (const int64_t *)(l.base + o_idx), n, (int8_t *)(l.base + ib), c->stream));
-  HIP_TRY(c, stage_out(c, out, l.base + ib, (size_t)n));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  return MPLX_OK;
+  StageRows s;
+  const auto i_idx = s.in(cell_index, (size_t)n * 8), o_val = s.out(out, (size_t)n);
+  if (int rc = stage_commit(c, &s)) return rc;
+  HIP_TRY(c, mplx::launch_gather_cells((const int8_t *)(which == 0 ? c->map.p : c->pot.p), s.dev<int64_t>(i_idx), n, s.dev<int8_t>(o_val), c->stream));
+  return stage_fetch(c, &s);
 }
 
 int mplx_map_upload_bytes(mplx_ctx *c, uint64_t *bytes) {

@@ -8,6 +8,7 @@
 #include "../../include/mplx_open.h"  // mplx_open, mplx_table_frontier: what open_push() below takes
 #include "../../include/mplx_traj.h"  // mplx_traj_set: what the traj_* helpers below take
 #include "mplx_internal.h"
+#include "mplx_stage.h"
 
 #include <cstdarg>
 #include <cstdio>
@@ -256,14 +257,22 @@ inline void release(DevBuf &b) {
 //  3. A call that enters another entry point while it holds arena rows has first copied everything it still needs to
 //     the host: the inner call carves the same block.
 //  4. Device-pointer entry points never touch the arena.  It only grows: the rounded rows of the largest call so far.
-inline size_t align256(size_t bytes) { return (bytes + 255) & ~(size_t)255; }  // the only rounding of staging offsets
-
-struct StageLayout {
-  size_t total = 0;
-  char *base = nullptr;       // the arena, once committed
-  // offset of a row of `bytes` (0: a row that was not asked for; the caller leaves its pointer null)
-  size_t add(size_t bytes) { const size_t at = total; total += align256(bytes); return at; }
-};
+// A host twin declares its rows once in a StageRows (mplx_stage.h: offsets and sizes, no HIP) and the rules are kept by
+// the two functions below:
+//  1. stage_commit(c, &s): the only ensure() of the arena in a call, then every input copy, in declaration order.  A row
+//     cannot be added afterwards with any effect: its device side is read through s.dev() only after the commit.
+//  2. stage_fetch(c, &s): every output copy, in declaration order, and the synchronise the twin ends with.  A twin that
+//     ends in a read-back of its own (seed_table: read_count; mplx_field_build: its passes) synchronises there instead.
+//  3. is the caller's: after stage_fetch its landed rows are host memory (s.host()), so it may enter another entry point.
+//  4. _device forms take no StageRows and no StageLayout: nothing in them can name the arena.
+// The StageRows of a call lives on its stack; no object keeps a pointer into it or into the arena.
+// Still on the raw layer (StageLayout + stage_in / stage_out), because their shape is not "copy in, launch, copy out,
+// synchronise":
+//   mplx_expand_lists, lists_host.cpp, lists_copy_api.cpp, expand_lists_packed -- zero-copy landing, the service kernel,
+//     deferral through resolve_pending;
+//   mplx_rollout (first site) -- reads the status row and synchronises first: where the other rows land depends on it;
+//   mplx_table_path -- reads the length first, then only that many ids and actions;
+//   mplx_heur_eval -- carves a block of its own (mplx_ctx::heur_ws), not the arena.
 inline int stage_commit(mplx_ctx *c, StageLayout *l) {
   if (int rc = ensure(c, c->s_arena, l->total)) return rc;
   l->base = (char *)c->s_arena.p;
@@ -282,6 +291,29 @@ inline hipError_t stage_out(mplx_ctx *c, void *host, const void *dev, size_t byt
 }
 inline hipError_t stage_out_rows(mplx_ctx *c, void *host, size_t dst_stride, const void *dev, size_t width, size_t rows) {
   return host ? hipMemcpy2DAsync(host, dst_stride, dev, width, width, rows, hipMemcpyDeviceToHost, c->stream) : hipSuccess;
+}
+
+// The rows of a call (StageRows): carve them, then the input copies in declaration order ...
+inline int stage_commit(mplx_ctx *c, StageRows *s) {
+  if (s->overflow) return fail(c, MPLX_ERR_ARG, "more than %d staged rows in one call", StageRows::kMaxRows);
+  if (s->land_total && !(s->landing = (char *)::operator new(s->land_total, std::nothrow))) return fail(c, MPLX_ERR_NOMEM, "out of host memory");
+  if (int rc = stage_commit(c, &s->l)) return rc;
+  for (int i = 0; i < s->n; i++) {
+    const StageRows::Rec &r = s->rec[i];
+    if (!r.src) continue;
+    HIP_TRY(c, r.pitch ? stage_in_rows(c, s->l.base + r.at, r.src, r.pitch, r.width, r.rows) : stage_in(c, s->l.base + r.at, r.src, r.bytes));
+  }
+  return MPLX_OK;
+}
+// ... and after the launches the output copies in declaration order and the one synchronise of the call.
+inline int stage_fetch(mplx_ctx *c, StageRows *s) {
+  for (int i = 0; i < s->n; i++) {
+    const StageRows::Rec &r = s->rec[i];
+    if (r.land) HIP_TRY(c, stage_out(c, s->landing + r.land_at, r.from ? r.from : s->l.base + r.at, r.land));
+    else if (r.dst) HIP_TRY(c, r.pitch ? stage_out_rows(c, r.dst, r.pitch, s->l.base + r.at, r.width, r.rows) : stage_out(c, r.dst, s->l.base + r.at, r.bytes));
+  }
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return MPLX_OK;
 }
 
 // The per-node lists of a host frontier, left packed in the context's pinned landing buffer (node k owns entries
@@ -374,9 +406,6 @@ int reserve_table_args(mplx_reserve *r, const char *who, mplx_ctx **c, mplx::Res
 // ... and as the check of a solved set (reserve_poly_api.cpp) sees it: MPLX_ERR_STATE before a fill only; the table
 // fields, Q (0 before mplx_reserve_set_queries) and, where Q >= 1, the query fields
 int reserve_fill_args(mplx_reserve *r, const char *who, mplx_ctx **c, mplx::ReserveArgs *a);
-// ... and `bytes` of the table's own row buffer, where the host-pointer calls of include/mplx_reserve_poly.h lay out their
-// rows with a StageLayout (they end in a synchronise; the buffer is the table's, not the context's arena)
-int reserve_host_rows(mplx_reserve *r, size_t bytes, char **base);
 // wait_api.cpp: the zero action of include/mplx_wait.h -- the smallest all-zero row of the control table -- or -1
 int32_t zero_action(const mplx_ctx *c);
 // ... and as the check of a reservation table (reserve_api.cpp) sees it: the same check, the per-node query column (null
@@ -392,11 +421,12 @@ int open_park_args(mplx_open *o, const char *who, mplx_ctx **c, mplx_table **tab
 void open_field_gone(mplx_open *o);
 
 // traj_api.cpp: the checks of a trajectory set, the chain launch into the context's segment table, and the staging of a
-// host set (rows carved by traj_set_rows, copied by traj_stage_set), for conflict_api.cpp.
+// host set (rows declared by traj_set_rows; after the commit traj_set_view gives the device set), for conflict_api.cpp.
 int traj_check_set(mplx_ctx *c, const char *who, const mplx_traj_set *s, const void *out);
 int traj_build_table(mplx_ctx *c, const mplx_traj_set *s, mplx::TrajArgs *out);
-void traj_set_rows(const mplx_ctx *c, const mplx_traj_set *s, StageLayout *l, size_t *starts, size_t *actions);
-int traj_stage_set(mplx_ctx *c, const mplx_traj_set *s, const StageLayout &l, size_t starts, size_t actions, mplx_traj_set *d);
+struct TrajSetRows { StageRows::Row starts, actions; };
+TrajSetRows traj_set_rows(const mplx_ctx *c, const mplx_traj_set *s, StageRows *st);
+mplx_traj_set traj_set_view(const mplx_traj_set *s, const StageRows &st, const TrajSetRows &r);
 
 // mplx_api.cpp: a goal as the kernels take it (mplx_set_goal's checks and hash), for the goals of an open set.
 int goal_fuse_of(mplx_ctx *c, const char *who, const mplx_goal_spec *g, mplx::PostFuse *out);

@@ -303,15 +303,13 @@ int mplx_open_set_goals(mplx_open *o, const mplx_goal_spec *h_goals, int32_t n) 
   if (int rc = ensure(c, o->goals, bytes)) return rc;
   if (int rc = ensure(c, o->goals0, bytes)) return rc;
   if (int rc = ensure(c, o->dyn_ctl, ctl.size() * 4)) return rc;
-  StageLayout l;
-  const size_t o_g = l.add(bytes), o_c = l.add(ctl.size() * 4);
-  if (int rc = stage_commit(c, &l)) return rc;
-  HIP_TRY(c, stage_in(c, l.base + o_g, f.data(), bytes));
-  HIP_TRY(c, stage_in(c, l.base + o_c, ctl.data(), ctl.size() * 4));
-  HIP_TRY(c, hipMemcpyAsync(o->dyn_ctl.p, l.base + o_c, ctl.size() * 4, hipMemcpyDeviceToDevice, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(o->goals.p, l.base + o_g, bytes, hipMemcpyDeviceToDevice, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(o->goals0.p, l.base + o_g, bytes, hipMemcpyDeviceToDevice, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));  // (f leaves scope; the arena is free again)
+  StageRows s;
+  const auto i_g = s.in(f.data(), bytes), i_c = s.in(ctl.data(), ctl.size() * 4);
+  if (int rc = stage_commit(c, &s)) return rc;
+  HIP_TRY(c, hipMemcpyAsync(o->dyn_ctl.p, s.dev<char>(i_c), ctl.size() * 4, hipMemcpyDeviceToDevice, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(o->goals.p, s.dev<char>(i_g), bytes, hipMemcpyDeviceToDevice, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(o->goals0.p, s.dev<char>(i_g), bytes, hipMemcpyDeviceToDevice, c->stream));
+  if (int rc = stage_fetch(c, &s)) return rc;  // (no output row: the synchronise -- f leaves scope; the arena is free again)
   o->has_priors = false;  // a new goal: the old prior no longer leads to it (include/mplx_prior.h)
   drop_field(o);          // ... and neither does the old field (include/mplx_field.h)
   o->has_goals = true;
@@ -481,12 +479,11 @@ int mplx_open_set_field(mplx_open *o, mplx_field *fld, const int32_t *h_field_of
   if (int rc = resolve_pending(c)) return rc;  // the arena is shared with the other host-pointer calls
   const size_t bytes = (size_t)o->Q * 4;
   if (int rc = ensure(c, o->fld_q, bytes)) return rc;
-  StageLayout l;
-  const size_t o_q = l.add(bytes);
-  if (int rc = stage_commit(c, &l)) return rc;
-  HIP_TRY(c, stage_in(c, l.base + o_q, fq.data(), bytes));
-  HIP_TRY(c, hipMemcpyAsync(o->fld_q.p, l.base + o_q, bytes, hipMemcpyDeviceToDevice, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));  // (fq leaves scope; the arena is free again)
+  StageRows s;
+  const auto i_q = s.in(fq.data(), bytes);
+  if (int rc = stage_commit(c, &s)) return rc;
+  HIP_TRY(c, hipMemcpyAsync(o->fld_q.p, s.dev<char>(i_q), bytes, hipMemcpyDeviceToDevice, c->stream));
+  if (int rc = stage_fetch(c, &s)) return rc;  // (no output row: the synchronise -- fq leaves scope; the arena is free again)
   if (o->fld != fld) {
     fld->users.push_back(o);  // (first: if it throws nothing has changed)
     drop_field(o);

@@ -70,13 +70,14 @@ int mplx_ray_trace(mplx_ctx *c, const double *h_p1, const double *h_p2, int64_t 
   if (int rc = bind_device(c)) return rc;
   if (int rc = resolve_pending(c)) return rc;  // the arena is shared with the other host-pointer calls
   const int D = c->dim;
-  const int64_t n2 = p2_stride == 0 ? 1 : n;
   const size_t N = (size_t)n, cell_bytes = h_out->cells ? N * (size_t)h_out->cell_cap * 4 : 0;
-  // One arena block: p1 [D][n], p2 [D][n] (or D doubles), status, n_cells, first_hit, cells.
-  StageLayout l;
-  const size_t o_p1 = l.add((size_t)D * N * 8), o_p2 = l.add((size_t)D * n2 * 8), o_status = l.add(N),
-               o_count = l.add(h_out->n_cells ? N * 4 : 0), o_hit = l.add(h_out->first_hit ? N * 4 : 0), o_cells = l.add(cell_bytes);
-  if (int rc = stage_commit(c, &l)) return rc;
+  // One arena block: p1 [D][n], p2 [D][n] (or D doubles), status, n_cells, first_hit, cells.  The entries of a cells row
+  // past min(n_cells, cell_cap) keep the caller's bytes: they make the round trip.
+  StageRows s;
+  const auto i_p1 = s.in_rows(h_p1, (size_t)stride * 8, N * 8, D),
+             i_p2 = p2_stride == 0 ? s.in(h_p2, (size_t)D * 8) : s.in_rows(h_p2, (size_t)p2_stride * 8, N * 8, D),
+             o_status = s.out_or_scratch(h_out->status, N), o_count = s.out(h_out->n_cells, N * 4), o_hit = s.out(h_out->first_hit, N * 4),
+             o_cells = s.inout(h_out->cells, cell_bytes);
   if (lanes == 0) {
     // the points are at hand here: the longest ray's own step count instead of the map's bound (BAD rays trace nothing)
     double steps = 0.0;
@@ -91,25 +92,15 @@ int mplx_ray_trace(mplx_ctx *c, const double *h_p1, const double *h_p2, int64_t 
     }
     lanes = auto_lanes(steps);
   }
-  HIP_TRY(c, stage_in_rows(c, l.base + o_p1, h_p1, (size_t)stride * 8, N * 8, D));
-  if (p2_stride == 0) HIP_TRY(c, stage_in(c, l.base + o_p2, h_p2, (size_t)D * 8));
-  else HIP_TRY(c, stage_in_rows(c, l.base + o_p2, h_p2, (size_t)p2_stride * 8, N * 8, D));
-  // the entries of a row past min(n_cells, cell_cap) keep the caller's bytes: they make the round trip
-  if (cell_bytes) HIP_TRY(c, stage_in(c, l.base + o_cells, h_out->cells, cell_bytes));
+  if (int rc = stage_commit(c, &s)) return rc;
   mplx_ray_out d{};
-  d.status = (uint8_t *)(l.base + o_status);
-  d.n_cells = h_out->n_cells ? (int32_t *)(l.base + o_count) : nullptr;
-  d.first_hit = h_out->first_hit ? (int32_t *)(l.base + o_hit) : nullptr;
-  d.cells = cell_bytes ? (int32_t *)(l.base + o_cells) : nullptr;
+  d.status = s.dev<uint8_t>(o_status);
+  d.n_cells = s.dev<int32_t>(o_count);
+  d.first_hit = s.dev<int32_t>(o_hit);
+  d.cells = s.dev<int32_t>(o_cells);
   d.cell_cap = h_out->cell_cap;
-  if (int rc = launch(c, (const double *)(l.base + o_p1), (const double *)(l.base + o_p2), n, n, p2_stride == 0 ? 0 : n, lanes, &d))
-    return rc;
-  HIP_TRY(c, stage_out(c, h_out->status, d.status, N));
-  HIP_TRY(c, stage_out(c, h_out->n_cells, d.n_cells, N * 4));
-  HIP_TRY(c, stage_out(c, h_out->first_hit, d.first_hit, N * 4));
-  HIP_TRY(c, stage_out(c, h_out->cells, d.cells, cell_bytes));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  return MPLX_OK;
+  if (int rc = launch(c, s.dev<double>(i_p1), s.dev<double>(i_p2), n, n, p2_stride == 0 ? 0 : n, lanes, &d)) return rc;
+  return stage_fetch(c, &s);
 }
 
 // goal_or_null / the context's goal, or (d_goals != null) the goal per list entry

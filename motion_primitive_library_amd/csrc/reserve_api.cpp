@@ -15,7 +15,6 @@ struct mplx_reserve {
   mplx_ctx *c = nullptr;
   DevBuf mem;      // the per-trajectory rows, then pos [D][n_steps][B] and act [n_steps][B]
   DevBuf queries;  // t0 [Q], radius [Q], ignore [Q]
-  DevBuf rows;     // the host rows of the host-pointer calls of include/mplx_reserve_poly.h; grown on demand
   bool filled = false;
   int32_t Q = 0;
   int64_t B = 0;
@@ -72,29 +71,17 @@ int fill(mplx_reserve *r, const mplx::TrajArgs &t, const mplx_conflict_in *in) {
   return MPLX_OK;
 }
 
-// the [K] rows of a host mplx_conflict_in in the arena
-struct Rows { size_t t0, radius, group; };
-Rows rows_of(size_t K, const mplx_conflict_in *in, StageLayout *l) {
-  Rows r;
-  r.t0 = l->add(in->t0 ? K * 8 : 0); r.radius = l->add(in->radius ? K * 8 : 0); r.group = l->add(in->group ? K * 4 : 0);
-  return r;
+// the [K] rows of a host mplx_conflict_in in the arena; after the commit, the device form of `h_in`
+struct Rows { StageRows::Row t0, radius, group; };
+Rows rows_of(size_t K, const mplx_conflict_in *in, StageRows *s) {
+  const auto t0 = s->in(in->t0, K * 8), radius = s->in(in->radius, K * 8);
+  return {t0, radius, s->in(in->group, K * 4)};
 }
-int stage_rows(mplx_ctx *c, size_t K, const StageLayout &l, const Rows &r, const mplx_conflict_in *h_in, mplx_conflict_in *in) {
-  *in = *h_in;
-  in->rank = nullptr;
-  if (h_in->t0) {
-    HIP_TRY(c, stage_in(c, l.base + r.t0, h_in->t0, K * 8));
-    in->t0 = (const double *)(l.base + r.t0);
-  }
-  if (h_in->radius) {
-    HIP_TRY(c, stage_in(c, l.base + r.radius, h_in->radius, K * 8));
-    in->radius = (const double *)(l.base + r.radius);
-  }
-  if (h_in->group) {
-    HIP_TRY(c, stage_in(c, l.base + r.group, h_in->group, K * 4));
-    in->group = (const int32_t *)(l.base + r.group);
-  }
-  return MPLX_OK;
+mplx_conflict_in staged_in(const StageRows &s, const Rows &r, const mplx_conflict_in *h_in) {
+  mplx_conflict_in in = *h_in;
+  in.rank = nullptr;
+  in.t0 = s.dev<double>(r.t0); in.radius = s.dev<double>(r.radius); in.group = s.dev<int32_t>(r.group);
+  return in;
 }
 
 int check_poly(mplx_reserve *r, mplx_poly *p, const char *who, const mplx_conflict_in *in) {
@@ -130,12 +117,6 @@ int mplx_detail::reserve_fill_args(mplx_reserve *r, const char *who, mplx_ctx **
   return MPLX_OK;
 }
 
-int mplx_detail::reserve_host_rows(mplx_reserve *r, size_t bytes, char **base) {
-  if (int rc = ensure(r->c, r->rows, std::max<size_t>(bytes, 256))) return rc;
-  *base = (char *)r->rows.p;
-  return MPLX_OK;
-}
-
 int mplx_detail::reserve_table_args(mplx_reserve *r, const char *who, mplx_ctx **c, mplx::ReserveArgs *a) {
   if (int rc = reserve_fill_args(r, who, c, a)) return rc;
   if (r->Q < 1) return fail(r->c, MPLX_ERR_STATE, "%s: mplx_reserve_set_queries has not been called", who);
@@ -167,7 +148,6 @@ void mplx_reserve_destroy(mplx_reserve *r) {
   (void)hipStreamSynchronize(r->c->stream);
   release(r->mem);
   release(r->queries);
-  release(r->rows);
   delete r;
 }
 
@@ -185,14 +165,12 @@ int mplx_reserve_fill_poly(mplx_reserve *r, mplx_poly *p, const mplx_conflict_in
   if (int rc = bind_device(c)) return rc;
   if (int rc = resolve_pending(c)) return rc;  // the arena is shared with the other host-pointer calls
   const size_t K = (size_t)p->n;
-  StageLayout l;
-  const Rows rows = rows_of(K, h_in, &l);
-  if (int rc = stage_commit(c, &l)) return rc;
-  mplx_conflict_in in;
-  if (int rc = stage_rows(c, K, l, rows, h_in, &in)) return rc;
+  StageRows s;
+  const Rows rows = rows_of(K, h_in, &s);
+  if (int rc = stage_commit(c, &s)) return rc;
+  const mplx_conflict_in in = staged_in(s, rows, h_in);
   if (int rc = fill(r, poly_table_args(p), &in)) return rc;
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  return MPLX_OK;
+  return stage_fetch(c, &s);
 }
 
 int mplx_reserve_fill_traj_device(mplx_reserve *r, mplx_ctx *ctx, const mplx_traj_set *d_set, const mplx_conflict_in *d_in) {
@@ -215,19 +193,15 @@ int mplx_reserve_fill_traj(mplx_reserve *r, mplx_ctx *ctx, const mplx_traj_set *
   const size_t K = (size_t)h_set->n_traj;
   mplx::TrajArgs t{};
   if (K == 0) return fill(r, t, h_in);
-  StageLayout l;
-  size_t o_starts, o_actions;
-  traj_set_rows(c, h_set, &l, &o_starts, &o_actions);
-  const Rows rows = rows_of(K, h_in, &l);
-  if (int rc = stage_commit(c, &l)) return rc;
-  mplx_traj_set d;
-  if (int rc = traj_stage_set(c, h_set, l, o_starts, o_actions, &d)) return rc;
-  mplx_conflict_in in;
-  if (int rc = stage_rows(c, K, l, rows, h_in, &in)) return rc;
+  StageRows s;
+  const TrajSetRows set = traj_set_rows(c, h_set, &s);
+  const Rows rows = rows_of(K, h_in, &s);
+  if (int rc = stage_commit(c, &s)) return rc;
+  const mplx_traj_set d = traj_set_view(h_set, s, set);
+  const mplx_conflict_in in = staged_in(s, rows, h_in);
   if (int rc = traj_build_table(c, &d, &t)) return rc;
   if (int rc = fill(r, t, &in)) return rc;
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  return MPLX_OK;
+  return stage_fetch(c, &s);
 }
 
 int mplx_reserve_shape(mplx_reserve *r, int64_t *n_traj, int32_t *n_steps, double *step) {

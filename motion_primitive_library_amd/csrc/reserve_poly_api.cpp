@@ -1,7 +1,7 @@
 // reserve_poly_api.cpp -- C ABI of the check of include/mplx_reserve_poly.h: the problems of a poly against a reservation
 // table (reserve_poly_kernel.hip).  The table is the mplx_reserve's own memory, the segment table the poly's; the launch
-// goes to the context's stream and the host-pointer twin lays out its [K] rows in the reservation table's own row buffer
-// (reserve_host_rows) and is synchronous.  The timed shortcut of the same header stands next to the shortcut it extends,
+// goes to the context's stream and the host-pointer twin stages its [K] rows through the context's arena like every other
+// twin and is synchronous.  The timed shortcut of the same header stands next to the shortcut it extends,
 // in limits_api.cpp.
 #include "mplx_poly.h"
 #include "../../include/mplx_reserve_poly.h"
@@ -59,29 +59,17 @@ int mplx_reserve_check_poly(mplx_reserve *r, mplx_poly *p, const mplx_reserve_po
   mplx::ReserveArgs t{};
   if (int rc = check(r, p, "mplx_reserve_check_poly", h_in, h_out, &c, &t)) return rc;
   if (p->n == 0) return MPLX_OK;
-  MPLX_GUARD_BEGIN
   if (int rc = bind_device(c)) return rc;
-  if (int rc = resolve_pending(c)) return rc;
+  if (int rc = resolve_pending(c)) return rc;  // the arena is shared with the other host-pointer calls
   const size_t K = (size_t)p->n;
-  StageLayout l;
-  const size_t i_t = l.add(K * 8), i_r = l.add(h_in->radius ? K * 8 : 0), i_g = l.add(h_in->ignore_group ? K * 4 : 0);
-  const size_t o_h = l.add(h_out->hit ? K * 8 : 0), o_s = l.add(h_out->status ? K : 0), o_n = l.add(h_out->n_hit ? 8 : 0);
-  if (int rc = reserve_host_rows(r, l.total, &l.base)) return rc;
-  HIP_TRY(c, stage_in(c, l.base + i_t, h_in->t_start, K * 8));
-  if (h_in->radius) HIP_TRY(c, stage_in(c, l.base + i_r, h_in->radius, K * 8));
-  if (h_in->ignore_group) HIP_TRY(c, stage_in(c, l.base + i_g, h_in->ignore_group, K * 4));
-  if (h_out->n_hit) HIP_TRY(c, stage_in(c, l.base + o_n, h_out->n_hit, 8));
-  int64_t *d_hit = h_out->hit ? (int64_t *)(l.base + o_h) : nullptr, *d_n = h_out->n_hit ? (int64_t *)(l.base + o_n) : nullptr;
-  uint8_t *d_st = h_out->status ? (uint8_t *)(l.base + o_s) : nullptr;
-  if (int rc = reserve_check_poly_launch(t, p, (const double *)(l.base + i_t), h_in->radius ? (const double *)(l.base + i_r) : nullptr,
-                                         h_in->radius_all, h_in->ignore_group ? (const int32_t *)(l.base + i_g) : nullptr, d_hit, d_st, d_n))
+  StageRows s;
+  const auto i_t = s.in(h_in->t_start, K * 8), i_r = s.in(h_in->radius, K * 8), i_g = s.in(h_in->ignore_group, K * 4);
+  const auto o_h = s.out(h_out->hit, K * 8), o_s = s.out(h_out->status, K), o_n = s.inout(h_out->n_hit, 8);
+  if (int rc = stage_commit(c, &s)) return rc;
+  if (int rc = reserve_check_poly_launch(t, p, s.dev<double>(i_t), s.dev<double>(i_r), h_in->radius_all, s.dev<int32_t>(i_g),
+                                         s.dev<int64_t>(o_h), s.dev<uint8_t>(o_s), s.dev<int64_t>(o_n)))
     return rc;
-  HIP_TRY(c, stage_out(c, h_out->hit, d_hit, K * 8));
-  HIP_TRY(c, stage_out(c, h_out->status, d_st, K));
-  HIP_TRY(c, stage_out(c, h_out->n_hit, d_n, 8));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  return MPLX_OK;
-  MPLX_GUARD_END(c)
+  return stage_fetch(c, &s);
 }
 
 }  // extern "C"

@@ -228,17 +228,14 @@ int mplx_rollout(mplx_ctx *c, const double *h_starts, int64_t n_starts, int64_t 
     std::vector<int32_t> minus1((size_t)r, -1);
     for (int64_t i = 0; i < r; i++)
       for (int f = 0; f < F; f++) st0[(size_t)f * r + i] = cur[(size_t)f * m + rehash[(size_t)i]];
-    StageLayout lr;  // (the arena again: nothing of the first launch is still needed on the device)
-    const size_t o_st0 = lr.add((size_t)F * r * 8), o_minus1 = lr.add((size_t)r * 4), o_h0 = lr.add((size_t)r * 8);
-    if (int rc = stage_commit(c, &lr)) return rc;
-    HIP_TRY(c, stage_in(c, lr.base + o_st0, st0.data(), st0.size() * 8));
-    HIP_TRY(c, stage_in(c, lr.base + o_minus1, minus1.data(), (size_t)r * 4));
+    StageRows sr;  // (the arena again: nothing of the first launch is still needed on the device)
+    const auto i_st0 = sr.in(st0.data(), st0.size() * 8), i_minus1 = sr.in(minus1.data(), (size_t)r * 4), o_h0 = sr.landed((size_t)r * 8);
+    if (int rc = stage_commit(c, &sr)) return rc;
     mplx_rollout_out ho{};
-    ho.end_hash = (uint64_t *)(lr.base + o_h0);
-    if (int rc = launch(c, (const double *)(lr.base + o_st0), r, r, (const int32_t *)(lr.base + o_minus1), r, 1, r, &ho)) return rc;
-    std::vector<uint64_t> h0((size_t)r);
-    HIP_TRY(c, stage_out(c, h0.data(), ho.end_hash, (size_t)r * 8));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    ho.end_hash = sr.dev<uint64_t>(o_h0);
+    if (int rc = launch(c, sr.dev<double>(i_st0), r, r, sr.dev<int32_t>(i_minus1), r, 1, r, &ho)) return rc;
+    if (int rc = stage_fetch(c, &sr)) return rc;
+    const uint64_t *h0 = sr.host<uint64_t>(o_h0);
     for (int64_t i = 0; i < r; i++) hash[(size_t)band[(size_t)rehash[(size_t)i]]] = h0[(size_t)i];
   }
   for (int64_t j = 0; j < m; j++) {

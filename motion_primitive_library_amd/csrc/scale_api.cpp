@@ -5,7 +5,6 @@
 #include "../../include/mplx_scale.h"
 
 #include <algorithm>
-#include <vector>
 
 using namespace mplx_detail;
 
@@ -101,25 +100,28 @@ int scale_down_launch(mplx_poly *p, const mplx_scale_down_in *in, const mplx_sca
   return MPLX_OK;
 }
 
-// The host side of a build: the poly's own compact rows, scattered into the caller's strides.  A problem with a solve
-// or load status, or one scale_down left alone (`down`), keeps the caller's bytes; one with a Lambda status its status.
-int read_back(mplx_poly *p, const mplx_lambda_out *h, const mplx_scale_down_out *down) {
-  mplx_ctx *c = p->c;
+// The host side of a build: the poly's own compact rows (none of them in the arena; the table exists from here on),
+// declared before the commit and scattered into the caller's strides after the launch.  A problem with a solve or load status, or one scale_down left
+// alone (`down`), keeps the caller's bytes; one with a Lambda status its status.
+struct BuildRows { StageRows::Row S, nl, st, total, Ts, segs, sc, res; };
+int build_rows(mplx_poly *p, const mplx_lambda_out *h, bool down, StageRows *s, BuildRows *out) {
+  if (int rc = ensure_lambda(p)) return rc;
   const size_t n = (size_t)p->n, W = (size_t)p->w;
-  char *b = (char *)p->lam.p;
-  std::vector<int32_t> S(n), nl(n);
-  std::vector<uint8_t> st(n), sc(down ? n : 0);
-  std::vector<double> total(n), Ts(h->Ts ? W * n : 0), segs(h->segs ? 64 * n : 0), res(down ? 3 * n : 0);
-  HIP_TRY(c, stage_out(c, S.data(), (char *)p->mem.p + p->o_S, n * 4));
-  HIP_TRY(c, stage_out(c, nl.data(), b + p->l_n, n * 4));
-  HIP_TRY(c, stage_out(c, st.data(), b + p->l_st, n));
-  HIP_TRY(c, stage_out(c, total.data(), b + p->l_total, n * 8));
-  HIP_TRY(c, stage_out(c, Ts.empty() ? nullptr : Ts.data(), b + p->l_Ts, Ts.size() * 8));
-  HIP_TRY(c, stage_out(c, segs.empty() ? nullptr : segs.data(), b + p->l_seg, segs.size() * 8));
-  HIP_TRY(c, stage_out(c, sc.empty() ? nullptr : sc.data(), b + p->l_scaled, sc.size()));
-  HIP_TRY(c, stage_out(c, res.empty() ? nullptr : res.data(), b + p->l_res, res.size() * 8));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  if (down && std::none_of(sc.begin(), sc.end(), [](uint8_t x) { return x != 0; }))
+  const char *b = (const char *)p->lam.p;
+  BuildRows &r = *out;
+  r.S = s->landed_from((const char *)p->mem.p + p->o_S, n * 4);
+  r.nl = s->landed_from(b + p->l_n, n * 4); r.st = s->landed_from(b + p->l_st, n); r.total = s->landed_from(b + p->l_total, n * 8);
+  r.Ts = s->landed_from(b + p->l_Ts, h->Ts ? W * n * 8 : 0); r.segs = s->landed_from(b + p->l_seg, h->segs ? 64 * n * 8 : 0);
+  r.sc = s->landed_from(b + p->l_scaled, down ? n : 0); r.res = s->landed_from(b + p->l_res, down ? 3 * n * 8 : 0);
+  return MPLX_OK;
+}
+int read_back(mplx_poly *p, StageRows *s, const BuildRows &r, const mplx_lambda_out *h, const mplx_scale_down_out *down) {
+  if (int rc = stage_fetch(p->c, s)) return rc;
+  const size_t n = (size_t)p->n;
+  const int32_t *S = s->host<int32_t>(r.S), *nl = s->host<int32_t>(r.nl);
+  const uint8_t *st = s->host<uint8_t>(r.st), *sc = s->host<uint8_t>(r.sc);
+  const double *total = s->host<double>(r.total), *Ts = s->host<double>(r.Ts), *segs = s->host<double>(r.segs), *res = s->host<double>(r.res);
+  if (down && std::none_of(sc, sc + n, [](uint8_t x) { return x != 0; }))
     p->has_lambda = false;  // nothing was scaled: the poly is a plain one again (sample, traverse)
   for (size_t k = 0; k < n; k++) {
     if (S[k] == 0) continue;
@@ -192,24 +194,20 @@ int mplx_poly_set_lambda(mplx_poly *p, const mplx_lambda_in *h_in, const mplx_la
   if (int rc = check_poly(p, "mplx_poly_set_lambda", h_in, h_out, h_in ? h_in->mode : 0)) return rc;
   if (int rc = check_lambda_out(p, "mplx_poly_set_lambda", h_out)) return rc;
   if (p->n > 0 && (!h_in->pts || h_in->stride < p->n)) return fail(c, MPLX_ERR_ARG, "mplx_poly_set_lambda: NULL pts or stride < n_prob");
-  MPLX_GUARD_BEGIN
   if (int rc = bind_device(c)) return rc;
   if (int rc = resolve_pending(c)) return rc;  // the arena is shared with the other host-pointer calls
   const size_t n = (size_t)p->n;
-  StageLayout l;
-  const size_t i_p = l.add(27 * n * 8), i_n = l.add(h_in->n_pts ? n * 4 : 0);
-  if (int rc = stage_commit(c, &l)) return rc;
+  StageRows s;
+  const auto i_p = s.in_rows(h_in->pts, (size_t)h_in->stride * 8, n * 8, 27), i_n = s.in(h_in->n_pts, n * 4);
+  BuildRows rb;
+  if (int rc = build_rows(p, h_out, false, &s, &rb)) return rc;
+  if (int rc = stage_commit(c, &s)) return rc;
   mplx_lambda_in in = *h_in;
-  HIP_TRY(c, stage_in_rows(c, l.base + i_p, h_in->pts, (size_t)h_in->stride * 8, n * 8, 27));
-  in.pts = (const double *)(l.base + i_p); in.stride = (int64_t)n;
-  if (h_in->n_pts) {
-    HIP_TRY(c, stage_in(c, l.base + i_n, h_in->n_pts, n * 4));
-    in.n_pts = (const int32_t *)(l.base + i_n);
-  }
+  in.pts = s.dev<double>(i_p); in.stride = (int64_t)n;
+  in.n_pts = s.dev<int32_t>(i_n);
   const mplx_lambda_out none{};
   if (int rc = set_lambda_launch(p, &in, &none)) return rc;
-  return read_back(p, h_out, nullptr);
-  MPLX_GUARD_END(c)
+  return read_back(p, &s, rb, h_out, nullptr);
 }
 
 int mplx_poly_scale_device(mplx_poly *p, const mplx_scale_in *d_in, const mplx_lambda_out *d_out) {
@@ -224,26 +222,20 @@ int mplx_poly_scale(mplx_poly *p, const mplx_scale_in *h_in, const mplx_lambda_o
   mplx_ctx *c = p->c;
   if (int rc = check_poly(p, "mplx_poly_scale", h_in, h_out, h_in ? h_in->mode : 0)) return rc;
   if (int rc = check_lambda_out(p, "mplx_poly_scale", h_out)) return rc;
-  MPLX_GUARD_BEGIN
   if (int rc = bind_device(c)) return rc;
   if (int rc = resolve_pending(c)) return rc;
   const size_t n = (size_t)p->n;
-  StageLayout l;
-  const size_t i_ri = l.add(h_in->ri_arr ? n * 8 : 0), i_rf = l.add(h_in->rf_arr ? n * 8 : 0);
-  if (int rc = stage_commit(c, &l)) return rc;
+  StageRows s;
+  const auto i_ri = s.in(h_in->ri_arr, n * 8), i_rf = s.in(h_in->rf_arr, n * 8);
+  BuildRows rb;
+  if (int rc = build_rows(p, h_out, false, &s, &rb)) return rc;
+  if (int rc = stage_commit(c, &s)) return rc;
   mplx_scale_in in = *h_in;
-  if (h_in->ri_arr) {
-    HIP_TRY(c, stage_in(c, l.base + i_ri, h_in->ri_arr, n * 8));
-    in.ri_arr = (const double *)(l.base + i_ri);
-  }
-  if (h_in->rf_arr) {
-    HIP_TRY(c, stage_in(c, l.base + i_rf, h_in->rf_arr, n * 8));
-    in.rf_arr = (const double *)(l.base + i_rf);
-  }
+  in.ri_arr = s.dev<double>(i_ri);
+  in.rf_arr = s.dev<double>(i_rf);
   const mplx_lambda_out none{};
   if (int rc = scale_launch(p, &in, &none)) return rc;
-  return read_back(p, h_out, nullptr);
-  MPLX_GUARD_END(c)
+  return read_back(p, &s, rb, h_out, nullptr);
 }
 
 int mplx_poly_scale_down_device(mplx_poly *p, const mplx_scale_down_in *in, const mplx_scale_down_out *d_out) {
@@ -258,13 +250,15 @@ int mplx_poly_scale_down(mplx_poly *p, const mplx_scale_down_in *in, const mplx_
   mplx_ctx *c = p->c;
   if (int rc = check_poly(p, "mplx_poly_scale_down", in, h_out, in ? in->mode : 0)) return rc;
   if (int rc = check_lambda_out(p, "mplx_poly_scale_down", &h_out->lambda)) return rc;
-  MPLX_GUARD_BEGIN
   if (int rc = bind_device(c)) return rc;
   if (int rc = resolve_pending(c)) return rc;
+  StageRows s;  // (no arena row: the build reads no host array)
+  BuildRows rb;
+  if (int rc = build_rows(p, &h_out->lambda, true, &s, &rb)) return rc;
+  if (int rc = stage_commit(c, &s)) return rc;
   const mplx_scale_down_out none{};
   if (int rc = scale_down_launch(p, in, &none)) return rc;
-  return read_back(p, &h_out->lambda, h_out);
-  MPLX_GUARD_END(c)
+  return read_back(p, &s, rb, &h_out->lambda, h_out);
 }
 
 int mplx_poly_tau_device(mplx_poly *p, const mplx_traj_times *d_times, const mplx_tau_out *d_out) {
@@ -280,45 +274,39 @@ int mplx_poly_tau(mplx_poly *p, const mplx_traj_times *h_times, const mplx_tau_o
   mplx_ctx *c = p->c;
   int64_t count = 0;
   if (int rc = check_tau(p, "mplx_poly_tau", h_times, h_out, &count)) return rc;
-  MPLX_GUARD_BEGIN
   if (int rc = bind_device(c)) return rc;
   if (int rc = resolve_pending(c)) return rc;
   const size_t n = (size_t)p->n, cnt = (size_t)count;
   const bool own_times = h_times->n_uniform == 0;
   const size_t n_cols = own_times ? (h_times->time_stride ? n : 1) : 0;
-  StageLayout l;
-  const size_t i_t = l.add(n_cols * cnt * 8), o_tau = l.add(n * cnt * 8), o_l = l.add(n * cnt * 8), o_d = l.add(n * cnt * 8), o_f = l.add(n * cnt);
-  if (int rc = stage_commit(c, &l)) return rc;
+  const size_t src_stride = (size_t)(h_times->time_stride ? h_times->time_stride : (int64_t)cnt) * 8;
+  StageRows s;
+  const auto i_t = s.in_rows(own_times ? h_times->times : nullptr, src_stride, cnt * 8, n_cols), o_tau = s.landed(n * cnt * 8),
+             o_l = s.landed(n * cnt * 8), o_d = s.landed(n * cnt * 8), o_f = s.landed(n * cnt),
+             t_S = s.landed_from((char *)p->mem.p + p->o_S, n * 4);
+  if (int rc = stage_commit(c, &s)) return rc;
   mplx_traj_times t = *h_times;
   if (own_times) {
-    const size_t src_stride = (size_t)(h_times->time_stride ? h_times->time_stride : (int64_t)cnt) * 8;
-    HIP_TRY(c, stage_in_rows(c, l.base + i_t, h_times->times, src_stride, cnt * 8, n_cols));
-    t.times = (const double *)(l.base + i_t);
+    t.times = s.dev<double>(i_t);
     t.time_stride = h_times->time_stride ? (int64_t)cnt : 0;
   }
   mplx_tau_out o{};
-  o.tau = (double *)(l.base + o_tau); o.lambda = (double *)(l.base + o_l); o.lambda_dot = (double *)(l.base + o_d);
-  o.found = (uint8_t *)(l.base + o_f); o.stride = (int64_t)cnt;
+  o.tau = s.dev<double>(o_tau); o.lambda = s.dev<double>(o_l); o.lambda_dot = s.dev<double>(o_d);
+  o.found = s.dev<uint8_t>(o_f); o.stride = (int64_t)cnt;
   if (int rc = tau_launch(p, &t, &o, count)) return rc;
-  std::vector<int32_t> S(n);
-  std::vector<double> tau(n * cnt), lam(n * cnt), dot(n * cnt);
-  std::vector<uint8_t> fd(n * cnt);
-  HIP_TRY(c, stage_out(c, S.data(), (char *)p->mem.p + p->o_S, n * 4));
-  HIP_TRY(c, stage_out(c, tau.data(), o.tau, n * cnt * 8));
-  HIP_TRY(c, stage_out(c, lam.data(), o.lambda, n * cnt * 8));
-  HIP_TRY(c, stage_out(c, dot.data(), o.lambda_dot, n * cnt * 8));
-  HIP_TRY(c, stage_out(c, fd.data(), o.found, n * cnt));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  if (int rc = stage_fetch(c, &s)) return rc;
+  const int32_t *S = s.host<int32_t>(t_S);
+  const double *tau = s.host<double>(o_tau), *lam = s.host<double>(o_l), *dot = s.host<double>(o_d);
+  const uint8_t *fd = s.host<uint8_t>(o_f);
   for (size_t k = 0; k < n; k++) {
     if (S[k] == 0) continue;  // a failed problem keeps the caller's bytes
     const int64_t at = (int64_t)k * h_out->stride;
-    if (h_out->tau) std::copy(tau.begin() + k * cnt, tau.begin() + (k + 1) * cnt, h_out->tau + at);
-    if (h_out->lambda) std::copy(lam.begin() + k * cnt, lam.begin() + (k + 1) * cnt, h_out->lambda + at);
-    if (h_out->lambda_dot) std::copy(dot.begin() + k * cnt, dot.begin() + (k + 1) * cnt, h_out->lambda_dot + at);
-    if (h_out->found) std::copy(fd.begin() + k * cnt, fd.begin() + (k + 1) * cnt, h_out->found + at);
+    if (h_out->tau) std::copy(tau + k * cnt, tau + (k + 1) * cnt, h_out->tau + at);
+    if (h_out->lambda) std::copy(lam + k * cnt, lam + (k + 1) * cnt, h_out->lambda + at);
+    if (h_out->lambda_dot) std::copy(dot + k * cnt, dot + (k + 1) * cnt, h_out->lambda_dot + at);
+    if (h_out->found) std::copy(fd + k * cnt, fd + (k + 1) * cnt, h_out->found + at);
   }
   return MPLX_OK;
-  MPLX_GUARD_END(c)
 }
 
 int mplx_poly_clear_lambda(mplx_poly *p) {

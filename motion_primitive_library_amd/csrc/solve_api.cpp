@@ -5,7 +5,6 @@
 #include "mplx_poly.h"
 
 #include <algorithm>
-#include <vector>
 
 using namespace mplx_detail;
 
@@ -126,12 +125,8 @@ int traverse_launch(mplx_poly *p, int32_t lanes, const mplx_traj_traverse_out *o
   return MPLX_OK;
 }
 
-// the S_k and status of the last solve, for the host twins: they decide which rows exist
-int fetch_counts(mplx_poly *p, std::vector<int32_t> *S) {
-  S->resize((size_t)p->n);
-  HIP_TRY(p->c, stage_out(p->c, S->data(), (char *)p->mem.p + p->o_S, (size_t)p->n * 4));
-  return MPLX_OK;
-}
+// the S_k of the last solve or load, for the host twins: they decide which rows exist
+StageRows::Row counts_row(mplx_poly *p, StageRows *s) { return s->landed_from((char *)p->mem.p + p->o_S, (size_t)p->n * 4); }
 
 }  // namespace
 
@@ -187,58 +182,33 @@ int mplx_solve(mplx_poly *p, const mplx_solve_in *h_in, const mplx_solve_out *h_
   int so = 0;
   if (int rc = check_in(p, "mplx_solve", h_in, h_out, &so)) return rc;
   if (h_in->n_prob == 0) return MPLX_OK;
-  MPLX_GUARD_BEGIN
   if (int rc = bind_device(c)) return rc;
   if (int rc = resolve_pending(c)) return rc;  // the arena is shared with the other host-pointer calls
   const size_t n = (size_t)h_in->n_prob, W = (size_t)h_in->w_max, D = (size_t)c->dim, F = 4 * D + 2, N = 2 * ((size_t)so + 1);
   const size_t cr = (W - 1) * N * D;  // coefficient rows
-  StageLayout l;
-  const size_t i_wp = l.add(F * W * n * 8), i_nwp = l.add(h_in->n_wp ? n * 4 : 0), i_dts = l.add(h_in->dts ? (W - 1) * n * 8 : 0),
-               i_v = l.add(h_in->v_arr ? n * 8 : 0), i_fl = l.add(h_in->wp_flags ? W * n : 0);
-  const size_t o_st = l.add(n), o_S = l.add(n * 4), o_T = l.add(n * 8), o_c = l.add(h_out->coeff ? cr * n * 8 : 0),
-               o_d = l.add(h_out->dts_out ? (W - 1) * n * 8 : 0), o_y = l.add(h_out->yaw_coeff ? 2 * (W - 1) * n * 8 : 0),
-               o_t = l.add(h_out->taus ? W * n * 8 : 0);
-  if (int rc = stage_commit(c, &l)) return rc;
+  StageRows s;
+  const auto i_wp = s.in_rows(h_in->waypoints, (size_t)h_in->wp_stride * 8, n * 8, F * W), i_nwp = s.in(h_in->n_wp, n * 4),
+             i_dts = s.in_rows(h_in->dts, (size_t)h_in->dt_stride * 8, n * 8, W - 1), i_v = s.in(h_in->v_arr, n * 8),
+             i_fl = s.in_rows(h_in->wp_flags, (size_t)h_in->flag_stride, n, W);
+  const auto o_st = s.landed(n), o_S = s.scratch(n * 4), o_T = s.landed(n * 8), o_c = s.landed(h_out->coeff, cr * n * 8),
+             o_d = s.landed(h_out->dts_out, (W - 1) * n * 8), o_y = s.landed(h_out->yaw_coeff, 2 * (W - 1) * n * 8),
+             o_t = s.landed(h_out->taus, W * n * 8), t_S = s.landed_from((char *)p->mem.p + p->o_S, n * 4);  // (S_k: 0 for a failed problem)
+  if (int rc = stage_commit(c, &s)) return rc;
   mplx_solve_in in = *h_in;
-  HIP_TRY(c, stage_in_rows(c, l.base + i_wp, h_in->waypoints, (size_t)h_in->wp_stride * 8, n * 8, F * W));
-  in.waypoints = (const double *)(l.base + i_wp); in.wp_stride = (int64_t)n;
-  if (h_in->n_wp) {
-    HIP_TRY(c, stage_in(c, l.base + i_nwp, h_in->n_wp, n * 4));
-    in.n_wp = (const int32_t *)(l.base + i_nwp);
-  }
-  if (h_in->dts) {
-    HIP_TRY(c, stage_in_rows(c, l.base + i_dts, h_in->dts, (size_t)h_in->dt_stride * 8, n * 8, W - 1));
-    in.dts = (const double *)(l.base + i_dts); in.dt_stride = (int64_t)n;
-  }
-  if (h_in->v_arr) {
-    HIP_TRY(c, stage_in(c, l.base + i_v, h_in->v_arr, n * 8));
-    in.v_arr = (const double *)(l.base + i_v);
-  }
-  if (h_in->wp_flags) {
-    HIP_TRY(c, stage_in_rows(c, l.base + i_fl, h_in->wp_flags, (size_t)h_in->flag_stride, n, W));
-    in.wp_flags = (const uint8_t *)(l.base + i_fl); in.flag_stride = (int64_t)n;
-  }
+  in.waypoints = s.dev<double>(i_wp); in.wp_stride = (int64_t)n;
+  in.n_wp = s.dev<int32_t>(i_nwp);
+  in.dts = s.dev<double>(i_dts); in.dt_stride = (int64_t)n;
+  in.v_arr = s.dev<double>(i_v);
+  in.wp_flags = s.dev<uint8_t>(i_fl); in.flag_stride = (int64_t)n;
   mplx_solve_out o{};
-  o.status = (uint8_t *)(l.base + o_st);
-  o.n_segs = (int32_t *)(l.base + o_S);
-  o.total_time = (double *)(l.base + o_T);
-  if (h_out->coeff) { o.coeff = (double *)(l.base + o_c); o.coeff_stride = (int64_t)n; }
-  if (h_out->dts_out) { o.dts_out = (double *)(l.base + o_d); o.dts_out_stride = (int64_t)n; }
-  if (h_out->yaw_coeff) { o.yaw_coeff = (double *)(l.base + o_y); o.yaw_stride = (int64_t)n; }
-  if (h_out->taus) { o.taus = (double *)(l.base + o_t); o.taus_stride = (int64_t)n; }
+  o.status = s.dev<uint8_t>(o_st); o.n_segs = s.dev<int32_t>(o_S); o.total_time = s.dev<double>(o_T);
+  o.coeff = s.dev<double>(o_c); o.dts_out = s.dev<double>(o_d); o.yaw_coeff = s.dev<double>(o_y); o.taus = s.dev<double>(o_t);
+  o.coeff_stride = o.dts_out_stride = o.yaw_stride = o.taus_stride = (int64_t)n;
   if (int rc = solve_launch(p, &in, &o, so)) return rc;
-  std::vector<uint8_t> st(n);
-  std::vector<int32_t> S(n);
-  std::vector<double> T(n), cf(h_out->coeff ? cr * n : 0), dt(h_out->dts_out ? (W - 1) * n : 0), yw(h_out->yaw_coeff ? 2 * (W - 1) * n : 0),
-      ta(h_out->taus ? W * n : 0);
-  HIP_TRY(c, stage_out(c, st.data(), o.status, n));
-  HIP_TRY(c, stage_out(c, S.data(), (char *)p->mem.p + p->o_S, n * 4));  // (0 for a failed problem)
-  HIP_TRY(c, stage_out(c, T.data(), o.total_time, n * 8));
-  HIP_TRY(c, stage_out(c, cf.empty() ? nullptr : cf.data(), o.coeff, cf.size() * 8));
-  HIP_TRY(c, stage_out(c, dt.empty() ? nullptr : dt.data(), o.dts_out, dt.size() * 8));
-  HIP_TRY(c, stage_out(c, yw.empty() ? nullptr : yw.data(), o.yaw_coeff, yw.size() * 8));
-  HIP_TRY(c, stage_out(c, ta.empty() ? nullptr : ta.data(), o.taus, ta.size() * 8));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  if (int rc = stage_fetch(c, &s)) return rc;
+  const uint8_t *st = s.host<uint8_t>(o_st);
+  const int32_t *S = s.host<int32_t>(t_S);
+  const double *T = s.host<double>(o_T), *cf = s.host<double>(o_c), *dt = s.host<double>(o_d), *yw = s.host<double>(o_y), *ta = s.host<double>(o_t);
   // a failed problem: its status only; rows past S_k keep the caller's bytes
   for (size_t k = 0; k < n; k++) {
     if (h_out->status) h_out->status[k] = st[k];
@@ -252,7 +222,6 @@ int mplx_solve(mplx_poly *p, const mplx_solve_in *h_in, const mplx_solve_out *h_
     for (size_t r = 0; r <= Sk && h_out->taus; r++) h_out->taus[(int64_t)r * h_out->taus_stride + (int64_t)k] = ta[r * n + k];
   }
   return MPLX_OK;
-  MPLX_GUARD_END(c)
 }
 
 int mplx_poly_info_device(mplx_poly *p, const mplx_traj_info_out *d_out) {
@@ -268,30 +237,25 @@ int mplx_poly_info(mplx_poly *p, const mplx_traj_info_out *h_out) {
   mplx_ctx *c = p->c;
   if (int rc = check_solved(p, "mplx_poly_info", h_out)) return rc;
   if (int rc = check_info(p, "mplx_poly_info", h_out)) return rc;
-  MPLX_GUARD_BEGIN
   if (int rc = bind_device(c)) return rc;
   if (int rc = resolve_pending(c)) return rc;
   const size_t n = (size_t)p->n, F = 4 * (size_t)c->dim + 2, W = (size_t)p->w;
-  StageLayout l;
-  const size_t o_st = l.add(n), o_T = l.add(n * 8), o_e = l.add(h_out->effort ? 5 * n * 8 : 0), o_seg = l.add(h_out->seg_state ? F * W * n * 8 : 0);
-  if (int rc = stage_commit(c, &l)) return rc;
+  StageRows s;
+  const auto o_st = s.landed(n), o_T = s.landed(n * 8), o_e = s.landed(h_out->effort, 5 * n * 8), o_seg = s.landed(h_out->seg_state, F * W * n * 8),
+             t_S = counts_row(p, &s);
+  if (int rc = stage_commit(c, &s)) return rc;
   mplx_traj_info_out o{};
-  o.status = (uint8_t *)(l.base + o_st);
-  o.total_time = (double *)(l.base + o_T);
-  o.effort = h_out->effort ? (double *)(l.base + o_e) : nullptr;
+  o.status = s.dev<uint8_t>(o_st);
+  o.total_time = s.dev<double>(o_T);
+  o.effort = s.dev<double>(o_e);
   o.effort_stride = (int64_t)n;
-  o.seg_state = h_out->seg_state ? (double *)(l.base + o_seg) : nullptr;
+  o.seg_state = s.dev<double>(o_seg);
   o.seg_stride = (int64_t)n;
   if (int rc = info_launch(p, &o)) return rc;
-  std::vector<int32_t> S;
-  std::vector<uint8_t> st(n);
-  std::vector<double> T(n), e(h_out->effort ? 5 * n : 0), seg(h_out->seg_state ? F * W * n : 0);
-  if (int rc = fetch_counts(p, &S)) return rc;
-  HIP_TRY(c, stage_out(c, st.data(), o.status, n));
-  HIP_TRY(c, stage_out(c, T.data(), o.total_time, n * 8));
-  HIP_TRY(c, stage_out(c, e.empty() ? nullptr : e.data(), o.effort, e.size() * 8));
-  HIP_TRY(c, stage_out(c, seg.empty() ? nullptr : seg.data(), o.seg_state, seg.size() * 8));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  if (int rc = stage_fetch(c, &s)) return rc;
+  const uint8_t *st = s.host<uint8_t>(o_st);
+  const int32_t *S = s.host<int32_t>(t_S);
+  const double *T = s.host<double>(o_T), *e = s.host<double>(o_e), *seg = s.host<double>(o_seg);
   for (size_t k = 0; k < n; k++) {
     if (h_out->status) h_out->status[k] = st[k];
     if (S[k] == 0) continue;
@@ -303,7 +267,6 @@ int mplx_poly_info(mplx_poly *p, const mplx_traj_info_out *h_out) {
         for (size_t w = 0; w <= (size_t)S[k]; w++) h_out->seg_state[(int64_t)(f * W + w) * h_out->seg_stride + (int64_t)k] = seg[(f * W + w) * n + k];
   }
   return MPLX_OK;
-  MPLX_GUARD_END(c)
 }
 
 int mplx_poly_sample_device(mplx_poly *p, const mplx_traj_times *d_times, const mplx_traj_sample_out *d_out) {
@@ -321,44 +284,39 @@ int mplx_poly_sample(mplx_poly *p, const mplx_traj_times *h_times, const mplx_tr
   int64_t count = 0;
   if (int rc = check_solved(p, "mplx_poly_sample", h_out)) return rc;
   if (int rc = check_times(p, "mplx_poly_sample", h_times, h_out, &count)) return rc;
-  MPLX_GUARD_BEGIN
   if (int rc = bind_device(c)) return rc;
   if (int rc = resolve_pending(c)) return rc;
   const size_t n = (size_t)p->n, cnt = (size_t)count, D = (size_t)c->dim;
   const size_t rows = h_times->form == MPLX_TRAJ_COMMAND ? 4 * D + 3 : 4 * D + 1;
   const bool own_times = h_times->n_uniform == 0;
   const size_t n_cols = own_times ? (h_times->time_stride ? n : 1) : 0;
-  StageLayout l;
-  const size_t o_t = l.add(n_cols * cnt * 8), o_st = l.add(n), o_out = l.add(h_out->out ? rows * n * cnt * 8 : 0);
-  if (int rc = stage_commit(c, &l)) return rc;
+  const size_t src_stride = (size_t)(h_times->time_stride ? h_times->time_stride : (int64_t)cnt) * 8;
+  StageRows s;
+  const auto i_t = s.in_rows(own_times ? h_times->times : nullptr, src_stride, cnt * 8, n_cols), o_st = s.out_or_scratch(h_out->status, n),
+             o_out = s.landed(h_out->out, rows * n * cnt * 8), t_S = counts_row(p, &s);
+  if (int rc = stage_commit(c, &s)) return rc;
   mplx_traj_times t = *h_times;
   if (own_times) {
-    const size_t src_stride = (size_t)(h_times->time_stride ? h_times->time_stride : (int64_t)cnt) * 8;
-    HIP_TRY(c, stage_in_rows(c, l.base + o_t, h_times->times, src_stride, cnt * 8, n_cols));
-    t.times = (const double *)(l.base + o_t);
+    t.times = s.dev<double>(i_t);
     t.time_stride = h_times->time_stride ? (int64_t)cnt : 0;
   }
   mplx_traj_sample_out o{};
-  o.out = h_out->out ? (double *)(l.base + o_out) : nullptr;
+  o.out = s.dev<double>(o_out);
   o.sample_stride = (int64_t)cnt;
   o.row_stride = (int64_t)(n * cnt);
-  o.status = (uint8_t *)(l.base + o_st);
+  o.status = s.dev<uint8_t>(o_st);
   if (int rc = sample_launch(p, &t, &o, count)) return rc;
-  std::vector<int32_t> S;
-  std::vector<double> buf(h_out->out ? rows * n * cnt : 0);
-  if (int rc = fetch_counts(p, &S)) return rc;
-  HIP_TRY(c, stage_out(c, h_out->status, o.status, n));
-  HIP_TRY(c, stage_out(c, h_out->out ? buf.data() : nullptr, o.out, buf.size() * 8));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  if (int rc = stage_fetch(c, &s)) return rc;
+  const int32_t *S = s.host<int32_t>(t_S);
+  const double *buf = s.host<double>(o_out);
   if (h_out->out)
     for (size_t r = 0; r < rows; r++)
       for (size_t k = 0; k < n; k++) {
         if (S[k] == 0) continue;  // a failed problem keeps the caller's bytes
-        std::copy(buf.begin() + (r * n + k) * cnt, buf.begin() + (r * n + k + 1) * cnt,
+        std::copy(buf + (r * n + k) * cnt, buf + (r * n + k + 1) * cnt,
                   h_out->out + (int64_t)r * h_out->row_stride + (int64_t)k * h_out->sample_stride);
       }
   return MPLX_OK;
-  MPLX_GUARD_END(c)
 }
 
 int mplx_poly_traverse_device(mplx_poly *p, int32_t lanes, const mplx_traj_traverse_out *d_out) {
@@ -377,24 +335,15 @@ int mplx_poly_traverse(mplx_poly *p, int32_t lanes, const mplx_traj_traverse_out
   if (int rc = bind_device(c)) return rc;
   if (int rc = resolve_pending(c)) return rc;
   const size_t n = (size_t)p->n;
-  StageLayout l;
-  const size_t o_st = l.add(h_out->status ? n : 0), o_cost = l.add(h_out->cost ? n * 8 : 0), o_ns = l.add(h_out->n_samples ? n * 4 : 0),
-               o_nc = l.add(h_out->n_cells ? n * 4 : 0), o_stop = l.add(h_out->stop_sample ? n * 4 : 0);
-  if (int rc = stage_commit(c, &l)) return rc;
+  StageRows s;
+  const auto o_st = s.out(h_out->status, n), o_cost = s.out(h_out->cost, n * 8), o_ns = s.out(h_out->n_samples, n * 4),
+             o_nc = s.out(h_out->n_cells, n * 4), o_stop = s.out(h_out->stop_sample, n * 4);
+  if (int rc = stage_commit(c, &s)) return rc;
   mplx_traj_traverse_out o{};
-  o.status = h_out->status ? (uint8_t *)(l.base + o_st) : nullptr;
-  o.cost = h_out->cost ? (double *)(l.base + o_cost) : nullptr;
-  o.n_samples = h_out->n_samples ? (int32_t *)(l.base + o_ns) : nullptr;
-  o.n_cells = h_out->n_cells ? (int32_t *)(l.base + o_nc) : nullptr;
-  o.stop_sample = h_out->stop_sample ? (int32_t *)(l.base + o_stop) : nullptr;
+  o.status = s.dev<uint8_t>(o_st); o.cost = s.dev<double>(o_cost); o.n_samples = s.dev<int32_t>(o_ns);
+  o.n_cells = s.dev<int32_t>(o_nc); o.stop_sample = s.dev<int32_t>(o_stop);
   if (int rc = traverse_launch(p, lanes, &o)) return rc;
-  HIP_TRY(c, stage_out(c, h_out->status, o.status, n));
-  HIP_TRY(c, stage_out(c, h_out->cost, o.cost, n * 8));
-  HIP_TRY(c, stage_out(c, h_out->n_samples, o.n_samples, n * 4));
-  HIP_TRY(c, stage_out(c, h_out->n_cells, o.n_cells, n * 4));
-  HIP_TRY(c, stage_out(c, h_out->stop_sample, o.stop_sample, n * 4));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  return MPLX_OK;
+  return stage_fetch(c, &s);
 }
 
 }  // extern "C"

@@ -380,16 +380,14 @@ static int seed_table(mplx_table *t, const char *who, const double *h_states, in
     return MPLX_OK;
   }
   const bool multi = t->Q > 1;  // (one query: every seed is query 0 and no kernel looks a query up)
-  StageLayout l;
-  const size_t o_st = l.add((size_t)t->F * (size_t)n * 8), o_g = l.add(h_g ? (size_t)n * 8 : 0), o_q = l.add(multi ? (size_t)n * 4 : 0);
-  if (int rc = stage_commit(c, &l)) return rc;
-  HIP_TRY(c, stage_in_rows(c, l.base + o_st, h_states, (size_t)stride * 8, (size_t)n * 8, (size_t)t->F));
-  if (h_g) HIP_TRY(c, stage_in(c, l.base + o_g, h_g, (size_t)n * 8));
-  if (multi) HIP_TRY(c, stage_in(c, l.base + o_q, h_query, (size_t)n * 4));
+  StageRows s;  // (no output row: read_count below is the call's read-back and synchronise)
+  const auto i_st = s.in_rows(h_states, (size_t)stride * 8, (size_t)n * 8, (size_t)t->F), i_g = s.in(h_g, (size_t)n * 8),
+             i_q = s.in(multi ? h_query : nullptr, (size_t)n * 4);
+  if (int rc = stage_commit(c, &s)) return rc;
   mplx::TableArgs a = table_args(t);
-  a.src_query = multi ? (const int32_t *)(l.base + o_q) : nullptr;
-  a.src_state = (const double *)(l.base + o_st); a.src_sstride = n;
-  a.n_rows = n; a.S = 1; a.parent_g = h_g ? (const double *)(l.base + o_g) : nullptr; a.g_max = INFINITY;
+  a.src_query = s.dev<int32_t>(i_q);
+  a.src_state = s.dev<double>(i_st); a.src_sstride = n;
+  a.n_rows = n; a.S = 1; a.parent_g = s.dev<double>(i_g); a.g_max = INFINITY;
   void *hashes = nullptr;
   if (int rc = run_passes(t, &a, d_frontier, (size_t)n * 8, &hashes)) return rc;
   a.src_hash = (const uint64_t *)hashes;
@@ -438,15 +436,11 @@ static int find_host(mplx_table *t, const char *who, const uint64_t *h_hash, con
   if (n == 0) return MPLX_OK;
   if (int rc = bind_device(c)) return rc;
   if (int rc = resolve_pending(c)) return rc;
-  StageLayout l;
-  const size_t o_h = l.add((size_t)n * 8), o_id = l.add((size_t)n * 4), o_q = l.add(h_query ? (size_t)n * 4 : 0);
-  if (int rc = stage_commit(c, &l)) return rc;
-  HIP_TRY(c, stage_in(c, l.base + o_h, h_hash, (size_t)n * 8));
-  if (h_query) HIP_TRY(c, stage_in(c, l.base + o_q, h_query, (size_t)n * 4));
-  HIP_TRY(c, mplx::launch_table_find(table_args(t), (const uint64_t *)(l.base + o_h), h_query ? (const int32_t *)(l.base + o_q) : nullptr, n,
-                                     (int32_t *)(l.base + o_id), c->stream));
-  HIP_TRY(c, stage_out(c, h_id, l.base + o_id, (size_t)n * 4));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  StageRows s;
+  const auto i_h = s.in(h_hash, (size_t)n * 8), o_id = s.out(h_id, (size_t)n * 4), i_q = s.in(h_query, (size_t)n * 4);
+  if (int rc = stage_commit(c, &s)) return rc;
+  HIP_TRY(c, mplx::launch_table_find(table_args(t), s.dev<uint64_t>(i_h), s.dev<int32_t>(i_q), n, s.dev<int32_t>(o_id), c->stream));
+  if (int rc = stage_fetch(c, &s)) return rc;
   observe(t);
   return MPLX_OK;
 }

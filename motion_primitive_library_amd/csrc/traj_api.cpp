@@ -6,7 +6,6 @@
 
 #include <algorithm>
 #include <cmath>
-#include <vector>
 
 using namespace mplx_detail;
 
@@ -110,35 +109,23 @@ int traverse_launch(mplx_ctx *c, const mplx_traj_set *s, int32_t lanes, const mp
   return MPLX_OK;
 }
 
-// Host set -> the arena: set_rows lays out starts [F][n_starts] and actions [H][n]; stage_set copies them: the device view.
-struct SetRows { size_t starts, actions; };
-SetRows set_rows(const mplx_ctx *c, const mplx_traj_set *s, StageLayout *l) {
-  const size_t o_starts = l->add((4 * (size_t)c->dim + 2) * (size_t)s->n_starts * 8);
-  return {o_starts, l->add((size_t)s->horizon * (size_t)s->n_traj * 4)};
-}
-int stage_set(mplx_ctx *c, const mplx_traj_set *s, const StageLayout &l, const SetRows &r, mplx_traj_set *d) {
-  const size_t F = 4 * (size_t)c->dim + 2, n = (size_t)s->n_traj, ns = (size_t)s->n_starts;
-  HIP_TRY(c, stage_in_rows(c, l.base + r.starts, s->starts, (size_t)s->start_stride * 8, ns * 8, F));
-  HIP_TRY(c, stage_in_rows(c, l.base + r.actions, s->actions, (size_t)s->action_stride * 4, n * 4, (size_t)s->horizon));
-  *d = *s;
-  d->starts = (const double *)(l.base + r.starts); d->start_stride = s->n_starts;
-  d->actions = (const int32_t *)(l.base + r.actions); d->action_stride = s->n_traj;
-  return MPLX_OK;
-}
-
 }  // namespace
 
 namespace mplx_detail {
 
 int traj_check_set(mplx_ctx *c, const char *who, const mplx_traj_set *s, const void *out) { return check_set(c, who, s, out); }
 int traj_build_table(mplx_ctx *c, const mplx_traj_set *s, mplx::TrajArgs *out) { return build(c, s, nullptr, out); }
-void traj_set_rows(const mplx_ctx *c, const mplx_traj_set *s, StageLayout *l, size_t *starts, size_t *actions) {
-  const SetRows r = set_rows(c, s, l);
-  *starts = r.starts;
-  *actions = r.actions;
+// Host set -> the arena: starts [F][n_starts] and actions [H][n] packed; after the commit, the device view of the set
+TrajSetRows traj_set_rows(const mplx_ctx *c, const mplx_traj_set *s, StageRows *st) {
+  const size_t F = 4 * (size_t)c->dim + 2, n = (size_t)s->n_traj, ns = (size_t)s->n_starts;
+  const auto starts = st->in_rows(s->starts, (size_t)s->start_stride * 8, ns * 8, F);
+  return {starts, st->in_rows(s->actions, (size_t)s->action_stride * 4, n * 4, (size_t)s->horizon)};
 }
-int traj_stage_set(mplx_ctx *c, const mplx_traj_set *s, const StageLayout &l, size_t starts, size_t actions, mplx_traj_set *d) {
-  return stage_set(c, s, l, SetRows{starts, actions}, d);
+mplx_traj_set traj_set_view(const mplx_traj_set *s, const StageRows &st, const TrajSetRows &r) {
+  mplx_traj_set d = *s;
+  d.starts = st.dev<double>(r.starts); d.start_stride = s->n_starts;
+  d.actions = st.dev<int32_t>(r.actions); d.action_stride = s->n_traj;
+  return d;
 }
 
 }  // namespace mplx_detail
@@ -160,43 +147,35 @@ int mplx_traj_info(mplx_ctx *c, const mplx_traj_set *h_set, const mplx_traj_info
   if (int rc = check_set(c, "mplx_traj_info", h_set, h_out)) return rc;
   if (int rc = check_info(c, "mplx_traj_info", h_set, h_out)) return rc;
   if (h_set->n_traj == 0) return MPLX_OK;
-  MPLX_GUARD_BEGIN
   if (int rc = bind_device(c)) return rc;
   if (int rc = resolve_pending(c)) return rc;  // the arena is shared with the other host-pointer calls
   const size_t n = (size_t)h_set->n_traj, F = 4 * (size_t)c->dim + 2, H1 = (size_t)h_set->horizon + 1;
-  StageLayout l;
-  const SetRows in = set_rows(c, h_set, &l);
-  const size_t o_st = l.add(n), o_S = l.add(n * 4), o_T = l.add(n * 8), o_e = l.add(h_out->effort ? 5 * n * 8 : 0),
-               o_seg = l.add(h_out->seg_state ? F * H1 * n * 8 : 0);
-  if (int rc = stage_commit(c, &l)) return rc;
-  mplx_traj_set d;
-  if (int rc = stage_set(c, h_set, l, in, &d)) return rc;
+  StageRows st;
+  const TrajSetRows in = traj_set_rows(c, h_set, &st);
+  const auto o_st = st.out_or_scratch(h_out->status, n), o_S = st.landed(n * 4), o_T = st.out_or_scratch(h_out->total_time, n * 8),
+             o_e = st.out_rows(h_out->effort, (size_t)h_out->effort_stride * 8, n * 8, 5), o_seg = st.landed(h_out->seg_state, F * H1 * n * 8);
+  if (int rc = stage_commit(c, &st)) return rc;
+  const mplx_traj_set d = traj_set_view(h_set, st, in);
   mplx_traj_info_out o{};
-  o.status = (uint8_t *)(l.base + o_st);
-  o.n_segs = (int32_t *)(l.base + o_S);
-  o.total_time = (double *)(l.base + o_T);
-  o.effort = h_out->effort ? (double *)(l.base + o_e) : nullptr;
+  o.status = st.dev<uint8_t>(o_st);
+  o.n_segs = st.dev<int32_t>(o_S);
+  o.total_time = st.dev<double>(o_T);
+  o.effort = st.dev<double>(o_e);
   o.effort_stride = (int64_t)n;
-  o.seg_state = h_out->seg_state ? (double *)(l.base + o_seg) : nullptr;
+  o.seg_state = st.dev<double>(o_seg);
   o.seg_stride = (int64_t)n;
   mplx::TrajArgs a;
   if (int rc = build(c, &d, &o, &a)) return rc;
-  std::vector<int32_t> S(n);
-  std::vector<double> seg(h_out->seg_state ? F * H1 * n : 0);
-  HIP_TRY(c, stage_out(c, S.data(), o.n_segs, n * 4));
-  HIP_TRY(c, stage_out(c, h_out->status, o.status, n));
-  HIP_TRY(c, stage_out(c, h_out->total_time, o.total_time, n * 8));
-  HIP_TRY(c, stage_out_rows(c, h_out->effort, (size_t)h_out->effort_stride * 8, o.effort, n * 8, 5));
-  HIP_TRY(c, stage_out(c, h_out->seg_state ? seg.data() : nullptr, o.seg_state, seg.size() * 8));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  if (h_out->n_segs) std::copy(S.begin(), S.end(), h_out->n_segs);
+  if (int rc = stage_fetch(c, &st)) return rc;
+  const int32_t *S = st.host<int32_t>(o_S);
+  const double *seg = st.host<double>(o_seg);
+  if (h_out->n_segs) std::copy(S, S + n, h_out->n_segs);
   if (h_out->seg_state)  // states past S_k keep the caller's bytes
     for (size_t f = 0; f < F; f++)
       for (size_t s = 0; s < H1; s++)
         for (size_t k = 0; k < n; k++)
           if ((int64_t)s <= (int64_t)S[k]) h_out->seg_state[(int64_t)(f * H1 + s) * h_out->seg_stride + (int64_t)k] = seg[(f * H1 + s) * n + k];
   return MPLX_OK;
-  MPLX_GUARD_END(c)
 }
 
 int mplx_traj_sample_device(mplx_ctx *c, const mplx_traj_set *d_set, const mplx_traj_times *d_times, const mplx_traj_sample_out *d_out) {
@@ -215,48 +194,42 @@ int mplx_traj_sample(mplx_ctx *c, const mplx_traj_set *h_set, const mplx_traj_ti
   if (int rc = check_set(c, "mplx_traj_sample", h_set, h_out)) return rc;
   if (int rc = check_times(c, "mplx_traj_sample", h_set, h_times, h_out, &count)) return rc;
   if (h_set->n_traj == 0) return MPLX_OK;
-  MPLX_GUARD_BEGIN
   if (int rc = bind_device(c)) return rc;
   if (int rc = resolve_pending(c)) return rc;
   const size_t n = (size_t)h_set->n_traj, cnt = (size_t)count, D = (size_t)c->dim;
   const size_t rows = h_times->form == MPLX_TRAJ_COMMAND ? 4 * D + 3 : 4 * D + 1;
   const bool own_times = h_times->n_uniform == 0;
   const size_t n_cols = own_times ? (h_times->time_stride ? n : 1) : 0;
-  StageLayout l;
-  const SetRows in = set_rows(c, h_set, &l);
-  const size_t o_t = l.add(n_cols * cnt * 8), o_st = l.add(n), o_S = l.add(n * 4), o_out = l.add(h_out->out ? rows * n * cnt * 8 : 0);
-  if (int rc = stage_commit(c, &l)) return rc;
-  mplx_traj_set d;
-  if (int rc = stage_set(c, h_set, l, in, &d)) return rc;
+  const size_t src_stride = (size_t)(h_times->time_stride ? h_times->time_stride : (int64_t)cnt) * 8;
+  StageRows st;
+  const TrajSetRows in = traj_set_rows(c, h_set, &st);
+  // the segment counts decide which samples exist: EMPTY trajectories keep the caller's bytes
+  const auto i_t = st.in_rows(own_times ? h_times->times : nullptr, src_stride, cnt * 8, n_cols), o_st = st.out_or_scratch(h_out->status, n),
+             o_S = st.landed(n * 4), o_out = st.landed(h_out->out, rows * n * cnt * 8);
+  if (int rc = stage_commit(c, &st)) return rc;
+  const mplx_traj_set d = traj_set_view(h_set, st, in);
   mplx_traj_times t = *h_times;
   if (own_times) {
-    const size_t src_stride = (size_t)(h_times->time_stride ? h_times->time_stride : (int64_t)cnt) * 8;
-    HIP_TRY(c, stage_in_rows(c, l.base + o_t, h_times->times, src_stride, cnt * 8, n_cols));
-    t.times = (const double *)(l.base + o_t);
+    t.times = st.dev<double>(i_t);
     t.time_stride = h_times->time_stride ? (int64_t)cnt : 0;
   }
   mplx_traj_sample_out o{};
-  o.out = h_out->out ? (double *)(l.base + o_out) : nullptr;
+  o.out = st.dev<double>(o_out);
   o.sample_stride = (int64_t)cnt;
   o.row_stride = (int64_t)(n * cnt);
-  o.status = (uint8_t *)(l.base + o_st);
-  // the segment counts decide which samples exist: EMPTY trajectories keep the caller's bytes
-  if (int rc = sample_launch(c, &d, &t, &o, count, (int32_t *)(l.base + o_S))) return rc;
-  std::vector<int32_t> S(n);
-  std::vector<double> buf(h_out->out ? rows * n * cnt : 0);
-  HIP_TRY(c, stage_out(c, S.data(), l.base + o_S, n * 4));
-  HIP_TRY(c, stage_out(c, h_out->status, o.status, n));
-  HIP_TRY(c, stage_out(c, h_out->out ? buf.data() : nullptr, o.out, buf.size() * 8));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  o.status = st.dev<uint8_t>(o_st);
+  if (int rc = sample_launch(c, &d, &t, &o, count, st.dev<int32_t>(o_S))) return rc;
+  if (int rc = stage_fetch(c, &st)) return rc;
+  const int32_t *S = st.host<int32_t>(o_S);
+  const double *buf = st.host<double>(o_out);
   if (h_out->out)
     for (size_t r = 0; r < rows; r++)
       for (size_t k = 0; k < n; k++) {
         if (S[k] == 0) continue;
-        std::copy(buf.begin() + (r * n + k) * cnt, buf.begin() + (r * n + k + 1) * cnt,
+        std::copy(buf + (r * n + k) * cnt, buf + (r * n + k + 1) * cnt,
                   h_out->out + (int64_t)r * h_out->row_stride + (int64_t)k * h_out->sample_stride);
       }
   return MPLX_OK;
-  MPLX_GUARD_END(c)
 }
 
 int mplx_traj_traverse_device(mplx_ctx *c, const mplx_traj_set *d_set, int32_t lanes, const mplx_traj_traverse_out *d_out) {
@@ -276,27 +249,17 @@ int mplx_traj_traverse(mplx_ctx *c, const mplx_traj_set *h_set, int32_t lanes, c
   if (int rc = bind_device(c)) return rc;
   if (int rc = resolve_pending(c)) return rc;
   const size_t n = (size_t)h_set->n_traj;
-  StageLayout l;
-  const SetRows in = set_rows(c, h_set, &l);
-  const size_t o_st = l.add(h_out->status ? n : 0), o_cost = l.add(h_out->cost ? n * 8 : 0), o_ns = l.add(h_out->n_samples ? n * 4 : 0),
-               o_nc = l.add(h_out->n_cells ? n * 4 : 0), o_stop = l.add(h_out->stop_sample ? n * 4 : 0);
-  if (int rc = stage_commit(c, &l)) return rc;
-  mplx_traj_set d;
-  if (int rc = stage_set(c, h_set, l, in, &d)) return rc;
+  StageRows st;
+  const TrajSetRows in = traj_set_rows(c, h_set, &st);
+  const auto o_st = st.out(h_out->status, n), o_cost = st.out(h_out->cost, n * 8), o_ns = st.out(h_out->n_samples, n * 4),
+             o_nc = st.out(h_out->n_cells, n * 4), o_stop = st.out(h_out->stop_sample, n * 4);
+  if (int rc = stage_commit(c, &st)) return rc;
+  const mplx_traj_set d = traj_set_view(h_set, st, in);
   mplx_traj_traverse_out o{};
-  o.status = h_out->status ? (uint8_t *)(l.base + o_st) : nullptr;
-  o.cost = h_out->cost ? (double *)(l.base + o_cost) : nullptr;
-  o.n_samples = h_out->n_samples ? (int32_t *)(l.base + o_ns) : nullptr;
-  o.n_cells = h_out->n_cells ? (int32_t *)(l.base + o_nc) : nullptr;
-  o.stop_sample = h_out->stop_sample ? (int32_t *)(l.base + o_stop) : nullptr;
+  o.status = st.dev<uint8_t>(o_st); o.cost = st.dev<double>(o_cost); o.n_samples = st.dev<int32_t>(o_ns);
+  o.n_cells = st.dev<int32_t>(o_nc); o.stop_sample = st.dev<int32_t>(o_stop);
   if (int rc = traverse_launch(c, &d, lanes, &o)) return rc;
-  HIP_TRY(c, stage_out(c, h_out->status, o.status, n));
-  HIP_TRY(c, stage_out(c, h_out->cost, o.cost, n * 8));
-  HIP_TRY(c, stage_out(c, h_out->n_samples, o.n_samples, n * 4));
-  HIP_TRY(c, stage_out(c, h_out->n_cells, o.n_cells, n * 4));
-  HIP_TRY(c, stage_out(c, h_out->stop_sample, o.stop_sample, n * 4));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  return MPLX_OK;
+  return stage_fetch(c, &st);
 }
 
 }  // extern "C"

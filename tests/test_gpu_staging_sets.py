@@ -26,6 +26,14 @@ device rows and returns the same bytes wherever both forms define them (twin_def
 the loader, info, samples, limits, Lambda builds and tau scatter only the defined entries of a problem, mplx_solve.h "A
 problem with any bit writes its status only"; traverse, conflicts and shortcut copy whole rows).
 
+The two timed twins of mplx_reserve_poly.h walk along (reserve_check_poly, shortcut_timed).  Their reservation table
+lives as long as the context; a step fills it with mplx_reserve_fill_poly from a second set (poly `b`: this step's set
+again, through the same setter) and sets one query per problem with mplx_reserve_set_queries.  The clocks decide what a
+check finds, whatever the trajectories are: a problem on its twin's clock is hit, one that starts when every
+reservation is gone is clear, one that starts at the table's last instant is past the horizon; a test without a GPU
+shows the three values with tests/reserve_poly_model.py.  Variants by visit: radius, ignore_group, each of hit /
+status / n_hit given or not (n_hit is added to: both contexts start it from the poison); h_chain_hit null or not.
+
 Sizes, order and poison: as tests/test_gpu_staging.py says.  Two kinds of that walk, expand_lists and ray_trace, are in
 this kind list unchanged, so every new kind runs directly after and directly before an old one at its largest size."""
 import ctypes as C
@@ -37,6 +45,7 @@ import re
 import numpy as np
 import pytest
 
+import reserve_poly_model as RPM
 import staging_walk as SW
 import test_gpu_staging as OLD
 from staging_walk import SIZES, assert_same_bytes, fill, poisoned, ptr, raw
@@ -46,18 +55,24 @@ W_MAX, W = 5, 4   # waypoints per problem: w_max leaves one unused
 N_UNIFORM, Q_TIMES = 4, 3
 N_INSTANTS, STEP = 40, 0.12
 MAX_HOP = 2
+R_STEP, R_STEPS = 0.25, 96   # the reservation tables: 23.75 s of clock, past every trajectory started in its first 12 s
+T_CLEAR = 12.0               # ... and at this t_start every reservation (t0 <= 1 s, at most 4 segments) is GONE
 OLD_KINDS = ("expand_lists", "ray_trace")
 NEW_KINDS = ("scale", "solve", "poly_load", "poly_info", "poly_sample", "poly_traverse", "poly_limits", "shortcut", "set_lambda",
-             "scale_down", "poly_tau", "poly_conflicts")
+             "scale_down", "poly_tau", "poly_conflicts", "reserve_check_poly", "shortcut_timed")
 # `scale` first in one configuration: its first step (visit 0, the 00 form) then commits zero bytes on an empty arena
 KINDS = {"2d_acc_yaw": NEW_KINDS[:6] + OLD_KINDS[:1] + NEW_KINDS[6:] + OLD_KINDS[1:],
          "3d_acc": NEW_KINDS[1:7] + OLD_KINDS[1:] + NEW_KINDS[7:] + NEW_KINDS[:1] + OLD_KINDS[:1]}
-READS = ("poly_info", "poly_sample", "poly_traverse", "poly_limits", "set_lambda", "scale", "scale_down", "poly_tau", "poly_conflicts")
+READS = ("poly_info", "poly_sample", "poly_traverse", "poly_limits", "set_lambda", "scale", "scale_down", "poly_tau", "poly_conflicts",
+         "reserve_check_poly")
+TIMED = ("reserve_check_poly", "shortcut_timed")  # kinds with a reservation table, filled from the second set (poly `b`)
 ENTRY_POINTS = {"solve": ("mplx_solve",), "poly_load": ("mplx_poly_load",), "poly_info": ("mplx_poly_info",),
                 "poly_sample": ("mplx_poly_sample",), "poly_traverse": ("mplx_poly_traverse",), "poly_limits": ("mplx_poly_limits",),
                 "shortcut": ("mplx_shortcut",), "set_lambda": ("mplx_poly_set_lambda",), "scale": ("mplx_poly_scale",),
-                "scale_down": (), "poly_tau": ("mplx_poly_tau",), "poly_conflicts": ("mplx_poly_conflicts",)}
+                "scale_down": ("mplx_poly_scale_down",), "poly_tau": ("mplx_poly_tau",), "poly_conflicts": ("mplx_poly_conflicts",),
+                "reserve_check_poly": ("mplx_reserve_check_poly",), "shortcut_timed": ("mplx_shortcut_timed",)}
 EMPTY, BAD_TIME, BAD_CHAIN, BAD_INPUT = 1, 2, 16, 128
+CHECK_ROWS = ((1, 1, 1), (0, 1, 1), (1, 0, 1), (1, 1, 0), (0, 0, 0))  # hit, status, n_hit asked for
 CONFLICT_VARIANTS = ((1, 1, 1, 1), (0, 1, 1, 1), (1, 0, 1, 1), (1, 1, 0, 1), (1, 1, 1, 0), (0, 0, 0, 0))  # t0, radius, group, rank
 
 
@@ -101,6 +116,10 @@ def variant(kind, visit):
         return visit % 4, (visit // 4) % 2                               # ramps: none / ri / rf / both; mode
     if kind == "poly_conflicts":
         return CONFLICT_VARIANTS[visit % 6], visit % 2, (0, 7)[(visit // 2) % 2], visit % 2 == 1   # rows, mode, chunk, pair_stride > K
+    if kind == "reserve_check_poly":
+        return visit % 2 == 0, (visit // 2) % 2 == 0, CHECK_ROWS[visit % 5]   # radius given, ignore_group given, rows
+    if kind == "shortcut_timed":
+        return visit % 2 == 1, (visit // 2) % 2 == 0                          # a stride above n, h_chain_hit given
     return ()
 
 
@@ -127,6 +146,9 @@ def test_the_order_runs_every_kind_at_every_size(config):
     assert reached["scale_down"] == {(r, m) for r in range(4) for m in (0, 1)}
     assert {v[0] for v in reached["poly_conflicts"]} == set(CONFLICT_VARIANTS)
     assert {v[1:] for v in reached["poly_conflicts"]} >= {(m, c, m == 1) for m in (0, 1) for c in (0, 7)}
+    assert {v[:2] for v in reached["reserve_check_poly"]} == {(r, g) for r in (False, True) for g in (False, True)}
+    assert {v[2] for v in reached["reserve_check_poly"]} == set(CHECK_ROWS)
+    assert reached["shortcut_timed"] == {(s, h) for s in (False, True) for h in (False, True)}
     for kind in READS:  # both setters, and the calls of another kind between setter and call
         visits = [visit for k, _, visit in steps if k == kind]
         assert {setter_of(kind, v) for v in visits} >= {"solve", "poly_load"}, kind
@@ -167,9 +189,55 @@ def test_every_step_has_solved_and_failed_problems(config):
                 assert name == "gather" or (st & (BAD_CHAIN if name == "shortcut" else BAD_TIME)).any(), (i, kind, name)
 
 
+def standin_positions(x):
+    """A position function [D] of (problem, local time): the waypoints of the step joined by straight lines.  It stands
+    in for the trajectories of BOTH sets in the model below: the condition on the inputs must not depend on how a
+    solved or loaded trajectory runs between its ends, only on who shares a clock with whom."""
+    pos, tau = x["wp_pos"], x["wp_tau"]   # [D][W_MAX][n], [W_MAX][n]
+
+    def at(k, tl):
+        return np.array([np.interp(tl, tau[:, k], pos[d, :, k]) for d in range(pos.shape[0])])
+    return at
+
+
+def model_hits(x, n):
+    """(hit, status, n_hit) of tests/reserve_poly_model.py for the inputs of a reserve_check_poly step: the table of the
+    second set as include/mplx_reserve.h fills it in mode GONE, on the stand-in positions."""
+    at, ok, total = standin_positions(x), x["predicted"][x["setter"]] == 0, x["total"]
+    tl = np.arange(R_STEPS)[:, None] * np.float64(R_STEP) - x["res_t0"][None, :]            # [n_steps][B]
+    active = ok[None, :] & (tl >= 0) & (tl <= total[None, :])
+    pos = np.zeros((R_STEPS, x["wp_pos"].shape[0], n))
+    for i, b in zip(*np.nonzero(active)):
+        pos[i, :, b] = at(b, tl[i, b])
+    table = {"pos": pos, "active": active, "included": ok, "radius": x["res_radius"], "group": x["group"]}
+    use_r, use_g, _ = variant("reserve_check_poly", x["visit"])
+    return RPM.check(x["predicted"][x["setter"]], np.where(ok, 1, 0), total, x["t_start"], x["c_radius"] if use_r else x["radius_all"],
+                     x["c_ignore"] if use_g else None, R_STEP, table, lambda k, i, t: at(k, t))
+
+
+@pytest.mark.parametrize("config", sorted(KINDS))
+def test_every_check_step_has_hits_clear_problems_and_problems_past_the_horizon(config):
+    """The hits tests/reserve_poly_model.py gives the inputs of every reserve_check_poly step, without a device: at
+    n >= 65 a real hit (>= 0), clear (-1) and past the horizon (-2) are all present, at least 10 % of the problems are
+    clear and at least 10 % are hit.  A hit is a problem on the clock of its own twin in the second set (distance 0,
+    whatever the trajectory), a clear one starts at T_CLEAR, when every reservation is GONE, and one past the horizon
+    starts at the table's last instant."""
+    w = World(config)
+    seen = 0
+    for i, (kind, n, visit) in enumerate(schedule(config)):
+        if kind != "reserve_check_poly" or n < 65:
+            continue
+        x = w.inputs(i, kind, n, visit)
+        hit, status, n_hit = model_hits(x, n)
+        assert (hit >= 0).mean() >= 0.1 and (hit == RPM.NO_HIT).mean() >= 0.1 and (hit == RPM.HORIZON).any(), (i, n, visit)
+        assert n_hit == int((hit != RPM.NO_HIT).sum()) and (status & BAD_INPUT).any(), (i, n, visit)
+        seen += 1
+    assert seen >= 3
+
+
 # file-local helpers that reach stage_commit -> the public entry points that call them
 HELPERS = {"seed_table": ("mplx_table_seed", "mplx_table_seed_multi"), "find_host": ("mplx_table_find", "mplx_table_find_multi"),
-           "expand_lists_packed": ("mplx_planner_plan",)}
+           "expand_lists_packed": ("mplx_planner_plan",), "shortcut_host": ("mplx_shortcut", "mplx_shortcut_timed")}
 # ... and the one that no walk runs: the planner stages its frontiers through the context it is attached to inside its own
 # search loop (tests/test_gpu_plan.py pins it against the reference planner), not as a call a walk can place
 NOT_WALKED = {"mplx_planner_plan"}
@@ -208,8 +276,8 @@ def staging_sites():
 
 def test_every_host_pointer_call_that_stages_is_in_a_walk():
     import test_gpu_staging_search as SEARCH
-    sites, occurrences = staging_sites()  # (32 sites in 16 files when this test was written, mplx_rollout twice)
-    assert len(sites) == occurrences >= 32 and sites.count(("rollout_api.cpp", "mplx_rollout")) == 2, (occurrences, sites)
+    sites, occurrences = staging_sites()  # (34 sites in 17 files, mplx_rollout twice, both shortcuts in shortcut_host)
+    assert len(sites) == occurrences >= 34 and sites.count(("rollout_api.cpp", "mplx_rollout")) == 2, (occurrences, sites)
     found = set()
     for _, fn in sites:
         assert fn.startswith("mplx_") or fn in HELPERS, "%s reaches stage_commit: name its public callers in HELPERS" % fn
@@ -232,7 +300,7 @@ class World(OLD.World):
             return OLD.World.inputs(self, i, kind, n, visit)
         rng = np.random.default_rng(SEED + i)
         D, F, ext, k = self.dim, self.F, self.extent(), np.arange(n)
-        x = {"setter": setter_of(kind, visit) if kind in READS else None, "predicted": {}, "visit": visit}
+        x = {"setter": setter_of(kind, visit) if kind in READS + TIMED else None, "predicted": {}, "visit": visit}
         wide = visit % 2 == 1                                            # the strides of the inputs: above n
         sv = solve_variant(visit)
         if kind == "poly_load":
@@ -295,7 +363,7 @@ class World(OLD.World):
             src_ok = predicted_status(src_S, dts[:1]) == 0
             good = (idx[:, :n] >= 0) & (idx[:, :n] < n) & src_ok[np.clip(idx[:, :n], 0, n - 1)]
             x["predicted"]["gather"] = np.where(used[0] & (~used | good).all(axis=0), 0, EMPTY).astype(np.uint8)
-        if kind == "shortcut":
+        if kind in ("shortcut", "shortcut_timed"):
             t = wp[4 * D + 1, :, :n]
             chain_bad = (np.diff(t, axis=0) <= 0) & (np.arange(W_MAX - 1)[:, None] < S[None, :])
             x["predicted"]["shortcut"] = np.where(S < 1, EMPTY, np.where(chain_bad.any(axis=0), BAD_CHAIN, 0)).astype(np.uint8)
@@ -323,6 +391,24 @@ class World(OLD.World):
         if kind == "poly_conflicts":  # a t0 that is not finite / a negative radius, where the row is given at all
             ut, ur = variant(kind, visit)[0][:2]
             x["bad_input"] = bool((ut and (k % 17 == 5).any()) or (ur and (k % 17 == 11).any()))
+        if kind in TIMED:
+            # -- the second set is this step's set again (poly `b`, the same setter): reservation b is the twin of problem b,
+            # on the clock res_t0.  A problem on its twin's clock is hit, one that starts at T_CLEAR finds every reservation
+            # GONE, one that starts at the table's last instant leaves the horizon.
+            res_t0 = rng.uniform(0.0, 1.0, size=n)
+            t_start = np.where(k % 3 == 0, res_t0, np.where(k % 3 == 1, T_CLEAR, (R_STEPS - 1) * R_STEP))
+            t_start[k % 17 == 5] = np.nan                                # MPLX_CONFLICT_BAD_INPUT
+            c_radius = rng.uniform(0.5, 1.5, size=n) * r0
+            c_radius[k % 17 == 11] = -1.0                                # ... where the row is given
+            used = dts if (x["setter"] == "poly_load" or sv[1]) else alloc
+            with np.errstate(invalid="ignore"):
+                dur = np.where(np.arange(W_MAX - 1)[:, None] < S[None, :], np.where(np.isfinite(used) & (used > 0), used, 0.0), 0.0)
+            x.update(res_t0=res_t0, res_radius=rng.uniform(0.5, 1.5, size=n) * r0, t_start=t_start, c_radius=c_radius,
+                     c_ignore=((k + 1) % 5).astype(np.int32), total=dur.sum(axis=0), wp_pos=pos,
+                     wp_tau=np.concatenate([np.zeros((1, n)), np.cumsum(dur, axis=0)]),
+                     q_t0=rng.uniform(0.0, 1.0, size=n), q_ignore=(k % 7 - 1).astype(np.int32),
+                     # (every fourth query as wide as the map: its chain is hit while any reservation is there; an EMPTY chain never is)
+                     q_radius=np.where(k % 4 == 0, 10.0, rng.uniform(0.5, 1.5, size=n) * r0))
         return x
 
 
@@ -343,15 +429,20 @@ class Polys:
         want = {"a": (k_cap, W_MAX)}
         if kind in (None, "poly_load"):
             want["src"] = (k_cap, 2 if kind else W_MAX)
-        if kind in (None, "shortcut"):
+        if kind in (None, "shortcut", "shortcut_timed"):
             want["pairs"], want["result"] = (k_cap * (W_MAX - 1) * MAX_HOP, 2), (k_cap, W_MAX)
+        if kind in (None,) + TIMED:
+            want["b"] = (k_cap, W_MAX)
         for name, (cap, w_max) in want.items():
             self.h[name] = SW.handle(abi, env._ctx, L.mplx_poly_create, env._ctx, cap, w_max)
+        self.table = SW.handle(abi, env._ctx, L.mplx_reserve_create, env._ctx) if kind in (None,) + TIMED else None
 
     def free(self):
         for h in self.h.values():
             self.abi.lib().mplx_poly_destroy(h)
-        self.h = {}
+        if self.table is not None:
+            self.abi.lib().mplx_reserve_destroy(self.table)
+        self.h, self.table = {}, None
 
 
 # ---- the rows a call is asked for: name -> (dtype, shape)
@@ -383,9 +474,15 @@ def out_spec(w, kind, n, visit, x):
         if variant(kind, visit)[0]:
             s.update(max_vel=("<f8", (D, n)), max_acc=("<f8", (D, n)), max_jrk=("<f8", (D, n)), exceed=("u1", (n,)), first_bad=("<i4", (n,)))
         return s
-    if kind == "shortcut":
-        return {"status": ("u1", (n,)), "n_keep": ("<i4", (n,)), "keep": ("<i4", (W_MAX, x["stride"])), "cost": ("<f8", (n,)),
-                "chain_cost": ("<f8", (n,)), "edge_cost": ("<f8", (n, W_MAX - 1, MAX_HOP))}
+    if kind in ("shortcut", "shortcut_timed"):
+        s = {"status": ("u1", (n,)), "n_keep": ("<i4", (n,)), "keep": ("<i4", (W_MAX, x["stride"])), "cost": ("<f8", (n,)),
+             "chain_cost": ("<f8", (n,)), "edge_cost": ("<f8", (n, W_MAX - 1, MAX_HOP))}
+        if kind == "shortcut_timed" and variant(kind, visit)[1]:
+            s["chain_hit"] = ("<i8", (n,))
+        return s
+    if kind == "reserve_check_poly":
+        rows = variant(kind, visit)[2]
+        return {k: v for k, v, asked in (("hit", ("<i8", (n,)), rows[0]), ("status", ("u1", (n,)), rows[1]), ("n_hit", ("<i8", (1,)), rows[2])) if asked}
     if kind in ("set_lambda", "scale"):
         return lambda_rows(n)
     if kind == "scale_down":
@@ -416,10 +513,10 @@ def lambda_out(abi, P, n):
     return fill(abi.LambdaOut(), {k: P.get(k) for k in ("status", "n_lseg", "total", "Ts", "segs")}, ts_stride=n, seg_stride=n)
 
 
-def call(abi, polys, w, kind, n, visit, x, P, I, sfx=""):
+def call(abi, polys, w, kind, n, visit, x, P, I, sfx="", poly="a"):
     """One call through the C ABI: P names the output rows, I the inputs (host addresses, or device addresses for the
     _device form; src_index is device memory in both)."""
-    L, ctx, a = abi.lib(), polys.env._ctx, polys.h["a"]
+    L, ctx, a = abi.lib(), polys.env._ctx, polys.h[poly]
     stride = x["stride"]
     if kind in ("solve", "solve_device"):
         _, given, flagged, _ = solve_variant(visit)
@@ -458,6 +555,19 @@ def call(abi, polys, w, kind, n, visit, x, P, I, sfx=""):
         i = fill(abi.ShortcutIn(), {}, states=I["wp"], n_query=n, w_max=W_MAX, control=w.control, stride=stride, n_wp=I["n_wp"], max_hop=MAX_HOP)
         o = fill(abi.ShortcutOut(), P, keep_stride=stride)
         rc = getattr(L, "mplx_shortcut" + sfx)(polys.h["pairs"], polys.h["result"], C.byref(i), C.byref(o))
+    elif kind == "fill_table":  # the reservation table of the step from the second set, then one query per problem
+        i = fill(abi.ConflictIn(), {}, step=R_STEP, n_steps=R_STEPS, mode=1, t0=I["res_t0"], radius=I["res_radius"], group=I["group"])
+        abi.check(ctx, L.mplx_reserve_fill_poly(polys.table, polys.h["b"], C.byref(i)))
+        rc = L.mplx_reserve_set_queries(polys.table, n, I["q_t0"], I["q_radius"], I["q_ignore"])
+    elif kind == "reserve_check_poly":
+        use_r, use_g, _ = variant(kind, visit)
+        i = fill(abi.ReservePolyIn(), {}, t_start=I["t_start"], radius=I["c_radius"] if use_r else None, radius_all=x["radius_all"],
+                 ignore_group=I["c_ignore"] if use_g else None)
+        rc = getattr(L, "mplx_reserve_check_poly" + sfx)(polys.table, a, C.byref(i), C.byref(fill(abi.ReservePolyOut(), P)))
+    elif kind == "shortcut_timed":
+        i = fill(abi.ShortcutIn(), {}, states=I["wp"], n_query=n, w_max=W_MAX, control=w.control, stride=stride, n_wp=I["n_wp"], max_hop=MAX_HOP)
+        o = fill(abi.ShortcutOut(), {k: v for k, v in P.items() if k != "chain_hit"}, keep_stride=stride)
+        rc = getattr(L, "mplx_shortcut_timed" + sfx)(polys.h["pairs"], polys.h["result"], C.byref(i), C.byref(o), polys.table, P.get("chain_hit"))
     elif kind == "set_lambda":
         with_n, mode = variant(kind, visit)
         i = fill(abi.LambdaIn(), {}, pts=I["pts"], stride=stride, n_pts=I["n_pts"] if with_n else None, mode=mode)
@@ -486,9 +596,10 @@ def call(abi, polys, w, kind, n, visit, x, P, I, sfx=""):
     abi.check(ctx, rc)
 
 
-ARRAYS = ("wp", "n_wp", "dts", "v_arr", "flags", "coeff", "n_segs", "src_n_segs", "times", "pts", "n_pts", "ri", "rf", "t0", "radius", "group", "rank")
+ARRAYS = ("wp", "n_wp", "dts", "v_arr", "flags", "coeff", "n_segs", "src_n_segs", "times", "pts", "n_pts", "ri", "rf", "t0", "radius", "group", "rank",
+          "res_t0", "res_radius", "t_start", "c_radius", "c_ignore", "q_t0", "q_radius", "q_ignore")
 NEEDS = {"solve": ("wp", "n_wp", "dts", "v_arr", "flags"), "poly_load": ("n_segs", "dts", "coeff"), "poly_sample": ("times",), "poly_tau": ("times",),
-         "shortcut": ("wp", "n_wp"), "set_lambda": ("pts", "n_pts"), "scale": ("ri", "rf"), "poly_conflicts": ("t0", "radius", "group", "rank")}
+         "shortcut": ("wp", "n_wp"), "shortcut_timed": ("wp", "n_wp"), "reserve_check_poly": ("t_start", "c_radius", "c_ignore"), "set_lambda": ("pts", "n_pts"), "scale": ("ri", "rf"), "poly_conflicts": ("t0", "radius", "group", "rank")}
 
 
 def host_rows(spec):
@@ -506,6 +617,7 @@ def host_step(engine, polys, w, kind, n, visit, x, long_lived):
     try:
         if x["setter"]:
             setter = x["setter"]
+            target = "b" if kind == "shortcut_timed" else "a"  # (the timed shortcut takes the chain states themselves: its setter fills the second set)
             got, P = host_rows(out_spec(w, "solve_device" if setter != "poly_load" else "poly_load", n, visit, x))
             if setter == "solve_device":  # the same rows through device memory: nothing is staged
                 Id = {k: dev.up(x[k]) for k in ("wp", "n_wp", "dts", "v_arr", "flags")}
@@ -513,7 +625,7 @@ def host_step(engine, polys, w, kind, n, visit, x, long_lived):
                 call(abi, polys, w, "solve_device", n, visit, x, Pd, Id)
                 got = dev.download()
             else:
-                call(abi, polys, w, setter, n, visit, x, P, I)
+                call(abi, polys, w, setter, n, visit, x, P, I, poly=target)
             out.update({"set_" + k: v for k, v in got.items()})
             if between:
                 SW.disturb(abi, env, w.cells.size)
@@ -527,10 +639,16 @@ def host_step(engine, polys, w, kind, n, visit, x, long_lived):
             call(abi, polys, w, "scale_for_tau", n, visit, x, {}, I)
             if between:
                 SW.disturb(abi, env, w.cells.size)
+        if kind in TIMED:
+            if kind == "reserve_check_poly":
+                call(abi, polys, w, x["setter"], n, visit, x, {}, I, poly="b")
+            call(abi, polys, w, "fill_table", n, visit, x, {}, I)
+            if between:
+                SW.disturb(abi, env, w.cells.size)
         got, P = host_rows(out_spec(w, kind, n, visit, x))
         call(abi, polys, w, kind, n, visit, x, P, I)
         out.update(got)
-        if kind == "shortcut":  # what the call left in its result poly
+        if kind in ("shortcut", "shortcut_timed"):  # what the call left in its result poly
             got, P = host_rows({k: v for k, v in out_spec(w, "poly_info", n, visit, x).items() if k != "seg_state"})
             L = abi.lib()
             abi.check(env._ctx, L.mplx_poly_info(polys.h["result"], C.byref(fill(abi.TrajInfoOut(), P, effort_stride=n))))
@@ -563,7 +681,7 @@ def twin_defined(kind, n, host):
         return np.concatenate([m, np.zeros(width - n, bool)])
 
     whole = {k: True for k in host if not k.startswith(("set_", "res_"))}
-    if kind in ("poly_traverse", "poly_conflicts", "shortcut"):
+    if kind in ("poly_traverse", "poly_conflicts", "shortcut", "shortcut_timed", "reserve_check_poly"):
         return whole
     ok = host["set_status"] == 0 if "set_status" in host else host["status"] == 0
     S = np.where(ok, host["set_n_segs"] if "set_n_segs" in host else host["n_segs"], 0)
@@ -622,7 +740,7 @@ def assert_not_vacuous(kind, n, x, want, what):
     if n < 65:
         return
     checks = [(x["setter"], "set_status")] if x["setter"] else []
-    checks += {"solve": [("solve", "status")], "shortcut": [("shortcut", "status")],
+    checks += {"solve": [("solve", "status")], "shortcut": [("shortcut", "status")], "shortcut_timed": [("shortcut", "status")],
                "poly_load": [("gather" if "src_index" in x else "poly_load", "status")]}.get(kind, [])
     for name, row in checks:
         st, pred = want[row], x["predicted"][name]
@@ -633,6 +751,11 @@ def assert_not_vacuous(kind, n, x, want, what):
         assert (want["status"] == 0).mean() >= 0.1, what + ": fewer than 10 % of the items at status 0"
     if kind == "set_lambda" or (kind == "scale" and any(variant(kind, x["visit"])[:2])):  # (the scalars of `scale` are good ratios)
         assert (want["status"] == 32).any(), what + ": no MPLX_LAMBDA_BAD_POINTS"
+    if kind == "reserve_check_poly" and "hit" in want:
+        hit = want["hit"]
+        assert (hit >= 0).mean() >= 0.1 and (hit == RPM.NO_HIT).mean() >= 0.1 and (hit == RPM.HORIZON).any(), what + ": hits, clear, past the horizon"
+    if kind == "shortcut_timed" and "chain_hit" in want:
+        assert (want["chain_hit"] != RPM.NO_HIT).any() and (want["chain_hit"] == RPM.NO_HIT).any(), what + ": no chain with a hit, or none without"
     if kind == "poly_conflicts":
         included = (want["set_status"] == 0) & ((want["status"] & BAD_INPUT) == 0)
         assert (want["first_step"][included] >= 0).any() and (want["first_step"][included] == -1).any(), what + ": no hit, or no miss"
