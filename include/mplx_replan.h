@@ -22,7 +22,9 @@
  *   the successor's lattice hash differs from hash[id],  or
  *   g[p] + cost > g[id]  (one IEEE add).
  * The last test is > on purpose: a child whose parent improved after the child was relaxed last is merely stale, and its
- * g is still the cost of a path that exists.  With check_edges == 0 no edge is bad.
+ * g is still the cost of a path that exists.  With check_edges == 0 no edge is bad -- with one exception that holds
+ * whatever check_edges is: a non-root id whose pred[id] >= n names no node of the table; its edge is bad and counted in
+ * n_bad_edges, and neither state[pred[id]] nor any other row past n is read.
  * With yaw controls and a heading limit, a pair with a heading-limit decision inside the band of the yaw pinning (what
  * mplx_rollout_device reports as MPLX_ROLLOUT_HEADING_BAND) counts as bad: the decision is taken with the device's
  * cos / sin, which may differ from the host libm's in the last place, and is not trusted near its threshold.  Dropping a

@@ -76,6 +76,20 @@ TIMED_SMALL_U = [c[0] for c in TIMED_ADDED if c[2] & YAW and c[7] == 65]
 # velocities along multiples of 45 degrees and yaws that are multiples of 0.3, no heading is within 0.015 rad of 0.5.
 TIMED_LIMITS = {c[0]: (1.0 if c[2] & 8 else 0.0, 0.5 if c[2] == (VEL | YAW) else 0.0) for c in TIMED_ADDED}
 
+# ---- tests/test_gpu_replan_untimed.py::test_untimed_edges_of_every_pair: the (dim, control) pairs whose untimed
+# replan_edge_kernel<D, K, YAW, false> ran in no GPU case before.  The worlds are those of the timed cases above: the yaw
+# pairs on the control table of 2^(dim + 1) rows, the same limits (j_max for K = 4, a heading limit for VELxYAW)
+UNTIMED_ADDED = [(2, VEL), (2, JRK), (2, VEL | YAW), (2, SNP | YAW), (3, VEL), (3, ACC), (3, VEL | YAW), (3, ACC | YAW),
+                 (3, JRK | YAW), (3, SNP | YAW)]
+
+
+def untimed_id(dim, control):
+    return "%dd-%s" % (dim, NAMES[control].lower().replace("x", ""))
+
+
+UNTIMED_SMALL_U = [untimed_id(d, c) for d, c in UNTIMED_ADDED if c & YAW]
+UNTIMED_LIMITS = {untimed_id(d, c): (1.0 if c & 8 else 0.0, 0.5 if c == (VEL | YAW) else 0.0) for d, c in UNTIMED_ADDED}
+
 # ---- tests/test_gpu_table.py::test_sweeps_round_by_round: id, dim, control, g_max, max_rounds, map edge.  g_max and the
 # edge are chosen on the model fed with the oracle's lists (tests/test_control_matrix.py repeats that choice's conditions)
 INF = float("inf")
@@ -121,6 +135,7 @@ TIMED = "tests/test_gpu_timed_replan.py::test_rebase_timed_equals_the_model"
 REBASE = "tests/test_gpu_replan.py::test_rebase_against_the_model"
 SEED_HASH = "tests/test_gpu_table.py::test_seed_hashes_equal_the_oracle"
 SWEEP = "tests/test_gpu_table.py::test_sweeps_round_by_round"
+UNTIMED = "tests/test_gpu_replan_untimed.py::test_untimed_edges_of_every_pair"
 
 # per switch: {instantiation: [GPU test cases that run it]}.  The key is what the switch dispatches on, with dim in front:
 # (dim, control name) for the flag switches, (dim, order) for the two reservation switches.
@@ -150,14 +165,12 @@ COVERAGE = {
          ((2, "JRK"), _ids(TIMED, ["2d-jrk-n4100-B64-Q3"])), ((3, "VEL"), _ids(TIMED, ["3d-vel-n4100-B15-nowait"]))] +
         [((c[1], NAMES[c[2]]), _ids(TIMED, [c[0]])) for c in TIMED_ADDED]),
     # replan_kernel.hip edge_dim<D, TIMED = false>: replan_edge_kernel<D, K, YAW, false>
-    ("replan_kernel.hip", "edge_dim", "untimed"): {
-        (2, "ACC"): _ids(REBASE, ["world_key0"]),
-        (3, "JRK"): _ids(REBASE, ["world_key1"]),
-        (2, "SNP"): _ids(REBASE, ["2d-snp"]),
-        (3, "SNP"): _ids(REBASE, ["3d-snp"]),
-        (2, "ACCxYAW"): ["tests/test_gpu_replan.py::test_yaw_controls"],
-        (2, "JRKxYAW"): ["tests/test_gpu_replan.py::test_yaw_controls_jrk"],
-    },
+    ("replan_kernel.hip", "edge_dim", "untimed"): dict(
+        [((2, "ACC"), _ids(REBASE, ["world_key0"])), ((3, "JRK"), _ids(REBASE, ["world_key1"])),
+         ((2, "SNP"), _ids(REBASE, ["2d-snp"])), ((3, "SNP"), _ids(REBASE, ["3d-snp"])),
+         ((2, "ACCxYAW"), ["tests/test_gpu_replan.py::test_yaw_controls"]),
+         ((2, "JRKxYAW"), ["tests/test_gpu_replan.py::test_yaw_controls_jrk"])] +
+        [((d, NAMES[c]), _ids(UNTIMED, [untimed_id(d, c)])) for d, c in UNTIMED_ADDED]),
     # replan_kernel.hip reserve_dim: replan_reserve_kernel<D, K>
     ("replan_kernel.hip", "reserve_dim"): {
         (2, 1): _ids(TIMED, ["2d-vel-n65-B64-nowait", "2d-velyaw-n257-B64-nowait"]),
@@ -176,7 +189,5 @@ COVERAGE = {
 for _c in SWEEP_ADDED:
     COVERAGE[("table_kernel.hip", "hash_dim")][(_c[1], NAMES[_c[2]])].append("%s[%s]" % (SWEEP, _c[0]))
 
-# Open work, not coverage: every pair runs replan_edge_kernel in its timed form, and these ten instantiations of the
-# untimed form run in no GPU case yet (tests/test_control_matrix.py holds the list exact, so that it can only shrink).
-UNTIMED_EDGE_NOT_RUN = [(2, "VEL"), (2, "JRK"), (2, "VELxYAW"), (2, "SNPxYAW"), (3, "VEL"), (3, "ACC"), (3, "VELxYAW"),
-                        (3, "ACCxYAW"), (3, "JRKxYAW"), (3, "SNPxYAW")]
+# Every pair runs replan_edge_kernel in both forms: nothing is left open (tests/test_control_matrix.py holds the list exact).
+UNTIMED_EDGE_NOT_RUN = []

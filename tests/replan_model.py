@@ -72,8 +72,8 @@ def roots_of(table, root=-1, roots=None):
 
 
 def bad_edges(table, is_root, edge, nU):
-    """{id: bad(id)} for the non-root nodes with a predecessor."""
-    todo = [i for i in range(table.n_nodes) if not is_root[i] and table.pred[i] >= 0]
+    """{id: bad(id)} for the non-root nodes with a predecessor that is a node."""
+    todo = [i for i in range(table.n_nodes) if not is_root[i] and 0 <= table.pred[i] < table.n_nodes]
     if hasattr(edge, "prepare"):
         edge.prepare([table.pred[i] for i in todo if 0 <= table.pred_action[i] < nU])
     bad = {}
@@ -97,6 +97,7 @@ def rebase(table, edge=None, nU=0, root=-1, roots=None, check_edges=True, capaci
     n = table.n_nodes
     is_root = roots_of(table, root, roots)
     bad = bad_edges(table, is_root, edge, nU) if check_edges else {}
+    bad.update({i: True for i in range(n) if not is_root[i] and table.pred[i] >= n})  # no node: bad whatever check_edges is
     kept = {}
     for i in range(n):
         chain, cur, dec = [], i, False
