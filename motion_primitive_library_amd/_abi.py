@@ -60,6 +60,8 @@ OPEN_SELECTED, OPEN_FOUND, OPEN_EMPTY = 0, 1, 2
 # ... and the ones include/mplx_multi.h declares (Q queries in one table and one open set)
 MULTI_SYMBOLS = ["mplx_table_create_multi", "mplx_table_query_of", "mplx_table_seed_multi", "mplx_table_find_multi_device",
                  "mplx_table_find_multi", "mplx_open_set_goals", "mplx_open_select_multi_device"]
+# ... and the ones include/mplx_best.h declares (the k best open nodes per query)
+BEST_SYMBOLS = ["mplx_open_select_best_device", "mplx_open_select_best_multi_device"]
 # ... and the ones include/mplx_replan.h declares (re-root and repair a table after a map edit)
 REPLAN_SYMBOLS = ["mplx_table_rebase_device", "mplx_table_rebase_multi_device", "mplx_open_push_closed_device"]
 # ... and the ones include/mplx_prior.h declares (prior-trajectory guidance of an open set)
@@ -533,6 +535,8 @@ def lib():
         "mplx_table_find_multi": (C.c_int, [vp, vp, vp, i64, vp]),
         "mplx_open_set_goals": (C.c_int, [vp, C.POINTER(GoalSpec), i32]),
         "mplx_open_select_multi_device": (C.c_int, [vp, dbl, C.POINTER(TableFrontier), vp, C.POINTER(OpenResult)]),
+        "mplx_open_select_best_device": (C.c_int, [vp, i64, dbl, C.POINTER(TableFrontier), vp, C.POINTER(OpenResult)]),
+        "mplx_open_select_best_multi_device": (C.c_int, [vp, i64, dbl, C.POINTER(TableFrontier), vp, C.POINTER(OpenResult)]),
         "mplx_table_rebase_device": (C.c_int, [vp, i32, i32, C.POINTER(TableFrontier), vp, C.POINTER(RebaseResult)]),
         "mplx_table_rebase_multi_device": (C.c_int, [vp, vp, i32, C.POINTER(TableFrontier), vp, C.POINTER(RebaseResult)]),
         "mplx_open_push_closed_device": (C.c_int, [vp, C.POINTER(TableFrontier), i64, dbl, i32]),
@@ -575,7 +579,7 @@ def lib():
         "mplx_table_set_time_keys": (C.c_int, [vp, i32]),
         "mplx_time_key": (C.c_uint64, [C.c_uint64, dbl]),
     }
-    for name in SYMBOLS + MAP_UTIL_SYMBOLS + ROLLOUT_SYMBOLS + RAY_SYMBOLS + TRAJ_SYMBOLS + TABLE_SYMBOLS + OPEN_SYMBOLS + MULTI_SYMBOLS + REPLAN_SYMBOLS + PRIOR_SYMBOLS + SOLVE_SYMBOLS + LIMITS_SYMBOLS + SCALE_SYMBOLS + CONFLICT_SYMBOLS + RESERVE_SYMBOLS + RESERVE_POLY_SYMBOLS + WAIT_SYMBOLS + REPLAN_TIMED_SYMBOLS + FIELD_SYMBOLS + HEUR_SYMBOLS:
+    for name in SYMBOLS + MAP_UTIL_SYMBOLS + ROLLOUT_SYMBOLS + RAY_SYMBOLS + TRAJ_SYMBOLS + TABLE_SYMBOLS + OPEN_SYMBOLS + MULTI_SYMBOLS + BEST_SYMBOLS + REPLAN_SYMBOLS + PRIOR_SYMBOLS + SOLVE_SYMBOLS + LIMITS_SYMBOLS + SCALE_SYMBOLS + CONFLICT_SYMBOLS + RESERVE_SYMBOLS + RESERVE_POLY_SYMBOLS + WAIT_SYMBOLS + REPLAN_TIMED_SYMBOLS + FIELD_SYMBOLS + HEUR_SYMBOLS:
         fn = getattr(L, name)  # AttributeError if the library does not export it
         fn.restype, fn.argtypes = sig[name]
     _lib = L

@@ -982,6 +982,31 @@ hipError_t launch_open_select(const OpenArgs &a, hipStream_t s);
 // select_multi: ctl / ctl_next / mirror / result are arrays of n_queries
 hipError_t launch_open_select_multi(const OpenArgs &a, hipStream_t s);
 
+// The k best open nodes per query (open_best_kernel.hip; include/mplx_best.h): a radix select over the keys' bit patterns
+// between the reduce pass and the tail (scan, emit, finish) of select_multi, which it shares with open_kernel.hip.
+constexpr int kBestBits = 8, kBestPasses = 8, kBestBins = 1 << kBestBits;  // 8 digits of 8 bits: the 64 bits of a key
+constexpr int kBestSeg = 1024;                                            // ids a wave ranks in order: kTableTile / 4
+struct BestState { uint32_t live, shift, krem, pad; unsigned long long prefix, pad2; };  // what a pass histograms with
+struct BestFinal { uint32_t valid, all, sh, ties; unsigned long long F, pad; };          // the threshold of a query
+struct BestArgs {
+  OpenArgs o;                      // as for select_multi
+  uint32_t k;                      // clamped to INT32_MAX by the host
+  // the scratch of the open set, zeroed in front of every best-select
+  uint32_t *active;                // [kBestPasses] a query histogrammed in that pass; [kBestPasses]: a node lies at a threshold
+  BestFinal *fin, *fin2;           // [n_queries] found by a histogram pass; by the classify pass from the last histogram
+  BestState *state;                // [kBestPasses][n_queries]
+  uint32_t *hist;                  // [kBestPasses][n_queries][kBestBins]
+  uint32_t *eqc;                   // [n_queries][seg_stride] nodes at the threshold per segment of kBestSeg ids, then their ranks
+  int64_t seg_stride;
+};
+inline size_t best_scratch_bytes(int64_t n_queries, int64_t cap) {
+  const size_t Q = (size_t)n_queries, segs = ((size_t)cap + kTableTile - 1) / kTableTile * (kTableTile / kBestSeg);
+  return 64 + Q * (2 * sizeof(BestFinal) + kBestPasses * (sizeof(BestState) + kBestBins * 4) + segs * 4);
+}
+hipError_t launch_open_reduce_only(const OpenArgs &a, bool multi, hipStream_t s);  // the first launch of a select
+hipError_t launch_open_tail_multi(const OpenArgs &a, hipStream_t s);               // scan, emit and finish of select_multi
+hipError_t launch_open_best(const BestArgs &b, hipStream_t s);                     // histograms, classify, rank, pick
+
 // Re-rooting and repair of a node table after a map edit (replan_kernel.hip, replan_api.cpp; include/mplx_replan.h).
 struct ReplanResult { int64_t n_kept, n_bad_edges, n_roots; };  // mplx_rebase_result
 struct ReplanArgs {

@@ -2,6 +2,7 @@
 // control blocks and scratch are its own; launches go to the stream of the table's context.  No call touches the
 // staging arena: push and select take device pointers only.
 #include "mplx_ctx.h"
+#include "../../include/mplx_best.h"
 #include "../../include/mplx_field.h"
 #include "../../include/mplx_heur.h"
 #include "../../include/mplx_multi.h"
@@ -44,6 +45,8 @@ struct mplx_open {
   int32_t heur_mode = 0;
   DevBuf dyn_ctl;
   double goals_wmin = 0.0;
+  // include/mplx_best.h: histograms, states and rank counts of a best-select, allocated by the first one
+  DevBuf best;
 };
 
 namespace {
@@ -61,7 +64,7 @@ void drop_field(mplx_open *o) {
 void release_open(mplx_open *o) {
   drop_field(o);
   for (DevBuf *b : {&o->f, &o->flags, &o->ctl, &o->mark, &o->tot, &o->rows, &o->goals, &o->goals0, &o->pr_n, &o->pr_pos, &o->pr_togo,
-                    &o->pr_status, &o->pr_sidx, &o->pr_sterm, &o->pr_costs, &o->pr_trav, &o->pr_grow, &o->pr_ghash, &o->fld_q, &o->dyn_ctl})
+                    &o->pr_status, &o->pr_sidx, &o->pr_sterm, &o->pr_costs, &o->pr_trav, &o->pr_grow, &o->pr_ghash, &o->fld_q, &o->dyn_ctl, &o->best})
     release(*b);
   if (o->mirror) (void)hipHostFree(o->mirror);
   delete o;
@@ -532,6 +535,79 @@ int mplx_open_prior_view_of(mplx_open *o, mplx_prior_view *v) {
   v->goal_hash = (const uint64_t *)o->pr_ghash.p;
   v->step_capacity = o->pr_cap;
   return MPLX_OK;
+}
+
+// ---- include/mplx_best.h -----------------------------------------------------------------------------------------------
+
+}  // extern "C"
+
+namespace {
+
+// Both forms: the reduce pass of the plain select, the radix select of open_best_kernel.hip, the tail of select_multi
+// (whose results on a table of one query are the plain select's bytes).
+int select_best(mplx_open *o, const char *who, bool single, int64_t k, double delta, const mplx_table_frontier *d_out,
+                mplx_open_result *d_results, mplx_open_result *h_results) {
+  mplx_ctx *c = o->c;
+  if (k < 1) return fail(c, MPLX_ERR_ARG, "%s: need k >= 1", who);
+  if (single && o->Q > 1) return fail(c, MPLX_ERR_STATE, "%s: the table has %d queries: mplx_open_select_best_multi_device", who, (int)o->Q);
+  if (!(delta >= 0.0)) return fail(c, MPLX_ERR_ARG, "%s: need delta >= 0", who);
+  if (int rc = check_frontier(c, who, d_out)) return rc;
+  mplx::BestArgs b{};
+  mplx::OpenArgs &a = b.o;
+  if (int rc = open_args(o, who, &a)) return rc;
+  if (int rc = bind_device(c)) return rc;
+  const size_t bytes = mplx::best_scratch_bytes(o->Q, o->cap);
+  if (int rc = ensure(c, o->best, bytes)) return rc;
+  set_frontier(&a, d_out);
+  a.delta = delta;
+  a.result = (mplx::OpenResult *)d_results;
+  a.n_tiles = (std::max<int64_t>(a.n_bound, 1) + mplx::kTableTile - 1) / mplx::kTableTile;
+  const size_t Q = (size_t)o->Q;
+  char *p = (char *)o->best.p;
+  b.k = (uint32_t)std::min<int64_t>(k, 0x7fffffff);
+  b.active = (uint32_t *)p;
+  b.fin = (mplx::BestFinal *)(p + 64);
+  b.fin2 = b.fin + Q;
+  b.state = (mplx::BestState *)(b.fin2 + Q);
+  b.hist = (uint32_t *)(b.state + (size_t)mplx::kBestPasses * Q);
+  b.eqc = b.hist + (size_t)mplx::kBestPasses * Q * mplx::kBestBins;
+  b.seg_stride = (int64_t)(((size_t)o->cap + mplx::kTableTile - 1) / mplx::kTableTile * (mplx::kTableTile / mplx::kBestSeg));
+  HIP_TRY(c, hipMemsetAsync(o->best.p, 0, bytes, c->stream));
+  HIP_TRY(c, mplx::launch_open_reduce_only(a, a.t_query != nullptr, c->stream));
+  HIP_TRY(c, mplx::launch_open_best(b, c->stream));
+  HIP_TRY(c, mplx::launch_open_tail_multi(a, c->stream));
+  o->parity = 1 - o->parity;
+  if (!h_results) return MPLX_OK;
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  table_observe(o->tab);
+  if (int rc = table_open_args(o->tab, who, &c, &a)) return rc;  // a status bit: the select did nothing
+  const volatile mplx::OpenResult *m = o->mirror;
+  for (int32_t q = 0; q < o->Q; q++) {
+    mplx_open_result *h = h_results + q;
+    h->status = m[q].status; h->goal_id = m[q].goal_id; h->count = m[q].count; h->n_open = m[q].n_open;
+    h->f_min = m[q].f_min; h->goal_f = m[q].goal_f; h->goal_g = m[q].goal_g;
+  }
+  return MPLX_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mplx_open_select_best_device(mplx_open *o, int64_t k, double delta, const mplx_table_frontier *d_out, mplx_open_result *d_result,
+                                 mplx_open_result *h_result) {
+  if (!o) return MPLX_ERR_ARG;
+  MPLX_GUARD_BEGIN
+  return select_best(o, "mplx_open_select_best_device", true, k, delta, d_out, d_result, h_result);
+  MPLX_GUARD_END(o->c)
+}
+
+int mplx_open_select_best_multi_device(mplx_open *o, int64_t k, double delta, const mplx_table_frontier *d_out,
+                                       mplx_open_result *d_results, mplx_open_result *h_results) {
+  if (!o) return MPLX_ERR_ARG;
+  MPLX_GUARD_BEGIN
+  return select_best(o, "mplx_open_select_best_multi_device", false, k, delta, d_out, d_results, h_results);
+  MPLX_GUARD_END(o->c)
 }
 
 }  // extern "C"

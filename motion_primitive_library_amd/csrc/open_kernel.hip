@@ -625,4 +625,22 @@ hipError_t launch_open_select_multi(const OpenArgs &a, hipStream_t s) {
   return hipGetLastError();
 }
 
+// include/mplx_best.h: the reduce pass in front of the launches of open_best_kernel.hip and the tail of select_multi
+// behind them -- the kernels above as they are, launched from here because they are this file's own.
+hipError_t launch_open_reduce_only(const OpenArgs &a, bool multi, hipStream_t s) {
+  const int64_t n = a.n_bound > 0 ? a.n_bound : 1;
+  const dim3 per_node((unsigned)((n + kBlock - 1) / kBlock)), block(kBlock);
+  if (multi) hipLaunchKernelGGL(open_reduce_multi_kernel, per_node, block, 0, s, a);
+  else hipLaunchKernelGGL(open_reduce_kernel, per_node, block, 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_open_tail_multi(const OpenArgs &a, hipStream_t s) {
+  const dim3 per_tile((unsigned)a.n_tiles), block(kBlock);
+  hipLaunchKernelGGL(open_scan_multi_kernel, dim3(1), dim3(1024), 0, s, a);
+  hipLaunchKernelGGL(open_emit_multi_kernel, per_tile, block, 0, s, a);
+  hipLaunchKernelGGL(open_finish_kernel, dim3((unsigned)((a.n_queries + kBlock - 1) / kBlock)), block, 0, s, a);
+  return hipGetLastError();
+}
+
 }  // namespace mplx

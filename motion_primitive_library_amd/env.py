@@ -1400,7 +1400,7 @@ class EnvMap:
     def search(self, start, goal_row, eps=1.0, delta=None, g_max=float("inf"), max_rounds=None, max_expand=None,
                capacity=1 << 16, max_frontier=None, lists_stride=None, sight=True, tol_pos=0.5, tol_vel=-1.0, tol_acc=-1.0,
                tol_yaw=-1.0, w=None, v_max=None, start_g=0.0, prior=None, avoid=None, t0=0.0, radius=None, ignore_group=-1,
-               time_keys=None, wait=False, park_goal=False, field=None, field_of_query=None, heur=None):
+               time_keys=None, wait=False, park_goal=False, field=None, field_of_query=None, heur=None, best=None):
         """A goal-directed search from `start` (one 4D+2 state) to the goal region of `goal_row` that stays on the
         device: set_goal, seed, push; then per round one select (the round's only read-back, 48 bytes), and while it
         selects: expand the selection, relax its lists against the table, push the nodes whose g fell.  Keys are
@@ -1434,18 +1434,24 @@ class EnvMap:
         heur: None -- the default heuristic and the calls of a search without the argument.  "robust": the pushes take
         the dynamics-aware heuristic (include/mplx_heur.h; OpenSet.set_heur): the cost of the unconstrained connection to
         the goal STATE minimised over the arrival time, never below the default; with a field the larger of the two.  A
-        replan keeps the mode.  heur together with prior is a ValueError."""
+        replan keeps the mode.  heur together with prior is a ValueError.
+        best: None -- the calls of a search without the argument.  k >= 1: a round expands only the k smallest keys among
+        the open nodes with f <= f_min + delta (ties by id; include/mplx_best.h), so delta=inf with best=k is a priority
+        queue that hands out k nodes a round.  It does nothing to optimality: the stopping rule is unchanged, the goal is
+        announced once no open key is below the best goal-region node's.  Without max_frontier the selection frontier and
+        the lists are allocated for min(capacity, best) nodes.  A replan keeps it."""
         from .search import run_search
         return run_search(self, start, goal_row, prior=prior, eps=eps, delta=delta, g_max=g_max, max_rounds=max_rounds,
                           max_expand=max_expand, capacity=capacity, max_frontier=max_frontier, lists_stride=lists_stride,
                           sight=sight, tol_pos=tol_pos, tol_vel=tol_vel, tol_acc=tol_acc, tol_yaw=tol_yaw, w=w, v_max=v_max,
                           start_g=start_g, avoid=avoid, t0=t0, radius=radius, ignore_group=ignore_group, time_keys=time_keys,
-                          wait=wait, park_goal=park_goal, field=field, field_of_query=field_of_query, heur=heur)
+                          wait=wait, park_goal=park_goal, field=field, field_of_query=field_of_query, heur=heur, best=best)
 
     def search_many(self, starts, goal_rows, eps=1.0, delta=None, g_max=float("inf"), max_rounds=None, max_expand=None,
                     capacity=1 << 16, max_frontier=None, lists_stride=None, sight=True, tol_pos=0.5, tol_vel=-1.0,
                     tol_acc=-1.0, tol_yaw=-1.0, w=None, v_max=None, start_g=0.0, priors=None, avoid=None, t0=0.0, radius=None,
-                    ignore_group=-1, time_keys=None, wait=False, park_goal=False, field=None, field_of_query=None, heur=None):
+                    ignore_group=-1, time_keys=None, wait=False, park_goal=False, field=None, field_of_query=None, heur=None,
+                    best=None):
         """Q searches of EnvMap.search at once, sharing every launch of a round (include/mplx_multi.h): starts
         [4D+2][Q], goal_rows [Q][4D+2], query q from starts[:, q] to the goal region of goal_rows[q].  One table of
         `capacity` nodes and one open set hold all of them; a round selects, expands, relaxes and pushes the union of
@@ -1458,14 +1464,17 @@ class EnvMap:
         every query has its own start on the clock, radius and ignored group, and one check serves them all.
         field: as EnvMap.search takes it; True builds one field per DISTINCT goal row (the delay candidates of one robot
         share one); a GoalField is used with field_of_query [Q] (default: query q uses field q; -1: the default heuristic).
-        heur: as EnvMap.search takes it; every query's own goal is the one its rows are measured against."""
+        heur: as EnvMap.search takes it; every query's own goal is the one its rows are measured against.
+        best: as EnvMap.search takes it, per query: every query selects its own k smallest keys, and without max_frontier
+        the selection frontier and the lists are allocated for min(capacity, best * Q) nodes, which no round can exceed.
+        Optimality is untouched: every query's stopping rule is the one it had."""
         from .search import run_search_many
         return run_search_many(self, starts, goal_rows, priors=priors, eps=eps, delta=delta, g_max=g_max, max_rounds=max_rounds,
                                max_expand=max_expand, capacity=capacity, max_frontier=max_frontier, lists_stride=lists_stride,
                                sight=sight, tol_pos=tol_pos, tol_vel=tol_vel, tol_acc=tol_acc, tol_yaw=tol_yaw, w=w,
                                v_max=v_max, start_g=start_g, avoid=avoid, t0=t0, radius=radius, ignore_group=ignore_group,
                                time_keys=time_keys, wait=wait, park_goal=park_goal, field=field, field_of_query=field_of_query,
-                               heur=heur)
+                               heur=heur, best=best)
 
     def _heur_goal(self, goal_row, goal_control, w, v_max):
         goal = np.ascontiguousarray(goal_row, dtype=np.float64)

@@ -235,14 +235,19 @@ class OpenSet:
         fn = _abi.lib().mplx_open_push_closed_device if closed else _abi.lib().mplx_open_push_device
         self._check(fn(self._open, C.byref(f), n, float(eps), 1 if sight else 0))
 
-    def select(self, delta, frontier, want_result=True, d_result=None):
+    def select(self, delta, frontier, want_result=True, d_result=None, best=None):
         """mplx_open_select_device into `frontier`.  Returns the result as a dict (one synchronisation), or None with
-        want_result=False -- the call is then asynchronous; d_result: a device buffer of 48 bytes, or None."""
+        want_result=False -- the call is then asynchronous; d_result: a device buffer of 48 bytes, or None.
+        best=k: mplx_open_select_best_device (include/mplx_best.h) -- of the open nodes with f <= f_min + delta only
+        the k smallest keys (ties by id) are selected.  It changes what a round expands, never when the goal is
+        announced: the stopping rule is the plain select's."""
         f = frontier.c_struct()
         r = _abi.OpenResult()
-        self._check(_abi.lib().mplx_open_select_device(self._open, float(delta), C.byref(f),
-                                                       d_result.ptr if d_result is not None else None,
-                                                       C.byref(r) if want_result else None))
+        d_res, h_res = d_result.ptr if d_result is not None else None, C.byref(r) if want_result else None
+        if best is None:
+            self._check(_abi.lib().mplx_open_select_device(self._open, float(delta), C.byref(f), d_res, h_res))
+        else:
+            self._check(_abi.lib().mplx_open_select_best_device(self._open, int(best), float(delta), C.byref(f), d_res, h_res))
         if not want_result:
             return None
         return {"status": int(r.status), "goal_id": int(r.goal_id), "count": int(r.count), "n_open": int(r.n_open),
@@ -270,14 +275,18 @@ class OpenSet:
         self._check(_abi.lib().mplx_open_set_goals(self._open, specs, n))
         self._field = None  # (dropped by the call)
 
-    def select_many(self, delta, frontier, want_result=True, d_results=None):
+    def select_many(self, delta, frontier, want_result=True, d_results=None, best=None):
         """mplx_open_select_multi_device into `frontier`.  Returns the Q results as a list of dicts (one
-        synchronisation), or None with want_result=False; d_results: a device buffer of Q * 48 bytes, or None."""
+        synchronisation), or None with want_result=False; d_results: a device buffer of Q * 48 bytes, or None.
+        best=k: mplx_open_select_best_multi_device (include/mplx_best.h) -- per query the k smallest keys among its
+        open nodes with f <= f_min + delta; the stopping rule of every query is unchanged."""
         f = frontier.c_struct()
         res = (_abi.OpenResult * self.n_queries)()
-        self._check(_abi.lib().mplx_open_select_multi_device(self._open, float(delta), C.byref(f),
-                                                             d_results.ptr if d_results is not None else None,
-                                                             res if want_result else None))
+        d_res, h_res = d_results.ptr if d_results is not None else None, res if want_result else None
+        if best is None:
+            self._check(_abi.lib().mplx_open_select_multi_device(self._open, float(delta), C.byref(f), d_res, h_res))
+        else:
+            self._check(_abi.lib().mplx_open_select_best_multi_device(self._open, int(best), float(delta), C.byref(f), d_res, h_res))
         if not want_result:
             return None
         return [{"status": int(r.status), "goal_id": int(r.goal_id), "count": int(r.count), "n_open": int(r.n_open),
@@ -816,7 +825,7 @@ def time_key(hashes, t):
 
 
 def plan_prioritised(env, starts, goal_rows, step, radius, order=None, delays=(0.0,), park=True, wait=False, park_goal=False,
-                     field=False, keep=False, **search_kw):
+                     field=False, keep=False, best=None, **search_kw):
     """Prioritised planning of R robots on one map: robot r plans against the trajectories of the robots planned
     before it, as obstacles that move on the common clock of conflicts().  starts [4D+2][R] (t = 0 each), goal_rows
     [R][4D+2], radius a scalar or [R]; step: the clock's.  Robots are planned in `order` (default: the index, so a lower
@@ -844,6 +853,9 @@ def plan_prioritised(env, starts, goal_rows, step, radius, order=None, delays=(0
     field=True: the R goal distance fields (include/mplx_field.h) are built in one GoalField.build up front, and robot r
     searches with its own for every delay candidate.
 
+    best=k goes to search_many (EnvMap.search states it): every delay candidate expands its k smallest keys a round.  It
+    does nothing to optimality -- the stopping rule is unchanged -- and replan_prioritised keeps it.
+
     Its limits: a robot that finds no path is reported and not reserved.  Protection holds to the table's horizon
     (`n_steps`) only.  An earlier robot is never re-planned when a later one cannot avoid it (replan_prioritised replans every robot,
     in the same order, after the world has changed).  A chain with waits is not
@@ -853,6 +865,8 @@ def plan_prioritised(env, starts, goal_rows, step, radius, order=None, delays=(0
     conflicts take it as it is."""
     starts = np.ascontiguousarray(starts, dtype=np.float64)
     goal_rows = np.ascontiguousarray(goal_rows, dtype=np.float64)
+    if best is not None:
+        search_kw = dict(search_kw, best=best)
     R = starts.shape[1]
     order = list(range(R)) if order is None else [int(r) for r in order]
     delays = np.atleast_1d(np.asarray(delays, dtype=np.float64))
@@ -1323,14 +1337,18 @@ def _search_loop(env, who, multi, tab, opn, sel, imp, lists, prm, total, rounds,
     selects: one _round on the selection.  rounds / expanded: per query (one entry for a table of one query), counted
     on from what they hold.  avoid: a Reservations whose check runs between the expansion and the relax; None: the calls
     of a search without one.  prm["wait"] / prm["park_goal"]: _edges.  With both off the loop issues exactly the calls it
-    issued before they existed.  Returns (status per query, the results of the last select, relax calls made)."""
+    issued before they existed.  prm["best"]: the selects are those of include/mplx_best.h; None: the plain ones.  Returns (status per query, the results of the last select, relax calls made)."""
     eps, delta, sight = prm["eps"], prm["delta"], prm["sight"]
     wait, park = _edges(prm, avoid)
     max_rounds, max_expand = prm["max_rounds"], prm["max_expand"]
+    best = prm.get("best")
     limit = None
     while True:
         try:
-            res = opn.select_many(delta, sel) if multi else [opn.select(delta, sel)]
+            if best is None:
+                res = opn.select_many(delta, sel) if multi else [opn.select(delta, sel)]
+            else:
+                res = opn.select_many(delta, sel, best=best) if multi else [opn.select(delta, sel, best=best)]
         except _abi.MplxError as e:
             if e.code != _abi.ERR_STATE:
                 raise
@@ -1367,11 +1385,17 @@ def _add_waits(env, avoid, sel, lists, n):
                                                                _device_ptr(sel.id), None))
 
 
-def _params(env, eps, delta, g_max, max_rounds, max_expand, capacity, max_frontier, lists_stride, sight, goal_kw):
+def _params(env, eps, delta, g_max, max_rounds, max_expand, capacity, max_frontier, lists_stride, sight, goal_kw, best=None, Q=1):
     if delta is None:
         delta = float(env._p.w) * float(env._p.dt)
+    if best is not None:
+        best = int(best)
+        if best < 1:
+            raise ValueError("best must be >= 1")
+    # with best no select takes more than best rows per query: the frontier and the lists need no more
+    fcap = int(max_frontier) if max_frontier is not None else int(capacity) if best is None else min(int(capacity), best * int(Q))
     return {"eps": eps, "delta": delta, "g_max": g_max, "max_rounds": max_rounds, "max_expand": max_expand,
-            "capacity": int(capacity), "fcap": int(capacity if max_frontier is None else max_frontier),
+            "capacity": int(capacity), "fcap": fcap, "best": best,
             "lists_stride": lists_stride, "sight": sight, "goal_kw": goal_kw,
             # what as_prior() hands on: the control set of this search
             "control": int(env._p.control), "U": getattr(env, "_U_host", None), "dt": float(env._p.dt)}
@@ -1427,7 +1451,7 @@ def _run(env, multi, starts, goal_rows, opts):
     Q = starts.shape[1]
     prm = _params(env, *(opts[k] for k in ("eps", "delta", "g_max", "max_rounds", "max_expand", "capacity", "max_frontier",
                                            "lists_stride", "sight")),
-                  {k: opts[k] for k in ("w", "v_max", "tol_pos", "tol_vel", "tol_acc", "tol_yaw")})
+                  {k: opts[k] for k in ("w", "v_max", "tol_pos", "tol_vel", "tol_acc", "tol_yaw")}, opts.get("best"), Q)
     prm["goal_rows"] = goal_rows
     # the open set carries its goals itself (several queries and priors need that): replan keeps it so
     prm["own_goals"] = multi or priors is not None
