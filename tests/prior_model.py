@@ -117,7 +117,9 @@ def prior_table(dim, control, U, pdt, start, actions, cells, map_dim, origin, re
                 grad_w=0.0, goal_row=None, goal_hash=None):
     """The prior table of one query.  control / U / pdt: the prior's; the rest the searching context's.  cells: the int8
     occupancy map, pot: the potential map or None (both flat, x fastest).  Returns a dict: status, n_steps, T,
-    total_cost, pos [n_steps][D], togo [n_steps], goal_row, goal_hash (the given goal when n_steps == 0)."""
+    total_cost, pos [n_steps][D], togo [n_steps], goal_row, goal_hash (the given goal when n_steps == 0), steps_t (the t_k),
+    taus (the segment ends) and samples: per Command sample (time stamp, |vel|, wrapped cell index, outside, occupied,
+    potential value read)."""
     K = _order(control)
     F = 4 * dim + 2
     U = np.asarray(U, dtype=np.float64)
@@ -220,7 +222,7 @@ def prior_table(dim, control, U, pdt, start, actions, cells, map_dim, origin, re
     g[4 * dim + 1] = 0.0
     g = [x + 0.0 for x in g]
     out.update(n_steps=len(ts), total_cost=total, pos=np.array(pos, dtype=np.float64).reshape(-1, dim), togo=np.array(togo),
-               goal_row=np.array(g), goal_hash=lattice_hash(dim, control, g), steps_t=ts)
+               goal_row=np.array(g), goal_hash=lattice_hash(dim, control, g), steps_t=ts, samples=pts, taus=taus)
     return out
 
 

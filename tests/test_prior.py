@@ -45,12 +45,12 @@ def test_every_function_of_the_header_is_exported_and_bound(engine):
 
 # ---- the host planner's table (the scenario of tests/test_plan_known_answer.py) against the model ----------------------
 
-def _planner(m, c, control, U, cells, dt, keep):
-    oenv = O.Env(2, control, U, cells, c["dim"], c["origin"], c["res"], v_max=1.0, a_max=1.0, dt=dt)
+def _planner(m, c, control, U, cells, dt, keep, dim=2):
+    oenv = O.Env(dim, control, U, cells, c["dim"], c["origin"], c["res"], v_max=1.0, a_max=1.0, dt=dt)
     prov, ce = provider_from_oracle(oenv)
     keep.append((oenv, ce))
-    pl = m.MapPlanner(2, provider=prov)
-    mu = m.MapUtil(2)
+    pl = m.MapPlanner(dim, provider=prov)
+    mu = m.MapUtil(dim)
     mu.setMap(c["origin"], c["dim"], cells, c["res"])
     pl.setMapUtil(mu)
     pl.setVmax(1.0)
