@@ -62,6 +62,8 @@ MULTI_SYMBOLS = ["mplx_table_create_multi", "mplx_table_query_of", "mplx_table_s
                  "mplx_table_find_multi", "mplx_open_set_goals", "mplx_open_select_multi_device"]
 # ... and the ones include/mplx_best.h declares (the k best open nodes per query)
 BEST_SYMBOLS = ["mplx_open_select_best_device", "mplx_open_select_best_multi_device"]
+# ... and the one include/mplx_anytime.h declares (re-key an open set, the lower bound of its open nodes)
+ANYTIME_SYMBOLS = ["mplx_open_rekey_device"]
 # ... and the ones include/mplx_replan.h declares (re-root and repair a table after a map edit)
 REPLAN_SYMBOLS = ["mplx_table_rebase_device", "mplx_table_rebase_multi_device", "mplx_open_push_closed_device"]
 # ... and the ones include/mplx_prior.h declares (prior-trajectory guidance of an open set)
@@ -279,6 +281,11 @@ class TableView(C.Structure):
 class TableFrontier(C.Structure):
     _fields_ = [("id", C.c_void_p), ("g", C.c_void_p), ("state", C.c_void_p), ("state_stride", C.c_int64),
                 ("capacity", C.c_int64), ("count", C.c_void_p)]
+
+
+class OpenBound(C.Structure):
+    """mplx_open_bound (include/mplx_anytime.h)"""
+    _fields_ = [("lower", C.c_double), ("n_open", C.c_int64), ("n_pruned", C.c_int64), ("n_rekeyed", C.c_int64)]
 
 
 class OpenView(C.Structure):
@@ -537,6 +544,7 @@ def lib():
         "mplx_open_select_multi_device": (C.c_int, [vp, dbl, C.POINTER(TableFrontier), vp, C.POINTER(OpenResult)]),
         "mplx_open_select_best_device": (C.c_int, [vp, i64, dbl, C.POINTER(TableFrontier), vp, C.POINTER(OpenResult)]),
         "mplx_open_select_best_multi_device": (C.c_int, [vp, i64, dbl, C.POINTER(TableFrontier), vp, C.POINTER(OpenResult)]),
+        "mplx_open_rekey_device": (C.c_int, [vp, dbl, i32, vp, vp, C.POINTER(OpenBound)]),
         "mplx_table_rebase_device": (C.c_int, [vp, i32, i32, C.POINTER(TableFrontier), vp, C.POINTER(RebaseResult)]),
         "mplx_table_rebase_multi_device": (C.c_int, [vp, vp, i32, C.POINTER(TableFrontier), vp, C.POINTER(RebaseResult)]),
         "mplx_open_push_closed_device": (C.c_int, [vp, C.POINTER(TableFrontier), i64, dbl, i32]),
@@ -579,7 +587,7 @@ def lib():
         "mplx_table_set_time_keys": (C.c_int, [vp, i32]),
         "mplx_time_key": (C.c_uint64, [C.c_uint64, dbl]),
     }
-    for name in SYMBOLS + MAP_UTIL_SYMBOLS + ROLLOUT_SYMBOLS + RAY_SYMBOLS + TRAJ_SYMBOLS + TABLE_SYMBOLS + OPEN_SYMBOLS + MULTI_SYMBOLS + BEST_SYMBOLS + REPLAN_SYMBOLS + PRIOR_SYMBOLS + SOLVE_SYMBOLS + LIMITS_SYMBOLS + SCALE_SYMBOLS + CONFLICT_SYMBOLS + RESERVE_SYMBOLS + RESERVE_POLY_SYMBOLS + WAIT_SYMBOLS + REPLAN_TIMED_SYMBOLS + FIELD_SYMBOLS + HEUR_SYMBOLS:
+    for name in SYMBOLS + MAP_UTIL_SYMBOLS + ROLLOUT_SYMBOLS + RAY_SYMBOLS + TRAJ_SYMBOLS + TABLE_SYMBOLS + OPEN_SYMBOLS + MULTI_SYMBOLS + BEST_SYMBOLS + ANYTIME_SYMBOLS + REPLAN_SYMBOLS + PRIOR_SYMBOLS + SOLVE_SYMBOLS + LIMITS_SYMBOLS + SCALE_SYMBOLS + CONFLICT_SYMBOLS + RESERVE_SYMBOLS + RESERVE_POLY_SYMBOLS + WAIT_SYMBOLS + REPLAN_TIMED_SYMBOLS + FIELD_SYMBOLS + HEUR_SYMBOLS:
         fn = getattr(L, name)  # AttributeError if the library does not export it
         fn.restype, fn.argtypes = sig[name]
     _lib = L

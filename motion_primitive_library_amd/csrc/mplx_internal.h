@@ -1007,6 +1007,22 @@ hipError_t launch_open_reduce_only(const OpenArgs &a, bool multi, hipStream_t s)
 hipError_t launch_open_tail_multi(const OpenArgs &a, hipStream_t s);               // scan, emit and finish of select_multi
 hipError_t launch_open_best(const BestArgs &b, hipStream_t s);                     // histograms, classify, rank, pick
 
+// Re-key of an open set and the lower bound of its open nodes (open_rekey_kernel.hip; include/mplx_anytime.h).
+struct OpenBound { double lower; int64_t n_open, n_pruned, n_rekeyed; };  // mplx_open_bound
+struct RekeyCtl {                  // device memory, one per query; reset by the first launch of every re-key
+  unsigned long long lower_bits;   // min over the open nodes of the bit pattern of g + h (+inf: none)
+  unsigned long long n_open, n_pruned, n_rekeyed;
+};
+struct RekeyArgs {
+  OpenArgs o;                      // the table, f, flags, eps and the heuristic's modes as for a push (no frontier)
+  int32_t write;                   // 0: the bound alone
+  const double *cut;               // [n_queries] in device memory, or null: nothing is pruned
+  RekeyCtl *rctl;                  // [n_queries]
+  OpenBound *d_bound;              // [n_queries] device memory of the caller, or null
+  OpenBound *mirror;               // [n_queries] pinned host memory
+};
+hipError_t launch_open_rekey(int dim, const RekeyArgs &r, hipStream_t s);  // reset, re-key, finish
+
 // Re-rooting and repair of a node table after a map edit (replan_kernel.hip, replan_api.cpp; include/mplx_replan.h).
 struct ReplanResult { int64_t n_kept, n_bad_edges, n_roots; };  // mplx_rebase_result
 struct ReplanArgs {

@@ -2,6 +2,7 @@
 // control blocks and scratch are its own; launches go to the stream of the table's context.  No call touches the
 // staging arena: push and select take device pointers only.
 #include "mplx_ctx.h"
+#include "../../include/mplx_anytime.h"
 #include "../../include/mplx_best.h"
 #include "../../include/mplx_field.h"
 #include "../../include/mplx_heur.h"
@@ -16,6 +17,7 @@
 using namespace mplx_detail;
 
 static_assert(sizeof(mplx::OpenResult) == sizeof(mplx_open_result), "mplx::OpenResult is mplx_open_result");
+static_assert(sizeof(mplx::OpenBound) == sizeof(mplx_open_bound), "mplx::OpenBound is mplx_open_bound");
 
 struct mplx_open {
   mplx_table *tab = nullptr;
@@ -47,6 +49,9 @@ struct mplx_open {
   double goals_wmin = 0.0;
   // include/mplx_best.h: histograms, states and rank counts of a best-select, allocated by the first one
   DevBuf best;
+  // include/mplx_anytime.h: the control blocks, the cut and the pinned mirror of the bound of a re-key ([Q] each), allocated on demand
+  DevBuf rk_ctl, rk_cut;
+  mplx::OpenBound *rk_mirror = nullptr;
 };
 
 namespace {
@@ -64,9 +69,10 @@ void drop_field(mplx_open *o) {
 void release_open(mplx_open *o) {
   drop_field(o);
   for (DevBuf *b : {&o->f, &o->flags, &o->ctl, &o->mark, &o->tot, &o->rows, &o->goals, &o->goals0, &o->pr_n, &o->pr_pos, &o->pr_togo,
-                    &o->pr_status, &o->pr_sidx, &o->pr_sterm, &o->pr_costs, &o->pr_trav, &o->pr_grow, &o->pr_ghash, &o->fld_q, &o->dyn_ctl, &o->best})
+                    &o->pr_status, &o->pr_sidx, &o->pr_sterm, &o->pr_costs, &o->pr_trav, &o->pr_grow, &o->pr_ghash, &o->fld_q, &o->dyn_ctl, &o->best, &o->rk_ctl, &o->rk_cut})
     release(*b);
   if (o->mirror) (void)hipHostFree(o->mirror);
+  if (o->rk_mirror) (void)hipHostFree(o->rk_mirror);
   delete o;
 }
 
@@ -92,6 +98,48 @@ int check_frontier(mplx_ctx *c, const char *who, const mplx_table_frontier *f) {
 
 void set_frontier(mplx::OpenArgs *a, const mplx_table_frontier *f) {
   a->f_id = f->id; a->f_g = f->g; a->f_state = f->state; a->f_stride = f->state_stride; a->f_cap = f->capacity; a->f_count = f->count;
+}
+
+// What the heuristic of a push reads, for the push and for the re-key of include/mplx_anytime.h: the goal(s), the priors,
+// the goal field (MPLX_ERR_STATE for one that is stale, empty or destroyed) and the mode of mplx_open_set_heur.
+int heur_args(mplx_open *o, const char *who, mplx::OpenArgs *ap) {
+  mplx_ctx *c = o->c;
+  mplx::OpenArgs &a = *ap;
+  a.goal = c->goal_fuse;
+  a.goals = o->has_goals ? (const mplx::PostFuse *)o->goals.p : nullptr;
+  if (o->has_priors && o->has_goals) {
+    a.prior_n = (const int32_t *)o->pr_n.p;
+    a.prior_pos = (const double *)o->pr_pos.p;
+    a.prior_togo = (const double *)o->pr_togo.p;
+    a.prior_cap = o->pr_cap;
+    a.prior_dt = o->pr_dt;
+  }
+  if (o->fld_gone) return fail(c, MPLX_ERR_STATE, "%s: the goal field in force was destroyed (mplx_open_clear_field, or set another)", who);
+  if (o->fld) {  // include/mplx_field.h
+    const mplx_field *fl = o->fld;
+    if (fl->epoch != c->blk_epoch) return fail(c, MPLX_ERR_STATE, "%s: the goal field is stale (the map changed since mplx_field_build)", who);
+    if (fl->F < 1 || o->fld_max >= fl->F || fl->n_cells != c->n_cells)
+      return fail(c, MPLX_ERR_STATE, "%s: the goal field is empty, or was rebuilt with fewer fields than the queries use", who);
+    if (!((o->has_goals ? o->goals_vmin : c->goal_fuse.v_max) > 0)) return fail(c, MPLX_ERR_STATE, "%s: a goal field needs v_max > 0", who);
+    a.field_dist = (const int32_t *)fl->dist.p;
+    a.field_of_query = (const int32_t *)o->fld_q.p;
+    a.field_F = fl->F;
+    a.field_cells = fl->n_cells;
+    for (int i = 0; i < 3; i++) {
+      a.field_dim[i] = c->mdim[i];
+      a.field_org[i] = c->origin[i];
+    }
+    a.field_res = c->res;
+  }
+  if (o->heur_mode == MPLX_HEUR_ROBUST) {  // include/mplx_heur.h
+    if (o->has_priors) return fail(c, MPLX_ERR_STATE, "%s: MPLX_HEUR_ROBUST with priors in force (mplx_open_clear_priors, or mplx_open_set_heur(DEFAULT))", who);
+    if (!((o->has_goals ? o->goals_wmin : c->goal_fuse.w) > 0)) return fail(c, MPLX_ERR_STATE, "%s: MPLX_HEUR_ROBUST needs w > 0", who);
+    a.dyn = MPLX_HEUR_ROBUST;
+    a.dyn_control[0] = c->goal_ctl[0];
+    a.dyn_control[1] = c->goal_ctl[1];
+    a.dyn_controls = o->has_goals ? (const int32_t *)o->dyn_ctl.p : nullptr;
+  }
+  return MPLX_OK;
 }
 
 }  // namespace
@@ -192,40 +240,7 @@ int mplx_detail::open_push(mplx_open *o, const char *who, const mplx_table_front
   set_frontier(&a, d_rows);
   a.n_max = n_max;
   a.eps = eps;
-  a.goal = c->goal_fuse;
-  a.goals = o->has_goals ? (const mplx::PostFuse *)o->goals.p : nullptr;
-  if (o->has_priors && o->has_goals) {
-    a.prior_n = (const int32_t *)o->pr_n.p;
-    a.prior_pos = (const double *)o->pr_pos.p;
-    a.prior_togo = (const double *)o->pr_togo.p;
-    a.prior_cap = o->pr_cap;
-    a.prior_dt = o->pr_dt;
-  }
-  if (o->fld_gone) return fail(c, MPLX_ERR_STATE, "%s: the goal field in force was destroyed (mplx_open_clear_field, or set another)", who);
-  if (o->fld) {  // include/mplx_field.h
-    const mplx_field *fl = o->fld;
-    if (fl->epoch != c->blk_epoch) return fail(c, MPLX_ERR_STATE, "%s: the goal field is stale (the map changed since mplx_field_build)", who);
-    if (fl->F < 1 || o->fld_max >= fl->F || fl->n_cells != c->n_cells)
-      return fail(c, MPLX_ERR_STATE, "%s: the goal field is empty, or was rebuilt with fewer fields than the queries use", who);
-    if (!((o->has_goals ? o->goals_vmin : c->goal_fuse.v_max) > 0)) return fail(c, MPLX_ERR_STATE, "%s: a goal field needs v_max > 0", who);
-    a.field_dist = (const int32_t *)fl->dist.p;
-    a.field_of_query = (const int32_t *)o->fld_q.p;
-    a.field_F = fl->F;
-    a.field_cells = fl->n_cells;
-    for (int i = 0; i < 3; i++) {
-      a.field_dim[i] = c->mdim[i];
-      a.field_org[i] = c->origin[i];
-    }
-    a.field_res = c->res;
-  }
-  if (o->heur_mode == MPLX_HEUR_ROBUST) {  // include/mplx_heur.h
-    if (o->has_priors) return fail(c, MPLX_ERR_STATE, "%s: MPLX_HEUR_ROBUST with priors in force (mplx_open_clear_priors, or mplx_open_set_heur(DEFAULT))", who);
-    if (!((o->has_goals ? o->goals_wmin : c->goal_fuse.w) > 0)) return fail(c, MPLX_ERR_STATE, "%s: MPLX_HEUR_ROBUST needs w > 0", who);
-    a.dyn = MPLX_HEUR_ROBUST;
-    a.dyn_control[0] = c->goal_ctl[0];
-    a.dyn_control[1] = c->goal_ctl[1];
-    a.dyn_controls = o->has_goals ? (const int32_t *)o->dyn_ctl.p : nullptr;
-  }
+  if (int rc = heur_args(o, who, &a)) return rc;
   if (!sight) {
     HIP_TRY(c, mplx::launch_open_push(c->dim, 0, a, rows, c->stream, closed));
     return MPLX_OK;
@@ -535,6 +550,61 @@ int mplx_open_prior_view_of(mplx_open *o, mplx_prior_view *v) {
   v->goal_hash = (const uint64_t *)o->pr_ghash.p;
   v->step_capacity = o->pr_cap;
   return MPLX_OK;
+}
+
+// ---- include/mplx_anytime.h --------------------------------------------------------------------------------------------
+
+int mplx_open_rekey_device(mplx_open *o, double eps, int32_t write, const double *h_cut, mplx_open_bound *d_bound, mplx_open_bound *h_bound) {
+  if (!o) return MPLX_ERR_ARG;
+  mplx_ctx *c = o->c;
+  const char *who = "mplx_open_rekey_device";
+  if (!(eps >= 0.0) || std::isinf(eps)) return fail(c, MPLX_ERR_ARG, "%s: need a finite eps >= 0", who);
+  if (h_cut)
+    for (int32_t q = 0; q < o->Q; q++)
+      if (!(h_cut[q] >= 0.0)) return fail(c, MPLX_ERR_ARG, "%s: cut[%d] is negative or NaN", who, (int)q);
+  if (o->Q > 1 && !o->has_goals) return fail(c, MPLX_ERR_STATE, "%s: no goals (mplx_open_set_goals)", who);
+  if (!o->has_goals && !c->has_goal) return fail(c, MPLX_ERR_STATE, "%s: no goal (mplx_set_goal)", who);
+  MPLX_GUARD_BEGIN
+  mplx::RekeyArgs r{};
+  mplx::OpenArgs &a = r.o;
+  if (int rc = open_args(o, who, &a)) return rc;
+  a.eps = eps;
+  if (int rc = heur_args(o, who, &a)) return rc;
+  if (int rc = bind_device(c)) return rc;
+  const size_t Q = (size_t)o->Q;
+  if (int rc = ensure(c, o->rk_ctl, Q * sizeof(mplx::RekeyCtl))) return rc;
+  if (!o->rk_mirror && hipHostMalloc((void **)&o->rk_mirror, std::max<size_t>(64, Q * sizeof(mplx::OpenBound)), hipHostMallocCoherent) != hipSuccess) {
+    o->rk_mirror = nullptr;
+    (void)hipGetLastError();
+    return fail(c, MPLX_ERR_HIP, "%s: hipHostMalloc failed", who);
+  }
+  r.write = write ? 1 : 0;
+  r.rctl = (mplx::RekeyCtl *)o->rk_ctl.p;
+  r.d_bound = (mplx::OpenBound *)d_bound;
+  r.mirror = o->rk_mirror;
+  bool waited = false;
+  if (h_cut) {
+    // The cut lands in a buffer of the open set's own, not in the context's staging arena: the call holds no arena row,
+    // so nothing another host-pointer call carves can move under the launch.  The wait lets the caller's array go.
+    if (int rc = ensure(c, o->rk_cut, Q * 8)) return rc;
+    HIP_TRY(c, hipMemcpyAsync(o->rk_cut.p, h_cut, Q * 8, hipMemcpyHostToDevice, c->stream));
+    r.cut = (const double *)o->rk_cut.p;
+    HIP_TRY(c, mplx::launch_open_rekey(c->dim, r, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    waited = true;
+  } else {
+    HIP_TRY(c, mplx::launch_open_rekey(c->dim, r, c->stream));
+  }
+  if (!h_bound) return MPLX_OK;
+  if (!waited) HIP_TRY(c, hipStreamSynchronize(c->stream));
+  table_observe(o->tab);
+  if (int rc = table_open_args(o->tab, who, &c, &a)) return rc;  // a status bit: the re-key did nothing
+  const volatile mplx::OpenBound *m = o->rk_mirror;
+  for (int32_t q = 0; q < o->Q; q++) {
+    h_bound[q].lower = m[q].lower; h_bound[q].n_open = m[q].n_open; h_bound[q].n_pruned = m[q].n_pruned; h_bound[q].n_rekeyed = m[q].n_rekeyed;
+  }
+  return MPLX_OK;
+  MPLX_GUARD_END(c)
 }
 
 // ---- include/mplx_best.h -----------------------------------------------------------------------------------------------

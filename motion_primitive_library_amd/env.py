@@ -1523,6 +1523,12 @@ class EnvMap:
         from .search import Reservations
         return Reservations(self, trajs, step, n_steps, t0, radius, group, park)
 
+    def anytime(self, result, schedule, max_expand=None, avoid=None):
+        """search.anytime: improve a SearchResult / MultiSearchResult of this EnvMap through a non-increasing schedule of eps
+        on the tree it has paid for (include/mplx_anytime.h); returns (final_result, stages)."""
+        from .search import anytime
+        return anytime(result, schedule, max_expand=max_expand, avoid=avoid)
+
     def synchronize(self):
         _abi.check(self._ctx, _abi.lib().mplx_synchronize(self._ctx))
 

@@ -203,6 +203,7 @@ class OpenSet:
         self._table = table  # (kept alive: the open set reads the table's arrays)
         self._open = None
         self._field = None  # (kept alive while it is in force)
+        self.has_priors, self.heur_mode = False, None  # what is in force, as the calls below left it (bound() asks)
         self.capacity = table.capacity
         self.n_queries = getattr(table, "n_queries", 1)
         o = C.c_void_p()
@@ -274,6 +275,7 @@ class OpenSet:
             g.tol_pos, g.tol_vel, g.tol_acc, g.tol_yaw = float(tp[q]), float(tv[q]), float(ta[q]), float(ty[q])
         self._check(_abi.lib().mplx_open_set_goals(self._open, specs, n))
         self._field = None  # (dropped by the call)
+        self.has_priors = False  # (likewise)
 
     def select_many(self, delta, frontier, want_result=True, d_results=None, best=None):
         """mplx_open_select_multi_device into `frontier`.  Returns the Q results as a list of dicts (one
@@ -316,7 +318,9 @@ class OpenSet:
             info = _abi.PriorInfo()
             info.status, info.n_steps = status.ctypes.data, n_steps.ctypes.data
             # (the info read-back synchronises: the uploads may be freed when the call returns)
+            self.has_priors = False  # (a failure leaves the open set without priors)
             self._check(_abi.lib().mplx_open_set_priors_device(self._open, C.byref(src), C.byref(s), C.byref(info)))
+            self.has_priors = True
         finally:
             for b in bufs:
                 b.free()
@@ -346,6 +350,7 @@ class OpenSet:
 
     def clear_priors(self):
         self._check(_abi.lib().mplx_open_clear_priors(self._open))
+        self.has_priors = False
 
     def set_field(self, field, field_of_query=None):
         """mplx_open_set_field: every push takes the heuristic of query q from field field_of_query[q] of `field` (a
@@ -368,7 +373,31 @@ class OpenSet:
         """mplx_open_set_heur (include/mplx_heur.h): "robust" -- every push from now on takes its heuristic from the
         dynamics-aware ROBUST form (never below the default; with a field the larger of the two); None / "default" -- the
         default again.  clear() keeps the mode; priors exclude it."""
-        self._check(_abi.lib().mplx_open_set_heur(self._open, _abi.heur_mode(mode)))
+        m = _abi.heur_mode(mode)
+        self._check(_abi.lib().mplx_open_set_heur(self._open, m))
+        self.heur_mode = None if m == _abi.HEUR_DEFAULT else "robust"
+
+    def rekey(self, eps, cut=None, write=True, want_result=True, d_bound=None):
+        """mplx_open_rekey_device (include/mplx_anytime.h): every node of the table that was ever pushed gets the key
+        g + eps * h again, with the table's current g and the h a push would compute now; per query the smallest g + h
+        among its open nodes is reported.  cut: one value or [Q] -- an open node of query q with g + h >= cut[q] is closed
+        (ties too; inf closes nothing); write=False: the bound alone, no byte of f or flags changes.  Returns the Q
+        bounds as a list of dicts {"lower", "n_open", "n_pruned", "n_rekeyed"} (one synchronisation), or None with
+        want_result=False; d_bound: a device buffer of Q * 32 bytes, or None.  Without cut and result the call is
+        asynchronous."""
+        Q = self.n_queries
+        res = (_abi.OpenBound * Q)()
+        h_cut = None
+        if cut is not None:
+            self._env._flush()
+            h_cut = np.ascontiguousarray(np.broadcast_to(np.asarray(cut, dtype=np.float64), (Q,)))
+        self._check(_abi.lib().mplx_open_rekey_device(self._open, float(eps), 1 if write else 0,
+                                                      None if h_cut is None else h_cut.ctypes.data,
+                                                      d_bound.ptr if d_bound is not None else None, res if want_result else None))
+        if not want_result:
+            return None
+        return [{"lower": float(r.lower), "n_open": int(r.n_open), "n_pruned": int(r.n_pruned), "n_rekeyed": int(r.n_rekeyed)}
+                for r in res]
 
     def priors(self):
         """The prior table in force (a download): {"n_steps" [Q], "pos": [Q] arrays [n_steps][D], "togo": [Q] arrays,
@@ -1115,6 +1144,55 @@ class _Result:
             raise ValueError("%s: give %s or advance, not both" % (who, "roots" if self._multi else "root"))
         return run_replan(self, self._multi, self._roots(who, roots, advance), goal_rows, check_edges, priors, timed, avoid)
 
+    rekey_info = None  # per query, of the re-key that made this result (improve sets it)
+    _pruned_at = None  # per query the smallest cut an improve pruned its open nodes with (None: never)
+
+    def _certificate(self):
+        """Per query (slack, certified): slack = w * tol_pos / v_max (w * tol_pos for v_max <= 0) -- h is measured to the
+        goal's centre while the goal test accepts a box, so h - slack is what is admissible --; certified: the heuristic
+        the open set pushes with is, less slack, a lower bound of the cost to go: the default, a goal field, and "robust"
+        with every tolerance zero; not priors, not "robust" on a goal box."""
+        Q, kw, p = self.n_queries, self._params["goal_kw"], self._env._p
+        per = lambda v, default=None: np.broadcast_to(np.asarray(default if v is None else v, dtype=np.float64), (Q,))
+        w, v_max, tol = per(kw["w"], p.w), per(kw["v_max"], p.v_max), per(kw["tol_pos"])
+        slack = [float(w[q] * tol[q] / v_max[q]) if v_max[q] > 0 else float(w[q] * tol[q]) for q in range(Q)]
+        exact = [all(per(kw[k])[q] == 0 for k in ("tol_pos", "tol_vel", "tol_acc", "tol_yaw")) for q in range(Q)]
+        opn = self.open
+        cert = [(not opn.has_priors) and (opn.heur_mode is None or exact[q]) for q in range(Q)]
+        return slack, cert
+
+    def _bound(self):
+        if self.table is None or self._params is None:
+            raise RuntimeError("bound: this result does not own a table (it was replanned, improved or freed)")
+        slack, cert = self._certificate()
+        rk = self.open.rekey(self._params["eps"], write=False)
+        g_max, cost = float(self._params["g_max"]), self._per_query("cost")
+        cuts = self._pruned_at or [math.inf] * self.n_queries
+        out = []
+        for q in range(self.n_queries):
+            # what cut the tree bounds nothing above itself: g_max, and the cut of a pruning improve (a pruned node had
+            # g + h >= cut, and is no longer open to say so)
+            lower = max(0.0, min(rk[q]["lower"], g_max, cuts[q]) - slack[q])
+            ratio = math.nan
+            if cert[q]:
+                ratio = cost[q] / lower if lower > 0 else (1.0 if cost[q] == 0 else math.inf)
+            out.append({"cost": cost[q], "lower": lower, "slack": slack[q], "ratio": ratio, "certified": cert[q],
+                        "n_open": rk[q]["n_open"]})
+        return out
+
+    def _improve(self, eps, prune, max_rounds, max_expand, avoid):
+        if self.table is None or self._params is None:
+            raise RuntimeError("improve: this result does not own a table (it was replanned, improved or freed)")
+        prm = self._params
+        if prm.get("avoid") and avoid is None:
+            raise ValueError("improve: the search ran with avoid: give the Reservations as they are now")
+        if avoid is not None and not prm.get("avoid"):
+            raise ValueError("improve: the search ran without avoid (no t0 / radius to check with)")
+        eps = float(eps)
+        if not (eps >= 0.0) or math.isinf(eps):
+            raise ValueError("improve: eps must be finite and >= 0")
+        return run_improve(self, self._multi, eps, prune, max_rounds, max_expand, avoid)
+
     def _hand_field(self, old=None, field=None, owned=False, foq=None):
         """The field of this result: from the search that made it, or handed on by the result `old` a replan consumed."""
         if old is not None:
@@ -1200,6 +1278,31 @@ class SearchResult(_Result):
         start."""
         return self._replan("replan_timed", root, advance, _one_goal(goal_row), check_edges, None, True, avoid)
 
+    def bound(self):
+        """How far the cost in hand can be from the optimum (include/mplx_anytime.h), from one pass over
+        the table that changes nothing: {"cost", "lower", "slack", "ratio", "certified", "n_open"}.  lower =
+        max(0, min(L_min, g_max, cut) - slack) with L_min the smallest g + h among the open nodes and cut what an
+        improve(prune=True) closed open nodes at (inf: never): after any completed round
+        some open node on an optimal path carries its optimal g, so no path that is cheaper than `cost` costs less than
+        `lower` -- the optimum is at least min(cost, lower).  ratio = cost / lower: cost <= ratio * optimum; a ratio
+        <= 1 proves the cost optimal (up to slack).  certified False (priors, "robust" on a goal box): h is no lower
+        bound, lower is still reported and ratio is nan.  Not valid on a table with a status bit (the call raises), nor
+        after a replan that was interrupted before its forced chunks finished."""
+        return self._bound()[0]
+
+    def improve(self, eps, prune=True, max_rounds=None, max_expand=None, avoid=None):
+        """Searches on with another eps on the tree this search has paid for (include/mplx_anytime.h):
+        every key of the table is recomputed as g + eps * h (OpenSet.rekey), then the loop of EnvMap.search finishes.
+        Nothing is re-rooted and no node is expanded for its own sake: a closed node is expanded again only if its g
+        falls (the push re-opens it).  prune: of a query that is FOUND and certified (bound()) the open nodes with
+        g + h >= cost + slack are closed by the re-key -- none of them can lead below the cost in hand; False closes
+        nothing.  max_rounds / max_expand: limits of this call alone (None: none); rounds and expanded of the new
+        result count on from this one's.  The field, priors, heuristic mode, best, wait / park_goal and time keys of the
+        search stay; a stale field is an error of the re-key (replan rebuilds one).  avoid: the Reservations as they are
+        now, required iff the search ran with avoid.  A later replan / replan_timed uses the new eps.  Returns a new
+        result that owns the table and the open set; this one no longer does."""
+        return self._improve(eps, prune, max_rounds, max_expand, avoid)
+
     def full_path(self):
         """(start_state, actions) from the ORIGINAL start (t = 0): the actions executed up to the root of every
         replan_timed so far, then those of path().  This is the chain conflicts() and a reservation fill take with the
@@ -1254,6 +1357,16 @@ class MultiSearchResult(_Result):
         query without a path keeps its seed), goal_rows [Q][4D+2] or None.  Returns a new MultiSearchResult that owns
         the table and the open set; this one no longer does."""
         return self._replan("replan_timed", roots, advance, goal_rows, check_edges, None, True, avoid)
+
+    def bound(self):
+        """SearchResult.bound per query: a list of Q dicts."""
+        return self._bound()
+
+    def improve(self, eps, prune=True, max_rounds=None, max_expand=None, avoid=None):
+        """SearchResult.improve for Q queries at once: one re-key and the shared rounds of search_many; a query is pruned
+        by its own cost.  Returns a new MultiSearchResult that owns the table and the open set; this one no longer
+        does."""
+        return self._improve(eps, prune, max_rounds, max_expand, avoid)
 
     def full_path(self, q):
         """SearchResult.full_path of query q."""
@@ -1589,3 +1702,74 @@ def run_replan(old, multi, roots, goal_rows, check_edges, priors=None, timed=Fal
         new._hand_field(old)
         old.table = old.open = None  # the new result owns them
         return new
+
+
+def run_improve(old, multi, eps, prune, max_rounds, max_expand, avoid=None):
+    """SearchResult.improve / MultiSearchResult.improve: re-key the open set of `old` for `eps` (pruning what cannot beat
+    the costs in hand), then the loop of the search with the new eps.  No rebase, no forced round: the calls of a round
+    are those of the search."""
+    env, prm, tab, opn = old._env, old._params, old.table, old.open
+    if avoid is not None:
+        avoid.set_queries(prm["t0"], prm["radius"], prm["ignore_group"])
+    env._flush()
+    Q = tab.n_queries
+    if not multi:
+        env.set_goal(prm["goal_rows"][0], **prm["goal_kw"])  # (the context's goal may have been moved since the search)
+    cut = None
+    if prune:
+        slack, cert = old._certificate()
+        found, cost = old._per_query("found"), old._per_query("cost")
+        cut = [cost[q] + slack[q] if (found[q] and cert[q]) else math.inf for q in range(Q)]
+    rounds, expanded, total = list(old._per_query("rounds")), list(old._per_query("expanded")), old.total_rounds
+    if not multi:
+        rounds = [total]
+    prm = dict(prm, eps=eps)  # what a later replan runs with; the limits below are this call's alone
+    run = dict(prm, max_rounds=None if max_rounds is None else total + int(max_rounds),
+               max_expand=None if max_expand is None else sum(expanded) + int(max_expand))
+    with contextlib.ExitStack() as always:
+        scratch = _own(always, _Scratch())
+        sel, imp = (scratch.add(TableFrontier(env, c)) for c in (prm["fcap"], prm["capacity"]))
+        lists = scratch.add(env.alloc_lists(prm["fcap"], want_state=True, stride=prm["lists_stride"]))
+        try:
+            info = opn.rekey(eps, cut=cut)
+        except _abi.MplxError as e:
+            if e.code == _abi.ERR_STATE:
+                _table_check(tab, "improve", "before the re-key")
+            raise
+        status, res, total = _search_loop(env, "improve", multi, tab, opn, sel, imp, lists, run, total, rounds, expanded, avoid)
+        new = type(old)._of(status, res, tab, opn, rounds, expanded, total, env, prm)
+        new.rebase_info, new._executed, new.rekey_info = old.rebase_info, old._executed, info
+        before = old._pruned_at or [math.inf] * Q
+        new._pruned_at = [min(a, b) for a, b in zip(before, cut or before)]
+        new._hand_field(old)
+        old.table = old.open = None  # the new result owns them
+        return new
+
+
+def anytime(result, schedule, max_expand=None, avoid=None):
+    """An anytime schedule on one tree: improve `result` (a SearchResult or MultiSearchResult, made with
+    any eps) through the eps values of `schedule`, which must not increase.  Stops early once every certified query
+    has ratio <= 1 (its cost is proven optimal; with no certified query the schedule runs to its end), or when max_expand
+    expansions (all stages and queries together) are spent.  avoid: as improve.  Returns (final_result, stages): per stage
+    {"eps", "status", "cost", "lower", "ratio", "certified", "rounds", "expanded"}, each but eps a list per query;
+    rounds / expanded are those of the stage alone.  `result` is consumed by the first stage, as improve consumes it."""
+    sched = [float(e) for e in schedule]
+    if any(b > a for a, b in zip(sched, sched[1:])):
+        raise ValueError("anytime: the schedule must be non-increasing")
+    stages, spent = [], 0
+    for eps in sched:
+        if max_expand is not None and spent >= max_expand:
+            break
+        r0, e0 = list(result._per_query("rounds")), list(result._per_query("expanded"))
+        result = result.improve(eps, max_expand=None if max_expand is None else max_expand - spent, avoid=avoid)
+        b = result._bound()
+        r1, e1 = result._per_query("rounds"), result._per_query("expanded")
+        spent += sum(e1) - sum(e0)
+        stages.append({"eps": eps, "status": list(result._per_query("status")), "cost": [x["cost"] for x in b],
+                       "lower": [x["lower"] for x in b], "ratio": [x["ratio"] for x in b],
+                       "certified": [x["certified"] for x in b],
+                       "rounds": [a - c for a, c in zip(r1, r0)], "expanded": [a - c for a, c in zip(e1, e0)]})
+        cert = [x for x in b if x["certified"]]
+        if cert and all(x["ratio"] <= 1.0 for x in cert):
+            break
+    return result, stages
