@@ -110,6 +110,12 @@ FIELD_MAX_BYTES = 1 << 30
 # ... and the ones include/mplx_heur.h declares (the dynamics-aware heuristic: batches of states, the push of an open set)
 HEUR_SYMBOLS = ["mplx_heur_eval", "mplx_heur_eval_device", "mplx_open_set_heur", "mplx_planner_set_heur_dynamics"]
 HEUR_DEFAULT, HEUR_REFERENCE, HEUR_ROBUST = 0, 1, 2
+# ... and the ones include/mplx_body.h declares (an ellipsoid body against a point cloud: lists and trajectory sets)
+BODY_SYMBOLS = ["mplx_body_create", "mplx_body_destroy", "mplx_body_set_shape", "mplx_body_fill", "mplx_body_fill_device",
+                "mplx_body_fill_map", "mplx_body_shape", "mplx_body_cells", "mplx_body_check_device",
+                "mplx_body_check_poly_device", "mplx_body_check_poly"]
+BODY_MAX_BYTES = 1 << 30
+BODY_BAD_ATTITUDE = 0x7fffffff
 HEUR_BISECT = 56
 
 
@@ -265,6 +271,14 @@ class ReservePolyIn(C.Structure):
 
 
 class ReservePolyOut(C.Structure):
+    _fields_ = [("hit", C.c_void_p), ("status", C.c_void_p), ("n_hit", C.c_void_p)]
+
+
+class BodyPolyIn(C.Structure):
+    _fields_ = [("step", C.c_double)]
+
+
+class BodyPolyOut(C.Structure):
     _fields_ = [("hit", C.c_void_p), ("status", C.c_void_p), ("n_hit", C.c_void_p)]
 
 
@@ -586,8 +600,19 @@ def lib():
         "mplx_planner_set_heur_dynamics": (C.c_int, [vp, i32]),
         "mplx_table_set_time_keys": (C.c_int, [vp, i32]),
         "mplx_time_key": (C.c_uint64, [C.c_uint64, dbl]),
+        "mplx_body_create": (C.c_int, [vp, C.POINTER(vp)]),
+        "mplx_body_destroy": (None, [vp]),
+        "mplx_body_set_shape": (C.c_int, [vp, dbl, dbl, dbl, dbl]),
+        "mplx_body_fill": (C.c_int, [vp, vp, i64]),
+        "mplx_body_fill_device": (C.c_int, [vp, vp, i64]),
+        "mplx_body_fill_map": (C.c_int, [vp, C.c_int]),
+        "mplx_body_shape": (C.c_int, [vp, C.POINTER(i64), C.POINTER(i64), vp, C.POINTER(dbl), vp, C.POINTER(i64)]),
+        "mplx_body_cells": (C.c_int, [vp, vp, vp]),
+        "mplx_body_check_device": (C.c_int, [vp, C.POINTER(SuccLists), i64, vp, vp, i64, i32, vp, vp]),
+        "mplx_body_check_poly_device": (C.c_int, [vp, vp, C.POINTER(BodyPolyIn), C.POINTER(BodyPolyOut)]),
+        "mplx_body_check_poly": (C.c_int, [vp, vp, C.POINTER(BodyPolyIn), C.POINTER(BodyPolyOut)]),
     }
-    for name in SYMBOLS + MAP_UTIL_SYMBOLS + ROLLOUT_SYMBOLS + RAY_SYMBOLS + TRAJ_SYMBOLS + TABLE_SYMBOLS + OPEN_SYMBOLS + MULTI_SYMBOLS + BEST_SYMBOLS + ANYTIME_SYMBOLS + REPLAN_SYMBOLS + PRIOR_SYMBOLS + SOLVE_SYMBOLS + LIMITS_SYMBOLS + SCALE_SYMBOLS + CONFLICT_SYMBOLS + RESERVE_SYMBOLS + RESERVE_POLY_SYMBOLS + WAIT_SYMBOLS + REPLAN_TIMED_SYMBOLS + FIELD_SYMBOLS + HEUR_SYMBOLS:
+    for name in SYMBOLS + MAP_UTIL_SYMBOLS + ROLLOUT_SYMBOLS + RAY_SYMBOLS + TRAJ_SYMBOLS + TABLE_SYMBOLS + OPEN_SYMBOLS + MULTI_SYMBOLS + BEST_SYMBOLS + ANYTIME_SYMBOLS + REPLAN_SYMBOLS + PRIOR_SYMBOLS + SOLVE_SYMBOLS + LIMITS_SYMBOLS + SCALE_SYMBOLS + CONFLICT_SYMBOLS + RESERVE_SYMBOLS + RESERVE_POLY_SYMBOLS + WAIT_SYMBOLS + REPLAN_TIMED_SYMBOLS + FIELD_SYMBOLS + HEUR_SYMBOLS + BODY_SYMBOLS:
         fn = getattr(L, name)  # AttributeError if the library does not export it
         fn.restype, fn.argtypes = sig[name]
     _lib = L

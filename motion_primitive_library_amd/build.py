@@ -14,8 +14,8 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(CSRC, "libmplx.so")
-SOURCES = ["expand_kernel.hip", "expand_tile_kernel.hip", "expand_grid_kernel.hip", "expand_lex_kernel.hip", "expand_pair_kernel.hip", "map_prep_kernel.hip", "map_prep_api.cpp", "map_util_kernel.hip", "map_util_api.cpp", "rollout_kernel.hip", "rollout_api.cpp", "ray_kernel.hip", "ray_api.cpp", "traj_kernel.hip", "traj_api.cpp", "solve_kernel.hip", "solve_api.cpp", "limits_kernel.hip", "limits_api.cpp", "scale_kernel.hip", "scale_api.cpp", "conflict_kernel.hip", "conflict_api.cpp", "reserve_kernel.hip", "reserve_api.cpp", "reserve_poly_kernel.hip", "reserve_poly_api.cpp", "wait_kernel.hip", "wait_api.cpp", "table_kernel.hip", "table_api.cpp", "open_kernel.hip", "open_best_kernel.hip", "open_rekey_kernel.hip", "open_api.cpp", "field_kernel.hip", "field_api.cpp", "heur_kernel.hip", "heur_api.cpp", "replan_kernel.hip", "replan_api.cpp", "post_kernel.hip", "identity_kernel.hip", "post_api.cpp", "edge_kernel.hip", "edge_api.cpp", "mplx_api.cpp", "lists_route.cpp", "yaw_pin.cpp", "lists_host.cpp", "planner_capi.cpp", "pack_kernel.hip", "store_model_kernel.hip", "lists_copy_api.cpp", "pack_api.cpp", "comm_api.cpp"]
-HEADERS = ["mplx_internal.h", "mplx_ctx.h", "mplx_stage.h", "mplx_device_common.h", "mplx_pair_device.h", "mplx_grid_common.h", "mplx_poly.h", "mplx_traj_device.h", "mplx_limits_math.h", "mplx_scale_math.h", "mplx_heur_math.h", "mplx_open_heur.h", "host_planner.hpp", "host_lpastar.hpp", os.path.join("..", "..", "include", "mplx.h"), os.path.join("..", "..", "include", "mplx_debug.h"), os.path.join("..", "..", "include", "mplx_map_util.h"), os.path.join("..", "..", "include", "mplx_rollout.h"), os.path.join("..", "..", "include", "mplx_ray.h"), os.path.join("..", "..", "include", "mplx_traj.h"), os.path.join("..", "..", "include", "mplx_table.h"), os.path.join("..", "..", "include", "mplx_open.h"), os.path.join("..", "..", "include", "mplx_multi.h"), os.path.join("..", "..", "include", "mplx_replan.h"), os.path.join("..", "..", "include", "mplx_replan_timed.h"), os.path.join("..", "..", "include", "mplx_prior.h"), os.path.join("..", "..", "include", "mplx_solve.h"), os.path.join("..", "..", "include", "mplx_limits.h"), os.path.join("..", "..", "include", "mplx_scale.h"), os.path.join("..", "..", "include", "mplx_conflict.h"), os.path.join("..", "..", "include", "mplx_reserve.h"), os.path.join("..", "..", "include", "mplx_reserve_poly.h"), os.path.join("..", "..", "include", "mplx_wait.h"), os.path.join("..", "..", "include", "mplx_field.h"), os.path.join("..", "..", "include", "mplx_heur.h"), os.path.join("..", "..", "include", "mplx_best.h"), os.path.join("..", "..", "include", "mplx_anytime.h")]
+SOURCES = ["expand_kernel.hip", "expand_tile_kernel.hip", "expand_grid_kernel.hip", "expand_lex_kernel.hip", "expand_pair_kernel.hip", "map_prep_kernel.hip", "map_prep_api.cpp", "map_util_kernel.hip", "map_util_api.cpp", "rollout_kernel.hip", "rollout_api.cpp", "ray_kernel.hip", "ray_api.cpp", "traj_kernel.hip", "traj_api.cpp", "solve_kernel.hip", "solve_api.cpp", "limits_kernel.hip", "limits_api.cpp", "scale_kernel.hip", "scale_api.cpp", "conflict_kernel.hip", "conflict_api.cpp", "reserve_kernel.hip", "reserve_api.cpp", "reserve_poly_kernel.hip", "reserve_poly_api.cpp", "body_kernel.hip", "body_api.cpp", "wait_kernel.hip", "wait_api.cpp", "table_kernel.hip", "table_api.cpp", "open_kernel.hip", "open_best_kernel.hip", "open_rekey_kernel.hip", "open_api.cpp", "field_kernel.hip", "field_api.cpp", "heur_kernel.hip", "heur_api.cpp", "replan_kernel.hip", "replan_api.cpp", "post_kernel.hip", "identity_kernel.hip", "post_api.cpp", "edge_kernel.hip", "edge_api.cpp", "mplx_api.cpp", "lists_route.cpp", "yaw_pin.cpp", "lists_host.cpp", "planner_capi.cpp", "pack_kernel.hip", "store_model_kernel.hip", "lists_copy_api.cpp", "pack_api.cpp", "comm_api.cpp"]
+HEADERS = ["mplx_internal.h", "mplx_ctx.h", "mplx_stage.h", "mplx_device_common.h", "mplx_pair_device.h", "mplx_grid_common.h", "mplx_poly.h", "mplx_traj_device.h", "mplx_limits_math.h", "mplx_scale_math.h", "mplx_heur_math.h", "mplx_open_heur.h", "mplx_body_args.h", "host_planner.hpp", "host_lpastar.hpp", os.path.join("..", "..", "include", "mplx.h"), os.path.join("..", "..", "include", "mplx_debug.h"), os.path.join("..", "..", "include", "mplx_map_util.h"), os.path.join("..", "..", "include", "mplx_rollout.h"), os.path.join("..", "..", "include", "mplx_ray.h"), os.path.join("..", "..", "include", "mplx_traj.h"), os.path.join("..", "..", "include", "mplx_table.h"), os.path.join("..", "..", "include", "mplx_open.h"), os.path.join("..", "..", "include", "mplx_multi.h"), os.path.join("..", "..", "include", "mplx_replan.h"), os.path.join("..", "..", "include", "mplx_replan_timed.h"), os.path.join("..", "..", "include", "mplx_prior.h"), os.path.join("..", "..", "include", "mplx_solve.h"), os.path.join("..", "..", "include", "mplx_limits.h"), os.path.join("..", "..", "include", "mplx_scale.h"), os.path.join("..", "..", "include", "mplx_conflict.h"), os.path.join("..", "..", "include", "mplx_reserve.h"), os.path.join("..", "..", "include", "mplx_reserve_poly.h"), os.path.join("..", "..", "include", "mplx_wait.h"), os.path.join("..", "..", "include", "mplx_field.h"), os.path.join("..", "..", "include", "mplx_heur.h"), os.path.join("..", "..", "include", "mplx_best.h"), os.path.join("..", "..", "include", "mplx_anytime.h"), os.path.join("..", "..", "include", "mplx_body.h")]
 ARCH = "gfx950"
 
 

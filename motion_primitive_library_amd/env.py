@@ -1400,7 +1400,8 @@ class EnvMap:
     def search(self, start, goal_row, eps=1.0, delta=None, g_max=float("inf"), max_rounds=None, max_expand=None,
                capacity=1 << 16, max_frontier=None, lists_stride=None, sight=True, tol_pos=0.5, tol_vel=-1.0, tol_acc=-1.0,
                tol_yaw=-1.0, w=None, v_max=None, start_g=0.0, prior=None, avoid=None, t0=0.0, radius=None, ignore_group=-1,
-               time_keys=None, wait=False, park_goal=False, field=None, field_of_query=None, heur=None, best=None):
+               time_keys=None, wait=False, park_goal=False, field=None, field_of_query=None, heur=None, best=None,
+               body=None, body_samples=4):
         """A goal-directed search from `start` (one 4D+2 state) to the goal region of `goal_row` that stays on the
         device: set_goal, seed, push; then per round one select (the round's only read-back, 48 bytes), and while it
         selects: expand the selection, relax its lists against the table, push the nodes whose g fell.  Keys are
@@ -1439,19 +1440,27 @@ class EnvMap:
         the open nodes with f <= f_min + delta (ties by id; include/mplx_best.h), so delta=inf with best=k is a priority
         queue that hands out k nodes a round.  It does nothing to optimality: the stopping rule is unchanged, the goal is
         announced once no open key is below the best goal-region node's.  Without max_frontier the selection frontier and
-        the lists are allocated for min(capacity, best) nodes.  A replan keeps it."""
+        the lists are allocated for min(capacity, best) nodes.  A replan keeps it.
+        body: None -- the calls of a search without the argument.  A search.Body (alloc_body, filled): every round checks
+        its lists against the body's cloud after the wait edges and the reservation check and before the relax
+        (include/mplx_body.h): an edge along which the ellipsoid, tilted as the edge's acceleration tilts it, touches a
+        point at one of body_samples + 1 samples, or has a bad attitude there, costs +inf.  One body serves all queries;
+        start and goal are checked only through their edges; the cloud must not be filled again while the result lives
+        (improve and anytime raise if it was); replan / replan_timed of such a result raise; shortcut and smooth are not
+        body-checked (Body.check_poly reports)."""
         from .search import run_search
         return run_search(self, start, goal_row, prior=prior, eps=eps, delta=delta, g_max=g_max, max_rounds=max_rounds,
                           max_expand=max_expand, capacity=capacity, max_frontier=max_frontier, lists_stride=lists_stride,
                           sight=sight, tol_pos=tol_pos, tol_vel=tol_vel, tol_acc=tol_acc, tol_yaw=tol_yaw, w=w, v_max=v_max,
                           start_g=start_g, avoid=avoid, t0=t0, radius=radius, ignore_group=ignore_group, time_keys=time_keys,
-                          wait=wait, park_goal=park_goal, field=field, field_of_query=field_of_query, heur=heur, best=best)
+                          wait=wait, park_goal=park_goal, field=field, field_of_query=field_of_query, heur=heur, best=best,
+                          body=body, body_samples=body_samples)
 
     def search_many(self, starts, goal_rows, eps=1.0, delta=None, g_max=float("inf"), max_rounds=None, max_expand=None,
                     capacity=1 << 16, max_frontier=None, lists_stride=None, sight=True, tol_pos=0.5, tol_vel=-1.0,
                     tol_acc=-1.0, tol_yaw=-1.0, w=None, v_max=None, start_g=0.0, priors=None, avoid=None, t0=0.0, radius=None,
                     ignore_group=-1, time_keys=None, wait=False, park_goal=False, field=None, field_of_query=None, heur=None,
-                    best=None):
+                    best=None, body=None, body_samples=4):
         """Q searches of EnvMap.search at once, sharing every launch of a round (include/mplx_multi.h): starts
         [4D+2][Q], goal_rows [Q][4D+2], query q from starts[:, q] to the goal region of goal_rows[q].  One table of
         `capacity` nodes and one open set hold all of them; a round selects, expands, relaxes and pushes the union of
@@ -1467,14 +1476,15 @@ class EnvMap:
         heur: as EnvMap.search takes it; every query's own goal is the one its rows are measured against.
         best: as EnvMap.search takes it, per query: every query selects its own k smallest keys, and without max_frontier
         the selection frontier and the lists are allocated for min(capacity, best * Q) nodes, which no round can exceed.
-        Optimality is untouched: every query's stopping rule is the one it had."""
+        Optimality is untouched: every query's stopping rule is the one it had.
+        body, body_samples: as EnvMap.search takes them; one body and one check serve all queries."""
         from .search import run_search_many
         return run_search_many(self, starts, goal_rows, priors=priors, eps=eps, delta=delta, g_max=g_max, max_rounds=max_rounds,
                                max_expand=max_expand, capacity=capacity, max_frontier=max_frontier, lists_stride=lists_stride,
                                sight=sight, tol_pos=tol_pos, tol_vel=tol_vel, tol_acc=tol_acc, tol_yaw=tol_yaw, w=w,
                                v_max=v_max, start_g=start_g, avoid=avoid, t0=t0, radius=radius, ignore_group=ignore_group,
                                time_keys=time_keys, wait=wait, park_goal=park_goal, field=field, field_of_query=field_of_query,
-                               heur=heur, best=best)
+                               heur=heur, best=best, body=body, body_samples=body_samples)
 
     def _heur_goal(self, goal_row, goal_control, w, v_max):
         goal = np.ascontiguousarray(goal_row, dtype=np.float64)
@@ -1522,6 +1532,14 @@ class EnvMap:
         max(t0 + total), as conflicts() does.  The `avoid` of search / search_many."""
         from .search import Reservations
         return Reservations(self, trajs, step, n_steps, t0, radius, group, park)
+
+    def alloc_body(self, r, h, g=9.81, tilt_max=None):
+        """An ellipsoid body and its obstacle point cloud on the device (include/mplx_body.h; search.Body): radius r across
+        the thrust axis, half-height h along it, the axis along acc + g e_z, tilt_max the largest tilt in radians (None:
+        any attitude whose thrust points up).  fill() / fill_resident() / fill_map() give it the cloud.  The `body` of
+        search / search_many."""
+        from .search import Body
+        return Body(self, r, h, g, tilt_max)
 
     def anytime(self, result, schedule, max_expand=None, avoid=None):
         """search.anytime: improve a SearchResult / MultiSearchResult of this EnvMap through a non-increasing schedule of eps

@@ -775,6 +775,124 @@ class Reservations:
             pass
 
 
+class Body:
+    """mplx_body of an EnvMap's context (include/mplx_body.h; EnvMap.alloc_body): the robot as an ellipsoid of radius r
+    across the thrust axis and half-height h along it, whose axis follows acc + g e_z, and an obstacle point cloud
+    binned on the device; the check of successor lists and of trajectory sets against it.  tilt_max: the largest tilt
+    in radians, in (0, pi / 2] (None: pi / 2 -- only a thrust that points down or vanishes is a bad attitude); its
+    cosine is taken here, once.  The `body` of EnvMap.search / search_many.  free() it before the EnvMap is closed."""
+
+    def __init__(self, env, r, h, g=9.81, tilt_max=None):
+        self._env, self._body = env, None
+        b = C.c_void_p()
+        _abi.check(env._ctx, _abi.lib().mplx_body_create(env._ctx, C.byref(b)))
+        self._body = b
+        try:
+            self.set_shape(r, h, g, tilt_max)
+        except Exception:
+            self.free()
+            raise
+
+    def _check(self, rc):
+        _abi.check(self._env._ctx, rc)
+
+    def set_shape(self, r, h, g=9.81, tilt_max=None, min_cos_tilt=None):
+        """mplx_body_set_shape; min_cos_tilt: the cosine itself instead of tilt_max (tests give representable values).  A
+        cloud that is in place is kept and binned again."""
+        if min_cos_tilt is None:
+            min_cos_tilt = 0.0 if tilt_max is None else max(0.0, math.cos(float(tilt_max)))
+        self._check(_abi.lib().mplx_body_set_shape(self._body, float(r), float(h), float(g), float(min_cos_tilt)))
+        self.r, self.h, self.g, self.min_cos_tilt = float(r), float(h), float(g), float(min_cos_tilt)
+
+    def fill(self, points):
+        """mplx_body_fill: points [n][D] (host; synchronous).  A point with a coordinate that is not finite never hits."""
+        self._env._flush()
+        pts = np.ascontiguousarray(np.asarray(points, dtype=np.float64).reshape(-1, self._env.dim))
+        self._check(_abi.lib().mplx_body_fill(self._body, pts.ctypes.data if len(pts) else None, len(pts)))
+
+    def fill_resident(self, ptr, n):
+        """mplx_body_fill_device: n points [n][D] in device memory (a buffer or an address).  Asynchronous."""
+        self._env._flush()
+        self._check(_abi.lib().mplx_body_fill_device(self._body, _device_ptr(ptr) if n else None, int(n)))
+
+    def fill_map(self, kind=_abi.CELL_OCCUPIED):
+        """mplx_body_fill_map: the cells of class `kind` of the map the EnvMap holds now, numbered as EnvMap's voxel
+        cloud of that class; the points stay on the device."""
+        self._env._flush()
+        self._check(_abi.lib().mplx_body_fill_map(self._body, int(kind)))
+
+    def shape(self):
+        """{"n", "n_excluded", "cells" [3], "edge", "origin" [3], "generation"} (mplx_body_shape; synchronises)."""
+        n, ne, gen, edge = C.c_int64(), C.c_int64(), C.c_int64(), C.c_double()
+        cells, origin = np.zeros(3, np.int32), np.zeros(3)
+        self._check(_abi.lib().mplx_body_shape(self._body, C.byref(n), C.byref(ne), cells.ctypes.data, C.byref(edge),
+                                               origin.ctypes.data, C.byref(gen)))
+        return {"n": n.value, "n_excluded": ne.value, "cells": cells, "edge": edge.value, "origin": origin,
+                "generation": gen.value}
+
+    @property
+    def generation(self):
+        return self.shape()["generation"]
+
+    def cells(self):
+        """(cell_of_point [n] int32, -1 excluded; cell_start [cells + 1] int32): the binning, a download for tests."""
+        sh = self.shape()
+        cop, start = np.zeros(sh["n"], np.int32), np.zeros(int(np.prod(sh["cells"].astype(np.int64))) + 1, np.int32)
+        self._check(_abi.lib().mplx_body_cells(self._body, cop.ctypes.data if len(cop) else None, start.ctypes.data))
+        return cop, start
+
+    def check(self, frontier, lists, n, n_samp=4, hit=None, n_blocked=None):
+        """mplx_body_check_device on the lists the expansion of `frontier` (its first n rows) left: the entries along
+        which the body touches a point of the cloud at one of n_samp + 1 samples, or has a bad attitude there, get cost
+        +inf.  hit: a device buffer of lists.n_slots int64, n_blocked: one of 8 bytes that the call adds to; either may
+        be None.  Asynchronous."""
+        s = lists.c_struct()
+        self._check(_abi.lib().mplx_body_check_device(
+            self._body, C.byref(s), int(n), _device_ptr(frontier.id), int(frontier.ptr), int(frontier.n_nodes), int(n_samp),
+            None if hit is None else _device_ptr(hit), None if n_blocked is None else _device_ptr(n_blocked)))
+
+    def check_poly(self, poly, step):
+        """mplx_body_check_poly (synchronous): the K trajectories of the PolyTrajSet `poly` at the local times i * step
+        and at their ends.  Returns {"hit" [K] int64: the smallest (sample << 32 | point), (sample << 32 | 0x7fffffff)
+        for a bad attitude, -1 none; "sample", "point" [K] int32 unpacked from it, -1 where there is none; "status" [K]:
+        the set's status bits; "n_hit"}."""
+        self._env._flush()
+        poly._need()
+        K = int(poly.n)
+        i, o = _abi.BodyPolyIn(), _abi.BodyPolyOut()
+        i.step = float(step)
+        hit, status, n_hit = np.full(K, -1, np.int64), np.zeros(K, np.uint8), np.zeros(1, np.int64)
+        if K:
+            o.hit, o.status = hit.ctypes.data, status.ctypes.data
+        o.n_hit = n_hit.ctypes.data
+        self._check(_abi.lib().mplx_body_check_poly(self._body, poly._h, C.byref(i), C.byref(o)))
+        some = hit >= 0
+        return {"hit": hit, "sample": np.where(some, hit >> 32, -1).astype(np.int32),
+                "point": np.where(some, hit & 0xffffffff, -1).astype(np.int32), "status": status, "n_hit": int(n_hit[0])}
+
+    def check_poly_resident(self, poly, step, hit=None, status=None, n_hit=None):
+        """mplx_body_check_poly_device: asynchronous, on device buffers: hit [K] int64, status [K] bytes, n_hit 8 bytes
+        that the call adds to; each may be None."""
+        i, o = _abi.BodyPolyIn(), _abi.BodyPolyOut()
+        i.step = float(step)
+        for key, v in (("hit", hit), ("status", status), ("n_hit", n_hit)):
+            if v is not None:
+                setattr(o, key, _device_ptr(v))
+        self._check(_abi.lib().mplx_body_check_poly_device(self._body, poly._h, C.byref(i), C.byref(o)))
+
+    def free(self):
+        b = self._body
+        self._body = None
+        if b and self._env._ctx:
+            _abi.lib().mplx_body_destroy(b)
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
 def load_traj_rows(env, rows, control=None):
     """One PolyTrajSet from host-side trajectories of different lengths (EnvMap.load_traj): rows = [(coeff [S_k][D + 1][6],
     dts [S_k])], as ShortcutResult.segments(k) returns them; trajectory k keeps its S_k segments."""
@@ -804,6 +922,7 @@ def refine_prioritised(env, plan, step, max_hop=None, control=None):
     reported with chain_hit -2); a robot with a chain hit keeps its raw chain and is reported, not replanned
     (replan_prioritised does that); the order is not revised, and a robot refined early is only ever refined against
     the RAW trajectories of the robots after it, so it cannot use room they give up later."""
+    _no_body_plan("refine_prioritised", plan)
     R = len(plan["paths"])
     order, rad, t0, n_steps = plan["order"], np.asarray(plan["radius"], dtype=np.float64), plan["t0"], plan["n_steps"]
     chains = {r: plan["results"][r].full_path(plan["winner"][r]) for r in order if plan["paths"][r] is not None}
@@ -894,6 +1013,8 @@ def plan_prioritised(env, starts, goal_rows, step, radius, order=None, delays=(0
     conflicts take it as it is."""
     starts = np.ascontiguousarray(starts, dtype=np.float64)
     goal_rows = np.ascontiguousarray(goal_rows, dtype=np.float64)
+    if search_kw.get("body") is not None:
+        raise ValueError("plan_prioritised: " + _BODY_REFUSED)
     if best is not None:
         search_kw = dict(search_kw, best=best)
     R = starts.shape[1]
@@ -986,6 +1107,7 @@ def replan_prioritised(env, plan, now, step, radius=None, order=None, park=True,
     until the caller plans it anew.  A plan made with field=True cannot be replanned after a map edit: its results
     search with the plan's GoalField (plan["field"], the caller's to free), which the edit makes stale, and replan_timed
     then raises RuntimeError as replan() does for a caller's stale field.  After a map edit such a fleet is planned anew."""
+    _no_body_plan("replan_prioritised", plan)
     results, winner, t0 = plan["results"], list(plan["winner"]), np.array(plan["t0"], dtype=np.float64)
     R = len(results)
     order = list(plan["order"]) if order is None else [int(r) for r in order]
@@ -1083,7 +1205,10 @@ class _Result:
         planned on and the repeated states of wait edges are legal.  The set's chain_times [w_max][Q] are those t.  avoid
         (with timed): a Reservations; the result is checked against it with the t0 / radius / ignore_group the search
         ran with (Reservations.check_poly) and the dict is the set's reserve_hit -- a smoothed trajectory is NOT kept
-        clear of the reservations, only reported."""
+        clear of the reservations, only reported.
+
+        Of a search that ran with a body (EnvMap.search(body=)) this returns what it returns without one: the output is
+        NOT body-checked.  Body.check_poly(the returned set, step) reports where the smoothed body touches the cloud."""
         if not timed:
             if avoid is not None:
                 raise ValueError("smooth: avoid goes with timed=True")
@@ -1108,7 +1233,11 @@ class _Result:
         the t0 / radius / ignore_group the search ran with, on the chain full_path(q), whose clock is the original
         start's: a hop is admitted only if it stays clear of the reservations inside the table's horizon, and
         ShortcutResult.chain_hit reports a chain that no longer holds (replan_timed then).  A search that ran with avoid
-        must be shortcut with it: an untimed hop across its waits would drift into what the search waited for."""
+        must be shortcut with it: an untimed hop across its waits would drift into what the search waited for.
+
+        Of a search that ran with a body (EnvMap.search(body=)) this returns what it returns without one: a hop is tested
+        as a point against the map and the output is NOT body-checked.  Body.check_poly(result.poly, step) reports where
+        the shortcut body touches the cloud."""
         prm = self._params or {}
         if prm.get("avoid") and avoid is None:
             raise ValueError("shortcut: the search ran with avoid: give the Reservations as they are now")
@@ -1136,6 +1265,7 @@ class _Result:
     def _replan(self, who, roots, advance, goal_rows, check_edges, priors, timed=False, avoid=None):
         if self.table is None or self._params is None:
             raise RuntimeError("%s: this result does not own a table (it was replanned or freed)" % who)
+        _no_body(who, self._params)
         if timed:
             _need_timed(self._params, avoid)
         else:
@@ -1392,6 +1522,40 @@ def _no_replan(prm):
                            "(include/mplx_replan_timed.h)")
 
 
+_BODY_REFUSED = ("a search with a body (include/mplx_body.h) cannot be replanned or planned in priority order: the rebase "
+                 "does not re-test bodies; search anew")
+
+
+def _no_body(who, prm):
+    if prm is not None and prm.get("body") is not None:
+        raise RuntimeError("%s: %s" % (who, _BODY_REFUSED))
+
+
+def _no_body_plan(who, plan):
+    for r in plan.get("results") or []:
+        _no_body(who, getattr(r, "_params", None))
+
+
+def _body_setup(who, body, body_samples, prm):
+    """The `body` / `body_samples` arguments of a search: the Body every round's lists are checked against, the samples per
+    edge, the generation of its cloud (improve and anytime refuse another one)."""
+    if not isinstance(body, Body):
+        raise TypeError("%s: body must be a search.Body (EnvMap.alloc_body)" % who)
+    if int(body_samples) < 1:
+        raise ValueError("%s: body_samples must be >= 1" % who)
+    sh = body.shape()
+    if not sh["cells"].any():
+        raise ValueError("%s: the body has no cloud: fill() it first (an empty cloud is fine)" % who)
+    prm["body"], prm["body_samples"], prm["body_generation"] = body, int(body_samples), sh["generation"]
+
+
+def _body_current(who, prm):
+    body = prm.get("body")
+    if body is not None and body.generation != prm["body_generation"]:
+        raise RuntimeError("%s: the body's cloud was filled again since the search (generation %d, the search ran with %d): "
+                           "the tree was built against another cloud; search anew" % (who, body.generation, prm["body_generation"]))
+
+
 def _avoid_setup(who, avoid, time_keys, starts, Q, t0, radius, ignore_group, tab, prm, wait=False, park_goal=False):
     """The `avoid` / `time_keys` / `wait` / `park_goal` arguments of a search: checks, the queries of the reservation
     table, the table's keys."""
@@ -1432,13 +1596,16 @@ def _edges(prm, avoid):
 def _round(env, tab, opn, avoid, rows, imp, lists, n, prm, wait, park):
     """One round on the n rows of `rows` (a selection, or a chunk of the nodes a rebase kept): expand them, append the
     wait edges, check the lists against the reservations of `avoid` (the edges it blocks cost +inf, which the relax
-    skips), relax the lists against the table, push the nodes whose g fell, veto the goal nodes the robot could not stay
-    at.  With avoid None and wait and park off these are the calls of a search without them."""
+    skips), check them against the cloud of prm["body"] (include/mplx_body.h: the same +inf), relax the lists against the
+    table, push the nodes whose g fell, veto the goal nodes the robot could not stay at.  With avoid None, wait and park
+    off and no body these are the calls of a search without them."""
     env.expand_lists_resident(rows, lists, n_nodes=n)
     if wait:
         _add_waits(env, avoid, rows, lists, n)
     if avoid is not None:
         avoid.check(rows, lists, n, table=tab)
+    if prm.get("body") is not None:
+        prm["body"].check(rows, lists, n, prm["body_samples"])
     tab.relax(lists, rows.id, rows.g, prm["g_max"], frontier=imp, n_nodes=n, want_count=False)
     opn.push(imp, n_max=n * lists.stride, eps=prm["eps"], sight=prm["sight"])
     if park:
@@ -1580,6 +1747,8 @@ def _run(env, multi, starts, goal_rows, opts):
         if avoid is not None or opts["time_keys"] or opts["wait"] or park_goal:
             _avoid_setup(who, avoid, opts["time_keys"], starts, Q, opts["t0"], opts["radius"], opts["ignore_group"], tab, prm,
                          opts["wait"], park_goal)
+        if opts.get("body") is not None:
+            _body_setup(who, opts["body"], opts.get("body_samples", 4), prm)
         opn = _own(owned, OpenSet(env, tab))
         if prm["own_goals"]:
             opn.set_goals(goal_rows, **prm["goal_kw"])
@@ -1709,6 +1878,7 @@ def run_improve(old, multi, eps, prune, max_rounds, max_expand, avoid=None):
     the costs in hand), then the loop of the search with the new eps.  No rebase, no forced round: the calls of a round
     are those of the search."""
     env, prm, tab, opn = old._env, old._params, old.table, old.open
+    _body_current("improve", prm)
     if avoid is not None:
         avoid.set_queries(prm["t0"], prm["radius"], prm["ignore_group"])
     env._flush()
